@@ -2,16 +2,20 @@
 """Headline benchmark: samples/s of the full multimodal training step (forward + backward + Adam,
 + RCCL gradient all-reduce when N > 1) on synthetic ECG batches, bf16 trunks, per-GPU batch 256.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N > 1: launched by torch.distributed.run, one rank per GPU; weak scaling: 256 samples per GPU)
 
-Prints ONE JSON line on rank 0 with the driver's fields plus
+Prints ONE JSON line on rank 0 with the driver's fields (value, ms_per_step = host time of one timed step).
+A plain run only sets up, warms up and times the K steps.  With --full it also reports
   "roofline":     the dominant kernel class (MFMA implicit-GEMM conv) timed with HIP events on its
-                  launch stream inside the timed region, algorithmic FLOPs / time vs the dense bf16
-                  MFMA peak (2.5 PFLOP/s, /opt/skills/guides/MI355X_MICROARCH.md);
+                  launch stream inside the timed region and in an extra one-stream pass, algorithmic
+                  FLOPs / time vs the MI355X's dense bf16 MFMA peak (2.5 PFLOP/s);
   "cpu_baseline": the CPU oracle (oracle/ref_models.py, a torch-fp32 restatement of the reference
                   step) timed on this box's host cores at the reference's CPU-runnable config
                   (batch 8), rank 0 and N == 1 only.
+--dump-outputs DIR writes what the last timed step computed (rank 0) as float32 .npy files: loss.npy,
+output_<i>.npy (the model's outputs), params_sample.npy / grads_sample.npy (a fixed seeded sample of the
+updated flat parameters and their gradients) and buffers.npy (the float buffers, e.g. BatchNorm statistics).
 """
 import argparse
 import ctypes as C
@@ -90,8 +94,11 @@ def parse():
                     "lead image, dataset_image.py:67-70)")
     ap.add_argument("--freeze-encoders", action="store_true", help="train.py:35-40 faithful step: the three encoders "
                     "get no gradients (forward in train mode, backward through the heads only); not the headline number")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-prof", action="store_true", help="skip the HIP-event kernel timing")
+    ap.add_argument("--full", action="store_true", help="also measure the roofline (HIP-event kernel timing, extra "
+                    "one-stream pass) and the CPU baseline; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-prof", action="store_true", help="with --full: skip the HIP-event kernel timing")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--serialize", action="store_true", help="profiling aid: every kernel on ONE stream (no encoder / "
                     "weight-gradient stream overlap), so rocprofv3 durations are per-kernel-alone; not the headline number")
@@ -212,6 +219,30 @@ def cpu_baseline(seconds):
                       f"3x224x224 + 5000-pt + 16-dim, CE + 0.1 var_loss, Adam"}
 
 
+DUMP_SAMPLE = 1 << 20   # elements of the flat parameter / gradient buffers written by --dump-outputs (4 MB each)
+
+
+def dump_outputs(path, model, loss, out):
+    """What the caller of one training step receives: the loss, the model's outputs, the updated parameters and
+    their gradients (a fixed seeded sample of the flat buffers: they hold ~12 M elements), the updated buffers."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, t):
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+    save("loss", loss)
+    for i, o in enumerate(out if isinstance(out, (tuple, list)) else (out,)):
+        save(f"output_{i}", o)
+    flat_p, flat_g = model._ecg_flat[:2]
+    idx = np.random.default_rng(0).choice(flat_p.numel(), min(DUMP_SAMPLE, flat_p.numel()), replace=False)
+    idx = torch.from_numpy(np.sort(idx)).to(flat_p.device)
+    save("params_sample", flat_p[idx])
+    save("grads_sample", flat_g[idx])
+    bufs = [b.reshape(-1).float() for b in model.buffers() if b.is_floating_point()]
+    if bufs:
+        save("buffers", torch.cat(bufs))
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` with N > 1 and no launcher environment: start N ranks (one per GPU) with
     torch.distributed.run as a CHILD process -- before this process has touched the GPU, and never by exec --
@@ -282,12 +313,13 @@ def main():
         opt.zero_grad()
         if ddp is not None:
             ddp.prepare_backward()
-        loss = loss_fn(model(*batch), labels)
+        out = model(*batch)
+        loss = loss_fn(out, labels)
         loss.backward()
         if ddp is not None:
             ddp.reduce_gradients()
         opt.step()
-        return loss
+        return loss, out
 
     def fence():
         torch.cuda.synchronize()
@@ -302,7 +334,7 @@ def main():
             model.config.overlap_encoders = False
     for _ in range(args.warmup):
         step()
-    prof = not args.no_prof
+    prof = args.full and not args.no_prof
     fence()
     if prof:
         # in the timed region only the kernel class the roofline line is about is bracketed by events (an event
@@ -320,10 +352,12 @@ def main():
         if prof:
             lib.ecgmm_prof_pause(int(i % PROF_EVERY != 0))
             n_sampled += int(i % PROF_EVERY == 0)
-        loss = step()
+        loss, out = step()
         step_ev[i + 1].record()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss, out)
     step_ms = sorted(step_ev[i].elapsed_time(step_ev[i + 1]) for i in range(args.steps))
 
     def pct(q):
@@ -434,7 +468,7 @@ def main():
             out["config"]["frozen_encoders"] = True
         if args.serialize:
             out["config"]["serialized_streams"] = True   # profiling configuration, not the headline number
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(out) + "\n").encode())

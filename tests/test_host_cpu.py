@@ -17,7 +17,7 @@ from ecgmm.train_image_only import ImageOnlyClassifier
 from oracle import ref_models as O
 
 
-def test_state_dict_keys_and_shapes_match_reference_layout(golden_dir):
+def test_state_dict_keys_and_shapes_match_reference_layout(golden_dir, tmp_path):
     cfg = type("C16", (Config,), {"clinical_input_dim": 16})
     mine, ref = ECGMultimodalModel(cfg), O.ECGMultimodalModel(2, 16)
     sm, sr = mine.state_dict(), ref.state_dict()
@@ -29,9 +29,9 @@ def test_state_dict_keys_and_shapes_match_reference_layout(golden_dir):
     sd = {k: torch.from_numpy(v) for k, v in np.load(f"{golden_dir}/best_ptbxl_tensors.npz").items()}
     ResNet1D_SE(1, 2).load_state_dict(sd, strict=True)
     # partial loader semantics of PMB:309-322 (drops classifier.4.*)
-    torch.save(sd, "/tmp/_ptbxl_test.pth")
+    torch.save(sd, tmp_path / "ptbxl.pth")
     before = mine.signal_encoder.classifier[4].weight.clone()
-    mine.load_pretrained_signal_encoder("/tmp/_ptbxl_test.pth", load_fc=False)
+    mine.load_pretrained_signal_encoder(str(tmp_path / "ptbxl.pth"), load_fc=False)
     assert torch.equal(mine.signal_encoder.classifier[4].weight, before)
     assert torch.equal(mine.signal_encoder.initial[0].weight, sd["initial.0.weight"])
     assert list(ImageOnlyClassifier().state_dict())[0] == "image_encoder.conv1.weight"
@@ -187,7 +187,9 @@ def test_bench_gpus_flag_launches_ranks_or_fails_loudly():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    # no device visible to the child, so the refusal is the same on a GPU machine as on a CPU-only one
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["HIP_VISIBLE_DEVICES"] = "-1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2"], env=env, capture_output=True, text=True)
     assert r.returncode != 0 and "only 0 GPU(s) visible" in r.stderr and "{" not in r.stdout
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8"], env=dict(env, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"),

@@ -20,13 +20,13 @@ python3 $R/tools/roofline_traffic.py $O/pmc_fetch $O/pmc_write $O/igemm_traffic.
 # profiles/rNN_igemm_traffic.json, which bench.py reads as roofline.traffic -- the lease-side profiles/ does not come back)
 python3 $R/tools/pmc_kernels.py $O/pmc_fetch > $O/pmc_by_kernel.txt 2>&1; python3 $R/tools/pmc_kernels.py $O/pmc_write >> $O/pmc_by_kernel.txt 2>&1
 echo pmc-done
-python3 $R/bench.py > $O/bench.json 2> $O/bench.err || exit 1
-python3 $R/bench.py --workload image_only --batch 128 --no-cpu-baseline > $O/bench_cfg2.json 2>/dev/null || exit 1
-python3 $R/bench.py --workload signal12 --batch 512 --no-cpu-baseline > $O/bench_cfg5.json 2>/dev/null || exit 1
-python3 $R/bench.py --image-hw 250x2500 --batch 32 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_f2.json 2>/dev/null || exit 1
+python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
+python3 $R/bench.py --full --workload image_only --batch 128 --no-cpu-baseline > $O/bench_cfg2.json 2>/dev/null || exit 1
+python3 $R/bench.py --full --workload signal12 --batch 512 --no-cpu-baseline > $O/bench_cfg5.json 2>/dev/null || exit 1
+python3 $R/bench.py --full --image-hw 250x2500 --batch 32 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_f2.json 2>/dev/null || exit 1
 echo final-done-main
 # SURVEY 8d extras: the train.py-faithful frozen-encoder step, and exact-fp32 runs of cfg 3 / cfg 5
-python3 $R/bench.py --freeze-encoders --no-cpu-baseline > $O/bench_cfg3_frozen.json 2>/dev/null || exit 1
-python3 $R/bench.py --dtype fp32 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_cfg3_fp32.json 2>/dev/null || exit 1
-python3 $R/bench.py --workload signal12 --batch 512 --dtype fp32 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_cfg5_fp32.json 2>/dev/null || exit 1
+python3 $R/bench.py --full --freeze-encoders --no-cpu-baseline > $O/bench_cfg3_frozen.json 2>/dev/null || exit 1
+python3 $R/bench.py --full --dtype fp32 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_cfg3_fp32.json 2>/dev/null || exit 1
+python3 $R/bench.py --full --workload signal12 --batch 512 --dtype fp32 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_cfg5_fp32.json 2>/dev/null || exit 1
 echo extras-done

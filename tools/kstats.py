@@ -3,7 +3,7 @@ import csv, glob, sys
 d, steps = sys.argv[1], float(sys.argv[2]) if len(sys.argv) > 2 else 1.0
 f = glob.glob(d + "/**/*_kernel_stats.csv", recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
-# one fused-Adam launch per optimizer step: the step count of the trace (bench.py with its kernel timing on runs an extra
+# one fused-Adam launch per optimizer step: the step count of the trace (bench.py --full with its kernel timing on runs an extra
 # one-stream pass, so the command line's --steps/--warmup undercount)
 adam = [int(r["Calls"]) for r in rows if "adam_kernel" in r["Name"]]
 if adam and adam[0] != steps:
