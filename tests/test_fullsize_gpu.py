@@ -168,8 +168,9 @@ def test_stream_form_of_the_layer1_tiles_is_race_free_under_concurrent_load():
     """The stream form of the 64 -> 64 channel 3x3 tiles (conv_halo_kernel<64, 9, ., NCS1, 8, false, ST>: the K loop runs on across
     tile boundaries, the previous tile's stores and the next tile's halo / weights all retire through counted vmcnt waits) is a
     synchronisation structure of its own.  Layer 1 at batch 256 (12.25 tiles per workgroup), forward with per-workgroup statistics
-    rows and input gradient, 12 launches each while another stream streams 1 GB copies through the chip: every launch must
-    reproduce the tile-at-a-time kernel's output AND statistics rows bit for bit."""
+    rows and input gradient without and with the residual addend (conv_halo_kernel<64, 9, 2, ..., ST, AD>), 12 launches each while
+    another stream streams 1 GB copies through the chip: every launch must reproduce the tile-at-a-time kernel's output AND
+    statistics rows bit for bit."""
     lib = L.lib()
     side = torch.cuda.Stream()
     big_a = torch.empty(256 << 20, device=DEV, dtype=torch.uint8)
@@ -179,8 +180,9 @@ def test_stream_form_of_the_layer1_tiles_is_race_free_under_concurrent_load():
     n = B * 56 * 56 * 64
     x = torch.randn(n, device=DEV, generator=g).to(torch.bfloat16)
     w = (torch.randn(64 * 64 * 9, device=DEV, generator=g) * 0.05).to(torch.bfloat16)
+    add = torch.randn(n, device=DEV, generator=g).to(torch.bfloat16)      # residual addend of a block's conv1 input gradient
     try:
-        for kind in ("fwd", "dgrad"):
+        for kind in ("fwd", "dgrad", "dgrad+addend"):
             def run(on):
                 lib.ecgmm_conv_halo_stream(on)
                 y = torch.empty(n, device=DEV, dtype=torch.bfloat16)
@@ -189,7 +191,8 @@ def test_stream_form_of_the_layer1_tiles_is_race_free_under_concurrent_load():
                 if kind == "fwd":
                     L.check(lib.ecgmm_conv_fwd_wgrows(L.BF16, C.byref(d), ptr(x), ptr(w), None, ptr(y), ptr(st), C.byref(rows), 0, stream()))
                 else:
-                    L.check(lib.ecgmm_conv_bwd_data(L.BF16, C.byref(d), ptr(x), ptr(w), None, ptr(y), stream()))
+                    L.check(lib.ecgmm_conv_bwd_data(L.BF16, C.byref(d), ptr(x), ptr(w), ptr(add) if kind == "dgrad+addend" else None,
+                                                    ptr(y), stream()))
                 return y, st
             ref, ref_st = run(0)
             torch.cuda.synchronize()
