@@ -94,6 +94,22 @@ int ecgmm_stem_bwd_weight(int dtype, const float* x, const void* dy, float* dw, 
   return ecg_stem_wgrad(dtype, x, dy, dw, accumulate, ws, ws_bytes, N, Cin, H, W, R, S_(stream));
 }
 
+int ecgmm_stem_bwd_data(int dtype, const void* dy, const float* w_oihw, float* dx, int N, int Cin, int H, int W, int R,
+                        void* stream) {
+  return ecg_stem_dgrad(dtype, dy, w_oihw, dx, N, Cin, H, W, R, S_(stream));
+}
+
+int ecgmm_bn_eval_bwd(int dtype, const void* dout, const void* maskref, const float* gate, const float* addc,
+                      int rows_per_sample, const void* y, const float* coef, float* dgamma, float* dbeta, void* dy,
+                      void* dz_out, float* dbias, int64_t M, int C, float* scratch, void* stream) {
+  return ecg_bn_eval_bwd(dtype, dout, maskref, gate, addc, rows_per_sample, y, coef, dgamma, dbeta, dy, dz_out, dbias,
+                         (long)M, C, scratch, S_(stream));
+}
+int ecgmm_bn_small_eval_bwd(const float* x, const float* dy, const float* gamma, const float* save, float* dx,
+                            float* dgamma, float* dbeta, int N, int C, int accumulate, void* stream) {
+  return ecg_bn_small_eval_bwd(x, dy, gamma, save, dx, dgamma, dbeta, N, C, accumulate, S_(stream));
+}
+
 int ecgmm_col_stats_rows(int dtype, int64_t M, int C) { return ecg_bn_rows(dtype, (long)M, C); }
 int ecgmm_col_stats(int dtype, const void* x, int64_t M, int C, float* partial, void* stream) {
   int rows = 0;

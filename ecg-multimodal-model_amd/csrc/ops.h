@@ -53,6 +53,10 @@ int ecg_stem_fwd_wgrows(int dtype, const float* x, const void* wpk, const float*
 int ecg_stem_stats_only(int dtype, const float* x, const void* wpk, const float* bias, float* stats, int N, int Cin, int H,
                         int W, int R, hipStream_t stream);
 int ecg_stem_wgrad_reduce(const float* slab, float* grad, int rows, int NG, int accumulate, hipStream_t stream);
+// conv_stem_dgrad.hip: input gradient of the stem convolutions (R = 7: 7x7 / 2 / 3; R = 1: 1x7 / 2 / 3 with H = 1); dy is the
+// [N][OH][OW][64] gradient of the conv output in the compute dtype, w the fp32 OIHW master weights, dx [N][Cin][H][W] fp32
+int ecg_stem_dgrad(int dtype, const void* dy, const float* w, float* dx, int N, int Cin, int H, int W, int R,
+                   hipStream_t stream);
 // conv_stem_fused.hip: the 2-D stem by recompute (bf16, R = 7, Cin <= 3): conv -> bn -> relu -> max-pool, no full-resolution tensor
 bool ecg_stem_fused_ok(int dtype, int Cin, int R);
 int ecg_stem_pool_fwd(const float* x, const void* wpk, const float* coef, void* pooled, unsigned char* idx, int N, int Cin,
@@ -95,6 +99,16 @@ int ecg_bn_bwd_tail(int dtype, const void* dout, const void* maskref, const void
                     const float* gamma, float* dgamma, float* dbeta, void* dy, const float* partial, int rows, long M,
                     int C, float* scratch, hipStream_t stream, const float* gate = nullptr, const float* addc = nullptr,
                     int rows_per_sample = 1, float* dbias = nullptr);
+// bn_eval_bwd.hip: backward of a BatchNorm whose forward used the running statistics (one pass; operands as ecg_bn_bwd;
+// scratch of ecg_bn_bwd_scratch(dtype, M, C) bytes, needed only when a parameter gradient is asked for)
+int ecg_bn_eval_bwd(int dtype, const void* dout, const void* maskref, const float* gate, const float* addc,
+                    int rows_per_sample, const void* y, const float* coef, float* dgamma, float* dbeta, void* dy,
+                    void* dz_out, float* dbias, long M, int C, float* scratch, hipStream_t stream);
+int ecg_bn_small_eval_bwd(const float* x, const float* dy, const float* gamma, const float* save, float* dx, float* dgamma,
+                          float* dbeta, int N, int C, int accumulate, hipStream_t stream);
+// gradcam.hip: relu(channel-weighted sum) / per-sample max, bilinear upsample (align_corners=False) to [N][H][W]
+int ecg_gradcam(int dtype, const void* act, const float* dpooled, float* small, float* out, int N, int Hs, int Ws, int C,
+                int H, int W, hipStream_t stream);
 int ecg_se_gate_bn(int dtype, const void* dout, const void* maskref, const void* y, const float* coef, void* dz,
                    float* dg, float* a1, float* a2, float* a3, int N, int R, int C, hipStream_t stream);
 int ecg_se_bn_nrows();   // rows ecg_se_bn_rows writes ([rows][2][C])

@@ -261,6 +261,25 @@ int bn_then_act(const R18& r, const float* stats, int rows, int C, long count, c
   return ecg_bn_act(dt, y, coef, res, rcoef, nullptr, 1, 1, out, count, C, s, relu_bits);
 }
 
+// BatchNorm backward of either forward mode: the training form (batch statistics: reduce + apply) or, behind an eval-mode
+// forward, the one-pass affine form (bn_eval_bwd.hip).  The training call is exactly the one the plan always made.
+int bn_bwd_mode(const R18& r, const void* dout, const void* maskref, const void* y, const float* coef, const float* gamma,
+                float* dgamma, float* dbeta, void* dy, void* dz_out, long M, int C, float* scratch, hipStream_t s,
+                const unsigned char* mask_bits = nullptr) {
+  if (r.d.training)
+    return ecg_bn_bwd(r.d.dtype, dout, maskref, nullptr, nullptr, 1, y, coef, gamma, dgamma, dbeta, dy, dz_out, nullptr, M,
+                      C, scratch, s, mask_bits);
+  return ecg_bn_eval_bwd(r.d.dtype, dout, maskref, nullptr, nullptr, 1, y, coef, dgamma, dbeta, dy, dz_out, nullptr, M, C,
+                         scratch, s);
+}
+
+// stage 0 up to the pooled features: d loss / d pooled [N][512] (+ the fc parameter gradients)
+int fc_bwd(const R18& r, const FwdWs& w, const BwdWs& q, const float* dfeat, const void* const* params, void* const* grads,
+           hipStream_t s) {
+  return ecg_linear_bwd(dfeat, w.pooled, P(params, r.p_fc), q.dpooled, G(grads, r.p_fc), G(grads, r.p_fc + 1), r.d.N, 512,
+                        r.d.out_dim, q.lin_ws, q.lin_bytes, s);
+}
+
 }  // namespace
 
 // Runtime switch for the side-stream weight-gradient overlap (default on; ECGMM_SIDE_WGRAD=0 disables it
@@ -426,13 +445,17 @@ extern "C" int ecgmm_resnet18_forward(const ecgmm_resnet18_desc* d, const float*
 }
 
 // stages: 0 = fc + avgpool, 1..8 = blocks 7..0, 9 = stem.  Run [stage_begin, stage_end).
-extern "C" int ecgmm_resnet18_backward(const ecgmm_resnet18_desc* d, const float* image, const float* dfeat,
-                                       const void* const* params, void* const* grads, void* ws_fwd, void* ws_bwd,
-                                       size_t ws_bwd_bytes, int stage_begin, int stage_end, void* stream_) {
-  hipStream_t s = (hipStream_t)stream_;
+// dimage (nullable): the input gradient [N][3][H][W] fp32, written by the last stage.  Behind an eval-mode forward
+// (training = 0) every BatchNorm backward is the affine form; nothing in the forward workspace is written in either mode.
+static int r18_backward(const ecgmm_resnet18_desc* d, const float* image, const float* dfeat, const void* const* params,
+                        void* const* grads, void* ws_fwd, void* ws_bwd, size_t ws_bwd_bytes, int stage_begin, int stage_end,
+                        float* dimage, hipStream_t s) {
   R18 r;
   ECG_TRY(build(d, r));
-  if (!r.d.training) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet18 bwd: forward ran in eval mode (no batch statistics saved)");
+  const bool train = r.d.training != 0;
+  if (stem_recompute(r.d.dtype) && (dimage || !train))
+    ECG_FAIL(ECGMM_ERR_SHAPE, "resnet18 bwd: %s needs the stored stem conv output; switch ecgmm_stem_recompute(0) "
+             "(ECGMM_STEM_RECOMPUTE) off", dimage ? "the input gradient" : "an eval-mode backward");
   FwdWs w;
   layout_fwd(r, ws_fwd, w);
   BwdWs q;
@@ -456,8 +479,7 @@ extern "C" int ecgmm_resnet18_backward(const ecgmm_resnet18_desc* d, const float
       g_side.doneA = g_side.doneB = g_side.doneC = nullptr;
       for (int a = 0; a < 3; ++a) g_side.done2[a][0] = g_side.done2[a][1] = nullptr;
       const BlockCfg& last = r.blk[7];
-      ECG_TRY(ecg_linear_bwd(dfeat, w.pooled, P(params, r.p_fc), q.dpooled, G(grads, r.p_fc), G(grads, r.p_fc + 1), N,
-                             512, r.d.out_dim, q.lin_ws, q.lin_bytes, s));
+      ECG_TRY(fc_bwd(r, w, q, dfeat, params, grads, s));
       const int R = last.hout * last.wout;
       ECG_TRY(ecg_bcast_rows(dt, q.dpooled, q.X[0], N, R, 512, 1.f / (float)R, s));
     } else if (st <= 8) {
@@ -491,7 +513,7 @@ extern "C" int ecgmm_resnet18_backward(const ecgmm_resnet18_desc* d, const float
       static const bool fold_on = [] { const char* e = getenv("ECGMM_DOWN_FOLD"); return !(e && e[0] == '0'); }();
       if (g_fuse_min_m < 0) { const char* e = getenv("ECGMM_BN_FUSE_MIN_M"); g_fuse_min_m = e ? atol(e) : FUSE_NEVER; }
       const long fuse_min_m = g_fuse_min_m;
-      const bool fuse_here = fuse_on && M >= fuse_min_m;
+      const bool fuse_here = train && fuse_on && M >= fuse_min_m;   // (the fused reductions are the training form's)
       if (fuse_here && i + 1 < 8 && !r.blk[i + 1].down) {
         const BlockCfg& kn = r.blk[i + 1];
         const ConvGeom gn = make_geom(N, kn.hin, kn.win, kn.cin, kn.cout, 3, 3, 1, 1, 1);
@@ -506,8 +528,9 @@ extern "C" int ecgmm_resnet18_backward(const ecgmm_resnet18_desc* d, const float
         ECG_TRY(ecg_bn_bwd_tail(dt, dcur, nullptr, b.y2, b.coef2, P(params, k.p_bn2), G(grads, k.p_bn2),
                                 G(grads, k.p_bn2 + 1), dyb, q.red2, fused2_rows, M, k.cout, q.bn_scratch, s));
       } else {
-        ECG_TRY(ecg_bn_bwd(dt, dcur, b.out, nullptr, nullptr, 1, b.y2, b.coef2, P(params, k.p_bn2), G(grads, k.p_bn2),
-                           G(grads, k.p_bn2 + 1), dyb, q.dz, nullptr, M, k.cout, q.bn_scratch, s, relu_bits_on() ? b.bits : nullptr));
+        // (the eval forward writes no mask bits: its backward re-reads `out`)
+        ECG_TRY(bn_bwd_mode(r, dcur, b.out, b.y2, b.coef2, P(params, k.p_bn2), G(grads, k.p_bn2), G(grads, k.p_bn2 + 1), dyb,
+                            q.dz, M, k.cout, q.bn_scratch, s, train && relu_bits_on() ? b.bits : nullptr));
       }
       if (G(grads, k.p_conv2)) {
         if (side) side_fork(s);
@@ -523,8 +546,8 @@ extern "C" int ecgmm_resnet18_backward(const ecgmm_resnet18_desc* d, const float
         ECG_TRY(ecg_bn_bwd_tail(dt, q.da, b.y1, b.y1, b.coef1, P(params, k.p_bn1), G(grads, k.p_bn1),
                                 G(grads, k.p_bn1 + 1), dy1b, q.red1, ea.red_rows_n, M, k.cout, q.bn_scratch, s));
       } else {
-        ECG_TRY(ecg_bn_bwd(dt, q.da, b.y1, nullptr, nullptr, 1, b.y1, b.coef1, P(params, k.p_bn1), G(grads, k.p_bn1),
-                           G(grads, k.p_bn1 + 1), dy1b, nullptr, nullptr, M, k.cout, q.bn_scratch, s));
+        ECG_TRY(bn_bwd_mode(r, q.da, b.y1, b.y1, b.coef1, P(params, k.p_bn1), G(grads, k.p_bn1), G(grads, k.p_bn1 + 1), dy1b,
+                            nullptr, M, k.cout, q.bn_scratch, s));
       }
       if (G(grads, k.p_conv1)) {
         if (side) side_fork(s);
@@ -534,9 +557,8 @@ extern "C" int ecgmm_resnet18_backward(const ecgmm_resnet18_desc* d, const float
       if (k.down) {
         ConvGeom gd = make_geom(N, k.hin, k.win, k.cin, k.cout, 1, 1, k.stride, 0, 0);
         main_wait(s, g_side.done2[2][pp]);
-        ECG_TRY(ecg_bn_bwd(dt, dzp, nullptr, nullptr, nullptr, 1, b.yd, b.coefd, P(params, k.p_dbn),
-                           G(grads, k.p_dbn), G(grads, k.p_dbn + 1), dydb, nullptr, nullptr, M, k.cout, q.bn_scratch,
-                           s));
+        ECG_TRY(bn_bwd_mode(r, dzp, nullptr, b.yd, b.coefd, P(params, k.p_dbn), G(grads, k.p_dbn), G(grads, k.p_dbn + 1), dydb,
+                            nullptr, M, k.cout, q.bn_scratch, s));
         if (G(grads, k.p_dconv)) {
           if (side) side_fork(s);
           ECG_TRY(ecg_conv_wgrad(dt, gd, in, dydb, G(grads, k.p_dconv), 0, q.wg_ws, q.wg_bytes, ws));
@@ -573,13 +595,14 @@ extern "C" int ecgmm_resnet18_backward(const ecgmm_resnet18_desc* d, const float
                                   G(grads, 0), q.stem_ws, q.stem_bytes, N, 3, r.d.H, r.d.W, s));
         continue;
       }
-      if (ecg_stem_fuse_on()) {
+      if (train && ecg_stem_fuse_on()) {
         ECG_TRY(ecg_pool_bn_bwd(dt, dp0, w.p0, w.idx0, w.y0, w.coef0, P(params, 1), G(grads, 1), G(grads, 2), q.big1,
                                 nullptr, N, r.H1, r.W1, 64, q.bn_scratch, s));
       } else {
+        // (eval: always the plain two passes -- max-pool + ReLU backward, then the affine BatchNorm backward)
         ECG_TRY(ecg_maxpool_relu_bwd(dt, dp0, w.p0, w.idx0, q.big0, N, r.H1, r.W1, 64, s));
-        ECG_TRY(ecg_bn_bwd(dt, q.big0, nullptr, nullptr, nullptr, 1, w.y0, w.coef0, P(params, 1), G(grads, 1),
-                           G(grads, 2), q.big1, nullptr, nullptr, (long)N * r.H1 * r.W1, 64, q.bn_scratch, s));
+        ECG_TRY(bn_bwd_mode(r, q.big0, nullptr, w.y0, w.coef0, P(params, 1), G(grads, 1), G(grads, 2), q.big1, nullptr,
+                            (long)N * r.H1 * r.W1, 64, q.bn_scratch, s));
       }
       if (G(grads, 0)) {
         // the last kernel of the backward stays on the caller's stream: nothing is left there to overlap it with, it
@@ -587,6 +610,8 @@ extern "C" int ecgmm_resnet18_backward(const ecgmm_resnet18_desc* d, const float
         // usually fired already (an exposed cross-stream wait costs 35-140 us here).  Own slab buffer: q.stem_ws.
         ECG_TRY(ecg_stem_wgrad(dt, image, q.big1, G(grads, 0), 0, q.stem_ws, q.stem_bytes, N, 3, r.d.H, r.d.W, 7, s));
       }
+      // the input gradient: the transposed stem convolution of the same dy0 (conv_stem_dgrad.hip)
+      if (dimage) ECG_TRY(ecg_stem_dgrad(dt, q.big1, P(params, 0), dimage, N, 3, r.d.H, r.d.W, 7, s));
     } else {
       ECG_FAIL(ECGMM_ERR_SHAPE, "resnet18 bwd: stage %d out of range", st);
     }
@@ -599,6 +624,43 @@ extern "C" int ecgmm_resnet18_backward(const ecgmm_resnet18_desc* d, const float
   }
   if (stage_end == 10) ecg_tl_mark(211, s);
   return 0;
+}
+
+extern "C" int ecgmm_resnet18_backward(const ecgmm_resnet18_desc* d, const float* image, const float* dfeat,
+                                       const void* const* params, void* const* grads, void* ws_fwd, void* ws_bwd,
+                                       size_t ws_bwd_bytes, int stage_begin, int stage_end, void* stream_) {
+  return r18_backward(d, image, dfeat, params, grads, ws_fwd, ws_bwd, ws_bwd_bytes, stage_begin, stage_end, nullptr,
+                      (hipStream_t)stream_);
+}
+
+// The same backward with the input gradient as one more output of the last stage (dimage may be null).
+extern "C" int ecgmm_resnet18_backward_dx(const ecgmm_resnet18_desc* d, const float* image, const float* dfeat,
+                                          const void* const* params, void* const* grads, void* ws_fwd, void* ws_bwd,
+                                          size_t ws_bwd_bytes, int stage_begin, int stage_end, float* dimage,
+                                          void* stream_) {
+  return r18_backward(d, image, dfeat, params, grads, ws_fwd, ws_bwd, ws_bwd_bytes, stage_begin, stage_end, dimage,
+                      (hipStream_t)stream_);
+}
+
+// Grad-CAM of layer4's output for the logits whose gradient w.r.t. the encoder output is dfeat [N][out_dim]: the fc
+// backward gives d / d pooled, the map kernels (gradcam.hip) do the rest.  cam: [N][H][W] fp32 in [0, 1].
+extern "C" int ecgmm_resnet18_gradcam(const ecgmm_resnet18_desc* d, const float* dfeat, const void* const* params,
+                                      void* ws_fwd, void* ws_bwd, size_t ws_bwd_bytes, float* cam, void* stream_) {
+  hipStream_t s = (hipStream_t)stream_;
+  R18 r;
+  ECG_TRY(build(d, r));
+  FwdWs w;
+  layout_fwd(r, ws_fwd, w);
+  BwdWs q;
+  layout_bwd(r, ws_bwd, q);
+  if (!ws_fwd || !ws_bwd || ws_bwd_bytes < q.bytes)
+    ECG_FAIL(ECGMM_ERR_WORKSPACE, "resnet18 gradcam: workspace %zu < %zu", ws_bwd_bytes, q.bytes);
+  if (!dfeat || !cam) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet18 gradcam: null operand");
+  ECG_TRY(fc_bwd(r, w, q, dfeat, params, nullptr, s));
+  const BlockCfg& last = r.blk[7];
+  // (q.X[0] holds max_act elements of the compute dtype >= N x hout x wout x 512: room for the N x hout x wout fp32 map)
+  return ecg_gradcam(r.d.dtype, w.b[7].out, q.dpooled, (float*)q.X[0], cam, r.d.N, last.hout, last.wout, 512, r.d.H, r.d.W,
+                     s);
 }
 
 // The image encoder's stem by recompute (conv_stem_fused.hip): 1 = on (bf16 only), 0 = the two-pass route with the

@@ -200,6 +200,31 @@ int bn_coef(const R1D& r, const float* stats, int rows, int C, long count, const
                           (const float*)buffers[b_bn + 1], r.d.bn_eps, coef, s);
 }
 
+// BatchNorm backward of either forward mode (operands as ecg_bn_bwd): the training form, or behind an eval-mode forward the
+// one-pass affine form (bn_eval_bwd.hip).  The training call is exactly the one the plan always made.
+int bn_bwd_mode(const R1D& r, const void* dout, const void* maskref, const float* gate, const float* addc, int rps,
+                const void* y, const float* coef, const float* gamma, float* dgamma, float* dbeta, void* dy, void* dz_out,
+                float* dbias, long M, int C, float* scratch, hipStream_t s) {
+  if (r.d.training)
+    return ecg_bn_bwd(r.d.dtype, dout, maskref, gate, addc, rps, y, coef, gamma, dgamma, dbeta, dy, dz_out, dbias, M, C,
+                      scratch, s);
+  return ecg_bn_eval_bwd(r.d.dtype, dout, maskref, gate, addc, rps, y, coef, dgamma, dbeta, dy, dz_out, dbias, M, C, scratch,
+                         s);
+}
+
+// stage 0 up to the pooled features: d loss / d pooled [N][256] (+ the classifier's parameter gradients)
+int classifier_bwd(const R1D& r, const Fwd1& w, const Bwd1& q, const float* dfeat, const void* const* params,
+                   void* const* grads, hipStream_t s) {
+  const int pc = r.p_cls, N = r.d.N;
+  const bool drop = r.d.training && r.d.dropout_p > 0.f;   // (as the forward: no dropout in eval mode)
+  ECG_TRY(ecg_linear_bwd(dfeat, drop ? w.hd : w.h1, P(params, pc + 2), q.dfeat_h, G(grads, pc + 2), G(grads, pc + 3), N, 64,
+                         r.d.num_classes, q.lin_ws, q.lin_bytes, s));
+  if (drop) ECG_TRY(ecg_dropout_bwd(q.dfeat_h, w.dmask, q.dfeat_h, (long)N * 64, r.d.dropout_p, s));
+  ECG_TRY(ecg_act_bwd(q.dfeat_h, w.h1, q.dh1, (long)N * 64, ECGMM_ACT_RELU, s));
+  return ecg_linear_bwd(q.dh1, w.pooled, P(params, pc), q.dpooled, G(grads, pc), G(grads, pc + 1), N, 256, 64, q.lin_ws,
+                        q.lin_bytes, s);
+}
+
 }  // namespace
 
 // weight-gradient side stream of this plan (side_stream.h); its own instance, see there
@@ -321,13 +346,14 @@ extern "C" int ecgmm_resnet1d_forward(const ecgmm_resnet1d_desc* d, const float*
 }
 
 // stages: 0 = classifier + avgpool, 1..3 = blocks 2..0, 4 = stem
-extern "C" int ecgmm_resnet1d_backward(const ecgmm_resnet1d_desc* d, const float* signal, const float* dfeat,
-                                       const void* const* params, void* const* grads, void* ws_fwd, void* ws_bwd,
-                                       size_t ws_bwd_bytes, int stage_begin, int stage_end, void* stream_) {
-  hipStream_t s = (hipStream_t)stream_;
+// dsignal (nullable): the input gradient [N][cin][L] fp32, written by the last stage.  Behind an eval-mode forward every
+// BatchNorm backward is the affine form (two-pass SE route); nothing in the forward workspace is written in either mode.
+static int r1d_backward(const ecgmm_resnet1d_desc* d, const float* signal, const float* dfeat, const void* const* params,
+                        void* const* grads, void* ws_fwd, void* ws_bwd, size_t ws_bwd_bytes, int stage_begin, int stage_end,
+                        float* dsignal, hipStream_t s) {
   R1D r;
   ECG_TRY(build(d, r));
-  if (!r.d.training) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet1d bwd: forward ran in eval mode (no batch statistics saved)");
+  const bool train = r.d.training != 0;
   Fwd1 w;
   layout_fwd(r, ws_fwd, w);
   Bwd1 q;
@@ -345,14 +371,7 @@ extern "C" int ecgmm_resnet1d_backward(const ecgmm_resnet1d_desc* d, const float
   for (int st = stage_begin; st < stage_end; ++st) {
     if (st == 0) {
       g_side1.doneA = g_side1.doneB = g_side1.doneC = nullptr;
-      const int pc = r.p_cls;
-      const bool drop = r.d.dropout_p > 0.f;
-      ECG_TRY(ecg_linear_bwd(dfeat, drop ? w.hd : w.h1, P(params, pc + 2), q.dfeat_h, G(grads, pc + 2),
-                             G(grads, pc + 3), N, 64, r.d.num_classes, q.lin_ws, q.lin_bytes, s));
-      if (drop) ECG_TRY(ecg_dropout_bwd(q.dfeat_h, w.dmask, q.dfeat_h, (long)N * 64, r.d.dropout_p, s));
-      ECG_TRY(ecg_act_bwd(q.dfeat_h, w.h1, q.dh1, (long)N * 64, ECGMM_ACT_RELU, s));
-      ECG_TRY(ecg_linear_bwd(q.dh1, w.pooled, P(params, pc), q.dpooled, G(grads, pc), G(grads, pc + 1), N, 256, 64,
-                             q.lin_ws, q.lin_bytes, s));
+      ECG_TRY(classifier_bwd(r, w, q, dfeat, params, grads, s));
       const int R = r.blk[2].lout;
       ECG_TRY(ecg_bcast_rows(dt, q.dpooled, q.X[0], N, R, 256, 1.f / (float)R, s));
     } else if (st <= 3) {
@@ -369,7 +388,8 @@ extern "C" int ecgmm_resnet1d_backward(const ecgmm_resnet1d_desc* d, const float
       // out = relu(bn2(y2) * g + identity); gate gradient first.  Merged form (default): this pass also stores the masked
       // gradient dz and the per-sample sums the BatchNorm-backward reduction needs, so bn2's backward below is finalize +
       // apply only -- one read of (dcur, out, y2) less per block.  ECGMM_SE_MERGE=0: the two-pass form.
-      static const bool se_merge = [] { const char* e = getenv("ECGMM_SE_MERGE"); return !(e && e[0] == '0'); }();
+      static const bool se_merge_on = [] { const char* e = getenv("ECGMM_SE_MERGE"); return !(e && e[0] == '0'); }();
+      const bool se_merge = se_merge_on && train;   // (the merged pass feeds the training form's reduction)
       if (se_merge) {
         ECG_TRY(ecg_se_gate_bn(dt, dcur, b.out, b.y2, b.coef2, q.dz, q.dg, q.sa1, q.sa2, q.sa3, N, k.lout, k.cout, s));
       } else {
@@ -393,8 +413,8 @@ extern "C" int ecgmm_resnet1d_backward(const ecgmm_resnet1d_desc* d, const float
         ECG_TRY(ecg_bn_bwd_tail(dt, q.dz, nullptr, b.y2, b.coef2, P(params, p + 6), G(grads, p + 6), G(grads, p + 7), q.dy,
                                 q.se_rows, ecg_se_bn_nrows(), M, k.cout, q.bn_scratch, s, b.g, q.dm, k.lout, G(grads, p + 5)));
       } else {
-        ECG_TRY(ecg_bn_bwd(dt, dcur, b.out, b.g, q.dm, k.lout, b.y2, b.coef2, P(params, p + 6), G(grads, p + 6),
-                           G(grads, p + 7), q.dy, q.dz, G(grads, p + 5), M, k.cout, q.bn_scratch, s));
+        ECG_TRY(bn_bwd_mode(r, dcur, b.out, b.g, q.dm, k.lout, b.y2, b.coef2, P(params, p + 6), G(grads, p + 6),
+                            G(grads, p + 7), q.dy, q.dz, G(grads, p + 5), M, k.cout, q.bn_scratch, s));
       }
       if (G(grads, p + 4)) {
         if (side) g_side1.fork(s);
@@ -403,8 +423,8 @@ extern "C" int ecgmm_resnet1d_backward(const ecgmm_resnet1d_desc* d, const float
       }
       ECG_TRY(ecg_conv_igemm(dt, 1, g2, q.dy, b.w2d, q.da, nullptr, nullptr, nullptr, 0, s));
       main_wait(s, g_side1.doneB);
-      ECG_TRY(ecg_bn_bwd(dt, q.da, b.y1 /* mask recomputed from y1 */, nullptr, nullptr, 1, b.y1, b.coef1, P(params, p + 2), G(grads, p + 2),
-                         G(grads, p + 3), q.dy1, nullptr, G(grads, p + 1), M, k.cout, q.bn_scratch, s));
+      ECG_TRY(bn_bwd_mode(r, q.da, b.y1 /* mask recomputed from y1 */, nullptr, nullptr, 1, b.y1, b.coef1, P(params, p + 2), G(grads, p + 2),
+                          G(grads, p + 3), q.dy1, nullptr, G(grads, p + 1), M, k.cout, q.bn_scratch, s));
       if (G(grads, p + 0)) {
         if (side) g_side1.fork(s);
         ECG_TRY(ecg_conv_wgrad(dt, g1, in, q.dy1, G(grads, p + 0), 0, q.wg_ws, q.wg_bytes, wst));
@@ -413,8 +433,8 @@ extern "C" int ecgmm_resnet1d_backward(const ecgmm_resnet1d_desc* d, const float
       if (k.down) {
         ConvGeom gd = make_geom(N, 1, k.lin, k.cin, k.cout, 1, 1, k.stride, 0, 0);
         main_wait(s, g_side1.doneC);
-        ECG_TRY(ecg_bn_bwd(dt, q.dz, nullptr, nullptr, nullptr, 1, b.yd, b.coefd, P(params, p + 14), G(grads, p + 14),
-                           G(grads, p + 15), q.dyd, nullptr, G(grads, p + 13), M, k.cout, q.bn_scratch, s));
+        ECG_TRY(bn_bwd_mode(r, q.dz, nullptr, nullptr, nullptr, 1, b.yd, b.coefd, P(params, p + 14), G(grads, p + 14),
+                            G(grads, p + 15), q.dyd, nullptr, G(grads, p + 13), M, k.cout, q.bn_scratch, s));
         if (G(grads, p + 12)) {
           if (side) g_side1.fork(s);
           ECG_TRY(ecg_conv_wgrad(dt, gd, in, q.dyd, G(grads, p + 12), 0, q.wg_ws, q.wg_bytes, wst));
@@ -433,20 +453,57 @@ extern "C" int ecgmm_resnet1d_backward(const ecgmm_resnet1d_desc* d, const float
       }
     } else if (st == 4) {
       const void* dp0 = q.X[3 & 1];
-      if (ecg_stem_fuse_on()) {
+      if (train && ecg_stem_fuse_on()) {
         ECG_TRY(ecg_pool_bn_bwd(dt, dp0, w.p0, w.idx0, w.y0, w.coef0, P(params, 2), G(grads, 2), G(grads, 3), q.big1,
                                 G(grads, 1), N, 1, r.L1, 64, q.bn_scratch, s));
       } else {
         ECG_TRY(ecg_maxpool_relu_bwd(dt, dp0, w.p0, w.idx0, q.big0, N, 1, r.L1, 64, s));
-        ECG_TRY(ecg_bn_bwd(dt, q.big0, nullptr, nullptr, nullptr, 1, w.y0, w.coef0, P(params, 2), G(grads, 2),
-                           G(grads, 3), q.big1, nullptr, G(grads, 1), (long)N * r.L1, 64, q.bn_scratch, s));
+        ECG_TRY(bn_bwd_mode(r, q.big0, nullptr, nullptr, nullptr, 1, w.y0, w.coef0, P(params, 2), G(grads, 2), G(grads, 3),
+                            q.big1, nullptr, G(grads, 1), (long)N * r.L1, 64, q.bn_scratch, s));
       }
       if (G(grads, 0))  // last kernel: stays on the caller's stream (own slab buffer), see plan_resnet18.hip
         ECG_TRY(ecg_stem_wgrad(dt, signal, q.big1, G(grads, 0), 0, q.stem_ws, q.stem_bytes, N, cin, 1, r.d.L, 1, s));
+      // the input gradient: the transposed stem convolution of the same dy0 (conv_stem_dgrad.hip)
+      if (dsignal) ECG_TRY(ecg_stem_dgrad(dt, q.big1, P(params, 0), dsignal, N, cin, 1, r.d.L, 1, s));
     } else {
       ECG_FAIL(ECGMM_ERR_SHAPE, "resnet1d bwd: stage %d out of range", st);
     }
   }
   if (side) ECG_TRY(g_side1.wait_on(s));  // join: everything the side stream did is ordered before the caller's next work
   return 0;
+}
+
+extern "C" int ecgmm_resnet1d_backward(const ecgmm_resnet1d_desc* d, const float* signal, const float* dfeat,
+                                       const void* const* params, void* const* grads, void* ws_fwd, void* ws_bwd,
+                                       size_t ws_bwd_bytes, int stage_begin, int stage_end, void* stream_) {
+  return r1d_backward(d, signal, dfeat, params, grads, ws_fwd, ws_bwd, ws_bwd_bytes, stage_begin, stage_end, nullptr,
+                      (hipStream_t)stream_);
+}
+
+// The same backward with the input gradient as one more output of the last stage (dsignal may be null).
+extern "C" int ecgmm_resnet1d_backward_dx(const ecgmm_resnet1d_desc* d, const float* signal, const float* dfeat,
+                                          const void* const* params, void* const* grads, void* ws_fwd, void* ws_bwd,
+                                          size_t ws_bwd_bytes, int stage_begin, int stage_end, float* dsignal,
+                                          void* stream_) {
+  return r1d_backward(d, signal, dfeat, params, grads, ws_fwd, ws_bwd, ws_bwd_bytes, stage_begin, stage_end, dsignal,
+                      (hipStream_t)stream_);
+}
+
+// Grad-CAM of the last block's output for the logits whose gradient w.r.t. the encoder output is dfeat [N][num_classes]
+// (see ecgmm_resnet18_gradcam).  cam: [N][L] fp32 in [0, 1].
+extern "C" int ecgmm_resnet1d_gradcam(const ecgmm_resnet1d_desc* d, const float* dfeat, const void* const* params,
+                                      void* ws_fwd, void* ws_bwd, size_t ws_bwd_bytes, float* cam, void* stream_) {
+  hipStream_t s = (hipStream_t)stream_;
+  R1D r;
+  ECG_TRY(build(d, r));
+  Fwd1 w;
+  layout_fwd(r, ws_fwd, w);
+  Bwd1 q;
+  layout_bwd(r, ws_bwd, q);
+  if (!ws_fwd || !ws_bwd || ws_bwd_bytes < q.bytes)
+    ECG_FAIL(ECGMM_ERR_WORKSPACE, "resnet1d gradcam: workspace %zu < %zu", ws_bwd_bytes, q.bytes);
+  if (!dfeat || !cam) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet1d gradcam: null operand");
+  ECG_TRY(classifier_bwd(r, w, q, dfeat, params, nullptr, s));
+  // (q.X[0] holds max_act elements >= N x lout x 256: room for the N x lout fp32 map)
+  return ecg_gradcam(r.d.dtype, w.b[2].out, q.dpooled, (float*)q.X[0], cam, r.d.N, 1, r.blk[2].lout, 256, 1, r.d.L, s);
 }

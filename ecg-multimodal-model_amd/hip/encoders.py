@@ -43,20 +43,27 @@ class _PlanFn(torch.autograd.Function):
         L.check(getattr(lib, spec.prefix + "_forward")(C.byref(desc), ptr(x), ptab, btab, ptr(feat), ptr(ws),
                                                         ws.numel(), stream()), spec.name + " forward")
         ctx.spec, ctx.desc, ctx.ws, ctx.x, ctx.params = spec, desc, ws, x, params
+        if spec.keep_last:   # (ecgmm/explain.py: Grad-CAM reads the last activation map out of the forward workspace)
+            spec.last = (desc, ws, x, params)
         return feat
 
     @staticmethod
     def backward(ctx, dfeat):
         spec, desc = ctx.spec, ctx.desc
-        if not desc.training:
-            raise RuntimeError(f"{spec.name}: backward through an eval-mode forward is not supported")
+        if ctx.ws is None:
+            raise RuntimeError(f"{spec.name}: second backward through a training-mode forward whose workspace was released "
+                               "by the first one (run the forward again; an eval-mode forward keeps its workspace)")
         lib = L.lib()
         dfeat = f32c(dfeat)
         ptab = _table(ctx.params)
         gtab = _table([grad_sink(p) if ctx.needs_input_grad[2 + i] else None for i, p in enumerate(ctx.params)])
         nb = getattr(lib, spec.prefix + "_bwd_workspace")(C.byref(desc))
         bws = _Scratch.get(spec.prefix + "_bwd", nb, dfeat.device)
-        fn = getattr(lib, spec.prefix + "_backward")
+        # the input gradient is one more output of the last stage; an eval-mode forward is differentiated through the
+        # running statistics.  A training-mode backward without an input gradient is the call it always was.
+        dx = torch.empty_like(ctx.x) if ctx.needs_input_grad[0] else None
+        with_dx = dx is not None or not desc.training
+        fn = getattr(lib, spec.prefix + ("_backward_dx" if with_dx else "_backward"))
         stages = spec.stage_groups or [(0, spec.n_stages)]
         # with a stage hook (data-parallel overlap) only the last group joins the weight-gradient side stream to
         # this stream; the hook orders its all-reduce after the side stream itself (ecgmm_side_wait)
@@ -66,21 +73,43 @@ class _PlanFn(torch.autograd.Function):
             for gi, (b, e) in enumerate(stages):
                 if defer:
                     lib.ecgmm_side_defer_join(int(gi + 1 < len(stages)))
+                tail = (ptr(dx), stream()) if with_dx else (stream(),)
                 L.check(fn(C.byref(desc), ptr(ctx.x), ptr(dfeat), ptab, gtab, ptr(ctx.ws), ptr(bws), bws.numel(), b, e,
-                           stream()), spec.name + " backward")
+                           *tail), spec.name + " backward")
                 if spec.stage_hook is not None:
                     spec.stage_hook(spec, gi)
         finally:
             if defer:
                 lib.ecgmm_side_defer_join(0)
-        ctx.ws = None
-        return (None, None) + (None,) * len(ctx.params)
+        if desc.training:
+            ctx.ws = None   # (an eval forward keeps it: per-class attributions run several backwards through one forward)
+        return (dx, None) + (None,) * len(ctx.params)
+
+
+def plan_grad_cam(spec, dfeat):
+    """Grad-CAM map of the encoder's last activation for the forward that ``spec.last`` recorded (``spec.keep_last``):
+    ``dfeat`` [N, out_dim] = d logit / d encoder output.  -> [N, H, W] (image) / [N, L] (signal) fp32 in [0, 1]."""
+    if spec.last is None:
+        raise RuntimeError(f"{spec.name}: no recorded forward (set spec.keep_last before the forward)")
+    desc, ws, x, params = spec.last
+    _require_cuda(dfeat, spec.name + " grad-cam")
+    lib = L.lib()
+    dfeat = f32c(dfeat)
+    cam = torch.empty((x.shape[0],) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32)
+    nb = getattr(lib, spec.prefix + "_bwd_workspace")(C.byref(desc))
+    bws = _Scratch.get(spec.prefix + "_bwd", nb, dfeat.device)
+    ws.record_stream(torch.cuda.current_stream(x.device))   # (the forward may have run on a side stream)
+    L.check(getattr(lib, spec.prefix + "_gradcam")(C.byref(desc), ptr(dfeat), _table(params), ptr(ws), ptr(bws),
+                                                   bws.numel(), ptr(cam), stream()), spec.name + " grad-cam")
+    return cam
 
 
 class PlanSpec:
     """Mutable per-module launch description (rebuilt cheaply every forward)."""
     stage_groups = None   # list of (begin, end) backward stage ranges (set by parallel.py for overlap)
     stage_hook = None     # callable(spec, group_index) fired after each group
+    keep_last = False     # record (desc, workspace, input, params) of the next forward in ``last`` (Grad-CAM)
+    last = None
 
     def __init__(self, name, prefix, n_stages):
         self.name, self.prefix, self.n_stages = name, prefix, n_stages

@@ -399,8 +399,6 @@ class BatchNorm1dFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        if not ctx.training:
-            raise RuntimeError("BatchNorm1d backward needs the forward to have run in training mode")
         x, y, coef = ctx.saved_tensors
         gamma, beta = ctx.params
         B, Cn = x.shape
@@ -408,6 +406,12 @@ class BatchNorm1dFn(torch.autograd.Function):
         lib = L.lib()
         dx = torch.empty_like(x)
         scratch = _Scratch.get("bn1d", lib.ecgmm_bn_bwd_scratch(L.F32, B, Cn), x.device)
+        if not ctx.training:   # eval forward: a constant affine map (running statistics)
+            L.check(lib.ecgmm_bn_eval_bwd(L.F32, ptr(dy), ptr(y) if ctx.relu else None, None, None, 1, ptr(x), ptr(coef),
+                                          ptr(grad_sink(gamma) if ctx.needs_input_grad[1] else None),
+                                          ptr(grad_sink(beta) if ctx.needs_input_grad[2] else None), ptr(dx), None, None, B,
+                                          Cn, ptr(scratch), stream()), "bn_eval_bwd")
+            return dx, None, None, None, None, None, None, None, None, None
         L.check(lib.ecgmm_bn_bwd(L.F32, ptr(dy), ptr(y) if ctx.relu else None, None, None, 1, ptr(x), ptr(coef),
                                  ptr(gamma), ptr(grad_sink(gamma) if ctx.needs_input_grad[1] else None),
                                  ptr(grad_sink(beta) if ctx.needs_input_grad[2] else None), ptr(dx), None, None, B, Cn,

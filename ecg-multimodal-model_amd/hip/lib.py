@@ -48,6 +48,8 @@ SIGNATURES = {
     "ecgmm_resnet18_bwd_workspace": (sz, [P(ResNet18Desc)]),
     "ecgmm_resnet18_forward": (i32, [P(ResNet18Desc), vp, P(vp), P(vp), vp, vp, sz, vp]),
     "ecgmm_resnet18_backward": (i32, [P(ResNet18Desc), vp, vp, P(vp), P(vp), vp, vp, sz, i32, i32, vp]),
+    "ecgmm_resnet18_backward_dx": (i32, [P(ResNet18Desc), vp, vp, P(vp), P(vp), vp, vp, sz, i32, i32, vp, vp]),
+    "ecgmm_resnet18_gradcam": (i32, [P(ResNet18Desc), vp, P(vp), vp, vp, sz, vp, vp]),
     "ecgmm_head_fwd_workspace": (sz, [P(HeadDesc)]),
     "ecgmm_head_bwd_workspace": (sz, [P(HeadDesc)]),
     "ecgmm_head_forward": (i32, [P(HeadDesc), P(vp), P(vp), P(vp), vp, vp, vp, sz, vp]),
@@ -70,6 +72,8 @@ SIGNATURES = {
     "ecgmm_resnet1d_bwd_workspace": (sz, [P(ResNet1DDesc)]),
     "ecgmm_resnet1d_forward": (i32, [P(ResNet1DDesc), vp, P(vp), P(vp), vp, vp, sz, vp]),
     "ecgmm_resnet1d_backward": (i32, [P(ResNet1DDesc), vp, vp, P(vp), P(vp), vp, vp, sz, i32, i32, vp]),
+    "ecgmm_resnet1d_backward_dx": (i32, [P(ResNet1DDesc), vp, vp, P(vp), P(vp), vp, vp, sz, i32, i32, vp, vp]),
+    "ecgmm_resnet1d_gradcam": (i32, [P(ResNet1DDesc), vp, P(vp), vp, vp, sz, vp, vp]),
     "ecgmm_nchw_to_nhwc": (i32, [i32, vp, vp, i32, i32, i64, vp]),
     "ecgmm_nhwc_to_nchw": (i32, [i32, vp, vp, i32, i32, i64, vp]),
     "ecgmm_cast": (i32, [i32, vp, vp, i64, vp]),
@@ -94,6 +98,7 @@ SIGNATURES = {
     "ecgmm_stem_pool_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, vp]),
     "ecgmm_stem_bwd_weight_workspace": (sz, [i32, i32, i32, i32, i32]),
     "ecgmm_stem_bwd_weight": (i32, [i32, vp, vp, vp, i32, vp, sz, i32, i32, i32, i32, i32, vp]),
+    "ecgmm_stem_bwd_data": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "ecgmm_col_stats_rows": (i32, [i32, i64, i32]),
     "ecgmm_col_stats": (i32, [i32, vp, i64, i32, vp, vp]),
     "ecgmm_bn_finalize": (i32, [vp, i32, i32, f64, vp, vp, vp, vp, vp, f32, f32, vp, vp]),
@@ -102,6 +107,7 @@ SIGNATURES = {
     "ecgmm_bn_act_from_rows": (i32, [i32, vp, vp, i32, f64, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, i32, i32, vp, i64, i32, vp]),
     "ecgmm_bn_bwd_scratch": (sz, [i32, i64, i32]),
     "ecgmm_bn_bwd": (i32, [i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp]),
+    "ecgmm_bn_eval_bwd": (i32, [i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp]),
     "ecgmm_conv_bwd_data_with_downsample": (i32, [i32, P(ConvDesc), vp, vp, vp, vp, vp, vp, vp]),
     "ecgmm_conv_bwd_data_bnred": (i32, [i32, P(ConvDesc), vp, vp, vp, vp, vp, vp, vp, vp, P(i32), vp]),
     "ecgmm_conv_bwd_data_bnred_rows": (i32, [i32, P(ConvDesc)]),
@@ -146,6 +152,7 @@ SIGNATURES = {
     "ecgmm_split_cols_bwd": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     "ecgmm_bn_small_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp]),
     "ecgmm_bn_small_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "ecgmm_bn_small_eval_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "ecgmm_entropy_fwd": (i32, [vp, vp, i64, i32, f32, vp]),
     "ecgmm_entropy_bwd": (i32, [vp, vp, vp, i64, i32, f32, vp]),
     "ecgmm_image_resize_tables_bytes": (sz, [i32, i32, i32, i32]),
@@ -156,7 +163,18 @@ SIGNATURES = {
     "ecgmm_prof_collect": (i32, [i32, P(f64), P(f64), P(f64), P(i64)]),
 }
 
+# Entry points of the input-gradient / Grad-CAM feature.  A library selected with ECGMM_LIB for an A/B run may predate them:
+# it still loads, and calling one of them then fails with a message instead of a missing attribute.
+LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_resnet1d_backward_dx",
+                 "ecgmm_resnet1d_gradcam", "ecgmm_stem_bwd_data", "ecgmm_bn_eval_bwd", "ecgmm_bn_small_eval_bwd")
+
 _lib = None
+
+
+def _missing(name):
+    def fail(*_a):
+        raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild the HIP library (there is no fallback)")
+    return fail
 
 
 def lib():
@@ -173,6 +191,9 @@ def lib():
         import torch  # noqa: F401
         h = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
+            if name in LATER_SYMBOLS and os.environ.get("ECGMM_LIB") and not hasattr(h, name):
+                setattr(h, name, _missing(name))
+                continue
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.ecgmm_version() != 100:

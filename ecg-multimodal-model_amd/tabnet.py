@@ -199,8 +199,6 @@ class _GhostBN(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        if not ctx.training:
-            raise RuntimeError("BatchNorm backward needs the forward to have run in training mode")
         x, save = ctx.saved_tensors
         gamma, beta = ctx.params
         dy = f32c(dy)
@@ -210,8 +208,9 @@ class _GhostBN(torch.autograd.Function):
         dg = grad_sink(gamma) if ctx.needs_input_grad[1] else None
         db = grad_sink(beta) if ctx.needs_input_grad[2] else None
         for k, (i0, i1) in enumerate(ctx.bounds):      # parameter gradients add up over the virtual batches
-            L.check(lib.ecgmm_bn_small_bwd(ptr(x[i0:i1]), ptr(dy[i0:i1]), ptr(gamma), ptr(save[k]), ptr(dx[i0:i1]), ptr(dg),
-                                           ptr(db), i1 - i0, Cn, int(k > 0), stream()), "bn_small_bwd")
+            fn = lib.ecgmm_bn_small_bwd if ctx.training else lib.ecgmm_bn_small_eval_bwd   # (eval: running statistics)
+            L.check(fn(ptr(x[i0:i1]), ptr(dy[i0:i1]), ptr(gamma), ptr(save[k]), ptr(dx[i0:i1]), ptr(dg), ptr(db), i1 - i0, Cn,
+                       int(k > 0), stream()), "bn_small_bwd")
         return dx, None, None, None, None, None, None, None, None, None
 
 

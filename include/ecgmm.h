@@ -65,6 +65,21 @@ int ecgmm_resnet18_forward(const ecgmm_resnet18_desc* d, const float* image, con
 int ecgmm_resnet18_backward(const ecgmm_resnet18_desc* d, const float* image, const float* dfeat,
                             const void* const* params, void* const* grads, void* ws_fwd, void* ws_bwd,
                             size_t ws_bwd_bytes, int stage_begin, int stage_end, void* stream);
+/* The same backward with the input gradient as one more output: dimage [N,3,H,W] fp32 (nullable) is written, in full, by
+ * the last stage (9) -- image.requires_grad_(True) upstream of self.image_encoder(image), PMB:325.  Both entry points
+ * also run behind a forward with training = 0 (torch: net.eval(); net(x).backward()): every BatchNorm backward is then
+ * the affine form over the running statistics, parameter gradients are produced for every non-null entry of grads as in
+ * training mode, and the forward workspace is only read, so one eval forward serves any number of backward calls.
+ * With ecgmm_stem_recompute(1) (no stored stem conv output) the input gradient and the eval backward are refused. */
+int ecgmm_resnet18_backward_dx(const ecgmm_resnet18_desc* d, const float* image, const float* dfeat,
+                               const void* const* params, void* const* grads, void* ws_fwd, void* ws_bwd,
+                               size_t ws_bwd_bytes, int stage_begin, int stage_end, float* dimage, void* stream);
+/* Grad-CAM of layer4's output (the overlays of the reference's gpt/ pictures): dfeat [N,out_dim] = d logit / d encoder
+ * output (from the head's backward); ws_fwd = the workspace of the forward, ws_bwd as for ecgmm_resnet18_backward.
+ * cam [N,H,W] fp32 = upsample_bilinear(relu(sum_c a_c A_c) / max), a_c = d logit / d pooled_c / (H'W'); all zero where
+ * the maximum is 0; align_corners=False. */
+int ecgmm_resnet18_gradcam(const ecgmm_resnet18_desc* d, const float* dfeat, const void* const* params, void* ws_fwd,
+                           void* ws_bwd, size_t ws_bwd_bytes, float* cam, void* stream);
 
 /* The ResNet18 backward runs its weight-gradient kernels on a library-owned side stream (forked from /
  * joined to `stream` with events inside each call).  0 = keep everything on the caller's stream. */
@@ -104,6 +119,14 @@ int ecgmm_resnet1d_forward(const ecgmm_resnet1d_desc* d, const float* signal, co
 int ecgmm_resnet1d_backward(const ecgmm_resnet1d_desc* d, const float* signal, const float* dfeat,
                             const void* const* params, void* const* grads, void* ws_fwd, void* ws_bwd,
                             size_t ws_bwd_bytes, int stage_begin, int stage_end, void* stream);
+/* as ecgmm_resnet18_backward_dx: dsignal [N,cin,L] fp32 (nullable) written by the last stage (4); eval-mode forwards
+ * (training = 0) are differentiated through the running statistics by both entry points */
+int ecgmm_resnet1d_backward_dx(const ecgmm_resnet1d_desc* d, const float* signal, const float* dfeat,
+                               const void* const* params, void* const* grads, void* ws_fwd, void* ws_bwd,
+                               size_t ws_bwd_bytes, int stage_begin, int stage_end, float* dsignal, void* stream);
+/* Grad-CAM of layer3's output along the signal: cam [N,L] fp32 (see ecgmm_resnet18_gradcam) */
+int ecgmm_resnet1d_gradcam(const ecgmm_resnet1d_desc* d, const float* dfeat, const void* const* params, void* ws_fwd,
+                           void* ws_bwd, size_t ws_bwd_bytes, float* cam, void* stream);
 
 /* The multimodal head: everything ECGMultimodalModel.forward does after the three encoders, as ONE call per
  * direction (PMB:326-354 / multimodal.py:440-469: three LayerNorms, three branch Linear heads, AttentionFusion,
@@ -216,6 +239,12 @@ int ecgmm_stem_fwd_wgrows(int dtype, const float* x, const void* packed, const f
 size_t ecgmm_stem_bwd_weight_workspace(int N, int Cin, int H, int W, int R);
 int ecgmm_stem_bwd_weight(int dtype, const float* x, const void* dy, float* dw_oihw, int accumulate, void* ws,
                           size_t ws_bytes, int N, int Cin, int H, int W, int R, void* stream);
+/* input gradient of the same two convolutions == autograd of F.conv2d(x, w, stride=2, padding=3) (R = 7) /
+ * F.conv1d(x, w, stride=2, padding=3) (R = 1, H = 1) w.r.t. x: dy [N,OH,OW,64] compute dtype channels-last (as
+ * ecgmm_stem_fwd stores y), w_oihw the fp32 master weights [64,Cin,R,7] (rounded to the compute dtype inside),
+ * dx [N,Cin,H,W] fp32, every element written once (no memset, no atomics); fp32 accumulation.  Cin <= 9 (R = 7) / 24. */
+int ecgmm_stem_bwd_data(int dtype, const void* dy, const float* w_oihw, float* dx, int N, int Cin, int H, int W, int R,
+                        void* stream);
 
 /* The 2-D stem BY RECOMPUTE (csrc/conv_stem_fused.hip; bf16, 7x7 stride 2, Cin <= 3): conv1 -> bn1 -> relu -> maxpool of
  * torchvision's resnet18 (the reference's image encoder, multimodal_paper_modal_balance.py:210) without the
@@ -270,6 +299,13 @@ size_t ecgmm_bn_bwd_scratch(int dtype, int64_t M, int C);
 int ecgmm_bn_bwd(int dtype, const void* dout, const void* maskref, const float* gate, const float* addc,
                  int rows_per_sample, const void* y, const float* coef, const float* gamma, float* dgamma,
                  float* dbeta, void* dy, void* dz_out, float* dbias, int64_t M, int C, void* scratch, void* stream);
+/* backward of a BatchNorm whose forward ran in eval mode (net.eval(): running statistics, a constant per-channel affine
+ * map -- torch differentiates it the same way): one pass, operands as ecgmm_bn_bwd,
+ *   g = [maskref > 0] * dout * [gate] + [addc],  dy = g * scale_c,  dbeta = sum g,  dgamma = sum g * (y - running_mean) * rstd,
+ *   dbias = sum dy.  scratch (ecgmm_bn_bwd_scratch bytes) is needed only when one of the three sums is asked for. */
+int ecgmm_bn_eval_bwd(int dtype, const void* dout, const void* maskref, const float* gate, const float* addc,
+                      int rows_per_sample, const void* y, const float* coef, float* dgamma, float* dbeta, void* dy,
+                      void* dz_out, float* dbias, int64_t M, int C, float* scratch, void* stream);
 
 /* The same backward with its reduction pass fused into the convolution that PRODUCES dout (autograd of
  * conv -> BatchNorm -> ReLU chains: torchvision BasicBlock, multimodal_paper_modal_balance.py:210; train.py:80):
@@ -412,6 +448,9 @@ int ecgmm_bn_small_fwd(const float* x, const float* gamma, const float* beta, fl
                        float* y, float* save, int N, int C, int training, float momentum, float eps, void* stream);
 int ecgmm_bn_small_bwd(const float* x, const float* dy, const float* gamma, const float* save, float* dx, float* dgamma,
                        float* dbeta, int N, int C, int accumulate, void* stream);
+/* the same behind an eval-mode forward (save = running mean, invstd): dx = dy * gamma * invstd (dx may be NULL) */
+int ecgmm_bn_small_eval_bwd(const float* x, const float* dy, const float* gamma, const float* save, float* dx,
+                            float* dgamma, float* dbeta, int N, int C, int accumulate, void* stream);
 int ecgmm_entropy_fwd(const float* M, float* out, int64_t N, int D, float eps, void* stream);
 int ecgmm_entropy_bwd(const float* M, const float* g, float* dM, int64_t N, int D, float eps, void* stream);
 
