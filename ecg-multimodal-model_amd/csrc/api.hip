@@ -219,6 +219,35 @@ int ecgmm_pool_bn_bwd(int dtype, const void* dp, const void* pooled, const uint8
   return ecg_pool_bn_bwd(dtype, dp, pooled, idx, y, coef, gamma, dgamma, dbeta, dy, dbias, N, H, W, C, (float*)scratch,
                          S_(stream));
 }
+// ---- per-op pieces of the inference plans (plan_infer.hip, infer_fold.hip) ----
+int ecgmm_conv_fwd_fused(int dtype, const ecgmm_conv_desc* c, const void* x, const void* w_fwd, const float* bias,
+                         const void* addend, void* y, int act, void* stream) {
+  if (dtype != ECGMM_BF16 && dtype != ECGMM_F32) ECG_FAIL(ECGMM_ERR_DTYPE, "conv_fwd_fused: bad dtype %d", dtype);
+  if (!c || !x || !w_fwd || !y) ECG_FAIL(ECGMM_ERR_SHAPE, "conv_fwd_fused: null operand");
+  if (act != ECGMM_ACT_NONE && act != ECGMM_ACT_RELU) ECG_FAIL(ECGMM_ERR_SHAPE, "conv_fwd_fused: act %d (none or ReLU)", act);
+  if (c->N < 1 || c->H < 1 || c->W < 1 || c->Cin < 1 || c->Cout < 1 || c->R < 1 || c->S < 1 || c->stride < 1 ||
+      c->pad_h < 0 || c->pad_w < 0 || c->H + 2 * c->pad_h < c->R || c->W + 2 * c->pad_w < c->S)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "conv_fwd_fused: bad geometry");
+  return ecg_conv_igemm(dtype, 0, geom_of(c), x, w_fwd, y, bias, addend, nullptr, act, S_(stream));
+}
+int ecgmm_fold_conv_bn(int dtype, int layout, const float* w, const float* conv_bias, const float* gamma, const float* beta,
+                       const float* running_mean, const float* running_var, float eps, void* w_out, float* b_out,
+                       float* scale_out, int Cout, int Cin, int RS, void* stream) {
+  if (layout != 0 && layout != 1) ECG_FAIL(ECGMM_ERR_SHAPE, "fold_conv_bn: layout %d (0 = forward pack, 1 = stem pack)", layout);
+  EcgFoldItem it = {};
+  it.kind = layout == 1 ? ECG_FOLD_STEM : ECG_FOLD_CONV;
+  it.w = w; it.conv_bias = conv_bias; it.gamma = gamma; it.beta = beta; it.rm = running_mean; it.rv = running_var;
+  it.wout = w_out; it.bout = b_out; it.scale_out = scale_out; it.Cout = Cout; it.Cin = Cin; it.RS = RS;
+  return ecg_fold_batch(dtype, &it, 1, eps, S_(stream));
+}
+int ecgmm_relu_maxpool(int dtype, const void* y, void* out, int N, int H, int W, int C, void* stream) {
+  return ecg_relu_maxpool(dtype, y, out, N, H, W, C, S_(stream));
+}
+int ecgmm_gate_res_relu(int dtype, const void* y, const float* gate, const void* res, void* out, int64_t M, int C,
+                        int rows_per_sample, void* stream) {
+  return ecg_gate_res_relu(dtype, y, gate, res, out, (long)M, C, rows_per_sample, S_(stream));
+}
+
 int ecgmm_avgpool(int dtype, const void* x, float* out, int N, int R, int C, const float* coef, void* stream) {
   return ecg_avgpool(dtype, x, out, N, R, C, coef, S_(stream));
 }

@@ -135,6 +135,28 @@ struct EcgPackItem {
   int Cout, Cin, RS;
 };
 int ecg_pack_weight_batch(int dtype, const EcgPackItem* items, int n, hipStream_t stream);
+// infer_fold.hip: inference-only kernels.  Fold an eval-mode BatchNorm into the convolution in front of it
+// (scale = gamma / sqrt(rv + eps); w' = w * scale[cout] rounded once to the compute dtype; b' = beta + (conv_bias - rm) * scale)
+constexpr int ECG_FOLD_MAX = 32;
+enum { ECG_FOLD_CONV = 0,    // OIHW / OIL fp32 -> forward pack [Cout][RS][Cin] (the layout of ecg_pack_weight)
+       ECG_FOLD_STEM = 1,    // [64][Cin][R][7] fp32 -> stem pack (ecg_stem_pack); RS = R (1 or 7)
+       ECG_FOLD_COPY = 2 };  // plain fp32 copy of Cout x Cin floats (dense-tail weights kept beside the folded ones)
+struct EcgFoldItem {
+  int kind;
+  const float* w;
+  const float* conv_bias;                 // nullable
+  const float *gamma, *beta, *rm, *rv;    // the BatchNorm (unused by ECG_FOLD_COPY)
+  void* wout;                             // compute dtype (fp32 for ECG_FOLD_COPY)
+  float* bout;                            // [Cout] fp32
+  float* scale_out;                       // nullable: the scale the kernel used, [Cout] fp32
+  int Cout, Cin, RS;
+};
+int ecg_fold_batch(int dtype, const EcgFoldItem* items, int n, float eps, hipStream_t stream);
+// max(0, 3x3 / 2 / 1 max-pool) of a [N][H][W][C] tensor (H = 1: the 1-D 3 / 2 / 1 pool)
+int ecg_relu_maxpool(int dtype, const void* y, void* out, int N, int H, int W, int C, hipStream_t stream);
+// out = relu(y * gate[row / rows_per_sample][c] + res); out may be y
+int ecg_gate_res_relu(int dtype, const void* y, const float* gate, const void* res, void* out, long M, int C,
+                      int rows_per_sample, hipStream_t stream);
 // plan_resnet1d.hip: switches the ResNet1D_SE backward's weight-gradient side stream (ecgmm_side_wgrad toggles both plans)
 int ecg_resnet1d_side_enable(int on);
 int ecg_pack_weight(int dtype, const float* w_oihw, void* fwd, void* dgrad, int Cout, int Cin, int RS,

@@ -158,6 +158,19 @@ SIGNATURES = {
     "ecgmm_image_resize_tables_bytes": (sz, [i32, i32, i32, i32]),
     "ecgmm_image_resize_tables": (i32, [i32, i32, i32, i32, vp, sz]),
     "ecgmm_image_transform": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, sz, P(f32), P(f32), vp]),
+    "ecgmm_resnet18_infer_prepared_bytes": (sz, [P(ResNet18Desc)]),
+    "ecgmm_resnet18_infer_prepare": (i32, [P(ResNet18Desc), P(vp), P(vp), vp, sz, vp]),
+    "ecgmm_resnet18_infer_workspace": (sz, [P(ResNet18Desc)]),
+    "ecgmm_resnet18_infer": (i32, [P(ResNet18Desc), vp, vp, sz, vp, vp, sz, vp]),
+    "ecgmm_resnet1d_infer_prepared_bytes": (sz, [P(ResNet1DDesc)]),
+    "ecgmm_resnet1d_infer_prepare": (i32, [P(ResNet1DDesc), P(vp), P(vp), vp, sz, vp]),
+    "ecgmm_resnet1d_infer_workspace": (sz, [P(ResNet1DDesc)]),
+    "ecgmm_resnet1d_infer": (i32, [P(ResNet1DDesc), vp, vp, sz, vp, vp, sz, vp]),
+    "ecgmm_infer_down_side": (i32, [i32]),
+    "ecgmm_conv_fwd_fused": (i32, [i32, P(ConvDesc), vp, vp, vp, vp, vp, i32, vp]),
+    "ecgmm_fold_conv_bn": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, vp]),
+    "ecgmm_relu_maxpool": (i32, [i32, vp, vp, i32, i32, i32, i32, vp]),
+    "ecgmm_gate_res_relu": (i32, [i32, vp, vp, vp, vp, i64, i32, i32, vp]),
     "ecgmm_prof_enable": (i32, [i32]),
     "ecgmm_prof_pause": (i32, [i32]),
     "ecgmm_prof_collect": (i32, [i32, P(f64), P(f64), P(f64), P(i64)]),
@@ -166,7 +179,12 @@ SIGNATURES = {
 # Entry points of the input-gradient / Grad-CAM feature.  A library selected with ECGMM_LIB for an A/B run may predate them:
 # it still loads, and calling one of them then fails with a message instead of a missing attribute.
 LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_resnet1d_backward_dx",
-                 "ecgmm_resnet1d_gradcam", "ecgmm_stem_bwd_data", "ecgmm_bn_eval_bwd", "ecgmm_bn_small_eval_bwd")
+                 "ecgmm_resnet1d_gradcam", "ecgmm_stem_bwd_data", "ecgmm_bn_eval_bwd", "ecgmm_bn_small_eval_bwd",
+                 # the inference plans (ecgmm/inference.py)
+                 "ecgmm_resnet18_infer_prepared_bytes", "ecgmm_resnet18_infer_prepare", "ecgmm_resnet18_infer_workspace",
+                 "ecgmm_resnet18_infer", "ecgmm_resnet1d_infer_prepared_bytes", "ecgmm_resnet1d_infer_prepare",
+                 "ecgmm_resnet1d_infer_workspace", "ecgmm_resnet1d_infer", "ecgmm_infer_down_side", "ecgmm_conv_fwd_fused",
+                 "ecgmm_fold_conv_bn", "ecgmm_relu_maxpool", "ecgmm_gate_res_relu")
 
 _lib = None
 

@@ -1,0 +1,226 @@
+"""Inference path: ``Predictor(model)(...)`` returns what ``model.eval()(...)`` returns under ``torch.no_grad()``, through
+the encoders' *inference plans* (csrc/plan_infer.hip) instead of the training plans' eval mode.
+
+What the reference does at every validation / test pass (train.py:92-95, 175-182; train_kfold.py:72-74, 118-121;
+train_image_only.py:142-144; signal_model.py:174-176) and for embedding extraction (shap_fusion_modal_balance.py:54-59)::
+
+    model.eval()
+    with torch.no_grad():
+        out = model(images, ecg, clinical)
+
+becomes::
+
+    predict = Predictor(model)          # folds every BatchNorm into its convolution, once
+    out = predict(images, ecg, clinical)
+
+An inference plan keeps nothing for a backward: no saved activations, no ReLU bits, no pool indices, no statistics rows.
+Grad-CAM and input gradients (ecgmm/explain.py) therefore keep using the model's own eval forward.
+
+**Stale weights.**  The folded weights are a snapshot.  ``FusedAdam`` (and the HIP backward) write parameters and
+gradients through raw pointers, so tensor version counters do not move and a ``Predictor`` cannot notice that the model
+was trained further: call :meth:`Predictor.refresh` after the weights changed (``load_state_dict``, an optimizer step).
+Until then it keeps returning the answer of the weights it was prepared from.  The snapshot covers both encoders and
+the multimodal head; the clinical branch (a few small dense layers, or TabNet) runs the model's own eval forward on the
+live parameters.
+"""
+import ctypes as C
+
+import torch
+
+from .hip import encoders as E
+from .hip import lib as L
+from .hip.functional import _Scratch, _require_cuda, f32c, new_bytes, ptr, stream
+from .image_encoder import ResNet18
+from .multimodal_paper_modal_balance import ECGMultimodalModel, ResNet1D_SE
+
+__all__ = ["Predictor"]
+
+
+class _EncoderPlan:
+    """Prepared blob + launch of one encoder (``ResNet18`` or ``ResNet1D_SE``)."""
+
+    def __init__(self, module):
+        if isinstance(module, ResNet18):
+            self.prefix, self.name, self.n_params, self.n_buffers = "ecgmm_resnet18", "resnet18", 62, 60
+        elif isinstance(module, ResNet1D_SE):
+            self.prefix, self.name, self.n_params, self.n_buffers = "ecgmm_resnet1d", "resnet1d_se", 52, 27
+        else:
+            raise TypeError(f"no inference plan for {type(module).__name__}")
+        self.module = module
+        self.blob = None
+        self.refresh()
+
+    def _desc(self, N, a, b):
+        m = self.module
+        if self.name == "resnet18":
+            return L.ResNet18Desc(N, a, b, self.out_dim, self.dtype, 0, 0.0, self.eps)
+        return L.ResNet1DDesc(N, m.input_channels, a, self.out_dim, self.dtype, 0, 0.0, self.eps, 0.0, 0, 0)
+
+    def refresh(self):
+        m = self.module
+        params, buffers = list(m.parameters()), list(m.buffers())
+        if len(params) != self.n_params or len(buffers) != self.n_buffers:
+            raise RuntimeError(f"{self.name}: expected {self.n_params} parameters / {self.n_buffers} buffers, found "
+                               f"{len(params)} / {len(buffers)}")
+        for t in params + buffers:
+            _require_cuda(t, f"Predictor({self.name}) parameter")
+        self.dtype = E.dtype_code(m.compute_dtype)
+        if self.name == "resnet18":
+            self.out_dim, self.eps = m.fc.weight.shape[0], float(m.bn1.eps)
+        else:
+            self.out_dim, self.eps = m.classifier[4].weight.shape[0], float(m.initial[1].eps)
+        lib = L.lib()
+        desc = self._desc(0, 0, 0)
+        nb = getattr(lib, self.prefix + "_infer_prepared_bytes")(C.byref(desc))
+        if nb == 0:
+            L.check(1, self.name + " prepared-size query")
+        dev = params[0].device
+        with torch.cuda.device(dev):
+            # a NEW blob: a forward already enqueued with the old one (another stream) keeps reading consistent weights
+            blob = new_bytes(nb, dev)
+            L.check(getattr(lib, self.prefix + "_infer_prepare")(C.byref(desc), E._table(params), E._table(buffers), ptr(blob),
+                                                                 blob.numel(), stream()), self.name + " infer prepare")
+        self.blob = blob
+
+    def __call__(self, x):
+        m = self.module
+        _require_cuda(x, f"Predictor({self.name})")
+        if E.dtype_code(m.compute_dtype) != self.dtype:
+            raise RuntimeError(f"Predictor({self.name}): the model's compute dtype is now {m.compute_dtype!r} but the weights "
+                               "were prepared in another one -- call refresh()")
+        if self.name == "resnet18":
+            if x.dim() != 4 or x.shape[1] != 3:
+                raise ValueError(f"image encoder expects [B,3,H,W], got {tuple(x.shape)}")
+            desc = self._desc(x.shape[0], x.shape[2], x.shape[3])
+        else:
+            if x.dim() != 3 or x.shape[1] != m.input_channels:
+                raise ValueError(f"signal encoder expects [B,{m.input_channels},L], got {tuple(x.shape)}")
+            desc = self._desc(x.shape[0], x.shape[2], 0)
+        x = f32c(x)
+        lib = L.lib()
+        nb = getattr(lib, self.prefix + "_infer_workspace")(C.byref(desc))
+        if nb == 0:
+            L.check(1, self.name + " infer workspace query")
+        ws = _Scratch.get(self.prefix + "_infer", nb, x.device)   # transient: nothing in it outlives the call
+        self.blob.record_stream(torch.cuda.current_stream(x.device))
+        feat = torch.empty(x.shape[0], self.out_dim, device=x.device, dtype=torch.float32)
+        L.check(getattr(lib, self.prefix + "_infer")(C.byref(desc), ptr(x), ptr(self.blob), self.blob.numel(), ptr(feat),
+                                                     ptr(ws), ws.numel(), stream()), self.name + " infer")
+        return feat
+
+    def workspace_bytes(self, *shape):
+        """Bytes of the inference workspace for an input of ``shape`` (no GPU work)."""
+        desc = self._desc(shape[0], shape[2], shape[3] if self.name == "resnet18" else 0)
+        return int(getattr(L.lib(), self.prefix + "_infer_workspace")(C.byref(desc)))
+
+
+def _find_encoder(model):
+    if isinstance(model, (ResNet18, ResNet1D_SE)):
+        return model
+    enc = getattr(model, "image_encoder", None)       # ImageOnlyClassifier and the like: a wrapper around one encoder
+    if isinstance(enc, ResNet18) and not isinstance(model, ECGMultimodalModel):
+        return enc
+    return None
+
+
+class Predictor:
+    """Eval-mode forward of ``model`` through the inference plans.
+
+    ``model``: an ``ECGMultimodalModel`` (either variant), a ``ResNet18`` / ``ImageOnlyClassifier`` or a ``ResNet1D_SE``,
+    on a ROCm device.  Construction prepares the folded weights; :meth:`refresh` prepares them again (see the module
+    docstring: nothing can detect stale weights for you).  Calling the predictor never changes ``model.training``, a
+    running statistic or a ``.grad``.
+    """
+
+    def __init__(self, model):
+        self.model = model
+        self.multimodal = isinstance(model, ECGMultimodalModel)
+        if self.multimodal:
+            self.image, self.signal = _EncoderPlan(model.image_encoder), _EncoderPlan(model.signal_encoder)
+            self._snapshot_head()
+        else:
+            enc = _find_encoder(model)
+            if enc is None:
+                raise TypeError(f"Predictor: unsupported model {type(model).__name__} (ECGMultimodalModel, ResNet18, "
+                                "ImageOnlyClassifier or ResNet1D_SE)")
+            self.encoder = _EncoderPlan(enc)
+
+    def _snapshot_head(self):
+        with torch.no_grad():
+            self._head_params = [p.detach().clone() for p in self.model._head_params()]
+
+    def refresh(self):
+        """Prepare the folded weights again from the model's current parameters and running statistics."""
+        if self.multimodal:
+            self.image.refresh()
+            self.signal.refresh()
+            self._snapshot_head()
+        else:
+            self.encoder.refresh()
+        return self
+
+    @torch.no_grad()
+    def __call__(self, *inputs):
+        if not self.multimodal:
+            if len(inputs) != 1:
+                raise TypeError(f"Predictor({type(self.model).__name__}) takes one input, got {len(inputs)}")
+            return self.encoder(inputs[0])
+        if len(inputs) != 3:
+            raise TypeError(f"Predictor({type(self.model).__name__}) takes (image, ecg_signal, clinical), got {len(inputs)} inputs")
+        model = self.model
+        image, ecg_signal, clinical = inputs
+        for t, what in ((image, "image"), (ecg_signal, "ecg_signal"), (clinical, "clinical")):
+            _require_cuda(t, f"Predictor {what}")
+        if model.clinical_encoder.training:
+            raise RuntimeError("Predictor: the clinical branch runs the model's own forward, which is in training mode "
+                               "(batch statistics, dropout) -- call model.eval() first; the predictor does not change it")
+        spec = model._head_spec()
+        if spec is None:
+            raise RuntimeError("Predictor: this model's head is not the fused Linear-ReLU-Dropout-Linear / LayerNorm layout")
+        spec.training = False
+        ecg_signal = ecg_signal.unsqueeze(1)
+        from . import multimodal_paper_modal_balance as pmb
+        if getattr(model.config, "overlap_encoders", True) and pmb._OVERLAP_ENV:
+            # as ECGMultimodalModel.forward: the small-kernel branches on a side stream underneath the image encoder
+            main = torch.cuda.current_stream(image.device)
+            side = model._side_stream = getattr(model, "_side_stream", None) or torch.cuda.Stream(image.device)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                signal_raw = self.signal(ecg_signal)
+                clinical_raw = model._clinical_forward(clinical)
+            image_raw = self.image(image)
+            main.wait_stream(side)
+            signal_raw.record_stream(main)
+            clinical_raw.record_stream(main)
+        else:
+            image_raw = self.image(image)
+            signal_raw = self.signal(ecg_signal)
+            clinical_raw = model._clinical_forward(clinical)
+        return E.run_head(image_raw, signal_raw, clinical_raw, spec, self._head_params)
+
+    def logits(self, *inputs):
+        """The class logits of a forward: ``fusion_logits`` of the multimodal 6-tuple, the output itself otherwise."""
+        out = self(*inputs)
+        return out[3] if self.multimodal else out
+
+    def predict_proba(self, loader, device=None):
+        """Softmax probabilities of a whole loader, in loader order.
+
+        Batches are ``(*inputs, labels)`` or ``(*inputs, labels, index)`` with three inputs for the multimodal model and
+        one otherwise (the dataset classes of this package).  -> ``(prob [n, classes], labels [n], index [n])`` CPU
+        tensors; without an index column the index is the running position."""
+        n_in = 3 if self.multimodal else 1
+        device = device or next(self.model.parameters()).device
+        probs, labels, index, seen = [], [], [], 0
+        for batch in loader:
+            if len(batch) not in (n_in + 1, n_in + 2):
+                raise ValueError(f"predict_proba: a batch of {len(batch)} tensors; expected {n_in} inputs, labels[, index]")
+            logits = self.logits(*(t.to(device) for t in batch[:n_in]))
+            probs.append(torch.softmax(logits.float().cpu(), dim=1))
+            labels.append(torch.as_tensor(batch[n_in]).cpu())
+            b = probs[-1].shape[0]
+            index.append(torch.as_tensor(batch[n_in + 1]).cpu() if len(batch) == n_in + 2 else torch.arange(seen, seen + b))
+            seen += b
+        if not probs:
+            return torch.empty(0, 0), torch.empty(0, dtype=torch.long), torch.empty(0, dtype=torch.long)
+        return torch.cat(probs), torch.cat(labels), torch.cat(index)

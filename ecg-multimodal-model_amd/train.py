@@ -38,8 +38,12 @@ def step_loss(outputs, labels):
     return HF.cross_entropy_plus(outputs[3], labels, outputs[4], 0.1)
 
 
-def run_epoch(model, loader, device, optimizer=None):
+def run_epoch(model, loader, device, optimizer=None, predictor=None):
+    """``predictor`` (optional, validation only): an ``ecgmm.inference.Predictor`` of ``model`` whose weights are current
+    (``refresh()`` after training); the forward then runs through the inference plans.  Default: the model's own forward."""
     train = optimizer is not None
+    if train and predictor is not None:
+        raise ValueError("run_epoch: a Predictor has no backward; pass it for validation passes only")
     model.train(train)
     tot, tot_var, correct, n = 0.0, 0.0, 0, 0
     ctx = torch.enable_grad() if train else torch.no_grad()
@@ -48,7 +52,7 @@ def run_epoch(model, loader, device, optimizer=None):
             images, ecg, clinical, labels = (t.to(device) for t in batch)
             if train:
                 optimizer.zero_grad()
-            outputs = model(images, ecg, clinical)
+            outputs = model(images, ecg, clinical) if predictor is None else predictor(images, ecg, clinical)
             loss = step_loss(outputs, labels)
             if train:
                 loss.backward()
@@ -61,15 +65,16 @@ def run_epoch(model, loader, device, optimizer=None):
     return tot / k, tot_var / k, correct / max(n, 1)
 
 
-def evaluate(model, loader, device):
-    """train.py:173-260: softmax[:,1] probabilities, accuracy / F1 / AUC on the test split."""
+def evaluate(model, loader, device, predictor=None):
+    """train.py:173-260: softmax[:,1] probabilities, accuracy / F1 / AUC on the test split.
+    ``predictor`` (optional): an ``ecgmm.inference.Predictor`` of ``model`` with current weights; default: ``model`` itself."""
     from sklearn.metrics import f1_score, roc_auc_score
     model.eval()
     y_true, y_prob, y_pred = [], [], []
     with torch.no_grad():
         for *batch, _index in loader:
             images, ecg, clinical, labels = (t.to(device) for t in batch)
-            logits = model(images, ecg, clinical)[3]
+            logits = (model if predictor is None else predictor)(images, ecg, clinical)[3]
             prob = torch.softmax(logits.float().cpu(), dim=1)   # host-side metrics, as in the reference
             y_true += labels.cpu().tolist()
             y_prob += prob[:, 1].tolist()
@@ -83,7 +88,9 @@ def evaluate(model, loader, device):
     return {"accuracy": acc, "f1": f1, "auc": auc}
 
 
-def main(config=Config, freeze_encoders=True, num_epochs=None, quiet=False, model_cls=None):
+def main(config=Config, freeze_encoders=True, num_epochs=None, quiet=False, model_cls=None, use_predictor=False):
+    """``use_predictor``: run the validation and test passes through an ``ecgmm.inference.Predictor`` (BatchNorm-folded
+    inference plans), refreshed after every training epoch and after every checkpoint load.  Default off."""
     torch.manual_seed(config.seed)
     HF.manual_seed(config.seed)
     device = torch.device(config.device)
@@ -105,10 +112,16 @@ def main(config=Config, freeze_encoders=True, num_epochs=None, quiet=False, mode
     ckpt_dir = os.path.join(config.checkpoint_dir, modeltime)
     os.makedirs(ckpt_dir, exist_ok=True)
 
+    predictor = None
+    if use_predictor:
+        from .inference import Predictor
+        predictor = Predictor(model)
     min_val, early, lr_ctr, history = float("inf"), 0, 0, []
     for epoch in range(num_epochs or config.num_epochs):
         tr_loss, _, tr_acc = run_epoch(model, train_loader, device, optimizer)
-        va_loss, va_var, va_acc = run_epoch(model, val_loader, device)
+        if predictor is not None:
+            predictor.refresh()   # (the optimizer wrote the weights through raw pointers: nothing else can tell)
+        va_loss, va_var, va_acc = run_epoch(model, val_loader, device, predictor=predictor)
         history.append(dict(epoch=epoch + 1, train_loss=tr_loss, train_acc=tr_acc, val_loss=va_loss, val_acc=va_acc))
         if not quiet:
             print(f"[{epoch + 1}] train {tr_loss:.4f}/{tr_acc:.4f}  val {va_loss:.4f}/{va_acc:.4f}")
@@ -138,7 +151,9 @@ def main(config=Config, freeze_encoders=True, num_epochs=None, quiet=False, mode
     results = {}
     for tag in ("best", "last"):
         model.load_state_dict(torch.load(os.path.join(ckpt_dir, f"{tag}.pth"), map_location=device))
-        results[tag] = evaluate(model, test_loader, device)
+        if predictor is not None:
+            predictor.refresh()
+        results[tag] = evaluate(model, test_loader, device, predictor=predictor)
         if not quiet:
             print(f"test[{tag}]: {results[tag]}")
     if writer is not None:

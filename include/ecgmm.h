@@ -128,6 +128,37 @@ int ecgmm_resnet1d_backward_dx(const ecgmm_resnet1d_desc* d, const float* signal
 int ecgmm_resnet1d_gradcam(const ecgmm_resnet1d_desc* d, const float* dfeat, const void* const* params, void* ws_fwd,
                            void* ws_bwd, size_t ws_bwd_bytes, float* cam, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Inference plans (opt-in): the eval-mode forward of either encoder with every BatchNorm folded into the convolution in
+ * front of it and bias / residual / ReLU in the convolution's epilogue.  They replace self.image_encoder(image) /
+ * self.signal_encoder(ecg_signal) under model.eval() + torch.no_grad(): the validation pass (train.py:92-95,
+ * train_kfold.py:72-74, train_image_only.py:142-144, signal_model.py:174-176), the test pass (train.py:175-182,
+ * train_kfold.py:118-121, train_image_only.py:180-185) and the embedding extraction of shap_fusion_modal_balance.py:54-59.
+ * The training plans above, their eval mode, the eval-mode backward and Grad-CAM are unchanged; an inference forward keeps
+ * nothing a backward could use.
+ *
+ * prepare: params / buffers (the tables of ecgmm_resnet18_forward / ecgmm_resnet1d_forward) -> a prepared blob of
+ *   *_infer_prepared_bytes(d) bytes, one launch.  Of the descriptor only dtype, out_dim / num_classes, cin and bn_eps are
+ *   read: one blob serves any batch and any input size.  Do it again after the weights changed.
+ * infer: input + blob -> feat_out [N, out_dim] fp32.  Reads no parameter, no buffer, writes nothing but feat_out and ws
+ *   (*_infer_workspace(d) bytes: the stem output + a fixed set of rotating block buffers).  `training`, `bn_momentum`,
+ *   `dropout_p`, `seed`, `offset` of the descriptors are ignored: there is no dropout and no statistics update. */
+size_t ecgmm_resnet18_infer_prepared_bytes(const ecgmm_resnet18_desc* d);
+int ecgmm_resnet18_infer_prepare(const ecgmm_resnet18_desc* d, const void* const* params, const void* const* buffers,
+                                 void* blob, size_t blob_bytes, void* stream);
+size_t ecgmm_resnet18_infer_workspace(const ecgmm_resnet18_desc* d);
+int ecgmm_resnet18_infer(const ecgmm_resnet18_desc* d, const float* image, const void* blob, size_t blob_bytes,
+                         float* feat_out, void* ws, size_t ws_bytes, void* stream);
+size_t ecgmm_resnet1d_infer_prepared_bytes(const ecgmm_resnet1d_desc* d);
+int ecgmm_resnet1d_infer_prepare(const ecgmm_resnet1d_desc* d, const void* const* params, const void* const* buffers,
+                                 void* blob, size_t blob_bytes, void* stream);
+size_t ecgmm_resnet1d_infer_workspace(const ecgmm_resnet1d_desc* d);
+int ecgmm_resnet1d_infer(const ecgmm_resnet1d_desc* d, const float* signal, const void* blob, size_t blob_bytes,
+                         float* feat_out, void* ws, size_t ws_bytes, void* stream);
+/* ResNet18 inference plan: the downsample convolution of a block on a library-owned side stream beside conv1 (1) or in
+ * line on the caller's stream (0, default).  Start-up value: ECGMM_INFER_DOWN_SIDE. */
+int ecgmm_infer_down_side(int on);
+
 /* The multimodal head: everything ECGMultimodalModel.forward does after the three encoders, as ONE call per
  * direction (PMB:326-354 / multimodal.py:440-469: three LayerNorms, three branch Linear heads, AttentionFusion,
  * fusion_classifier = Linear-ReLU-Dropout-Linear, var_loss).  Same kernels as the per-op entry points below.
@@ -482,6 +513,28 @@ int ecgmm_prof_collect(int nkinds, double* ms, double* flops, double* bytes, int
 int ecgmm_tl_enable(int on);
 int ecgmm_tl_mark(int id, void* stream);
 int ecgmm_tl_collect(int cap, int* ids, float* ms);
+
+/* ---- per-op pieces of the inference plans ----
+ * F.relu(F.conv2d(x, w, bias) + addend) as ONE launch -- what torchvision's BasicBlock does in three modules (conv2, bn2
+ * folded into w / bias, `out += identity; out = self.relu(out)`) and PMB:84-93 in the 1-D blocks.  bias [Cout] fp32 and
+ * addend (the shape and dtype of y) are nullable; act = ECGMM_ACT_NONE or ECGMM_ACT_RELU; no statistics. */
+int ecgmm_conv_fwd_fused(int dtype, const ecgmm_conv_desc* c, const void* x, const void* w_fwd, const float* bias,
+                         const void* addend, void* y, int act, void* stream);
+/* nn.BatchNorm2d / nn.BatchNorm1d in eval mode behind a convolution (torchvision BasicBlock bn1 / bn2 / downsample.1,
+ * PMB:72,75,82,100) folded into it: scale = gamma / sqrt(running_var + eps); w_out = w * scale[cout] (fp32 product, rounded
+ * once to dtype), packed as layout 0 = the forward pack of ecgmm_pack_conv_weight ([Cout][RS][Cin]) or 1 = ecgmm_stem_pack
+ * (Cout = 64, RS = kernel rows 1 or 7); b_out = beta + (conv_bias - running_mean) * scale, fp32.  conv_bias and scale_out
+ * (the scale the kernel used, [Cout] fp32) are nullable. */
+int ecgmm_fold_conv_bn(int dtype, int layout, const float* w, const float* conv_bias, const float* gamma, const float* beta,
+                       const float* running_mean, const float* running_var, float eps, void* w_out, float* b_out,
+                       float* scale_out, int Cout, int Cin, int RS, void* stream);
+/* nn.ReLU + nn.MaxPool2d(3, 2, 1) (torchvision resnet stem) / nn.MaxPool1d(3, 2, 1) (PMB:103, H = 1) of a channels-last
+ * tensor: ecgmm_bnrelu_maxpool without coefficients and without the argmax bytes. */
+int ecgmm_relu_maxpool(int dtype, const void* y, void* out, int N, int H, int W, int C, void* stream);
+/* out = relu(y * gate[row / rows_per_sample][c] + res): `out = self.se(out); out += identity; out = self.relu(out)`,
+ * PMB:88-92, with bn2 already folded into y.  out may be y. */
+int ecgmm_gate_res_relu(int dtype, const void* y, const float* gate, const void* res, void* out, int64_t M, int C,
+                        int rows_per_sample, void* stream);
 
 #ifdef __cplusplus
 }
