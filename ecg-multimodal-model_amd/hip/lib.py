@@ -143,6 +143,8 @@ SIGNATURES = {
     "ecgmm_axpby": (i32, [f32, vp, f32, vp, i64, vp]),
     "ecgmm_signal_preprocess_workspace": (sz, [i32, i32, i32]),
     "ecgmm_signal_preprocess": (i32, [vp, vp, i32, i32, vp, vp, i32, P(f64), P(f64), P(f64), i32, vp, sz, vp]),
+    "ecgmm_signal_filter_zscore": (i32, [vp, vp, i32, i32, P(f64), P(f64), P(f64), i32, i32, f64, vp]),
+    "ecgmm_signal_gather_augment": (i32, [vp, i64, i32, vp, i32, vp, vp, i32, f32, f32, f32, f32, i32, i32, u64, u64, vp]),
     "ecgmm_glu_fwd": (i32, [vp, vp, i64, i32, vp]),
     "ecgmm_glu_bwd": (i32, [vp, vp, vp, i64, i32, vp]),
     "ecgmm_sparsemax_fwd": (i32, [vp, vp, i64, i32, vp]),
@@ -184,7 +186,9 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  "ecgmm_resnet18_infer_prepared_bytes", "ecgmm_resnet18_infer_prepare", "ecgmm_resnet18_infer_workspace",
                  "ecgmm_resnet18_infer", "ecgmm_resnet1d_infer_prepared_bytes", "ecgmm_resnet1d_infer_prepare",
                  "ecgmm_resnet1d_infer_workspace", "ecgmm_resnet1d_infer", "ecgmm_infer_down_side", "ecgmm_conv_fwd_fused",
-                 "ecgmm_fold_conv_bn", "ecgmm_relu_maxpool", "ecgmm_gate_res_relu")
+                 "ecgmm_fold_conv_bn", "ecgmm_relu_maxpool", "ecgmm_gate_res_relu",
+                 # the PhysioNet-2017 path (ecgmm/train_physionet.py)
+                 "ecgmm_signal_filter_zscore", "ecgmm_signal_gather_augment")
 
 _lib = None
 

@@ -33,6 +33,51 @@ def butter_lowpass(order, wn):
     return b, a
 
 
+def butter_bandpass(order, low, high):
+    """== scipy.signal.butter(order, [low, high], 'band') (b, a), 2*order + 1 coefficients each: analog low-pass prototype
+    -> band-pass transform about sqrt(w1 w2) with bandwidth w2 - w1 (pre-warped edges) -> bilinear transform with fs = 2
+    -> polynomial coefficients.  The steps and their order are scipy's (buttap, lp2bp_zpk, bilinear_zpk, zpk2tf)."""
+    if not (0.0 < low < high < 1.0):
+        raise ValueError(f"butter_bandpass: need 0 < low < high < 1 (fractions of Nyquist), got {low}, {high}")
+    fs = 2.0
+    p = -np.exp(1j * np.pi * np.arange(-order + 1, order, 2) / (2 * order))
+    w1, w2 = 2 * fs * np.tan(np.pi * low / fs), 2 * fs * np.tan(np.pi * high / fs)
+    bw, wo = w2 - w1, np.sqrt(w1 * w2)
+    p_lp = p * bw / 2
+    root = np.sqrt(p_lp.astype(complex) ** 2 - wo ** 2)
+    p_bp = np.concatenate((p_lp + root, p_lp - root))
+    z_bp = np.zeros(order)
+    k_bp = bw ** order
+    fs2 = 2 * fs
+    z_d = np.append((fs2 + z_bp) / (fs2 - z_bp), -np.ones(order))
+    p_d = (fs2 + p_bp) / (fs2 - p_bp)
+    k_d = k_bp * np.real(np.prod(fs2 - z_bp) / np.prod(fs2 - p_bp))
+    b = k_d * np.real(np.poly(z_d))
+    a = np.real(np.poly(p_d))
+    return b, a
+
+
+def filter_zscore(x, b, a, zscore=True, eps=1e-8):
+    """z_score_normalize(scipy.signal.filtfilt(b, a, x)) per record of a CUDA float tensor [..., L] in one launch (fp64
+    arithmetic, fp32 result; train_physionet.py:23-45).  Orders 1..8 (up to 9 coefficients); ``zscore=False`` stops after
+    the filter.  A record must fit one CU's LDS: L <= 19904 - 3*(len(b) + len(a)) samples, longer ones are refused."""
+    _require_cuda(x, "filter_zscore")
+    b, a = np.atleast_1d(np.asarray(b, dtype=np.float64)), np.atleast_1d(np.asarray(a, dtype=np.float64))
+    n = max(len(a), len(b))
+    b, a = np.pad(b, (0, n - len(b))) / a[0], np.pad(a, (0, n - len(a))) / a[0]
+    if n < 2:
+        raise ValueError("filter_zscore: the transfer function needs at least two coefficients")
+    zi = lfilter_zi(b, a)
+    shape = x.shape
+    x2 = x.reshape(-1, shape[-1]).float().contiguous()
+    S, Ln = x2.shape
+    out = torch.empty_like(x2)
+    dbl = lambda v: (C.c_double * len(v))(*[float(t) for t in v])
+    L.check(L.lib().ecgmm_signal_filter_zscore(ptr(x2), ptr(out), S, Ln, dbl(b), dbl(a), dbl(zi), n - 1, int(bool(zscore)),
+                                               float(eps), stream()), "signal_filter_zscore")
+    return out.reshape(shape)
+
+
 def lfilter_zi(b, a):
     """== scipy.signal.lfilter_zi: initial state of the transposed direct-form-II filter for a unit step."""
     b, a = np.asarray(b, dtype=np.float64) / a[0], np.asarray(a, dtype=np.float64) / a[0]

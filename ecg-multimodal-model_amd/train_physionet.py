@@ -1,0 +1,378 @@
+"""PhysioNet-2017 single-lead trainer, N vs AF/O (reference: train_physionet.py:22-132, 267-451).
+
+The reference filters every sample again at every ``__getitem__`` on the CPU (4th-order Butterworth band-pass ``filtfilt``
+-> z-score -> random augmentation).  Here each split is padded on the host, uploaded once and pre-processed once by ONE
+``filter_zscore`` launch (the result is a pure function of the record, so caching it changes nothing); per batch one
+``gather_augment`` launch gathers the rows and applies ``augment_signal`` on the device.  The model, loss, optimizer and
+schedule are the reference's: ``ResNet1D_SE`` on ``[B, 1, 3000]``, ``FocalLoss(1, 2)``, Adam(1e-3), OneCycleLR per batch.
+
+Not carried over: ``resample_signal`` (the reference never reaches it: ``orig_fs == target_fs`` at its only call site),
+the unused ``ECGTransformer1D``, plots.  ``wfdb`` is replaced by :func:`read_record`, ``keras`` by :func:`pad_sequences`.
+"""
+import csv
+import os
+import re
+import time
+
+import numpy as np
+import torch
+
+from . import preprocess as PP
+from .config import Config
+from .hip import functional as HF
+from .hip import lib as L
+from .hip.functional import _require_cuda, ptr, stream
+from .optim import FusedAdam
+from .signal_model import FocalLoss, ResNet1D_SE
+
+LABEL_MAP = {"N": 0, "AF": 1, "O": 1}      # train_physionet.py:93 ('~' records are dropped at :92)
+MAX_LEN = 3000
+# train_physionet.py:113-118: 80 % train, the remaining 20 % halved into validation and test
+SPLIT = (0.2, 0.5)
+AUG_DEFAULTS = dict(p=0.5, sigma=0.01, scale=(0.8, 1.2), shift=(-10, 10))   # train_physionet.py:47-58
+
+
+# --------------------------------------------------------------------------------------------
+# pre-processing (device)                                   reference: train_physionet.py:23-45
+# --------------------------------------------------------------------------------------------
+def z_score_normalize(signal, eps=1e-8):
+    """(x - mean) / (std + eps) per record of a CUDA tensor [..., L] (population std, fp64 inside)."""
+    return PP.filter_zscore(signal, [1.0, 0.0], [1.0, 0.0], zscore=True, eps=eps)   # identity filter: y = x exactly
+
+
+def _band(lowcut, highcut, fs, order):
+    nyq = 0.5 * fs
+    return PP.butter_bandpass(order, lowcut / nyq, highcut / nyq)
+
+
+def bandpass_filter(signal, lowcut=16, highcut=149, fs=300, order=4):
+    """filtfilt(butter(order, [low, high], 'band'), signal) per record of a CUDA tensor [..., L]."""
+    b, a = _band(lowcut, highcut, fs, order)
+    return PP.filter_zscore(signal, b, a, zscore=False)
+
+
+def preprocess_signal(raw_signal, orig_fs=300, target_fs=300):
+    """bandpass_filter -> z_score_normalize in one launch.  raw_signal: CUDA float tensor [..., L]."""
+    if orig_fs != target_fs:
+        raise NotImplementedError("preprocess_signal: resample_signal (orig_fs != target_fs) is not part of this path; the "
+                                  "reference never reaches it (train_physionet.py:81 passes 300 / 300)")
+    _require_cuda(raw_signal, "preprocess_signal")
+    b, a = _band(16, 149, orig_fs, 4)
+    return PP.filter_zscore(raw_signal, b, a, zscore=True, eps=1e-8)
+
+
+def gather_augment(src, index, augment=False, p=0.5, sigma=0.01, scale=(0.8, 1.2), shift=(-10, 10),
+                   return_decisions=False, seed_offset=None, check_index=True):
+    """``out[i] = augment_signal(src[index[i]])`` in one launch; ``augment=False`` is the plain gather.
+
+    src: CUDA fp32 [n, L]; index: int64 [B], on the host (checked there, then uploaded) or on the device (checked with one
+    device read unless ``check_index=False``).  Randomness comes from the Philox stream of ``ecgmm.hip.functional``
+    (``manual_seed``), advanced by one counter block per call; ``seed_offset=(seed, offset)`` pins it instead.
+    -> out [B, L] (and the decision record [B, 4]: noise flag, scale or 1, shift or 0, decisions as bits 1 / 2 / 4)."""
+    _require_cuda(src, "gather_augment")
+    if src.dim() != 2 or src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError("gather_augment: src must be a contiguous float32 [n, L] tensor")
+    index = torch.as_tensor(index)
+    if index.dtype != torch.int64 or index.dim() != 1 or index.numel() < 1:
+        raise ValueError("gather_augment: index must be a non-empty int64 vector")
+    n, Ln = src.shape
+    if check_index:
+        lo, hi = int(index.min()), int(index.max())
+        if lo < 0 or hi >= n:
+            raise IndexError(f"gather_augment: index range [{lo}, {hi}] outside the {n} rows of src")
+    index = index.to(src.device).contiguous()
+    B = index.numel()
+    out = torch.empty(B, Ln, dtype=torch.float32, device=src.device)
+    dec = torch.empty(B, 4, dtype=torch.float32, device=src.device) if return_decisions else None
+    seed, off = (0, 0)
+    if augment:
+        seed, off = HF._PhiloxState.take(1) if seed_offset is None else seed_offset
+    L.check(L.lib().ecgmm_signal_gather_augment(ptr(src), n, Ln, ptr(index), B, ptr(out), ptr(dec), int(bool(augment)),
+                                                float(p), float(sigma), float(scale[0]), float(scale[1]), int(shift[0]),
+                                                int(shift[1]), int(seed), int(off), stream()), "signal_gather_augment")
+    return (out, dec) if return_decisions else out
+
+
+def augment_signal(signal, **kw):
+    """train_physionet.py:47-60 per record of a CUDA tensor [..., L]: three independent coin flips -- N(0, 0.01^2) noise,
+    a U(0.8, 1.2) gain, a circular roll by -10 .. 9 samples.  Draws from ``HF``'s Philox state."""
+    _require_cuda(signal, "augment_signal")
+    shape = signal.shape
+    x = signal.reshape(-1, shape[-1]).float().contiguous()
+    idx = torch.arange(x.shape[0], dtype=torch.int64, device=x.device)
+    return gather_augment(x, idx, augment=True, check_index=False, **{**AUG_DEFAULTS, **kw}).reshape(shape)
+
+
+# --------------------------------------------------------------------------------------------
+# host side: records, padding, labels, split
+# --------------------------------------------------------------------------------------------
+def pad_sequences(sequences, maxlen, dtype="float32", padding="post", truncating="post", value=0.0):
+    """keras ``pad_sequences`` for the arguments the reference uses (train_physionet.py:72-74): zero padding at the end,
+    truncation at the end.  -> numpy [len(sequences), maxlen]."""
+    if padding != "post" or truncating != "post":
+        raise NotImplementedError("pad_sequences: only padding='post', truncating='post' (the reference's call)")
+    out = np.full((len(sequences), int(maxlen)), value, dtype=dtype)
+    for i, s in enumerate(sequences):
+        s = np.asarray(s)[:maxlen]
+        out[i, :len(s)] = s
+    return out
+
+
+_GAIN = re.compile(r"^([0-9.eE+-]+)(?:\((-?\d+)\))?(?:/.*)?$")
+
+
+def read_record(path):
+    """Physical signal ``p_signal`` [samples, signals] (float64) of one challenge record, as ``wfdb.rdrecord(path).p_signal``:
+    ``path`` names the ``NAME.hea`` + ``NAME.mat`` pair without extension (``val`` int16 [signals, samples]; gain and
+    baseline from each signal line of the header, gain 200 when absent or 0, baseline = ADC zero when not in parentheses;
+    ``(val - baseline) / gain``).  A ``.npy`` path (or ``NAME.npy`` next to no header) is loaded as is."""
+    if path.endswith(".npy") or (not os.path.exists(path + ".hea") and os.path.exists(path + ".npy")):
+        x = np.load(path if path.endswith(".npy") else path + ".npy").astype(np.float64)
+        return x.reshape(-1, 1) if x.ndim == 1 else x
+    from scipy.io import loadmat
+    with open(path + ".hea") as f:
+        lines = [ln.strip() for ln in f if ln.strip() and not ln.startswith("#")]
+    nsig = int(lines[0].split()[1])
+    gains, baselines = [], []
+    for ln in lines[1:1 + nsig]:
+        fld = ln.split()
+        gain, base = 200.0, None
+        if len(fld) > 2:
+            m = _GAIN.match(fld[2])
+            if m is None:
+                raise ValueError(f"{path}.hea: cannot parse the gain field {fld[2]!r}")
+            gain = float(m.group(1)) or 200.0
+            base = None if m.group(2) is None else int(m.group(2))
+        if base is None:
+            base = int(fld[4]) if len(fld) > 4 else 0
+        gains.append(gain)
+        baselines.append(base)
+    val = np.asarray(loadmat(path + ".mat")["val"], dtype=np.float64)
+    if val.shape[0] != nsig:
+        raise ValueError(f"{path}.mat: {val.shape[0]} signals, the header declares {nsig}")
+    return ((val - np.array(baselines, dtype=np.float64)[:, None]) / np.array(gains)[:, None]).T
+
+
+def read_labels(label_file, label_map=LABEL_MAP):
+    """REFERENCE.csv (``record,label``, no header) -> [(record, class)] for the labels in ``label_map``; the rest ('~') dropped."""
+    rows = []
+    with open(label_file, newline="") as f:
+        for rec in csv.reader(f):
+            if len(rec) >= 2 and rec[1].strip() in label_map:
+                rows.append((rec[0].strip(), label_map[rec[1].strip()]))
+    return rows
+
+
+def synthetic_records(config=Config, label_map=LABEL_MAP):
+    """Generated variable-length single-lead records (2000 .. 18000 samples at 300 Hz) in place of the challenge data:
+    a beat train whose regularity depends on the class, baseline wander and noise, in mV."""
+    n = config.synthetic_train_size + config.synthetic_val_size + config.synthetic_test_size
+    rng = np.random.RandomState(config.seed)
+    names = sorted(label_map, key=lambda k: (label_map[k], k))
+    signals, labels = [], []
+    for i in range(n):
+        name = names[i % len(names)]
+        length = int(rng.randint(2000, 18001))
+        t = np.arange(length) / 300.0
+        rate = {"N": 1.1, "AF": 1.9, "O": 1.4}.get(name, 1.0)
+        jitter = {"N": 0.0, "AF": 0.35, "O": 0.1}.get(name, 0.0)
+        phase = 2 * np.pi * rate * t + jitter * np.cumsum(rng.randn(length)) * 0.2
+        beat = np.exp(8.0 * (np.cos(phase) - 1.0))
+        x = 0.9 * beat + 0.1 * np.sin(2 * np.pi * 0.3 * t + rng.rand() * 6.28) + 0.02 * rng.randn(length)
+        signals.append(x)
+        labels.append(label_map[name])
+    return signals, np.array(labels, dtype=np.int64)
+
+
+def load_records(config=Config, label_map=LABEL_MAP, quiet=True):
+    """-> (list of 1-D float64 signals, int64 labels): lead 0 of every record of REFERENCE.csv that loads
+    (train_physionet.py:91-109; a record that fails to load is skipped with a warning)."""
+    if getattr(config, "synthetic", False):
+        return synthetic_records(config, label_map)
+    signals, labels = [], []
+    for name, lab in read_labels(config.physionet_label_file, label_map):
+        try:
+            signals.append(read_record(os.path.join(config.physionet_data_dir, name))[:, 0])
+            labels.append(lab)
+        except Exception as e:   # noqa: BLE001 -- as the reference: any failure skips the record
+            if not quiet:
+                print(f"Warning: Failed to load record {name}: {e}")
+    return signals, np.array(labels, dtype=np.int64)
+
+
+def split_indices(labels, seed=Config.seed, split=SPLIT):
+    """Stratified train / val / test indices: ``train_test_split(test_size=split[0])`` then the held-out part split again
+    with ``test_size=split[1]``, both seeded with ``seed`` (train_physionet.py:112-118)."""
+    from sklearn.model_selection import train_test_split
+    labels = np.asarray(labels)
+    idx = np.arange(len(labels))
+    train_idx, temp_idx, _, temp_y = train_test_split(idx, labels, test_size=split[0], stratify=labels, random_state=seed)
+    val_idx, test_idx = train_test_split(temp_idx, test_size=split[1], stratify=temp_y, random_state=seed)
+    return train_idx, val_idx, test_idx
+
+
+# --------------------------------------------------------------------------------------------
+# dataset + loader (device resident)
+# --------------------------------------------------------------------------------------------
+class SignalOnlyDataset:
+    """One split, resident on the device: padded to ``max_len`` on the host, uploaded once, band-pass filtered and
+    z-scored once (train_physionet.py:63-86 does both per sample per epoch).  ``signals`` [n, max_len] fp32, ``labels`` [n]."""
+
+    def __init__(self, indices, labels, ecg_signals, augment=True, max_len=MAX_LEN, split="train", device=None):
+        device = torch.device(device or Config.device)
+        self.labels_host = torch.as_tensor(np.asarray(labels)[np.asarray(indices)], dtype=torch.long)
+        self.ecg_signals_padded = pad_sequences([ecg_signals[i] for i in indices], maxlen=max_len, dtype="float32",
+                                                padding="post", truncating="post")
+        self.max_len, self.split = max_len, split
+        self.augment = bool(augment) and split == "train"
+        self.signals = preprocess_signal(torch.from_numpy(self.ecg_signals_padded).to(device), orig_fs=300, target_fs=300)
+        self.labels = self.labels_host.to(device)
+
+    def __len__(self):
+        return self.labels_host.numel()
+
+    def __getitem__(self, idx):
+        sig = self.signals[idx]
+        if self.augment:
+            sig = augment_signal(sig)
+        return sig, self.labels[idx]
+
+
+class DeviceSignalLoader:
+    """Batches of a :class:`SignalOnlyDataset`: ``(signals [B, L] fp32 on the device, labels [B] on the device)``, one
+    ``gather_augment`` launch per batch (augmentation as the dataset says).  ``shuffle``: a ``torch.randperm`` of the seeded
+    ``generator`` per epoch, kept in ``last_order``."""
+
+    def __init__(self, dataset, batch_size=8, shuffle=False, generator=None, drop_last=False):
+        self.dataset, self.batch_size, self.shuffle, self.drop_last = dataset, int(batch_size), shuffle, drop_last
+        self.generator = generator
+        self.last_order = None
+
+    def __len__(self):
+        n, b = len(self.dataset), self.batch_size
+        return n // b if self.drop_last else (n + b - 1) // b
+
+    def __iter__(self):
+        ds, n = self.dataset, len(self.dataset)
+        order = torch.randperm(n, generator=self.generator) if self.shuffle else torch.arange(n)
+        self.last_order = order
+        order_dev = order.to(ds.signals.device)   # in range by construction: one upload per epoch, no per-batch check
+        for k in range(len(self)):
+            idx = order_dev[k * self.batch_size:(k + 1) * self.batch_size]
+            yield gather_augment(ds.signals, idx, augment=ds.augment, check_index=False, **AUG_DEFAULTS), ds.labels[idx]
+
+
+def get_signalonly_dataloaders(config=Config, batch_size=8, label_map=LABEL_MAP, augment=True, split=SPLIT, max_len=MAX_LEN):
+    """train / val / test :class:`DeviceSignalLoader` (train_physionet.py:89-132; batch 8, only the train split shuffled)."""
+    signals, labels = load_records(config, label_map)
+    train_idx, val_idx, test_idx = split_indices(labels, config.seed, split)
+    device = torch.device(config.device)
+    mk = lambda idx, name: SignalOnlyDataset(idx, labels, signals, augment=augment, max_len=max_len, split=name, device=device)
+    gen = torch.Generator().manual_seed(config.seed)
+    return (DeviceSignalLoader(mk(train_idx, "train"), batch_size, shuffle=True, generator=gen),
+            DeviceSignalLoader(mk(val_idx, "val"), batch_size), DeviceSignalLoader(mk(test_idx, "test"), batch_size))
+
+
+# --------------------------------------------------------------------------------------------
+# training                                                  reference: train_physionet.py:267-451
+# --------------------------------------------------------------------------------------------
+def evaluate(model, loader, num_classes=2, predictor=None):
+    """Softmax probabilities of the split -> accuracy / F1 / AUC (binary: class-1 probability thresholded at 0.5,
+    train_physionet.py:359-379; more classes: argmax, macro F1, one-vs-rest AUC, train_physionet_multi.py:312-330)."""
+    from sklearn.metrics import f1_score, roc_auc_score
+    model.eval()
+    y_true, y_prob = [], []
+    with torch.no_grad():
+        for signals, labels in loader:
+            logits = (model if predictor is None else predictor)(signals.unsqueeze(1))
+            y_prob.append(torch.softmax(logits.float(), dim=1).cpu().numpy())
+            y_true.append(labels.cpu().numpy())
+    y_true, y_prob = np.concatenate(y_true), np.concatenate(y_prob)
+    if num_classes == 2:
+        y_pred = (y_prob[:, 1] >= 0.5).astype(int)
+        f1 = float(f1_score(y_true, y_pred, zero_division=0))
+    else:
+        y_pred = np.argmax(y_prob, axis=1)
+        f1 = float(f1_score(y_true, y_pred, average="macro", zero_division=0))
+    try:
+        auc = float(roc_auc_score(y_true, y_prob[:, 1]) if num_classes == 2 else
+                    roc_auc_score(y_true, y_prob, multi_class="ovr"))
+    except ValueError:
+        auc = float("nan")
+    return {"accuracy": float((y_true == y_pred).mean()), "f1": f1, "auc": auc}
+
+
+def main(config=Config, num_epochs=30, batch_size=8, quiet=False, use_predictor=False, num_classes=2, label_map=LABEL_MAP,
+         augment=True, split=SPLIT):
+    """``use_predictor``: run the validation and test passes through an ``ecgmm.inference.Predictor`` (BatchNorm-folded
+    inference plan), refreshed after every training epoch and after every checkpoint load.  Default off.
+    -> (history, {"best": metrics, "last": metrics}, checkpoint directory)."""
+    torch.manual_seed(config.seed)
+    np.random.seed(config.seed)
+    HF.manual_seed(config.seed)
+    device = torch.device(config.device)
+    if not quiet:
+        print(f"Using device: {device}")
+    train_loader, val_loader, test_loader = get_signalonly_dataloaders(config, batch_size, label_map, augment, split)
+    model = ResNet1D_SE(num_classes=num_classes, compute_dtype=getattr(config, "compute_dtype", "bf16")).to(device)
+    criterion = FocalLoss(alpha=1.0, gamma=2.0)
+    optimizer = FusedAdam(model.parameters(), lr=0.001)
+    scheduler = torch.optim.lr_scheduler.OneCycleLR(optimizer, max_lr=0.001, steps_per_epoch=len(train_loader),
+                                                    epochs=num_epochs)
+    ckpt_dir = os.path.join(config.checkpoint_dir, time.strftime("%m%d_%H%M%S"))
+    os.makedirs(ckpt_dir, exist_ok=True)
+    predictor = None
+    if use_predictor:
+        from .inference import Predictor
+        predictor = Predictor(model)
+    min_val, history = float("inf"), []
+    for epoch in range(num_epochs):
+        model.train()
+        tl, correct, total = 0.0, 0, 0
+        for signals, labels in train_loader:
+            optimizer.zero_grad()
+            out = model(signals.unsqueeze(1))   # [B, L] -> [B, 1, L]
+            loss = criterion(out, labels)
+            loss.backward()
+            optimizer.step()
+            scheduler.step()
+            tl += loss.item()
+            correct += out.argmax(1).eq(labels).sum().item()
+            total += labels.size(0)
+        model.eval()
+        if predictor is not None:
+            predictor.refresh()
+        vl, vc, vt = 0.0, 0, 0
+        with torch.no_grad():
+            for signals, labels in val_loader:
+                out = (model if predictor is None else predictor)(signals.unsqueeze(1))
+                vl += criterion(out, labels).item()
+                vc += out.argmax(1).eq(labels).sum().item()   # accumulated (the reference's `=` at :326 is a bug)
+                vt += labels.size(0)
+        avg = vl / max(len(val_loader), 1)
+        history.append(dict(epoch=epoch + 1, train_loss=tl / max(len(train_loader), 1), train_acc=correct / max(total, 1),
+                            val_loss=avg, val_acc=vc / max(vt, 1)))
+        if not quiet:
+            h = history[-1]
+            print(f"[{epoch + 1}] train {h['train_loss']:.4f}/{h['train_acc']:.4f}  val {avg:.4f}/{h['val_acc']:.4f}")
+        torch.save(model.state_dict(), os.path.join(ckpt_dir, "last.pth"))
+        if avg < min_val:   # train_physionet.py:335-341
+            min_val = avg
+            torch.save(model.state_dict(), os.path.join(ckpt_dir, "best.pth"))
+            torch.save(model.state_dict(), os.path.join(ckpt_dir, f"best_signal_only_epoch{epoch + 1}.pth"))
+    results = {}
+    for tag in ("best", "last"):
+        path = os.path.join(ckpt_dir, f"{tag}.pth")
+        if not os.path.exists(path):   # no epoch improved on inf (a NaN validation loss): nothing was saved as best
+            continue
+        model.load_state_dict(torch.load(path, map_location=device))
+        if predictor is not None:
+            predictor.refresh()
+        results[tag] = evaluate(model, test_loader, num_classes, predictor=predictor)
+        if not quiet:
+            print(f"test[{tag}]: {results[tag]}")
+    return history, results, ckpt_dir
+
+
+if __name__ == "__main__":
+    main()

@@ -458,6 +458,27 @@ int ecgmm_signal_preprocess(const float* x, float* out, int S, int L, const floa
                             int window, const double* b, const double* a, const double* zi, int order, void* ws,
                             size_t ws_bytes, void* stream);
 
+/* PhysioNet-2017 single-lead path.  filtfilt + z-score of a whole [S][L] fp32 matrix in one launch: exactly
+ * scipy.signal.filtfilt(b, a, x) (odd padding 3*(order+1), lfilter_zi initial conditions `zi`) for a general transfer
+ * function b[0..order], a[0..order] (a[0] = 1, 1 <= order <= 8: the 4th-order Butterworth band-pass is order 8), then, when
+ * `zscore` is set, (y - mean(y)) / (std(y) + eps) with the population standard deviation over the L samples.  fp64
+ * arithmetic, fp32 result.  Replaces bandpass_filter + z_score_normalize = preprocess_signal, train_physionet.py:23-45,
+ * train_physionet_multi.py:20-42.  One record stays resident in one CU's LDS: L <= 19904 - 6*(order+1) (19850 at
+ * order 8), longer records are refused. */
+int ecgmm_signal_filter_zscore(const float* x, float* out, int S, int L, const double* b, const double* a,
+                               const double* zi, int order, int zscore, double eps, void* stream);
+/* The per-step batch gather fused with augment_signal (train_physionet.py:47-60): out[i][:] = augment(src[index[i]][:]),
+ * src [n][L] fp32, index int64 [B], out [B][L] fp32.  augment = 0: the plain gather.  augment = 1, per row i: three
+ * Bernoulli(p) decisions in the reference's order -- add N(0, sigma^2) noise per sample point; multiply by a uniform on
+ * [scale_lo, scale_hi); circular roll out[(t + shift) mod L] = v[t] by an integer uniform on [shift_lo, shift_hi).
+ * Philox4x32-10 keyed by `seed`; the counter is (offset, i, element group), so row i's result does not depend on B, on
+ * the launch geometry or on the other rows; the caller advances `offset` by one per call.
+ * decisions (nullable) [B][4] fp32: noise flag, scale (1 when not drawn), shift (0 when not drawn), the three decisions as
+ * bits (1 noise, 2 scale, 4 roll).  A row whose index is outside [0, n) is filled with NaN and never addresses memory. */
+int ecgmm_signal_gather_augment(const float* src, int64_t n, int L, const int64_t* index, int B, float* out,
+                                float* decisions, int augment, float p, float sigma, float scale_lo, float scale_hi,
+                                int shift_lo, int shift_hi, uint64_t seed, uint64_t offset, void* stream);
+
 /* SURVEY 8(f3) -- the TabNet clinical encoder of multimodal.py:109-148 (pytorch_tabnet.tab_network.TabNetNoEmbeddings:
  * third-party, source and version absent from the reference; restated from its published algorithm).  Row kernels,
  * fp32: GLU gate out = z[:, :D] * sigmoid(z[:, D:]) of a [N, 2D] tensor; sparsemax along rows of [N, D], D <= 64;
