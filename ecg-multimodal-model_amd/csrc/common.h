@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/ecgmm.h"
@@ -127,6 +128,17 @@ __device__ __forceinline__ void mfma_drain() {
 #if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" ::: "memory");  // >= 18 wait states: last MFMA's D -> any reader
 #endif
+}
+
+// ---- environment switches (host).  Two polarities, named: env_on = ON unless the value starts with '0' (unset: on);
+// env_off = OFF unless it starts with '1' (unset: off).  env_int: the value as an integer, `def` when unset.
+// env_level: a one-digit level 0..hi, `def` when unset or anything else.
+static inline bool env_on(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }
+static inline bool env_off(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }
+static inline long env_int(const char* name, long def) { const char* e = getenv(name); return e ? atol(e) : def; }
+static inline int env_level(const char* name, int hi, int def) {
+  const char* e = getenv(name);
+  return e && e[0] >= '0' && e[0] <= '0' + hi ? e[0] - '0' : def;
 }
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }

@@ -1244,7 +1244,7 @@ int halo_gk(int ntn, int ntm, int wg_per_cu = 1) {
     }
     cus = ncu[dev];
   }
-  if (g_halo_cu_cap < 0) { const char* e = getenv("ECGMM_HALO_CUS"); g_halo_cu_cap = e ? atoi(e) : 0; if (g_halo_cu_cap < 0) g_halo_cu_cap = 0; }
+  if (g_halo_cu_cap < 0) { g_halo_cu_cap = (int)env_int("ECGMM_HALO_CUS", 0); if (g_halo_cu_cap < 0) g_halo_cu_cap = 0; }
   if (g_halo_cu_cap > 0 && cus > g_halo_cu_cap) cus = g_halo_cu_cap;
   int Gk = cus * wg_per_cu / (ntn < 1 ? 1 : ntn);
   if (Gk > ntm) Gk = ntm;
@@ -1334,10 +1334,7 @@ extern "C" int ecgmm_conv_halo_cus(int cus) {
 
 // Is the halo kernel applicable to this (stride-1, "same") convolution?  mode 0 = forward, 1 = input gradient.
 bool ecg_conv_halo_ok(int dtype, int mode, const ConvGeom& g) {
-  if (g_halo_enabled < 0) {
-    const char* e = getenv("ECGMM_CONV_HALO");
-    g_halo_enabled = e && e[0] >= '0' && e[0] <= '2' ? e[0] - '0' : 1;
-  }
+  if (g_halo_enabled < 0) g_halo_enabled = env_level("ECGMM_CONV_HALO", 2, 1);
   if (!g_halo_enabled || dtype != ECGMM_BF16 || g.stride != 1 || g.S != 3) return false;
   if (!((g.R == 3 && g.pad_h == 1) || (g.R == 1 && g.pad_h == 0)) || g.pad_w != 1) return false;
   if (g.OH != g.H || g.OW != g.W) return false;
@@ -1357,7 +1354,7 @@ bool ecg_conv_halo_ok(int dtype, int mode, const ConvGeom& g) {
 
 // partial rows a halo launch with ConvEpi.wg_rows writes: one per workgroup of a channel tile
 static bool halo_w4(const ConvGeom& g, int Cs, int Cd) {
-  if (g_halo_w4 < 0) { const char* e = getenv("ECGMM_HALO_W4"); g_halo_w4 = (e && e[0] == '1'); }
+  if (g_halo_w4 < 0) g_halo_w4 = env_off("ECGMM_HALO_W4");
   return g_halo_w4 && g.R == 3 && Cs == 64 && Cd == 64;
 }
 // (rows of the fused BatchNorm-backward reduction: that instantiation always runs one 8-wave workgroup per CU)
@@ -1389,8 +1386,8 @@ int ecg_conv_halo(int mode, const ConvGeom& g, const void* src, const void* wpk,
       p.red_rows = epi->red_rows;
     }
   }
-  if (g_halo_stagger < 0) { const char* e = getenv("ECGMM_HALO_STAGGER"); g_halo_stagger = !(e && e[0] == '0'); }
-  if (g_halo_pp < 0) { const char* e = getenv("ECGMM_HALO_PP"); g_halo_pp = !(e && e[0] == '0'); }
+  if (g_halo_stagger < 0) g_halo_stagger = env_on("ECGMM_HALO_STAGGER");
+  if (g_halo_pp < 0) g_halo_pp = env_on("ECGMM_HALO_PP");
   p.stagger = g_halo_stagger;
   int wg = 0;
   const bool wide = p.Cd > 64;
@@ -1398,13 +1395,13 @@ int ecg_conv_halo(int mode, const ConvGeom& g, const void* src, const void* wpk,
   // MODE 2 = input gradient WITHOUT the fused BatchNorm-backward reduction compiled in: the reduction's operand registers
   // push the BN = 128 instantiation over its 256-VGPR budget (396 B of scratch per lane) whether or not a launch uses it --
   // 13 us of a 88 us layer-2 launch (tools/halo_abl.sh, ablation 7)
-  static const bool ncs1_on = [] { const char* e = getenv("ECGMM_HALO_NCS1"); return !(e && e[0] == '0'); }();
+  static const bool ncs1_on = env_on("ECGMM_HALO_NCS1");
   if (halo_w4(g, p.Cs, p.Cd) && !p.red_y) {   // the 64 -> 64 channel 3x3 layers: 4-wave workgroups, two per CU (option)
     if (mode == 0) rc = launch_halo<64, 9, 0, false, 4>(p, &wg, stream);
     else rc = launch_halo<64, 9, 2, false, 4>(p, &wg, stream);
   } else if (g.R == 3 && !wide && p.ncs == 1 && ncs1_on) {   // the same on one 8-wave workgroup per CU: next tile's halo during the K loop
     // (stream form: forward with per-workgroup statistics rows or none, input gradient without addend / fused reduction)
-    if (g_halo_stream < 0) { const char* e = getenv("ECGMM_HALO_STREAM"); g_halo_stream = !(e && e[0] == '0'); }
+    if (g_halo_stream < 0) g_halo_stream = env_on("ECGMM_HALO_STREAM");
     if (mode == 0 && g_halo_stream && (!p.stats || p.wg_rows) && !p.addend && !p.bias && p.act != 1) rc = launch_halo<64, 9, 0, true, 8, false, true>(p, &wg, stream);
     else if (mode != 0 && g_halo_stream && !p.red_y && !p.addend && !p.bias && p.act != 1) rc = launch_halo<64, 9, 2, true, 8, false, true>(p, &wg, stream);
     else if (mode != 0 && g_halo_stream && !p.red_y && p.addend && !p.bias && p.act != 1) rc = launch_halo<64, 9, 2, true, 8, false, true, true>(p, &wg, stream);

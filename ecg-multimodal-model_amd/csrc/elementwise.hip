@@ -1371,7 +1371,7 @@ bool ecg_bn_fold_ok(int C, int rows) {
   // BEFORE the fold -- its ~3 us then cover their HBM latency -- the folded form is the faster one: same-call A/B 6.47, 6.46 ->
   // 6.44, 6.46 ms (multimodal batch 256), 2.96, 2.97 -> 2.95, 2.97 (12-lead batch 512), 3.44, 3.45 -> 3.44, 3.44 (image-only batch
   // 128), and 35 launches fewer per step.  DEFAULT ON; ECGMM_BN_FOLD=0 / ecgmm_bn_fold(0) restores the separate launches.
-  if (g_bn_fold < 0) { const char* e = getenv("ECGMM_BN_FOLD"); g_bn_fold = !(e && e[0] == '0'); }
+  if (g_bn_fold < 0) g_bn_fold = env_on("ECGMM_BN_FOLD");
   if (!g_bn_fold || rows < 1 || rows > 512 || C > 512) return false;
   return C >= 128 ? C % 128 == 0 : (C >= 16 && 1024 % C == 0);
 }
@@ -1594,7 +1594,7 @@ int ecg_pool_bn_bwd_reduce(int dtype, const void* dp, const void* pooled, const 
 
 // ECGMM_STEM_FUSE=0: the plans fall back to max-pool backward + full BatchNorm backward as separate passes (A/B switch)
 bool ecg_stem_fuse_on() {
-  static const bool on = [] { const char* e = getenv("ECGMM_STEM_FUSE"); return !(e && e[0] == '0'); }();
+  static const bool on = env_on("ECGMM_STEM_FUSE");
   return on;
 }
 

@@ -17,17 +17,10 @@
 //
 // Workspace: the stem output, the pooled tensor and a fixed set of rotating block buffers of the largest block activation
 // instead of one saved set per block; the rotating buffers alias the stem output, which is dead once the max-pool has read it.
-#include <stdlib.h>
-
-#include "ops.h"
+#include "plan_common.h"
 #include "side_stream.h"
 
 namespace {
-
-int check_dtype(int dtype, const char* who) {
-  if (dtype != ECGMM_BF16 && dtype != ECGMM_F32) ECG_FAIL(ECGMM_ERR_DTYPE, "%s: bad dtype %d", who, dtype);
-  return 0;
-}
 
 // rotating block buffers: `cur` holds the block's input, take() hands out one of the others
 struct Rot {
@@ -49,65 +42,17 @@ struct Rot {
 // ================================================================================================
 // ResNet18
 // ================================================================================================
-struct Blk18 {
-  int cin, cout, stride, hin, win, hout, wout;
-  bool down;
-  int p_conv1, p_bn1, p_conv2, p_bn2, p_dconv, p_dbn;  // parameter indices (weight; bn bias = +1)
-  int b_bn1, b_bn2, b_dbn;                              // buffer indices (rm; rv = +1)
-};
-struct I18 {
-  ecgmm_resnet18_desc d;
-  int H1, W1, H2, W2;
-  Blk18 blk[8];
-  int p_fc;
-  size_t max_act;
-};
-
-// the weight-only part of the description (what the blob depends on)
-int build18_static(const ecgmm_resnet18_desc* d, I18& r) {
-  if (!d) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet18 infer: null desc");
-  ECG_TRY(check_dtype(d->dtype, "resnet18 infer"));
+// The network description is net_desc.h's; the blob depends on the weight-only part of it (net18_static) and, beyond what
+// the training plans validate, on out_dim and eps.
+int build18_static(const ecgmm_resnet18_desc* d, Net18& r) {
+  ECG_TRY(net18_static(d, r, "resnet18 infer"));
   if (d->out_dim < 1) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet18 infer: out_dim %d", d->out_dim);
   if (!(d->bn_eps >= 0.f)) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet18 infer: bn_eps %g", (double)d->bn_eps);
-  r.d = *d;
-  int pi = 3, bi = 3, cin = 64;
-  for (int L = 0; L < 4; ++L) {
-    const int cout = 64 << L;
-    for (int b = 0; b < 2; ++b) {
-      Blk18& k = r.blk[L * 2 + b];
-      k.cin = cin; k.cout = cout; k.stride = (b == 0 && L > 0) ? 2 : 1;
-      k.down = (k.stride != 1 || cin != cout);
-      k.p_conv1 = pi; k.p_bn1 = pi + 1; k.p_conv2 = pi + 3; k.p_bn2 = pi + 4; pi += 6;
-      k.b_bn1 = bi; k.b_bn2 = bi + 3; bi += 6;
-      if (k.down) { k.p_dconv = pi; k.p_dbn = pi + 1; pi += 3; k.b_dbn = bi; bi += 3; }
-      else k.p_dconv = k.p_dbn = k.b_dbn = -1;
-      cin = cout;
-    }
-  }
-  r.p_fc = pi;
-  if (pi + 2 != ECGMM_RESNET18_NPARAMS || bi != ECGMM_RESNET18_NBUFFERS)
-    ECG_FAIL(ECGMM_ERR_SHAPE, "resnet18 infer: internal table mismatch %d %d", pi + 2, bi);
   return 0;
 }
-int build18(const ecgmm_resnet18_desc* d, I18& r) {
+int build18(const ecgmm_resnet18_desc* d, Net18& r) {
   ECG_TRY(build18_static(d, r));
-  if (d->N < 1 || d->H < 32 || d->W < 32) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet18 infer: bad input %dx%dx%d", d->N, d->H, d->W);
-  r.H1 = (d->H + 6 - 7) / 2 + 1;
-  r.W1 = (d->W + 6 - 7) / 2 + 1;
-  r.H2 = (r.H1 + 2 - 3) / 2 + 1;
-  r.W2 = (r.W1 + 2 - 3) / 2 + 1;
-  int h = r.H2, w = r.W2;
-  r.max_act = (size_t)d->N * h * w * 64;
-  for (int i = 0; i < 8; ++i) {
-    Blk18& k = r.blk[i];
-    k.hin = h; k.win = w;
-    k.hout = (h + 2 - 3) / k.stride + 1;
-    k.wout = (w + 2 - 3) / k.stride + 1;
-    const size_t a = (size_t)d->N * k.hout * k.wout * k.cout;
-    if (a > r.max_act) r.max_act = a;
-    h = k.hout; w = k.wout;
-  }
-  return 0;
+  return net18_shape(r, "resnet18 infer");
 }
 
 struct Blob18 {
@@ -116,7 +61,7 @@ struct Blob18 {
   float *fcw, *fcb;
   size_t bytes;
 };
-void layout_blob18(const I18& r, void* base, Blob18& q) {
+void layout_blob18(const Net18& r, void* base, Blob18& q) {
   Arena a(base);
   const size_t es = dtype_size(r.d.dtype);
   q.wstem = a.take_bytes(ecg_stem_packed_elems(3, 7) * es);
@@ -145,7 +90,7 @@ struct Ws18 {
   float* pooled;
   size_t bytes;
 };
-void layout_ws18(const I18& r, void* base, Ws18& w) {
+void layout_ws18(const Net18& r, void* base, Ws18& w) {
   Arena a(base);
   const size_t es = dtype_size(r.d.dtype);
   const size_t act = align_up(r.max_act * es, 256), y0 = (size_t)r.d.N * r.H1 * r.W1 * 64 * es;
@@ -162,65 +107,23 @@ void layout_ws18(const I18& r, void* base, Ws18& w) {
 SideStream g_side_inf;
 int g_down_side = -1;
 bool down_side_on() {
-  if (g_down_side < 0) { const char* e = getenv("ECGMM_INFER_DOWN_SIDE"); g_down_side = (e && e[0] == '1'); }
+  if (g_down_side < 0) g_down_side = env_off("ECGMM_INFER_DOWN_SIDE");
   return g_down_side != 0;
 }
-
-inline const float* P(const void* const* t, int i) { return (const float*)t[i]; }
 
 // ================================================================================================
 // ResNet1D_SE
 // ================================================================================================
-struct Blk1 {
-  int cin, cout, stride, lin, lout, cr;
-  bool down;
-  int p0, b0;
-};
-struct I1D {
-  ecgmm_resnet1d_desc d;
-  int L1, L2;
-  Blk1 blk[3];
-  int p_cls;
-  size_t max_act;
-};
-int build1d_static(const ecgmm_resnet1d_desc* d, I1D& r) {
-  if (!d) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet1d infer: null desc");
-  ECG_TRY(check_dtype(d->dtype, "resnet1d infer"));
+int build1d_static(const ecgmm_resnet1d_desc* d, Net1D& r) {
+  ECG_TRY(net1d_static(d, r, "resnet1d infer"));
   if (d->cin < 1 || d->cin > 24) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet1d infer: cin %d (1..24)", d->cin);
   if (d->num_classes < 1) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet1d infer: num_classes %d", d->num_classes);
   if (!(d->bn_eps >= 0.f)) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet1d infer: bn_eps %g", (double)d->bn_eps);
-  r.d = *d;
-  int pi = 4, bi = 3, cin = 64;
-  for (int i = 0; i < 3; ++i) {
-    Blk1& k = r.blk[i];
-    k.cin = cin; k.cout = 64 << i; k.stride = i == 0 ? 1 : 2;
-    k.cr = k.cout / 16;
-    k.down = (k.stride != 1 || k.cin != k.cout);
-    k.p0 = pi; k.b0 = bi;
-    pi += k.down ? 16 : 12;
-    bi += k.down ? 9 : 6;
-    cin = k.cout;
-  }
-  r.p_cls = pi;
-  if (pi + 4 != ECGMM_RESNET1D_NPARAMS || bi != ECGMM_RESNET1D_NBUFFERS)
-    ECG_FAIL(ECGMM_ERR_SHAPE, "resnet1d infer: internal table mismatch %d %d", pi + 4, bi);
   return 0;
 }
-int build1d(const ecgmm_resnet1d_desc* d, I1D& r) {
+int build1d(const ecgmm_resnet1d_desc* d, Net1D& r) {
   ECG_TRY(build1d_static(d, r));
-  if (d->N < 1 || d->L < 64) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet1d infer: bad input N=%d L=%d", d->N, d->L);
-  r.L1 = (d->L + 6 - 7) / 2 + 1;
-  r.L2 = (r.L1 + 2 - 3) / 2 + 1;
-  int l = r.L2;
-  r.max_act = (size_t)d->N * r.L2 * 64;
-  for (int i = 0; i < 3; ++i) {
-    Blk1& k = r.blk[i];
-    k.lin = l; k.lout = (l + 2 - 3) / k.stride + 1;
-    const size_t a = (size_t)d->N * k.lout * k.cout;
-    if (a > r.max_act) r.max_act = a;
-    l = k.lout;
-  }
-  return 0;
+  return net1d_shape(r, "resnet1d infer");
 }
 
 struct Blob1D {
@@ -229,7 +132,7 @@ struct Blob1D {
   float *cw1, *cb1, *cw2, *cb2;
   size_t bytes;
 };
-void layout_blob1d(const I1D& r, void* base, Blob1D& q) {
+void layout_blob1d(const Net1D& r, void* base, Blob1D& q) {
   Arena a(base);
   const size_t es = dtype_size(r.d.dtype);
   q.wstem = a.take_bytes(ecg_stem_packed_elems(r.d.cin, 1) * es);
@@ -261,7 +164,7 @@ struct Ws1D {
   float *m, *h, *g, *pooled, *h1;
   size_t bytes;
 };
-void layout_ws1d(const I1D& r, void* base, Ws1D& w) {
+void layout_ws1d(const Net1D& r, void* base, Ws1D& w) {
   Arena a(base);
   const size_t es = dtype_size(r.d.dtype);
   const size_t act = align_up(r.max_act * es, 256), y0 = (size_t)r.d.N * r.L1 * 64 * es;
@@ -306,7 +209,7 @@ EcgFoldItem copy_item(const float* src, float* dst, int rows, int cols) {
 
 // ---- ResNet18 ------------------------------------------------------------------------------------------------------
 extern "C" size_t ecgmm_resnet18_infer_prepared_bytes(const ecgmm_resnet18_desc* d) {
-  I18 r;
+  Net18 r;
   if (build18_static(d, r)) return 0;
   Blob18 q;
   layout_blob18(r, nullptr, q);
@@ -315,12 +218,12 @@ extern "C" size_t ecgmm_resnet18_infer_prepared_bytes(const ecgmm_resnet18_desc*
 
 extern "C" int ecgmm_resnet18_infer_prepare(const ecgmm_resnet18_desc* d, const void* const* params,
                                             const void* const* buffers, void* blob, size_t blob_bytes, void* stream_) {
-  I18 r;
+  Net18 r;
   ECG_TRY(build18_static(d, r));
   ECG_TRY(check_tables(params, ECGMM_RESNET18_NPARAMS, buffers, ECGMM_RESNET18_NBUFFERS, "resnet18 infer prepare"));
   Blob18 q;
   layout_blob18(r, blob, q);
-  if (!blob || blob_bytes < q.bytes) ECG_FAIL(ECGMM_ERR_WORKSPACE, "resnet18 infer prepare: blob %zu < %zu", blob_bytes, q.bytes);
+  ECG_NEED(blob, blob_bytes, q.bytes, "resnet18 infer prepare: blob");
   EcgFoldItem items[ECG_FOLD_MAX];
   int n = 0;
   items[n++] = conv_item(ECG_FOLD_STEM, params, 0, nullptr, 1, buffers, 0, q.wstem, q.bstem, 64, 3, 7);
@@ -338,7 +241,7 @@ extern "C" int ecgmm_resnet18_infer_prepare(const ecgmm_resnet18_desc* d, const 
 }
 
 extern "C" size_t ecgmm_resnet18_infer_workspace(const ecgmm_resnet18_desc* d) {
-  I18 r;
+  Net18 r;
   if (build18(d, r)) return 0;
   Ws18 w;
   layout_ws18(r, nullptr, w);
@@ -353,22 +256,21 @@ extern "C" int ecgmm_infer_down_side(int on) {
 extern "C" int ecgmm_resnet18_infer(const ecgmm_resnet18_desc* d, const float* image, const void* blob, size_t blob_bytes,
                                     float* feat_out, void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t s = (hipStream_t)stream_;
-  I18 r;
+  Net18 r;
   ECG_TRY(build18(d, r));
   if (!image || !feat_out) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet18 infer: null image / output");
   Blob18 q;
   layout_blob18(r, const_cast<void*>(blob), q);
-  if (!blob || blob_bytes < q.bytes) ECG_FAIL(ECGMM_ERR_WORKSPACE, "resnet18 infer: blob %zu < %zu", blob_bytes, q.bytes);
+  ECG_NEED(blob, blob_bytes, q.bytes, "resnet18 infer: blob");
   Ws18 w;
   layout_ws18(r, ws, w);
-  if (!ws || ws_bytes < w.bytes) ECG_FAIL(ECGMM_ERR_WORKSPACE, "resnet18 infer: workspace %zu < %zu", ws_bytes, w.bytes);
+  ECG_NEED(ws, ws_bytes, w.bytes, "resnet18 infer: workspace");
   const int dt = r.d.dtype, N = r.d.N;
   const bool side = down_side_on();
   if (side) ECG_TRY(g_side_inf.init());
 
   // (bf16: the instantiation the eval forward of the training plan runs)
-  if (dt == ECGMM_BF16) ECG_TRY(ecg_stem_fwd_wgrows(dt, image, q.wstem, q.bstem, w.y0, nullptr, N, 3, r.d.H, r.d.W, 7, s));
-  else ECG_TRY(ecg_stem_fwd(dt, image, q.wstem, q.bstem, w.y0, nullptr, N, 3, r.d.H, r.d.W, 7, s));
+  ECG_TRY(stem_forward(dt, image, q.wstem, q.bstem, w.y0, nullptr, N, 3, r.d.H, r.d.W, 7, s));
   ECG_TRY(ecg_relu_maxpool(dt, w.y0, w.rot[0], N, r.H1, r.W1, 64, s));
 
   Rot rot = {{w.rot[0], w.rot[1], w.rot[2], w.rot[3]}, 0, 0u};
@@ -379,9 +281,9 @@ extern "C" int ecgmm_resnet18_infer(const ecgmm_resnet18_desc* d, const float* i
     void* a1 = rot.take();
     void* yd = k.down ? rot.take() : nullptr;
     void* out = rot.take();
-    const ConvGeom g1 = make_geom(N, k.hin, k.win, k.cin, k.cout, 3, 3, k.stride, 1, 1);
-    const ConvGeom g2 = make_geom(N, k.hout, k.wout, k.cout, k.cout, 3, 3, 1, 1, 1);
-    const ConvGeom gd = make_geom(N, k.hin, k.win, k.cin, k.cout, 1, 1, k.stride, 0, 0);
+    const ConvGeom g1 = k.conv1_geom(N);
+    const ConvGeom g2 = k.conv2_geom(N);
+    const ConvGeom gd = k.down_geom(N);
     hipEvent_t down_done = nullptr;
     if (k.down && side) {
       g_side_inf.fork(s);
@@ -401,7 +303,7 @@ extern "C" int ecgmm_resnet18_infer(const ecgmm_resnet18_desc* d, const float* i
 
 // ---- ResNet1D_SE ---------------------------------------------------------------------------------------------------
 extern "C" size_t ecgmm_resnet1d_infer_prepared_bytes(const ecgmm_resnet1d_desc* d) {
-  I1D r;
+  Net1D r;
   if (build1d_static(d, r)) return 0;
   Blob1D q;
   layout_blob1d(r, nullptr, q);
@@ -410,12 +312,12 @@ extern "C" size_t ecgmm_resnet1d_infer_prepared_bytes(const ecgmm_resnet1d_desc*
 
 extern "C" int ecgmm_resnet1d_infer_prepare(const ecgmm_resnet1d_desc* d, const void* const* params,
                                             const void* const* buffers, void* blob, size_t blob_bytes, void* stream_) {
-  I1D r;
+  Net1D r;
   ECG_TRY(build1d_static(d, r));
   ECG_TRY(check_tables(params, ECGMM_RESNET1D_NPARAMS, buffers, ECGMM_RESNET1D_NBUFFERS, "resnet1d infer prepare"));
   Blob1D q;
   layout_blob1d(r, blob, q);
-  if (!blob || blob_bytes < q.bytes) ECG_FAIL(ECGMM_ERR_WORKSPACE, "resnet1d infer prepare: blob %zu < %zu", blob_bytes, q.bytes);
+  ECG_NEED(blob, blob_bytes, q.bytes, "resnet1d infer prepare: blob");
   EcgFoldItem items[ECG_FOLD_MAX];
   int n = 0;
   items[n++] = conv_item(ECG_FOLD_STEM, params, 0, P(params, 1), 2, buffers, 0, q.wstem, q.bstem, 64, r.d.cin, 1);
@@ -423,25 +325,28 @@ extern "C" int ecgmm_resnet1d_infer_prepare(const ecgmm_resnet1d_desc* d, const 
     const Blk1& k = r.blk[i];
     const Blob1D::B& b = q.b[i];
     const int p = k.p0, bb = k.b0;
-    items[n++] = conv_item(ECG_FOLD_CONV, params, p, P(params, p + 1), p + 2, buffers, bb, b.w1, b.b1, k.cout, k.cin, 3);
-    items[n++] = conv_item(ECG_FOLD_CONV, params, p + 4, P(params, p + 5), p + 6, buffers, bb + 3, b.w2, b.b2, k.cout, k.cout, 3);
-    items[n++] = copy_item(P(params, p + 8), b.sw1, k.cr, k.cout);
-    items[n++] = copy_item(P(params, p + 9), b.sb1, k.cr, 1);
-    items[n++] = copy_item(P(params, p + 10), b.sw2, k.cout, k.cr);
-    items[n++] = copy_item(P(params, p + 11), b.sb2, k.cout, 1);
+    items[n++] = conv_item(ECG_FOLD_CONV, params, p + T1_CONV1_W, P(params, p + T1_CONV1_B), p + T1_BN1, buffers, bb + T1B_BN1,
+                           b.w1, b.b1, k.cout, k.cin, 3);
+    items[n++] = conv_item(ECG_FOLD_CONV, params, p + T1_CONV2_W, P(params, p + T1_CONV2_B), p + T1_BN2, buffers, bb + T1B_BN2,
+                           b.w2, b.b2, k.cout, k.cout, 3);
+    items[n++] = copy_item(P(params, p + T1_SE_W1), b.sw1, k.cr, k.cout);
+    items[n++] = copy_item(P(params, p + T1_SE_B1), b.sb1, k.cr, 1);
+    items[n++] = copy_item(P(params, p + T1_SE_W2), b.sw2, k.cout, k.cr);
+    items[n++] = copy_item(P(params, p + T1_SE_B2), b.sb2, k.cout, 1);
     if (k.down)
-      items[n++] = conv_item(ECG_FOLD_CONV, params, p + 12, P(params, p + 13), p + 14, buffers, bb + 6, b.wd, b.bd, k.cout, k.cin, 1);
+      items[n++] = conv_item(ECG_FOLD_CONV, params, p + T1_DOWN_W, P(params, p + T1_DOWN_B), p + T1_DBN, buffers, bb + T1B_DBN,
+                             b.wd, b.bd, k.cout, k.cin, 1);
   }
   const int pc = r.p_cls;
-  items[n++] = copy_item(P(params, pc), q.cw1, 64, 256);
-  items[n++] = copy_item(P(params, pc + 1), q.cb1, 64, 1);
-  items[n++] = copy_item(P(params, pc + 2), q.cw2, r.d.num_classes, 64);
-  items[n++] = copy_item(P(params, pc + 3), q.cb2, r.d.num_classes, 1);
+  items[n++] = copy_item(P(params, pc + T1_CLS_W1), q.cw1, 64, 256);
+  items[n++] = copy_item(P(params, pc + T1_CLS_B1), q.cb1, 64, 1);
+  items[n++] = copy_item(P(params, pc + T1_CLS_W2), q.cw2, r.d.num_classes, 64);
+  items[n++] = copy_item(P(params, pc + T1_CLS_B2), q.cb2, r.d.num_classes, 1);
   return ecg_fold_batch(r.d.dtype, items, n, r.d.bn_eps, (hipStream_t)stream_);
 }
 
 extern "C" size_t ecgmm_resnet1d_infer_workspace(const ecgmm_resnet1d_desc* d) {
-  I1D r;
+  Net1D r;
   if (build1d(d, r)) return 0;
   Ws1D w;
   layout_ws1d(r, nullptr, w);
@@ -451,19 +356,18 @@ extern "C" size_t ecgmm_resnet1d_infer_workspace(const ecgmm_resnet1d_desc* d) {
 extern "C" int ecgmm_resnet1d_infer(const ecgmm_resnet1d_desc* d, const float* signal, const void* blob, size_t blob_bytes,
                                     float* feat_out, void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t s = (hipStream_t)stream_;
-  I1D r;
+  Net1D r;
   ECG_TRY(build1d(d, r));
   if (!signal || !feat_out) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet1d infer: null signal / output");
   Blob1D q;
   layout_blob1d(r, const_cast<void*>(blob), q);
-  if (!blob || blob_bytes < q.bytes) ECG_FAIL(ECGMM_ERR_WORKSPACE, "resnet1d infer: blob %zu < %zu", blob_bytes, q.bytes);
+  ECG_NEED(blob, blob_bytes, q.bytes, "resnet1d infer: blob");
   Ws1D w;
   layout_ws1d(r, ws, w);
-  if (!ws || ws_bytes < w.bytes) ECG_FAIL(ECGMM_ERR_WORKSPACE, "resnet1d infer: workspace %zu < %zu", ws_bytes, w.bytes);
+  ECG_NEED(ws, ws_bytes, w.bytes, "resnet1d infer: workspace");
   const int dt = r.d.dtype, N = r.d.N, cin = r.d.cin;
 
-  if (dt == ECGMM_BF16) ECG_TRY(ecg_stem_fwd_wgrows(dt, signal, q.wstem, q.bstem, w.y0, nullptr, N, cin, 1, r.d.L, 1, s));
-  else ECG_TRY(ecg_stem_fwd(dt, signal, q.wstem, q.bstem, w.y0, nullptr, N, cin, 1, r.d.L, 1, s));
+  ECG_TRY(stem_forward(dt, signal, q.wstem, q.bstem, w.y0, nullptr, N, cin, 1, r.d.L, 1, s));
   ECG_TRY(ecg_relu_maxpool(dt, w.y0, w.rot[0], N, 1, r.L1, 64, s));
 
   Rot rot = {{w.rot[0], w.rot[1], w.rot[2], w.rot[3]}, 0, 0u};
@@ -475,20 +379,15 @@ extern "C" int ecgmm_resnet1d_infer(const ecgmm_resnet1d_desc* d, const float* s
     void* y2 = rot.take();
     void* yd = k.down ? rot.take() : nullptr;
     const long M = (long)N * k.lout;
-    const ConvGeom g1 = make_geom(N, 1, k.lin, k.cin, k.cout, 1, 3, k.stride, 0, 1);
-    const ConvGeom g2 = make_geom(N, 1, k.lout, k.cout, k.cout, 1, 3, 1, 0, 1);
+    const ConvGeom g1 = k.conv1_geom(N);
+    const ConvGeom g2 = k.conv2_geom(N);
     ECG_TRY(ecg_conv_igemm(dt, 0, g1, cur, b.w1, a1, b.b1, nullptr, nullptr, 1, s));
     ECG_TRY(ecg_conv_igemm(dt, 0, g2, a1, b.w2, y2, b.b2, nullptr, nullptr, 0, s));
     // squeeze-excite gate from mean_L(y2): y2 already IS bn2(conv2(a1))
     ECG_TRY(ecg_avgpool(dt, y2, w.m, N, k.lout, k.cout, nullptr, s));
-    if (ecg_se_mlp_fused_ok(k.cout, k.cr)) {
-      ECG_TRY(ecg_se_mlp_fwd(w.m, b.sw1, b.sb1, b.sw2, b.sb2, w.h, w.g, N, k.cout, k.cr, s));
-    } else {
-      ECG_TRY(ecg_linear_fwd(w.m, b.sw1, b.sb1, w.h, N, k.cout, k.cr, ECGMM_ACT_RELU, nullptr, s));
-      ECG_TRY(ecg_linear_fwd(w.h, b.sw2, b.sb2, w.g, N, k.cr, k.cout, ECGMM_ACT_SIGMOID, nullptr, s));
-    }
+    ECG_TRY(se_mlp_forward(w.m, b.sw1, b.sb1, b.sw2, b.sb2, w.h, w.g, N, k.cout, k.cr, s));
     if (k.down) {
-      const ConvGeom gd = make_geom(N, 1, k.lin, k.cin, k.cout, 1, 1, k.stride, 0, 0);
+      const ConvGeom gd = k.down_geom(N);
       ECG_TRY(ecg_conv_igemm(dt, 0, gd, cur, b.wd, yd, b.bd, nullptr, nullptr, 0, s));
     }
     ECG_TRY(ecg_gate_res_relu(dt, y2, w.g, k.down ? yd : cur, y2, M, k.cout, k.lout, s));

@@ -5,16 +5,8 @@
 // Activations live channels-last in the compute dtype inside a caller-owned workspace; the image
 // enters as NCHW fp32 exactly as the reference's DataLoader hands it over.
 //
-// Parameter table order (62 entries, == named_parameters() order of the Python module):
-//   conv1.weight, bn1.weight, bn1.bias,
-//   layer{1..4}.{0,1}.{conv1.weight, bn1.weight, bn1.bias, conv2.weight, bn2.weight, bn2.bias,
-//                      [downsample.0.weight, downsample.1.weight, downsample.1.bias]},
-//   fc.weight, fc.bias
-// Buffer table order (60 entries): per BatchNorm in the same walk: running_mean, running_var,
-//   num_batches_tracked (int64).
-#include <stdlib.h>
-
-#include "ops.h"
+// The network description (block table, parameter / buffer table order, geometry): net_desc.h.
+#include "plan_common.h"
 #include "side_stream.h"
 
 namespace {
@@ -24,72 +16,21 @@ namespace {
 // forward 418 -> 396 us, backward 401 -> 584 us.  Kept as a tested option (memory: -1.2 GB of workspace at batch 256).
 int g_stem_recompute = -1;
 bool stem_recompute(int dtype) {
-  if (g_stem_recompute < 0) { const char* e = getenv("ECGMM_STEM_RECOMPUTE"); g_stem_recompute = (e && e[0] == '1'); }
+  if (g_stem_recompute < 0) g_stem_recompute = env_off("ECGMM_STEM_RECOMPUTE");
   return g_stem_recompute != 0 && ecg_stem_fused_ok(dtype, 3, 7);
 }
 // bn2's backward takes the block's ReLU mask from one bit per element written by the forward activation pass instead of re-reading
 // the activated tensor (ECGMM_RELU_BITS=0: re-read it).  Read once per process: forward and backward must agree.
 bool relu_bits_on() {
-  static const bool on = [] { const char* e = getenv("ECGMM_RELU_BITS"); return !(e && e[0] == '0'); }();
+  static const bool on = env_on("ECGMM_RELU_BITS");
   return on;
 }
 constexpr long FUSE_NEVER = 1L << 40;
 long g_fuse_min_m = -1;  // pixel-count threshold of the fused BatchNorm-backward reductions (-1: read ECGMM_BN_FUSE_MIN_M)
 
-struct BlockCfg {
-  int cin, cout, stride, hin, win, hout, wout;
-  bool down;
-  int p_conv1, p_bn1, p_conv2, p_bn2, p_dconv, p_dbn;  // param indices (weight; bn bias = +1)
-  int b_bn1, b_bn2, b_dbn;                              // buffer indices (rm; rv = +1; nbt = +2)
-};
-
-struct R18 {
-  ecgmm_resnet18_desc d;
-  int H1, W1, H2, W2;
-  BlockCfg blk[8];
-  int p_fc;
-  size_t max_act;  // largest block-level activation (elements)
-};
-
-int build(const ecgmm_resnet18_desc* d, R18& r) {
-  if (!d) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet18: null desc");
-  if (d->dtype != ECGMM_BF16 && d->dtype != ECGMM_F32) ECG_FAIL(ECGMM_ERR_DTYPE, "resnet18: bad dtype %d", d->dtype);
-  if (d->N < 1 || d->H < 32 || d->W < 32) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet18: bad input %dx%dx%d", d->N, d->H, d->W);
-  r.d = *d;
-  r.H1 = (d->H + 6 - 7) / 2 + 1;
-  r.W1 = (d->W + 6 - 7) / 2 + 1;
-  r.H2 = (r.H1 + 2 - 3) / 2 + 1;
-  r.W2 = (r.W1 + 2 - 3) / 2 + 1;
-  int pi = 3, bi = 3, h = r.H2, w = r.W2, cin = 64;
-  r.max_act = 0;
-  for (int L = 0; L < 4; ++L) {
-    int cout = 64 << L;
-    for (int b = 0; b < 2; ++b) {
-      BlockCfg& k = r.blk[L * 2 + b];
-      k.cin = cin; k.cout = cout; k.stride = (b == 0 && L > 0) ? 2 : 1;
-      k.hin = h; k.win = w;
-      k.hout = (h + 2 - 3) / k.stride + 1;
-      k.wout = (w + 2 - 3) / k.stride + 1;
-      k.down = (k.stride != 1 || cin != cout);
-      k.p_conv1 = pi; k.p_bn1 = pi + 1; k.p_conv2 = pi + 3; k.p_bn2 = pi + 4; pi += 6;
-      k.b_bn1 = bi; k.b_bn2 = bi + 3; bi += 6;
-      if (k.down) {
-        k.p_dconv = pi; k.p_dbn = pi + 1; pi += 3;
-        k.b_dbn = bi; bi += 3;
-      } else {
-        k.p_dconv = k.p_dbn = k.b_dbn = -1;
-      }
-      size_t a = (size_t)d->N * k.hin * k.win * k.cin;
-      if (a > r.max_act) r.max_act = a;
-      a = (size_t)d->N * k.hout * k.wout * k.cout;
-      if (a > r.max_act) r.max_act = a;
-      h = k.hout; w = k.wout; cin = cout;
-    }
-  }
-  r.p_fc = pi;
-  if (pi + 2 != ECGMM_RESNET18_NPARAMS || bi != ECGMM_RESNET18_NBUFFERS)
-    ECG_FAIL(ECGMM_ERR_SHAPE, "resnet18: internal table mismatch %d %d", pi + 2, bi);
-  return 0;
+int build(const ecgmm_resnet18_desc* d, Net18& r) {
+  ECG_TRY(net18_static(d, r, "resnet18"));
+  return net18_shape(r, "resnet18");
 }
 
 // saved-for-backward workspace
@@ -108,7 +49,7 @@ struct FwdWs {
   size_t bytes;
 };
 
-void layout_fwd(const R18& r, void* base, FwdWs& w) {
+void layout_fwd(const Net18& r, void* base, FwdWs& w) {
   Arena a(base);
   const size_t es = dtype_size(r.d.dtype);
   const int N = r.d.N;
@@ -123,7 +64,7 @@ void layout_fwd(const R18& r, void* base, FwdWs& w) {
   max_rows_c += (size_t)ECG_TAIL_ROWS * 2 * 64;
   size_t max_rows_d = 64;
   for (int i = 0; i < 8; ++i) {
-    const BlockCfg& k = r.blk[i];
+    const Blk18& k = r.blk[i];
     FwdWs::B& b = w.b[i];
     size_t osz = (size_t)N * k.hout * k.wout * k.cout;
     b.w1f = a.take_bytes((size_t)k.cout * k.cin * 9 * es);
@@ -179,7 +120,7 @@ struct BwdWs {
   size_t bytes;
 };
 
-void layout_bwd(const R18& r, void* base, BwdWs& w) {
+void layout_bwd(const Net18& r, void* base, BwdWs& w) {
   Arena a(base);
   const size_t es = dtype_size(r.d.dtype);
   const int N = r.d.N;
@@ -200,15 +141,15 @@ void layout_bwd(const R18& r, void* base, BwdWs& w) {
   size_t bn = ecg_bn_bwd_scratch(r.d.dtype, (long)N * r.H1 * r.W1, 64);
   size_t wg = 0;
   for (int i = 0; i < 8; ++i) {
-    const BlockCfg& k = r.blk[i];
+    const Blk18& k = r.blk[i];
     size_t s = ecg_bn_bwd_scratch(r.d.dtype, (long)N * k.hout * k.wout, k.cout);
     if (s > bn) bn = s;
-    size_t g1 = ecg_conv_wgrad_workspace(r.d.dtype, make_geom(N, k.hin, k.win, k.cin, k.cout, 3, 3, k.stride, 1, 1));
-    size_t g2 = ecg_conv_wgrad_workspace(r.d.dtype, make_geom(N, k.hout, k.wout, k.cout, k.cout, 3, 3, 1, 1, 1));
+    size_t g1 = ecg_conv_wgrad_workspace(r.d.dtype, k.conv1_geom(N));
+    size_t g2 = ecg_conv_wgrad_workspace(r.d.dtype, k.conv2_geom(N));
     if (g1 > wg) wg = g1;
     if (g2 > wg) wg = g2;
     if (k.down) {
-      size_t g3 = ecg_conv_wgrad_workspace(r.d.dtype, make_geom(N, k.hin, k.win, k.cin, k.cout, 1, 1, k.stride, 0, 0));
+      size_t g3 = ecg_conv_wgrad_workspace(r.d.dtype, k.down_geom(N));
       if (g3 > wg) wg = g3;
     }
   }
@@ -231,24 +172,10 @@ inline hipEvent_t side_next_ev() { return g_side.next_ev(); }
 inline void side_fork(hipStream_t main) { g_side.fork(main); }
 inline hipEvent_t side_mark() { return g_side.mark(); }
 
-inline const float* P(const void* const* params, int i) { return (const float*)params[i]; }
-inline float* G(void* const* grads, int i) { return grads ? (float*)grads[i] : nullptr; }
-
-// BN statistics of a fresh conv output -> coefficients (train: batch stats + running update; eval: running stats)
-int bn_coef(const R18& r, const float* stats, int rows, int C, long count, const void* const* params, int p_bn,
-            void* const* buffers, int b_bn, float* coef, hipStream_t s) {
-  if (r.d.training)
-    return ecg_bn_finalize(stats, rows, C, (double)count, P(params, p_bn), P(params, p_bn + 1), (float*)buffers[b_bn],
-                           (float*)buffers[b_bn + 1], (long long*)buffers[b_bn + 2], r.d.bn_momentum, r.d.bn_eps, coef,
-                           s);
-  return ecg_bn_eval_coef(C, P(params, p_bn), P(params, p_bn + 1), (const float*)buffers[b_bn],
-                          (const float*)buffers[b_bn + 1], r.d.bn_eps, coef, s);
-}
-
 // BatchNorm (training statistics from a conv's partial rows, or running statistics in eval mode) + activation pass.
 // Where the rows are few enough the finalize is folded into the activation pass itself (ecg_bn_act_fold: one dependent
 // ~5 us launch less on the forward's critical path, 16 times per forward).
-int bn_then_act(const R18& r, const float* stats, int rows, int C, long count, const void* const* params, int p_bn,
+int bn_then_act(const Net18& r, const float* stats, int rows, int C, long count, const void* const* params, int p_bn,
                 void* const* buffers, int b_bn, float* coef, const void* y, const void* res, const float* rcoef, void* out,
                 hipStream_t s, unsigned char* relu_bits = nullptr) {
   const int dt = r.d.dtype;
@@ -257,24 +184,12 @@ int bn_then_act(const R18& r, const float* stats, int rows, int C, long count, c
                    (float*)buffers[b_bn + 1], (long long*)buffers[b_bn + 2], r.d.bn_momentum, r.d.bn_eps};
     return ecg_bn_act_fold(dt, y, coef, f, res, rcoef, nullptr, 1, 1, out, count, C, s, relu_bits);
   }
-  ECG_TRY(bn_coef(r, stats, rows, C, count, params, p_bn, buffers, b_bn, coef, s));
+  ECG_TRY(bn_coef(r.bn, stats, rows, C, count, params, p_bn, buffers, b_bn, coef, s));
   return ecg_bn_act(dt, y, coef, res, rcoef, nullptr, 1, 1, out, count, C, s, relu_bits);
 }
 
-// BatchNorm backward of either forward mode: the training form (batch statistics: reduce + apply) or, behind an eval-mode
-// forward, the one-pass affine form (bn_eval_bwd.hip).  The training call is exactly the one the plan always made.
-int bn_bwd_mode(const R18& r, const void* dout, const void* maskref, const void* y, const float* coef, const float* gamma,
-                float* dgamma, float* dbeta, void* dy, void* dz_out, long M, int C, float* scratch, hipStream_t s,
-                const unsigned char* mask_bits = nullptr) {
-  if (r.d.training)
-    return ecg_bn_bwd(r.d.dtype, dout, maskref, nullptr, nullptr, 1, y, coef, gamma, dgamma, dbeta, dy, dz_out, nullptr, M,
-                      C, scratch, s, mask_bits);
-  return ecg_bn_eval_bwd(r.d.dtype, dout, maskref, nullptr, nullptr, 1, y, coef, dgamma, dbeta, dy, dz_out, nullptr, M, C,
-                         scratch, s);
-}
-
 // stage 0 up to the pooled features: d loss / d pooled [N][512] (+ the fc parameter gradients)
-int fc_bwd(const R18& r, const FwdWs& w, const BwdWs& q, const float* dfeat, const void* const* params, void* const* grads,
+int fc_bwd(const Net18& r, const FwdWs& w, const BwdWs& q, const float* dfeat, const void* const* params, void* const* grads,
            hipStream_t s) {
   return ecg_linear_bwd(dfeat, w.pooled, P(params, r.p_fc), q.dpooled, G(grads, r.p_fc), G(grads, r.p_fc + 1), r.d.N, 512,
                         r.d.out_dim, q.lin_ws, q.lin_bytes, s);
@@ -322,7 +237,7 @@ extern "C" int ecgmm_side_fork(void* stream) {
 }
 
 extern "C" size_t ecgmm_resnet18_fwd_workspace(const ecgmm_resnet18_desc* d) {
-  R18 r;
+  Net18 r;
   if (build(d, r)) return 0;
   FwdWs w;
   layout_fwd(r, nullptr, w);
@@ -330,7 +245,7 @@ extern "C" size_t ecgmm_resnet18_fwd_workspace(const ecgmm_resnet18_desc* d) {
 }
 
 extern "C" size_t ecgmm_resnet18_bwd_workspace(const ecgmm_resnet18_desc* d) {
-  R18 r;
+  Net18 r;
   if (build(d, r)) return 0;
   BwdWs w;
   layout_bwd(r, nullptr, w);
@@ -341,15 +256,15 @@ extern "C" int ecgmm_resnet18_forward(const ecgmm_resnet18_desc* d, const float*
                                       void* const* buffers, float* feat_out, void* ws, size_t ws_bytes,
                                       void* stream_) {
   hipStream_t s = (hipStream_t)stream_;
-  R18 r;
+  Net18 r;
   ECG_TRY(build(d, r));
   FwdWs w;
   layout_fwd(r, ws, w);
-  if (!ws || ws_bytes < w.bytes) ECG_FAIL(ECGMM_ERR_WORKSPACE, "resnet18 fwd: workspace %zu < %zu", ws_bytes, w.bytes);
+  ECG_NEED(ws, ws_bytes, w.bytes, "resnet18 fwd: workspace");
   const int dt = r.d.dtype, N = r.d.N;
   const int stats_rows = r.d.training ? 1 : 0;
   ECG_TRY(side_init());
-  static const bool down_side_on = [] { const char* e = getenv("ECGMM_DOWN_SIDE"); return !(e && e[0] == '0'); }();
+  static const bool down_side_on = env_on("ECGMM_DOWN_SIDE");
   const bool side_fwd = g_side.enabled && down_side_on;
 
   ecg_tl_mark(100, s);
@@ -360,7 +275,7 @@ extern "C" int ecgmm_resnet18_forward(const ecgmm_resnet18_desc* d, const float*
     EcgPackItem items[ECG_PACK_MAX];
     int n = 0;
     for (int i = 0; i < 8; ++i) {
-      const BlockCfg& k = r.blk[i];
+      const Blk18& k = r.blk[i];
       FwdWs::B& b = w.b[i];
       items[n++] = {P(params, k.p_conv1), b.w1f, b.w1d, k.cout, k.cin, 9};
       items[n++] = {P(params, k.p_conv2), b.w2f, b.w2d, k.cout, k.cout, 9};
@@ -374,32 +289,25 @@ extern "C" int ecgmm_resnet18_forward(const ecgmm_resnet18_desc* d, const float*
     // pass 1: statistics only; pass 2: conv recomputed -> bn -> relu -> max-pool.  The 64 x H1 x W1 conv output (411 MB at
     // batch 256) is never written: 154 + 154 MB read, 154 MB written instead of 154 + 411 + 411 read/written + 154
     if (stats_rows) ECG_TRY(ecg_stem_stats_only(dt, image, w.wstem, nullptr, w.stats, N, 3, r.d.H, r.d.W, 7, s));
-    ECG_TRY(bn_coef(r, w.stats, ecg_stem_stats_only_rows(N, 3, r.d.H, r.d.W, 7), 64, (long)N * r.H1 * r.W1, params, 1,
+    ECG_TRY(bn_coef(r.bn, w.stats, ecg_stem_stats_only_rows(N, 3, r.d.H, r.d.W, 7), 64, (long)N * r.H1 * r.W1, params, 1,
                     buffers, 0, w.coef0, s));
     ECG_TRY(ecg_stem_pool_fwd(image, w.wstem, w.coef0, w.p0, w.idx0, N, 3, r.d.H, r.d.W, s));
   } else {
-    // (bf16: statistics rows per workgroup -- sums kept in registers across the workgroup's tiles -- instead of per tile)
-    if (dt == ECGMM_BF16) {
-      ECG_TRY(ecg_stem_fwd_wgrows(dt, image, w.wstem, nullptr, w.y0, stats_rows ? w.stats : nullptr, N, 3, r.d.H, r.d.W, 7, s));
-      ECG_TRY(bn_coef(r, w.stats, ecg_stem_wg_stats_rows(N, 3, r.d.H, r.d.W, 7), 64, (long)N * r.H1 * r.W1, params, 1,
-                      buffers, 0, w.coef0, s));
-    } else {
-      ECG_TRY(ecg_stem_fwd(dt, image, w.wstem, nullptr, w.y0, stats_rows ? w.stats : nullptr, N, 3, r.d.H, r.d.W, 7, s));
-      ECG_TRY(bn_coef(r, w.stats, ecg_stem_stats_rows(N, 3, r.d.H, r.d.W, 7), 64, (long)N * r.H1 * r.W1, params, 1,
-                      buffers, 0, w.coef0, s));
-    }
+    ECG_TRY(stem_forward(dt, image, w.wstem, nullptr, w.y0, stats_rows ? w.stats : nullptr, N, 3, r.d.H, r.d.W, 7, s));
+    ECG_TRY(bn_coef(r.bn, w.stats, stem_forward_rows(dt, N, 3, r.d.H, r.d.W, 7), 64, (long)N * r.H1 * r.W1, params, 1,
+                    buffers, 0, w.coef0, s));
     ECG_TRY(ecg_bnrelu_maxpool(dt, w.y0, w.coef0, w.p0, w.idx0, N, r.H1, r.W1, 64, s));
   }
 
   ecg_tl_mark(101, s);
   const void* cur = w.p0;
   for (int i = 0; i < 8; ++i) {
-    const BlockCfg& k = r.blk[i];
+    const Blk18& k = r.blk[i];
     FwdWs::B& b = w.b[i];
     const long M = (long)N * k.hout * k.wout;
     const int rows = ecg_conv_stats_rows(M);
-    ConvGeom g1 = make_geom(N, k.hin, k.win, k.cin, k.cout, 3, 3, k.stride, 1, 1);
-    ConvGeom g2 = make_geom(N, k.hout, k.wout, k.cout, k.cout, 3, 3, 1, 1, 1);
+    ConvGeom g1 = k.conv1_geom(N);
+    ConvGeom g2 = k.conv2_geom(N);
     // (ConvEpi.wg_rows: the halo kernel writes one partial-sum row per workgroup instead of one per 64 pixels)
     ConvEpi e1 = {}, e2 = {};
     e1.wg_rows = e2.wg_rows = 1;
@@ -408,10 +316,10 @@ extern "C" int ecgmm_resnet18_forward(const ecgmm_resnet18_desc* d, const float*
     hipEvent_t down_done = nullptr;
     const bool down_side = k.down && side_fwd;
     if (down_side) {
-      ConvGeom gd = make_geom(N, k.hin, k.win, k.cin, k.cout, 1, 1, k.stride, 0, 0);
+      ConvGeom gd = k.down_geom(N);
       side_fork(s);
       ECG_TRY(ecg_conv_igemm(dt, 0, gd, cur, b.wdf, b.yd, nullptr, nullptr, stats_rows ? w.stats_d : nullptr, 0, g_side.s));
-      ECG_TRY(bn_coef(r, w.stats_d, rows, k.cout, M, params, k.p_dbn, buffers, k.b_dbn, b.coefd, g_side.s));
+      ECG_TRY(bn_coef(r.bn, w.stats_d, rows, k.cout, M, params, k.p_dbn, buffers, k.b_dbn, b.coefd, g_side.s));
       down_done = side_mark();
     }
     ECG_TRY(ecg_conv_igemm(dt, 0, g1, cur, b.w1f, b.y1, nullptr, nullptr, stats_rows ? w.stats : nullptr, 0, s, &e1));
@@ -422,10 +330,10 @@ extern "C" int ecgmm_resnet18_forward(const ecgmm_resnet18_desc* d, const float*
       if (down_side) {
         main_wait(s, down_done);
       } else {
-        ConvGeom gd = make_geom(N, k.hin, k.win, k.cin, k.cout, 1, 1, k.stride, 0, 0);
+        ConvGeom gd = k.down_geom(N);
         // (own row buffer: bn2's rows in w.stats are still unread -- their finalize is folded into the pass below)
         ECG_TRY(ecg_conv_igemm(dt, 0, gd, cur, b.wdf, b.yd, nullptr, nullptr, stats_rows ? w.stats_d : nullptr, 0, s));
-        ECG_TRY(bn_coef(r, w.stats_d, rows, k.cout, M, params, k.p_dbn, buffers, k.b_dbn, b.coefd, s));
+        ECG_TRY(bn_coef(r.bn, w.stats_d, rows, k.cout, M, params, k.p_dbn, buffers, k.b_dbn, b.coefd, s));
       }
       ECG_TRY(bn_then_act(r, w.stats, e2.stats_rows, k.cout, M, params, k.p_bn2, buffers, k.b_bn2, b.coef2, b.y2, b.yd,
                           b.coefd, b.out, s, r.d.training && relu_bits_on() ? b.bits : nullptr));
@@ -436,7 +344,7 @@ extern "C" int ecgmm_resnet18_forward(const ecgmm_resnet18_desc* d, const float*
     cur = b.out;
     ecg_tl_mark(102 + i, s);
   }
-  const BlockCfg& last = r.blk[7];
+  const Blk18& last = r.blk[7];
   ECG_TRY(ecg_avgpool(dt, cur, w.pooled, N, last.hout * last.wout, 512, nullptr, s));
   ECG_TRY(ecg_linear_fwd(w.pooled, P(params, r.p_fc), P(params, r.p_fc + 1), feat_out, N, 512, r.d.out_dim, 0, nullptr,
                          s));
@@ -450,7 +358,7 @@ extern "C" int ecgmm_resnet18_forward(const ecgmm_resnet18_desc* d, const float*
 static int r18_backward(const ecgmm_resnet18_desc* d, const float* image, const float* dfeat, const void* const* params,
                         void* const* grads, void* ws_fwd, void* ws_bwd, size_t ws_bwd_bytes, int stage_begin, int stage_end,
                         float* dimage, hipStream_t s) {
-  R18 r;
+  Net18 r;
   ECG_TRY(build(d, r));
   const bool train = r.d.training != 0;
   if (stem_recompute(r.d.dtype) && (dimage || !train))
@@ -460,8 +368,7 @@ static int r18_backward(const ecgmm_resnet18_desc* d, const float* image, const 
   layout_fwd(r, ws_fwd, w);
   BwdWs q;
   layout_bwd(r, ws_bwd, q);
-  if (!ws_fwd || !ws_bwd || ws_bwd_bytes < q.bytes)
-    ECG_FAIL(ECGMM_ERR_WORKSPACE, "resnet18 bwd: workspace %zu < %zu", ws_bwd_bytes, q.bytes);
+  ECG_NEED(ws_fwd && ws_bwd, ws_bwd_bytes, q.bytes, "resnet18 bwd: workspace");
   const int dt = r.d.dtype, N = r.d.N;
   ECG_TRY(side_init());
   const bool side = g_side.enabled;
@@ -478,20 +385,20 @@ static int r18_backward(const ecgmm_resnet18_desc* d, const float* image, const 
     if (st == 0) {
       g_side.doneA = g_side.doneB = g_side.doneC = nullptr;
       for (int a = 0; a < 3; ++a) g_side.done2[a][0] = g_side.done2[a][1] = nullptr;
-      const BlockCfg& last = r.blk[7];
+      const Blk18& last = r.blk[7];
       ECG_TRY(fc_bwd(r, w, q, dfeat, params, grads, s));
       const int R = last.hout * last.wout;
       ECG_TRY(ecg_bcast_rows(dt, q.dpooled, q.X[0], N, R, 512, 1.f / (float)R, s));
     } else if (st <= 8) {
       const int i = 8 - st;
-      const BlockCfg& k = r.blk[i];
+      const Blk18& k = r.blk[i];
       FwdWs::B& b = w.b[i];
       const void* in = i == 0 ? w.p0 : w.b[i - 1].out;
       const void* dcur = q.X[(st - 1) & 1];
       void* din = q.X[st & 1];
       const long M = (long)N * k.hout * k.wout;
-      ConvGeom g1 = make_geom(N, k.hin, k.win, k.cin, k.cout, 3, 3, k.stride, 1, 1);
-      ConvGeom g2 = make_geom(N, k.hout, k.wout, k.cout, k.cout, 3, 3, 1, 1, 1);
+      ConvGeom g1 = k.conv1_geom(N);
+      ConvGeom g2 = k.conv2_geom(N);
       const int pp = st & 1;  // which of the two dy / dy1 / dyd buffers (and their reader events) this block uses
       void *dyb = q.dy[pp], *dy1b = q.dy1[pp], *dydb = q.dyd[pp];
       // The REDUCTION pass of a BatchNorm backward is fused into the epilogue of the dgrad that produces its input,
@@ -509,14 +416,14 @@ static int r18_backward(const ecgmm_resnet18_desc* d, const float* image, const 
       // same-call A/B of the whole step, fused on layer 1 / never fused = 6.84, 6.88 / 6.75, 6.75 ms.
       // ECGMM_BN_FUSE_MIN_M (ecgmm_bn_fuse_min_pixels) sets the pixel-count threshold: 400000 = round 2's choice (layer 1 at
       // batch 256), 0 = fuse wherever possible.
-      static const bool fuse_on = [] { const char* e = getenv("ECGMM_BN_FUSE"); return !(e && e[0] == '0'); }();
-      static const bool fold_on = [] { const char* e = getenv("ECGMM_DOWN_FOLD"); return !(e && e[0] == '0'); }();
-      if (g_fuse_min_m < 0) { const char* e = getenv("ECGMM_BN_FUSE_MIN_M"); g_fuse_min_m = e ? atol(e) : FUSE_NEVER; }
+      static const bool fuse_on = env_on("ECGMM_BN_FUSE");
+      static const bool fold_on = env_on("ECGMM_DOWN_FOLD");
+      if (g_fuse_min_m < 0) g_fuse_min_m = env_int("ECGMM_BN_FUSE_MIN_M", FUSE_NEVER);
       const long fuse_min_m = g_fuse_min_m;
       const bool fuse_here = train && fuse_on && M >= fuse_min_m;   // (the fused reductions are the training form's)
       if (fuse_here && i + 1 < 8 && !r.blk[i + 1].down) {
-        const BlockCfg& kn = r.blk[i + 1];
-        const ConvGeom gn = make_geom(N, kn.hin, kn.win, kn.cin, kn.cout, 3, 3, 1, 1, 1);
+        const Blk18& kn = r.blk[i + 1];
+        const ConvGeom gn = kn.conv1_geom(N);
         fused2 = ecg_conv_halo_ok(dt, 1, gn);
         fused2_rows = fused2 ? ecg_conv_halo_rows(1, gn) : 0;
       }
@@ -529,8 +436,9 @@ static int r18_backward(const ecgmm_resnet18_desc* d, const float* image, const 
                                 G(grads, k.p_bn2 + 1), dyb, q.red2, fused2_rows, M, k.cout, q.bn_scratch, s));
       } else {
         // (the eval forward writes no mask bits: its backward re-reads `out`)
-        ECG_TRY(bn_bwd_mode(r, dcur, b.out, b.y2, b.coef2, P(params, k.p_bn2), G(grads, k.p_bn2), G(grads, k.p_bn2 + 1), dyb,
-                            q.dz, M, k.cout, q.bn_scratch, s, train && relu_bits_on() ? b.bits : nullptr));
+        ECG_TRY(bn_bwd_mode(r.bn, dcur, b.out, nullptr, nullptr, 1, b.y2, b.coef2, P(params, k.p_bn2), G(grads, k.p_bn2),
+                            G(grads, k.p_bn2 + 1), dyb, q.dz, nullptr, M, k.cout, q.bn_scratch, s,
+                            train && relu_bits_on() ? b.bits : nullptr));
       }
       if (G(grads, k.p_conv2)) {
         if (side) side_fork(s);
@@ -546,8 +454,8 @@ static int r18_backward(const ecgmm_resnet18_desc* d, const float* image, const 
         ECG_TRY(ecg_bn_bwd_tail(dt, q.da, b.y1, b.y1, b.coef1, P(params, k.p_bn1), G(grads, k.p_bn1),
                                 G(grads, k.p_bn1 + 1), dy1b, q.red1, ea.red_rows_n, M, k.cout, q.bn_scratch, s));
       } else {
-        ECG_TRY(bn_bwd_mode(r, q.da, b.y1, b.y1, b.coef1, P(params, k.p_bn1), G(grads, k.p_bn1), G(grads, k.p_bn1 + 1), dy1b,
-                            nullptr, M, k.cout, q.bn_scratch, s));
+        ECG_TRY(bn_bwd_mode(r.bn, q.da, b.y1, nullptr, nullptr, 1, b.y1, b.coef1, P(params, k.p_bn1), G(grads, k.p_bn1),
+                            G(grads, k.p_bn1 + 1), dy1b, nullptr, nullptr, M, k.cout, q.bn_scratch, s));
       }
       if (G(grads, k.p_conv1)) {
         if (side) side_fork(s);
@@ -555,10 +463,10 @@ static int r18_backward(const ecgmm_resnet18_desc* d, const float* image, const 
         if (side) g_side.done2[1][pp] = side_mark();
       }
       if (k.down) {
-        ConvGeom gd = make_geom(N, k.hin, k.win, k.cin, k.cout, 1, 1, k.stride, 0, 0);
+        ConvGeom gd = k.down_geom(N);
         main_wait(s, g_side.done2[2][pp]);
-        ECG_TRY(bn_bwd_mode(r, dzp, nullptr, b.yd, b.coefd, P(params, k.p_dbn), G(grads, k.p_dbn), G(grads, k.p_dbn + 1), dydb,
-                            nullptr, M, k.cout, q.bn_scratch, s));
+        ECG_TRY(bn_bwd_mode(r.bn, dzp, nullptr, nullptr, nullptr, 1, b.yd, b.coefd, P(params, k.p_dbn), G(grads, k.p_dbn),
+                            G(grads, k.p_dbn + 1), dydb, nullptr, nullptr, M, k.cout, q.bn_scratch, s));
         if (G(grads, k.p_dconv)) {
           if (side) side_fork(s);
           ECG_TRY(ecg_conv_wgrad(dt, gd, in, dydb, G(grads, k.p_dconv), 0, q.wg_ws, q.wg_bytes, ws));
@@ -601,8 +509,8 @@ static int r18_backward(const ecgmm_resnet18_desc* d, const float* image, const 
       } else {
         // (eval: always the plain two passes -- max-pool + ReLU backward, then the affine BatchNorm backward)
         ECG_TRY(ecg_maxpool_relu_bwd(dt, dp0, w.p0, w.idx0, q.big0, N, r.H1, r.W1, 64, s));
-        ECG_TRY(bn_bwd_mode(r, q.big0, nullptr, w.y0, w.coef0, P(params, 1), G(grads, 1), G(grads, 2), q.big1, nullptr,
-                            (long)N * r.H1 * r.W1, 64, q.bn_scratch, s));
+        ECG_TRY(bn_bwd_mode(r.bn, q.big0, nullptr, nullptr, nullptr, 1, w.y0, w.coef0, P(params, 1), G(grads, 1), G(grads, 2),
+                            q.big1, nullptr, nullptr, (long)N * r.H1 * r.W1, 64, q.bn_scratch, s));
       }
       if (G(grads, 0)) {
         // the last kernel of the backward stays on the caller's stream: nothing is left there to overlap it with, it
@@ -647,17 +555,16 @@ extern "C" int ecgmm_resnet18_backward_dx(const ecgmm_resnet18_desc* d, const fl
 extern "C" int ecgmm_resnet18_gradcam(const ecgmm_resnet18_desc* d, const float* dfeat, const void* const* params,
                                       void* ws_fwd, void* ws_bwd, size_t ws_bwd_bytes, float* cam, void* stream_) {
   hipStream_t s = (hipStream_t)stream_;
-  R18 r;
+  Net18 r;
   ECG_TRY(build(d, r));
   FwdWs w;
   layout_fwd(r, ws_fwd, w);
   BwdWs q;
   layout_bwd(r, ws_bwd, q);
-  if (!ws_fwd || !ws_bwd || ws_bwd_bytes < q.bytes)
-    ECG_FAIL(ECGMM_ERR_WORKSPACE, "resnet18 gradcam: workspace %zu < %zu", ws_bwd_bytes, q.bytes);
+  ECG_NEED(ws_fwd && ws_bwd, ws_bwd_bytes, q.bytes, "resnet18 gradcam: workspace");
   if (!dfeat || !cam) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet18 gradcam: null operand");
   ECG_TRY(fc_bwd(r, w, q, dfeat, params, nullptr, s));
-  const BlockCfg& last = r.blk[7];
+  const Blk18& last = r.blk[7];
   // (q.X[0] holds max_act elements of the compute dtype >= N x hout x wout x 512: room for the N x hout x wout fp32 map)
   return ecg_gradcam(r.d.dtype, w.b[7].out, q.dpooled, (float*)q.X[0], cam, r.d.N, last.hout, last.wout, 512, r.d.H, r.d.W,
                      s);

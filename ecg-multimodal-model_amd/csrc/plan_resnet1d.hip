@@ -5,57 +5,15 @@
 // Conv1d layers keep their bias in front of BN, as the reference does.  Activations are [N, L, C]
 // channels-last in the compute dtype; the signal enters as [N, cin, L] fp32.
 //
-// Parameter table (52): initial.0.{weight,bias}, initial.1.{weight,bias}, then per layer
-//   conv1.{w,b}, bn1.{w,b}, conv2.{w,b}, bn2.{w,b}, se.fc.0.{w,b}, se.fc.2.{w,b},
-//   [downsample.0.{w,b}, downsample.1.{w,b}] (layers 2,3), then classifier.1.{w,b}, classifier.4.{w,b}.
-// Buffer table (27): running_mean, running_var, num_batches_tracked per BatchNorm in the same walk.
-#include "ops.h"
+// The network description (block table, parameter / buffer table order and the named T1_* offsets, geometry): net_desc.h.
+#include "plan_common.h"
 #include "side_stream.h"
 
 namespace {
 
-struct Blk1 {
-  int cin, cout, stride, lin, lout, cr;
-  bool down;
-  int p0;  // first param index
-  int b0;  // first buffer index
-};
-
-struct R1D {
-  ecgmm_resnet1d_desc d;
-  int L1, L2;
-  Blk1 blk[3];
-  int p_cls;
-  size_t max_act;
-};
-
-int build(const ecgmm_resnet1d_desc* d, R1D& r) {
-  if (!d) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet1d: null desc");
-  if (d->dtype != ECGMM_BF16 && d->dtype != ECGMM_F32) ECG_FAIL(ECGMM_ERR_DTYPE, "resnet1d: bad dtype %d", d->dtype);
-  if (d->N < 1 || d->L < 64 || d->cin < 1 || d->cin > 24)
-    ECG_FAIL(ECGMM_ERR_SHAPE, "resnet1d: bad input N=%d cin=%d L=%d", d->N, d->cin, d->L);
-  r.d = *d;
-  r.L1 = (d->L + 6 - 7) / 2 + 1;
-  r.L2 = (r.L1 + 2 - 3) / 2 + 1;
-  int pi = 4, bi = 3, l = r.L2, cin = 64;
-  r.max_act = (size_t)d->N * r.L2 * 64;
-  for (int i = 0; i < 3; ++i) {
-    Blk1& k = r.blk[i];
-    k.cin = cin; k.cout = 64 << i; k.stride = i == 0 ? 1 : 2;
-    k.lin = l; k.lout = (l + 2 - 3) / k.stride + 1;
-    k.cr = k.cout / 16;
-    k.down = (k.stride != 1 || k.cin != k.cout);
-    k.p0 = pi; k.b0 = bi;
-    pi += k.down ? 16 : 12;
-    bi += k.down ? 9 : 6;
-    size_t a = (size_t)d->N * k.lout * k.cout;
-    if (a > r.max_act) r.max_act = a;
-    l = k.lout; cin = k.cout;
-  }
-  r.p_cls = pi;
-  if (pi + 4 != ECGMM_RESNET1D_NPARAMS || bi != ECGMM_RESNET1D_NBUFFERS)
-    ECG_FAIL(ECGMM_ERR_SHAPE, "resnet1d: internal table mismatch %d %d", pi + 4, bi);
-  return 0;
+int build(const ecgmm_resnet1d_desc* d, Net1D& r) {
+  ECG_TRY(net1d_static(d, r, "resnet1d"));
+  return net1d_shape(r, "resnet1d");
 }
 
 struct Fwd1 {
@@ -71,7 +29,7 @@ struct Fwd1 {
   size_t bytes;
 };
 
-void layout_fwd(const R1D& r, void* base, Fwd1& w) {
+void layout_fwd(const Net1D& r, void* base, Fwd1& w) {
   Arena a(base);
   const size_t es = dtype_size(r.d.dtype);
   const int N = r.d.N;
@@ -130,7 +88,7 @@ struct Bwd1 {
   size_t bytes;
 };
 
-void layout_bwd(const R1D& r, void* base, Bwd1& w) {
+void layout_bwd(const Net1D& r, void* base, Bwd1& w) {
   Arena a(base);
   const size_t es = dtype_size(r.d.dtype);
   const int N = r.d.N;
@@ -165,12 +123,12 @@ void layout_bwd(const R1D& r, void* base, Bwd1& w) {
     const Blk1& k = r.blk[i];
     size_t s = ecg_bn_bwd_scratch(r.d.dtype, (long)N * k.lout, k.cout);
     if (s > bn) bn = s;
-    size_t g1 = ecg_conv_wgrad_workspace(r.d.dtype, make_geom(N, 1, k.lin, k.cin, k.cout, 1, 3, k.stride, 0, 1));
-    size_t g2 = ecg_conv_wgrad_workspace(r.d.dtype, make_geom(N, 1, k.lout, k.cout, k.cout, 1, 3, 1, 0, 1));
+    size_t g1 = ecg_conv_wgrad_workspace(r.d.dtype, k.conv1_geom(N));
+    size_t g2 = ecg_conv_wgrad_workspace(r.d.dtype, k.conv2_geom(N));
     if (g1 > wg) wg = g1;
     if (g2 > wg) wg = g2;
     if (k.down) {
-      size_t g3 = ecg_conv_wgrad_workspace(r.d.dtype, make_geom(N, 1, k.lin, k.cin, k.cout, 1, 1, k.stride, 0, 0));
+      size_t g3 = ecg_conv_wgrad_workspace(r.d.dtype, k.down_geom(N));
       if (g3 > wg) wg = g3;
     }
     size_t la = ecg_linear_bwd_scratch(N, k.cr, k.cout), lb = ecg_linear_bwd_scratch(N, k.cout, k.cr);
@@ -187,42 +145,17 @@ void layout_bwd(const R1D& r, void* base, Bwd1& w) {
   w.bytes = align_up(a.off, 256);
 }
 
-inline const float* P(const void* const* params, int i) { return (const float*)params[i]; }
-inline float* G(void* const* grads, int i) { return grads ? (float*)grads[i] : nullptr; }
-
-int bn_coef(const R1D& r, const float* stats, int rows, int C, long count, const void* const* params, int p_bn,
-            void* const* buffers, int b_bn, float* coef, hipStream_t s) {
-  if (r.d.training)
-    return ecg_bn_finalize(stats, rows, C, (double)count, P(params, p_bn), P(params, p_bn + 1), (float*)buffers[b_bn],
-                           (float*)buffers[b_bn + 1], (long long*)buffers[b_bn + 2], r.d.bn_momentum, r.d.bn_eps, coef,
-                           s);
-  return ecg_bn_eval_coef(C, P(params, p_bn), P(params, p_bn + 1), (const float*)buffers[b_bn],
-                          (const float*)buffers[b_bn + 1], r.d.bn_eps, coef, s);
-}
-
-// BatchNorm backward of either forward mode (operands as ecg_bn_bwd): the training form, or behind an eval-mode forward the
-// one-pass affine form (bn_eval_bwd.hip).  The training call is exactly the one the plan always made.
-int bn_bwd_mode(const R1D& r, const void* dout, const void* maskref, const float* gate, const float* addc, int rps,
-                const void* y, const float* coef, const float* gamma, float* dgamma, float* dbeta, void* dy, void* dz_out,
-                float* dbias, long M, int C, float* scratch, hipStream_t s) {
-  if (r.d.training)
-    return ecg_bn_bwd(r.d.dtype, dout, maskref, gate, addc, rps, y, coef, gamma, dgamma, dbeta, dy, dz_out, dbias, M, C,
-                      scratch, s);
-  return ecg_bn_eval_bwd(r.d.dtype, dout, maskref, gate, addc, rps, y, coef, dgamma, dbeta, dy, dz_out, dbias, M, C, scratch,
-                         s);
-}
-
 // stage 0 up to the pooled features: d loss / d pooled [N][256] (+ the classifier's parameter gradients)
-int classifier_bwd(const R1D& r, const Fwd1& w, const Bwd1& q, const float* dfeat, const void* const* params,
+int classifier_bwd(const Net1D& r, const Fwd1& w, const Bwd1& q, const float* dfeat, const void* const* params,
                    void* const* grads, hipStream_t s) {
   const int pc = r.p_cls, N = r.d.N;
   const bool drop = r.d.training && r.d.dropout_p > 0.f;   // (as the forward: no dropout in eval mode)
-  ECG_TRY(ecg_linear_bwd(dfeat, drop ? w.hd : w.h1, P(params, pc + 2), q.dfeat_h, G(grads, pc + 2), G(grads, pc + 3), N, 64,
-                         r.d.num_classes, q.lin_ws, q.lin_bytes, s));
+  ECG_TRY(ecg_linear_bwd(dfeat, drop ? w.hd : w.h1, P(params, pc + T1_CLS_W2), q.dfeat_h, G(grads, pc + T1_CLS_W2),
+                         G(grads, pc + T1_CLS_B2), N, 64, r.d.num_classes, q.lin_ws, q.lin_bytes, s));
   if (drop) ECG_TRY(ecg_dropout_bwd(q.dfeat_h, w.dmask, q.dfeat_h, (long)N * 64, r.d.dropout_p, s));
   ECG_TRY(ecg_act_bwd(q.dfeat_h, w.h1, q.dh1, (long)N * 64, ECGMM_ACT_RELU, s));
-  return ecg_linear_bwd(q.dh1, w.pooled, P(params, pc), q.dpooled, G(grads, pc), G(grads, pc + 1), N, 256, 64, q.lin_ws,
-                        q.lin_bytes, s);
+  return ecg_linear_bwd(q.dh1, w.pooled, P(params, pc + T1_CLS_W1), q.dpooled, G(grads, pc + T1_CLS_W1),
+                        G(grads, pc + T1_CLS_B1), N, 256, 64, q.lin_ws, q.lin_bytes, s);
 }
 
 }  // namespace
@@ -248,14 +181,14 @@ extern "C" int ecgmm_resnet1d_side_wgrad(int on) {
 }
 
 extern "C" size_t ecgmm_resnet1d_fwd_workspace(const ecgmm_resnet1d_desc* d) {
-  R1D r;
+  Net1D r;
   if (build(d, r)) return 0;
   Fwd1 w;
   layout_fwd(r, nullptr, w);
   return w.bytes;
 }
 extern "C" size_t ecgmm_resnet1d_bwd_workspace(const ecgmm_resnet1d_desc* d) {
-  R1D r;
+  Net1D r;
   if (build(d, r)) return 0;
   Bwd1 w;
   layout_bwd(r, nullptr, w);
@@ -266,11 +199,11 @@ extern "C" int ecgmm_resnet1d_forward(const ecgmm_resnet1d_desc* d, const float*
                                       void* const* buffers, float* feat_out, void* ws, size_t ws_bytes,
                                       void* stream_) {
   hipStream_t s = (hipStream_t)stream_;
-  R1D r;
+  Net1D r;
   ECG_TRY(build(d, r));
   Fwd1 w;
   layout_fwd(r, ws, w);
-  if (!ws || ws_bytes < w.bytes) ECG_FAIL(ECGMM_ERR_WORKSPACE, "resnet1d fwd: workspace %zu < %zu", ws_bytes, w.bytes);
+  ECG_NEED(ws, ws_bytes, w.bytes, "resnet1d fwd: workspace");
   const int dt = r.d.dtype, N = r.d.N, cin = r.d.cin;
   float* st = r.d.training ? w.stats : nullptr;
 
@@ -280,23 +213,16 @@ extern "C" int ecgmm_resnet1d_forward(const ecgmm_resnet1d_desc* d, const float*
     for (int i = 0; i < 3; ++i) {
       const Blk1& k = r.blk[i];
       Fwd1::B& b = w.b[i];
-      items[n++] = {P(params, k.p0 + 0), b.w1f, b.w1d, k.cout, k.cin, 3};
-      items[n++] = {P(params, k.p0 + 4), b.w2f, b.w2d, k.cout, k.cout, 3};
-      if (k.down) items[n++] = {P(params, k.p0 + 12), b.wdf, b.wdd, k.cout, k.cin, 1};
+      items[n++] = {P(params, k.p0 + T1_CONV1_W), b.w1f, b.w1d, k.cout, k.cin, 3};
+      items[n++] = {P(params, k.p0 + T1_CONV2_W), b.w2f, b.w2d, k.cout, k.cout, 3};
+      if (k.down) items[n++] = {P(params, k.p0 + T1_DOWN_W), b.wdf, b.wdd, k.cout, k.cin, 1};
     }
     ECG_TRY(ecg_pack_weight_batch(dt, items, n, s));
   }
   ECG_TRY(ecg_stem_pack(dt, P(params, 0), w.wstem, cin, 1, s));
-  // (bf16: statistics rows per workgroup -- sums kept in registers across the workgroup's tiles -- instead of per tile)
-  if (dt == ECGMM_BF16) {
-    ECG_TRY(ecg_stem_fwd_wgrows(dt, signal, w.wstem, P(params, 1), w.y0, st, N, cin, 1, r.d.L, 1, s));
-    ECG_TRY(bn_coef(r, w.stats, ecg_stem_wg_stats_rows(N, cin, 1, r.d.L, 1), 64, (long)N * r.L1, params, 2, buffers, 0,
-                    w.coef0, s));
-  } else {
-    ECG_TRY(ecg_stem_fwd(dt, signal, w.wstem, P(params, 1), w.y0, st, N, cin, 1, r.d.L, 1, s));
-    ECG_TRY(bn_coef(r, w.stats, ecg_stem_stats_rows(N, cin, 1, r.d.L, 1), 64, (long)N * r.L1, params, 2, buffers, 0,
-                    w.coef0, s));
-  }
+  ECG_TRY(stem_forward(dt, signal, w.wstem, P(params, 1), w.y0, st, N, cin, 1, r.d.L, 1, s));
+  ECG_TRY(bn_coef(r.bn, w.stats, stem_forward_rows(dt, N, cin, 1, r.d.L, 1), 64, (long)N * r.L1, params, 2, buffers, 0,
+                  w.coef0, s));
   ECG_TRY(ecg_bnrelu_maxpool(dt, w.y0, w.coef0, w.p0, w.idx0, N, 1, r.L1, 64, s));
 
   const void* cur = w.p0;
@@ -306,27 +232,21 @@ extern "C" int ecgmm_resnet1d_forward(const ecgmm_resnet1d_desc* d, const float*
     const int p = k.p0, bb = k.b0;
     const long M = (long)N * k.lout;
     const int rows = ecg_conv_stats_rows(M);
-    ConvGeom g1 = make_geom(N, 1, k.lin, k.cin, k.cout, 1, 3, k.stride, 0, 1);
-    ConvGeom g2 = make_geom(N, 1, k.lout, k.cout, k.cout, 1, 3, 1, 0, 1);
-    ECG_TRY(ecg_conv_igemm(dt, 0, g1, cur, b.w1f, b.y1, P(params, p + 1), nullptr, st, 0, s));
-    ECG_TRY(bn_coef(r, w.stats, rows, k.cout, M, params, p + 2, buffers, bb, b.coef1, s));
+    ConvGeom g1 = k.conv1_geom(N);
+    ConvGeom g2 = k.conv2_geom(N);
+    ECG_TRY(ecg_conv_igemm(dt, 0, g1, cur, b.w1f, b.y1, P(params, p + T1_CONV1_B), nullptr, st, 0, s));
+    ECG_TRY(bn_coef(r.bn, w.stats, rows, k.cout, M, params, p + T1_BN1, buffers, bb + T1B_BN1, b.coef1, s));
     ECG_TRY(ecg_bn_act(dt, b.y1, b.coef1, nullptr, nullptr, nullptr, 1, 1, b.a1, M, k.cout, s));
-    ECG_TRY(ecg_conv_igemm(dt, 0, g2, b.a1, b.w2f, b.y2, P(params, p + 5), nullptr, st, 0, s));
-    ECG_TRY(bn_coef(r, w.stats, rows, k.cout, M, params, p + 6, buffers, bb + 3, b.coef2, s));
+    ECG_TRY(ecg_conv_igemm(dt, 0, g2, b.a1, b.w2f, b.y2, P(params, p + T1_CONV2_B), nullptr, st, 0, s));
+    ECG_TRY(bn_coef(r.bn, w.stats, rows, k.cout, M, params, p + T1_BN2, buffers, bb + T1B_BN2, b.coef2, s));
     // squeeze-excite gate from mean_L(bn2(y2))
     ECG_TRY(ecg_avgpool(dt, b.y2, b.m, N, k.lout, k.cout, b.coef2, s));
-    if (ecg_se_mlp_fused_ok(k.cout, k.cr)) {
-      ECG_TRY(ecg_se_mlp_fwd(b.m, P(params, p + 8), P(params, p + 9), P(params, p + 10), P(params, p + 11), b.h, b.g, N,
-                             k.cout, k.cr, s));
-    } else {
-      ECG_TRY(ecg_linear_fwd(b.m, P(params, p + 8), P(params, p + 9), b.h, N, k.cout, k.cr, ECGMM_ACT_RELU, nullptr, s));
-      ECG_TRY(ecg_linear_fwd(b.h, P(params, p + 10), P(params, p + 11), b.g, N, k.cr, k.cout, ECGMM_ACT_SIGMOID, nullptr,
-                             s));
-    }
+    ECG_TRY(se_mlp_forward(b.m, P(params, p + T1_SE_W1), P(params, p + T1_SE_B1), P(params, p + T1_SE_W2),
+                           P(params, p + T1_SE_B2), b.h, b.g, N, k.cout, k.cr, s));
     if (k.down) {
-      ConvGeom gd = make_geom(N, 1, k.lin, k.cin, k.cout, 1, 1, k.stride, 0, 0);
-      ECG_TRY(ecg_conv_igemm(dt, 0, gd, cur, b.wdf, b.yd, P(params, p + 13), nullptr, st, 0, s));
-      ECG_TRY(bn_coef(r, w.stats, rows, k.cout, M, params, p + 14, buffers, bb + 6, b.coefd, s));
+      ConvGeom gd = k.down_geom(N);
+      ECG_TRY(ecg_conv_igemm(dt, 0, gd, cur, b.wdf, b.yd, P(params, p + T1_DOWN_B), nullptr, st, 0, s));
+      ECG_TRY(bn_coef(r.bn, w.stats, rows, k.cout, M, params, p + T1_DBN, buffers, bb + T1B_DBN, b.coefd, s));
       ECG_TRY(ecg_bn_act(dt, b.y2, b.coef2, b.yd, b.coefd, b.g, k.lout, 1, b.out, M, k.cout, s));
     } else {
       ECG_TRY(ecg_bn_act(dt, b.y2, b.coef2, cur, nullptr, b.g, k.lout, 1, b.out, M, k.cout, s));
@@ -335,13 +255,15 @@ extern "C" int ecgmm_resnet1d_forward(const ecgmm_resnet1d_desc* d, const float*
   }
   const int pc = r.p_cls;
   ECG_TRY(ecg_avgpool(dt, cur, w.pooled, N, r.blk[2].lout, 256, nullptr, s));
-  ECG_TRY(ecg_linear_fwd(w.pooled, P(params, pc), P(params, pc + 1), w.h1, N, 256, 64, ECGMM_ACT_RELU, nullptr, s));
+  ECG_TRY(ecg_linear_fwd(w.pooled, P(params, pc + T1_CLS_W1), P(params, pc + T1_CLS_B1), w.h1, N, 256, 64, ECGMM_ACT_RELU,
+                         nullptr, s));
   const float* hin = w.h1;
   if (r.d.training && r.d.dropout_p > 0.f) {
     ECG_TRY(ecg_dropout_fwd(w.h1, w.hd, w.dmask, (long)N * 64, r.d.dropout_p, r.d.seed, r.d.offset, s));
     hin = w.hd;
   }
-  ECG_TRY(ecg_linear_fwd(hin, P(params, pc + 2), P(params, pc + 3), feat_out, N, 64, r.d.num_classes, 0, nullptr, s));
+  ECG_TRY(ecg_linear_fwd(hin, P(params, pc + T1_CLS_W2), P(params, pc + T1_CLS_B2), feat_out, N, 64, r.d.num_classes, 0,
+                         nullptr, s));
   return 0;
 }
 
@@ -351,15 +273,14 @@ extern "C" int ecgmm_resnet1d_forward(const ecgmm_resnet1d_desc* d, const float*
 static int r1d_backward(const ecgmm_resnet1d_desc* d, const float* signal, const float* dfeat, const void* const* params,
                         void* const* grads, void* ws_fwd, void* ws_bwd, size_t ws_bwd_bytes, int stage_begin, int stage_end,
                         float* dsignal, hipStream_t s) {
-  R1D r;
+  Net1D r;
   ECG_TRY(build(d, r));
   const bool train = r.d.training != 0;
   Fwd1 w;
   layout_fwd(r, ws_fwd, w);
   Bwd1 q;
   layout_bwd(r, ws_bwd, q);
-  if (!ws_fwd || !ws_bwd || ws_bwd_bytes < q.bytes)
-    ECG_FAIL(ECGMM_ERR_WORKSPACE, "resnet1d bwd: workspace %zu < %zu", ws_bwd_bytes, q.bytes);
+  ECG_NEED(ws_fwd && ws_bwd, ws_bwd_bytes, q.bytes, "resnet1d bwd: workspace");
   const int dt = r.d.dtype, N = r.d.N, cin = r.d.cin;
   ECG_TRY(g_side1.init());
   const bool side = g_side1.enabled && g_side1_alone;
@@ -383,12 +304,12 @@ static int r1d_backward(const ecgmm_resnet1d_desc* d, const float* signal, const
       const void* dcur = q.X[(st - 1) & 1];
       void* din = q.X[st & 1];
       const long M = (long)N * k.lout;
-      ConvGeom g1 = make_geom(N, 1, k.lin, k.cin, k.cout, 1, 3, k.stride, 0, 1);
-      ConvGeom g2 = make_geom(N, 1, k.lout, k.cout, k.cout, 1, 3, 1, 0, 1);
+      ConvGeom g1 = k.conv1_geom(N);
+      ConvGeom g2 = k.conv2_geom(N);
       // out = relu(bn2(y2) * g + identity); gate gradient first.  Merged form (default): this pass also stores the masked
       // gradient dz and the per-sample sums the BatchNorm-backward reduction needs, so bn2's backward below is finalize +
       // apply only -- one read of (dcur, out, y2) less per block.  ECGMM_SE_MERGE=0: the two-pass form.
-      static const bool se_merge_on = [] { const char* e = getenv("ECGMM_SE_MERGE"); return !(e && e[0] == '0'); }();
+      static const bool se_merge_on = env_on("ECGMM_SE_MERGE");
       const bool se_merge = se_merge_on && train;   // (the merged pass feeds the training form's reduction)
       if (se_merge) {
         ECG_TRY(ecg_se_gate_bn(dt, dcur, b.out, b.y2, b.coef2, q.dz, q.dg, q.sa1, q.sa2, q.sa3, N, k.lout, k.cout, s));
@@ -396,51 +317,55 @@ static int r1d_backward(const ecgmm_resnet1d_desc* d, const float* signal, const
         ECG_TRY(ecg_se_gate_grad(dt, dcur, b.out, b.y2, b.coef2, q.dg, N, k.lout, k.cout, s));
       }
       if (ecg_se_mlp_fused_ok(k.cout, k.cr)) {   // the SE MLP's backward in two launches (head_fused.hip)
-        ECG_TRY(ecg_se_mlp_bwd(q.dg, b.g, b.h, b.m, P(params, p + 8), P(params, p + 10), q.ds, q.dh, q.dm, G(grads, p + 8),
-                               G(grads, p + 9), G(grads, p + 10), G(grads, p + 11), N, k.cout, k.cr, 1.f / (float)k.lout, s));
+        ECG_TRY(ecg_se_mlp_bwd(q.dg, b.g, b.h, b.m, P(params, p + T1_SE_W1), P(params, p + T1_SE_W2), q.ds, q.dh, q.dm,
+                               G(grads, p + T1_SE_W1), G(grads, p + T1_SE_B1), G(grads, p + T1_SE_W2), G(grads, p + T1_SE_B2),
+                               N, k.cout, k.cr, 1.f / (float)k.lout, s));
       } else {
         ECG_TRY(ecg_act_bwd(q.dg, b.g, q.ds, (long)N * k.cout, ECGMM_ACT_SIGMOID, s));
-        ECG_TRY(ecg_linear_bwd(q.ds, b.h, P(params, p + 10), q.dh, G(grads, p + 10), G(grads, p + 11), N, k.cr, k.cout,
-                               q.lin_ws, q.lin_bytes, s));
+        ECG_TRY(ecg_linear_bwd(q.ds, b.h, P(params, p + T1_SE_W2), q.dh, G(grads, p + T1_SE_W2), G(grads, p + T1_SE_B2), N,
+                               k.cr, k.cout, q.lin_ws, q.lin_bytes, s));
         ECG_TRY(ecg_act_bwd(q.dh, b.h, q.dh, (long)N * k.cr, ECGMM_ACT_RELU, s));
-        ECG_TRY(ecg_linear_bwd(q.dh, b.m, P(params, p + 8), q.dm, G(grads, p + 8), G(grads, p + 9), N, k.cout, k.cr,
-                               q.lin_ws, q.lin_bytes, s));
+        ECG_TRY(ecg_linear_bwd(q.dh, b.m, P(params, p + T1_SE_W1), q.dm, G(grads, p + T1_SE_W1), G(grads, p + T1_SE_B1), N,
+                               k.cout, k.cr, q.lin_ws, q.lin_bytes, s));
         ECG_TRY(ecg_axpby(1.f / (float)k.lout, q.dm, 0.f, q.dm, (long)N * k.cout, s));
       }
       main_wait(s, g_side1.doneA);  // the previous block's wgrad2 has finished reading q.dy
       if (se_merge) {
         ECG_TRY(ecg_se_bn_rows(q.sa1, q.sa2, q.sa3, b.g, q.dm, N, k.lout, k.cout, q.se_rows, s));
-        ECG_TRY(ecg_bn_bwd_tail(dt, q.dz, nullptr, b.y2, b.coef2, P(params, p + 6), G(grads, p + 6), G(grads, p + 7), q.dy,
-                                q.se_rows, ecg_se_bn_nrows(), M, k.cout, q.bn_scratch, s, b.g, q.dm, k.lout, G(grads, p + 5)));
+        ECG_TRY(ecg_bn_bwd_tail(dt, q.dz, nullptr, b.y2, b.coef2, P(params, p + T1_BN2), G(grads, p + T1_BN2),
+                                G(grads, p + T1_BN2 + 1), q.dy, q.se_rows, ecg_se_bn_nrows(), M, k.cout, q.bn_scratch, s, b.g,
+                                q.dm, k.lout, G(grads, p + T1_CONV2_B)));
       } else {
-        ECG_TRY(bn_bwd_mode(r, dcur, b.out, b.g, q.dm, k.lout, b.y2, b.coef2, P(params, p + 6), G(grads, p + 6),
-                            G(grads, p + 7), q.dy, q.dz, G(grads, p + 5), M, k.cout, q.bn_scratch, s));
+        ECG_TRY(bn_bwd_mode(r.bn, dcur, b.out, b.g, q.dm, k.lout, b.y2, b.coef2, P(params, p + T1_BN2), G(grads, p + T1_BN2),
+                            G(grads, p + T1_BN2 + 1), q.dy, q.dz, G(grads, p + T1_CONV2_B), M, k.cout, q.bn_scratch, s));
       }
-      if (G(grads, p + 4)) {
+      if (G(grads, p + T1_CONV2_W)) {
         if (side) g_side1.fork(s);
-        ECG_TRY(ecg_conv_wgrad(dt, g2, b.a1, q.dy, G(grads, p + 4), 0, q.wg_ws, q.wg_bytes, wst));
+        ECG_TRY(ecg_conv_wgrad(dt, g2, b.a1, q.dy, G(grads, p + T1_CONV2_W), 0, q.wg_ws, q.wg_bytes, wst));
         if (side) g_side1.doneA = g_side1.mark();
       }
       ECG_TRY(ecg_conv_igemm(dt, 1, g2, q.dy, b.w2d, q.da, nullptr, nullptr, nullptr, 0, s));
       main_wait(s, g_side1.doneB);
-      ECG_TRY(bn_bwd_mode(r, q.da, b.y1 /* mask recomputed from y1 */, nullptr, nullptr, 1, b.y1, b.coef1, P(params, p + 2), G(grads, p + 2),
-                          G(grads, p + 3), q.dy1, nullptr, G(grads, p + 1), M, k.cout, q.bn_scratch, s));
-      if (G(grads, p + 0)) {
+      ECG_TRY(bn_bwd_mode(r.bn, q.da, b.y1 /* mask recomputed from y1 */, nullptr, nullptr, 1, b.y1, b.coef1,
+                          P(params, p + T1_BN1), G(grads, p + T1_BN1), G(grads, p + T1_BN1 + 1), q.dy1, nullptr,
+                          G(grads, p + T1_CONV1_B), M, k.cout, q.bn_scratch, s));
+      if (G(grads, p + T1_CONV1_W)) {
         if (side) g_side1.fork(s);
-        ECG_TRY(ecg_conv_wgrad(dt, g1, in, q.dy1, G(grads, p + 0), 0, q.wg_ws, q.wg_bytes, wst));
+        ECG_TRY(ecg_conv_wgrad(dt, g1, in, q.dy1, G(grads, p + T1_CONV1_W), 0, q.wg_ws, q.wg_bytes, wst));
         if (side) g_side1.doneB = g_side1.mark();
       }
       if (k.down) {
-        ConvGeom gd = make_geom(N, 1, k.lin, k.cin, k.cout, 1, 1, k.stride, 0, 0);
+        ConvGeom gd = k.down_geom(N);
         main_wait(s, g_side1.doneC);
-        ECG_TRY(bn_bwd_mode(r, q.dz, nullptr, nullptr, nullptr, 1, b.yd, b.coefd, P(params, p + 14), G(grads, p + 14),
-                            G(grads, p + 15), q.dyd, nullptr, G(grads, p + 13), M, k.cout, q.bn_scratch, s));
-        if (G(grads, p + 12)) {
+        ECG_TRY(bn_bwd_mode(r.bn, q.dz, nullptr, nullptr, nullptr, 1, b.yd, b.coefd, P(params, p + T1_DBN),
+                            G(grads, p + T1_DBN), G(grads, p + T1_DBN + 1), q.dyd, nullptr, G(grads, p + T1_DOWN_B), M, k.cout,
+                            q.bn_scratch, s));
+        if (G(grads, p + T1_DOWN_W)) {
           if (side) g_side1.fork(s);
-          ECG_TRY(ecg_conv_wgrad(dt, gd, in, q.dyd, G(grads, p + 12), 0, q.wg_ws, q.wg_bytes, wst));
+          ECG_TRY(ecg_conv_wgrad(dt, gd, in, q.dyd, G(grads, p + T1_DOWN_W), 0, q.wg_ws, q.wg_bytes, wst));
           if (side) g_side1.doneC = g_side1.mark();
         }
-        static const bool fold_on = [] { const char* e = getenv("ECGMM_DOWN_FOLD"); return !(e && e[0] == '0'); }();
+        static const bool fold_on = env_on("ECGMM_DOWN_FOLD");
         ConvEpi ed = {};   // downsample branch folded into the stride-2 dgrad (see plan_resnet18.hip)
         if (fold_on) { ed.src2 = q.dyd; ed.wpk2 = b.wdd; }
         if (ed.src2) ECG_TRY(ecg_conv_igemm(dt, 1, g1, q.dy1, b.w1d, din, nullptr, nullptr, nullptr, 0, s, &ed));
@@ -458,7 +383,7 @@ static int r1d_backward(const ecgmm_resnet1d_desc* d, const float* signal, const
                                 G(grads, 1), N, 1, r.L1, 64, q.bn_scratch, s));
       } else {
         ECG_TRY(ecg_maxpool_relu_bwd(dt, dp0, w.p0, w.idx0, q.big0, N, 1, r.L1, 64, s));
-        ECG_TRY(bn_bwd_mode(r, q.big0, nullptr, nullptr, nullptr, 1, w.y0, w.coef0, P(params, 2), G(grads, 2), G(grads, 3),
+        ECG_TRY(bn_bwd_mode(r.bn, q.big0, nullptr, nullptr, nullptr, 1, w.y0, w.coef0, P(params, 2), G(grads, 2), G(grads, 3),
                             q.big1, nullptr, G(grads, 1), (long)N * r.L1, 64, q.bn_scratch, s));
       }
       if (G(grads, 0))  // last kernel: stays on the caller's stream (own slab buffer), see plan_resnet18.hip
@@ -494,14 +419,13 @@ extern "C" int ecgmm_resnet1d_backward_dx(const ecgmm_resnet1d_desc* d, const fl
 extern "C" int ecgmm_resnet1d_gradcam(const ecgmm_resnet1d_desc* d, const float* dfeat, const void* const* params,
                                       void* ws_fwd, void* ws_bwd, size_t ws_bwd_bytes, float* cam, void* stream_) {
   hipStream_t s = (hipStream_t)stream_;
-  R1D r;
+  Net1D r;
   ECG_TRY(build(d, r));
   Fwd1 w;
   layout_fwd(r, ws_fwd, w);
   Bwd1 q;
   layout_bwd(r, ws_bwd, q);
-  if (!ws_fwd || !ws_bwd || ws_bwd_bytes < q.bytes)
-    ECG_FAIL(ECGMM_ERR_WORKSPACE, "resnet1d gradcam: workspace %zu < %zu", ws_bwd_bytes, q.bytes);
+  ECG_NEED(ws_fwd && ws_bwd, ws_bwd_bytes, q.bytes, "resnet1d gradcam: workspace");
   if (!dfeat || !cam) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet1d gradcam: null operand");
   ECG_TRY(classifier_bwd(r, w, q, dfeat, params, nullptr, s));
   // (q.X[0] holds max_act elements >= N x lout x 256: room for the N x lout fp32 map)

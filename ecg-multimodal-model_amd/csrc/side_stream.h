@@ -7,8 +7,6 @@
 // attempted in round 2 faulted inside capture and was dropped (the step is not launch-bound: host enqueue 3.1 ms vs 7 ms GPU).  MFMA-bound wgrad overlaps the HBM-bound BatchNorm passes.  Each encoder plan has
 // its own instance: the two encoders of the multimodal model run concurrently and must not couple through one stream.
 #pragma once
-#include <cstdlib>
-
 #include "ops.h"
 
 struct SideStream {
@@ -21,8 +19,7 @@ struct SideStream {
 
   int init() {
     if (ok) return 0;
-    const char* e = getenv("ECGMM_SIDE_WGRAD");
-    enabled = !(e && e[0] == '0');
+    enabled = env_on("ECGMM_SIDE_WGRAD");
     if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess)
       ECG_FAIL(ECGMM_ERR_LAUNCH, "side stream creation failed");
     for (int i = 0; i < 64; ++i)

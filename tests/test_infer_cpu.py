@@ -17,6 +17,7 @@ NEW = ("ecgmm_resnet18_infer_prepared_bytes", "ecgmm_resnet18_infer_prepare", "e
        "ecgmm_resnet18_infer", "ecgmm_resnet1d_infer_prepared_bytes", "ecgmm_resnet1d_infer_prepare",
        "ecgmm_resnet1d_infer_workspace", "ecgmm_resnet1d_infer", "ecgmm_infer_down_side", "ecgmm_conv_fwd_fused",
        "ecgmm_fold_conv_bn", "ecgmm_relu_maxpool", "ecgmm_gate_res_relu")
+SIZE_FNS = ("fwd_workspace", "bwd_workspace", "infer_workspace", "infer_prepared_bytes")
 
 
 def test_new_symbols_in_header_table_and_library():
@@ -52,6 +53,52 @@ def test_size_queries_and_bad_descriptors_need_no_device():
     assert lib.ecgmm_resnet1d_infer_workspace(C.byref(bad1)) == 0 and "dtype" in _err()
     small = L.ResNet18Desc(8, 16, 16, 256, L.BF16, 0, 0.1, 1e-5)
     assert lib.ecgmm_resnet18_infer_workspace(C.byref(small)) == 0 and "bad input" in _err()
+    # Exact sizes [fwd_workspace, bwd_workspace, infer_workspace, infer_prepared_bytes].  The integers are what the library
+    # returned before the network descriptions moved into csrc/net_desc.h (a build of that commit, queried on the CPU): the
+    # training and inference plans now share one description, and no size may move.  A too-small input zeroes the three
+    # workspaces but not the blob, which never looks at the shape; a bad dtype or cin zeroes all four.
+    # (rows the ECGMM_STEM_RECOMPUTE switch cannot touch; the bf16 ResNet18 rows are in the test below)
+    for d, want in ((L.ResNet18Desc(1, 32, 32, 2, L.F32, 0, 0.1, 1e-5), [90274816, 14307328, 83968, 44702720]),
+                    (L.ResNet18Desc(8, 31, 224, 2, L.F32, 1, 0.1, 1e-5), [0, 0, 0, 44702720]),
+                    (L.ResNet18Desc(8, 224, 224, 2, 7, 1, 0.1, 1e-5), [0, 0, 0, 0])):
+        assert [getattr(lib, "ecgmm_resnet18_" + f)(C.byref(d)) for f in SIZE_FNS] == want
+    for d, want in ((L.ResNet1DDesc(512, 12, 5000, 256, L.BF16, 1, 0.1, 1e-5, 0.3, 0, 0),
+                     [1459741696, 1041141760, 329940992, 1063936]),
+                    (L.ResNet1DDesc(8, 1, 63, 2, L.F32, 1, 0.1, 1e-5, 0.3, 0, 0), [0, 0, 0, 1862400]),
+                    (L.ResNet1DDesc(8, 25, 5000, 2, L.F32, 1, 0.1, 1e-5, 0.3, 0, 0), [0, 0, 0, 0])):
+        assert [getattr(lib, "ecgmm_resnet1d_" + f)(C.byref(d)) for f in SIZE_FNS] == want
+
+
+_CHILD = """
+import ctypes as C, json, sys
+sys.path.insert(0, sys.argv[1])
+from ecgmm.hip import lib as L
+lib = L.lib()
+fns = ("fwd_workspace", "bwd_workspace", "infer_workspace", "infer_prepared_bytes")
+out = []
+for N, H, W, od in ((256, 224, 224, 256), (8, 250, 2500, 2)):
+    d = L.ResNet18Desc(N, H, W, od, L.BF16, 1, 0.1, 1e-5)
+    out.append([getattr(lib, "ecgmm_resnet18_" + f)(C.byref(d)) for f in fns])
+print(json.dumps(out))
+"""
+
+
+@pytest.mark.parametrize("recompute, want", [
+    (None, [[2320534528, 2084395008, 514326528, 22884096], [943228416, 898026496, 200336384, 22363136]]),
+    ("1", [[1864535040, 1262476032, 514326528, 22884096], [765107712, 578191104, 200336384, 22363136]]),
+])
+def test_bf16_resnet18_sizes_with_and_without_stem_recompute(recompute, want):
+    """The bf16 training-plan sizes depend on ECGMM_STEM_RECOMPUTE, which is read once per process: each setting gets a
+    child process of its own (no device needed).  Integers from the same build as the rows above."""
+    import json
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k != "ECGMM_STEM_RECOMPUTE"}
+    if recompute is not None:
+        env["ECGMM_STEM_RECOMPUTE"] = recompute
+    r = subprocess.run([sys.executable, "-c", _CHILD, ROOT], env=env, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert json.loads(r.stdout.strip().splitlines()[-1]) == want
 
 
 def test_null_and_short_buffers_are_errors_not_traps():
