@@ -326,4 +326,17 @@ int ecgmm_axpby(float a, const float* x, float b, float* y, int64_t n, void* str
   return ecg_axpby(a, x, b, y, (long)n, S_(stream));
 }
 
+size_t ecgmm_lstm_fwd_workspace(const ecgmm_lstm_desc* d) { return ecg_lstm_fwd_workspace(d); }
+size_t ecgmm_lstm_bwd_workspace(const ecgmm_lstm_desc* d) { return ecg_lstm_bwd_workspace(d); }
+int ecgmm_lstm_forward(const ecgmm_lstm_desc* d, const float* x, const float* const* params, const float* h0,
+                       const float* c0, float* y, float* hn, float* cn, void* ws, size_t ws_bytes, void* stream) {
+  return ecg_lstm_forward(d, x, params, h0, c0, y, hn, cn, ws, ws_bytes, S_(stream));
+}
+int ecgmm_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const float* const* params, const float* h0,
+                        const float* c0, const float* dy, const float* dhn, const float* dcn, const void* ws, float* dx,
+                        float* const* grads, float* dh0, float* dc0, void* scratch, size_t scratch_bytes, void* stream) {
+  return ecg_lstm_backward(d, x, params, h0, c0, dy, dhn, dcn, ws, dx, grads, dh0, dc0, scratch, scratch_bytes,
+                           S_(stream));
+}
+
 }  // extern "C"

@@ -1,0 +1,482 @@
+// nn.LSTM (multi-layer, optionally bidirectional), fp32, forward and back-propagation through time.
+//
+// Per layer and direction (torch semantics, gate order i, f, g, o):
+//   gates_t = x_t W_ih^T + b_ih + h_{t-1} W_hh^T + b_hh;  c_t = s(f) c_{t-1} + s(i) tanh(g);  h_t = s(o) tanh(c_t)
+// The input projection x W_ih^T + b_ih of ALL time steps is one ecg_linear_fwd launch (linear.hip) per layer and direction;
+// what is left is the recurrence, sequential in t and independent across batch rows:
+//
+//   lstm_seq_fwd_kernel : a persistent workgroup owns LSTM_ROWS = 16 batch rows of one direction (blockIdx.y) for all T
+//     steps.  h (double-buffered) and c of the slice live in LDS; W_hh [4H][H] streams from L2 every step.  The 16 batch
+//     rows are the M side of v_mfma_f32_16x16x4_f32 (exact fp32 products); the hidden units are split over the 8 waves
+//     in tiles of 16, and a wave computes all four gates of its tiles, so the cell update is lane-local in the MFMA's
+//     C/D layout.  One workgroup barrier per step.  No synchronisation between workgroups of any kind.
+//   lstm_seq_bwd_kernel : the same slices, time in the opposite order.  Per step the gate gradients are formed lane-locally
+//     (same ownership as the forward), staged in LDS, and dh_{t-1} = dgates_t W_hh is an MFMA with K = 4H.  Two barriers
+//     per step (the staged gate gradients are read by every wave).  It writes dgates [B T][4H]; the parameter and input
+//     gradients are the existing GEMMs of ecg_linear_bwd over (dgates, layer input) and (dgates, h_{t-1}).
+//
+// Rows >= B of a ragged slice are masked at every global access (never read or written); no barrier sits in a branch.
+// Any H works: H % 4 != 0 (or a W_hh that is not 16-byte aligned) takes 4-byte W_hh loads in the forward.
+// LSTM_MAX_H = 384: the backward stages 16 x (4 Hp + 4) gate gradients + 2 x 16 x (Hp + 4) carries in LDS (Hp = H rounded
+// up to 16) = 148 KiB at H = 384 of the 160 KiB of a CU; the forward needs 3 x 16 x (Hp + 4) floats (73 KiB).
+#include "ops.h"
+
+namespace {
+
+constexpr int LSTM_ROWS = 16;
+constexpr int LSTM_THREADS = 512;
+constexpr int LSTM_WAVES = LSTM_THREADS / 64;
+constexpr int LSTM_MAX_H = 384;
+constexpr int LSTM_MAX_LAYERS = 8;
+
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }   // exp -> inf gives exactly 0
+
+struct LstmFwdDir {
+  float* gates;         // [B T][4H]: in x W_ih^T + b_ih; out (save) the activated gates
+  const float* w_hh;    // [4H][H]
+  const float* b_hh;    // [4H]
+  const float* h0;      // [B][H] of this layer and direction, or null (zeros)
+  const float* c0;
+  float* out;           // layer output + this direction's column offset, row stride ldo
+  float* hprev;         // save: [B T][H], h_{t-1} of every step (h0 at the first)
+  float* csave;         // save: [B T][H], c_t
+  float* hn;            // [B][H] or null
+  float* cn;
+  int reverse;
+};
+struct LstmFwdArgs {
+  LstmFwdDir d[2];
+  int B, T, H, ldo, batch_first, save;
+};
+
+struct LstmBwdDir {
+  const float* gates;   // activated gates of the forward
+  const float* csave;
+  const float* c0;      // [B][H] or null
+  const float* w_hh;
+  const float* dy;      // gradient of the layer output + column offset, row stride ldo; or null
+  const float* dhn;     // [B][H] or null
+  const float* dcn;
+  float* dgates;        // [B T][4H]
+  float* dh0;           // [B][H] or null
+  float* dc0;
+  int reverse;
+};
+struct LstmBwdArgs {
+  LstmBwdDir d[2];
+  int B, T, H, ldo, batch_first;
+};
+
+__device__ __forceinline__ size_t seq_row(int b, int t, int B, int T, int batch_first) {
+  return batch_first ? (size_t)b * T + t : (size_t)t * B + b;
+}
+
+template <bool V4>
+__global__ __launch_bounds__(LSTM_THREADS) void lstm_seq_fwd_kernel(LstmFwdArgs a) {
+  extern __shared__ float lstm_lds[];
+  const LstmFwdDir& p = a.d[blockIdx.y];
+  const int H = a.H, Hp = (H + 15) & ~15, HS = Hp + 4, B = a.B, T = a.T;
+  float* hb = lstm_lds;                       // [2][16][HS]
+  float* cb = lstm_lds + 2 * LSTM_ROWS * HS;  // [16][HS]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i16 = lane & 15, g4 = lane >> 4;
+  const int b0 = blockIdx.x * LSTM_ROWS;
+
+  for (int e = tid; e < LSTM_ROWS * HS; e += LSTM_THREADS) {
+    const int b = e / HS, j = e - b * HS;
+    const bool ok = j < H && b0 + b < B;
+    hb[e] = ok && p.h0 ? p.h0[(size_t)(b0 + b) * H + j] : 0.f;
+    hb[LSTM_ROWS * HS + e] = 0.f;
+    cb[e] = ok && p.c0 ? p.c0[(size_t)(b0 + b) * H + j] : 0.f;
+  }
+  __syncthreads();
+
+  const size_t HH = (size_t)H * H;
+  const int G4 = 4 * H;
+  for (int s = 0; s < T; ++s) {
+    const int t = p.reverse ? T - 1 - s : s;
+    const float* hc = hb + (s & 1) * LSTM_ROWS * HS;
+    float* hx = hb + ((s + 1) & 1) * LSTM_ROWS * HS;
+    for (int ht = wave; ht * 16 < Hp; ht += LSTM_WAVES) {
+      const int j = ht * 16 + i16;   // hidden unit: row of W_hh fed as the B operand, column of the C/D tile
+      const bool jok = j < H;
+      size_t row[4];
+      bool rok[4];
+      float xg[4][4], bh[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int b = b0 + g4 * 4 + r;
+        rok[r] = jok && b < B;
+        row[r] = seq_row(b < B ? b : B - 1, t, B, T, a.batch_first);
+      }
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        bh[g] = jok ? p.b_hh[g * H + j] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) xg[g][r] = rok[r] ? p.gates[row[r] * G4 + g * H + j] : 0.f;
+      }
+      f32x4 acc[4];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const float* wrow = p.w_hh + (size_t)(jok ? j : 0) * H;
+      for (int k0 = 0; k0 < Hp; k0 += 16) {
+        const int k = k0 + 4 * g4;   // this lane's four reduction indices of the 16-wide step: k .. k + 3
+        const float4 hv = *reinterpret_cast<const float4*>(hc + i16 * HS + k);
+        const float av[4] = {hv.x, hv.y, hv.z, hv.w};
+        float wv[4][4];
+        if (V4) {
+          const bool ok = jok && k < H;
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            float4 w = ok ? *reinterpret_cast<const float4*>(wrow + g * HH + k) : float4{0.f, 0.f, 0.f, 0.f};
+            wv[g][0] = w.x; wv[g][1] = w.y; wv[g][2] = w.z; wv[g][3] = w.w;
+          }
+        } else {
+#pragma unroll
+          for (int g = 0; g < 4; ++g)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) wv[g][u] = jok && k + u < H ? wrow[g * HH + k + u] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], wv[g][u], acc[g], 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int bl = g4 * 4 + r;
+        const float ig = sigmoidf_(acc[0][r] + xg[0][r] + bh[0]);
+        const float fg = sigmoidf_(acc[1][r] + xg[1][r] + bh[1]);
+        const float gg = tanhf(acc[2][r] + xg[2][r] + bh[2]);
+        const float og = sigmoidf_(acc[3][r] + xg[3][r] + bh[3]);
+        const float hp = hc[bl * HS + j];
+        const float c = fg * cb[bl * HS + j] + ig * gg;
+        const float h = og * tanhf(c);
+        cb[bl * HS + j] = jok ? c : 0.f;
+        hx[bl * HS + j] = jok ? h : 0.f;   // columns H .. Hp stay zero: they are reduction padding of the next step
+        if (rok[r]) {
+          p.out[row[r] * a.ldo + j] = h;
+          if (a.save) {
+            float* gp = p.gates + row[r] * G4 + j;
+            gp[0] = ig; gp[H] = fg; gp[2 * H] = gg; gp[3 * H] = og;
+            p.csave[row[r] * H + j] = c;
+            p.hprev[row[r] * H + j] = hp;
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  const float* hl = hb + (T & 1) * LSTM_ROWS * HS;
+  for (int e = tid; e < LSTM_ROWS * H; e += LSTM_THREADS) {
+    const int b = e / H, j = e - b * H;
+    if (b0 + b < B) {
+      if (p.hn) p.hn[(size_t)(b0 + b) * H + j] = hl[b * HS + j];
+      if (p.cn) p.cn[(size_t)(b0 + b) * H + j] = cb[b * HS + j];
+    }
+  }
+}
+
+__global__ __launch_bounds__(LSTM_THREADS) void lstm_seq_bwd_kernel(LstmBwdArgs a) {
+  extern __shared__ float lstm_lds[];
+  const LstmBwdDir& p = a.d[blockIdx.y];
+  const int H = a.H, Hp = (H + 15) & ~15, HS = Hp + 4, GS = 4 * Hp + 4, B = a.B, T = a.T;
+  float* dgs = lstm_lds;                  // [16][GS]: gate gradients of the step, gate g at columns g Hp .. g Hp + H
+  float* dhb = dgs + LSTM_ROWS * GS;      // [16][HS]: dh carried to the previous step
+  float* dcb = dhb + LSTM_ROWS * HS;      // [16][HS]: dc carried
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i16 = lane & 15, g4 = lane >> 4;
+  const int b0 = blockIdx.x * LSTM_ROWS;
+
+  for (int e = tid; e < LSTM_ROWS * GS; e += LSTM_THREADS) dgs[e] = 0.f;
+  for (int e = tid; e < LSTM_ROWS * HS; e += LSTM_THREADS) {
+    const int b = e / HS, j = e - b * HS;
+    const bool ok = j < H && b0 + b < B;
+    dhb[e] = ok && p.dhn ? p.dhn[(size_t)(b0 + b) * H + j] : 0.f;
+    dcb[e] = ok && p.dcn ? p.dcn[(size_t)(b0 + b) * H + j] : 0.f;
+  }
+  __syncthreads();
+
+  const int G4 = 4 * H;
+  for (int s = 0; s < T; ++s) {
+    const int t = p.reverse ? s : T - 1 - s;          // the forward walk, backwards
+    const bool first = s == T - 1;                    // the forward's first step: c_{t-1} = c0
+    const int tp = p.reverse ? t + 1 : t - 1;
+    for (int ht = wave; ht * 16 < Hp; ht += LSTM_WAVES) {
+      const int j = ht * 16 + i16;
+      const bool jok = j < H;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int bl = g4 * 4 + r, b = b0 + bl;
+        float di = 0.f, df = 0.f, dg = 0.f, dop = 0.f, dcp = 0.f;
+        if (jok && b < B) {
+          const size_t row = seq_row(b, t, B, T, a.batch_first);
+          const float* gp = p.gates + row * G4 + j;
+          const float ig = gp[0], fg = gp[H], gg = gp[2 * H], og = gp[3 * H];
+          const float c = p.csave[row * H + j];
+          const float cp = first ? (p.c0 ? p.c0[(size_t)b * H + j] : 0.f)
+                                 : p.csave[seq_row(b, tp, B, T, a.batch_first) * H + j];
+          const float dh = (p.dy ? p.dy[row * a.ldo + j] : 0.f) + dhb[bl * HS + j];
+          const float tc = tanhf(c);
+          const float dc = dcb[bl * HS + j] + dh * og * (1.f - tc * tc);
+          dop = dh * tc * og * (1.f - og);
+          di = dc * gg * ig * (1.f - ig);
+          df = dc * cp * fg * (1.f - fg);
+          dg = dc * ig * (1.f - gg * gg);
+          dcp = dc * fg;
+          float* dq = p.dgates + row * G4 + j;
+          dq[0] = di; dq[H] = df; dq[2 * H] = dg; dq[3 * H] = dop;
+        }
+        dcb[bl * HS + j] = dcp;
+        float* ds = dgs + bl * GS + j;
+        ds[0] = di; ds[Hp] = df; ds[2 * Hp] = dg; ds[3 * Hp] = dop;
+      }
+    }
+    __syncthreads();
+    // dh_{t-1}[b][k] = sum_n dgates[b][n] W_hh[n][k]: this wave's tiles of k, the same tiles it owns above
+    for (int kt = wave; kt * 16 < Hp; kt += LSTM_WAVES) {
+      const int k = kt * 16 + i16;
+      const bool kok = k < H;
+      const float* wcol = p.w_hh + (kok ? k : 0);
+      f32x4 acc[4];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int j0 = 0; j0 < Hp; j0 += 16) {
+        const int jj = j0 + 4 * g4;
+        float av[4][4], wv[4][4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const float4 d4 = *reinterpret_cast<const float4*>(dgs + i16 * GS + g * Hp + jj);
+          av[g][0] = d4.x; av[g][1] = d4.y; av[g][2] = d4.z; av[g][3] = d4.w;
+#pragma unroll
+          for (int u = 0; u < 4; ++u) wv[g][u] = kok && jj + u < H ? wcol[(size_t)(g * H + jj + u) * H] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[g][u], wv[g][u], acc[g], 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dhb[(g4 * 4 + r) * HS + k] = (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]);
+    }
+    __syncthreads();
+  }
+
+  for (int e = tid; e < LSTM_ROWS * H; e += LSTM_THREADS) {
+    const int b = e / H, j = e - b * H;
+    if (b0 + b < B) {
+      if (p.dh0) p.dh0[(size_t)(b0 + b) * H + j] = dhb[b * HS + j];
+      if (p.dc0) p.dc0[(size_t)(b0 + b) * H + j] = dcb[b * HS + j];
+    }
+  }
+}
+
+inline size_t fwd_lds(int H) { const int Hp = (H + 15) & ~15; return (size_t)3 * LSTM_ROWS * (Hp + 4) * sizeof(float); }
+inline size_t bwd_lds(int H) {
+  const int Hp = (H + 15) & ~15;
+  return (size_t)LSTM_ROWS * ((4 * Hp + 4) + 2 * (Hp + 4)) * sizeof(float);
+}
+
+int check_desc(const ecgmm_lstm_desc* d, const char* what) {
+  if (!d) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: null descriptor", what);
+  if (d->B < 1 || d->T < 1 || d->In < 1 || d->H < 1)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "%s: B=%d T=%d In=%d H=%d must all be >= 1", what, d->B, d->T, d->In, d->H);
+  if (d->H > LSTM_MAX_H)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "%s: hidden size H=%d above the cap of %d (LDS budget of the recurrence kernels)", what, d->H,
+             LSTM_MAX_H);
+  if (d->layers < 1 || d->layers > LSTM_MAX_LAYERS)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "%s: layers=%d outside 1..%d", what, d->layers, LSTM_MAX_LAYERS);
+  if ((d->bidirectional | d->batch_first | d->save_for_backward) & ~1)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "%s: bidirectional / batch_first / save_for_backward must be 0 or 1", what);
+  const int D = d->bidirectional ? 2 : 1;
+  const int wide = d->In > D * d->H ? d->In : D * d->H;
+  if ((double)d->B * d->T * (4.0 * d->H > wide ? 4.0 * d->H : wide) >= 2147483648.0)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "%s: B*T*max(4H, In)=%.0f does not fit 31 bits", what, (double)d->B * d->T * 4.0 * d->H);
+  return 0;
+}
+
+struct FwdLayout {
+  float* gates[LSTM_MAX_LAYERS][2];
+  float* csave[LSTM_MAX_LAYERS][2];
+  float* hprev[LSTM_MAX_LAYERS][2];
+  float* out[LSTM_MAX_LAYERS];   // outputs of layers 0 .. L-2 (the last layer writes y)
+  size_t bytes;
+};
+FwdLayout fwd_layout(const ecgmm_lstm_desc* d, void* ws) {
+  FwdLayout f;
+  memset(&f, 0, sizeof(f));
+  Arena ar(ws);
+  const int D = d->bidirectional ? 2 : 1, L = d->layers;
+  const size_t BT = (size_t)d->B * d->T, H = d->H;
+  if (d->save_for_backward) {
+    for (int l = 0; l < L; ++l) {
+      for (int k = 0; k < D; ++k) {
+        f.gates[l][k] = ar.take<float>(BT * 4 * H);
+        f.csave[l][k] = ar.take<float>(BT * H);
+        f.hprev[l][k] = ar.take<float>(BT * H);
+      }
+      if (l < L - 1) f.out[l] = ar.take<float>(BT * D * H);
+    }
+  } else {   // one projection buffer per direction and two layer outputs in turn
+    float* xg[2] = {nullptr, nullptr};
+    for (int k = 0; k < D; ++k) xg[k] = ar.take<float>(BT * 4 * H);
+    float* pp[2] = {nullptr, nullptr};
+    if (L > 1) { pp[0] = ar.take<float>(BT * D * H); pp[1] = ar.take<float>(BT * D * H); }
+    for (int l = 0; l < L; ++l) {
+      for (int k = 0; k < D; ++k) f.gates[l][k] = xg[k];
+      if (l < L - 1) f.out[l] = pp[l & 1];
+    }
+  }
+  f.bytes = align_up(ar.off, 256);
+  return f;
+}
+
+struct BwdLayout {
+  float* dgates[2];
+  float* dyb[2];
+  float* dxtmp;
+  void* lin;
+  size_t lin_bytes, bytes;
+};
+BwdLayout bwd_layout(const ecgmm_lstm_desc* d, void* scratch) {
+  BwdLayout b;
+  memset(&b, 0, sizeof(b));
+  Arena ar(scratch);
+  const int D = d->bidirectional ? 2 : 1, L = d->layers, H = d->H;
+  const size_t BT = (size_t)d->B * d->T;
+  const int rows = (int)BT;
+  for (int k = 0; k < D; ++k) b.dgates[k] = ar.take<float>(BT * 4 * H);
+  if (L > 1) { b.dyb[0] = ar.take<float>(BT * D * H); b.dyb[1] = ar.take<float>(BT * D * H); }
+  const size_t wide = (size_t)(d->In > D * H ? d->In : D * H);
+  if (D == 2) b.dxtmp = ar.take<float>(BT * wide);
+  size_t lin = ecg_linear_bwd_scratch(rows, d->In, 4 * H);
+  if (L > 1 && ecg_linear_bwd_scratch(rows, D * H, 4 * H) > lin) lin = ecg_linear_bwd_scratch(rows, D * H, 4 * H);
+  if (ecg_linear_bwd_scratch(rows, H, 4 * H) > lin) lin = ecg_linear_bwd_scratch(rows, H, 4 * H);
+  b.lin_bytes = lin;
+  b.lin = ar.take_bytes(lin);
+  b.bytes = align_up(ar.off, 256);
+  return b;
+}
+
+bool lds_attr_done = false;
+void set_lds_attrs() {
+  if (lds_attr_done) return;
+  (void)hipFuncSetAttribute((const void*)lstm_seq_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  (void)hipFuncSetAttribute((const void*)lstm_seq_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  (void)hipFuncSetAttribute((const void*)lstm_seq_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  lds_attr_done = true;
+}
+
+}  // namespace
+
+size_t ecg_lstm_fwd_workspace(const ecgmm_lstm_desc* d) {
+  if (check_desc(d, "lstm_fwd_workspace") != 0) return 0;
+  return fwd_layout(d, nullptr).bytes;
+}
+size_t ecg_lstm_bwd_workspace(const ecgmm_lstm_desc* d) {
+  if (check_desc(d, "lstm_bwd_workspace") != 0) return 0;
+  return bwd_layout(d, nullptr).bytes;
+}
+
+int ecg_lstm_forward(const ecgmm_lstm_desc* d, const float* x, const float* const* params, const float* h0,
+                     const float* c0, float* y, float* hn, float* cn, void* ws, size_t ws_bytes, hipStream_t s) {
+  ECG_TRY(check_desc(d, "lstm_forward"));
+  if (!x || !params || !y) ECG_FAIL(ECGMM_ERR_SHAPE, "lstm_forward: x, params and y must not be null");
+  const FwdLayout f = fwd_layout(d, ws);
+  if (!ws || ws_bytes < f.bytes)
+    ECG_FAIL(ECGMM_ERR_WORKSPACE, "lstm_forward: workspace %zu bytes, need %zu", ws_bytes, f.bytes);
+  const int D = d->bidirectional ? 2 : 1, L = d->layers, H = d->H, B = d->B, T = d->T;
+  const int rows = B * T;
+  const size_t BH = (size_t)B * H;
+  set_lds_attrs();
+  for (int l = 0; l < L; ++l) {
+    const float* in = l == 0 ? x : f.out[l - 1];
+    const int In = l == 0 ? d->In : D * H;
+    float* dst = l == L - 1 ? y : f.out[l];
+    LstmFwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = B; a.T = T; a.H = H; a.ldo = D * H; a.batch_first = d->batch_first; a.save = d->save_for_backward;
+    bool v4 = H % 4 == 0;
+    for (int k = 0; k < D; ++k) {
+      const float* const* pr = params + (size_t)(l * D + k) * 4;   // w_ih, w_hh, b_ih, b_hh
+      if (!pr[0] || !pr[1] || !pr[2] || !pr[3]) ECG_FAIL(ECGMM_ERR_SHAPE, "lstm_forward: null parameter (layer %d)", l);
+      ECG_TRY(ecg_linear_fwd(in, pr[0], pr[2], f.gates[l][k], rows, In, 4 * H, ECGMM_ACT_NONE, nullptr, s));
+      LstmFwdDir& q = a.d[k];
+      q.gates = f.gates[l][k]; q.w_hh = pr[1]; q.b_hh = pr[3];
+      q.h0 = h0 ? h0 + (size_t)(l * D + k) * BH : nullptr;
+      q.c0 = c0 ? c0 + (size_t)(l * D + k) * BH : nullptr;
+      q.out = dst + (size_t)k * H;
+      q.hprev = f.hprev[l][k]; q.csave = f.csave[l][k];
+      q.hn = hn ? hn + (size_t)(l * D + k) * BH : nullptr;
+      q.cn = cn ? cn + (size_t)(l * D + k) * BH : nullptr;
+      q.reverse = k;
+      v4 = v4 && ((uintptr_t)pr[1] & 15) == 0;
+    }
+    const dim3 grid(ceil_div(B, LSTM_ROWS), D);
+    // 2 (4H x H) FLOPs per batch row and step; W_hh once per step and slice from L2 (not HBM: 0 algorithmic bytes beyond
+    // the projections, the saved tensors and the output)
+    if (v4) hipLaunchKernelGGL(lstm_seq_fwd_kernel<true>, grid, dim3(LSTM_THREADS), fwd_lds(H), s, a);
+    else hipLaunchKernelGGL(lstm_seq_fwd_kernel<false>, grid, dim3(LSTM_THREADS), fwd_lds(H), s, a);
+    ECG_CHECK_LAUNCH("lstm_seq_fwd");
+  }
+  return 0;
+}
+
+int ecg_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const float* const* params, const float* h0,
+                      const float* c0, const float* dy, const float* dhn, const float* dcn, const void* ws, float* dx,
+                      float* const* grads, float* dh0, float* dc0, void* scratch, size_t scratch_bytes,
+                      hipStream_t s) {
+  ECG_TRY(check_desc(d, "lstm_backward"));
+  if (!d->save_for_backward) ECG_FAIL(ECGMM_ERR_SHAPE, "lstm_backward: the forward ran with save_for_backward = 0");
+  if (!x || !params || !ws) ECG_FAIL(ECGMM_ERR_SHAPE, "lstm_backward: x, params and the forward workspace must not be null");
+  const FwdLayout f = fwd_layout(d, const_cast<void*>(ws));   // read only
+  const BwdLayout w = bwd_layout(d, scratch);
+  if (!scratch || scratch_bytes < w.bytes)
+    ECG_FAIL(ECGMM_ERR_WORKSPACE, "lstm_backward: scratch %zu bytes, need %zu", scratch_bytes, w.bytes);
+  const int D = d->bidirectional ? 2 : 1, L = d->layers, H = d->H, B = d->B, T = d->T;
+  const int rows = B * T;
+  const size_t BH = (size_t)B * H;
+  (void)h0;   // h_{t-1} of every step, h0 included, is in the forward workspace
+  set_lds_attrs();
+  for (int l = L - 1; l >= 0; --l) {
+    const float* in = l == 0 ? x : f.out[l - 1];
+    const int In = l == 0 ? d->In : D * H;
+    const float* dyl = l == L - 1 ? dy : w.dyb[(l + 1) & 1];
+    LstmBwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = B; a.T = T; a.H = H; a.ldo = D * H; a.batch_first = d->batch_first;
+    for (int k = 0; k < D; ++k) {
+      const float* const* pr = params + (size_t)(l * D + k) * 4;
+      if (!pr[0] || !pr[1]) ECG_FAIL(ECGMM_ERR_SHAPE, "lstm_backward: null weight (layer %d)", l);
+      LstmBwdDir& q = a.d[k];
+      q.gates = f.gates[l][k]; q.csave = f.csave[l][k];
+      q.c0 = c0 ? c0 + (size_t)(l * D + k) * BH : nullptr;
+      q.w_hh = pr[1];
+      q.dy = dyl ? dyl + (size_t)k * H : nullptr;
+      q.dhn = dhn ? dhn + (size_t)(l * D + k) * BH : nullptr;
+      q.dcn = dcn ? dcn + (size_t)(l * D + k) * BH : nullptr;
+      q.dgates = w.dgates[k];
+      q.dh0 = dh0 ? dh0 + (size_t)(l * D + k) * BH : nullptr;
+      q.dc0 = dc0 ? dc0 + (size_t)(l * D + k) * BH : nullptr;
+      q.reverse = k;
+    }
+    hipLaunchKernelGGL(lstm_seq_bwd_kernel, dim3(ceil_div(B, LSTM_ROWS), D), dim3(LSTM_THREADS), bwd_lds(H), s, a);
+    ECG_CHECK_LAUNCH("lstm_seq_bwd");
+    float* dst = l > 0 ? w.dyb[l & 1] : dx;   // dx of layer l is the dy of layer l - 1
+    for (int k = 0; k < D; ++k) {
+      const float* const* pr = params + (size_t)(l * D + k) * 4;
+      float* const* gr = grads ? grads + (size_t)(l * D + k) * 4 : nullptr;
+      float* gwi = gr ? gr[0] : nullptr; float* gwh = gr ? gr[1] : nullptr;
+      float* gbi = gr ? gr[2] : nullptr; float* gbh = gr ? gr[3] : nullptr;
+      float* dxk = dst ? (k == 0 ? dst : w.dxtmp) : nullptr;
+      if (dxk || gwi || gbi)
+        ECG_TRY(ecg_linear_bwd(w.dgates[k], in, pr[0], dxk, gwi, gbi, rows, In, 4 * H, w.lin, w.lin_bytes, s));
+      if (dxk && k == 1) ECG_TRY(ecg_axpby(1.f, w.dxtmp, 1.f, dst, (long)rows * In, s));   // forward + reverse, in that order
+      if (gwh) ECG_TRY(ecg_linear_bwd(w.dgates[k], f.hprev[l][k], pr[1], nullptr, gwh, nullptr, rows, H, 4 * H, w.lin,
+                                      w.lin_bytes, s));
+      if (gbh) ECG_TRY(ecg_rows_sum(w.dgates[k], rows, 4 * H, gbh, 0, s));
+    }
+  }
+  return 0;
+}

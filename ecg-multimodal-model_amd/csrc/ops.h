@@ -233,6 +233,15 @@ int ecg_linear_fwd(const float* x, const float* w, const float* bias, float* y, 
 int ecg_linear_bwd(const float* dz, const float* x, const float* w, float* dx, float* dw, float* db, int B, int In,
                    int Out, void* scratch, size_t scratch_bytes, hipStream_t s);
 
+// lstm.hip: nn.LSTM plans (projection GEMMs through ecg_linear_*, the recurrence on lstm_seq_fwd / lstm_seq_bwd kernels)
+size_t ecg_lstm_fwd_workspace(const ecgmm_lstm_desc* d);
+size_t ecg_lstm_bwd_workspace(const ecgmm_lstm_desc* d);
+int ecg_lstm_forward(const ecgmm_lstm_desc* d, const float* x, const float* const* params, const float* h0,
+                     const float* c0, float* y, float* hn, float* cn, void* ws, size_t ws_bytes, hipStream_t s);
+int ecg_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const float* const* params, const float* h0,
+                      const float* c0, const float* dy, const float* dhn, const float* dcn, const void* ws, float* dx,
+                      float* const* grads, float* dh0, float* dc0, void* scratch, size_t scratch_bytes, hipStream_t s);
+
 // prof.hip
 enum { ECG_PROF_IGEMM_FWD = 0, ECG_PROF_IGEMM_DGRAD = 1, ECG_PROF_WGRAD = 2, ECG_PROF_STEM_FWD = 3, ECG_PROF_STEM_WGRAD = 4,
        ECG_PROF_IGEMM_F32_FWD = 5, ECG_PROF_IGEMM_F32_DGRAD = 6 };  // exact-fp32 instantiation (other MFMA peak): own kinds

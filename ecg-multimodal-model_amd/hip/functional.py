@@ -421,3 +421,131 @@ class BatchNorm1dFn(torch.autograd.Function):
 
 def batch_norm1d(x, gamma, beta, rm, rv, nbt, training, momentum=0.1, eps=1e-5, relu=False):
     return BatchNorm1dFn.apply(x, gamma, beta, rm, rv, nbt, training, momentum, eps, relu)
+
+
+# --------------------------------------------------------------------------------------------
+# LSTM (multi-layer, bidirectional)      reference: nn.LSTM at train_physionet2.py:75-76,94
+# --------------------------------------------------------------------------------------------
+def _ptr_table(tensors):
+    return (vp * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _grad_wanted(p):
+    """Inside a backward: does this pass accumulate into ``p.grad``?  ``ctx.needs_input_grad`` only says that ``p`` required
+    grad at the forward; ``torch.autograd.grad(..., inputs)`` and ``backward(inputs=...)`` that do not name ``p`` run this
+    node without ``p``'s AccumulateGrad node, which the engine reports.  Where it cannot tell, the sink is written."""
+    with torch.enable_grad():
+        node = p.view_as(p).grad_fn.next_functions[0][0]
+    try:
+        return torch._C._will_engine_execute_node(node)
+    except RuntimeError:   # autograd.grad() naming a leaf itself: not answered by the engine
+        return True
+
+
+class LSTMFn(torch.autograd.Function):
+    """y, h_n, c_n = LSTM(x, h0, c0; params).  ``params`` in torch's ``_flat_weights`` order (per layer, per direction:
+    w_ih, w_hh, b_ih, b_hh).  The forward keeps its workspace (activated gates, c_t, h_{t-1}) on ``ctx`` only when some
+    input requires grad; the backward reads it and writes parameter gradients into their sinks."""
+
+    @staticmethod
+    def forward(ctx, x, h0, c0, cfg, *params):
+        hidden, layers, bidirectional, batch_first = cfg
+        _require_cuda(x, "lstm")
+        for t in (h0, c0) + params:
+            if t is not None:
+                _require_cuda(t, "lstm")
+        D = 2 if bidirectional else 1
+        if x.dim() != 3:
+            raise RuntimeError(f"lstm: input must be 3-D (batched), got {x.dim()}-D")
+        if len(params) != 4 * layers * D:
+            raise RuntimeError(f"lstm: {len(params)} parameters, expected {4 * layers * D}")
+        x = f32c(x)
+        B, T = (x.shape[0], x.shape[1]) if batch_first else (x.shape[1], x.shape[0])
+        In = x.shape[2]
+        h0 = None if h0 is None else f32c(h0)
+        c0 = None if c0 is None else f32c(c0)
+        for t, name in ((h0, "h_0"), (c0, "c_0")):
+            if t is not None and tuple(t.shape) != (layers * D, B, hidden):
+                raise RuntimeError(f"lstm: {name} has shape {tuple(t.shape)}, expected {(layers * D, B, hidden)}")
+        for p in params:
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError("lstm: parameters must be contiguous fp32")
+        save = any(ctx.needs_input_grad)
+        desc = L.LSTMDesc(B, T, In, hidden, layers, int(bidirectional), int(batch_first), int(save))
+        lib = L.lib()
+        nb = lib.ecgmm_lstm_fwd_workspace(C.byref(desc))
+        if nb == 0:
+            raise RuntimeError("ecgmm lstm: " + lib.ecgmm_last_error().decode(errors="replace"))
+        ws = new_bytes(nb, x.device) if save else _Scratch.get("lstm_fwd", nb, x.device)
+        yshape = (B, T, D * hidden) if batch_first else (T, B, D * hidden)
+        y = torch.empty(yshape, device=x.device, dtype=torch.float32)
+        hn = torch.empty(layers * D, B, hidden, device=x.device, dtype=torch.float32)
+        cn = torch.empty_like(hn)
+        L.check(lib.ecgmm_lstm_forward(C.byref(desc), ptr(x), _ptr_table(params), ptr(h0), ptr(c0), ptr(y), ptr(hn),
+                                       ptr(cn), ptr(ws), ws.numel(), stream()), "lstm_forward")
+        if save:
+            ctx.desc, ctx.ws, ctx.params = desc, ws, params
+            ctx.save_for_backward(x, h0, c0)
+            ctx.set_materialize_grads(False)
+        return y, hn, cn
+
+    @staticmethod
+    def backward(ctx, dy, dhn, dcn):
+        x, h0, c0 = ctx.saved_tensors
+        desc, params = ctx.desc, ctx.params
+        dy, dhn, dcn = (None if g is None else f32c(g) for g in (dy, dhn, dcn))
+        need = ctx.needs_input_grad
+        dx = torch.empty_like(x) if need[0] else None
+        dh0 = torch.empty_like(h0) if h0 is not None and need[1] else None
+        dc0 = torch.empty_like(c0) if c0 is not None and need[2] else None
+        # sinks only for the gradients this backward was asked for (torch.autograd.grad w.r.t. inputs leaves .grad alone)
+        sinks = [grad_sink(p) if need[4 + i] and _grad_wanted(p) else None for i, p in enumerate(params)]
+        lib = L.lib()
+        nb = lib.ecgmm_lstm_bwd_workspace(C.byref(desc))
+        scratch = _Scratch.get("lstm_bwd", nb, x.device)
+        L.check(lib.ecgmm_lstm_backward(C.byref(desc), ptr(x), _ptr_table(params), ptr(h0), ptr(c0), ptr(dy), ptr(dhn),
+                                        ptr(dcn), ptr(ctx.ws), ptr(dx), _ptr_table(sinks), ptr(dh0), ptr(dc0),
+                                        ptr(scratch), scratch.numel(), stream()), "lstm_backward")
+        return (dx, dh0, dc0, None) + (None,) * len(params)
+
+
+def lstm(x, hx, params, hidden_size, num_layers=1, bidirectional=False, batch_first=False):
+    """``torch.nn.LSTM`` forward (with bias, no dropout, no projection): returns ``(output, (h_n, c_n))``."""
+    h0, c0 = (None, None) if hx is None else hx
+    y, hn, cn = LSTMFn.apply(x, h0, c0, (int(hidden_size), int(num_layers), bool(bidirectional), bool(batch_first)),
+                             *params)
+    return y, (hn, cn)
+
+
+class SeqMeanFn(torch.autograd.Function):
+    """mean over the time axis of a [B, T, C] fp32 sequence (ecgmm_avgpool forward, ecgmm_bcast_rows backward)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        _require_cuda(x, "seq_mean")
+        x = f32c(x)
+        B, T, Cn = x.shape
+        # the pooling kernel wants C / 4 to divide 256: wider rows are zero-padded to the next such width (plumbing copy)
+        Cp = next((c for c in (4, 8, 16, 32, 64, 128, 256, 512, 1024) if c >= Cn), None) if (Cn % 4 or 256 % (Cn // 4)) else Cn
+        if Cp is None:
+            raise RuntimeError(f"seq_mean: C={Cn} above 1024 is not supported")
+        if Cp != Cn:
+            xp = torch.zeros(B, T, Cp, device=x.device, dtype=torch.float32)
+            xp[:, :, :Cn] = x
+            x = xp
+        out = torch.empty(B, Cp, device=x.device, dtype=torch.float32)
+        L.check(L.lib().ecgmm_avgpool(L.F32, ptr(x), ptr(out), B, T, Cp, None, stream()), "avgpool")
+        ctx.shape = (B, T, Cn)
+        return out[:, :Cn].contiguous() if Cp != Cn else out
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, T, Cn = ctx.shape
+        dy = f32c(dy)
+        dx = torch.empty(B, T, Cn, device=dy.device, dtype=torch.float32)
+        L.check(L.lib().ecgmm_bcast_rows(L.F32, ptr(dy), ptr(dx), B, T, Cn, 1.0 / T, stream()), "bcast_rows")
+        return dx
+
+
+def seq_mean(x):
+    return SeqMeanFn.apply(x)

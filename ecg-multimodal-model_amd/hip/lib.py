@@ -38,6 +38,10 @@ class HeadDesc(C.Structure):
                 ("ln_eps", f32), ("dropout_p", f32), ("seed", u64), ("offset", u64)]
 
 
+class LSTMDesc(C.Structure):
+    _fields_ = [(n, i32) for n in ("B", "T", "In", "H", "layers", "bidirectional", "batch_first", "save_for_backward")]
+
+
 P = C.POINTER
 # name -> (restype, argtypes).  Must list every function declared in include/ecgmm.h
 # (tests/test_abi.py parses the header and checks the two agree).
@@ -176,6 +180,10 @@ SIGNATURES = {
     "ecgmm_prof_enable": (i32, [i32]),
     "ecgmm_prof_pause": (i32, [i32]),
     "ecgmm_prof_collect": (i32, [i32, P(f64), P(f64), P(f64), P(i64)]),
+    "ecgmm_lstm_fwd_workspace": (sz, [P(LSTMDesc)]),
+    "ecgmm_lstm_bwd_workspace": (sz, [P(LSTMDesc)]),
+    "ecgmm_lstm_forward": (i32, [P(LSTMDesc), vp, P(vp), vp, vp, vp, vp, vp, vp, sz, vp]),
+    "ecgmm_lstm_backward": (i32, [P(LSTMDesc), vp, P(vp), vp, vp, vp, vp, vp, vp, vp, P(vp), vp, vp, vp, sz, vp]),
 }
 
 # Entry points of the input-gradient / Grad-CAM feature.  A library selected with ECGMM_LIB for an A/B run may predate them:
@@ -188,7 +196,9 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  "ecgmm_resnet1d_infer_workspace", "ecgmm_resnet1d_infer", "ecgmm_infer_down_side", "ecgmm_conv_fwd_fused",
                  "ecgmm_fold_conv_bn", "ecgmm_relu_maxpool", "ecgmm_gate_res_relu",
                  # the PhysioNet-2017 path (ecgmm/train_physionet.py)
-                 "ecgmm_signal_filter_zscore", "ecgmm_signal_gather_augment")
+                 "ecgmm_signal_filter_zscore", "ecgmm_signal_gather_augment",
+                 # nn.LSTM (ecgmm.hip.nn.LSTM)
+                 "ecgmm_lstm_fwd_workspace", "ecgmm_lstm_bwd_workspace", "ecgmm_lstm_forward", "ecgmm_lstm_backward")
 
 _lib = None
 

@@ -136,3 +136,53 @@ class Sequential(nn.Sequential):
                 x = m(x)
             i += 1
         return x
+
+
+class LSTM(nn.Module):
+    """``torch.nn.LSTM`` on the HIP recurrence kernels (train_physionet2.py:75-76): same parameter names, shapes,
+    registration order, initialisation and state_dict keys, so checkpoints move in both directions.  Train and eval modes
+    compute the same function (there is no dropout)."""
+
+    def __init__(self, input_size, hidden_size, num_layers=1, bias=True, batch_first=False, dropout=0.0,
+                 bidirectional=False, proj_size=0):
+        super().__init__()
+        if dropout != 0:
+            raise ValueError(f"LSTM: dropout={dropout} is not supported (only dropout=0)")
+        if proj_size != 0:
+            raise ValueError(f"LSTM: proj_size={proj_size} is not supported (only proj_size=0)")
+        if not bias:
+            raise ValueError("LSTM: bias=False is not supported (only bias=True)")
+        if input_size < 1 or hidden_size < 1 or num_layers < 1:
+            raise ValueError("LSTM: input_size, hidden_size and num_layers must be >= 1")
+        self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
+        self.bias, self.batch_first, self.dropout, self.bidirectional, self.proj_size = True, batch_first, 0.0, bidirectional, 0
+        D = 2 if bidirectional else 1
+        self._flat_names = []
+        for layer in range(num_layers):
+            for direction in range(D):
+                In = input_size if layer == 0 else D * hidden_size
+                sfx = f"_l{layer}" + ("_reverse" if direction else "")
+                for name, shape in (("weight_ih", (4 * hidden_size, In)), ("weight_hh", (4 * hidden_size, hidden_size)),
+                                    ("bias_ih", (4 * hidden_size,)), ("bias_hh", (4 * hidden_size,))):
+                    setattr(self, name + sfx, nn.Parameter(torch.empty(*shape)))
+                    self._flat_names.append(name + sfx)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        bound = 1.0 / math.sqrt(self.hidden_size)
+        for p in self.parameters():
+            nn.init.uniform_(p, -bound, bound)
+
+    def forward(self, x, hx=None):
+        if isinstance(x, nn.utils.rnn.PackedSequence):
+            raise TypeError("LSTM: a PackedSequence input is not supported (pass a padded tensor)")
+        if x.dim() != 3:
+            raise ValueError(f"LSTM: input must be 3-D (batched); unbatched {x.dim()}-D input is not supported")
+        if x.shape[2] != self.input_size:
+            raise ValueError(f"LSTM: input has {x.shape[2]} features, expected input_size={self.input_size}")
+        params = [getattr(self, n) for n in self._flat_names]
+        return HF.lstm(x, hx, params, self.hidden_size, self.num_layers, self.bidirectional, self.batch_first)
+
+    def extra_repr(self):
+        return (f"{self.input_size}, {self.hidden_size}, num_layers={self.num_layers}, batch_first={self.batch_first}, "
+                f"bidirectional={self.bidirectional}")

@@ -557,6 +557,34 @@ int ecgmm_relu_maxpool(int dtype, const void* y, void* out, int N, int H, int W,
 int ecgmm_gate_res_relu(int dtype, const void* y, const float* gate, const void* res, void* out, int64_t M, int C,
                         int rows_per_sample, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * nn.LSTM(In, H, num_layers, batch_first, bidirectional) with bias, fp32 (train_physionet2.py:75-76,94: the CRNN's
+ * nn.LSTM(512, 200, num_layers=3, batch_first=True, bidirectional=True)).  Gate order i, f, g, o; the reverse direction
+ * walks t = T-1 .. 0; the output is [fwd | rev] along features; layer l > 0 reads the D*H wide output of layer l-1.
+ * H <= 384 (the LDS budget of the recurrence kernels), layers <= 8.
+ *   x [B,T,In] (batch_first = 1) or [T,B,In] (0: rows are indexed t*B + b, no transposing copy); y likewise, D*H wide.
+ *   params / grads: torch's _flat_weights order -- per layer, per direction: w_ih [4H,In_l], w_hh [4H,H], b_ih, b_hh [4H].
+ *   h0, c0, hn, cn, dhn, dcn, dh0, dc0: [layers*D, B, H]; h0 / c0 null = zeros; hn / cn nullable.
+ * save_for_backward = 1 keeps the activated gates, c_t and h_{t-1} of every layer and direction in the forward
+ * workspace, which ecgmm_lstm_backward only READS; 0 keeps nothing beyond the layer outputs (smaller workspace).
+ * Backward: dy, dhn, dcn each nullable (zero cotangent); dx, dh0, dc0 and every grads entry nullable (not computed);
+ * gradients are WRITTEN, reductions in a fixed order.  The workspace queries need no GPU and return 0 on a bad
+ * descriptor (ecgmm_last_error() says why). */
+typedef struct {
+  int B, T, In, H, layers, bidirectional, batch_first, save_for_backward;
+} ecgmm_lstm_desc;
+/* train_physionet2.py:75-76,94 */
+size_t ecgmm_lstm_fwd_workspace(const ecgmm_lstm_desc* d);
+/* train_physionet2.py:75-76,94 (its loss.backward()) */
+size_t ecgmm_lstm_bwd_workspace(const ecgmm_lstm_desc* d);
+/* train_physionet2.py:75-76,94: x, (h_n, c_n) = self.lstm(x) */
+int ecgmm_lstm_forward(const ecgmm_lstm_desc* d, const float* x, const float* const* params, const float* h0,
+                       const float* c0, float* y, float* hn, float* cn, void* ws, size_t ws_bytes, void* stream);
+/* train_physionet2.py:75-76,94: the nn.LSTM part of loss.backward() */
+int ecgmm_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const float* const* params, const float* h0,
+                        const float* c0, const float* dy, const float* dhn, const float* dcn, const void* ws, float* dx,
+                        float* const* grads, float* dh0, float* dc0, void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
