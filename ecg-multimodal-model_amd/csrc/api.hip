@@ -339,4 +339,36 @@ int ecgmm_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const float* c
                            S_(stream));
 }
 
+// ---- CRNN front end, per-op (crnn_front.hip; train_physionet2.py:55-65, 87-93) ----
+int ecgmm_conv5_in1_stats_rows(int N, int H, int W) { return ecg_conv5_in1_stats_rows(N, H, W); }
+int ecgmm_conv5_in1_fwd(int dtype, const float* x, const float* w_oihw, const float* bias, void* y, float* stats, int N, int H,
+                        int W, void* stream) {
+  return ecg_conv5_in1_fwd(dtype, x, w_oihw, bias, y, stats, N, H, W, S_(stream));
+}
+size_t ecgmm_conv5_in1_bwd_weight_workspace(int N, int H, int W) { return ecg_conv5_in1_wgrad_workspace(N, H, W); }
+int ecgmm_conv5_in1_bwd_weight(int dtype, const float* x, const void* dy, float* dw_oihw, float* dbias, int accumulate, void* ws,
+                               size_t ws_bytes, int N, int H, int W, void* stream) {
+  return ecg_conv5_in1_wgrad(dtype, x, dy, dw_oihw, dbias, accumulate, ws, ws_bytes, N, H, W, S_(stream));
+}
+size_t ecgmm_conv5_bwd_weight_workspace(int dtype, const ecgmm_conv_desc* c) {
+  if (!c) { ecg_set_error("conv5_bwd_weight_workspace: null desc"); return 0; }
+  return ecg_conv5_wgrad_workspace(dtype, geom_of(c));
+}
+int ecgmm_conv5_bwd_weight(int dtype, const ecgmm_conv_desc* c, const void* x, const void* dy, float* dw_oihw, int accumulate,
+                           void* ws, size_t ws_bytes, void* stream) {
+  if (!c) ECG_FAIL(ECGMM_ERR_SHAPE, "conv5_bwd_weight: null desc");
+  return ecg_conv5_wgrad(dtype, geom_of(c), x, dy, dw_oihw, accumulate, ws, ws_bytes, S_(stream));
+}
+int ecgmm_bnrelu_maxpool2(int dtype, const void* y, const float* coef, void* out, uint8_t* idx, int N, int H, int W, int C,
+                          int seq_layout, void* stream) {
+  return ecg_bnrelu_maxpool2(dtype, y, coef, out, idx, N, H, W, C, seq_layout, S_(stream));
+}
+size_t ecgmm_pool2_bn_bwd_workspace(int N, int H, int W, int C) { return ecg_pool2_bn_bwd_workspace(N, H, W, C); }
+int ecgmm_pool2_bn_bwd(int dtype, const void* dp, const uint8_t* idx, const void* y, const float* coef, int training,
+                       float* dgamma, float* dbeta, void* dy, float* dbias, int N, int H, int W, int C, int seq_layout,
+                       void* ws, size_t ws_bytes, void* stream) {
+  return ecg_pool2_bn_bwd(dtype, dp, idx, y, coef, training, dgamma, dbeta, dy, dbias, N, H, W, C, seq_layout, ws, ws_bytes,
+                          S_(stream));
+}
+
 }  // extern "C"

@@ -242,6 +242,24 @@ int ecg_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const float* con
                       const float* c0, const float* dy, const float* dhn, const float* dcn, const void* ws, float* dx,
                       float* const* grads, float* dh0, float* dc0, void* scratch, size_t scratch_bytes, hipStream_t s);
 
+// crnn_front.hip: the CRNN front end's own kernels (train_physionet2.py:55-65, 87-93).  Conv2d(1, 32, 5, pad 2) straight from
+// the [N][H][W] fp32 spectrogram; the 5x5 weight gradient (Cin, Cout multiples of 32); [BatchNorm -> ReLU -> MaxPool2d(2)]
+int ecg_conv5_in1_stats_rows(int N, int H, int W);
+int ecg_conv5_in1_fwd(int dtype, const float* x, const float* w, const float* bias, void* y, float* stats, int N, int H,
+                      int W, hipStream_t s);
+size_t ecg_conv5_in1_wgrad_workspace(int N, int H, int W);
+int ecg_conv5_in1_wgrad(int dtype, const float* x, const void* dy, float* dw, float* db, int accumulate, void* ws,
+                        size_t ws_bytes, int N, int H, int W, hipStream_t s);
+size_t ecg_conv5_wgrad_workspace(int dtype, const ConvGeom& g);
+int ecg_conv5_wgrad(int dtype, const ConvGeom& g, const void* x, const void* dy, float* dw, int accumulate, void* ws,
+                    size_t ws_bytes, hipStream_t s);
+int ecg_bnrelu_maxpool2(int dtype, const void* y, const float* coef, void* out, unsigned char* idx, int N, int H, int W, int C,
+                        int seq_layout, hipStream_t s);
+size_t ecg_pool2_bn_bwd_workspace(int N, int H, int W, int C);
+int ecg_pool2_bn_bwd(int dtype, const void* dp, const unsigned char* idx, const void* y, const float* coef, int training,
+                     float* dgamma, float* dbeta, void* dy, float* dbias, int N, int H, int W, int C, int seq_layout, void* ws,
+                     size_t ws_bytes, hipStream_t s);
+
 // prof.hip
 enum { ECG_PROF_IGEMM_FWD = 0, ECG_PROF_IGEMM_DGRAD = 1, ECG_PROF_WGRAD = 2, ECG_PROF_STEM_FWD = 3, ECG_PROF_STEM_WGRAD = 4,
        ECG_PROF_IGEMM_F32_FWD = 5, ECG_PROF_IGEMM_F32_DGRAD = 6 };  // exact-fp32 instantiation (other MFMA peak): own kinds

@@ -549,3 +549,60 @@ class SeqMeanFn(torch.autograd.Function):
 
 def seq_mean(x):
     return SeqMeanFn.apply(x)
+
+
+# --------------------------------------------------------------------------------------------
+# CRNN conv front end (three ConvBlocks as one plan)      reference: train_physionet2.py:55-65, 87-93
+# --------------------------------------------------------------------------------------------
+class CRNNFrontFn(torch.autograd.Function):
+    """seq [B, T/8, 128*(F/8)] = front end(x [B,1,F,T]; 12 params, 9 buffers).  Holds the forward workspace on ``ctx``; the
+    backward writes the parameter gradients into their sinks.  No input gradient: the spectrogram is data."""
+
+    @staticmethod
+    def forward(ctx, x, cfg, buffers, *params):
+        training, momentum, eps, dtype = cfg
+        _require_cuda(x, "crnn_front")
+        for t in tuple(params) + tuple(buffers):
+            _require_cuda(t, "crnn_front parameter")
+        if x.dim() != 4 or x.shape[1] != 1:
+            raise ValueError(f"crnn_front expects [B,1,F,T], got {tuple(x.shape)}")
+        if len(params) != 12 or len(buffers) != 9:
+            raise RuntimeError(f"crnn_front: {len(params)} parameters / {len(buffers)} buffers, expected 12 / 9")
+        for p in params:
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError("crnn_front: parameters must be contiguous fp32")
+        x = f32c(x)
+        B, _, F, T = x.shape
+        desc = L.CRNNFrontDesc(B, F, T, int(dtype), int(bool(training)), float(momentum), float(eps))
+        lib = L.lib()
+        nb = lib.ecgmm_crnn_front_fwd_workspace(C.byref(desc))
+        if nb == 0:
+            L.check(1, "crnn_front workspace query")
+        ws = new_bytes(nb, x.device)
+        seq = torch.empty(B, T // 8, 128 * (F // 8), device=x.device, dtype=torch.float32)
+        L.check(lib.ecgmm_crnn_front_forward(C.byref(desc), ptr(x), _ptr_table(params), _ptr_table(buffers), ptr(seq),
+                                             ptr(ws), ws.numel(), stream()), "crnn_front forward")
+        ctx.desc, ctx.ws, ctx.x, ctx.params = desc, ws, x, params
+        return seq
+
+    @staticmethod
+    def backward(ctx, dseq):
+        desc, params = ctx.desc, ctx.params
+        if ctx.ws is None:
+            raise RuntimeError("crnn_front: second backward through a training-mode forward whose workspace was released")
+        lib = L.lib()
+        dseq = f32c(dseq)
+        sinks = [grad_sink(p) if ctx.needs_input_grad[3 + i] else None for i, p in enumerate(params)]
+        nb = lib.ecgmm_crnn_front_bwd_workspace(C.byref(desc))
+        bws = _Scratch.get("crnn_front_bwd", nb, dseq.device)
+        L.check(lib.ecgmm_crnn_front_backward(C.byref(desc), ptr(ctx.x), ptr(dseq), _ptr_table(params), _ptr_table(sinks),
+                                              ptr(ctx.ws), ptr(bws), bws.numel(), stream()), "crnn_front backward")
+        if desc.training:
+            ctx.ws = None
+        return (None, None, None) + (None,) * len(params)
+
+
+def crnn_front(x, params, buffers, training, momentum=0.1, eps=1e-5, dtype=L.F32):
+    """conv1..conv3 of the CRNN + permute + Flatten: ``params`` per block conv weight, conv bias, bn weight, bn bias;
+    ``buffers`` per block running_mean, running_var, num_batches_tracked"""
+    return CRNNFrontFn.apply(x, (training, momentum, eps, dtype), tuple(buffers), *params)

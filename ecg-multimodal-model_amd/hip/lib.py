@@ -42,6 +42,10 @@ class LSTMDesc(C.Structure):
     _fields_ = [(n, i32) for n in ("B", "T", "In", "H", "layers", "bidirectional", "batch_first", "save_for_backward")]
 
 
+class CRNNFrontDesc(C.Structure):
+    _fields_ = [("B", i32), ("F", i32), ("T", i32), ("dtype", i32), ("training", i32), ("bn_momentum", f32), ("bn_eps", f32)]
+
+
 P = C.POINTER
 # name -> (restype, argtypes).  Must list every function declared in include/ecgmm.h
 # (tests/test_abi.py parses the header and checks the two agree).
@@ -184,6 +188,19 @@ SIGNATURES = {
     "ecgmm_lstm_bwd_workspace": (sz, [P(LSTMDesc)]),
     "ecgmm_lstm_forward": (i32, [P(LSTMDesc), vp, P(vp), vp, vp, vp, vp, vp, vp, sz, vp]),
     "ecgmm_lstm_backward": (i32, [P(LSTMDesc), vp, P(vp), vp, vp, vp, vp, vp, vp, vp, P(vp), vp, vp, vp, sz, vp]),
+    "ecgmm_conv5_in1_stats_rows": (i32, [i32, i32, i32]),
+    "ecgmm_conv5_in1_fwd": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "ecgmm_conv5_in1_bwd_weight_workspace": (sz, [i32, i32, i32]),
+    "ecgmm_conv5_in1_bwd_weight": (i32, [i32, vp, vp, vp, vp, i32, vp, sz, i32, i32, i32, vp]),
+    "ecgmm_conv5_bwd_weight_workspace": (sz, [i32, P(ConvDesc)]),
+    "ecgmm_conv5_bwd_weight": (i32, [i32, P(ConvDesc), vp, vp, vp, i32, vp, sz, vp]),
+    "ecgmm_bnrelu_maxpool2": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "ecgmm_pool2_bn_bwd_workspace": (sz, [i32, i32, i32, i32]),
+    "ecgmm_pool2_bn_bwd": (i32, [i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
+    "ecgmm_crnn_front_fwd_workspace": (sz, [P(CRNNFrontDesc)]),
+    "ecgmm_crnn_front_bwd_workspace": (sz, [P(CRNNFrontDesc)]),
+    "ecgmm_crnn_front_forward": (i32, [P(CRNNFrontDesc), vp, P(vp), P(vp), vp, vp, sz, vp]),
+    "ecgmm_crnn_front_backward": (i32, [P(CRNNFrontDesc), vp, vp, P(vp), P(vp), vp, vp, sz, vp]),
 }
 
 # Entry points of the input-gradient / Grad-CAM feature.  A library selected with ECGMM_LIB for an A/B run may predate them:
@@ -198,7 +215,13 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  # the PhysioNet-2017 path (ecgmm/train_physionet.py)
                  "ecgmm_signal_filter_zscore", "ecgmm_signal_gather_augment",
                  # nn.LSTM (ecgmm.hip.nn.LSTM)
-                 "ecgmm_lstm_fwd_workspace", "ecgmm_lstm_bwd_workspace", "ecgmm_lstm_forward", "ecgmm_lstm_backward")
+                 "ecgmm_lstm_fwd_workspace", "ecgmm_lstm_bwd_workspace", "ecgmm_lstm_forward", "ecgmm_lstm_backward",
+                 # the CRNN front end's per-op kernels (csrc/crnn_front.hip)
+                 "ecgmm_conv5_in1_stats_rows", "ecgmm_conv5_in1_fwd", "ecgmm_conv5_in1_bwd_weight_workspace",
+                 "ecgmm_conv5_in1_bwd_weight", "ecgmm_conv5_bwd_weight_workspace", "ecgmm_conv5_bwd_weight",
+                 "ecgmm_bnrelu_maxpool2", "ecgmm_pool2_bn_bwd_workspace", "ecgmm_pool2_bn_bwd",
+                 "ecgmm_crnn_front_fwd_workspace", "ecgmm_crnn_front_bwd_workspace", "ecgmm_crnn_front_forward",
+                 "ecgmm_crnn_front_backward")
 
 _lib = None
 

@@ -585,6 +585,67 @@ int ecgmm_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const float* c
                         const float* c0, const float* dy, const float* dhn, const float* dcn, const void* ws, float* dx,
                         float* const* grads, float* dh0, float* dc0, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * CRNN convolutional front end, per-op (train_physionet2.py:55-65, 87-93): three ConvBlocks
+ * Conv2d(k = 5, pad = 2, bias) -> BatchNorm2d -> ReLU -> MaxPool2d(2) on a log-spectrogram [B, 1, F, T].  Activations are
+ * channels-last with H = frequency, W = time.  Forward and input gradient of the 32 -> 64 and 64 -> 128 convolutions are
+ * ecgmm_conv_fwd / ecgmm_conv_fwd_wgrows / ecgmm_conv_bwd_data at R = S = 5, pad 2 (weights from ecgmm_pack_conv_weight,
+ * RS = 25); the entry points below are the pieces those do not cover.  ecgmm_conv_bwd_weight goes on refusing 25 taps.
+ * Every split reduction is a fixed-order second pass (no float atomics): results are run-to-run identical.
+ * ------------------------------------------------------------------------------------------- */
+/* train_physionet2.py:59 with in_channels = 1 (line 70): x [N,H,W] fp32 (Cin = 1: NCHW == NHWC), w_oihw [32,1,5,5] fp32,
+ * bias [32] (nullable) -> y [N,H,W,32] compute dtype.  ECGMM_BF16 rounds x and w to bf16; products and sums are fp32.
+ * stats (nullable): ecgmm_conv5_in1_stats_rows(N,H,W) BatchNorm partial rows [2][32] (+ ECGMM_BN_TAIL_ROWS spare rows). */
+int ecgmm_conv5_in1_stats_rows(int N, int H, int W);
+int ecgmm_conv5_in1_fwd(int dtype, const float* x, const float* w_oihw, const float* bias, void* y, float* stats, int N, int H,
+                        int W, void* stream);
+/* train_physionet2.py:59, 70 (its loss.backward()): dw_oihw [32,1,5,5] and dbias [32] fp32 (either nullable) from x and
+ * dy [N,H,W,32] (compute dtype).  accumulate != 0 adds into both.  No input gradient: the spectrogram is data. */
+size_t ecgmm_conv5_in1_bwd_weight_workspace(int N, int H, int W);
+int ecgmm_conv5_in1_bwd_weight(int dtype, const float* x, const void* dy, float* dw_oihw, float* dbias, int accumulate, void* ws,
+                               size_t ws_bytes, int N, int H, int W, void* stream);
+/* train_physionet2.py:59, 71-72 (their loss.backward()): weight gradient of a 5x5, stride 1, pad 2 convolution with Cin and
+ * Cout multiples of 32: dw_oihw [Cout,Cin,5,5] fp32 from x [N,H,W,Cin] and dy [N,H,W,Cout] (compute dtype).  accumulate as
+ * in ecgmm_conv_bwd_weight.  The workspace query needs no GPU and returns 0 on a descriptor it does not serve. */
+size_t ecgmm_conv5_bwd_weight_workspace(int dtype, const ecgmm_conv_desc* c);
+int ecgmm_conv5_bwd_weight(int dtype, const ecgmm_conv_desc* c, const void* x, const void* dy, float* dw_oihw, int accumulate,
+                           void* ws, size_t ws_bytes, void* stream);
+/* train_physionet2.py:60-62: relu(bn(y)) -> MaxPool2d(2), floor semantics (the last row / column of an odd extent is
+ * dropped); ties go to the first element of the window in row-major order, as torch.  y [N,H,W,C] compute dtype, coef [4][C]
+ * (ecgmm_bn_finalize / ecgmm_bn_eval_coef), C = 32, 64, 128 or 256.  out [N,H/2,W/2,C] compute dtype, or with
+ * seq_layout != 0 the LSTM's input seq[n][w][c * (H/2) + h] fp32 (permute(0,3,1,2) + Flatten(2), train_physionet2.py:92-93).
+ * idx [N,H/2,W/2,C] (nullable): position of the winner in its window, 2 * row + column. */
+int ecgmm_bnrelu_maxpool2(int dtype, const void* y, const float* coef, void* out, uint8_t* idx, int N, int H, int W, int C,
+                          int seq_layout, void* stream);
+/* train_physionet2.py:60-62 (their loss.backward()): backward of [BatchNorm -> ReLU -> MaxPool2d(2)].  dp = gradient of the
+ * pooled output in the layout ecgmm_bnrelu_maxpool2 wrote it (seq_layout: fp32).  training != 0: batch-statistics form, the
+ * reductions run over all N H W conv outputs (rows / columns the floor dropped receive no pooled gradient but count);
+ * training == 0: the affine form behind an eval-mode forward (as ecgmm_bn_eval_bwd).  dgamma, dbeta [C], dy [N,H,W,C]
+ * (compute dtype) and dbias [C] (= column sum of dy: the convolution's bias gradient) are each nullable. */
+size_t ecgmm_pool2_bn_bwd_workspace(int N, int H, int W, int C);
+int ecgmm_pool2_bn_bwd(int dtype, const void* dp, const uint8_t* idx, const void* y, const float* coef, int training,
+                       float* dgamma, float* dbeta, void* dy, float* dbias, int N, int H, int W, int C, int seq_layout,
+                       void* ws, size_t ws_bytes, void* stream);
+
+/* The three blocks as ONE call per direction (train_physionet2.py:55-65, 87-93: conv1..conv3 of CRNN, permute, Flatten).
+ * spec [B,1,F,T] fp32; params (12): per block conv weight [cout,cin,5,5], conv bias, bn weight, bn bias (cout = 32, 64,
+ * 128); buffers (9): per block running_mean, running_var, num_batches_tracked (int64); seq_out [B, T/8, 128 * (F/8)] fp32.
+ * training = 0 uses the running statistics; a backward behind it is the affine form.  grads[i] == NULL skips a parameter;
+ * gradients are WRITTEN.  The forward workspace is only read by the backward.  F < 8, T < 8, an unknown dtype or a short
+ * workspace are refused with a message; the workspace queries need no GPU and return 0 on a bad descriptor. */
+typedef struct {
+  int B, F, T, dtype, training;
+  float bn_momentum, bn_eps;
+} ecgmm_crnn_front_desc;
+/* train_physionet2.py:55-65, 87-93 */
+size_t ecgmm_crnn_front_fwd_workspace(const ecgmm_crnn_front_desc* d);
+size_t ecgmm_crnn_front_bwd_workspace(const ecgmm_crnn_front_desc* d);
+int ecgmm_crnn_front_forward(const ecgmm_crnn_front_desc* d, const float* spec, const void* const* params,
+                             void* const* buffers, float* seq_out, void* ws, size_t ws_bytes, void* stream);
+/* train_physionet2.py:55-65, 87-93 (their loss.backward()); no input gradient: the spectrogram is data */
+int ecgmm_crnn_front_backward(const ecgmm_crnn_front_desc* d, const float* spec, const float* dseq, const void* const* params,
+                              void* const* grads, void* ws_fwd, void* ws_bwd, size_t ws_bwd_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
