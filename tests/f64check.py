@@ -230,3 +230,448 @@ def check_bnred(rows, dx_stored, y, coef, mask=None, name="bnred"):
     sums, slack, mags = bnred_ref(dx_stored, y, coef, mask)
     check_colsums(rows[:, 0].sum(0), sums[0], slack[0], mags[0], name=name + " sum g")
     check_colsums(rows[:, 1].sum(0), sums[1], slack[1], mags[1], name=name + " sum g(y-mu)")
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# BatchNorm and pooling passes (csrc/elementwise.hip, csrc/bn_eval_bwd.hip), tensors channels-last: [M rows][C] for the
+# BatchNorm passes, [N][H][W][C] for the pooling passes.  Operands are taken as given (bf16-rounded where the kernel
+# reads bf16), a pass that consumes another pass's fp32 output (coef rows, partial rows, pooled / idx, dbeta / dgamma)
+# gets that output as its given input, and the float64 evaluation of the same formula is the exact answer.
+#
+#   stored tensors (out, dy, dz):  |got - ref| <= round_T(|ref| + g_K * A) + g_K * A
+#       A: the same expression on absolute values, g_K = K u / (1 - K u), u = 2^-24, K = the number of fp32 roundings on
+#       the longest operand-to-result path (an fma only removes one), round_T = half_ulp_bf16 (bf16) or u |.| (fp32)
+#   sums (partial rows, dgamma, dbeta, dbias):  colsum_ratio with sigma = g_K, K = the per-element roundings plus the
+#       longest chain of fp32 additions: ceil(M / (rows * rpi)) in the thread + rpi in the block fold (chain_len; rows as
+#       the library reports them, rpi = threads / (C / vec)) + 1 where a double sum is rounded to fp32 at the end
+#   coef: the sum bounds carried through mean = s1 / M, var = s2 / M - mean^2, invstd = 1 / sqrt(var + eps) (coef_ref)
+#
+# Every K below is the derived worst case, none is tightened; measured on the MI355X over tests/test_bn_pool_f64_gpu.py
+# the worst ratio to these bounds is recorded in that file's docstring.  All of them accept torch's own fp32 evaluation
+# of the same formulas on the CPU, stored as fp32 and as bf16 (tests/test_f64check.py: test_bn_pool_checkers_accept_torch_fp32
+# for the statistics, coef, K_ACT, K_DZ, K_DZXHAT, K_DY and the sums; test_eval_backward_checker_accepts_torch_fp32 for
+# K_EVAL_DY; test_pool_checkers_accept_torch for K_AFFINE and K_POOL_DZ; test_fused_stem_backward_checker_accepts_torch_fp32
+# for K_POOL_RED and K_POOL_DY).
+# ----------------------------------------------------------------------------------------------------------------------
+U = 2.0 ** -24
+# |y * scale + shift| decided within this many roundings of zero: the mask / the all-zero window may go either way
+K_AFFINE = 2                 # y * scale, + shift
+# out = relu((y * scale + shift) * gate + (res * rscale + rshift)): y * scale, + shift, * gate, [res * rscale, + rshift,] + -> 4
+# on the path from y, 3 from res; the stored rounding is round_T
+K_ACT = 4
+# dz = dout * gate + addc: 2
+K_DZ = 2
+# xhat = (y - mean) * invstd: 2;  dz * xhat: K_DZ + 2 + 1
+K_DZXHAT = K_DZ + 3
+# dy = k1 * ((dz - k2) - xhat * k3), k2 = (float)(s1 / M) against dbeta / M: 2, k1 = gamma * invstd: 1.
+#   from dz: 2 + sub + sub + mul = 5;  from xhat or k3: 2 + mul + sub + mul = 5;  from k2: 2 + sub + sub + mul = 5
+K_DY = 5
+# eval mode: dy = dz * scale: K_DZ + 1
+K_EVAL_DY = K_DZ + 1
+# fused stem backward: dy = k1 * z + (bn * y + an), z = up to 4 routed terms (3 adds), bn = -(k1 * k3) * invstd,
+# an = -(k1 * k2) - bn * mean.  Longest path, from k3 (2 roundings of its own): k1 * k3, * invstd, bn * mean, an's subtraction,
+# (bn * y) + an, + k1 * z = 2 + 6 = 8
+K_POOL_DY = 8
+# its reduction: g * (p - beta) * (1 / scale), beta = shift + mean * scale: 2, p - beta: 1, g *: 1, 1 / scale: 1, * rsc: 1 -> 6
+K_POOL_RED = 6
+# max-pool backward: up to four routed terms, three additions
+K_POOL_DZ = 3
+UNSURE_CAP = 1e-4
+
+
+def g_k(K):
+    """(1 + u)^K - 1 <= K u / (1 - K u)"""
+    return K * U / (1.0 - K * U)
+
+
+def round_T(v, bf16):
+    return half_ulp_bf16(v) if bf16 else U * v.abs().double()
+
+
+def chain_len(M, rows, C, vec, threads):
+    """longest chain of fp32 additions behind one column of `rows` partial rows: the thread's own rows, then the fold of
+    the block's rpi threads that share the channel chunk (vec = 8 bf16 / 4 fp32 channels per thread)"""
+    rpi = threads // (C // vec)
+    return -(-M // (rows * rpi)) + rpi
+
+
+def _ratio(err, bound):
+    err = torch.where(torch.isfinite(err), err, torch.full_like(err, float("inf")))
+    return torch.where(bound > 0, err / bound, torch.where(err > 0, torch.full_like(err, float("inf")), err))
+
+
+def stored_ratio(got, ref, acc_abs, K, bf16, name="out", skip=None):
+    """worst ratio of |got - ref| to the stored-tensor bound; skip: elements left out (unsure ReLU masks)"""
+    got, ref, acc_abs = got.double(), ref.double(), acc_abs.double()
+    err = (got - ref).abs()
+    acc = g_k(K) * acc_abs
+    ratio = _ratio(err, round_T(ref.abs() + acc, bf16) + acc)
+    seen = torch.where(acc_abs > 0, (err - round_T(ref, bf16)).clamp_min(0) / (U * acc_abs).clamp_min(1e-300), torch.zeros_like(err))
+    if skip is not None:
+        ratio, seen = ratio.masked_fill(skip, 0.0), seen.masked_fill(skip, 0.0)
+    flat = int(torch.argmax(ratio))
+    seen = seen[torch.isfinite(seen)]
+    return Report(name, float(ratio.reshape(-1)[flat]), _unravel(flat, ref.shape), float(seen.max()) if seen.numel() else 0.0)
+
+
+def check_stored(got, ref, acc_abs, K, bf16, name="out", skip=None):
+    """(the accumulation term printed is the error beyond the stored rounding in units of u * A: the measured K)"""
+    r = stored_ratio(got, ref, acc_abs, K, bf16, name, skip)
+    print(r)
+    assert r.ok, str(r)
+    return r
+
+
+def check_sum(got, want, mag, K, name, slack=None):
+    return check_colsums(got, want, torch.zeros_like(mag) if slack is None else slack, mag, sigma=g_k(K), name=name)
+
+
+def check_unsure(unsure, name):
+    share = float(unsure.double().mean())
+    assert share <= UNSURE_CAP, "%s: %.3g of the elements have a ReLU mask decided inside fp32 rounding" % (name, share)
+    return share
+
+
+def per_row(v, rows_per_sample, M):
+    """[N][C] per-sample values -> [M][C]"""
+    return v.double().repeat_interleave(rows_per_sample, 0)[:M]
+
+
+def colstats_ref(y):
+    """(sum y, sum y^2) over the rows of y [M][C] and the sums of magnitudes"""
+    y = y.double()
+    return (y.sum(0), (y * y).sum(0)), (y.abs().sum(0), (y * y).sum(0))
+
+
+def check_colstats(rows, y, K, name="col_stats"):
+    """rows [n][2][C] as the kernel wrote them; K = chain_len(...); y * y is one more rounding"""
+    (s1, s2), (m1, m2) = colstats_ref(y)
+    rows = rows.double()
+    a = check_sum(rows[:, 0].sum(0), s1, m1, K, name + " sum y")
+    b = check_sum(rows[:, 1].sum(0), s2, m2, K + 1, name + " sum y^2")
+    return max(a.ratio, b.ratio)
+
+
+def f32(v):
+    """a Python float as the fp32 value the kernel receives"""
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+@dataclass
+class CoefRef:
+    val: dict                # scale, shift, mean, invstd, rm, rv: float64 [C]
+    bound: dict              # the allowed |error| of each
+
+
+def coef_ref(s1, s2, M, gamma, beta, eps, rm0=None, rv0=None, momentum=0.1, ds1=None, ds2=None):
+    """BatchNorm finalize in float64 from the column sums s1, s2 [C] known to within ds1, ds2 (None: exact), with the
+    allowed error of every output.  The kernel sums the rows and forms mean / var / invstd in double (relative 2^-50
+    covers it) and rounds to fp32 where it stores:
+      mean   : ds1 / M, + 1 rounding
+      var    : dvar = ds2 / M + (2 |mean| + ds1 / M) ds1 / M       <- the term that grows with mean^2 / var
+      invstd : relative 1 / sqrt(1 - dvar / (var + eps)) - 1  (= 0.5 dvar / (var + eps) to first order), + 1 rounding
+      scale  = gamma * invstd: + 1;   shift = beta - mean * scale: mean (1), scale (2), product, difference
+      running_mean = (1 - m) * rm0 + m * mean: 3 roundings on either path;  running_var likewise from the unbiased
+      variance var * M / (M - 1) (var itself for M == 1)."""
+    s1, s2, g, b = s1.double(), s2.double(), gamma.double(), beta.double()
+    z = torch.zeros_like(s1)
+    ds1 = z if ds1 is None else ds1.double()
+    ds2 = z if ds2 is None else ds2.double()
+    tiny = 2.0 ** -50
+    eps, mom = f32(eps), f32(momentum)
+    mean = s1 / M
+    dm = ds1 / M + tiny * mean.abs()
+    ex2 = s2 / M
+    var = (ex2 - mean * mean).clamp_min(0)
+    dvar = ds2 / M + (2 * mean.abs() + dm) * dm + tiny * (ex2.abs() + mean * mean)
+    w = var + eps
+    invstd = 1.0 / w.sqrt()
+    t = dvar / w
+    rel = torch.where(t < 1, 1.0 / (1 - t).clamp_min(1e-300).sqrt() - 1, torch.full_like(t, float("inf")))
+    d_inv = invstd * (rel + g_k(1) * (1 + rel))
+    scale = g * invstd
+    d_scale = g.abs() * invstd * (rel + g_k(2) * (1 + rel))
+    d_mean = dm + U * (mean.abs() + dm)
+    shift = b - mean * scale
+    prod, d_prod = (mean * scale).abs(), mean.abs() * d_scale + scale.abs() * d_mean + d_mean * d_scale
+    d_shift = d_prod + g_k(2) * (b.abs() + prod + d_prod)
+    val = dict(scale=scale, shift=shift, mean=mean, invstd=invstd)
+    bound = dict(scale=d_scale, shift=d_shift, mean=d_mean, invstd=d_inv)
+    if rm0 is not None:
+        unb = var * M / (M - 1) if M > 1 else var
+        d_unb = dvar * M / (M - 1) if M > 1 else dvar
+        val["rm"] = (1 - mom) * rm0.double() + mom * mean
+        bound["rm"] = mom * dm + g_k(3) * ((1 - mom) * rm0.double().abs() + mom * (mean.abs() + dm))
+        val["rv"] = (1 - mom) * rv0.double() + mom * unb
+        bound["rv"] = mom * d_unb + g_k(3) * ((1 - mom) * rv0.double().abs() + mom * (unb + d_unb))
+    return CoefRef(val, bound)
+
+
+def coef_ratio(coef, ref, rm=None, rv=None, name="coef"):
+    """coef [4][C] (scale, shift, mean, invstd) as stored -> worst |err| / bound and the quantity / channel it is at"""
+    got = dict(scale=coef[0], shift=coef[1], mean=coef[2], invstd=coef[3])
+    if rm is not None:
+        got["rm"], got["rv"] = rm, rv
+    worst = Report(name, 0.0, ("", 0))
+    for k, v in got.items():
+        ratio = _ratio((v.double() - ref.val[k]).abs(), ref.bound[k])
+        c = int(torch.argmax(ratio))
+        if float(ratio[c]) >= worst.ratio:
+            worst = Report(name, float(ratio[c]), (k, c))
+    return worst
+
+
+def check_coef(coef, ref, rm=None, rv=None, name="coef"):
+    r = coef_ratio(coef, ref, rm, rv, name)
+    print(r)
+    assert r.ok, str(r)
+    return r
+
+
+def bn_act_ref(y, scale, shift, res=None, rscale=None, rshift=None, gate=None, relu=False):
+    """out = relu?((y * scale + shift) * gate + res * rscale + rshift) and the same on absolute values; y, res, gate [M][C]
+    (gate already per row), the coefficients [C]"""
+    y = y.double()
+    ref = y * scale.double() + shift.double()
+    A = y.abs() * scale.double().abs() + shift.double().abs()
+    if gate is not None:
+        ref, A = ref * gate.double(), A * gate.double().abs()
+    if res is not None:
+        r = res.double()
+        rs = torch.ones_like(scale.double()) if rscale is None else rscale.double()
+        rb = torch.zeros_like(rs) if rshift is None else rshift.double()
+        ref, A = ref + r * rs + rb, A + r.abs() * rs.abs() + rb.abs()
+    return (ref.clamp_min(0) if relu else ref), A
+
+
+def affine_mask(y, scale, shift):
+    """the recomputed ReLU mask bn(y) > 0 and the elements whose sign fp32 may decide either way"""
+    y = y.double()
+    z = y * scale.double() + shift.double()
+    A = y.abs() * scale.double().abs() + shift.double().abs()
+    return z > 0, z.abs() <= g_k(K_AFFINE) * A
+
+
+def bn_dz_ref(dout, mask=None, gate=None, addc=None):
+    """dz = [mask] * dout * gate + addc and the same on absolute values (gate, addc [M][C], per row); the masked dout on
+    its own is what dz_out stores, exactly"""
+    d = dout.double()
+    if mask is not None:
+        d = torch.where(mask, d, torch.zeros_like(d))
+    masked = d
+    A = d.abs()
+    if gate is not None:
+        d, A = d * gate.double(), A * gate.double().abs()
+    if addc is not None:
+        d, A = d + addc.double(), A + addc.double().abs()
+    return d, A, masked
+
+
+def xhat_ref(y, coef):
+    return (y.double() - coef[2].double()) * coef[3].double()
+
+
+def bn_bwd_sums_ref(dz, A, xhat, unsure=None, dswing=None):
+    """(sum dz, sum dz * xhat), the slack of the unsure elements (dswing: what flipping their mask changes dz by) and the
+    sums of magnitudes"""
+    sums = (dz.sum(0), (dz * xhat).sum(0))
+    mags = (A.sum(0), (A * xhat.abs()).sum(0))
+    if unsure is None:
+        z = torch.zeros_like(sums[0])
+        return sums, (z, z), mags
+    sw = dswing.abs() * unsure.double()
+    return sums, (sw.sum(0), (sw * xhat.abs()).sum(0)), mags
+
+
+def bn_dy_ref(dz, A, xhat, k1, k2, k3):
+    """dy = k1 * (dz - k2 - xhat * k3) and the same on absolute values"""
+    k1, k2, k3 = k1.double(), k2.double(), k3.double()
+    return k1 * (dz - k2 - xhat * k3), k1.abs() * (A + k2.abs() + xhat.abs() * k3.abs())
+
+
+def bn_eval_dy_ref(dz, A, scale):
+    return dz * scale.double(), A * scale.double().abs()
+
+
+# ---- 3x3 / stride 2 / pad 1 max-pool fused with BatchNorm + ReLU ----
+def pool_taps(a, fill):
+    """a [N][H][W][C] float64 -> [N][OH][OW][9][C]: the nine taps (kh * 3 + kw) of every window, `fill` outside the image"""
+    N, H, W, C = a.shape
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    p = torch.full((N, 2 * OH + 1, 2 * OW + 1, C), float(fill), dtype=a.dtype, device=a.device)
+    p[:, 1:H + 1, 1:W + 1] = a
+    return torch.stack([p[:, kh:kh + 2 * OH:2, kw:kw + 2 * OW:2] for kh in range(3) for kw in range(3)], dim=3)
+
+
+def pool_fwd_ratio(pooled, idx, y, scale, shift, bf16, name="maxpool"):
+    """pooled, idx [N][OH][OW][C] as the kernel stored them against a64 = relu(y * scale + shift) in float64:
+    pooled within the stored bound (K_AFFINE) of the window maximum; idx an in-image tap whose a64 is within that bound of
+    the maximum; where idx names a tap that ties the maximum exactly, it is the earliest such tap (windows holding an
+    element whose sign fp32 may decide either way are left out of this last rule)."""
+    y = y.double()
+    z = y * scale.double() + shift.double()
+    A = y.abs() * scale.double().abs() + shift.double().abs()
+    unsure = z.abs() <= g_k(K_AFFINE) * A
+    check_unsure(unsure, name)
+    T, TA = pool_taps(z.clamp_min(0), float("-inf")), pool_taps(A, 0.0)
+    TU = pool_taps(unsure.double(), 0.0).amax(3) > 0
+    mx, acc = T.amax(3), g_k(K_AFFINE) * TA.amax(3)
+    bound = round_T(mx + acc, bf16) + acc
+    r_val = _ratio((pooled.double() - mx).abs(), bound)
+    ix = idx.long()
+    sel = T.gather(3, ix.clamp(0, 8).unsqueeze(3)).squeeze(3)
+    in_range = (ix < 9) & torch.isfinite(sel)
+    r_tap = torch.where(in_range, _ratio(mx - torch.where(in_range, sel, mx), bound), torch.full_like(mx, float("inf")))
+    first = (T == mx.unsqueeze(3)).double().argmax(3)
+    late = in_range & (sel == mx) & (ix != first) & ~TU
+    ratio = torch.where(late, torch.full_like(mx, float("inf")), torch.maximum(r_val, r_tap))
+    ratio = torch.where(torch.isnan(ratio), torch.full_like(ratio, float("inf")), ratio)
+    flat = int(torch.argmax(ratio))
+    r = Report(name, float(ratio.reshape(-1)[flat]), _unravel(flat, mx.shape))
+    r.parts = dict(value=float(r_val.max()), tap=float(r_tap.max()), late_ties=int(late.sum()))
+    r.ties = int(((T == mx.unsqueeze(3)).sum(3) > 1).sum())
+    return r
+
+
+def check_pool_fwd(pooled, idx, y, scale, shift, bf16, name="maxpool"):
+    r = pool_fwd_ratio(pooled, idx, y, scale, shift, bf16, name)
+    print(r, r.parts, "windows with exact ties: %d" % r.ties)
+    assert r.ok, str(r) + " " + str(r.parts)
+    return r
+
+
+def pool_bwd_ref(dp, pooled, idx, H, W):
+    """float64 scatter of dp into the taps idx names, for windows with pooled > 0: dz [N][H][W][C] and sum |terms|"""
+    N, OH, OW, C = dp.shape
+    dev_ = dp.device
+    ix = idx.long()
+    n = torch.arange(N, device=dev_).view(N, 1, 1, 1)
+    h = 2 * torch.arange(OH, device=dev_).view(1, OH, 1, 1) - 1 + ix // 3
+    w = 2 * torch.arange(OW, device=dev_).view(1, 1, OW, 1) - 1 + ix % 3
+    c = torch.arange(C, device=dev_).view(1, 1, 1, C)
+    ok = (pooled.double() > 0) & (ix < 9) & (h >= 0) & (h < H) & (w >= 0) & (w < W)
+    flat = (((n * H + h) * W + w) * C + c)[ok]
+    v = dp.double()[ok]
+    dz = torch.zeros(N * H * W * C, dtype=torch.float64, device=dev_).index_add_(0, flat, v)
+    mag = torch.zeros_like(dz).index_add_(0, flat, v.abs())
+    return dz.view(N, H, W, C), mag.view(N, H, W, C)
+
+
+def pool_bwd_ratio(dz, dp, pooled, idx, bf16, name="maxpool bwd"):
+    """|dz - ref| <= half an ulp of the stored type + K_POOL_DZ u sum |terms|"""
+    ref, mag = pool_bwd_ref(dp, pooled, idx, dz.shape[1], dz.shape[2])
+    ratio = _ratio((dz.double() - ref).abs(), round_T(ref, bf16) + K_POOL_DZ * U * mag)
+    flat = int(torch.argmax(ratio))
+    return Report(name, float(ratio.reshape(-1)[flat]), _unravel(flat, ref.shape))
+
+
+def check_pool_bwd(dz, dp, pooled, idx, bf16, name="maxpool bwd"):
+    r = pool_bwd_ratio(dz, dp, pooled, idx, bf16, name)
+    print(r)
+    assert r.ok, str(r)
+    return r
+
+
+def pool_red_ref(dp, pooled, coef):
+    """the fused stem backward's reduction over windows: g = dp * [pooled > 0];  sum g  and
+    invstd * sum g * (pooled - beta) / scale with beta = shift + mean * scale (0 where scale == 0), and their magnitudes"""
+    sc, sh, mu, inv = (coef[i].double() for i in range(4))
+    p = pooled.double()
+    g = torch.where(p > 0, dp.double(), torch.zeros_like(p))
+    rsc = torch.where(sc != 0, 1.0 / sc, torch.zeros_like(sc))
+    dims = (0, 1, 2)
+    s1, s2 = g.sum(dims), (g * (p - (sh + mu * sc)) * rsc).sum(dims) * inv
+    m2 = (g.abs() * (p.abs() + sh.abs() + (mu * sc).abs()) * rsc.abs()).sum(dims) * inv.abs()
+    return (s1, s2), (g.abs().sum(dims), m2)
+
+
+def pool_dy_ref(dz, mag, y, coef, k1, k2, k3):
+    """dy of the fused stem backward as the kernel forms it: k1 * dz + (bn * y + an), an = -(k1 * k2) - bn * mean,
+    bn = -(k1 * k3) * invstd; the reference is the float64 value, A follows the kernel's own (uncentred) expression"""
+    mu, inv = coef[2].double(), coef[3].double()
+    k1, k2, k3 = k1.double(), k2.double(), k3.double()
+    yv = y.double()
+    bn = -(k1 * k3) * inv
+    ref = k1 * dz + bn * yv - k1 * k2 - bn * mu
+    A = k1.abs() * mag + bn.abs() * yv.abs() + (k1 * k2).abs() + (bn * mu).abs()
+    return ref, A
+
+
+def check_bn_bwd(dout, y, coef, gamma, bf16, K_sum, dgamma, dbeta, dy=None, dz_out=None, dbias=None, K_bias=None,
+                 maskref=None, gate=None, addc=None, name="bn_bwd"):
+    """Every output of one BatchNorm-backward call against float64.  dout, y [M][C] as given; coef [4][C] the forward's
+    stored fp32 coefficients; maskref: None, the string "y" (mask = bn(y) > 0, recomputed) or a tensor (mask = maskref > 0);
+    gate, addc [M][C] per row.  K_sum = chain_len(...) of the reduction rows, K_bias that of the dy rows.
+    dgamma / dbeta: K_DZXHAT / K_DZ per element + K_sum + 1 (the double sum of the rows stored as fp32).
+    dy: given the kernel's own k2 = dbeta / M, k3 = dgamma / M (K_DY).  dz_out: the masked dout, exactly.
+    dbias: the float64 sum of the dy values stored (K_bias + 1).  Returns {output: worst ratio}."""
+    M = y.shape[0]
+    unsure, mask = None, None
+    if isinstance(maskref, str):
+        mask, unsure = affine_mask(y, coef[0], coef[1])
+        check_unsure(unsure, name)
+    elif maskref is not None:
+        mask = maskref.double() > 0
+    dz, A, masked = bn_dz_ref(dout, mask, gate, addc)
+    xh = xhat_ref(y, coef)
+    swing = None if unsure is None else (dout.double() * (1 if gate is None else gate.double()))
+    sums, slack, mags = bn_bwd_sums_ref(dz, A, xh, unsure, swing)
+    out = {}
+    if dbeta is not None:
+        out["dbeta"] = check_sum(dbeta, sums[0], mags[0], K_DZ + K_sum + 1, name + " dbeta", slack[0]).ratio
+        out["dgamma"] = check_sum(dgamma, sums[1], mags[1], K_DZXHAT + K_sum + 1, name + " dgamma", slack[1]).ratio
+    if dz_out is not None:
+        bad = (dz_out.double() != masked)
+        if unsure is not None:
+            bad &= ~unsure
+        assert not bool(bad.any()), "%s dz_out: %d elements are not the masked gradient" % (name, int(bad.sum()))
+        out["dz_out"] = 0.0
+    if dy is not None:
+        k1 = gamma.double() * coef[3].double()
+        ref, Ady = bn_dy_ref(dz, A, xh, k1, dbeta.double() / M, dgamma.double() / M)
+        out["dy"] = check_stored(dy, ref, Ady, K_DY, bf16, name + " dy", skip=unsure).ratio
+    if dbias is not None:
+        s = dy.double()
+        out["dbias"] = check_sum(dbias, s.sum(0), s.abs().sum(0), K_bias + 1, name + " dbias").ratio
+    return out
+
+
+# ---- input families of tests/test_bn_pool_f64_gpu.py (hash-filled; tests/test_f64check.py verifies on the CPU that the
+#      float64 reference alone keeps the unsure-mask share of each under UNSURE_CAP) ----
+def _b(t, bf16):
+    """tests/util.bf16_round, behind a switch (util imports the HIP library's ctypes layer; nothing in this file may, so
+    that the checker and its CPU tests load without the built library)"""
+    return t.to(torch.bfloat16).float() if bf16 else t
+
+
+def bn_inputs(M, C, bf16, rows_per_sample=None, mean_ratios=None):
+    """y, res, dout [M][C], gamma, beta, rscale, rshift [C], gate, addc [N][C] (N samples of rows_per_sample rows).
+    mean_ratios: channel c gets mean = mean_ratios[c % len] * std (sign alternating) instead of 0.5"""
+    from oracle import fill
+    h = fill.hash_tensor
+    y = h((M, C), 31, 2.0)
+    if mean_ratios is None:
+        y = y + 0.5
+    else:
+        c = torch.arange(C)
+        r = torch.tensor(mean_ratios, dtype=torch.float32)[c % len(mean_ratios)]
+        y = y + (r * (2.0 / 3 ** 0.5) * (1 - 2 * ((c // len(mean_ratios)) % 2).float()))[None]
+    rps = rows_per_sample or M
+    N = -(-M // rps)
+    d = dict(y=_b(y, bf16), res=_b(h((M, C), 32), bf16), dout=_b(h((M, C), 37), bf16), gamma=1 + 0.2 * h((C,), 35),
+             beta=0.1 * h((C,), 36), rscale=1 + 0.3 * h((C,), 38), rshift=0.2 * h((C,), 39), gate=0.5 + 0.4 * h((N, C), 33),
+             addc=0.01 * h((N, C), 34), rps=rps, N=N)
+    return d
+
+
+def pool_inputs(N, C, H, W, bf16):
+    """y [N][H][W][C], scale, shift [C] (shift negative enough that about a quarter of the full 3x3 windows are all zero
+    after the ReLU), dp [N][OH][OW][C]; mean, invstd [C] complete a forward coef [4][C] for the fused stem backward, with
+    gamma = scale / invstd"""
+    from oracle import fill
+    h = fill.hash_tensor
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    sc = 1 + 0.3 * h((C,), 42)
+    inv = 0.8 + 0.2 * h((C,), 46)
+    return dict(y=_b(h((N, H, W, C), 41, 2.0), bf16), scale=sc, shift=-1.4 * sc + 0.1 * h((C,), 43),
+                dp=_b(h((N, OH, OW, C), 44), bf16), mean=0.1 * h((C,), 45), invstd=inv, gamma=sc / inv)

@@ -185,3 +185,343 @@ def test_statistics_and_reduction_sums():
     rows[0, 1, 7] += 0.01 * float(s2.abs().max())
     with pytest.raises(AssertionError):
         F64.check_bnred(rows, d, yb, coef)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# BatchNorm and pooling checkers: the "kernel output" is torch's own fp32 (or bf16-stored) evaluation of the same formulas.
+# It passes every bound; each defect below fails.
+# ----------------------------------------------------------------------------------------------------------------------
+def _bn_emulate(d, bf16, rows, rps=None, mask="y", eps=1e-5):
+    """the passes in torch fp32: statistics rows (the M pixel rows split into `rows` chunks), finalize (rows summed in double
+    as the kernels do), apply, backward.  Returns a dict of what the kernels would store."""
+    y, dout = d["y"], d["dout"]
+    M, C = y.shape
+    o = dict(M=M, C=C)
+    o["rows"] = torch.stack([torch.stack([c.sum(0), (c * c).sum(0)]) for c in y.chunk(rows)])              # [rows][2][C] fp32
+    s1, s2 = o["rows"][:, 0].double().sum(0), o["rows"][:, 1].double().sum(0)
+    mean, var = s1 / M, (s2 / M - (s1 / M) ** 2).clamp_min(0)
+    inv = (1.0 / (var + F64.f32(eps)).sqrt()).float()
+    sc = d["gamma"] * inv
+    o["coef"] = torch.stack([sc, d["beta"] - mean.float() * sc, mean.float(), inv])
+    unb = var * M / (M - 1) if M > 1 else var
+    o["rm"] = (1 - 0.1) * torch.zeros(C) + torch.tensor(0.1) * mean.float()
+    o["rv"] = (1 - 0.1) * torch.ones(C) + torch.tensor(0.1) * unb.float()
+    gate = F64.per_row(d["gate"], rps, M).float() if rps else None
+    addc = F64.per_row(d["addc"], rps, M).float() if rps else None
+    o["gate"], o["addc"] = gate, addc
+    z = y * o["coef"][0] + o["coef"][1]
+    out = (z * gate if rps else z) + (d["res"] * d["rscale"] + d["rshift"])
+    o["out"] = F64._b(out.clamp_min(0), bf16)
+    m = (z > 0) if mask == "y" else (mask > 0)
+    o["masked"] = torch.where(m, dout, torch.zeros_like(dout))
+    dz = o["masked"] * gate + addc if rps else o["masked"]
+    xh = (y - o["coef"][2]) * o["coef"][3]
+    o["dbeta"], o["dgamma"] = dz.sum(0), (dz * xh).sum(0)
+    k1, k2, k3 = d["gamma"] * o["coef"][3], o["dbeta"] / M, o["dgamma"] / M
+    o["dz"], o["xh"], o["k"] = dz, xh, (k1, k2, k3)
+    o["dy_unrounded"] = k1 * (dz - k2 - xh * k3)
+    o["dy"] = F64._b(o["dy_unrounded"], bf16)
+    o["dbias"] = o["dy"].sum(0)
+    return o
+
+
+def _bwd_ratios(d, o, bf16, rps, **over):
+    g = dict(dgamma=o["dgamma"], dbeta=o["dbeta"], dy=o["dy"], dz_out=o["masked"], dbias=o["dbias"])
+    g.update(over)
+    K = F64.chain_len(o["M"], 1, o["C"], 8 if bf16 else 4, 1024)
+    return F64.check_bn_bwd(d["dout"], d["y"], o["coef"], d["gamma"], bf16, K, g["dgamma"], g["dbeta"], g["dy"], g["dz_out"],
+                            g["dbias"], K, maskref="y", gate=o["gate"] if rps else None, addc=o["addc"] if rps else None)
+
+
+BN_CPU = [(777, 16, False, None, 2), (626, 64, True, 313, 5), (626, 64, False, 313, 5), (1, 64, False, None, 1)]
+
+
+@pytest.mark.parametrize("M,C,bf16,rps,rows", BN_CPU)
+def test_bn_pool_checkers_accept_torch_fp32(M, C, bf16, rps, rows):
+    d = F64.bn_inputs(M, C, bf16, rps)
+    o = _bn_emulate(d, bf16, rows, rps)
+    vec = 8 if bf16 else 4
+    F64.check_colstats(o["rows"], d["y"], F64.chain_len(M, rows, C, vec, 256))
+    s1, s2 = o["rows"][:, 0].double().sum(0), o["rows"][:, 1].double().sum(0)
+    ref = F64.coef_ref(s1, s2, M, d["gamma"], d["beta"], 1e-5, torch.zeros(C), torch.ones(C), 0.1)
+    F64.check_coef(o["coef"], ref, o["rm"], o["rv"])
+    want, A = F64.bn_act_ref(d["y"], o["coef"][0], o["coef"][1], d["res"], d["rscale"], d["rshift"], o["gate"] if rps else None, True)
+    F64.check_stored(o["out"], want, A, F64.K_ACT, bf16, "bn_act")
+    _bwd_ratios(d, o, bf16, rps)
+    if M > 1 and not bf16:
+        # F.batch_norm itself (its own summation order), against the bound carried from the statistics' sum bounds
+        (t1, t2), (m1, m2) = F64.colstats_ref(d["y"])
+        K = F64.chain_len(M, rows, C, vec, 256)
+        ref = F64.coef_ref(t1, t2, M, d["gamma"], d["beta"], 1e-5, torch.zeros(C), torch.ones(C), 0.1,
+                           F64.g_k(K) * m1, F64.g_k(K + 1) * m2)
+        rm, rv = torch.zeros(C), torch.ones(C)
+        x4 = d["y"].t().reshape(1, C, M, 1)
+        bn = F.batch_norm(x4, rm, rv, d["gamma"], d["beta"], True, 0.1, 1e-5)
+        inv = 1.0 / (x4.var(dim=(0, 2, 3), unbiased=False) + 1e-5).sqrt()
+        sc = d["gamma"] * inv
+        F64.check_coef(torch.stack([sc, d["beta"] - rm / 0.1 * sc, rm / 0.1, inv]), ref, rm, rv, name="F.batch_norm coef")
+
+
+def test_unsure_share_of_every_input_family_is_under_the_cap():
+    """the float64 reference alone: |bn(y)| inside K_AFFINE roundings of zero for at most UNSURE_CAP of the elements.
+    (Every family a ReLU mask is recomputed on.  The large-mean sweep, ratios 1 .. 32768, is measured through col_stats and
+    bn_finalize only: no mask is taken there, and at |mean| / std in the thousands y * scale + shift cancels so far that
+    5e-4 of its elements would be unsure.)"""
+    def share(y, sc, sh):
+        return F64.check_unsure(F64.affine_mask(y, sc, sh)[1], "inputs")
+    for M, C, bf16, ratios in [(1, 64, 0, None), (1, 64, 1, None), (7, 4, 0, None), (7, 8, 1, None), (777, 16, 0, None), (777, 16, 1, None), (626, 64, 0, None),
+                               (626, 64, 1, None), (4099, 128, 0, None), (4099, 128, 1, None), (300, 1024, 1, None),
+                               (20000, 512, 0, None), (40000, 512, 1, None), (4099, 64, 0, (0, 4, 32, 256))]:
+        d = F64.bn_inputs(M, C, bool(bf16), None, ratios)
+        (s1, s2), _ = F64.colstats_ref(d["y"])
+        v = F64.coef_ref(s1, s2, M, d["gamma"], d["beta"], 1e-5).val
+        print((M, C, bf16), share(d["y"], v["scale"].float(), v["shift"].float()))
+    for shape in [(2, 64, 1, 1), (1, 64, 2, 2), (3, 64, 1, 41), (2, 64, 7, 1), (2, 64, 9, 7), (1, 128, 12, 10), (2, 64, 364, 364)]:
+        for bf16 in ((False, True) if shape[2] < 300 else (False,)):
+            p = F64.pool_inputs(shape[0], shape[1], shape[2], shape[3], bf16)
+            print(shape, bf16, share(p["y"].reshape(-1, shape[1]), p["scale"], p["shift"]))
+
+
+def _fails(fn):
+    try:
+        fn()
+    except AssertionError:
+        return True
+    return False
+
+
+def test_rejects_each_batchnorm_forward_defect():
+    M, C, rows, rps = 626, 64, 5, 313
+    d = F64.bn_inputs(M, C, False, rps)
+    o = _bn_emulate(d, False, rows, rps)
+    K = F64.chain_len(M, rows, C, 4, 256)
+    y = d["y"]
+    # 1. one pixel row missing from the statistics
+    short = torch.stack([torch.stack([c.sum(0), (c * c).sum(0)]) for c in y[:-1].chunk(rows)])
+    assert _fails(lambda: F64.check_colstats(short, y, K))
+    # 2. one partial row counted twice
+    assert _fails(lambda: F64.check_colstats(torch.cat([o["rows"], o["rows"][1:2]]), y, K))
+    s1, s2 = o["rows"][:, 0].double().sum(0), o["rows"][:, 1].double().sum(0)
+    ref = F64.coef_ref(s1, s2, M, d["gamma"], d["beta"], 1e-5, torch.zeros(C), torch.ones(C), 0.1)
+    assert F64.coef_ratio(o["coef"], ref, o["rm"], o["rv"]).ok
+    # 3. eps left out of invstd
+    var = (s2 / M - (s1 / M) ** 2)
+    c = o["coef"].clone()
+    c[3] = (1.0 / var.sqrt()).float()
+    r = F64.coef_ratio(c, ref)
+    assert not r.ok and r.where[0] == "invstd", r
+    # 4. biased variance written to running_var
+    r = F64.coef_ratio(o["coef"], ref, o["rm"], 0.9 * torch.ones(C) + 0.1 * var.float())
+    assert not r.ok and r.where[0] == "rv", r
+    # 5. mean off by one bf16 ulp
+    c = o["coef"].clone()
+    c[2] += (2 * F64.half_ulp_bf16(c[2])).float()
+    r = F64.coef_ratio(c, ref)
+    assert not r.ok and r.where[0] == "mean", r
+    # 6. the neighbouring sample's gate on the last row of a sample (a row -> sample division off by one), rows_per_sample = 313
+    for bf16 in (False, True):
+        db = F64.bn_inputs(M, C, bf16, rps)
+        ob = _bn_emulate(db, bf16, rows, rps)
+        want, A = F64.bn_act_ref(db["y"], ob["coef"][0], ob["coef"][1], db["res"], db["rscale"], db["rshift"], ob["gate"], True)
+        assert F64.stored_ratio(ob["out"], want, A, F64.K_ACT, bf16).ok
+        z = db["y"][312] * ob["coef"][0] + ob["coef"][1]
+        bad = ob["out"].clone()
+        bad[312] = F64._b((z * db["gate"][1] + (db["res"][312] * db["rscale"] + db["rshift"])).clamp_min(0), bf16)
+        r = F64.stored_ratio(bad, want, A, F64.K_ACT, bf16)
+        assert not r.ok and r.where[0] == 312, r
+
+
+@pytest.mark.parametrize("bf16", [False, True])
+def test_rejects_each_batchnorm_backward_defect(bf16):
+    M, C, rows, rps = 626, 64, 5, 313
+    d = F64.bn_inputs(M, C, bf16, rps)
+    o = _bn_emulate(d, bf16, rows, rps)
+    assert max(_bwd_ratios(d, o, bf16, rps).values()) <= 1.0
+    k1, k2, k3 = o["k"]
+    # 6. (backward) the neighbouring sample's gate and additive term on the last row of sample 0
+    dz = o["dz"].clone()
+    dz[312] = o["masked"][312] * d["gate"][1] + d["addc"][1]
+    assert _fails(lambda: _bwd_ratios(d, o, bf16, rps, dy=F64._b(k1 * (dz - k2 - o["xh"] * k3), bf16)))
+    # 7. one ReLU mask bit flipped on an element that is clearly non-zero
+    z = d["y"] * o["coef"][0] + o["coef"][1]
+    i = int(torch.argmax((z.abs() * d["dout"].abs()).reshape(-1)))
+    r_, c_ = i // C, i % C
+    flip = o["masked"].clone()
+    flip[r_, c_] = d["dout"][r_, c_] - flip[r_, c_]
+    dzf = flip * o["gate"] + o["addc"]
+    assert _fails(lambda: _bwd_ratios(d, o, bf16, rps, dz_out=flip))
+    assert _fails(lambda: _bwd_ratios(d, o, bf16, rps, dy=F64._b(k1 * (dzf - k2 - o["xh"] * k3), bf16), dz_out=None))
+    assert _fails(lambda: _bwd_ratios(d, o, bf16, rps, dbeta=dzf.sum(0), dgamma=(dzf * o["xh"]).sum(0), dy=None, dz_out=None, dbias=None))
+    # 8. k3 applied without xhat
+    assert _fails(lambda: _bwd_ratios(d, o, bf16, rps, dy=F64._b(k1 * (o["dz"] - k2 - k3), bf16), dbias=None))
+    if bf16:
+        # 9. dy wrong by 4 ulp (an element of median magnitude).  Of the stored bf16 type only: 4 fp32 ulps are 8 u |ref|, and
+        # the derived fp32 bound, u |ref| + 2 g_5 A with A >= |ref|, is 11 u |ref| at the least -- the per-element bound cannot
+        # resolve a few fp32 ulps, and no constant is tightened to make it (the fp32 dy is pinned by mutations 6 - 8 instead)
+        flat = o["dy"].reshape(-1)
+        k = int(torch.argsort(flat.abs())[flat.numel() // 2])
+        b16 = flat.to(torch.bfloat16).clone()
+        b16.view(torch.int16)[k] += 4
+        assert _fails(lambda: _bwd_ratios(d, o, bf16, rps, dy=b16.float().view(M, C), dbias=None))
+        # 10. dbias summed from the unrounded dy instead of the stored dy
+        assert _fails(lambda: _bwd_ratios(d, o, bf16, rps, dbias=o["dy_unrounded"].sum(0)))
+
+
+def _pool_emulate(p, bf16):
+    """torch's own pooling of the stored-precision activations: pooled, idx (earliest tap on ties), dz"""
+    a = F64._b((p["y"] * p["scale"] + p["shift"]).clamp_min(0), bf16)
+    T = F64.pool_taps(a.double(), float("-inf"))
+    pooled = T.amax(3)
+    idx = (T == pooled.unsqueeze(3)).double().argmax(3).to(torch.uint8)
+    N, H, W, C = a.shape
+    dz, _ = F64.pool_bwd_ref(p["dp"], pooled, idx, H, W)
+    return pooled.float(), idx, F64._b(dz.float(), bf16)
+
+
+POOL_CPU = [(2, 64, 1, 1), (1, 64, 2, 2), (3, 64, 1, 41), (2, 64, 7, 1), (2, 64, 9, 7), (1, 128, 12, 10)]
+
+
+@pytest.mark.parametrize("bf16", [False, True])
+@pytest.mark.parametrize("shape", POOL_CPU)
+def test_pool_checkers_accept_torch(shape, bf16):
+    N, C, H, W = shape
+    p = F64.pool_inputs(N, C, H, W, bf16)
+    pooled, idx, dz = _pool_emulate(p, bf16)
+    r = F64.check_pool_fwd(pooled, idx, p["y"], p["scale"], p["shift"], bf16)
+    assert r.ties > 0 or H * W == 1                     # all-zero windows: exact ties (a 1x1 image has one tap)
+    F64.check_pool_bwd(dz, p["dp"], pooled, idx, bf16)
+
+
+@pytest.mark.parametrize("bf16", [False, True])
+def test_rejects_each_pooling_defect(bf16):
+    N, C, H, W = 2, 64, 9, 7
+    p = F64.pool_inputs(N, C, H, W, bf16)
+    pooled, idx, dz = _pool_emulate(p, bf16)
+    fwd = lambda pl, ix: F64.pool_fwd_ratio(pl, ix, p["y"], p["scale"], p["shift"], bf16)
+    assert fwd(pooled, idx).ok
+    # 11. arg-max on the later of two tied taps: an interior all-zero window (taps 0 and 1 tie at 0) naming tap 1
+    a = (p["y"].double() * p["scale"].double() + p["shift"].double()).clamp_min(0)
+    T = F64.pool_taps(a, float("-inf"))
+    zero = (T.amax(3) == 0) & torch.isfinite(T[:, :, :, 0]) & torch.isfinite(T[:, :, :, 1])
+    assert zero.any()
+    w = tuple(int(v) for v in zero.nonzero()[0])
+    bad = idx.clone()
+    bad[w] = 1
+    r = fwd(pooled, bad)
+    assert not r.ok and r.parts["late_ties"] == 1 and r.parts["value"] <= 1 and r.parts["tap"] <= 1, r.parts
+    # ... and on a border window whose first taps lie outside the image: the earliest is the first tap inside
+    assert int(idx[0, 0, 0].min()) >= 4
+    bad = idx.clone()
+    bad[0, 0, 0] = 0
+    assert not fwd(pooled, bad).ok
+    # 13. the last window row dropped (H = 9 is odd: window row 4 covers input rows 7, 8)
+    bad = pooled.clone()
+    bad[:, -1] = 0
+    r = fwd(bad, idx)
+    assert not r.ok and r.where[1] == pooled.shape[1] - 1, r
+    # 12. a window's gradient routed to the same tap of the neighbouring window
+    assert F64.pool_bwd_ratio(dz, p["dp"], pooled, idx, bf16).ok
+    live = (pooled[:, 1:-1, 1:-1] > 0).nonzero()[0]
+    n_, oh, ow, c_ = int(live[0]), int(live[1]) + 1, int(live[2]) + 1, int(live[3])
+    t = int(idx[n_, oh, ow, c_])
+    h, w_ = 2 * oh - 1 + t // 3, 2 * ow - 1 + t % 3
+    bad = dz.clone()
+    g = p["dp"][n_, oh, ow, c_]
+    bad[n_, h, w_, c_] -= g
+    bad[n_, h, w_ + 2, c_] += g
+    assert not F64.pool_bwd_ratio(F64._b(bad, bf16), p["dp"], pooled, idx, bf16).ok
+
+
+@pytest.mark.parametrize("bf16", [False, True])
+def test_eval_backward_checker_accepts_torch_fp32(bf16):
+    """ecgmm_bn_eval_bwd's formulas in torch fp32 (dy stored as fp32 / bf16), gated with rows_per_sample = 313, against
+    bn_eval_dy_ref / K_EVAL_DY and the sum bounds; the scale left out of dy, or the dy sum taken unrounded, is rejected"""
+    M, C, rows, rps = 626, 64, 5, 313
+    d = F64.bn_inputs(M, C, bf16, rps)
+    o = _bn_emulate(d, bf16, rows, rps)
+    coef = o["coef"]
+    dz32, xh32 = o["dz"], o["xh"]                                  # masked dout * gate + addc, (y - mean) * invstd: fp32
+    dy = F64._b(dz32 * coef[0], bf16)
+    K = F64.chain_len(M, rows, C, 8 if bf16 else 4, 256)
+    mask, unsure = F64.affine_mask(d["y"], coef[0], coef[1])
+    F64.check_unsure(unsure, "eval bwd")
+    dz, A, masked = F64.bn_dz_ref(d["dout"], mask, o["gate"], o["addc"])
+    assert not bool(((o["masked"].double() != masked) & ~unsure).any())
+    xh = F64.xhat_ref(d["y"], coef)
+    sums, slack, mags = F64.bn_bwd_sums_ref(dz, A, xh, unsure, d["dout"].double() * o["gate"].double())
+    F64.check_sum(dz32.sum(0), sums[0], mags[0], F64.K_DZ + K + 1, "eval dbeta", slack[0])
+    F64.check_sum((dz32 * xh32).sum(0), sums[1], mags[1], F64.K_DZXHAT + K + 1, "eval dgamma", slack[1])
+    want, Ady = F64.bn_eval_dy_ref(dz, A, coef[0])
+    F64.check_stored(dy, want, Ady, F64.K_EVAL_DY, bf16, "eval dy", skip=unsure)
+    F64.check_sum(dy.sum(0), dy.double().sum(0), dy.double().abs().sum(0), K + 1, "eval dbias")
+    assert not F64.stored_ratio(F64._b(dz32, bf16), want, Ady, F64.K_EVAL_DY, bf16, skip=unsure).ok            # dy without the scale
+    bad = dy.clone()
+    bad[312] = F64._b((o["masked"][312] * d["gate"][1] + d["addc"][1]) * coef[0], bf16)                      # the next sample's gate
+    r = F64.stored_ratio(bad, want, Ady, F64.K_EVAL_DY, bf16, skip=unsure)
+    assert not r.ok and r.where[0] == 312, r
+    if bf16:
+        assert _fails(lambda: F64.check_sum((dz32 * coef[0]).sum(0), dy.double().sum(0), dy.double().abs().sum(0), K + 1, "dbias"))
+
+
+def _stem_bwd_emulate(p, pooled, idx, bf16):
+    """ecgmm_pool_bn_bwd in torch fp32, in the kernels' own form: the reduction over windows of g = dp * [pooled > 0] and
+    g * (pooled - beta) with beta = shift + mean * scale, scaled by 1 / scale after the sum and by invstd in the finalize;
+    dy = k1 * z + (bn * y + an) with bn = -(k1 * k3) * invstd, an = -(k1 * k2) - bn * mean, z the fp32 sum of the routed terms"""
+    sc, sh, mu, inv = p["scale"], p["shift"], p["mean"], p["invstd"]
+    N, H, W, C = p["y"].shape
+    M = N * H * W
+    g = torch.where(pooled > 0, p["dp"], torch.zeros_like(p["dp"]))
+    beta = sh + mu * sc
+    rsc = torch.where(sc != 0, 1.0 / sc, torch.zeros_like(sc))
+    dbeta = g.sum((0, 1, 2))
+    dgamma = ((g * (pooled - beta)).sum((0, 1, 2)) * rsc * inv)
+    k1, k2, k3 = p["gamma"] * inv, dbeta / M, dgamma / M
+    bn = -(k1 * k3) * inv
+    an = -(k1 * k2) - bn * mu
+    z = F64.pool_bwd_ref(p["dp"], pooled, idx, H, W)[0].float()
+    unrounded = k1 * z + (bn * p["y"] + an)
+    dy = F64._b(unrounded, bf16)
+    return dict(dbeta=dbeta, dgamma=dgamma, dy=dy, dbias=dy.sum((0, 1, 2)), k=(k1, bn, an), z=z, M=M, unrounded=unrounded)
+
+
+@pytest.mark.parametrize("bf16", [False, True])
+@pytest.mark.parametrize("shape", [(2, 64, 9, 7), (1, 128, 12, 10), (3, 64, 1, 41)])
+def test_fused_stem_backward_checker_accepts_torch_fp32(shape, bf16):
+    """pool_red_ref / K_POOL_RED and pool_dy_ref / K_POOL_DY accept the torch fp32 evaluation of the fused stem backward (dy
+    stored as fp32 / bf16), stage by stage through its own stored dbeta / dgamma; they reject the shift left out of beta, the
+    mean term left out of `an`, and a window's gradient at the neighbouring pixel"""
+    N, C, H, W = shape
+    vec = 8 if bf16 else 4
+    p = F64.pool_inputs(N, C, H, W, bf16)
+    pooled, idx, _ = _pool_emulate(p, bf16)
+    e = _stem_bwd_emulate(p, pooled, idx, bf16)
+    coef = torch.stack([p["scale"], p["shift"], p["mean"], p["invstd"]])
+    MP = pooled.numel() // C
+    K = F64.chain_len(MP, 1, C, vec, 1024)
+    (s1, s2), (m1, m2) = F64.pool_red_ref(p["dp"], pooled, coef)
+    F64.check_sum(e["dbeta"], s1, m1, K + 1, "stem dbeta")
+    F64.check_sum(e["dgamma"], s2, m2, F64.K_POOL_RED + K + 1, "stem dgamma")
+    dz64, mag = F64.pool_bwd_ref(p["dp"], pooled, idx, H, W)
+    k1 = p["gamma"].double() * p["invstd"].double()
+
+    def dy_ratio(dy):
+        want, A = F64.pool_dy_ref(dz64, mag, p["y"], coef, k1, e["dbeta"].double() / e["M"], e["dgamma"].double() / e["M"])
+        return F64.stored_ratio(dy, want, A, F64.K_POOL_DY, bf16, "stem dy")
+    r = dy_ratio(e["dy"])
+    print(r)
+    assert r.ok, r
+    s = e["dy"].double().reshape(-1, C)
+    Kb = 4 * (e["M"] // 4 + 1) + 1
+    F64.check_sum(e["dbias"], s.sum(0), s.abs().sum(0), Kb, "stem dbias")
+    # defects
+    g = torch.where(pooled > 0, p["dp"], torch.zeros_like(p["dp"]))
+    rsc = 1.0 / p["scale"]
+    noshift = (g * (pooled - p["mean"] * p["scale"])).sum((0, 1, 2)) * rsc * p["invstd"]
+    assert _fails(lambda: F64.check_sum(noshift, s2, m2, F64.K_POOL_RED + K + 1, "stem dgamma"))
+    k1f, bn, an = e["k"]
+    assert not dy_ratio(F64._b(k1f * e["z"] + (bn * p["y"] + (an + bn * p["mean"])), bf16)).ok
+    zs = torch.roll(e["z"], 1, dims=2)
+    assert not dy_ratio(F64._b(k1f * zs + (bn * p["y"] + an), bf16)).ok
+    if bf16:
+        u = e["unrounded"].double().reshape(-1, C)
+        assert _fails(lambda: F64.check_sum(u.sum(0).float(), s.sum(0), s.abs().sum(0), Kb, "stem dbias"))
