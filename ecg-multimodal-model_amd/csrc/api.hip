@@ -132,14 +132,22 @@ int ecgmm_bn_act_from_rows(int dtype, const void* y, const float* partial, int r
                            const float* beta, float* running_mean, float* running_var, int64_t* num_batches_tracked,
                            float momentum, float eps, float* coef_out, const void* res, const float* rcoef,
                            const float* gate, int rows_per_sample, int relu, void* out, int64_t M, int C, void* stream) {
+  return ecgmm_bn_act_from_rows_bits(dtype, y, partial, rows, count, gamma, beta, running_mean, running_var, num_batches_tracked,
+                                     momentum, eps, coef_out, res, rcoef, gate, rows_per_sample, relu, out, nullptr, M, C, stream);
+}
+int ecgmm_bn_act_from_rows_bits(int dtype, const void* y, const float* partial, int rows, double count, const float* gamma,
+                                const float* beta, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                                float momentum, float eps, float* coef_out, const void* res, const float* rcoef,
+                                const float* gate, int rows_per_sample, int relu, void* out, uint8_t* relu_bits, int64_t M,
+                                int C, void* stream) {
   if (!partial || !coef_out) ECG_FAIL(ECGMM_ERR_SHAPE, "bn_act_from_rows: null partial rows / coef");
   if (!ecg_bn_fold_ok(C, rows)) {   // the separate finalize launch, same results
     ECG_TRY(ecg_bn_finalize(partial, rows, C, count, gamma, beta, running_mean, running_var, (long long*)num_batches_tracked,
                             momentum, eps, coef_out, S_(stream)));
-    return ecg_bn_act(dtype, y, coef_out, res, rcoef, gate, rows_per_sample, relu, out, (long)M, C, S_(stream));
+    return ecg_bn_act(dtype, y, coef_out, res, rcoef, gate, rows_per_sample, relu, out, (long)M, C, S_(stream), relu_bits);
   }
   EcgBnFold f = {partial, rows, count, gamma, beta, running_mean, running_var, (long long*)num_batches_tracked, momentum, eps};
-  return ecg_bn_act_fold(dtype, y, coef_out, f, res, rcoef, gate, rows_per_sample, relu, out, (long)M, C, S_(stream));
+  return ecg_bn_act_fold(dtype, y, coef_out, f, res, rcoef, gate, rows_per_sample, relu, out, (long)M, C, S_(stream), relu_bits);
 }
 size_t ecgmm_bn_bwd_scratch(int dtype, int64_t M, int C) { return ecg_bn_bwd_scratch(dtype, (long)M, C); }
 int ecgmm_bn_bwd(int dtype, const void* dout, const void* maskref, const float* gate, const float* addc,
@@ -147,6 +155,13 @@ int ecgmm_bn_bwd(int dtype, const void* dout, const void* maskref, const float* 
                  float* dbeta, void* dy, void* dz_out, float* dbias, int64_t M, int C, void* scratch, void* stream) {
   return ecg_bn_bwd(dtype, dout, maskref, gate, addc, rows_per_sample, y, coef, gamma, dgamma, dbeta, dy, dz_out, dbias,
                     (long)M, C, (float*)scratch, S_(stream));
+}
+int ecgmm_bn_bwd_bits(int dtype, const void* dout, const uint8_t* mask_bits, const float* gate, const float* addc,
+                      int rows_per_sample, const void* y, const float* coef, const float* gamma, float* dgamma,
+                      float* dbeta, void* dy, void* dz_out, float* dbias, int64_t M, int C, void* scratch, void* stream) {
+  if (dtype != ECGMM_BF16 || !mask_bits) ECG_FAIL(ECGMM_ERR_SHAPE, "bn_bwd_bits: bf16 with a bit mask only");
+  return ecg_bn_bwd(dtype, dout, nullptr, gate, addc, rows_per_sample, y, coef, gamma, dgamma, dbeta, dy, dz_out, dbias,
+                    (long)M, C, (float*)scratch, S_(stream), mask_bits);
 }
 
 int ecgmm_conv_bwd_data_bnred(int dtype, const ecgmm_conv_desc* c, const void* dy, const void* w_dgrad,

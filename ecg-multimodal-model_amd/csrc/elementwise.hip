@@ -247,11 +247,26 @@ __device__ __forceinline__ void fin_fold_group(const float* __restrict__ partial
   }
 }
 
-// forward fold: s_coef = [2][C] (scale, shift) in LDS for this workgroup; workgroup 0 writes coef_out / running statistics
+// Channel-sliced launch of the folded passes (C >= 256; host side: bn_fold_slices): blockIdx.y = slice s, and the workgroup
+// reads, transforms and writes only channels [128 s, 128 s + 128) of its rows -- 256 contiguous bytes per bf16 row (512 per
+// fp32 row: both element types take the same scheme).  It then needs 128 coefficients, not C: ONE fin_fold_group call at any C
+// instead of C / 128 of them one after the other.  gridDim.y == 1 is the unsliced launch (the workgroup owns all C channels).
+// Channel group g0, thread -> (channel, row slice) and the order of additions are those of the unsliced fold, so every
+// coefficient and output element has the same bits.  Global memory is indexed by the GLOBAL channel, LDS by the local one.
+struct ChanSlice { int c_lo, W; };   // first channel and width of this workgroup's slice
+__device__ __forceinline__ ChanSlice chan_slice(int C) {
+  ChanSlice s;
+  s.W = gridDim.y > 1 ? 128 : C;
+  s.c_lo = (int)blockIdx.y * s.W;
+  return s;
+}
+
+// forward fold: s_coef = [2][W] (scale, shift) of the workgroup's channels in LDS; the workgroups of pixel chunk 0 write
+// their channels of coef_out / the running statistics
 template <int THREADS>
-__device__ __forceinline__ void bn_fin_prologue(const BnFin& f, int C, float* s_coef, double* s_red) {
+__device__ __forceinline__ void bn_fin_prologue(const BnFin& f, int C, ChanSlice cs, float* s_coef, double* s_red) {
   const int G = C < 128 ? C : 128;
-  for (int g0 = 0; g0 < C; g0 += G) {
+  for (int g0 = cs.c_lo; g0 < cs.c_lo + cs.W; g0 += G) {
     double s1, s2;
     fin_fold_group<THREADS>(f.partial, f.rows, C, g0, G, s_red, s1, s2);
     if ((int)threadIdx.x < G) {
@@ -263,8 +278,8 @@ __device__ __forceinline__ void bn_fin_prologue(const BnFin& f, int C, float* s_
       const float g = f.gamma ? f.gamma[c] : 1.f, b = f.beta ? f.beta[c] : 0.f;
       const float sc = g * invstd;
       const float sh = b - (float)mean * sc;
-      s_coef[c] = sc;
-      s_coef[C + c] = sh;
+      s_coef[c - cs.c_lo] = sc;
+      s_coef[cs.W + c - cs.c_lo] = sh;
       if (blockIdx.x == 0) {
         f.coef_out[c] = sc;
         f.coef_out[C + c] = sh;
@@ -279,24 +294,25 @@ __device__ __forceinline__ void bn_fin_prologue(const BnFin& f, int C, float* s_
     }
     __syncthreads();   // s_red is reused by the next group; s_coef complete after the last one
   }
-  if (f.nbt && blockIdx.x == 0 && threadIdx.x == 0) *f.nbt += 1;
+  if (f.nbt && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *f.nbt += 1;
 }
 
-// backward fold: s_bcoef = [3][C] (gamma * invstd, mean dz, mean dz * xhat) in LDS; workgroup 0 writes dgamma / dbeta
+// backward fold: s_bcoef = [3][W] (gamma * invstd, mean dz, mean dz * xhat) in LDS; the workgroups of pixel chunk 0 write
+// their channels of dgamma / dbeta
 template <int THREADS>
-__device__ __forceinline__ void bn_bwd_fin_prologue(const BnBwdFin& f, const float* __restrict__ coef, int C, float* s_bcoef,
-                                                    double* s_red) {
+__device__ __forceinline__ void bn_bwd_fin_prologue(const BnBwdFin& f, const float* __restrict__ coef, int C, ChanSlice cs,
+                                                    float* s_bcoef, double* s_red) {
   const int G = C < 128 ? C : 128;
-  for (int g0 = 0; g0 < C; g0 += G) {
+  for (int g0 = cs.c_lo; g0 < cs.c_lo + cs.W; g0 += G) {
     double s1, s2;
     fin_fold_group<THREADS>(f.partial, f.rows, C, g0, G, s_red, s1, s2);
     if ((int)threadIdx.x < G) {
       const int c = g0 + threadIdx.x;
       const float inv = coef[3 * C + c];
       if (f.centered) s2 *= (double)inv;
-      s_bcoef[c] = (f.gamma ? f.gamma[c] : 1.f) * inv;
-      s_bcoef[C + c] = (float)(s1 / f.count);
-      s_bcoef[2 * C + c] = (float)(s2 / f.count);
+      s_bcoef[c - cs.c_lo] = (f.gamma ? f.gamma[c] : 1.f) * inv;
+      s_bcoef[cs.W + c - cs.c_lo] = (float)(s1 / f.count);
+      s_bcoef[2 * cs.W + c - cs.c_lo] = (float)(s2 / f.count);
       if (blockIdx.x == 0) {
         if (f.dgamma) f.dgamma[c] = (float)s2;
         if (f.dbeta) f.dbeta[c] = (float)s1;
@@ -330,14 +346,15 @@ struct BnActParams {
 template <typename T>
 __global__ __launch_bounds__(BN_ACT_THREADS) void bn_act_kernel(BnActParams p) {
   constexpr int VEC = Elem<T>::VEC;
-  const int cpr = p.C / VEC, rpi = BN_ACT_THREADS / cpr;
+  const ChanSlice cs = chan_slice(p.C);
+  const int cpr = cs.W / VEC, rpi = BN_ACT_THREADS / cpr;   // 16-B chunks per row (slice), rows per iteration
   const int chunk = threadIdx.x % cpr, r0 = threadIdx.x / cpr;
-  const int c0 = chunk * VEC;
+  const int c0 = cs.c_lo + chunk * VEC;   // GLOBAL channel: every tensor / coefficient / gate / bit index below
   __shared__ double s_red[FIN_LDS_DOUBLES];
   __shared__ float s_coef[2 * 512];
-  const float* cf = p.coef;
+  const float* cf = p.coef + c0;
   int cfs = p.C;           // stride between the scale and the shift rows
-  // (fold form: the first trip's loads are issued BEFORE the fold of the partial rows, whose ~3 us then hide their HBM latency)
+  // (fold form: the first trip's loads are issued BEFORE the fold of the partial rows, which then hides their HBM latency)
   const T* y = (const T*)p.y;
   const T* res = (const T*)p.res;
   const long stride = (long)gridDim.x * rpi;
@@ -354,14 +371,15 @@ __global__ __launch_bounds__(BN_ACT_THREADS) void bn_act_kernel(BnActParams p) {
     }
   }
   if (p.fin.partial) {
-    bn_fin_prologue<BN_ACT_THREADS>(p.fin, p.C, s_coef, s_red);
-    cf = s_coef;
+    bn_fin_prologue<BN_ACT_THREADS>(p.fin, p.C, cs, s_coef, s_red);
+    cf = s_coef + chunk * VEC;   // (LDS: the local channel)
+    cfs = cs.W;
   }
   float sc[VEC], sh[VEC], rs[VEC], rb[VEC];
 #pragma unroll
   for (int j = 0; j < VEC; ++j) {
-    sc[j] = cf[c0 + j];
-    sh[j] = cf[cfs + c0 + j];
+    sc[j] = cf[j];
+    sh[j] = cf[cfs + j];
     rs[j] = p.rcoef ? p.rcoef[c0 + j] : 1.f;
     rb[j] = p.rcoef ? p.rcoef[p.C + c0 + j] : 0.f;
   }
@@ -412,7 +430,7 @@ __global__ __launch_bounds__(BN_ACT_THREADS) void bn_act_kernel(BnActParams p) {
         unsigned bits = 0u;
 #pragma unroll
         for (int j = 0; j < VEC; ++j) bits |= (g[j] > 0.f ? 1u : 0u) << j;
-        p.relu_bits[rr * cpr + chunk] = (unsigned char)bits;
+        p.relu_bits[rr * (p.C / VEC) + c0 / VEC] = (unsigned char)bits;
       }
       if (u == 0 || two) st16(out + rr * p.C + c0, pack16<T>(f));
     }
@@ -451,12 +469,16 @@ __global__ __launch_bounds__(BWD_THREADS) void bn_bwd_kernel(BnBwdParams p) {
   constexpr int VEC = Elem<T>::VEC;
   extern __shared__ float shm_dyn[];
   float(*shm)[2 * VEC + 1] = reinterpret_cast<float(*)[2 * VEC + 1]>(shm_dyn);  // [BWD_THREADS][2*VEC+1]
-  const int cpr = p.C / VEC, rpi = BWD_THREADS / cpr;
+  // (sliced only as the folded apply pass without bias-gradient rows: host side.  The reduce pass and the row sums at the
+  //  end of this kernel always run with gridDim.y == 1, where cs.W == C and c0 is the chunk's channel as before)
+  const ChanSlice cs = chan_slice(p.C);
+  const int cpr = cs.W / VEC, rpi = BWD_THREADS / cpr;
   const int chunk = threadIdx.x % cpr, r0 = threadIdx.x / cpr;
-  const int c0 = chunk * VEC;
+  const int c0 = cs.c_lo + chunk * VEC;   // GLOBAL channel
   __shared__ double s_red[APPLY ? FIN_LDS_DOUBLES : 1];
   __shared__ float s_bcoef[APPLY ? 3 * 512 : 1];
-  const float* bc = p.bcoef;
+  const float* bc = p.bcoef + c0;
+  int bcs = p.C;
   // (fold form: the first row's loads are issued before the fold, as in bn_act_kernel)
   const long rfirst = (long)blockIdx.x * rpi + r0;
   u32x4 pd = {}, pv = {};
@@ -466,8 +488,9 @@ __global__ __launch_bounds__(BWD_THREADS) void bn_bwd_kernel(BnBwdParams p) {
     pv = ld16s((const T*)p.y + rfirst * p.C + c0);
   }
   if (APPLY && p.fin.partial) {
-    bn_bwd_fin_prologue<BWD_THREADS>(p.fin, p.coef, p.C, s_bcoef, s_red);
-    bc = s_bcoef;
+    bn_bwd_fin_prologue<BWD_THREADS>(p.fin, p.coef, p.C, cs, s_bcoef, s_red);
+    bc = s_bcoef + chunk * VEC;   // (LDS: the local channel)
+    bcs = cs.W;
   }
   float mean[VEC], inv[VEC], k1[VEC], k2[VEC], k3[VEC], a1[VEC], a2[VEC], msc[VEC], msh[VEC];
 #pragma unroll
@@ -478,9 +501,9 @@ __global__ __launch_bounds__(BWD_THREADS) void bn_bwd_kernel(BnBwdParams p) {
     inv[j] = p.coef[3 * p.C + c0 + j];
     a1[j] = a2[j] = 0.f;
     if (APPLY) {
-      k1[j] = bc[c0 + j];
-      k2[j] = bc[p.C + c0 + j];
-      k3[j] = bc[2 * p.C + c0 + j];
+      k1[j] = bc[j];
+      k2[j] = bc[bcs + j];
+      k3[j] = bc[2 * bcs + j];
     }
   }
   const T* dout = (const T*)p.dout;
@@ -1368,12 +1391,35 @@ extern "C" int ecgmm_bn_fold(int on) {
 bool ecg_bn_fold_ok(int C, int rows) {
   // Mid-round 3 this measured 6.98 ms with the separate launches against 7.04 ms folded (256 workgroups each re-reading the same
   // 128-256 KB of partial rows cost what the ~5 us launch + its boundary cost the stream).  With the consumers' first loads issued
-  // BEFORE the fold -- its ~3 us then cover their HBM latency -- the folded form is the faster one: same-call A/B 6.47, 6.46 ->
+  // BEFORE the fold -- which then covers their HBM latency -- the folded form is the faster one: same-call A/B 6.47, 6.46 ->
   // 6.44, 6.46 ms (multimodal batch 256), 2.96, 2.97 -> 2.95, 2.97 (12-lead batch 512), 3.44, 3.45 -> 3.44, 3.44 (image-only batch
   // 128), and 35 launches fewer per step.  DEFAULT ON; ECGMM_BN_FOLD=0 / ecgmm_bn_fold(0) restores the separate launches.
+  // What the fold costs a workgroup is rows * 2 C / 1024 loads per thread in dependent trips of 8: 4 trips at C = 64 with 256
+  // rows (the "~3 us" this comment used to quote for every layer), but 16 at C = 256 and 24-32 at C = 512 when it folds all C
+  // channels, group after group -- hence the channel-sliced launch (bn_fold_slices), 8 trips at any C >= 128.
   if (g_bn_fold < 0) g_bn_fold = env_on("ECGMM_BN_FOLD");
   if (!g_bn_fold || rows < 1 || rows > 512 || C > 512) return false;
   return C >= 128 ? C % 128 == 0 : (C >= 16 && 1024 % C == 0);
+}
+
+// Channel-sliced launch of the folded passes (kernel side: ChanSlice).  NS = C / 128 slices for C >= 256, each workgroup a
+// (pixel chunk, slice) pair, at most 256 workgroups in all as before.  DEFAULT ON; ECGMM_BN_FOLD_SLICE=0 /
+// ecgmm_bn_fold_slice(0) restores the launch in which every workgroup walks whole rows and folds all C channels.
+static int g_bn_fold_slice = -1;
+extern "C" int ecgmm_bn_fold_slice(int on) {
+  g_bn_fold_slice = on != 0;
+  return 0;
+}
+static int bn_fold_slices(int C) {
+  if (g_bn_fold_slice < 0) g_bn_fold_slice = env_on("ECGMM_BN_FOLD_SLICE");
+  return g_bn_fold_slice && C >= 256 && C % 128 == 0 ? C / 128 : 1;
+}
+// grid of a folded pass: x = pixel chunks of `rows_per_wg` rows of (C / ns)-channel row segments each, y = the ns slices
+static dim3 bn_fold_grid(int dtype, long M, int C, int ns, int threads, int trips) {
+  const int vec = dtype == ECGMM_BF16 ? 8 : 4;
+  int gx = ew_grid(M, (threads / (C / ns / vec)) * trips);
+  if (gx > 256 / ns) gx = 256 / ns;
+  return dim3(gx, ns);
 }
 
 // bn_act whose coefficients are folded from the producer's partial rows inside the launch (no bn_finalize launch);
@@ -1391,11 +1437,9 @@ int ecg_bn_act_fold(int dtype, const void* y, float* coef, const EcgBnFold& f, c
   p.fin.partial = f.partial; p.fin.rows = f.rows; p.fin.count = f.count; p.fin.gamma = f.gamma; p.fin.beta = f.beta;
   p.fin.rm = f.rm; p.fin.rv = f.rv; p.fin.nbt = f.nbt; p.fin.momentum = f.momentum; p.fin.eps = f.eps; p.fin.coef_out = coef;
   p.relu_bits = dtype == ECGMM_BF16 && relu ? relu_bits : nullptr;
-  int vec = dtype == ECGMM_BF16 ? 8 : 4;
-  int grid = ew_grid(M, (BN_ACT_THREADS / (C / vec)) * 4);
-  if (grid > 256) grid = 256;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(bn_act_kernel<bf16_t>, dim3(grid), dim3(BN_ACT_THREADS), 0, stream, p),
-             hipLaunchKernelGGL(bn_act_kernel<float>, dim3(grid), dim3(BN_ACT_THREADS), 0, stream, p), "bn_act");
+  const dim3 grid = bn_fold_grid(dtype, M, C, bn_fold_slices(C), BN_ACT_THREADS, 4);   // (ns == 1: the grid of ecg_bn_act)
+  DISPATCH_T(dtype, hipLaunchKernelGGL(bn_act_kernel<bf16_t>, grid, dim3(BN_ACT_THREADS), 0, stream, p),
+             hipLaunchKernelGGL(bn_act_kernel<float>, grid, dim3(BN_ACT_THREADS), 0, stream, p), "bn_act");
   ECG_CHECK_LAUNCH("bn_act_fold");
   return 0;
 }
@@ -1428,14 +1472,22 @@ static int bn_bwd_rows(int dtype, long M, int C) {
   return g > 256 ? 256 : g;
 }
 template <typename T, bool APPLY>
-static void bn_bwd_launch(const BnBwdParams& p, int grid, hipStream_t stream) {
+static void bn_bwd_launch(const BnBwdParams& p, dim3 grid, hipStream_t stream) {
   constexpr size_t lds = (size_t)BWD_THREADS * (2 * Elem<T>::VEC + 1) * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)bn_bwd_kernel<T, APPLY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
-  hipLaunchKernelGGL((bn_bwd_kernel<T, APPLY>), dim3(grid), dim3(BWD_THREADS), lds, stream, p);
+  hipLaunchKernelGGL((bn_bwd_kernel<T, APPLY>), grid, dim3(BWD_THREADS), lds, stream, p);
+}
+// grid of the apply pass: channel-sliced when it folds the finalize and writes no bias-gradient rows (those are one row of
+// all C channels per workgroup, summed in workgroup order: they keep the unsliced launch and its summation order); the
+// reduce pass's grid (`rows`, also the number of partial rows it wrote) otherwise.  The reduce pass itself is never
+// sliced: it folds nothing, and the apply pass reads its rows whatever their number.
+static dim3 bn_bwd_apply_grid(int dtype, const BnBwdParams& p, int rows) {
+  if (!p.fin.partial || p.partial) return dim3(rows);
+  return bn_fold_grid(dtype, p.M, p.C, bn_fold_slices(p.C), BWD_THREADS, 8);   // (ns == 1: == bn_bwd_rows)
 }
 
 // full BN backward: reduce -> finalize -> apply.  scratch: partial rows [rows][2][C] + bcoef [3][C]
@@ -1481,7 +1533,8 @@ int ecg_bn_bwd(int dtype, const void* dout, const void* maskref, const float* ga
   }
   if (dz_early) { p.dout = dz_out; p.maskref = nullptr; p.mask_bits = nullptr; p.dz_out = nullptr; }
   p.partial = dbias ? partial : nullptr;  // reuse (finalize already consumed it; stream-ordered)
-  DISPATCH_T(dtype, (bn_bwd_launch<bf16_t, true>(p, grid, stream)), (bn_bwd_launch<float, true>(p, grid, stream)), "bn_bwd");
+  const dim3 agrid = bn_bwd_apply_grid(dtype, p, grid);
+  DISPATCH_T(dtype, (bn_bwd_launch<bf16_t, true>(p, agrid, stream)), (bn_bwd_launch<float, true>(p, agrid, stream)), "bn_bwd");
   ECG_CHECK_LAUNCH("bn_bwd_apply");
   if (dbias) {
     hipLaunchKernelGGL(rows_sum_kernel, dim3(ceil_div(C, 64)), dim3(1024), 0, stream, partial, grid, C, dbias, 0);
@@ -1518,7 +1571,8 @@ int ecg_bn_bwd_tail(int dtype, const void* dout, const void* maskref, const void
     p.fin.dbeta = dbeta; p.fin.centered = 1;
   }
   p.partial = dbias ? scratch : nullptr;   // (the finalize above reads `partial`, a different buffer: scratch's rows are free)
-  DISPATCH_T(dtype, (bn_bwd_launch<bf16_t, true>(p, grid, stream)), (bn_bwd_launch<float, true>(p, grid, stream)), "bn_bwd");
+  const dim3 agrid = bn_bwd_apply_grid(dtype, p, grid);
+  DISPATCH_T(dtype, (bn_bwd_launch<bf16_t, true>(p, agrid, stream)), (bn_bwd_launch<float, true>(p, agrid, stream)), "bn_bwd");
   ECG_CHECK_LAUNCH("bn_bwd_apply");
   if (dbias) {
     hipLaunchKernelGGL(rows_sum_kernel, dim3(ceil_div(C, 64)), dim3(1024), 0, stream, (const float*)scratch, grid, C, dbias, 0);

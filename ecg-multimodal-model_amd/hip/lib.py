@@ -124,6 +124,9 @@ SIGNATURES = {
     "ecgmm_maxpool_relu_bwd": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "ecgmm_bn_fuse_min_pixels": (i32, [i64]),
     "ecgmm_bn_fold": (i32, [i32]),
+    "ecgmm_bn_fold_slice": (i32, [i32]),
+    "ecgmm_bn_act_from_rows_bits": (i32, [i32, vp, vp, i32, f64, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, i32, i32, vp, vp, i64, i32, vp]),
+    "ecgmm_bn_bwd_bits": (i32, [i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp]),
     "ecgmm_tl_enable": (i32, [i32]),
     "ecgmm_tl_mark": (i32, [i32, vp]),
     "ecgmm_tl_collect": (i32, [i32, vp, vp]),

@@ -375,6 +375,22 @@ int ecgmm_bn_fuse_min_pixels(int64_t m);
  * partial rows itself instead of a separate ~5 us launch in between; csrc/elementwise.hip): 1 = on (default), 0 = separate
  * launches.  Start-up value: ECGMM_BN_FOLD.  Same values up to the fp64 summation grouping of the partial rows. */
 int ecgmm_bn_fold(int on);
+/* Channel-sliced launch of those folded passes for C >= 256: a workgroup is a (pixel chunk, 128-channel slice) pair, folds
+ * only its own 128 channels of the partial rows (one group instead of C / 128, one after the other) and walks 128-channel
+ * row segments; at most 256 workgroups as before.  1 = on (default), 0 = every workgroup walks whole rows and folds all C
+ * channels.  Start-up value: ECGMM_BN_FOLD_SLICE.  Bit-identical results (same fp64 summation order per channel). */
+int ecgmm_bn_fold_slice(int on);
+/* ecgmm_bn_act_from_rows that also writes the ReLU mask as bits (bf16 and relu != 0; relu_bits nullable): [M][C / 8] bytes,
+ * bit j of byte [row][k] = (out[row][8 k + j] > 0), 1/16 of the activated tensor's bytes; and ecgmm_bn_bwd reading that
+ * mask (bf16 only) instead of a mask tensor -- the pair the ResNet18 plan runs around each residual block's bn2. */
+int ecgmm_bn_act_from_rows_bits(int dtype, const void* y, const float* partial, int rows, double count, const float* gamma,
+                                const float* beta, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                                float momentum, float eps, float* coef_out, const void* res, const float* rcoef,
+                                const float* gate, int rows_per_sample, int relu, void* out, uint8_t* relu_bits, int64_t M,
+                                int C, void* stream);
+int ecgmm_bn_bwd_bits(int dtype, const void* dout, const uint8_t* mask_bits, const float* gate, const float* addc,
+                      int rows_per_sample, const void* y, const float* coef, const float* gamma, float* dgamma,
+                      float* dbeta, void* dy, void* dz_out, float* dbias, int64_t M, int C, void* scratch, void* stream);
 /* ResNet18 plan: run the stem by recompute (ecgmm_stem_stats_only / stem_pool_fwd / stem_pool_bwd; bf16 only): 1 = on,
  * 0 = the two-pass route that keeps the full-resolution conv output (default: 0.2 ms per step faster at batch 256 although
  * it moves 1.6 GB more -- the recomputing kernels are instruction-bound).  Start-up value: ECGMM_STEM_RECOMPUTE.

@@ -1,6 +1,8 @@
 """Stand-alone rates of the BatchNorm element-wise passes at the ResNet18 layer shapes (batch 256, bf16): bn_act without / with
 a residual, full BatchNorm backward (reduce + finalize + apply) and the apply-from-rows form.  Bytes = the tensors each pass must
-move once; GB/s against the 6.29 TB/s a float4 copy reaches on this chip (MI355X_MICROARCH.md)."""
+move once; GB/s against the 6.29 TB/s a float4 copy reaches on this chip (MI355X_MICROARCH.md).
+The passes that fold the finalize (bn_act from rows, both backward forms) are timed with the channel-sliced launch off and on
+(ecgmm_bn_fold_slice) where it applies (C >= 256), alternating, in the same process."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -37,6 +39,20 @@ for name, HW, Cn in (("l1", 56 * 56, 64), ("l2", 28 * 28, 128), ("l3", 14 * 14, 
     def bwd(): i = nxt(); return lib.ecgmm_bn_bwd(L.BF16, ptr(rs[i]), ptr(ys[i]), None, None, 1, ptr(ys[i]), ptr(coef), ptr(gamma), ptr(dg), ptr(db), ptr(os_[i]), None, None, M, Cn, ptr(scratch), stream())
     rows = torch.rand(256 * 2 * Cn, device="cuda:0")
     def bwd_rows(): i = nxt(); return lib.ecgmm_bn_bwd_from_rows(L.BF16, ptr(rs[i]), ptr(ys[i]), ptr(ys[i]), ptr(coef), ptr(gamma), ptr(dg), ptr(db), ptr(os_[i]), ptr(rows), 256, M, Cn, ptr(scratch), stream())
-    for label, fn, tensors in (("bn_act", act, 2), ("bn_act+residual", act_res, 3), ("bn_bwd reduce+apply", bwd, 5), ("bn_bwd apply from rows", bwd_rows, 3)):
-        us = timeit(fn)
-        print(f"{name} C={Cn:3d} M={M:7d} {label:24s} {us:7.1f} us  {tensors * n * 2 / us / 1e6:6.2f} TB/s ({tensors} x {n * 2 / 1e6:.0f} MB, {K} buffer sets in rotation)")
+    beta, rm, rv = torch.zeros(Cn, device="cuda:0"), torch.zeros(Cn, device="cuda:0"), torch.ones(Cn, device="cuda:0")
+    nbt = torch.zeros((), dtype=torch.int64, device="cuda:0")
+    coef_o = torch.empty(4 * Cn, device="cuda:0")
+    srows = torch.rand(256 * 2 * Cn, device="cuda:0") + 1.0
+    def act_rows(res):
+        def f(): i = nxt(); return lib.ecgmm_bn_act_from_rows(L.BF16, ptr(ys[i]), ptr(srows), 256, float(M), ptr(gamma), ptr(beta), ptr(rm), ptr(rv), ptr(nbt), 0.1, 1e-5, ptr(coef_o), ptr(rs[i]) if res else None, None, None, 1, 1, ptr(os_[i]), M, Cn, stream())
+        return f
+    def show(label, us, tensors):
+        print(f"{name} C={Cn:3d} M={M:7d} {label:34s} {us:7.1f} us  {tensors * n * 2 / us / 1e6:6.2f} TB/s ({tensors} x {n * 2 / 1e6:.0f} MB, {K} buffer sets in rotation)")
+    for label, fn, tensors in (("bn_act", act, 2), ("bn_act+residual", act_res, 3)):
+        show(label, timeit(fn), tensors)
+    for label, fn, tensors in (("bn_act from rows", act_rows(False), 2), ("bn_act+residual from rows", act_rows(True), 3),
+                               ("bn_bwd reduce+apply", bwd, 5), ("bn_bwd apply from rows", bwd_rows, 3)):
+        for sl in ((0, 1, 0, 1) if Cn >= 256 else (1,)):
+            lib.ecgmm_bn_fold_slice(sl)
+            show(label + (" [slice %d]" % sl if Cn >= 256 else ""), timeit(fn), tensors)
+    lib.ecgmm_bn_fold_slice(1)
