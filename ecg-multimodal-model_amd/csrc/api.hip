@@ -22,6 +22,38 @@ extern "C" {
 int ecgmm_version(void) { return ECGMM_VERSION; }
 const char* ecgmm_last_error(void) { return g_err; }
 
+// ---- run-time switches (switches.h): by name, and the named setters as wrappers over the same table entries
+const char* ecgmm_switch_name(int i) { return i >= 0 && i < sw::COUNT ? sw::ALL[i]->env : nullptr; }
+int ecgmm_switch_get(const char* env_name, int64_t* value) {
+  Switch* s = sw::find(env_name);
+  if (!s) ECG_FAIL(ECGMM_ERR_SHAPE, "switch_get: unknown switch %s", env_name ? env_name : "(null)");
+  if (!value) ECG_FAIL(ECGMM_ERR_SHAPE, "switch_get: null value pointer");
+  *value = s->get();
+  return 0;
+}
+int ecgmm_switch_set(const char* env_name, int64_t value) {
+  Switch* s = sw::find(env_name);
+  if (!s) ECG_FAIL(ECGMM_ERR_SHAPE, "switch_set: unknown switch %s", env_name ? env_name : "(null)");
+  if (s == &sw::SIDE_WGRAD)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "switch_set: ECGMM_SIDE_WGRAD is each plan's own state after start-up, call ecgmm_side_wgrad()");
+  if (!s->runtime) ECG_FAIL(ECGMM_ERR_SHAPE, "switch_set: %s is read once at start-up", s->env);
+  s->set((long)value);
+  return 0;
+}
+int ecgmm_conv_halo_enable(int on) { sw::CONV_HALO.set(on); return 0; }
+int ecgmm_conv_halo_cus(int cus) { sw::HALO_CUS.set(cus); return 0; }
+int ecgmm_conv_halo_w4(int on) { sw::HALO_W4.set(on); return 0; }
+int ecgmm_conv_halo_stagger(int on) { sw::HALO_STAGGER.set(on); return 0; }
+int ecgmm_conv_halo_stream(int on) { sw::HALO_STREAM.set(on); return 0; }
+int ecgmm_conv_halo_pingpong(int on) { sw::HALO_PP.set(on); return 0; }
+int ecgmm_conv_wgrad_pingpong(int on) { sw::WGRAD_PP.set(on); return 0; }
+int ecgmm_conv_wgrad_ring_enable(int on) { sw::WGRAD_RING.set(on); return 0; }
+int ecgmm_bn_fold(int on) { sw::BN_FOLD.set(on); return 0; }
+int ecgmm_bn_fold_slice(int on) { sw::BN_FOLD_SLICE.set(on); return 0; }
+int ecgmm_bn_fuse_min_pixels(int64_t m) { sw::BN_FUSE_MIN_M.set((long)m); return 0; }
+int ecgmm_stem_recompute(int on) { sw::STEM_RECOMPUTE.set(on); return 0; }
+int ecgmm_infer_down_side(int on) { sw::INFER_DOWN_SIDE.set(on); return 0; }
+
 int ecgmm_nchw_to_nhwc(int dtype, const float* src, void* dst, int N, int C, int64_t HW, void* stream) {
   return ecg_nchw_to_nhwc(dtype, src, dst, N, C, (long)HW, S_(stream));
 }

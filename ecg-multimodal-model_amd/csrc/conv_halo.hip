@@ -1232,7 +1232,6 @@ void halo_magic_div(unsigned d, unsigned& m, unsigned& sh) {
   m = (unsigned)(((1ull << (31 + l)) + d - 1) / d);
   sh = 31 + l;
 }
-int g_halo_cu_cap = -1;  // -1: read ECGMM_HALO_CUS at first use; <= 0 after that: no cap
 int halo_gk(int ntn, int ntm, int wg_per_cu = 1) {
   static int ncu[16] = {0};
   int dev = 0, cus = 256;
@@ -1244,8 +1243,8 @@ int halo_gk(int ntn, int ntm, int wg_per_cu = 1) {
     }
     cus = ncu[dev];
   }
-  if (g_halo_cu_cap < 0) { g_halo_cu_cap = (int)env_int("ECGMM_HALO_CUS", 0); if (g_halo_cu_cap < 0) g_halo_cu_cap = 0; }
-  if (g_halo_cu_cap > 0 && cus > g_halo_cu_cap) cus = g_halo_cu_cap;
+  const long cu_cap = sw::HALO_CUS.get();   // 0: no cap
+  if (cu_cap > 0 && cus > cu_cap) cus = (int)cu_cap;
   int Gk = cus * wg_per_cu / (ntn < 1 ? 1 : ntn);
   if (Gk > ntm) Gk = ntm;
   if (Gk > 512) Gk = 512;   // (partial-row buffers hold 512 rows: ECGMM_BN_RED_ROWS)
@@ -1276,15 +1275,9 @@ int launch_halo(const HaloParams& p, int* rows_out, hipStream_t stream) {
   return 0;
 }
 
-// 64 -> 64 channel 3x3 layers on 4-wave workgroups, two per CU (-1: read ECGMM_HALO_W4).  DEFAULT OFF.  Measured (round 3,
-// batch 256): stand-alone forward 94.5 -> 90.5 us, input gradient 94.7 -> 82.5 us (same-call A/B, tools/conv_bench.py --w4),
-// but the whole step 6.93 -> 7.28 ms: 512 half-size workgroups that CAN share a CU with other streams' waves lose more to the
-// concurrent weight-gradient / signal-encoder kernels than the overlap of their own phases gains.  The instantiation with the
-// fused BatchNorm-backward reduction (MODE 1) is never dispatched on 4 waves: it needs 432 B of scratch per lane, and with
-// compiler-inserted scratch traffic inside the counted-vmcnt K loop its partial rows were NOT reproducible run to run once
-// other streams shared the GPU (tools/det_check_mm.py; every scratch-free instantiation is bit-reproducible).
-#ifdef ECG_STAMP
 }  // namespace
+
+#ifdef ECG_STAMP
 extern "C" int ecgmm_hstamp_read(unsigned long long* out8, int reset) {
   if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_hstamp), sizeof(g_hstamp)) != hipSuccess) return 1;
   if (reset) {
@@ -1293,49 +1286,13 @@ extern "C" int ecgmm_hstamp_read(unsigned long long* out8, int reset) {
   }
   return 0;
 }
-namespace {
 #endif
-int g_halo_w4 = -1;
-int g_halo_pp = -1;       // ping-pong K loop on the 128-channel tiles (-1: read ECGMM_HALO_PP, default on)
-int g_halo_stream = -1;   // stream form of the 64 -> 64 channel 3x3 tiles (-1: read ECGMM_HALO_STREAM, default on)
-int g_halo_stagger = -1;  // waves 4-7 staggered by one MFMA block (-1: read ECGMM_HALO_STAGGER, default on)
-int g_halo_enabled = -1;  // read once from ECGMM_CONV_HALO: 0 = off, 1 = where it is the faster kernel (default), 2 = wherever applicable
-
-}  // namespace
-
-// Runtime switch (A/B against conv_igemm from one process: tools/conv_bench.py): 0 = never take the halo kernel.
-extern "C" int ecgmm_conv_halo_enable(int on) {
-  g_halo_enabled = on < 0 ? 0 : on > 2 ? 2 : on;
-  return 0;
-}
-
-extern "C" int ecgmm_conv_halo_pingpong(int on) {
-  g_halo_pp = on != 0;
-  return 0;
-}
-extern "C" int ecgmm_conv_halo_stream(int on) {
-  g_halo_stream = on != 0;
-  return 0;
-}
-extern "C" int ecgmm_conv_halo_stagger(int on) {
-  g_halo_stagger = on != 0;
-  return 0;
-}
-extern "C" int ecgmm_conv_halo_w4(int on) {
-  g_halo_w4 = on != 0;
-  return 0;
-}
-
-// Cap on the CUs (= persistent workgroups) a halo launch occupies: 0 = all (default).  Start-up value: ECGMM_HALO_CUS.
-extern "C" int ecgmm_conv_halo_cus(int cus) {
-  g_halo_cu_cap = cus < 0 ? 0 : cus;
-  return 0;
-}
 
 // Is the halo kernel applicable to this (stride-1, "same") convolution?  mode 0 = forward, 1 = input gradient.
+// (ECGMM_CONV_HALO / ecgmm_conv_halo_enable: the A/B against conv_igemm from one process, tools/conv_bench.py)
 bool ecg_conv_halo_ok(int dtype, int mode, const ConvGeom& g) {
-  if (g_halo_enabled < 0) g_halo_enabled = env_level("ECGMM_CONV_HALO", 2, 1);
-  if (!g_halo_enabled || dtype != ECGMM_BF16 || g.stride != 1 || g.S != 3) return false;
+  const long level = sw::CONV_HALO.get();
+  if (!level || dtype != ECGMM_BF16 || g.stride != 1 || g.S != 3) return false;
   if (!((g.R == 3 && g.pad_h == 1) || (g.R == 1 && g.pad_h == 0)) || g.pad_w != 1) return false;
   if (g.OH != g.H || g.OW != g.W) return false;
   const int Cs = mode == 0 ? g.Cin : g.Cout, Cd = mode == 0 ? g.Cout : g.Cin;
@@ -1344,7 +1301,7 @@ bool ecg_conv_halo_ok(int dtype, int mode, const ConvGeom& g) {
   const int HL = g.pad_h * g.W + g.pad_w, hrows = 256 + 2 * HL;
   if (hrows > (Cd > 64 ? HaloCfg<128>::HCAP : HaloCfg<64>::HCAP)) return false;
   if ((double)M * Cs * 2.0 > 2.0e9 || (double)M * Cd * 2.0 > 8.0e9) return false;
-  if (g_halo_enabled == 2) return true;
+  if (level == 2) return true;
   // Where it pays (B = 256 / 512 layer shapes, same-call A/B against conv_igemm, profiles/r02_conv_bench_layers.txt and
   // tools/halo_1d.sh): every 3x3 layer (+5...+18 %) and the 1-D encoder's 128- and 256-channel stages (+7...+20 %).  The
   // 64-channel 1-D layer (3 K steps per tile) does not amortise the per-tile prologue / epilogue of the one resident
@@ -1352,11 +1309,17 @@ bool ecg_conv_halo_ok(int dtype, int mode, const ConvGeom& g) {
   return g.R == 3 || Cs >= 128;
 }
 
-// partial rows a halo launch with ConvEpi.wg_rows writes: one per workgroup of a channel tile
+// 64 -> 64 channel 3x3 layers on 4-wave workgroups, two per CU (ECGMM_HALO_W4).  DEFAULT OFF.  Measured (round 3,
+// batch 256): stand-alone forward 94.5 -> 90.5 us, input gradient 94.7 -> 82.5 us (same-call A/B, tools/conv_bench.py --w4),
+// but the whole step 6.93 -> 7.28 ms: 512 half-size workgroups that CAN share a CU with other streams' waves lose more to the
+// concurrent weight-gradient / signal-encoder kernels than the overlap of their own phases gains.  The instantiation with the
+// fused BatchNorm-backward reduction (MODE 1) is never dispatched on 4 waves: it needs 432 B of scratch per lane, and with
+// compiler-inserted scratch traffic inside the counted-vmcnt K loop its partial rows were NOT reproducible run to run once
+// other streams shared the GPU (tools/det_check_mm.py; every scratch-free instantiation is bit-reproducible).
 static bool halo_w4(const ConvGeom& g, int Cs, int Cd) {
-  if (g_halo_w4 < 0) g_halo_w4 = env_off("ECGMM_HALO_W4");
-  return g_halo_w4 && g.R == 3 && Cs == 64 && Cd == 64;
+  return sw::HALO_W4.get() && g.R == 3 && Cs == 64 && Cd == 64;
 }
+// partial rows a halo launch with ConvEpi.wg_rows writes: one per workgroup of a channel tile
 // (rows of the fused BatchNorm-backward reduction: that instantiation always runs one 8-wave workgroup per CU)
 int ecg_conv_halo_rows(int mode, const ConvGeom& g) {
   const int Cd = mode == 0 ? g.Cout : g.Cin;
@@ -1386,29 +1349,26 @@ int ecg_conv_halo(int mode, const ConvGeom& g, const void* src, const void* wpk,
       p.red_rows = epi->red_rows;
     }
   }
-  if (g_halo_stagger < 0) g_halo_stagger = env_on("ECGMM_HALO_STAGGER");
-  if (g_halo_pp < 0) g_halo_pp = env_on("ECGMM_HALO_PP");
-  p.stagger = g_halo_stagger;
+  p.stagger = (int)sw::HALO_STAGGER.get();
   int wg = 0;
   const bool wide = p.Cd > 64;
   int rc;
   // MODE 2 = input gradient WITHOUT the fused BatchNorm-backward reduction compiled in: the reduction's operand registers
   // push the BN = 128 instantiation over its 256-VGPR budget (396 B of scratch per lane) whether or not a launch uses it --
   // 13 us of a 88 us layer-2 launch (tools/halo_abl.sh, ablation 7)
-  static const bool ncs1_on = env_on("ECGMM_HALO_NCS1");
   if (halo_w4(g, p.Cs, p.Cd) && !p.red_y) {   // the 64 -> 64 channel 3x3 layers: 4-wave workgroups, two per CU (option)
     if (mode == 0) rc = launch_halo<64, 9, 0, false, 4>(p, &wg, stream);
     else rc = launch_halo<64, 9, 2, false, 4>(p, &wg, stream);
-  } else if (g.R == 3 && !wide && p.ncs == 1 && ncs1_on) {   // the same on one 8-wave workgroup per CU: next tile's halo during the K loop
+  } else if (g.R == 3 && !wide && p.ncs == 1 && sw::HALO_NCS1.get()) {   // the same on one 8-wave workgroup per CU: next tile's halo during the K loop
     // (stream form: forward with per-workgroup statistics rows or none, input gradient without addend / fused reduction)
-    if (g_halo_stream < 0) g_halo_stream = env_on("ECGMM_HALO_STREAM");
-    if (mode == 0 && g_halo_stream && (!p.stats || p.wg_rows) && !p.addend && !p.bias && p.act != 1) rc = launch_halo<64, 9, 0, true, 8, false, true>(p, &wg, stream);
-    else if (mode != 0 && g_halo_stream && !p.red_y && !p.addend && !p.bias && p.act != 1) rc = launch_halo<64, 9, 2, true, 8, false, true>(p, &wg, stream);
-    else if (mode != 0 && g_halo_stream && !p.red_y && p.addend && !p.bias && p.act != 1) rc = launch_halo<64, 9, 2, true, 8, false, true, true>(p, &wg, stream);
+    const bool st = sw::HALO_STREAM.get() != 0;
+    if (mode == 0 && st && (!p.stats || p.wg_rows) && !p.addend && !p.bias && p.act != 1) rc = launch_halo<64, 9, 0, true, 8, false, true>(p, &wg, stream);
+    else if (mode != 0 && st && !p.red_y && !p.addend && !p.bias && p.act != 1) rc = launch_halo<64, 9, 2, true, 8, false, true>(p, &wg, stream);
+    else if (mode != 0 && st && !p.red_y && p.addend && !p.bias && p.act != 1) rc = launch_halo<64, 9, 2, true, 8, false, true, true>(p, &wg, stream);
     else if (mode == 0) rc = launch_halo<64, 9, 0, true>(p, &wg, stream);
     else if (p.red_y) rc = launch_halo<64, 9, 1, true>(p, &wg, stream);
     else rc = launch_halo<64, 9, 2, true>(p, &wg, stream);
-  } else if (wide && g.R == 3 && g_halo_pp) {
+  } else if (wide && g.R == 3 && sw::HALO_PP.get()) {
     // 128-channel 3x3 tiles: ping-pong K loop.  Same-call A/B against the lock-step loop (tools/conv_bench.py --pp, batch 256):
     // layer 2 fwd 79-82 -> 74 us, dgrad 75-82 -> 70-75; layer 3 64.5-65.7 -> 62.5 / 62.4-63.2 -> 60.0; layer 4 58.3 -> 55-56 /
     // 56.3 -> 52.7-53.7 (-4...-10 %).  The 1x3 layers of the signal encoder (3 steps per slice) measured 2 % slower: lock step.

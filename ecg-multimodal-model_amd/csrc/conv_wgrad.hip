@@ -795,10 +795,8 @@ int launch_wgrad_nt(WgradParams& p, dim3 grid, hipStream_t stream) {
 
 // two 4-wave groups per workgroup (see wgrad_kernel): bf16 filters with 3 or 9 taps, where the slabs are the larger part of
 // the launch's traffic.  ECGMM_WGRAD_GROUPS=1 keeps 256-thread workgroups (A/B switch).
-int g_wgrad_groups = -1;
 int wgrad_groups(int dtype, const ConvGeom& g) {
-  if (g_wgrad_groups < 0) g_wgrad_groups = env_off("ECGMM_WGRAD_GROUPS") ? 1 : 2;
-  return dtype == ECGMM_BF16 && g.R * g.S >= 3 ? g_wgrad_groups : 1;
+  return dtype == ECGMM_BF16 && g.R * g.S >= 3 && !sw::WGRAD_GROUPS.get() ? 2 : 1;
 }
 
 template <typename T>
@@ -816,18 +814,18 @@ int launch_wgrad(const ConvGeom& g, WgradParams& p, int nsplit, int groups, hipS
   ECG_FAIL(ECGMM_ERR_SHAPE, "conv wgrad: %dx%d filter unsupported (1, 3 or 9 taps)", g.R, g.S);
 }
 
-int g_wgrad_ring = -1;   // ECGMM_WGRAD_RING: 0 = wgrad_kernel everywhere, 1 = ring kernel where it is faster (default), 2 = wherever applicable
-
+// ECGMM_WGRAD_RING / ecgmm_conv_wgrad_ring_enable (same-process A/B, tools/conv_bench.py --ring): 0 = wgrad_kernel everywhere,
+// 1 = ring kernel where it is faster (default), 2 = wherever applicable
 bool wgrad_ring_ok(int dtype, const ConvGeom& g) {
-  if (g_wgrad_ring < 0) g_wgrad_ring = env_level("ECGMM_WGRAD_RING", 2, 1);
-  if (!g_wgrad_ring || dtype != ECGMM_BF16 || g.stride != 1 || g.S != 3 || g.pad_w != 1) return false;
+  const long level = sw::WGRAD_RING.get();
+  if (!level || dtype != ECGMM_BF16 || g.stride != 1 || g.S != 3 || g.pad_w != 1) return false;
   if (!((g.R == 3 && g.pad_h == 1) || (g.R == 1 && g.pad_h == 0))) return false;
   if (g.OH != g.H || g.OW != g.W || g.W < 4 || g.Cin % 64 || g.Cout % 64) return false;
   const int HL = g.pad_h * g.W + 1, HLa = (HL + 7) / 8 * 8;
   if (HL + HLa + 32 * RING_D + 32 > RING_ROWS) return false;
   const double M = (double)g.N * g.H * g.W;
   if (!(M * g.Cin * 2.0 < 2.0e9 && M * g.Cout * 2.0 < 2.0e9)) return false;
-  if (g_wgrad_ring == 2) return true;
+  if (level == 2) return true;
   // Same-call A/B at B = 256 with the 4 x 1 wave layout (profiles/r02_wgrad_ring_ab.txt, second table): the ring form is
   // 5-8 % faster on every 3x3 layer and on the 128/256-channel 1-D k = 3 layers, 12 % slower on the 64-channel 1-D layer
   // (its halo is a small share of a 1250-pixel row; wgrad_kernel's two-group form wins there).
@@ -864,7 +862,7 @@ int pick_nsplit(const ConvGeom& g, int kp, int groups) {
   // ResNet18 plan asks for 192 (96 of the 256 CUs) from batch 192 up; the image-only step at batch 128 (3.445 / 3.48 ms) and
   // the 12-lead signal encoder at batch 512 (2.95 / 3.13 ms) are faster at 256 and keep it (the caller's choice:
   // ecg_conv_wgrad_narrow's second argument).  ECGMM_WGRAD_WGS overrides.
-  static const int slots_env = (int)env_int("ECGMM_WGRAD_WGS", 0);
+  const int slots_env = (int)sw::WGRAD_WGS.get();
   const int slots = slots_env > 0 ? slots_env : (g_wgrad_narrow ? g_wgrad_narrow_slots : 512);
   int want = ceil_div(slots / groups, tiles);
   int ns = want < 1 ? 1 : want;
@@ -874,20 +872,6 @@ int pick_nsplit(const ConvGeom& g, int kp, int groups) {
 }
 
 }  // namespace
-
-// Ping-pong between the two wave groups of wgrad_ring_kernel<9, 2> (see its K loop): 1 = on, 0 = lock step (DEFAULT: measured
-// stand-alone at batch 256, layers 1-4: 86.2 / 85.3 / 81.4 / 90.6 us in lock step, 86.6 / 86.7 / 82.4 / 91.8 us with it -- this
-// kernel's K step is not limited by the two groups meeting at the matrix pipe).  Start-up value: ECGMM_WGRAD_PP.  Bit-identical results.
-static int g_wgrad_pp = -1;
-extern "C" int ecgmm_conv_wgrad_pingpong(int on) {
-  g_wgrad_pp = on != 0;
-  return 0;
-}
-// Runtime switch (same-process A/B, tools/conv_bench.py --ring): 0 = every weight gradient on wgrad_kernel.
-extern "C" int ecgmm_conv_wgrad_ring_enable(int on) {
-  g_wgrad_ring = on < 0 ? 0 : on > 2 ? 2 : on;
-  return 0;
-}
 
 // narrow = the caller runs its weight gradients on a side stream beside other work (see pick_nsplit)
 void ecg_conv_wgrad_narrow(bool narrow, int slots) { g_wgrad_narrow = narrow; g_wgrad_narrow_slots = slots > 0 ? slots : 256; }
@@ -935,8 +919,10 @@ int ecg_conv_wgrad(int dtype, const ConvGeom& g, const void* x, const void* dy, 
     q.HL = g.pad_h * g.W + 1;
     q.HLa = (q.HL + 7) / 8 * 8;
     q.mul_hw = p.mul_hw; q.sh_hw = p.sh_hw; q.mul_w = p.mul_w; q.sh_w = p.sh_w;
-    if (g_wgrad_pp < 0) g_wgrad_pp = env_off("ECGMM_WGRAD_PP");
-    q.pingpong = g_wgrad_pp;
+    // Ping-pong between the two wave groups of wgrad_ring_kernel<9, 2> (see its K loop): 1 = on, 0 = lock step (DEFAULT: measured
+    // stand-alone at batch 256, layers 1-4: 86.2 / 85.3 / 81.4 / 90.6 us in lock step, 86.6 / 86.7 / 82.4 / 91.8 us with it -- this
+    // kernel's K step is not limited by the two groups meeting at the matrix pipe).  ECGMM_WGRAD_PP.  Bit-identical results.
+    q.pingpong = (int)sw::WGRAD_PP.get();
     dim3 grid((g.Cout / 64) * (g.Cin / 64), ns);
     if (groups == 2) rc = g.R == 3 ? launch_wgrad_ring<9, 2>(q, grid, stream) : launch_wgrad_ring<3, 2>(q, grid, stream);
     else rc = g.R == 3 ? launch_wgrad_ring<9, 1>(q, grid, stream) : launch_wgrad_ring<3, 1>(q, grid, stream);

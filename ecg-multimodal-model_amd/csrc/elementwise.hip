@@ -1383,11 +1383,6 @@ int ecg_col_stats(int dtype, const void* x, long M, int C, float* partial, int* 
 }
 
 // Finalize folded into the consumer (kernels above; default): ECGMM_BN_FOLD=0 / ecgmm_bn_fold(0) restores the separate launches.
-static int g_bn_fold = -1;
-extern "C" int ecgmm_bn_fold(int on) {
-  g_bn_fold = on != 0;
-  return 0;
-}
 bool ecg_bn_fold_ok(int C, int rows) {
   // Mid-round 3 this measured 6.98 ms with the separate launches against 7.04 ms folded (256 workgroups each re-reading the same
   // 128-256 KB of partial rows cost what the ~5 us launch + its boundary cost the stream).  With the consumers' first loads issued
@@ -1397,22 +1392,15 @@ bool ecg_bn_fold_ok(int C, int rows) {
   // What the fold costs a workgroup is rows * 2 C / 1024 loads per thread in dependent trips of 8: 4 trips at C = 64 with 256
   // rows (the "~3 us" this comment used to quote for every layer), but 16 at C = 256 and 24-32 at C = 512 when it folds all C
   // channels, group after group -- hence the channel-sliced launch (bn_fold_slices), 8 trips at any C >= 128.
-  if (g_bn_fold < 0) g_bn_fold = env_on("ECGMM_BN_FOLD");
-  if (!g_bn_fold || rows < 1 || rows > 512 || C > 512) return false;
+  if (!sw::BN_FOLD.get() || rows < 1 || rows > 512 || C > 512) return false;
   return C >= 128 ? C % 128 == 0 : (C >= 16 && 1024 % C == 0);
 }
 
 // Channel-sliced launch of the folded passes (kernel side: ChanSlice).  NS = C / 128 slices for C >= 256, each workgroup a
 // (pixel chunk, slice) pair, at most 256 workgroups in all as before.  DEFAULT ON; ECGMM_BN_FOLD_SLICE=0 /
 // ecgmm_bn_fold_slice(0) restores the launch in which every workgroup walks whole rows and folds all C channels.
-static int g_bn_fold_slice = -1;
-extern "C" int ecgmm_bn_fold_slice(int on) {
-  g_bn_fold_slice = on != 0;
-  return 0;
-}
 static int bn_fold_slices(int C) {
-  if (g_bn_fold_slice < 0) g_bn_fold_slice = env_on("ECGMM_BN_FOLD_SLICE");
-  return g_bn_fold_slice && C >= 256 && C % 128 == 0 ? C / 128 : 1;
+  return sw::BN_FOLD_SLICE.get() && C >= 256 && C % 128 == 0 ? C / 128 : 1;
 }
 // grid of a folded pass: x = pixel chunks of `rows_per_wg` rows of (C / ns)-channel row segments each, y = the ns slices
 static dim3 bn_fold_grid(int dtype, long M, int C, int ns, int threads, int trips) {
@@ -1647,10 +1635,7 @@ int ecg_pool_bn_bwd_reduce(int dtype, const void* dp, const void* pooled, const 
 }
 
 // ECGMM_STEM_FUSE=0: the plans fall back to max-pool backward + full BatchNorm backward as separate passes (A/B switch)
-bool ecg_stem_fuse_on() {
-  static const bool on = env_on("ECGMM_STEM_FUSE");
-  return on;
-}
+bool ecg_stem_fuse_on() { return sw::STEM_FUSE.get() != 0; }
 
 int ecg_pool_bn_bwd(int dtype, const void* dp, const void* pooled, const unsigned char* idx, const void* y,
                     const float* coef, const float* gamma, float* dgamma, float* dbeta, void* dy, float* dbias, int N,

@@ -627,8 +627,7 @@ inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 }  // namespace
 
 bool ecg_se_mlp_fused_ok(int C, int CR) {
-  static const bool on = env_on("ECGMM_SE_MLP_FUSED");
-  return on && C >= 1 && C <= SE_MAXC && CR >= 1 && CR <= SE_MAXR;
+  return sw::SE_MLP_FUSED.get() && C >= 1 && C <= SE_MAXC && CR >= 1 && CR <= SE_MAXR;
 }
 int ecg_se_mlp_fwd(const float* m, const float* w1, const float* b1, const float* w2, const float* b2, float* h, float* g,
                    int N, int C, int CR, hipStream_t s) {
@@ -653,8 +652,7 @@ int ecg_se_mlp_bwd(const float* dg, const float* g, const float* h, const float*
 
 // Can the fused head serve this description?  (dims <= 512, classes <= 4, MFMA-tileable sizes)
 bool ecg_head_fused_ok(const int* dim, int B, int hidden, int num_classes) {
-  static const bool on = env_on("ECGMM_HEAD_FUSED");
-  if (!on) return false;
+  if (!sw::HEAD_FUSED.get()) return false;
   const int D = dim[0] + dim[1] + dim[2];
   for (int m = 0; m < 3; ++m)
     if (dim[m] < 2 || dim[m] > 512) return false;

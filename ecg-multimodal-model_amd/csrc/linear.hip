@@ -12,8 +12,7 @@ inline ConvGeom lin_geom(int B, int In, int Out) { return make_geom(B, 1, 1, In,
 // dense16_kernel (head_fused.hip): the implicit-GEMM kernel gives them 2-4 workgroups walking a serial K chain
 // (12-57 us a launch); independent waves take 5-14 us.  ECGMM_DENSE16=0: always the implicit-GEMM route.
 inline bool dense16_route(const void* a, const void* b, const void* c, int B, int In, int Out) {
-  static const bool on = env_on("ECGMM_DENSE16");
-  return on && ecg_dense16_ok(a, b, c, B, In, Out) && (double)B * In * Out <= 134217728.0;
+  return sw::DENSE16.get() && ecg_dense16_ok(a, b, c, B, In, Out) && (double)B * In * Out <= 134217728.0;
 }
 }  // namespace
 

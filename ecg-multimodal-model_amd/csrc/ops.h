@@ -1,6 +1,7 @@
 // Internal (C++) launch interface between the kernel files, the encoder plans and the C-ABI layer.
 #pragma once
 #include "common.h"
+#include "switches.h"
 
 // conv_igemm.hip
 int ecg_conv_stats_rows(long M);

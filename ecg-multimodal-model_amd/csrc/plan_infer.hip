@@ -105,11 +105,7 @@ void layout_ws18(const Net18& r, void* base, Ws18& w) {
 // The downsample convolution on a library-owned side stream beside conv1 (as the training forward does), or in line.
 // DEFAULT in line: see DESIGN.md (inference plans) for the same-call measurement.
 SideStream g_side_inf;
-int g_down_side = -1;
-bool down_side_on() {
-  if (g_down_side < 0) g_down_side = env_off("ECGMM_INFER_DOWN_SIDE");
-  return g_down_side != 0;
-}
+bool down_side_on() { return sw::INFER_DOWN_SIDE.get() != 0; }
 
 // ================================================================================================
 // ResNet1D_SE
@@ -246,11 +242,6 @@ extern "C" size_t ecgmm_resnet18_infer_workspace(const ecgmm_resnet18_desc* d) {
   Ws18 w;
   layout_ws18(r, nullptr, w);
   return w.bytes;
-}
-
-extern "C" int ecgmm_infer_down_side(int on) {
-  g_down_side = on != 0;
-  return 0;
 }
 
 extern "C" int ecgmm_resnet18_infer(const ecgmm_resnet18_desc* d, const float* image, const void* blob, size_t blob_bytes,

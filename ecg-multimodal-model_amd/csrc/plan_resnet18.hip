@@ -10,23 +10,16 @@
 #include "side_stream.h"
 
 namespace {
-// The 2-D stem by recompute (conv_stem_fused.hip): -1 = read ECGMM_STEM_RECOMPUTE.  DEFAULT OFF: measured in the step
+// The 2-D stem by recompute (conv_stem_fused.hip), ECGMM_STEM_RECOMPUTE / ecgmm_stem_recompute.  DEFAULT OFF: measured in the step
 // (same-call A/B, batch 256, round 3) it removes 1.6 GB of fabric traffic per step and is 0.2 ms SLOWER (7.12 -> 7.32 ms):
 // its kernels are VALU-issue-bound (~2600 instructions per 128-pixel tile for 96 MFMAs), not byte-bound -- stand-alone
 // forward 418 -> 396 us, backward 401 -> 584 us.  Kept as a tested option (memory: -1.2 GB of workspace at batch 256).
-int g_stem_recompute = -1;
 bool stem_recompute(int dtype) {
-  if (g_stem_recompute < 0) g_stem_recompute = env_off("ECGMM_STEM_RECOMPUTE");
-  return g_stem_recompute != 0 && ecg_stem_fused_ok(dtype, 3, 7);
+  return sw::STEM_RECOMPUTE.get() && ecg_stem_fused_ok(dtype, 3, 7);
 }
 // bn2's backward takes the block's ReLU mask from one bit per element written by the forward activation pass instead of re-reading
 // the activated tensor (ECGMM_RELU_BITS=0: re-read it).  Read once per process: forward and backward must agree.
-bool relu_bits_on() {
-  static const bool on = env_on("ECGMM_RELU_BITS");
-  return on;
-}
-constexpr long FUSE_NEVER = 1L << 40;
-long g_fuse_min_m = -1;  // pixel-count threshold of the fused BatchNorm-backward reductions (-1: read ECGMM_BN_FUSE_MIN_M)
+bool relu_bits_on() { return sw::RELU_BITS.get() != 0; }
 
 int build(const ecgmm_resnet18_desc* d, Net18& r) {
   ECG_TRY(net18_static(d, r, "resnet18"));
@@ -264,8 +257,7 @@ extern "C" int ecgmm_resnet18_forward(const ecgmm_resnet18_desc* d, const float*
   const int dt = r.d.dtype, N = r.d.N;
   const int stats_rows = r.d.training ? 1 : 0;
   ECG_TRY(side_init());
-  static const bool down_side_on = env_on("ECGMM_DOWN_SIDE");
-  const bool side_fwd = g_side.enabled && down_side_on;
+  const bool side_fwd = g_side.enabled && sw::DOWN_SIDE.get();
 
   ecg_tl_mark(100, s);
   // ---- every conv weight -> compute-dtype operand layouts, one launch.  (Running it on the side stream underneath
@@ -416,11 +408,7 @@ static int r18_backward(const ecgmm_resnet18_desc* d, const float* image, const 
       // same-call A/B of the whole step, fused on layer 1 / never fused = 6.84, 6.88 / 6.75, 6.75 ms.
       // ECGMM_BN_FUSE_MIN_M (ecgmm_bn_fuse_min_pixels) sets the pixel-count threshold: 400000 = round 2's choice (layer 1 at
       // batch 256), 0 = fuse wherever possible.
-      static const bool fuse_on = env_on("ECGMM_BN_FUSE");
-      static const bool fold_on = env_on("ECGMM_DOWN_FOLD");
-      if (g_fuse_min_m < 0) g_fuse_min_m = env_int("ECGMM_BN_FUSE_MIN_M", FUSE_NEVER);
-      const long fuse_min_m = g_fuse_min_m;
-      const bool fuse_here = train && fuse_on && M >= fuse_min_m;   // (the fused reductions are the training form's)
+      const bool fuse_here = train && sw::BN_FUSE.get() && M >= sw::BN_FUSE_MIN_M.get();   // (the fused reductions are the training form's)
       if (fuse_here && i + 1 < 8 && !r.blk[i + 1].down) {
         const Blk18& kn = r.blk[i + 1];
         const ConvGeom gn = kn.conv1_geom(N);
@@ -476,7 +464,7 @@ static int r18_backward(const ecgmm_resnet18_desc* d, const float* image, const 
         // no [N][H][W][Cin] temporary written and re-read as addend
         ConvEpi ed = {};
         ed.src2 = dydb; ed.wpk2 = b.wdd;
-        if (!fold_on) ed.src2 = nullptr;
+        if (!sw::DOWN_FOLD.get()) ed.src2 = nullptr;
         if (ed.src2) {
           ECG_TRY(ecg_conv_igemm(dt, 1, g1, dy1b, b.w1d, din, nullptr, nullptr, nullptr, 0, s, &ed));
         }
@@ -570,15 +558,3 @@ extern "C" int ecgmm_resnet18_gradcam(const ecgmm_resnet18_desc* d, const float*
                      s);
 }
 
-// The image encoder's stem by recompute (conv_stem_fused.hip): 1 = on (bf16 only), 0 = the two-pass route with the
-// full-resolution conv output in memory (default: faster, see above).  Start-up value: ECGMM_STEM_RECOMPUTE.  Changes the workspace layouts: set it
-// between steps, never between a forward and its backward.
-extern "C" int ecgmm_stem_recompute(int on) {
-  g_stem_recompute = on != 0;
-  return 0;
-}
-
-extern "C" int ecgmm_bn_fuse_min_pixels(int64_t m) {
-  g_fuse_min_m = m < 0 ? FUSE_NEVER : (long)m;
-  return 0;
-}

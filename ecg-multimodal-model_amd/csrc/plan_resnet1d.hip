@@ -309,8 +309,7 @@ static int r1d_backward(const ecgmm_resnet1d_desc* d, const float* signal, const
       // out = relu(bn2(y2) * g + identity); gate gradient first.  Merged form (default): this pass also stores the masked
       // gradient dz and the per-sample sums the BatchNorm-backward reduction needs, so bn2's backward below is finalize +
       // apply only -- one read of (dcur, out, y2) less per block.  ECGMM_SE_MERGE=0: the two-pass form.
-      static const bool se_merge_on = env_on("ECGMM_SE_MERGE");
-      const bool se_merge = se_merge_on && train;   // (the merged pass feeds the training form's reduction)
+      const bool se_merge = sw::SE_MERGE.get() && train;   // (the merged pass feeds the training form's reduction)
       if (se_merge) {
         ECG_TRY(ecg_se_gate_bn(dt, dcur, b.out, b.y2, b.coef2, q.dz, q.dg, q.sa1, q.sa2, q.sa3, N, k.lout, k.cout, s));
       } else {
@@ -365,9 +364,8 @@ static int r1d_backward(const ecgmm_resnet1d_desc* d, const float* signal, const
           ECG_TRY(ecg_conv_wgrad(dt, gd, in, q.dyd, G(grads, p + T1_DOWN_W), 0, q.wg_ws, q.wg_bytes, wst));
           if (side) g_side1.doneC = g_side1.mark();
         }
-        static const bool fold_on = env_on("ECGMM_DOWN_FOLD");
         ConvEpi ed = {};   // downsample branch folded into the stride-2 dgrad (see plan_resnet18.hip)
-        if (fold_on) { ed.src2 = q.dyd; ed.wpk2 = b.wdd; }
+        if (sw::DOWN_FOLD.get()) { ed.src2 = q.dyd; ed.wpk2 = b.wdd; }
         if (ed.src2) ECG_TRY(ecg_conv_igemm(dt, 1, g1, q.dy1, b.w1d, din, nullptr, nullptr, nullptr, 0, s, &ed));
         if (!ed.src2_done) {
           ECG_TRY(ecg_conv_igemm(dt, 1, gd, q.dyd, b.wdd, q.dtmp, nullptr, nullptr, nullptr, 0, s));

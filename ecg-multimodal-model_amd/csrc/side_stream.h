@@ -19,7 +19,7 @@ struct SideStream {
 
   int init() {
     if (ok) return 0;
-    enabled = env_on("ECGMM_SIDE_WGRAD");
+    enabled = sw::SIDE_WGRAD.get() != 0;
     if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess)
       ECG_FAIL(ECGMM_ERR_LAUNCH, "side stream creation failed");
     for (int i = 0; i < 64; ++i)

@@ -52,6 +52,9 @@ P = C.POINTER
 SIGNATURES = {
     "ecgmm_version": (i32, []),
     "ecgmm_last_error": (C.c_char_p, []),
+    "ecgmm_switch_name": (C.c_char_p, [i32]),
+    "ecgmm_switch_get": (i32, [C.c_char_p, P(i64)]),
+    "ecgmm_switch_set": (i32, [C.c_char_p, i64]),
     "ecgmm_resnet18_fwd_workspace": (sz, [P(ResNet18Desc)]),
     "ecgmm_resnet18_bwd_workspace": (sz, [P(ResNet18Desc)]),
     "ecgmm_resnet18_forward": (i32, [P(ResNet18Desc), vp, P(vp), P(vp), vp, vp, sz, vp]),
@@ -224,7 +227,9 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  "ecgmm_conv5_in1_bwd_weight", "ecgmm_conv5_bwd_weight_workspace", "ecgmm_conv5_bwd_weight",
                  "ecgmm_bnrelu_maxpool2", "ecgmm_pool2_bn_bwd_workspace", "ecgmm_pool2_bn_bwd",
                  "ecgmm_crnn_front_fwd_workspace", "ecgmm_crnn_front_bwd_workspace", "ecgmm_crnn_front_forward",
-                 "ecgmm_crnn_front_backward")
+                 "ecgmm_crnn_front_backward",
+                 # the switch table by name (csrc/switches.h)
+                 "ecgmm_switch_name", "ecgmm_switch_get", "ecgmm_switch_set")
 
 _lib = None
 

@@ -39,6 +39,15 @@ enum {
 int ecgmm_version(void);
 const char* ecgmm_last_error(void);
 
+/* The ECGMM_* environment switches the library reads (one table: csrc/switches.h; list: INTEGRATION.md section 5), by
+ * name.  ecgmm_switch_name(i): the i-th switch's environment variable name, NULL past the end.  ecgmm_switch_get: the
+ * value in effect (reads the environment if nothing has yet).  ecgmm_switch_set: what the named setter below does, with
+ * the same clamp; ECGMM_ERR_SHAPE for an unknown name and for a switch that is read once at start-up.  ECGMM_SIDE_WGRAD
+ * is refused too: after start-up it is each plan's own state, switched with ecgmm_side_wgrad(), which initialises the GPU. */
+const char* ecgmm_switch_name(int i);
+int ecgmm_switch_get(const char* env_name, int64_t* value);
+int ecgmm_switch_set(const char* env_name, int64_t value);
+
 /* ---------------------------------------------------------------------------------------------
  * Encoder plans (the product path: one call = one encoder forward / backward)
  * ------------------------------------------------------------------------------------------- */

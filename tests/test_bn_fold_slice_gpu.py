@@ -14,8 +14,6 @@ rows_per_sample = 7, the residual carries rcoef, bf16 writes and reads the ReLU 
 (c) num_batches_tracked advances by exactly 1 per call.
 Every output buffer is NaN-filled (0xAA for the bit mask) before each call.
 """
-import os
-
 import pytest
 import torch
 
@@ -23,12 +21,10 @@ from ecgmm.hip import lib as L
 from ecgmm.hip.functional import ptr, stream
 
 from . import f64check as F64
-from .util import DEV, TDT, dev
+from .util import DEV, TDT, dev, switches
 
 pytestmark = pytest.mark.gpu
 NAN = float("nan")
-FOLD_DEFAULT = 0 if os.environ.get("ECGMM_BN_FOLD", "1") == "0" else 1
-SLICE_DEFAULT = 0 if os.environ.get("ECGMM_BN_FOLD_SLICE", "1") == "0" else 1
 TAIL = 64
 RPS = 7
 
@@ -80,18 +76,9 @@ def split_rows(a, b, rows):
     return torch.cat([part.float(), nanbuf((TAIL, 2, C))]).contiguous()
 
 
-class Switches:
-    """fold on, slicing as asked; both back to what the library started with"""
-    def __init__(self, lib, sliced):
-        self.lib, self.sliced = lib, sliced
-
-    def __enter__(self):
-        self.lib.ecgmm_bn_fold(1)
-        self.lib.ecgmm_bn_fold_slice(self.sliced)
-
-    def __exit__(self, *a):
-        self.lib.ecgmm_bn_fold(FOLD_DEFAULT)
-        self.lib.ecgmm_bn_fold_slice(SLICE_DEFAULT)
+def fold_sliced(lib, sliced):
+    """fold on, slicing as asked; both back to what ecgmm_switch_get returned before"""
+    return switches(lib, ECGMM_BN_FOLD=1, ECGMM_BN_FOLD_SLICE=sliced)
 
 
 @pytest.mark.parametrize("C,M,rows,dt", PARAMS)
@@ -107,7 +94,7 @@ def test_folded_bn_act_sliced(C, M, rows, dt):
         nbt = torch.full((), 6, dtype=torch.int64, device=DEV)
         out = nanbuf(M * C, TDT[dt])
         bits = torch.full((M * C // 8,), 0xAA, dtype=torch.uint8, device=DEV) if bf16 else None
-        with Switches(lib, sliced):
+        with fold_sliced(lib, sliced):
             for n in (7, 8):
                 if n == 8:                      # (the second call starts from the first call's running statistics)
                     rm1, rv1 = rm.clone(), rv.clone()
@@ -167,7 +154,7 @@ def test_folded_bn_bwd_sliced(C, M, rows, dt):
         scratch = nanbuf(nscratch)
         dgam, dbet = nanbuf(C), nanbuf(C)
         dy, dz = nanbuf(M * C, TDT[dt]), nanbuf(M * C, TDT[dt])
-        with Switches(lib, sliced):
+        with fold_sliced(lib, sliced):
             if form == "gated":       # mask tensor + dz_out, gate and addc with rows_per_sample = 7
                 L.check(lib.ecgmm_bn_bwd(dt, ptr(g["dout_t"]), ptr(maskt), ptr(g["gate"]), ptr(g["addc"]), g["rps"], ptr(g["y_t"]),
                                          ptr(coef), ptr(g["gamma"]), ptr(dgam), ptr(dbet), ptr(dy), ptr(dz), None, M, C, ptr(scratch), stream()))

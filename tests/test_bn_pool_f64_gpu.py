@@ -14,7 +14,6 @@ bnrelu_maxpool 1 (bf16) / < 0.4 (fp32), maxpool_relu_bwd 1 (bf16) / 0 (fp32: exa
 large-mean coef 0.046.  No kernel broke a bound.
 """
 import math
-import os
 
 import pytest
 import torch
@@ -23,11 +22,10 @@ from ecgmm.hip import lib as L
 from ecgmm.hip.functional import ptr, stream
 
 from . import f64check as F64
-from .util import DEV, TDT, dev
+from .util import DEV, TDT, dev, switches
 
 pytestmark = pytest.mark.gpu
 NAN = float("nan")
-FOLD_DEFAULT = 0 if os.environ.get("ECGMM_BN_FOLD", "1") == "0" else 1      # what the library starts with
 TAIL = 64                       # spare rows every partial-row buffer carries
 
 
@@ -164,8 +162,7 @@ def test_batchnorm_forward_against_float64(case, dt):
         worst(F64.check_stored(out.view(M, C), want, A, F64.K_ACT, bf16, "bn_act " + name))
     # finalize folded into the consumer, from the real statistics rows: against coefficients derived from the same rows in
     # float64, their bound carried through (rows > 512 or an unfoldable C: the two-launch route, same contract)
-    try:
-        lib.ecgmm_bn_fold(1)
+    with switches(lib, ECGMM_BN_FOLD=1):
         partial = torch.cat([stat_rows, nanbuf((TAIL, 2, C))]).contiguous()
         coef2, rm2, rv2 = nanbuf((4, C)), torch.zeros(C, device=DEV), torch.ones(C, device=DEV)
         nbt = torch.zeros((), dtype=torch.int64, device=DEV)
@@ -174,8 +171,6 @@ def test_batchnorm_forward_against_float64(case, dt):
                                            ptr(rv2), ptr(nbt), 0.1, 1e-5, ptr(coef2), ptr(g["res_t"]), None,
                                            ptr(g["gate"]) if rps else None, rps or 1, 1, ptr(out), M, C, stream()))
         torch.cuda.synchronize()
-    finally:
-        lib.ecgmm_bn_fold(FOLD_DEFAULT)
     assert int(nbt) == 1 and torch.isfinite(out.float()).all()
     worst(F64.check_coef(coef2, cref, rm2, rv2, name="bn_act_from_rows coef"))
     want, A = F64.bn_act_ref(g["y"], cref.val["scale"], cref.val["shift"], g["res"], None, None, gate, True)
@@ -222,13 +217,10 @@ def test_batchnorm_backward_against_float64(case, dt):
             a.update(mask=ptr(maskt), dz=ptr(dz), gate=ptr(g["gate"]), addc=ptr(g["addc"]), dbias=ptr(dbias))
         else:
             a.update(mask=ptr(g["y_t"]), dy=None)
-        try:
-            lib.ecgmm_bn_fold(fold)
+        with switches(lib, ECGMM_BN_FOLD=fold):
             L.check(lib.ecgmm_bn_bwd(dt, ptr(g["dout_t"]), a["mask"], a["gate"], a["addc"], rps or M, ptr(g["y_t"]), ptr(coef),
                                      ptr(g["gamma"]), ptr(dgam), ptr(dbet), a["dy"], a["dz"], a["dbias"], M, C, ptr(scratch), stream()))
             torch.cuda.synchronize()
-        finally:
-            lib.ecgmm_bn_fold(FOLD_DEFAULT)
         rowsbuf = scratch[:(brows + TAIL) * 2 * C].view(brows + TAIL, -1)
         assert torch.isnan(rowsbuf[brows:]).all()                                        # nothing beyond the rows the library reports
         assert torch.isfinite(dgam).all() and torch.isfinite(dbet).all()

@@ -57,7 +57,7 @@ from ecgmm.hip import lib as L
 from ecgmm.hip.functional import ptr, stream
 
 from . import f64check as F64
-from .util import DEV
+from .util import DEV, switches
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -359,13 +359,10 @@ def test_fused_batchnorm_reduction_at_full_size(layer):
     ref =F64.conv_ref64(torch.zeros(256, c, hw, hw, device=DEV), w, dy, 1, (1, 1))
     dyg, addg = _nhwc(dy), _nhwc(add)
     _, wd = _pack(w)
-    try:
-        lib.ecgmm_bn_fuse_min_pixels(0)
+    with switches(lib, ECGMM_BN_FUSE_MIN_M=0):
         tag = "bnred B256 %dx%dx%d" % (hw, hw, c)
         _check_bnred(tag + " bn1", g, ref, None, _bnred(g, dyg, wd, 310, False))
         _check_bnred(tag + " bn2+addend", g, ref, add, _bnred(g, dyg, wd, 320, True, addg))
-    finally:
-        lib.ecgmm_bn_fuse_min_pixels(-1)
 
 
 # ------------------------------------------------------------------------------------- part 2: the persistent loop
@@ -416,11 +413,8 @@ def test_persistent_halo_loop(case, cap):
     ref = F64.conv_ref64(x, w, dy, 1, (g.ph, 1), bias=b)
     wf, wd = _pack(w)
     tag = "halo %s cap %d" % (case, cap)
-    try:
-        lib.ecgmm_conv_halo_cus(cap)
-        lib.ecgmm_conv_halo_w4(tog.get("w4", 0))
-        lib.ecgmm_conv_halo_stream(tog.get("stream", 1))
-        lib.ecgmm_conv_halo_pingpong(tog.get("pp", 1))
+    with switches(lib, ECGMM_HALO_CUS=cap, ECGMM_HALO_W4=tog.get("w4", 0), ECGMM_HALO_STREAM=tog.get("stream", 1),
+                  ECGMM_HALO_PP=tog.get("pp", 1)):
         if op.startswith("fwd"):
             y, rows, tail = fwd(g, _nhwc(x), wf, b, wgrows=True)
             ntn = 1 if Cout <= 64 else Cout // 128
@@ -438,8 +432,3 @@ def test_persistent_halo_loop(case, cap):
             sep = op == "bnred_sep"
             a = add if sep else None
             _check_bnred(tag, g, ref, a, _bnred(g, _nhwc(dy), wd, seed + 5, sep, _nhwc(a) if sep else None))
-    finally:
-        lib.ecgmm_conv_halo_cus(0)
-        lib.ecgmm_conv_halo_w4(0)
-        lib.ecgmm_conv_halo_stream(1)
-        lib.ecgmm_conv_halo_pingpong(1)

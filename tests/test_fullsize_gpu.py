@@ -15,6 +15,8 @@ from ecgmm.multimodal_paper_modal_balance import ECGMultimodalModel
 from ecgmm.optim import FusedAdam
 from ecgmm.parallel import flatten
 
+from .util import switch_get, switches
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 B = 256
@@ -54,7 +56,7 @@ def test_full_size_step_is_bitwise_deterministic_and_schedule_independent():
         HF.manual_seed(123)                       # same dropout masks in every run
         runs.append(_one_step(m, batch))
         del m
-    L.lib().ecgmm_side_wgrad(1)
+    L.check(L.lib().ecgmm_side_wgrad(switch_get(L.lib(), "ECGMM_SIDE_WGRAD")))   # back to what the process started with
     (l0, y0, g0), (l1, y1, g1), (l2, y2, g2) = runs
     assert l0 == l1 == l2 and torch.equal(y0, y1) and torch.equal(y0, y2)
     for k in g0:                                  # run to run: identical bits
@@ -136,7 +138,7 @@ def test_pingpong_conv_loop_is_race_free_under_concurrent_load():
     big_a = torch.empty(256 << 20, device=DEV, dtype=torch.uint8)
     big_b = torch.empty_like(big_a)
     g = torch.Generator(device=DEV).manual_seed(5)
-    try:
+    with switches(lib, ECGMM_HALO_PP=1):   # (run() sets it; the value from before the test comes back on exit)
         for (H, W, Cn) in ((28, 28, 128), (14, 14, 256), (7, 7, 512)):
             d = L.ConvDesc(B, H, W, Cn, Cn, 3, 3, 1, 1, 1)
             n = B * H * W * Cn
@@ -160,8 +162,6 @@ def test_pingpong_conv_loop_is_race_free_under_concurrent_load():
                     y = run(1)
                     torch.cuda.synchronize()
                     assert torch.equal(y.view(torch.int16), ref.view(torch.int16)), (H, Cn, fn.__name__, it)
-    finally:
-        lib.ecgmm_conv_halo_pingpong(1)
 
 
 def test_stream_form_of_the_layer1_tiles_is_race_free_under_concurrent_load():
@@ -181,7 +181,7 @@ def test_stream_form_of_the_layer1_tiles_is_race_free_under_concurrent_load():
     x = torch.randn(n, device=DEV, generator=g).to(torch.bfloat16)
     w = (torch.randn(64 * 64 * 9, device=DEV, generator=g) * 0.05).to(torch.bfloat16)
     add = torch.randn(n, device=DEV, generator=g).to(torch.bfloat16)      # residual addend of a block's conv1 input gradient
-    try:
+    with switches(lib, ECGMM_HALO_STREAM=1):   # (run() sets it; the value from before the test comes back on exit)
         for kind in ("fwd", "dgrad", "dgrad+addend"):
             def run(on):
                 lib.ecgmm_conv_halo_stream(on)
@@ -204,5 +204,3 @@ def test_stream_form_of_the_layer1_tiles_is_race_free_under_concurrent_load():
                 torch.cuda.synchronize()
                 assert torch.equal(y.view(torch.int16), ref.view(torch.int16)), (kind, it)
                 assert torch.equal(st, ref_st), (kind, it)
-    finally:
-        lib.ecgmm_conv_halo_stream(1)

@@ -11,7 +11,7 @@ from ecgmm.multimodal_paper_modal_balance import ResNet1D_SE
 from oracle import fill, ref_models as O
 
 from .f64check import KAPPA, conv_ref64
-from .util import DEV, bf16_round, dev, rel_err, to_nhwc
+from .util import DEV, bf16_round, dev, rel_err, switches, to_nhwc
 
 pytestmark = pytest.mark.gpu
 
@@ -164,14 +164,11 @@ def test_second_backward_through_training_forward_fails_clearly():
 def test_stem_recompute_refuses_input_gradient():
     lib = L.lib()
     _ref, net = _pair("r18", R18_SHAPES[0], "bf16")   # (the recomputing stem exists for bf16 only)
-    lib.ecgmm_stem_recompute(1)
-    try:
+    with switches(lib, ECGMM_STEM_RECOMPUTE=1):
         xd = dev(_input("r18", R18_SHAPES[0])).requires_grad_(True)
         f = net.train()(xd)
         with pytest.raises(RuntimeError, match="ecgmm_stem_recompute"):
             f.sum().backward()
-    finally:
-        lib.ecgmm_stem_recompute(0)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

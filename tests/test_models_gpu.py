@@ -12,7 +12,7 @@ from ecgmm.multimodal_paper_modal_balance import ECGMultimodalModel, ResNet1D_SE
 from ecgmm.optim import FusedAdam
 from oracle import fill, ref_models as O
 
-from .util import DEV, dev, rel_err
+from .util import DEV, dev, rel_err, switches
 
 pytestmark = pytest.mark.gpu
 
@@ -278,12 +278,9 @@ def conv_kernel_choice(request):
     everywhere: the halo conv kernel, the ring wgrad kernel and the fused BatchNorm-backward reductions wherever applicable,
     and the stem by recompute (csrc/conv_stem_fused.hip: an option, off by default)"""
     from ecgmm.hip import lib as L
-    if request.param == "everywhere":
-        L.lib().ecgmm_conv_halo_enable(2); L.lib().ecgmm_conv_wgrad_ring_enable(2); L.lib().ecgmm_bn_fuse_min_pixels(0)
-        L.lib().ecgmm_stem_recompute(1)
-    yield request.param
-    L.lib().ecgmm_conv_halo_enable(1); L.lib().ecgmm_conv_wgrad_ring_enable(1); L.lib().ecgmm_bn_fuse_min_pixels(-1)
-    L.lib().ecgmm_stem_recompute(0)
+    everywhere = dict(ECGMM_CONV_HALO=2, ECGMM_WGRAD_RING=2, ECGMM_BN_FUSE_MIN_M=0, ECGMM_STEM_RECOMPUTE=1)
+    with switches(L.lib(), **(everywhere if request.param == "everywhere" else {})):
+        yield request.param
 
 
 @pytest.mark.parametrize("shape", [(4, 3, 64, 64), (8, 3, 128, 96)])

@@ -12,7 +12,7 @@ from ecgmm.hip import lib as L
 from ecgmm.hip.functional import ptr, stream
 from oracle import fill
 
-from .util import DEV, TDT, bf16_round, conv_desc, dev, from_nhwc, pack_weight, rel_err, to_nhwc
+from .util import DEV, TDT, bf16_round, conv_desc, dev, from_nhwc, pack_weight, rel_err, switch_get, switches, to_nhwc
 
 pytestmark = pytest.mark.gpu
 
@@ -50,13 +50,8 @@ def _conv_ref(x, w, b, stride, ph, pw):
 @pytest.fixture
 def halo_everywhere():
     """conv_halo.hip / wgrad_ring_kernel for every shape they can serve (the defaults only pick them where faster)"""
-    L.lib().ecgmm_conv_halo_enable(2)
-    L.lib().ecgmm_conv_wgrad_ring_enable(2)
-    L.lib().ecgmm_bn_fuse_min_pixels(0)
-    yield
-    L.lib().ecgmm_bn_fuse_min_pixels(-1)
-    L.lib().ecgmm_conv_halo_enable(1)
-    L.lib().ecgmm_conv_wgrad_ring_enable(1)
+    with switches(L.lib(), ECGMM_CONV_HALO=2, ECGMM_WGRAD_RING=2, ECGMM_BN_FUSE_MIN_M=0):
+        yield
 
 
 @pytest.mark.parametrize("case", CONV_CASES)
@@ -161,9 +156,8 @@ def test_conv_halo_kernel_agrees_with_the_general_kernel():
     wf, wd = pack_weight(bf16_round(fill.hash_tensor((Cout, Cin, 3, 3), 42, 0.05)), L.BF16)
     M = N * H * W
     outs = []
-    try:
-        for on in (2, 0):
-            lib.ecgmm_conv_halo_enable(on)
+    for on in (2, 0):
+        with switches(lib, ECGMM_CONV_HALO=on):
             y = torch.empty(M * Cout, device=DEV, dtype=torch.bfloat16)
             dx = torch.empty(M * Cin, device=DEV, dtype=torch.bfloat16)
             st = torch.zeros(lib.ecgmm_conv_stats_rows(M), 2, Cout, device=DEV)
@@ -171,8 +165,6 @@ def test_conv_halo_kernel_agrees_with_the_general_kernel():
             L.check(lib.ecgmm_conv_bwd_data(L.BF16, C.byref(d), ptr(y), ptr(wd), ptr(x), ptr(dx), stream()))
             torch.cuda.synchronize()
             outs.append((y.float().cpu(), dx.float().cpu(), st.sum(0).cpu()))
-    finally:
-        lib.ecgmm_conv_halo_enable(1)
     for a, b in zip(*outs):
         assert rel_err(a, b) < 3e-3          # bf16 output rounding of differently ordered fp32 sums
     assert (outs[0][0] >= 0).all()           # act = ReLU in the epilogue
@@ -230,12 +222,9 @@ def test_dgrad_with_fused_batchnorm_backward_reduction(case, sep_mask):
         torch.cuda.synchronize()
         return from_nhwc(dyo, dt, y.shape), dgam.cpu(), dbet.cpu()
 
-    try:
-        lib.ecgmm_conv_halo_enable(2)
+    with switches(lib, ECGMM_CONV_HALO=2):
         a = run(True)
         b = run(False)
-    finally:
-        lib.ecgmm_conv_halo_enable(1)
     for u, v in zip(a, b):
         assert rel_err(u, v) < 2e-3
     # and against torch autograd (bf16 storage of the conv gradient is part of both GPU paths: loose tolerance)
@@ -288,15 +277,10 @@ def test_fused_reduction_row_count_follows_the_halo_cu_cap(cap):
         torch.cuda.synchronize()
         return n.value, dx.clone(), dyo.float().cpu(), dgam.cpu(), dbet.cpu()
 
-    try:
-        lib.ecgmm_conv_halo_enable(2)
-        lib.ecgmm_conv_halo_cus(0)
+    with switches(lib, ECGMM_CONV_HALO=2, ECGMM_HALO_CUS=0):
         full = run()
         lib.ecgmm_conv_halo_cus(cap)
         capped = run()
-    finally:
-        lib.ecgmm_conv_halo_cus(0)
-        lib.ecgmm_conv_halo_enable(1)
     assert capped[0] <= full[0] and (cap == 0 or capped[0] <= 2 * cap)   # (64-channel tiles: up to two workgroups per CU)
     assert torch.equal(capped[1], full[1])                                  # the gradient itself: pure scheduling
     for u, v in zip(capped[2:], full[2:]):
@@ -325,8 +309,6 @@ def test_finalize_folded_into_the_consumer_pass(dt, shape):
     part = (wgt[:, :, None] * col[None]).contiguous()                                            # [rows][2][C]
     part = torch.cat([part, torch.zeros(64, 2, Cn, device=DEV)])
 
-    lib.ecgmm_bn_fold(1)       # (ecgmm_bn_act_from_rows falls back to two launches when the fold is switched off)
-
     def fwd(folded):
         rm, rv, nbt = torch.zeros(Cn, device=DEV), torch.ones(Cn, device=DEV), torch.zeros((), dtype=torch.int64, device=DEV)
         coef = torch.full((4, Cn), float("nan"), device=DEV)
@@ -341,7 +323,8 @@ def test_finalize_folded_into_the_consumer_pass(dt, shape):
         torch.cuda.synchronize()
         return out.float().cpu(), coef.cpu(), rm.cpu(), rv.cpu(), int(nbt)
 
-    a, b = fwd(True), fwd(False)
+    with switches(lib, ECGMM_BN_FOLD=1):   # (ecgmm_bn_act_from_rows falls back to two launches when the fold is switched off)
+        a, b = fwd(True), fwd(False)
     assert a[4] == b[4] == 1
     for u, v in zip(a[1:4], b[1:4]):
         assert torch.allclose(u, v, rtol=1e-6, atol=1e-7), float((u - v).abs().max())
@@ -363,10 +346,8 @@ def test_finalize_folded_into_the_consumer_pass(dt, shape):
         torch.cuda.synchronize()
         return dx.float().cpu(), dgam.cpu(), dbet.cpu()
 
-    try:
+    with switches(lib, ECGMM_BN_FOLD=1):   # (bwd sets it; the value from before the test comes back on exit)
         c, d = bwd(1), bwd(0)
-    finally:
-        lib.ecgmm_bn_fold(0)
     assert torch.equal(c[1], d[1]) or torch.allclose(c[1], d[1], rtol=1e-6, atol=1e-6)
     assert torch.allclose(c[2], d[2], rtol=1e-6, atol=1e-6)
     assert rel_err(c[0], d[0]) < (1e-6 if dt == L.F32 else 2e-3)
@@ -385,8 +366,7 @@ def test_conv_forward_statistics_one_row_per_workgroup(case):
     x = to_nhwc(bf16_round(fill.hash_tensor((N, Cin, H, W), 81)), dt)
     wf, _ = pack_weight(bf16_round(fill.hash_tensor((Cout, Cin, R, 3), 82, 0.05)), dt)
     rows = lib.ecgmm_conv_stats_rows(M)
-    try:
-        lib.ecgmm_conv_halo_enable(2)
+    with switches(lib, ECGMM_CONV_HALO=2):
         y0 = torch.empty(M * Cout, device=DEV, dtype=torch.bfloat16)
         s0 = torch.zeros(rows + 64, 2, Cout, device=DEV)
         L.check(lib.ecgmm_conv_fwd(dt, C.byref(d), ptr(x), ptr(wf), None, ptr(y0), ptr(s0), 0, stream()))
@@ -395,8 +375,6 @@ def test_conv_forward_statistics_one_row_per_workgroup(case):
         n = C.c_int(0)
         L.check(lib.ecgmm_conv_fwd_wgrows(dt, C.byref(d), ptr(x), ptr(wf), None, ptr(y1), ptr(s1), C.byref(n), 0, stream()))
         torch.cuda.synchronize()
-    finally:
-        lib.ecgmm_conv_halo_enable(1)
     assert 1 <= n.value <= 512 and torch.isfinite(s1[:n.value]).all()
     assert torch.equal(y0.view(torch.int16), y1.view(torch.int16))
     a, b = s0[:rows].sum(0), s1[:n.value].sum(0)
@@ -785,7 +763,6 @@ def test_stream_form_of_64_channel_halo_tiles_matches_tile_at_a_time(B, H, W, ca
     tile counts that are not a multiple of the workgroup count, bias + ReLU.  Output, statistics rows and input gradient must be
     bit-identical between the two forms."""
     lib = L.lib()
-    lib.ecgmm_conv_halo_enable(2)
     d = L.ConvDesc(B, H, W, 64, 64, 3, 3, 1, 1, 1)
     g = torch.Generator(device=DEV).manual_seed(B * 131 + H)
     n = B * H * W * 64
@@ -794,8 +771,7 @@ def test_stream_form_of_64_channel_halo_tiles_matches_tile_at_a_time(B, H, W, ca
     bias = torch.randn(64, device=DEV, generator=g) if use_bias else None
     add = torch.randn(n, device=DEV, generator=g).to(torch.bfloat16)
     res = {}
-    try:
-        lib.ecgmm_conv_halo_cus(cap)
+    with switches(lib, ECGMM_CONV_HALO=2, ECGMM_HALO_CUS=cap, ECGMM_HALO_STREAM=1):
         for on in (0, 1):
             lib.ecgmm_conv_halo_stream(on)
             y = torch.full((n,), 7.0, device=DEV).to(torch.bfloat16)
@@ -810,10 +786,6 @@ def test_stream_form_of_64_channel_halo_tiles_matches_tile_at_a_time(B, H, W, ca
             L.check(lib.ecgmm_conv_bwd_data(L.BF16, C.byref(d), ptr(x), ptr(w), ptr(add), ptr(dxa), stream()))
             torch.cuda.synchronize()
             res[on] = (y, st[: rows.value * 2 * 64].clone(), dx, y2, rows.value, dxa)
-    finally:
-        lib.ecgmm_conv_halo_cus(0)
-        lib.ecgmm_conv_halo_stream(1)
-        lib.ecgmm_conv_halo_enable(1)
     assert res[0][4] == res[1][4] and res[1][4] >= 1
     for i, name in ((0, "output"), (1, "statistics rows"), (2, "input gradient"), (3, "output without statistics"), (5, "input gradient + residual addend")):
         a, b = res[0][i], res[1][i]
@@ -832,3 +804,41 @@ def test_stream_form_of_64_channel_halo_tiles_matches_tile_at_a_time(B, H, W, ca
     tot = res[1][1].view(-1, 2, 64).sum(0)
     assert rel_err(tot[0], ref.sum((0, 2, 3))) < 2e-3 or ref.sum((0, 2, 3)).abs().max() < 1.0
     assert rel_err(tot[1], (ref * ref).sum((0, 2, 3))) < 2e-3
+
+
+def test_halo_stream_switch_by_name_and_by_setter_give_the_same_bits():
+    """ECGMM_HALO_STREAM through ecgmm_switch_set (1, then 0) and through ecgmm_conv_halo_stream(0) on the smallest shape that
+    reaches the stream-form dispatch (bf16 3x3 64 -> 64, N = 4, H = W = 16: one 64-channel slice, four 256-pixel tiles): the
+    header documents the switch as bit-identical, so all three outputs are, and they are the convolution (float64 reference on
+    the bf16-rounded operands, the bf16 tolerance of test_conv_fwd_dgrad_wgrad).  Both switches end as ecgmm_switch_get found them."""
+    lib = L.lib()
+    N, H, W, Cn = 4, 16, 16, 64
+    d = conv_desc(N, H, W, Cn, Cn, 3, 3, 1, 1, 1)
+    x = bf16_round(fill.hash_tensor((N, Cn, H, W), 91))
+    w = bf16_round(fill.hash_tensor((Cn, Cn, 3, 3), 92, 0.05))
+    xg = to_nhwc(x, L.BF16)
+    wf, _ = pack_weight(w, L.BF16)
+    before = {k: switch_get(lib, k) for k in ("ECGMM_CONV_HALO", "ECGMM_HALO_STREAM")}
+
+    def run():
+        y = torch.full((N * H * W * Cn,), 7.0, device=DEV).to(torch.bfloat16)
+        L.check(lib.ecgmm_conv_fwd(L.BF16, C.byref(d), ptr(xg), ptr(wf), None, ptr(y), None, 0, stream()))
+        torch.cuda.synchronize()
+        return y
+
+    outs = []
+    with switches(lib, ECGMM_CONV_HALO=2, ECGMM_HALO_STREAM=1):   # (puts both back on exit)
+        lib.ecgmm_conv_halo_enable(2)
+        for on in (1, 0):
+            L.check(lib.ecgmm_switch_set(b"ECGMM_HALO_STREAM", on))
+            assert switch_get(lib, "ECGMM_HALO_STREAM") == on
+            outs.append(run())
+        L.check(lib.ecgmm_switch_set(b"ECGMM_HALO_STREAM", 1))
+        lib.ecgmm_conv_halo_stream(0)
+        assert switch_get(lib, "ECGMM_HALO_STREAM") == 0
+        outs.append(run())
+    assert {k: switch_get(lib, k) for k in before} == before
+    for y in outs[1:]:
+        assert torch.equal(y.view(torch.int16), outs[0].view(torch.int16))
+    ref = F.conv2d(x.double(), w.double(), None, stride=1, padding=1)
+    assert rel_err(from_nhwc(outs[0], L.BF16, ref.shape), ref) < 6e-3   # bf16: output rounding 2^-9 relative

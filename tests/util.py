@@ -1,4 +1,5 @@
 """Helpers shared by the GPU parity tests: call the C ABI with torch tensors, convert layouts."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -55,3 +56,24 @@ def rel_err(a, b):
 
 def bf16_round(t):
     return t.to(torch.bfloat16).float()
+
+
+def switch_get(lib, name):
+    """the value in effect of a library switch, by environment name (whatever the environment or a setter made it)"""
+    v = C.c_int64()
+    L.check(lib.ecgmm_switch_get(name.encode(), C.byref(v)), name)
+    return v.value
+
+
+@contextlib.contextmanager
+def switches(lib, **values):
+    """`with switches(lib, ECGMM_HALO_CUS=3, ...):` sets library switches by environment name and puts back, on exit, the
+    values ecgmm_switch_get returned before -- not hard-coded defaults, so the suite also runs under an A/B environment."""
+    old = {name: switch_get(lib, name) for name in values}
+    try:
+        for name, v in values.items():
+            L.check(lib.ecgmm_switch_set(name.encode(), v), name)
+        yield
+    finally:
+        for name, v in old.items():
+            L.check(lib.ecgmm_switch_set(name.encode(), v), name)
