@@ -58,3 +58,4 @@ class Config:
     synthetic_val_size = 32
     synthetic_test_size = 32
     num_workers = 0
+    physionet2_max_len = None       # train_physionet2: truncate longer records before the spectrogram (None: keep all)

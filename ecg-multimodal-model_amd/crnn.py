@@ -1,7 +1,7 @@
 """The spectrogram CRNN of the reference's train_physionet2.py:55-96 on the HIP kernels: three 5x5 ConvBlocks (one launch
 plan, csrc/plan_crnn.hip), a 3-layer bidirectional LSTM, the mean over time and a two-layer classifier.  Parameter names,
 shapes, registration order and initialisation are torch's, so ``state_dict``s move in both directions with the reference's
-``CRNN``.  The log-spectrogram itself and the training script are not part of this module."""
+``CRNN``."""
 import torch
 import torch.nn as nn
 

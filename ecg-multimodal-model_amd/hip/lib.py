@@ -207,6 +207,8 @@ SIGNATURES = {
     "ecgmm_crnn_front_bwd_workspace": (sz, [P(CRNNFrontDesc)]),
     "ecgmm_crnn_front_forward": (i32, [P(CRNNFrontDesc), vp, P(vp), P(vp), vp, vp, sz, vp]),
     "ecgmm_crnn_front_backward": (i32, [P(CRNNFrontDesc), vp, vp, P(vp), P(vp), vp, vp, sz, vp]),
+    "ecgmm_log_spectrogram_frames": (i32, [i32, i32, i32]),
+    "ecgmm_log_spectrogram": (i32, [vp, i32, i32, vp, i32, i32, vp, i32, vp]),
 }
 
 # Entry points of the input-gradient / Grad-CAM feature.  A library selected with ECGMM_LIB for an A/B run may predate them:
@@ -229,7 +231,9 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  "ecgmm_crnn_front_fwd_workspace", "ecgmm_crnn_front_bwd_workspace", "ecgmm_crnn_front_forward",
                  "ecgmm_crnn_front_backward",
                  # the switch table by name (csrc/switches.h)
-                 "ecgmm_switch_name", "ecgmm_switch_get", "ecgmm_switch_set")
+                 "ecgmm_switch_name", "ecgmm_switch_get", "ecgmm_switch_set",
+                 # the log-spectrogram (ecgmm/spectrogram.py, csrc/spectrogram.hip)
+                 "ecgmm_log_spectrogram_frames", "ecgmm_log_spectrogram")
 
 _lib = None
 

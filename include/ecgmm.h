@@ -671,6 +671,20 @@ int ecgmm_crnn_front_forward(const ecgmm_crnn_front_desc* d, const float* spec, 
 int ecgmm_crnn_front_backward(const ecgmm_crnn_front_desc* d, const float* spec, const float* dseq, const void* const* params,
                               void* const* grads, void* ws_fwd, void* ws_bwd, size_t ws_bwd_bytes, void* stream);
 
+/* The log-spectrogram in front of the CRNN (train_physionet2.py:30-34): np.log1p(np.abs(scipy.signal.stft(x, fs, window,
+ * nperseg=64, noverlap = 64 - hop)[2])) with scipy's defaults (boundary='zeros', padded=True, one-sided, scaling='spectrum',
+ * no detrend) for a whole [S][L] fp32 matrix in one launch.  Frame t covers samples [hop*t - 32, hop*t + 32) of the record,
+ * zeros outside [0, L); T = ceil(L / hop) + 1 frames (ecgmm_log_spectrogram_frames: no GPU needed, 0 with the message set
+ * for a refused shape).  table [33][64][2] fp32 on the device: w[j] / sum(w) * (cos, -sin)(2 pi j k / 64) for the window
+ * coefficients w, built by the caller (ecgmm/spectrogram.py) -- the kernel evaluates no sin / cos.  out [S][33][T] fp32 =
+ * the [S,1,33,T] memory ecgmm_crnn_front_forward reads; every element is written, an all-zero frame gives exactly 0, so a
+ * record zero-padded to the longest one gives its own spectrogram followed by zeros.  fp32 accumulation in a fixed order,
+ * no atomics: a row's bits do not depend on S.  Refused with a message: nperseg != 64, hop outside 1..64, L < nperseg
+ * ("length"), T != the query's value ("frames"), null operands, S < 1.  L is not bounded by LDS. */
+int ecgmm_log_spectrogram_frames(int L, int nperseg, int hop);
+int ecgmm_log_spectrogram(const float* x, int S, int L, const float* table, int nperseg, int hop, float* out, int T,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,8 @@
 """Times the CRNN conv front end (forward, forward + backward) and the whole CRNN step (FocalLoss + FusedAdam) in both compute
 dtypes at B = 256, F = 33, T = 573, next to the same modules through torch / MIOpen on the same card.  Prints one JSON line.
-Warm-up first, then `--reps` repetitions timed with device events; the median is reported."""
+Warm-up first, then `--reps` repetitions timed with device events; the median is reported.
+`--spectrogram` times only the log-spectrogram launch at `--records` x `--length` samples, next to the reference's
+per-record scipy.signal.stft loop on the host, with the launch's algorithmic bytes and FLOP."""
 import argparse
 import json
 import os
@@ -26,6 +28,29 @@ def timed(fn, warmup, reps):
     return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms)}
 
 
+def spectrogram(a):
+    import time
+
+    import numpy as np
+    import scipy.signal
+
+    from ecgmm.spectrogram import compute_log_spectrogram, stft_frames
+    dev = torch.device("cuda:0")
+    S, Ln, T = a.records, a.length, stft_frames(a.length)
+    x = torch.randn(S, Ln, device=dev)
+    out = {"shape": [S, Ln], "frames": T, "device": torch.cuda.get_device_name(0),
+           "bytes": 4 * S * (Ln + 33 * T), "flop": 2 * 64 * 66 * S * T}      # x read once, out written once; direct DFT
+    out["log_spectrogram"] = timed(lambda: compute_log_spectrogram(x), a.warmup, a.reps)
+    ms = out["log_spectrogram"]["median_ms"]
+    out["GB_per_s"], out["GFLOP_per_s"] = out["bytes"] / ms / 1e6, out["flop"] / ms / 1e6
+    xh = x.cpu().numpy().astype(np.float64)
+    t0 = time.perf_counter()
+    for row in xh:      # train_physionet2.py:30-34, 135-142: one record at a time
+        np.log1p(np.abs(scipy.signal.stft(row, fs=300, window="tukey", nperseg=64, noverlap=32)[2]))
+    out["scipy_host_ms"] = (time.perf_counter() - t0) * 1e3
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
@@ -33,7 +58,12 @@ def main():
     ap.add_argument("--T", type=int, default=573)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--spectrogram", action="store_true")
+    ap.add_argument("--records", type=int, default=1024)
+    ap.add_argument("--length", type=int, default=18286)
     a = ap.parse_args()
+    if a.spectrogram:
+        return spectrogram(a)
     from ecgmm.crnn import CRNN
     from ecgmm.hip import functional as HF
     from ecgmm.optim import FusedAdam
