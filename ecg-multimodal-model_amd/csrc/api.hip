@@ -306,6 +306,24 @@ int ecgmm_se_gate_grad(int dtype, const void* dout, const void* maskref, const v
   return ecg_se_gate_grad(dtype, dout, maskref, y, coef, dg, N, R, C, S_(stream));
 }
 
+// ---- squeeze-excite MLP, per-op (head_fused.hip; SEBlock.fc, PMB:35-46): the fused kernels whatever ECGMM_SE_MLP_FUSED says ----
+static int se_mlp_shape(const char* what, int N, int C, int CR) {
+  if (N < 1 || C < 1 || C > 1024 || CR < 1 || CR > 64)   // the kernels' LDS arrays hold 1024 channels / 64 hidden units
+    ECG_FAIL(ECGMM_ERR_SHAPE, "%s: N=%d C=%d CR=%d outside N >= 1, C 1..1024, CR 1..64", what, N, C, CR);
+  return 0;
+}
+int ecgmm_se_mlp_fwd(const float* m, const float* w1, const float* b1, const float* w2, const float* b2, float* h, float* g,
+                     int N, int C, int CR, void* stream) {
+  ECG_TRY(se_mlp_shape("se_mlp_fwd", N, C, CR));
+  return ecg_se_mlp_fwd(m, w1, b1, w2, b2, h, g, N, C, CR, S_(stream));
+}
+int ecgmm_se_mlp_bwd(const float* dg, const float* g, const float* h, const float* m, const float* w1, const float* w2,
+                     float* ds, float* dh, float* dm, float* dw1, float* db1, float* dw2, float* db2, int N, int C, int CR,
+                     float scale, void* stream) {
+  ECG_TRY(se_mlp_shape("se_mlp_bwd", N, C, CR));
+  return ecg_se_mlp_bwd(dg, g, h, m, w1, w2, ds, dh, dm, dw1, db1, dw2, db2, N, C, CR, scale, S_(stream));
+}
+
 int ecgmm_linear_fwd(const float* x, const float* w, const float* bias, float* y, int B, int In, int Out, int act,
                      void* stream) {
   return ecg_linear_fwd(x, w, bias, y, B, In, Out, act, nullptr, S_(stream));

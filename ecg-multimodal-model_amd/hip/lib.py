@@ -138,6 +138,8 @@ SIGNATURES = {
     "ecgmm_avgpool": (i32, [i32, vp, vp, i32, i32, i32, vp, vp]),
     "ecgmm_bcast_rows": (i32, [i32, vp, vp, i32, i32, i32, f32, vp]),
     "ecgmm_se_gate_grad": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "ecgmm_se_mlp_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "ecgmm_se_mlp_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp]),
     "ecgmm_linear_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "ecgmm_linear_bwd_scratch": (sz, [i32, i32, i32]),
     "ecgmm_linear_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]),
@@ -233,7 +235,9 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  # the switch table by name (csrc/switches.h)
                  "ecgmm_switch_name", "ecgmm_switch_get", "ecgmm_switch_set",
                  # the log-spectrogram (ecgmm/spectrogram.py, csrc/spectrogram.hip)
-                 "ecgmm_log_spectrogram_frames", "ecgmm_log_spectrogram")
+                 "ecgmm_log_spectrogram_frames", "ecgmm_log_spectrogram",
+                 # the SE MLP per-op (csrc/head_fused.hip)
+                 "ecgmm_se_mlp_fwd", "ecgmm_se_mlp_bwd")
 
 _lib = None
 

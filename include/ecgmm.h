@@ -423,6 +423,17 @@ int ecgmm_avgpool(int dtype, const void* x, float* out, int N, int R, int C, con
 int ecgmm_bcast_rows(int dtype, const float* v, void* out, int N, int R, int C, float scale, void* stream);
 int ecgmm_se_gate_grad(int dtype, const void* dout, const void* maskref, const void* y, const float* coef, float* dg,
                        int N, int R, int C, void* stream);
+/* SEBlock.fc (PMB:35-46) on the pooled means m [N][C], fp32, one kernel forward and two backward (the kernels the ResNet1D_SE
+ * and inference plans use, whatever ECGMM_SE_MLP_FUSED says): h [N][CR] = relu(m W1^T + b1), g [N][C] = sigmoid(h W2^T + b2),
+ * w1 [CR][C], w2 [C][CR].  Backward: ds [N][C] = dg * g * (1 - g) and dh [N][CR] = (ds W2) * [h > 0] are caller-provided
+ * scratch that is written, dm [N][C] = (dh W1) * scale (scale = 1 / L: the mean over L), dw2 = ds^T h, db2 = sum_n ds,
+ * dw1 = dh^T m, db1 = sum_n dh; each of dw1 / db1 / dw2 / db2 may be NULL (skipped).
+ * ECGMM_ERR_SHAPE unless N >= 1, 1 <= C <= 1024, 1 <= CR <= 64. */
+int ecgmm_se_mlp_fwd(const float* m, const float* w1, const float* b1, const float* w2, const float* b2, float* h, float* g,
+                     int N, int C, int CR, void* stream);
+int ecgmm_se_mlp_bwd(const float* dg, const float* g, const float* h, const float* m, const float* w1, const float* w2,
+                     float* ds, float* dh, float* dm, float* dw1, float* db1, float* dw2, float* db2, int N, int C, int CR,
+                     float scale, void* stream);
 
 /* nn.Linear (+bias, +ReLU/Sigmoid) fp32: MFMA (exact f32) when the shape allows, VALU otherwise.
  * (clinical_encoder PMB:256-262, fusion_classifier PMB:283-289, branch heads PMB:269-271, SE fc PMB:53-58) */

@@ -1,4 +1,6 @@
-"""Float64 checker for the bf16 conv kernels.
+"""Float64 checkers: the bf16 conv kernels (below), the BatchNorm / pooling passes and the fp32 dense tails (their own
+sections further down, each with its bounds derived in a header comment).
+
 
 With the operands rounded to bf16, every product x * w is exact in float64 and so is any sum of a few million of them to
 well below a bf16 ulp: a float64 convolution of the same operands is the exact answer.  What a kernel may deviate by is
@@ -675,3 +677,272 @@ def pool_inputs(N, C, H, W, bf16):
     inv = 0.8 + 0.2 * h((C,), 46)
     return dict(y=_b(h((N, H, W, C), 41, 2.0), bf16), scale=sc, shift=-1.4 * sc + 0.1 * h((C,), 43),
                 dp=_b(h((N, OH, OW, C), 44), bf16), mean=0.1 * h((C,), 45), invstd=inv, gamma=sc / inv)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The fp32 dense tails (csrc/linear.hip, csrc/head.hip, csrc/head_fused.hip): Linear on its three routes, the squeeze-excite
+# MLP, the fused head, LayerNorm / attention fusion, the losses and Adam.  Operands are fp32 and taken as given.
+#
+#   dot-product outputs stored as fp32 (Linear y / dx / dw / db, every stage of the SE MLP, ecg_rows_sum):
+#       |got - ref| <= g_k(K + 2) * A        K = the reduction length, A = the same product on absolute values (+ |bias|)
+#     the standard bound of an fp32 dot product summed in ANY order (Higham, Accuracy and Stability, 3.1: every summand passes
+#     through at most K roundings whatever the tree); fma chains -- the f32-input MFMA -- only remove roundings.  The + 2
+#     covers the bias add and one more operation (accumulate, scale, or the stored product).  ReLU keeps the bound
+#     (1-Lipschitz); a sigmoid output gets 0.25 * g_k(K + 2) * A + 4 u (its Lipschitz constant; expf, the add and the divide
+#     on a value <= 1).  Where A == 0 the result must be exact.  Every K is the derived worst case, none is tightened.
+#   a consumer stage gets the kernel's own stored output of the producer stage as its given input (se_mlp_stages), so the
+#     float64 evaluation of that one stage is the exact answer.
+#   chains that are not one dot product (LayerNorm, attention fusion, var_loss, CE / focal, the head end to end, Adam):
+#       m(t) = max_i |got_i - ref_i| / (|ref_i| + rms(ref_t))  against the float64 torch formulas, at most CHAIN_MARGIN x the
+#     m(t) torch's own CPU fp32 run of the same formulas reaches on the same inputs, with a floor of CHAIN_MARGIN * u.  The
+#     margin is 8 and not the 4 of the conv constants: the two sides differ in summation order (wave butterfly and per-wave
+#     serial rows against torch's blocked sums) and in rsqrtf against 1 / sqrt, and the figure is a maximum over up to ~2e5
+#     elements, where the reference run can simply be lucky.
+# ----------------------------------------------------------------------------------------------------------------------
+CHAIN_MARGIN = 8.0
+
+
+def dot_bound(A, K, sigmoid=False):
+    b = g_k(K + 2) * A.double()
+    return 0.25 * b + 4 * U if sigmoid else b
+
+
+def dot_ratio(got, ref, A, K, name="dot", sigmoid=False):
+    """worst |got - ref| / bound of a dot-product output; got, ref, A: same shape"""
+    got, ref = got.double(), ref.double()
+    ratio = _ratio((got - ref).abs(), dot_bound(A, K, sigmoid))
+    if ratio.numel() == 0:
+        return Report(name, 0.0, ())
+    flat = int(torch.argmax(ratio))
+    seen = torch.where(A.double() > 0, (got - ref).abs() / (U * A.double()).clamp_min(1e-300), torch.zeros_like(ref))
+    seen = seen[torch.isfinite(seen)]
+    return Report(name, float(ratio.reshape(-1)[flat]), _unravel(flat, ref.shape), float(seen.max()) if seen.numel() else 0.0)
+
+
+def check_dot(got, ref, A, K, name="dot", sigmoid=False):
+    """(the accumulation term printed is the worst error in units of u * A: the measured K)"""
+    r = dot_ratio(got, ref, A, K, name, sigmoid)
+    print(r)
+    assert r.ok, str(r)
+    return r
+
+
+def linear_ref(x, w, b=None, dz=None, act="none"):
+    """float64 Linear: {name: (ref, A, K, sigmoid)} for y = act(x w^T + b) and, given dz (the gradient of the
+    pre-activation), dx = dz w, dw = dz^T x, db = sum_b dz.  x [B][In], w [Out][In], b [Out] or None, dz [B][Out]."""
+    x, w = x.double(), w.double()
+    B, In = x.shape
+    pre, A = x @ w.t(), x.abs() @ w.abs().t()
+    if b is not None:
+        pre, A = pre + b.double(), A + b.double().abs()
+    y = {"none": pre, "relu": pre.clamp_min(0), "sigmoid": torch.sigmoid(pre)}[act]
+    out = {"y": (y, A, In, act == "sigmoid")}
+    if dz is not None:
+        d = dz.double()
+        out["dx"] = (d @ w, d.abs() @ w.abs(), w.shape[0], False)
+        out["dw"] = (d.t() @ x, d.abs().t() @ x.abs(), B, False)
+        out["db"] = (d.sum(0), d.abs().sum(0), B, False)
+    return out
+
+
+def se_mlp_stages(m, w1, b1, w2, b2, h, g, dg=None, ds=None, dh=None, scale=1.0):
+    """The stages of the squeeze-excite MLP in float64, each from the STORED output of the stage before it:
+    {stage: (ref, A, K, kind)}, kind "dot", "sigmoid" or "ds" (bound g_k(4) * |ref|).  m [N][C], w1 [CR][C], w2 [C][CR];
+    h, g: what the forward stored; ds, dh: what the backward stored; scale: the fp32 value the kernel received."""
+    m, w1, b1, w2, b2 = (t.double() for t in (m, w1, b1, w2, b2))
+    N, C = m.shape
+    CR = w1.shape[0]
+    out = {"h": ((m @ w1.t() + b1).clamp_min(0), m.abs() @ w1.abs().t() + b1.abs(), C, "dot")}
+    hs = h.double()
+    out["g"] = (torch.sigmoid(hs @ w2.t() + b2), hs.abs() @ w2.abs().t() + b2.abs(), CR, "sigmoid")
+    if dg is None:
+        return out
+    gs, dgd, dss, dhs = g.double(), dg.double(), ds.double(), dh.double()
+    r = dgd * gs * (1 - gs)
+    out["ds"] = (r, r.abs(), 0, "ds")
+    mask = (hs > 0).double()
+    out["dh"] = ((dss @ w2) * mask, (dss.abs() @ w2.abs()) * mask, C, "dot")
+    sc = f32(scale)
+    out["dm"] = ((dhs @ w1) * sc, (dhs.abs() @ w1.abs()) * abs(sc), CR, "dot")
+    out["dw2"] = (dss.t() @ hs, dss.abs().t() @ hs.abs(), N, "dot")
+    out["db2"] = (dss.sum(0), dss.abs().sum(0), N, "dot")
+    out["dw1"] = (dhs.t() @ m, dhs.abs().t() @ m.abs(), N, "dot")
+    out["db1"] = (dhs.sum(0), dhs.abs().sum(0), N, "dot")
+    return out
+
+
+def se_stage_ratio(got, stage, name):
+    ref, A, K, kind = stage
+    if kind == "ds":
+        got = got.double()
+        ratio = _ratio((got - ref).abs(), g_k(4) * A)
+        flat = int(torch.argmax(ratio))
+        return Report(name, float(ratio.reshape(-1)[flat]), _unravel(flat, ref.shape))
+    return dot_ratio(got, ref, A, K, name, sigmoid=kind == "sigmoid")
+
+
+def check_se_mlp(stages, got, name="se_mlp"):
+    """got: {stage: stored tensor or None}; every stage given is checked.  Returns {stage: Report}"""
+    out = {}
+    for k, st in stages.items():
+        if got.get(k) is None:
+            continue
+        r = se_stage_ratio(got[k], st, "%s %s" % (name, k))
+        print(r)
+        assert r.ok, str(r)
+        out[k] = r
+    return out
+
+
+def se_inputs(N, C, CR):
+    """m, w1, b1, w2, b2, dg of one SEBlock.fc (hash-filled, torch's Linear scale)"""
+    from oracle import fill
+    h = fill.hash_tensor
+    return dict(m=h((N, C), 51) * 0.8 + 0.3, w1=h((CR, C), 52, (3.0 / C) ** 0.5), b1=h((CR,), 53, 0.1),
+                w2=h((C, CR), 54, (3.0 / CR) ** 0.5), b2=h((C,), 55, 0.1), dg=h((N, C), 56))
+
+
+def chain_figure(got, ref):
+    """m(t) = max_i |got_i - ref_i| / (|ref_i| + rms(ref_t)); an element whose denominator is 0 must be exact"""
+    got, ref = got.double().reshape(-1), ref.double().reshape(-1)
+    if ref.numel() == 0:
+        return 0.0
+    err = (got - ref).abs()
+    den = ref.abs() + float(ref.pow(2).mean().sqrt())
+    return float(_ratio(err, den).max())
+
+
+def chain_ratio(got, ref, own, name="chain"):
+    """got: the kernel's tensor, ref: float64, own: torch's CPU fp32 run of the same formulas.  ratio = m(got) / bar,
+    bar = CHAIN_MARGIN * max(m(own), u)"""
+    mk, mt = chain_figure(got, ref), chain_figure(own, ref)
+    bar = CHAIN_MARGIN * max(mt, U)
+    r = Report(name, mk / bar, ())
+    r.kernel, r.torch32, r.bar = mk, mt, bar
+    return r
+
+
+def check_chain(got, ref, own, name="chain"):
+    r = chain_ratio(got, ref, own, name)
+    print("%-34s kernel %.3g, torch fp32 %.3g, bar %.3g: ratio %.3g" % (name, r.kernel, r.torch32, r.bar, r.ratio))
+    assert r.ok, "%s: m = %.3g above %g x torch fp32's own %.3g" % (name, r.kernel, CHAIN_MARGIN, r.torch32)
+    return r
+
+
+class HeadRef(torch.nn.Module):
+    """The multimodal head (multimodal_paper_modal_balance.py:326-354) at any widths, as plain torch modules: three
+    LayerNorms, three branch classifiers, attention fusion, Linear-ReLU-Linear, var_loss.  .table() lists the 19 parameters
+    in the order of ecgmm_head_forward."""
+
+    def __init__(self, dims, hidden, num_classes):
+        super().__init__()
+        nn = torch.nn
+        D = sum(dims)
+        self.dims = tuple(dims)
+        self.norms = nn.ModuleList([nn.LayerNorm(d) for d in dims])
+        self.cls = nn.ModuleList([nn.Linear(d, num_classes) for d in dims])
+        self.aw = nn.Parameter(torch.ones(3))
+        self.fnorm = nn.LayerNorm(D)
+        self.fc0 = nn.Linear(D, hidden)
+        self.fc3 = nn.Linear(hidden, num_classes)
+
+    def table(self):
+        t = []
+        for n in self.norms:
+            t += [n.weight, n.bias]
+        for c in self.cls:
+            t += [c.weight, c.bias]
+        return t + [self.aw, self.fnorm.weight, self.fnorm.bias, self.fc0.weight, self.fc0.bias, self.fc3.weight, self.fc3.bias]
+
+    TABLE_NAMES = ("image_norm.w", "image_norm.b", "signal_norm.w", "signal_norm.b", "clinical_norm.w", "clinical_norm.b",
+                   "image_cls.w", "image_cls.b", "signal_cls.w", "signal_cls.b", "clinical_cls.w", "clinical_cls.b",
+                   "fusion.weights", "fusion.norm.w", "fusion.norm.b", "fc0.w", "fc0.b", "fc3.w", "fc3.b")
+
+    def forward(self, raws):
+        """-> (image, signal, clinical, fusion logits, var_loss, softmax weights), per-row variances [3][B]"""
+        f = [n(r) for n, r in zip(self.norms, raws)]
+        w = torch.softmax(self.aw, 0)
+        fused = self.fnorm(torch.cat([w[m] * f[m] for m in range(3)], 1))
+        logits = [c(t) for c, t in zip(self.cls, f)] + [self.fc3(torch.relu(self.fc0(fused)))]
+        rv = [torch.var(t, dim=1) for t in f]
+        v = [t.mean() for t in rv]
+        var = (v[0] - v[1]).abs() + (v[0] - v[2]).abs() + (v[1] - v[2]).abs()
+        return (*logits, var, w), rv
+
+
+def head_fill(head, salt=0):
+    """hash fill: gammas near 1, biases small, Linear weights at torch's scale, fusion weights apart"""
+    from oracle import fill
+    with torch.no_grad():
+        for i, p in enumerate(head.table()):
+            s = 700 + 31 * salt + i
+            if i == 12:
+                p.copy_(torch.tensor([1.3, 0.2, 0.8]))
+            elif p.dim() == 2:
+                p.copy_(fill.hash_tensor(p.shape, s, (3.0 / p.shape[1]) ** 0.5))
+            elif i in (0, 2, 4):     # branch gammas apart, so that the three mean variances of var_loss differ by O(1)
+                p.copy_((1.0, 1.5, 0.6)[i // 2] + 0.2 * fill.hash_tensor(p.shape, s))
+            elif i == 13:
+                p.copy_(1 + 0.2 * fill.hash_tensor(p.shape, s))
+            else:
+                p.copy_(0.1 * fill.hash_tensor(p.shape, s))
+    return head
+
+
+def head_inputs(B, dims, num_classes):
+    from oracle import fill
+    raws = [fill.hash_tensor((B, d), 90 + i, 1.0 + 0.5 * i) + 0.2 * i for i, d in enumerate(dims)]
+    return raws, torch.arange(B) % num_classes
+
+
+HEAD_LOSSES = ("all_heads", "train_py", "signal_only", "var_only")
+
+
+def head_loss(out, labels, kind, ce=F.cross_entropy):
+    if kind == "all_heads":
+        return ce(out[0], labels) + ce(out[1], labels) + ce(out[2], labels) + ce(out[3], labels) + 0.1 * out[4]
+    if kind == "train_py":
+        return ce(out[3], labels) + 0.1 * out[4]
+    if kind == "signal_only":
+        return ce(out[1], labels)
+    return out[4] * 1.0
+
+
+def head_run(head, raws, labels, kind, dtype, row_weight=None):
+    """outputs, d raw x 3 and the 19 parameter gradients (None where the branch is not in the loss) of `head` evaluated in
+    `dtype` on the CPU.  row_weight [B] (None = ones) weights every row's share of the loss: the cross-entropy terms are row
+    sums, and var_loss enters through its own linearisation sum_m sign_m * mean_b var_m[b] (the signs of the full batch),
+    whose gradient is var_loss's -- so a zero weight removes exactly that row's contribution from every gradient."""
+    h = HeadRef(head.dims, head.fc0.out_features, head.fc3.out_features).to(dtype)
+    h.load_state_dict({k: v.to(dtype) for k, v in head.state_dict().items()})
+    rr = [r.to(dtype).clone().requires_grad_(True) for r in raws]
+    out, rv = h(rr)
+    if row_weight is None:
+        loss = head_loss(out, labels, kind)
+    else:
+        wgt = row_weight.to(dtype)
+        B = labels.shape[0]
+        ce = lambda lg, y: (F.cross_entropy(lg, y, reduction="none") * wgt).sum() / B
+        v = [t.mean().detach() for t in rv]
+        sg = [torch.sign(v[0] - v[1]) + torch.sign(v[0] - v[2]), -torch.sign(v[0] - v[1]) + torch.sign(v[1] - v[2]),
+              -torch.sign(v[0] - v[2]) - torch.sign(v[1] - v[2])]
+        lin = sum(sg[m] * (rv[m] * wgt).sum() / B for m in range(3))
+        loss = head_loss((*out[:4], lin, out[5]), labels, kind, ce)
+    loss.backward()
+    return [o.detach() for o in out], [r.grad for r in rr], [p.grad for p in h.table()]
+
+
+# ---- cases shared by tests/test_dense_f64_gpu.py and the CPU tests of the checkers (tests/test_f64check.py) ----
+# (B, In, Out) of a Linear, and what each reaches in csrc/linear.hip
+LINEAR_CASES = [(16, 16, 16), (48, 80, 16), (272, 672, 128), (17, 672, 128), (7, 96, 40), (300, 10, 30), (70, 300, 30),
+                (1040, 768, 2), (6, 4, 64), (6, 64, 4), (1, 16, 16)]
+# (N, C, CR) of the SE MLP: every width at N = 67 (the model's four stages, an odd one and the limit), every N at (64, 4)
+SE_CASES = [(67, 64, 4), (67, 128, 8), (67, 256, 16), (67, 512, 32), (67, 100, 7), (67, 1024, 64),
+            (1, 64, 4), (5, 64, 4), (16, 64, 4), (17, 64, 4), (49, 64, 4), (130, 64, 4)]
+SE_SCALE = 1.0 / 313            # the mean over L = 313 positions: not a power of two
+
+
+def linear_inputs(B, In, Out):
+    from oracle import fill
+    h = fill.hash_tensor
+    return h((B, In), 1), h((Out, In), 2, In ** -0.5), h((Out,), 3, 0.1), h((B, Out), 4)

@@ -525,3 +525,143 @@ def test_fused_stem_backward_checker_accepts_torch_fp32(shape, bf16):
     if bf16:
         u = e["unrounded"].double().reshape(-1, C)
         assert _fails(lambda: F64.check_sum(u.sum(0).float(), s.sum(0), s.abs().sum(0), Kb, "stem dbias"))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The dense tails: the dot-product bound, the per-stage SE MLP check and the chain bar accept torch's fp32 and reject each
+# defect of the launch geometry they are there for.
+# ----------------------------------------------------------------------------------------------------------------------
+ACTS = {"none": lambda z: z, "relu": torch.relu, "sigmoid": torch.sigmoid}
+
+
+def _linear_fp32(B, In, Out, act="none"):
+    x, w, b, dz = F64.linear_inputs(B, In, Out)
+    xr, wr, br = (t.clone().requires_grad_(True) for t in (x, w, b))
+    z = F.linear(xr, wr, br)
+    z.backward(dz)
+    return (x, w, b, dz), dict(y=ACTS[act](z.detach()), dx=xr.grad, dw=wr.grad, db=br.grad)
+
+
+@pytest.mark.parametrize("act", list(ACTS))
+@pytest.mark.parametrize("shape", F64.LINEAR_CASES)
+def test_dot_checker_accepts_torch_fp32_linear(shape, act):
+    (x, w, b, dz), got = _linear_fp32(*shape, act)
+    ref = F64.linear_ref(x, w, b, dz, act)
+    for k, (r, A, K, sig) in ref.items():
+        F64.check_dot(got[k], r, A, K, "%s %s %s" % (shape, act, k), sigmoid=sig)
+    # and without a bias
+    r, A, K, sig = F64.linear_ref(x, w, None, None, act)["y"]
+    F64.check_dot(ACTS[act](F.linear(x, w)), r, A, K, "%s %s y, no bias" % (shape, act), sigmoid=sig)
+
+
+def _se_fp32(N, C, CR, rows=None):
+    """the SE MLP stage by stage in torch fp32; rows: the batch rows the weight gradients sum over (None = all)"""
+    d = F64.se_inputs(N, C, CR)
+    m, w1, b1, w2, b2, dg = (d[k] for k in ("m", "w1", "b1", "w2", "b2", "dg"))
+    o = {"h": torch.relu(m @ w1.t() + b1)}
+    o["g"] = torch.sigmoid(o["h"] @ w2.t() + b2)
+    o["ds"] = dg * o["g"] * (1 - o["g"])
+    o["dh"] = (o["ds"] @ w2) * (o["h"] > 0).float()
+    o["dm"] = (o["dh"] @ w1) * torch.tensor(F64.SE_SCALE, dtype=torch.float32)
+    r = slice(None) if rows is None else rows
+    o["dw2"], o["db2"] = o["ds"][r].t() @ o["h"][r], o["ds"][r].sum(0)
+    o["dw1"], o["db1"] = o["dh"][r].t() @ m[r], o["dh"][r].sum(0)
+    st = F64.se_mlp_stages(m, w1, b1, w2, b2, o["h"], o["g"], dg, o["ds"], o["dh"], F64.SE_SCALE)
+    return st, o
+
+
+@pytest.mark.parametrize("shape", F64.SE_CASES)
+def test_se_mlp_checker_accepts_an_fp32_restatement(shape):
+    st, o = _se_fp32(*shape)
+    assert set(st) == {"h", "g", "ds", "dh", "dm", "dw1", "db1", "dw2", "db2"}
+    F64.check_se_mlp(st, o, "se_mlp %s" % (shape,))
+
+
+def test_dot_bound_demands_exactness_where_nothing_is_summed():
+    z = torch.zeros(3, 4)
+    assert F64.dot_ratio(z, z, z, 16).ok
+    assert not F64.dot_ratio(z + 1e-30, z, z, 16).ok
+    assert not F64.dot_ratio(z + float("nan"), z, z + 1, 16).ok
+
+
+@pytest.mark.parametrize("shape", [(272, 672, 128), (48, 80, 16), (16, 16, 16)])
+def test_dot_checker_rejects_each_tile_defect_of_a_linear(shape):
+    """one 16x16 output tile of y, dx and dw, each with: one 4-wide k group dropped, one counted twice, the neighbour tile's
+    values, and (y) the bias missing on one column.  At (16, 16, 16) every output is a single tile and has no neighbour:
+    there the tile holds its rows displaced by one 4-row MFMA block, the nearest displacement the kernel's indexing has."""
+    B, In, Out = shape
+    (x, w, b, dz), got = _linear_fp32(B, In, Out)
+    ref = F64.linear_ref(x, w, b, dz)
+    # (left operand rows, right operand rows, reduction axis): out[i][j] = sum_k Lop[i][k] * Rop[j][k]
+    ops = {"y": (x, w), "dx": (dz, w.t().contiguous()), "dw": (dz.t().contiguous(), x.t().contiguous())}
+    for k, (lo, ro) in ops.items():
+        r, A, K, _ = ref[k]
+        M, N = r.shape
+        assert K == lo.shape[1] and F64.dot_ratio(got[k], r, A, K).ok
+        m0, n0, k0 = M - 16, N - 16, 4 * ((K // 4) // 2)
+        group = lo[m0:m0 + 16, k0:k0 + 4] @ ro[n0:n0 + 16, k0:k0 + 4].t()
+        for sign, what in ((-1, "dropped"), (1, "counted twice")):
+            bad = got[k].clone()
+            bad[m0:m0 + 16, n0:n0 + 16] += sign * group
+            rep = F64.dot_ratio(bad, r, A, K)
+            assert not rep.ok and m0 <= rep.where[0] < m0 + 16 and n0 <= rep.where[1] < n0 + 16, (k, what, rep)
+        bad = got[k].clone()
+        if m0 >= 16:
+            bad[m0:m0 + 16, n0:n0 + 16] = got[k][m0 - 16:m0, n0:n0 + 16]
+        elif n0 >= 16:
+            bad[m0:m0 + 16, n0:n0 + 16] = got[k][m0:m0 + 16, n0 - 16:n0]
+        else:
+            bad[m0:m0 + 16, n0:n0 + 16] = torch.roll(got[k][m0:m0 + 16, n0:n0 + 16], 4, 0)
+        assert not F64.dot_ratio(bad, r, A, K).ok, (k, "neighbour tile")
+    r, A, K, _ = ref["y"]
+    col = Out - 16 + int(b[Out - 16:].abs().argmax())
+    bad = got["y"].clone()
+    bad[B - 16:, col] -= b[col]
+    rep = F64.dot_ratio(bad, r, A, K)
+    assert not rep.ok and rep.where[1] == col, rep
+
+
+@pytest.mark.parametrize("C,CR", [(64, 4), (128, 8)])
+def test_se_mlp_checker_rejects_weight_gradient_defects(C, CR):
+    """se_mlp_bwd_weights_kernel at N = 67: batch slice 15 (rows 15, 31, 47, 63) missing; the 4x-unrolled trip's rows
+    (0..63: every slice makes one) missing, leaving only the tail loop's rows 64..66"""
+    N = 67
+    st, good = _se_fp32(N, C, CR)
+    every = torch.arange(N)
+    for what, rows in (("slice 15", every[every % 16 != 15]), ("unrolled trip", every[every >= 64])):
+        _, bad = _se_fp32(N, C, CR, rows)
+        for k in ("dw1", "db1", "dw2", "db2"):
+            assert F64.se_stage_ratio(good[k], st[k], k).ok
+            assert not F64.se_stage_ratio(bad[k], st[k], k).ok, (what, k)
+
+
+def test_chain_bar_rejects_missing_rows_of_the_head_backward():
+    """head_rows_bwd_kernel at B = 272 (64 blocks x 4 waves, rows 256..271 are a wave's second row): those rows missing from
+    every parameter gradient; one wave's partial (rows 1 and 257) missing from the fold of the row kernel's gradients"""
+    B, dims, hidden, nc = 272, (256, 256, 256), 128, 2
+    head = F64.head_fill(F64.HeadRef(dims, hidden, nc))
+    raws, lab = F64.head_inputs(B, dims, nc)
+    ones = torch.ones(B)
+    out64, draw64, g64 = F64.head_run(head, raws, lab, "all_heads", torch.float64)
+    _, _, g64w = F64.head_run(head, raws, lab, "all_heads", torch.float64, ones)
+    out32, draw32, g32 = F64.head_run(head, raws, lab, "all_heads", torch.float32)
+    for a, b in zip(g64, g64w):     # the row-weighted loss with unit weights has the gradients of the loss itself
+        assert F64.chain_figure(b, a) < 1e-12
+    for a, r, o in zip(list(out32[:5]) + draw32 + g32, list(out64[:5]) + draw64 + g64, list(out32[:5]) + draw32 + g32):
+        assert F64.chain_ratio(a, r, o).ratio <= 1 / F64.CHAIN_MARGIN + 1e-12
+    second = ones.clone()
+    second[256:] = 0
+    _, _, bad = F64.head_run(head, raws, lab, "all_heads", torch.float32, second)
+    for i, name in enumerate(F64.HeadRef.TABLE_NAMES):
+        assert not F64.chain_ratio(bad[i], g64[i], g32[i], name).ok, name
+    wave = ones.clone()
+    wave[1] = wave[257] = 0
+    _, _, bad = F64.head_run(head, raws, lab, "all_heads", torch.float32, wave)
+    for i, name in enumerate(F64.HeadRef.TABLE_NAMES[:15]):
+        assert not F64.chain_ratio(bad[i], g64[i], g32[i], name).ok, name
+
+
+def test_chain_figure_demands_exactness_of_an_all_zero_tensor():
+    z = torch.zeros(5)
+    assert F64.chain_figure(z, z) == 0.0 and F64.chain_figure(z + 1e-30, z) == float("inf")
+    assert F64.chain_figure(torch.tensor([1.0, float("nan")]), torch.ones(2)) == float("inf")
