@@ -470,8 +470,11 @@ int ecg_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const float* con
       float* gwi = gr ? gr[0] : nullptr; float* gwh = gr ? gr[1] : nullptr;
       float* gbi = gr ? gr[2] : nullptr; float* gbh = gr ? gr[3] : nullptr;
       float* dxk = dst ? (k == 0 ? dst : w.dxtmp) : nullptr;
-      if (dxk || gwi || gbi)
-        ECG_TRY(ecg_linear_bwd(w.dgates[k], in, pr[0], dxk, gwi, gbi, rows, In, 4 * H, w.lin, w.lin_bytes, s));
+      // b_ih's gradient is, like b_hh's, the column sum of dgates: ecg_rows_sum for both, not ecg_linear_bwd's db, whose VALU
+      // route sums in another order when dw is requested with it -- the same bits whatever else the caller asked for
+      if (dxk || gwi)
+        ECG_TRY(ecg_linear_bwd(w.dgates[k], in, pr[0], dxk, gwi, nullptr, rows, In, 4 * H, w.lin, w.lin_bytes, s));
+      if (gbi) ECG_TRY(ecg_rows_sum(w.dgates[k], rows, 4 * H, gbi, 0, s));
       if (dxk && k == 1) ECG_TRY(ecg_axpby(1.f, w.dxtmp, 1.f, dst, (long)rows * In, s));   // forward + reverse, in that order
       if (gwh) ECG_TRY(ecg_linear_bwd(w.dgates[k], f.hprev[l][k], pr[1], nullptr, gwh, nullptr, rows, H, 4 * H, w.lin,
                                       w.lin_bytes, s));

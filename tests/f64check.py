@@ -1,5 +1,5 @@
-"""Float64 checkers: the bf16 conv kernels (below), the BatchNorm / pooling passes and the fp32 dense tails (their own
-sections further down, each with its bounds derived in a header comment).
+"""Float64 checkers: the bf16 conv kernels (below), the BatchNorm / pooling passes, the fp32 dense tails and the LSTM
+recurrence (their own sections further down, each with its bounds derived in a header comment).
 
 
 With the operands rounded to bf16, every product x * w is exact in float64 and so is any sum of a few million of them to
@@ -22,6 +22,8 @@ value measured over every layer of the benchmarked step (below).  TAU_DW is set 
 serial sums are longer than the kernels' split-K chunks.  The mutation test in tests/test_f64check.py shows that they still reject a zeroed tile, a neighbour's tile, a missing K slice,
 a wrong image-border row, a 4-ulp error and (dw) a missing tile or a split-K chunk counted twice.
 """
+import copy
+import functools
 from dataclasses import dataclass
 
 import torch
@@ -946,3 +948,226 @@ def linear_inputs(B, In, Out):
     from oracle import fill
     h = fill.hash_tensor
     return h((B, In), 1), h((Out, In), 2, In ** -0.5), h((Out,), 3, 0.1), h((B, Out), 4)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The LSTM recurrence (csrc/lstm.hip: lstm_seq_fwd_kernel, lstm_seq_bwd_kernel and the GEMMs around them), fp32, operands
+# taken as given.  References: torch.nn.LSTM on the CPU in float64 (the answer) and in float32 (the yardstick).
+#
+# (a) The LSTM is a chain, so it falls under the chain rule above -- but per slice.  A whole-tensor figure is blind to
+#     magnitudes that decay in time: with the loss on h_n only, dx of the 70-step case falls from an rms of O(1e-2) at the
+#     last step to 2.2e-15 at t = 0, and max|a - ref| / max|ref| accepts a backward that is wrong by 100 % over the first 60
+#     steps.  So, for every time step t of a tensor with a time axis (y, dx),
+#         m_t = max_i |got_i - ref_i| / (|ref_i| + rms(ref[t]))          over that step's slice
+#     and every m_t <= CHAIN_MARGIN * max(u, max_t m_t(own32)): the yardstick is the MAXIMUM over the slices of torch's own
+#     fp32 run, so that one lucky slice of that run cannot tighten the bar.  hn, cn, dh0, dc0 are one slice per (layer,
+#     direction) (their leading axis), a parameter gradient is one slice.  No slice is skipped; the float64 reference's
+#     smallest slice rms must be >= LSTM_MIN_RMS = 1e-25, far above fp32's subnormal range (the smallest over LSTM_CHAIN_CASES
+#     is the 2.2e-15 above).  torch fp32's own worst per-slice figure over LSTM_CHAIN_CASES is 15 - 33 u on the CPU.
+#
+# (b) One step (T = 1) reads and writes only public tensors (x, h0, c0 -> y, hn, cn), so the float64 evaluation of one
+#     cell is the exact answer and every output has a derived bound:
+#       pre-activations   A = |x| |W_ih|^T + |b_ih| + |h0| |W_hh|^T + |b_hh|,   b = g_k(In + H + 4) * A
+#                         the any-order dot-product bound of the dense section; the + 4: the stored projection, its bias
+#                         and the two adds in the kernel
+#       gates             d(i, f, o) = 0.25 b + E (sigmoid is 0.25-Lipschitz),   dg = b + E (tanh is 1-Lipschitz)
+#       cell state        dc = |c0| df + |g| di + |i| dg + di dg + g_k(3) (|f c0| + |i g|)     (two products, one add)
+#       output            dh = do + dc + E + u |h|       (|tanh c| <= 1, o <= 1; tanhf of c; the product)
+#     E = K_FN * u is the absolute error of sigmoidf_ (1 / (1 + expf(-x))) and tanhf on the device, the one constant here
+#     that is measured: the worst error of y / cn beyond the remaining terms, in units of what one u of E adds to the
+#     bound, over every case of LSTM_STEP_* (tests/test_lstm_f64_gpu.py prints it).  K_FN is at most 4x that.
+#     hn must equal y bit for bit at T = 1.
+#
+# Measured on the MI355X (tests/test_lstm_f64_gpu.py, 120 shapes + the saturated one): the function error seen beyond the
+# remaining terms is 0.00 u at every case -- no element of y or cn leaves the derived terms alone, which are worst-case sums
+# of In + H + 4 roundings where the functions contribute one or two -- so K_FN = 4 x 0 = 0 and E drops out of the bound (it
+# stays in the formulas for a device whose expf / tanhf were worse).  Worst ratio to that bound: 0.143 (H = 4), 0.097
+# (H = 16), 0.085 (H = 1), under 0.04 from H = 37 up, 0.0066 at the cap; torch's CPU fp32 cell: 0.16 (tests/test_f64check.py).
+# Per-slice chain bar, worst ratio over LSTM_CHAIN_CASES: 0.56 (dc0 at H = 1: 10.1 u against torch fp32's 2.2 u on that
+# tensor), 0.35 at the cap (dx, 40.6 u), 0.15 on the 70-step case; torch fp32's own worst slice there is 13.9 - 45.6 u.
+# ----------------------------------------------------------------------------------------------------------------------
+K_FN = 0.0                   # measured 0.00 u beyond the other terms (above)
+LSTM_MIN_RMS = 1e-25
+
+# (B, T, In, H, layers, bidirectional, batch_first, h0 / c0 given), the cotangents in the loss, what the case reaches
+LSTM_CHAIN_CASES = [
+    ((16, 70, 24, 200, 1, False, False, True), ("h",)),          # dx decays to 2.2e-15 at t = 0
+    ((9, 24, 20, 132, 1, False, True, False), ("c",)),           # wave 0 alone takes a second tile
+    ((17, 3, 24, 384, 1, True, True, True), ("y", "h", "c")),    # the cap: 148 224 B of LDS in the backward
+    ((17, 3, 24, 128, 1, True, False, True), ("y", "h", "c")),   # exactly one tile per wave
+    ((17, 3, 24, 256, 1, True, True, True), ("y", "h", "c")),    # two tiles per wave
+    ((3, 5, 16, 8, 8, True, False, False), ("y",)),              # 8 layers
+    ((5, 1, 12, 37, 2, True, True, True), ("y", "h", "c")),      # T = 1: the backward's `first` branch in both directions
+    ((33, 4, 16, 1, 1, True, True, True), ("y", "h", "c")),      # H = 1
+]
+LSTM_CHAIN_IDS = ["t70_hn_only", "h132_cn_only", "h384_cap", "h128", "h256", "layers8", "t1x2", "h1"]
+LSTM_STEP_H = (1, 4, 16, 37, 128, 132, 200, 256, 380, 384)
+LSTM_STEP_B = (1, 16, 17)
+LSTM_STEP_IN = (3, 24)
+
+
+def lstm_step_case(B, In, H, bi):
+    return (B, 1, In, H, 1, bi, True, True)
+
+
+@functools.lru_cache(maxsize=None)
+def lstm_inputs(case, wscale=1.0, xscale=1.0):
+    """(torch.nn.LSTM, x, h0, c0, gy, gh, gc) of a case, seeded by its shape; cached and never modified"""
+    B, T, In, H, layers, bi, bf, given = case
+    torch.manual_seed(1234 + B * 7 + T)
+    mod = torch.nn.LSTM(In, H, layers, batch_first=bf, bidirectional=bi)
+    with torch.no_grad():
+        for p in mod.parameters():
+            p.mul_(wscale)
+    D = 2 if bi else 1
+    x = torch.randn((B, T, In) if bf else (T, B, In)) * xscale
+    h0 = torch.randn(layers * D, B, H) * 0.5 if given else None
+    c0 = torch.randn(layers * D, B, H) * 0.5 if given else None
+    gy = torch.randn((B, T, D * H) if bf else (T, B, D * H))
+    gh, gc = torch.randn(layers * D, B, H), torch.randn(layers * D, B, H)
+    return mod, x, h0, c0, gy, gh, gc
+
+
+def lstm_run(ins, dtype, use=("y", "h", "c")):
+    """torch.nn.LSTM on the CPU in `dtype`: outputs and every gradient of sum y gy + sum h_n gh + sum c_n gc (the terms
+    named in `use`).  ins = (module, x, h0, c0, gy, gh, gc), left as they are."""
+    mod, x, h0, c0, gy, gh, gc = ins
+    m = copy.deepcopy(mod).to(dtype)
+    leaf = lambda t: t.detach().to(dtype).clone().requires_grad_()
+    x = leaf(x)
+    hx = None if h0 is None else (leaf(h0), leaf(c0))
+    y, (hn, cn) = m(x, hx)
+    loss = 0
+    if "y" in use:
+        loss = loss + (y * gy.to(dtype)).sum()
+    if "h" in use:
+        loss = loss + (hn * gh.to(dtype)).sum()
+    if "c" in use:
+        loss = loss + (cn * gc.to(dtype)).sum()
+    loss.backward()
+    out = {"y": y, "hn": hn, "cn": cn, "dx": x.grad}
+    if hx is not None:
+        out["dh0"], out["dc0"] = hx[0].grad, hx[1].grad
+    for n, p in m.named_parameters():
+        out["d" + n] = p.grad
+    return {k: v.detach() for k, v in out.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def lstm_refs(case, use=("y", "h", "c"), wscale=1.0, xscale=1.0):
+    """(float64 run, float32 run) of a case on the CPU; computed once and never modified"""
+    ins = lstm_inputs(case, wscale, xscale)
+    return lstm_run(ins, torch.float64, use), lstm_run(ins, torch.float32, use)
+
+
+def lstm_slice_dim(key, batch_first):
+    """the axis a tensor of lstm_run is sliced along: time for y / dx, (layer, direction) for the states, None = one slice"""
+    if key in ("y", "dx"):
+        return 1 if batch_first else 0
+    return 0 if key in ("hn", "cn", "dh0", "dc0") else None
+
+
+def seq_slice_figures(got, ref, dim):
+    """(m_t, rms(ref[t])) for every slice t along `dim` (None: the tensor is one slice)"""
+    got, ref = got.double(), ref.double()
+    if dim is None:
+        got, ref = got.reshape(1, -1), ref.reshape(1, -1)
+    else:
+        n = ref.shape[dim]
+        got, ref = got.movedim(dim, 0).reshape(n, -1), ref.movedim(dim, 0).reshape(n, -1)
+    rms = ref.pow(2).mean(1, keepdim=True).sqrt()
+    return _ratio((got - ref).abs(), ref.abs() + rms).amax(1), rms.reshape(-1)
+
+
+def seq_chain_ratio(got, ref64, own32, time_dim, name="seq"):
+    assert got.shape == ref64.shape == own32.shape, (name, got.shape, ref64.shape, own32.shape)
+    mk, rms = seq_slice_figures(got, ref64, time_dim)
+    mt, _ = seq_slice_figures(own32, ref64, time_dim)
+    bar = CHAIN_MARGIN * max(float(mt.max()), U)
+    t = int(torch.argmax(mk))
+    r = Report(name, float(mk[t]) / bar, (t,))
+    r.kernel, r.torch32, r.bar, r.min_rms = float(mk[t]), float(mt.max()), bar, float(rms.min())
+    return r
+
+
+def seq_chain_check(got, ref64, own32, time_dim, name="seq", quiet=False):
+    """every slice of `got` along time_dim within CHAIN_MARGIN x the worst slice of torch's own fp32 run (header (a))"""
+    r = seq_chain_ratio(got, ref64, own32, time_dim, name)
+    if not quiet:
+        print("%-34s worst slice %s: kernel %.3g, torch fp32 %.3g (= %.1f u), bar %.3g: ratio %.3g" %
+              (name, r.where, r.kernel, r.torch32, r.torch32 / U, r.bar, r.ratio))
+    assert r.min_rms >= LSTM_MIN_RMS, "%s: a slice of the float64 reference has rms %.3g" % (name, r.min_rms)
+    assert r.ok, "%s: slice %s has m = %.3g above %g x torch fp32's own worst %.3g" % (name, r.where, r.kernel, CHAIN_MARGIN,
+                                                                                    r.torch32)
+    return r
+
+
+def lstm_chain_check(out, ref64, own32, batch_first, name, keys=None, quiet=True):
+    """seq_chain_check of every tensor of `out` named in keys (default: every tensor of the reference).  Returns the worst
+    Report; prints one line: the worst per-slice figure next to torch fp32's own."""
+    worst = None
+    for k in (keys or ref64):
+        r = seq_chain_check(out[k], ref64[k], own32[k], lstm_slice_dim(k, batch_first), name + " " + k, quiet)
+        if worst is None or r.ratio >= worst.ratio:
+            worst = r
+    own = max(seq_chain_ratio(own32[k], ref64[k], own32[k], lstm_slice_dim(k, batch_first)).torch32 for k in (keys or ref64))
+    print("[lstm f64] %-30s worst %.3g = %.1f u (%s, slice %s), ratio to its bar %.3g; torch fp32's own worst %.1f u" %
+          (name, worst.kernel, worst.kernel / U, worst.name.split()[-1], worst.where, worst.ratio, own / U))
+    return worst
+
+
+def lstm_step_ref(x, h0, c0, w_ih, w_hh, b_ih, b_hh, k_fn=K_FN):
+    """one LSTM cell in float64: (h, c, dh, dc), the outputs and their bounds (header (b)).  x [B][In], h0, c0 [B][H]"""
+    x, h0, c0, w_ih, w_hh, b_ih, b_hh = (t.double() for t in (x, h0, c0, w_ih, w_hh, b_ih, b_hh))
+    In, H = x.shape[1], h0.shape[1]
+    pre = x @ w_ih.t() + b_ih + h0 @ w_hh.t() + b_hh
+    A = x.abs() @ w_ih.abs().t() + b_ih.abs() + h0.abs() @ w_hh.abs().t() + b_hh.abs()
+    b = g_k(In + H + 4) * A
+    E = k_fn * U
+    i, f, g, o = torch.sigmoid(pre[:, :H]), torch.sigmoid(pre[:, H:2 * H]), torch.tanh(pre[:, 2 * H:3 * H]), torch.sigmoid(pre[:, 3 * H:])
+    di, df, dg, do = 0.25 * b[:, :H] + E, 0.25 * b[:, H:2 * H] + E, b[:, 2 * H:3 * H] + E, 0.25 * b[:, 3 * H:] + E
+    c = f * c0 + i * g
+    dc = c0.abs() * df + g.abs() * di + i.abs() * dg + di * dg + g_k(3) * ((f * c0).abs() + (i * g).abs())
+    h = o * torch.tanh(c)
+    dh = do + dc + E + U * h.abs()
+    return h, c, dh, dc
+
+
+def lstm_step_ratio(out, ins, name="lstm step"):
+    """y, hn, cn of a T = 1, one-layer run (out) against the float64 cell of every direction.  Report.ratio: worst
+    |err| / bound; .fn_seen: the worst error beyond the bound's other terms in units of what one u of E adds (the measured
+    K_FN); .hn_is_y: hn equals y bit for bit"""
+    mod, x, h0, c0 = ins[:4]
+    H = mod.hidden_size
+    D = 2 if mod.bidirectional else 1
+    xs = (x[:, 0] if mod.batch_first else x[0])
+    y = out["y"].detach().cpu()
+    y = y[:, 0] if mod.batch_first else y[0]
+    worst = Report(name, 0.0, ())
+    worst.fn_seen, worst.hn_is_y = 0.0, True
+    for k in range(D):
+        sfx = "_l0" + ("_reverse" if k else "")
+        par = [getattr(mod, n + sfx).detach() for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+        h, c, dh, dc = lstm_step_ref(xs, h0[k], c0[k], *par)
+        _, _, dh0_, dc0_ = lstm_step_ref(xs, h0[k], c0[k], *par, k_fn=0.0)
+        _, _, dh1_, dc1_ = lstm_step_ref(xs, h0[k], c0[k], *par, k_fn=1.0)
+        got_h, got_c, got_hn = y[:, k * H:(k + 1) * H].double(), out["cn"][k].detach().cpu().double(), out["hn"][k].detach().cpu()
+        worst.hn_is_y = worst.hn_is_y and torch.equal(got_hn, y[:, k * H:(k + 1) * H])
+        for tag, got, ref, bound, b0, b1 in (("y", got_h, h, dh, dh0_, dh1_), ("cn", got_c, c, dc, dc0_, dc1_)):
+            ratio = _ratio((got - ref).abs(), bound)
+            flat = int(torch.argmax(ratio))
+            if float(ratio.reshape(-1)[flat]) >= worst.ratio:
+                worst.ratio, worst.where = float(ratio.reshape(-1)[flat]), (tag, k) + _unravel(flat, ref.shape)
+            seen = ((got - ref).abs() - b0).clamp_min(0) / (b1 - b0)
+            seen = seen[torch.isfinite(seen)]
+            worst.fn_seen = max(worst.fn_seen, float(seen.max()) if seen.numel() else 0.0)
+    return worst
+
+
+def lstm_step_check(out, ins, name="lstm step"):
+    r = lstm_step_ratio(out, ins, name)
+    print("[lstm step] %-30s worst ratio to the bound %.3g at %s; function error seen %.2f u; hn == y: %s" %
+          (name, r.ratio, r.where, r.fn_seen, r.hn_is_y))
+    assert r.hn_is_y, name + ": hn differs from y at T = 1"
+    assert r.ok, str(r)
+    return r

@@ -665,3 +665,164 @@ def test_chain_figure_demands_exactness_of_an_all_zero_tensor():
     z = torch.zeros(5)
     assert F64.chain_figure(z, z) == 0.0 and F64.chain_figure(z + 1e-30, z) == float("inf")
     assert F64.chain_figure(torch.tensor([1.0, float("nan")]), torch.ones(2)) == float("inf")
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The LSTM checkers (f64check.py, "The LSTM recurrence")
+# ----------------------------------------------------------------------------------------------------------------------
+def _old_bar(a, ref):
+    """the whole-tensor figure of tests/test_lstm_gpu.py (bar 2e-5)"""
+    a, ref = a.double(), ref.double()
+    return float((a - ref).abs().max() / ref.abs().max())
+
+
+@pytest.mark.parametrize("case,use", F64.LSTM_CHAIN_CASES, ids=F64.LSTM_CHAIN_IDS)
+def test_seq_chain_checker_accepts_torch_fp32_lstm(case, use):
+    """torch's own fp32 run sits at 1 / CHAIN_MARGIN of its bar by construction; what this asserts from the float64 reference
+    alone is that no slice of any tensor of any case is below LSTM_MIN_RMS, so that none needs skipping"""
+    r64, r32 = F64.lstm_refs(case, use)
+    w = F64.lstm_chain_check(r32, r64, r32, case[6], F64.LSTM_CHAIN_IDS[F64.LSTM_CHAIN_CASES.index((case, use))])
+    assert w.ratio <= 1 / F64.CHAIN_MARGIN + 1e-12
+    rms = min(F64.seq_chain_ratio(r32[k], r64[k], r32[k], F64.lstm_slice_dim(k, case[6])).min_rms for k in r64)
+    print("smallest slice rms of the float64 reference: %.3g" % rms)
+    assert rms >= F64.LSTM_MIN_RMS
+    if use == ("h",):       # the decaying-gradient case: the smallest slice is dx[t = 0]
+        _, dx_rms = F64.seq_slice_figures(r64["dx"], r64["dx"], 0)
+        assert float(dx_rms[0]) == rms and 1e-15 < rms < 5e-15 and float(dx_rms[-1]) > 1e-3
+
+
+@pytest.mark.parametrize("H", F64.LSTM_STEP_H)
+def test_single_step_bound_accepts_torch_fp32_cell(H):
+    worst = 0.0
+    for B in F64.LSTM_STEP_B:
+        for In in F64.LSTM_STEP_IN:
+            for bi in (False, True):
+                ins = F64.lstm_inputs(F64.lstm_step_case(B, In, H, bi))
+                r = F64.lstm_step_check(F64.lstm_run(ins, torch.float32), ins, "torch fp32 H=%d B=%d In=%d D=%d" % (H, B, In, 1 + bi))
+                worst = max(worst, r.ratio)
+    ins = F64.lstm_inputs(F64.lstm_step_case(17, 24, 132, True), 3.0, 4.0)
+    F64.lstm_step_check(F64.lstm_run(ins, torch.float32), ins, "torch fp32 saturated")
+    assert worst <= 1.0
+
+
+def test_single_step_bound_rejects_cell_defects():
+    ins = F64.lstm_inputs(F64.lstm_step_case(17, 24, 132, True))
+    good = F64.lstm_run(ins, torch.float32)
+    assert F64.lstm_step_ratio(good, ins).ok
+    for name, mutate in (("tile 8 of y zeroed", lambda o: o["y"][:, 0, 128:132].zero_()),
+                         ("rows 15 and 16 of cn swapped", lambda o: o["cn"][0, 15:17].copy_(o["cn"][0, 15:17].flip(0))),
+                         ("one element of cn 1e-3 off", lambda o: o["cn"][1, 3, 7].add_(1e-3))):
+        bad = {k: v.clone() for k, v in good.items()}
+        mutate(bad)
+        bad["hn"] = bad["y"][:, 0].reshape(17, 2, 132).transpose(0, 1).contiguous()
+        assert not F64.lstm_step_ratio(bad, ins).ok, name
+    bad = {k: v.clone() for k, v in good.items()}
+    bad["hn"][0, 0, 0] += 1e-6
+    assert not F64.lstm_step_ratio(bad, ins).hn_is_y
+
+
+def _unrolled(ins, dtype, use, cut=None, wrong_c=False):
+    """a one-layer, one-direction, batch-first LSTM unrolled by hand in `dtype`, named as F64.lstm_run names its results.
+    cut = s: the backward drops the carry (dh, dc) between step s and step s - 1.  wrong_c: the backward's forget-gate
+    gradient reads c_{t-2} for c_{t-1} (the forward's values are unchanged: the substitute enters as (f - f) * c)."""
+    mod, x, h0, c0, gy, gh, gc = ins
+    H, T = mod.hidden_size, x.shape[1]
+    leaf = lambda t: t.detach().to(dtype).clone().requires_grad_()
+    names = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+    w_ih, w_hh, b_ih, b_hh = par = [leaf(getattr(mod, n)) for n in names]
+    x, h0, c0 = leaf(x), leaf(h0), leaf(c0)
+    h, c, cs, ys = h0[0], c0[0], [c0[0]], []
+    for t in range(T):
+        if cut == t:
+            h, c = h.detach(), c.detach()
+        pre = x[:, t] @ w_ih.t() + b_ih + h @ w_hh.t() + b_hh
+        i, f, g, o = torch.sigmoid(pre[:, :H]), torch.sigmoid(pre[:, H:2 * H]), torch.tanh(pre[:, 2 * H:3 * H]), torch.sigmoid(pre[:, 3 * H:])
+        if wrong_c and t >= 1:
+            c = f.detach() * c + (f - f.detach()) * cs[t - 1].detach() + i * g
+        else:
+            c = f * c + i * g
+        h = o * torch.tanh(c)
+        cs.append(c)
+        ys.append(h)
+    y = torch.stack(ys, 1)
+    loss = 0
+    if "y" in use:
+        loss = loss + (y * gy.to(dtype)).sum()
+    if "h" in use:
+        loss = loss + (h * gh[0].to(dtype)).sum()
+    if "c" in use:
+        loss = loss + (c * gc[0].to(dtype)).sum()
+    loss.backward()
+    out = {"y": y, "hn": h[None], "cn": c[None], "dx": x.grad, "dh0": h0.grad, "dc0": c0.grad}
+    out.update({"d" + n: p.grad for n, p in zip(names, par)})
+    return {k: v.detach() for k, v in out.items()}
+
+
+def _seq_ok(got, r64, r32, key, bf=True):
+    return F64.seq_chain_ratio(got[key], r64[key], r32[key], F64.lstm_slice_dim(key, bf), key).ok
+
+
+def test_seq_chain_checker_rejects_backward_indexing_slips():
+    case, use = (5, 9, 12, 37, 1, False, True, True), ("y", "h", "c")
+    ins = F64.lstm_inputs(case)
+    r64, r32 = F64.lstm_refs(case, use)
+    good = _unrolled(ins, torch.float32, use)
+    assert F64.chain_figure(_unrolled(ins, torch.float64, use)["dx"], r64["dx"]) < 1e-12     # the restatement is the LSTM
+    for k in r64:
+        assert _seq_ok(good, r64, r32, k), k
+    cut = _unrolled(ins, torch.float32, use, cut=6)        # the carry dropped at step 6: dx of steps 0..5 lacks it
+    for k in ("y", "hn", "cn"):
+        assert torch.equal(cut[k], good[k])
+    assert torch.equal(cut["dx"][:, 6:], good["dx"][:, 6:])
+    for k in ("dx", "dh0", "dc0", "dweight_ih_l0", "dweight_hh_l0", "dbias_ih_l0", "dbias_hh_l0"):
+        assert not _seq_ok(cut, r64, r32, k), k
+    wrong = _unrolled(ins, torch.float32, use, wrong_c=True)
+    for k in ("y", "hn", "cn"):
+        assert torch.equal(wrong[k], good[k])
+    for k in ("dx", "dh0", "dweight_ih_l0", "dweight_hh_l0", "dbias_ih_l0", "dbias_hh_l0"):
+        assert not _seq_ok(wrong, r64, r32, k), k
+
+
+def test_seq_chain_checker_rejects_forward_tile_and_row_slips():
+    case, use = F64.LSTM_CHAIN_CASES[1]      # (9, 24, 20, 132), batch-first
+    r64, r32 = F64.lstm_refs(case, use)
+    y = r32["y"].clone()
+    y[:, 7, 16:32] = 0                       # one 16-wide hidden tile of one step zeroed
+    assert not F64.seq_chain_ratio(y, r64["y"], r32["y"], 1).ok
+    y = r32["y"].clone()
+    y[[2, 3], 7] = y[[3, 2], 7]              # two batch rows swapped at one step
+    r = F64.seq_chain_ratio(y, r64["y"], r32["y"], 1)
+    assert not r.ok and r.where == (7,)
+    y = r32["y"].clone()
+    y[0, 23, 131] = float("nan")
+    assert not F64.seq_chain_ratio(y, r64["y"], r32["y"], 1).ok
+
+
+def test_per_slice_check_sees_what_the_whole_tensor_bar_does_not():
+    """dx of the 70-step case with the loss on h_n only, whose per-step maximum falls by 1.5 - 2 x per step going back:
+      - the first 45 steps scaled by 1.5 (wrong by 50 % over two thirds of the sequence): PASSES the old whole-tensor bar
+        (2.5e-6 < 2e-5), rejected per slice;
+      - the first 60 steps scaled by 1.5: rejected per slice; the old bar sees this one too (2.8e-3): step 59 still carries
+        5.5e-3 of the tensor's maximum;
+    y of the reverse direction shifted by one step: FAILS the old bar already, and is rejected per slice."""
+    case, use = F64.LSTM_CHAIN_CASES[0]
+    r64, r32 = F64.lstm_refs(case, use)
+    for steps, old_passes in ((45, True), (60, False)):
+        dx = r32["dx"].clone()
+        dx[:steps] *= 1.5
+        old = _old_bar(dx, r64["dx"])
+        print("dx[:%d] x 1.5: whole-tensor figure %.3g (bar 2e-5)" % (steps, old))
+        assert (old < 2e-5) == old_passes
+        r = F64.seq_chain_ratio(dx, r64["dx"], r32["dx"], 0)
+        assert not r.ok and r.ratio > 1e4
+        with pytest.raises(AssertionError):
+            F64.seq_chain_check(dx, r64["dx"], r32["dx"], 0, quiet=True)
+    case, use = F64.LSTM_CHAIN_CASES[3]      # (17, 3, 24, 128), bidirectional, time-major
+    r64, r32 = F64.lstm_refs(case, use)
+    H = case[3]
+    y = r32["y"].clone()
+    y[:, :, H:] = y[:, :, H:].roll(1, 0)
+    old = _old_bar(y, r64["y"])
+    print("reverse direction shifted by one step: whole-tensor figure %.3g (bar 2e-5)" % old)
+    assert old > 2e-5
+    assert not F64.seq_chain_ratio(y, r64["y"], r32["y"], 0).ok

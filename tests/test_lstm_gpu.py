@@ -1,8 +1,12 @@
 """nn.LSTM on the HIP recurrence kernels against torch.nn.LSTM on the CPU in float64 (the call train_physionet2.py:75-76,94
 makes), same weights, inputs and states.  Error per tensor: max|a - ref| / max|ref|; bar 2e-5, the project's fp32 op-level
-bar.  Every test prints its worst figure next to torch-CPU-fp32's own deviation from float64 (run with -s)."""
-import copy
-import ctypes as C
+bar.  Every test prints its worst figure next to torch-CPU-fp32's own deviation from float64 (run with -s).
+
+Which file holds which check: this one holds the whole-tensor bar above and the behaviour of the module path (frozen
+parameters, gradient sinks, state dicts, no_grad, the three-step tail); tests/test_lstm_f64_gpu.py holds the element-by-element
+float64 checks of the recurrence (the per-time-step chain bar at every tiling of H, the derived single-step bound, null
+pointers, sentinels, causality, seq_mean), whose bounds are derived in tests/f64check.py.  test_partial_cotangents and
+test_parity_with_torch_float64 run the per-slice check on y and dx as well.  The ABI runner is tests/lstm_abi.py."""
 import functools
 
 import pytest
@@ -11,8 +15,10 @@ import torch
 from ecgmm.hip import functional as HF
 from ecgmm.hip import lib as L
 from ecgmm.hip import nn as HN
-from ecgmm.hip.functional import ptr, stream
 from ecgmm.optim import FusedAdam
+
+from . import f64check as F64
+from . import lstm_abi
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -36,90 +42,31 @@ def rel(a, ref):
     return ((a - ref).abs().max() / ref.abs().max().clamp_min(1e-300)).item()
 
 
-@functools.lru_cache(maxsize=None)
-def inputs(case, wscale=1.0, xscale=1.0):
-    B, T, In, H, layers, bi, bf, given = case
-    torch.manual_seed(1234 + B * 7 + T)
-    mod = torch.nn.LSTM(In, H, layers, batch_first=bf, bidirectional=bi)
-    with torch.no_grad():
-        for p in mod.parameters():
-            p.mul_(wscale)
-    D = 2 if bi else 1
-    x = torch.randn((B, T, In) if bf else (T, B, In)) * xscale
-    h0 = torch.randn(layers * D, B, H) * 0.5 if given else None
-    c0 = torch.randn(layers * D, B, H) * 0.5 if given else None
-    gy = torch.randn((B, T, D * H) if bf else (T, B, D * H))
-    gh, gc = torch.randn(layers * D, B, H), torch.randn(layers * D, B, H)
-    return mod, x, h0, c0, gy, gh, gc
+inputs = F64.lstm_inputs     # (torch module, x, h0, c0, gy, gh, gc) of a case, cached
 
 
 def torch_run(case, dtype, wscale=1.0, xscale=1.0, use=("y", "h", "c")):
     """torch.nn.LSTM on the CPU in `dtype`: outputs and every gradient of sum y gy + sum h_n gh + sum c_n gc."""
-    mod, x, h0, c0, gy, gh, gc = inputs(case, wscale, xscale)
-    m = copy.deepcopy(mod).to(dtype)
-    leaf = lambda t: t.detach().to(dtype).clone().requires_grad_()   # the cached inputs stay as they are
-    x = leaf(x)
-    hx = None if h0 is None else (leaf(h0), leaf(c0))
-    y, (hn, cn) = m(x, hx)
-    loss = 0
-    if "y" in use:
-        loss = loss + (y * gy.to(dtype)).sum()
-    if "h" in use:
-        loss = loss + (hn * gh.to(dtype)).sum()
-    if "c" in use:
-        loss = loss + (cn * gc.to(dtype)).sum()
-    loss.backward()
-    out = {"y": y, "hn": hn, "cn": cn, "dx": x.grad}
-    if hx is not None:
-        out["dh0"], out["dc0"] = hx[0].grad, hx[1].grad
-    for n, p in m.named_parameters():
-        out["d" + n] = p.grad
-    return {k: v.detach() for k, v in out.items()}
+    return F64.lstm_run(inputs(case, wscale, xscale), dtype, use)
 
 
 @functools.lru_cache(maxsize=None)
 def reference(case, wscale=1.0, xscale=1.0, use=("y", "h", "c")):
     """(float64 reference, torch-fp32's own worst deviation from it); computed once per case and never modified"""
-    r64 = torch_run(case, torch.float64, wscale, xscale, use)
-    r32 = torch_run(case, torch.float32, wscale, xscale, use)
+    r64, r32 = F64.lstm_refs(case, tuple(use), wscale, xscale)
     own = max(rel(r32[k], r64[k]) for k in r64)
     return r64, own
 
 
 def abi_run(case, wscale=1.0, xscale=1.0):
-    """the C entry points with every output, the workspace and the scratch NaN-filled first"""
-    B, T, In, H, layers, bi, bf, given = case
-    mod, x, h0, c0, gy, gh, gc = inputs(case, wscale, xscale)
-    D = 2 if bi else 1
-    lib = L.lib()
-    names = [n for n, _ in mod.named_parameters()]
-    params = [p.detach().to(DEV).contiguous() for p in mod.parameters()]
-    dv = lambda t: None if t is None else t.to(DEV).contiguous()
-    nanlike = lambda t: torch.full_like(t, float("nan"))
-    x, h0, c0, gy, gh, gc = (dv(t) for t in (x, h0, c0, gy, gh, gc))
-    d = L.LSTMDesc(B, T, In, H, layers, int(bi), int(bf), 1)
-    nf, nb = lib.ecgmm_lstm_fwd_workspace(C.byref(d)), lib.ecgmm_lstm_bwd_workspace(C.byref(d))
-    assert nf > 0 and nb > 0
-    ws = torch.full((nf // 4 + 4,), float("nan"), device=DEV)
-    sc = torch.full((nb // 4 + 4,), float("nan"), device=DEV)
-    y, hn, cn = nanlike(gy), nanlike(gh), nanlike(gc)
-    tab = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-    L.check(lib.ecgmm_lstm_forward(C.byref(d), ptr(x), tab(params), ptr(h0), ptr(c0), ptr(y), ptr(hn), ptr(cn), ptr(ws),
-                                   ws.numel() * 4, stream()), "lstm_forward")
-    grads = [nanlike(p) for p in params]
-    dx = nanlike(x)
-    dh0 = None if h0 is None else nanlike(h0)
-    dc0 = None if c0 is None else nanlike(c0)
-    L.check(lib.ecgmm_lstm_backward(C.byref(d), ptr(x), tab(params), ptr(h0), ptr(c0), ptr(gy), ptr(gh), ptr(gc), ptr(ws),
-                                    ptr(dx), tab(grads), ptr(dh0), ptr(dc0), ptr(sc), sc.numel() * 4, stream()),
-            "lstm_backward")
-    torch.cuda.synchronize()
-    out = {"y": y, "hn": hn, "cn": cn, "dx": dx}
-    if given:
-        out["dh0"], out["dc0"] = dh0, dc0
-    for n, g in zip(names, grads):
-        out["d" + n] = g
-    return out
+    """the C entry points with every output, the workspace and the scratch NaN-filled first (tests/lstm_abi.py)"""
+    return lstm_abi.run(case, inputs(case, wscale, xscale))
+
+
+def slice_check(out, case, tag, use=("y", "h", "c")):
+    """the per-slice float64 check (tests/f64check.py, the LSTM section) of y and dx"""
+    r64, r32 = F64.lstm_refs(case, tuple(use))
+    F64.lstm_chain_check({k: out[k].detach().cpu() for k in ("y", "dx")}, r64, r32, case[6], tag, keys=("y", "dx"))
 
 
 def check(out, case, tag, wscale=1.0, xscale=1.0, use=("y", "h", "c"), keys=None):
@@ -170,7 +117,9 @@ def module_run(case, use=("y", "h", "c"), x_grad=True, freeze=False, m=None):
 
 @pytest.mark.parametrize("case", CASES, ids=IDS)
 def test_parity_with_torch_float64(case):
-    check(abi_run(case), case, "parity " + IDS[CASES.index(case)])
+    out = abi_run(case)
+    check(out, case, "parity " + IDS[CASES.index(case)])
+    slice_check(out, case, "parity " + IDS[CASES.index(case)])
 
 
 def test_saturated_gates_stay_finite_and_exact():
@@ -200,6 +149,7 @@ def test_input_without_grad_gives_the_same_parameter_gradients():
 def test_partial_cotangents(use):
     out, _ = module_run(SMALL, use=use)
     check(out, SMALL, "cotangent " + use[0] + " only", use=use)
+    slice_check(out, SMALL, "cotangent " + use[0] + " only", use=use)
 
 
 def test_no_grad_saves_nothing_and_matches():
