@@ -296,6 +296,7 @@ extern "C" int ecgmm_bn_small_fwd(const float* x, const float* gamma, const floa
                                   float eps, void* stream) {
   if (N < 1 || C < 1) ECG_FAIL(ECGMM_ERR_SHAPE, "bn_small: empty input");
   if (!training && (!rm || !rv)) ECG_FAIL(ECGMM_ERR_SHAPE, "bn_small: eval mode needs running statistics");
+  if (training && N < 2) ECG_FAIL(ECGMM_ERR_SHAPE, "bn_small: training needs more than 1 row per channel (N=%d)", N);
   hipLaunchKernelGGL(bn_small_fwd_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, rm, rv, nbt, y, save,
                      N, C, training, momentum, eps);
   ECG_CHECK_LAUNCH("bn_small_fwd");

@@ -4,8 +4,8 @@ restated from its published algorithm, module / parameter names kept so that a c
 
     ClinicalTabNetEncoder(input_dim=2, latent_dim=32)  ->  forward(x [B, 2]) = (z [B, 32], M_loss)
 
-Linear layers use the library's dense kernels, BatchNorm / Ghost-BatchNorm its column-stats + finalize + apply
-kernels (one virtual batch = one row slice, no concatenation), and the TabNet-specific pieces are the row kernels of
+Linear layers use the library's dense kernels, BatchNorm / Ghost-BatchNorm the small-matrix kernels ecgmm_bn_small_fwd /
+_bwd / _eval_bwd (one virtual batch = one row slice, no concatenation), and the TabNet-specific pieces are the row kernels of
 csrc/tabnet.hip: GLU gate, sparsemax, the mask / prior recurrence, column split (+ReLU), mask entropy.
 Every arithmetic step is a HIP kernel with a hand-written backward (torch.autograd.Function); there is no CPU path.
 """

@@ -531,7 +531,10 @@ int ecgmm_split_cols(const float* x, float* d, float* a, int64_t N, int D, int n
 int ecgmm_split_cols_bwd(const float* d, const float* gd, const float* ga, float* gx, int64_t N, int D, int nd, int relu,
                          void* stream);
 /* BatchNorm1d over the rows of a small [N, C] fp32 matrix, any C (one block per channel): the 2- / 64- / 128-wide
- * (ghost) batch norms of TabNet.  save = [2][C] mean, invstd.  accumulate != 0 adds into dgamma / dbeta. */
+ * (ghost) batch norms of TabNet.  save = [2][C] mean, invstd.  accumulate != 0 adds into dgamma / dbeta.
+ * gamma / beta NULL = 1 / 0.  training != 0: batch statistics; rm / rv (both or neither) take the momentum update with the
+ * unbiased variance and *nbt (nullable) goes up by one with it; N == 1 is refused with ECGMM_ERR_SHAPE as torch refuses one
+ * value per channel (nothing is written).  training == 0 needs rm / rv and changes neither them nor *nbt. */
 int ecgmm_bn_small_fwd(const float* x, const float* gamma, const float* beta, float* rm, float* rv, long long* nbt,
                        float* y, float* save, int N, int C, int training, float momentum, float eps, void* stream);
 int ecgmm_bn_small_bwd(const float* x, const float* dy, const float* gamma, const float* save, float* dx, float* dgamma,

@@ -1,5 +1,5 @@
-"""Float64 checkers: the bf16 conv kernels (below), the BatchNorm / pooling passes, the fp32 dense tails and the LSTM
-recurrence (their own sections further down, each with its bounds derived in a header comment).
+"""Float64 checkers: the bf16 conv kernels (below), the BatchNorm / pooling passes, the fp32 dense tails, the LSTM
+recurrence and the TabNet clinical branch (their own sections further down, each with its bounds derived in a header comment).
 
 
 With the operands rounded to bf16, every product x * w is exact in float64 and so is any sum of a few million of them to
@@ -1171,3 +1171,508 @@ def lstm_step_check(out, ins, name="lstm step"):
     assert r.hn_is_y, name + ": hn differs from y at T = 1"
     assert r.ok, str(r)
     return r
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The TabNet clinical branch (csrc/tabnet.hip, bn_small_eval_bwd of csrc/bn_eval_bwd.hip, ecgmm/tabnet.py), fp32, operands
+# taken as given.  Every kernel is checked on its own stored input, so the float64 evaluation of that one operation is the
+# exact answer, and every mask (ReLU, sparsemax support) is taken from the kernel's stored output.  u = 2^-24, g_k as above.
+#
+#   sigmoid     s' = 1 / (1 + expf(-b)): |s' - s| <= E_SIG = K_SIG u, the convention of the dense section (expf, the add and the
+#               divide on a value <= 1: a relative error eps of expf moves s by s (1 - s) eps <= eps / 4, the add and the divide
+#               by u s each).  It is absolute, so it also holds where expf overflows (b = -100: s' = 1 / inf = 0, s = 4e-44) or
+#               underflows (b = 100: s' = 1).  K_SIG = 4 is ASSUMED (expf within 2 ulp); the GLU checks print what is seen.
+#   GLU fwd     out = a s':                |err| <= |a| E + u |a| (s + E)
+#   GLU bwd     dz_a = g s':               |err| <= |g| E + u |g| (s + E)
+#               dz_b = ((g a) s') (1 - s'): s'(1 - s') is off by <= E |1 - 2 s| + E^2 <= E + E^2, then 1 - s' and three products:
+#                                          |err| <= |g a| (E + E^2) + g_k(4) |g a| (s (1 - s) + E + E^2)
+#   sparsemax   z = x - max(x) in float64, sorted descending; tau_k = (S_k - 1) / k, S_k the sum of the k largest; the support
+#     fwd       size k* is the last k with z_(k) > tau_k; p = max(z - tau_k*, 0).  The kernel forms v = fl(x - max) (u |z| each),
+#               the serial fp32 prefix sum (every summand passes <= k roundings with its own: g_k(k + 1) A_k, A_k = the sum of
+#               the k largest |z|, leaves one to spare), tau' = fl(fl(cum - 1) / k) (two roundings of |tau_k| >= 1 / k) and
+#               fl(v - tau').  For the support size k the kernel settled on:
+#                   dtau(k) = g_k(k + 1) A_k / k + g_k(2) (|tau_k| + g_k(k + 1) A_k / k)
+#                   b_d(k)  = u |z_d| + dtau(k) + u (|z_d - tau_k| + u |z_d| + dtau(k))          (max(., 0) is 1-Lipschitz)
+#               The kernel's support test fl(1 + fl(k v_(k))) > cum, divided by k, is off by at most 2 u |z_(k)| + u |tau_k| +
+#               g_k(k) A_k / k <= 2 b_(k)(k): where float64 has |z_(k) - tau_k| <= 2 b_(k)(k) the test at k may go either way, and
+#               the kernel (which keeps the LAST k that passes) may have settled on k or on k - 1.  tau_k <= tau_k* for every k
+#               and tau_k - tau_(k-1) = (z_(k) - tau_(k-1)) / k, so such a k moves tau by that distance over k only: the output
+#               is continuous and no element is skipped.  The bound of element d is the maximum over the admissible k (k* and
+#               every such k, k - 1) of |max(z_d - tau_k, 0) - p_d| + b_d(k).  Row sums: |sum_d p'_d - 1| <= sum_d bound_d.
+#               p >= 0; D = 1 gives exactly 1 (v = 0, tau' = -1); a lead of >= 1 gives exactly one-hot (tau' = -1, v <= -1).
+#   sparsemax   support = {p' > 0} as stored; dx = dp - mean_support(dp): a serial fp32 sum of k terms and the divide
+#     bwd       (dv = g_k(k) A / k, A = sum_support |dp|), then the subtract: |err| <= dv + u (|ref| + dv); 0 outside, exactly
+#   entropy     term_i = fl(M_i logf(fl(M_i + eps))): the argument's rounding moves the logarithm by <= g_k(1) absolute, logf is
+#     fwd       ASSUMED within K_LOG u relative (K_LOG = 2: one ulp), the product rounds once:
+#                   e_i = M_i (g_k(1) + g_k(K_LOG + 1) (|L_i| + g_k(1))),  L = log(M + eps) in float64, eps as the fp32 it is
+#               M_i = 0 gives 0 * logf(eps) = 0 exactly.  The kernel sums in double and rounds (sum / N) once:
+#                   |err| <= (1 + u) sum_i e_i / N + u |ref|
+#     bwd       dM = gs (logf(M + eps) + M / (M + eps)), gs = fl(g / N): from L: logf, add, product, gs = K_LOG + 3 roundings;
+#               from q = M / (M + eps): argument, divide, add, product, gs = 5:
+#                   |err| <= |g / N| (g_k(max(K_LOG + 3, 5)) (|L| + q) + g_k(1) (1 + g_k(K_LOG + 3)))
+#   ecgmm_ew    MUL, ADD, RELU, RELU_BWD, SCALE, NEG_MUL, RSUB: one correctly rounded operation (or none), so the stored value
+#               EQUALS the float64 result rounded to fp32 (53 >= 2 * 24 + 2 bits: no double rounding).  ADD_SCALE, PRIOR: two
+#               roundings, |err| <= g_k(2) |ref|.  split_cols(_bwd): copies and masks, exact (-0.0 == 0.0).
+#   bn_small    the kernel sums x and x^2 in double (ceil(N / 256) serial adds + the 8-level fold + the divide and subtract:
+#     fwd       K64 = ceil(N / 256) + 11 roundings of 2^-53 on sum |x|, sum x^2) and rounds mean / invstd / the unbiased variance to
+#               fp32: coef_ref above with ds1 = K64 2^-53 sum |x|, ds2 = K64 2^-53 sum x^2 gives save (mean, invstd) and the
+#               running statistics with their bounds (unbiased variance, momentum as the fp32 it is; three roundings on either
+#               path).  y = ((x - m') inv') g + b with the STORED m', inv' against the float64 mean / invstd:
+#                   |err| <= |g| (d_mean inv + |x - mean| d_inv + d_mean d_inv) + g_k(4) (|g| (|x - mean| + d_mean) (inv + d_inv) + |b|)
+#               whose first term, u |mean| inv |g| from the cast of the mean, dominates at a large mean / std.  nbt += 1 with every
+#               update of the running statistics (a call that is given none leaves nbt alone).
+#               Eval mode: mean = running_mean exactly, invstd = fl(1 / sqrt(running_var + eps)) (one rounding), nothing updated.
+#     bwd       the kernel's stored save = (m, inv) is GIVEN.  xh = fl(fl(x - m) inv) (two roundings), the sums in double:
+#               dbeta = sum dy, dgamma = sum dy xh are dot products of length N: dot_bound(A, N), A = sum |dy| [|xh|] (+ |what was
+#               there| when accumulate = 1; + 2 covers the cast and that add).  dx = k (dy - S1 / N - xh S2 / N), k = fl(g inv),
+#               S1, S2 the float64 sums the kernel holds to e1 = g_k(1) |S1|, e2 = g_k(1) |S2| + g_k(2) sum |dy| |xh|; the longest
+#               path (xh: 2, product, subtract, product; or a divide in its place) has 5 roundings, k one more:
+#                   |err| <= g_k(6) |k| (|dy| + |S1| / N + |xh| |S2| / N) + (1 + g_k(6)) |k| (e1 + |xh| e2) / N
+#     eval bwd  dx = dy fl(g inv): g_k(2) |ref|.  dbeta = sum dy, dgamma = sum dy xh as above (dot_bound(A, N)).
+#   ghost BN    every torch.chunk slice is one bn_small call: forward per slice from the running statistics the float64
+#               reference has reached (the bound of a running statistic carries (1 - momentum) of the slice before it),
+#               nbt + 1 per slice, dx per slice, dgamma / dbeta = the sum over the slices: dot_bound(A, B + slices).
+#   Linear      linear_ref / check_dot of the dense section; the weight gradient of a layer used `uses` times per forward is
+#               the float64 sum over its uses of dy_i^T x_i, K = uses * B (+ 2 covers the accumulate).
+#
+# The worst ratios measured on the MI355X (tests/test_tabnet_f64_gpu.py) are recorded in DESIGN.md, "f3 TabNet ... Checks".
+# ----------------------------------------------------------------------------------------------------------------------
+K_SIG = 4.0                  # assumed: |sigmoid' - sigmoid| <= 4 u (dense section)
+K_LOG = 2.0                  # assumed: logf within one ulp = 2 u relative
+ENT_EPS = 1e-15
+EW_OPS = dict(MUL=0, ADD_SCALE=1, PRIOR=2, RELU=3, RELU_BWD=4, SCALE=5, NEG_MUL=6, ADD=7, RSUB=8)
+EW_EXACT = ("MUL", "ADD", "RELU", "RELU_BWD", "SCALE", "NEG_MUL", "RSUB")
+EW_ARITY = dict(MUL=2, ADD_SCALE=2, PRIOR=2, RELU=1, RELU_BWD=2, SCALE=1, NEG_MUL=2, ADD=2, RSUB=1)
+EW_GRID_CAP = 4096 * 256
+
+TAB_ROWS = (1, 255, 256, 257, 513)
+SPMAX_D = (1, 2, 3, 5, 63, 64)
+SPMAX_FAMILIES = ("hash", "equal", "ascending", "descending", "ties", "dominant", "shift_up", "shift_down", "prior")
+GLU_D = (1, 32, 64)
+BN_SMALL_N = (2, 65, 128, 255, 256, 257, 513)
+BN_SMALL_C = (1, 2, 3, 64, 128)
+GHOST_CASES = [(2, 128), (128, 128), (129, 128), (130, 128), (255, 128), (257, 128), (300, 128), (385, 128), (50, 16)]
+SPLIT_CASES = [(1, 2, 1), (257, 5, 1), (257, 5, 2), (257, 5, 4), (513, 64, 32), (7, 64, 63)]
+
+
+def _report(name, ratio, shape, seen=0.0):
+    if ratio.numel() == 0:
+        return Report(name, 0.0, ())
+    flat = int(torch.argmax(ratio))
+    return Report(name, float(ratio.reshape(-1)[flat]), _unravel(flat, shape), seen)
+
+
+def _bounded(got, ref, bound, name, unit=None):
+    """Report of |got - ref| / bound; kappa_seen = the worst error in units of `unit` (u * something) where that is > 0"""
+    got, ref = got.double(), ref.double()
+    err = (got - ref).abs()
+    seen = 0.0
+    if unit is not None:
+        s = torch.where(unit > 0, err / unit.clamp_min(1e-300), torch.zeros_like(err))
+        s = s[torch.isfinite(s)]
+        seen = float(s.max()) if s.numel() else 0.0
+    return _report(name, _ratio(err, bound.double()), ref.shape, seen)
+
+
+def _check(r):
+    print(r)
+    assert r.ok, str(r)
+    return r
+
+
+def glu_ref(z, dout=None):
+    """{out, dza, dzb: (ref, bound, unit)} of the GLU gate on z [N][2 D] (a | b); unit = u |a| etc.: the sigmoid error seen"""
+    z = z.double()
+    D = z.shape[1] // 2
+    a, b = z[:, :D], z[:, D:]
+    s = torch.sigmoid(b)
+    E = K_SIG * U
+    out = {"out": (a * s, a.abs() * E + U * a.abs() * (s + E), U * a.abs())}
+    if dout is not None:
+        g = dout.double()
+        ga = (g * a).abs()
+        out["dza"] = (g * s, g.abs() * E + U * g.abs() * (s + E), U * g.abs())
+        out["dzb"] = (g * a * s * (1 - s), ga * (E + E * E) + g_k(4) * ga * (s * (1 - s) + E + E * E), U * ga)
+    return out
+
+
+def check_glu(z, out, dout=None, dz=None, name="glu"):
+    """out [N][D], dz [N][2 D] as stored.  Returns {output: Report}; kappa_seen of each is the sigmoid error seen in u"""
+    D = z.shape[1] // 2
+    ref = glu_ref(z, dout)
+    got = {"out": out}
+    if dz is not None:
+        got["dza"], got["dzb"] = dz[:, :D], dz[:, D:]
+    res = {}
+    for k, t in got.items():
+        assert bool(torch.isfinite(t).all()), "%s %s: NaN / inf" % (name, k)
+        res[k] = _check(_bounded(t, *ref[k][:2], "%s %s" % (name, k), unit=ref[k][2]))
+    return res
+
+
+def sparsemax_ref(x):
+    """float64 sparsemax of every row of x [N][D] and the bound of every element (header): (p, bound, kstar)"""
+    x = x.double()
+    N, D = x.shape
+    z = x - x.amax(1, keepdim=True)
+    zs = z.sort(1, descending=True).values
+    ks = torch.arange(1, D + 1, dtype=torch.float64).view(1, D)
+    tau = (zs.cumsum(1) - 1) / ks
+    A = zs.abs().cumsum(1)
+    kstar = (zs > tau).sum(1, keepdim=True)                       # >= 1: z_(1) = 0 > -1
+    gk = ks * 0 + torch.tensor([g_k(k + 1) for k in range(1, D + 1)], dtype=torch.float64).view(1, D)
+    dtau = gk * A / ks + g_k(2) * (tau.abs() + gk * A / ks)
+    own = U * zs.abs() + dtau + U * ((zs - tau).abs() + U * zs.abs() + dtau)       # b_(k)(k)
+    near = (zs - tau).abs() <= 2 * own
+    cand = torch.zeros(N, D, dtype=torch.bool)
+    cand.scatter_(1, kstar - 1, True)
+    cand |= near
+    cand[:, :-1] |= near[:, 1:]
+    p = (z - tau.gather(1, kstar - 1)).clamp_min(0)
+    bound = torch.zeros_like(z)
+    for k in range(D):
+        if not bool(cand[:, k].any()):
+            continue
+        tk, dk = tau[:, k:k + 1], dtau[:, k:k + 1]
+        b = U * z.abs() + dk + U * ((z - tk).abs() + U * z.abs() + dk)
+        tot = ((z - tk).clamp_min(0) - p).abs() + b
+        bound = torch.where(cand[:, k:k + 1], torch.maximum(bound, tot), bound)
+    return p, bound, kstar.reshape(-1)
+
+
+def check_sparsemax(x, p, name="sparsemax"):
+    """p [N][D] as stored against float64 sparsemax of the same rows; p >= 0, row sums 1, D = 1 and a lead >= 1 exact"""
+    assert bool(torch.isfinite(p).all()), name + ": NaN / inf"
+    ref, bound, kstar = sparsemax_ref(x)
+    pd = p.double()
+    assert bool((pd >= 0).all()), name + ": negative probability"
+    r = _check(_bounded(p, ref, bound, name, unit=U * (1 + (x.double() - x.double().amax(1, keepdim=True)).abs())))
+    rs = _check(_bounded(pd.sum(1), torch.ones(p.shape[0], dtype=torch.float64), bound.sum(1), name + " row sum"))
+    if p.shape[1] == 1:
+        assert bool((pd == 1).all()), name + ": D = 1 must give exactly 1"
+    xs = x.double().sort(1, descending=True).values
+    if p.shape[1] > 1:
+        lead = (xs[:, 0] - xs[:, 1]) >= 1
+        onehot = (x.double() == xs[:, :1]).double()
+        assert bool((pd[lead] == onehot[lead]).all()), name + ": a lead of >= 1 must give exactly one-hot"
+    r.row_sum, r.kstar = rs.ratio, kstar
+    return r
+
+
+def check_sparsemax_bwd(p, dp, dx, name="sparsemax bwd"):
+    """dx as stored; the support is the kernel's own stored p > 0"""
+    assert bool(torch.isfinite(dx).all()), name + ": NaN / inf"
+    sup = p.double() > 0
+    g = dp.double()
+    k = sup.sum(1, keepdim=True).clamp_min(1).double()
+    A = (g.abs() * sup).sum(1, keepdim=True)
+    vhat = (g * sup).sum(1, keepdim=True) / k
+    ref = torch.where(sup, g - vhat, torch.zeros_like(g))
+    gk = torch.tensor([g_k(int(v)) for v in k.reshape(-1)], dtype=torch.float64).view(-1, 1)
+    dv = gk * A / k
+    bound = torch.where(sup, dv + U * (ref.abs() + dv), torch.zeros_like(g))
+    return _check(_bounded(dx, ref, bound, name, unit=U * (g.abs() + A / k)))
+
+
+def entropy_ref(M, eps=ENT_EPS, g=None):
+    """(ref, bound) of mean_n sum_d M log(M + eps) and, given g [1], (ref, bound, unit) of its backward"""
+    M = M.double()
+    N = M.shape[0]
+    e = f32(eps)
+    Lg = torch.log(M + e)
+    ei = M * (g_k(1) + g_k(K_LOG + 1) * (Lg.abs() + g_k(1)))
+    ref = (M * Lg).sum() / N
+    fwd = (ref.reshape(1), ((1 + U) * ei.sum() / N + U * ref.abs()).reshape(1))
+    if g is None:
+        return fwd, None
+    gs = abs(float(g.double().reshape(-1)[0])) / N
+    q = M / (M + e)
+    rb = float(g.double().reshape(-1)[0]) / N * (Lg + q)
+    bb = gs * (g_k(max(K_LOG + 3, 5)) * (Lg.abs() + q) + g_k(1) * (1 + g_k(K_LOG + 3)))
+    return fwd, (rb, bb, U * gs * (Lg.abs() + q))
+
+
+def check_entropy(M, out, eps=ENT_EPS, g=None, dM=None, name="entropy"):
+    fwd, bwd = entropy_ref(M, eps, g)
+    res = {}
+    if out is not None:
+        assert bool(torch.isfinite(out).all()), name + ": NaN / inf"
+        res["out"] = _check(_bounded(out.reshape(1), fwd[0], fwd[1], name + " fwd"))
+    if dM is not None:
+        assert bool(torch.isfinite(dM).all()), name + " bwd: NaN / inf"
+        res["dM"] = _check(_bounded(dM, bwd[0], bwd[1], name + " bwd", unit=bwd[2]))
+    return res
+
+
+def ew_ref(op, a, b, s):
+    """(ref float64, exact?) of one ecgmm_ew op; s is the fp32 scalar the kernel receives"""
+    a = a.double()
+    b = None if b is None else b.double()
+    s = f32(s)
+    ref = {"MUL": lambda: a * b, "ADD_SCALE": lambda: (a + b) * s, "PRIOR": lambda: b * (s - a), "RELU": lambda: a.clamp_min(0),
+           "RELU_BWD": lambda: torch.where(a > 0, b, torch.zeros_like(a)), "SCALE": lambda: a * s, "NEG_MUL": lambda: -a * b,
+           "ADD": lambda: a + b, "RSUB": lambda: s - a}[op]()
+    return ref, op in EW_EXACT
+
+
+def check_ew(op, a, b, s, out, name=None):
+    name = name or "ew " + op
+    ref, exact = ew_ref(op, a, b, s)
+    assert bool(torch.isfinite(out).all()), name + ": NaN / inf"
+    if exact:
+        bad = out != ref.float()
+        assert not bool(bad.any()), "%s: %d elements are not the correctly rounded result (first at %d)" % (
+            name, int(bad.sum()), int(bad.reshape(-1).nonzero()[0]))
+        r = Report(name, 0.0, ())
+        print(r)
+        return r
+    return _check(_bounded(out, ref, g_k(2) * ref.abs(), name, unit=U * ref.abs()))
+
+
+def split_ref(x, nd, relu):
+    d = x[:, :nd]
+    return (d.clamp_min(0) if relu else d).contiguous(), x[:, nd:].contiguous()
+
+
+def split_bwd_ref(d, gd, ga, D, nd, relu):
+    N = d.shape[0]
+    gx = torch.zeros(N, D, dtype=d.dtype)
+    if gd is not None:
+        gx[:, :nd] = torch.where(d <= 0, torch.zeros_like(gd), gd) if relu else gd
+    if ga is not None:
+        gx[:, nd:] = ga
+    return gx
+
+
+def _k64(N):
+    return (-(-N // 256) + 11) * 2.0 ** -53
+
+
+def bn_small_fwd_ref(x, gamma, beta, rm0, rv0, momentum, eps, training):
+    """float64 BatchNorm over the rows of x [N][C]: CoefRef (mean, invstd[, rm, rv] and their bounds) and (y, |.| parts).
+    gamma / beta / rm0 / rv0 may be None (training).  Eval: mean = rm0, var = rv0."""
+    x = x.double()
+    N, C = x.shape
+    g = torch.ones(C, dtype=torch.float64) if gamma is None else gamma.double()
+    b = torch.zeros(C, dtype=torch.float64) if beta is None else beta.double()
+    if training:
+        k = _k64(N)
+        cr = coef_ref(x.sum(0), (x * x).sum(0), N, g, b, eps, rm0, rv0, momentum, ds1=k * x.abs().sum(0), ds2=k * (x * x).sum(0))
+        # the exact mean / variance (two-pass) in place of the one-pass float64 values coef_ref forms: the difference is inside dvar
+        mean = x.mean(0)
+        cr.val["mean"] = mean
+    else:
+        mean = rm0.double()
+        inv = 1.0 / (rv0.double() + f32(eps)).sqrt()
+        cr = CoefRef(dict(mean=mean, invstd=inv), dict(mean=torch.zeros_like(mean), invstd=g_k(1) * inv * (1 + 2.0 ** -50)))
+    inv, dm, di = cr.val["invstd"], cr.bound["mean"], cr.bound["invstd"]
+    dev = (x - mean).abs()
+    y = (x - mean) * inv * g + b
+    bound = g.abs() * (dm * inv + dev * di + dm * di) + g_k(4) * (g.abs() * (dev + dm) * (inv + di) + b.abs())
+    return cr, y, bound
+
+
+def check_bn_small_fwd(x, gamma, beta, rm0, rv0, nbt0, momentum, eps, training, y, save, rm, rv, nbt, name="bn_small fwd",
+                       carry=None):
+    """y [N][C], save [2][C], rm, rv [C], nbt (int) as stored after the call (rm / rv / nbt None where null was passed).
+    carry: (drm, drv) bounds on rm0 / rv0 themselves (ghost BN: the slices before).  Returns ({output: Report}, CoefRef)"""
+    cr, yr, yb = bn_small_fwd_ref(x, gamma, beta, rm0, rv0, momentum, eps, training)
+    res = {"y": _check(_bounded(y, yr, yb, name + " y", unit=U * (yr.abs() + 1)))}
+    res["mean"] = _check(_bounded(save[0], cr.val["mean"], cr.bound["mean"], name + " save mean"))
+    res["invstd"] = _check(_bounded(save[1], cr.val["invstd"], cr.bound["invstd"], name + " save invstd"))
+    if training and rm is not None:
+        mom = f32(momentum)
+        for k, got, c in (("rm", rm, 0), ("rv", rv, 1)):
+            bd = cr.bound[k] + (0 if carry is None else (1 - mom) * (1 + g_k(3)) * carry[c])
+            cr.bound[k] = bd
+            res[k] = _check(_bounded(got, cr.val[k], bd, name + " running " + ("mean" if k == "rm" else "var")))
+    elif rm is not None:
+        assert torch.equal(rm, rm0) and torch.equal(rv, rv0), name + ": eval mode changed the running statistics"
+    if nbt is not None:
+        # nbt counts the updates of the running statistics: a training call that is given none leaves it alone
+        step = 1 if training and rm0 is not None else 0
+        assert int(nbt) == int(nbt0) + step, "%s: nbt %d after %d" % (name, int(nbt), int(nbt0))
+    return res, cr
+
+
+def bn_small_bwd_ref(x, dy, gamma, save, training, dg0=None, db0=None):
+    """{dx, dgamma, dbeta: (ref, bound)} from the kernel's own stored save [2][C]; dg0 / db0: what accumulate = 1 adds to"""
+    x, dy, m, inv = x.double(), dy.double(), save[0].double(), save[1].double()
+    N, C = x.shape
+    g = torch.ones(C, dtype=torch.float64) if gamma is None else gamma.double()
+    xh = (x - m) * inv
+    out = {}
+    if training:
+        S1, S2 = dy.sum(0), (dy * xh).sum(0)
+        A1, A2 = dy.abs().sum(0), (dy * xh).abs().sum(0)
+        k = g * inv
+        e1, e2 = g_k(1) * S1.abs(), g_k(1) * S2.abs() + g_k(2) * A2
+        ref = k * (dy - S1 / N - xh * S2 / N)
+        bound = g_k(6) * k.abs() * (dy.abs() + S1.abs() / N + xh.abs() * S2.abs() / N) + (1 + g_k(6)) * k.abs() * (e1 + xh.abs() * e2) / N
+        out["dx"] = (ref, bound)
+    else:
+        ref = dy * (g * inv)
+        out["dx"] = (ref, g_k(2) * ref.abs())
+        S1, S2 = dy.sum(0), (dy * xh).sum(0)
+        A1, A2 = dy.abs().sum(0), (dy * xh).abs().sum(0)
+    if dg0 is not None:
+        S1, S2, A1, A2 = S1 + db0.double(), S2 + dg0.double(), A1 + db0.double().abs(), A2 + dg0.double().abs()
+    out["dbeta"] = (S1, dot_bound(A1, N))
+    out["dgamma"] = (S2, dot_bound(A2, N))
+    return out
+
+
+def check_bn_small_bwd(x, dy, gamma, save, training, dx=None, dgamma=None, dbeta=None, dg0=None, db0=None, name="bn_small bwd"):
+    ref = bn_small_bwd_ref(x, dy, gamma, save, training, dg0, db0)
+    res = {}
+    for k, t in (("dx", dx), ("dgamma", dgamma), ("dbeta", dbeta)):
+        if t is not None:
+            assert bool(torch.isfinite(t).all()), "%s %s: NaN / inf" % (name, k)
+            res[k] = _check(_bounded(t, ref[k][0], ref[k][1], "%s %s" % (name, k), unit=U * ref[k][0].abs()))
+    return res
+
+
+def ghost_slices(B, vbs):
+    """torch.chunk's split of B rows into ceil(B / vbs) chunks: [(i0, i1)]"""
+    return [(int(c[0]), int(c[-1]) + 1) for c in torch.arange(B).chunk(-(-B // vbs) if vbs else 1)]
+
+
+def check_ghost_bn(x, gamma, beta, rm0, rv0, nbt0, momentum, eps, vbs, training, y, save, rm, rv, nbt, dy=None, dx=None,
+                   dgamma=None, dbeta=None, name="ghost bn", slices=None):
+    """One _GhostBN call against float64 applied per torch.chunk slice, in order.  save [slices][2][C] as the forward
+    stored it (taken as given by the backward).  Returns the worst ratio of each output."""
+    B = x.shape[0]
+    sl = slices or ghost_slices(B, vbs)
+    assert save.shape[0] == len(sl), "%s: %d slices stored, torch.chunk makes %d" % (name, save.shape[0], len(sl))
+    worst = {}
+    up = lambda d: [worst.__setitem__(k, max(worst.get(k, 0.0), r.ratio)) for k, r in d.items()]
+    r_m, r_v, carry, n = rm0, rv0, None, int(nbt0)
+    last = len(sl) - 1
+    sums = {"dgamma": [0.0, 0.0], "dbeta": [0.0, 0.0]}
+    for j, (i0, i1) in enumerate(sl):
+        # the running statistics are only visible after the last slice: the slices before it update the float64 reference
+        res, cr = check_bn_small_fwd(x[i0:i1], gamma, beta, r_m, r_v, n, momentum, eps, training, y[i0:i1], save[j],
+                                     rm if j == last and training else None, rv if j == last and training else None,
+                                     None, "%s slice %d" % (name, j), carry)
+        up(res)
+        if training:
+            if j != last:
+                mom = f32(momentum)
+                for k, c in (("rm", 0), ("rv", 1)):
+                    cr.bound[k] = cr.bound[k] + (0 if carry is None else (1 - mom) * (1 + g_k(3)) * carry[c])
+            r_m, r_v, carry, n = cr.val["rm"], cr.val["rv"], (cr.bound["rm"], cr.bound["rv"]), n + 1
+        if dy is not None:
+            ref = bn_small_bwd_ref(x[i0:i1], dy[i0:i1], gamma, save[j], training)
+            if dx is not None:
+                up({"dx": _check(_bounded(dx[i0:i1], *ref["dx"], "%s slice %d dx" % (name, j)))})
+            for k in sums:
+                sums[k][0] = sums[k][0] + ref[k][0]
+                sums[k][1] = sums[k][1] + ref[k][1] / g_k(i1 - i0 + 2)          # back to A
+    if not training:
+        assert torch.equal(rm, rm0) and torch.equal(rv, rv0), name + ": eval mode changed the running statistics"
+    assert int(nbt) == n, "%s: nbt %d, expected %d (one step per slice)" % (name, int(nbt), n)
+    if dy is not None:
+        for k, t in (("dgamma", dgamma), ("dbeta", dbeta)):
+            if t is not None:
+                up({k: _check(_bounded(t, sums[k][0], dot_bound(sums[k][1], B + len(sl)), "%s %s" % (name, k)))})
+    return worst
+
+
+def shared_dw_ref(pairs):
+    """[(x_i, dy_i)] of every use of one weight -> (ref, A, K) of sum_i dy_i^T x_i for check_dot"""
+    ref = sum(dy.double().t() @ x.double() for x, dy in pairs)
+    A = sum(dy.double().abs().t() @ x.double().abs() for x, dy in pairs)
+    return ref, A, sum(x.shape[0] for x, _ in pairs)
+
+
+# ---- input families shared by tests/test_tabnet_f64_gpu.py and the CPU tests of the checkers ----
+def sparsemax_rows(N, D, family):
+    """x [N][D] fp32 of one family of SPMAX_FAMILIES"""
+    from oracle import fill
+    h = fill.hash_tensor
+    base = h((N, D), 61, 2.0)
+    col = torch.arange(D, dtype=torch.float32).view(1, D)
+    row = torch.arange(N, dtype=torch.float32).view(N, 1)
+    if family == "hash":
+        return base
+    if family == "equal":
+        return (h((N, 1), 62, 3.0)).expand(N, D).contiguous()
+    if family in ("ascending", "descending"):        # strictly monotone, steps from 1 / 64 (most in the support) to 1 (one-hot)
+        step = 2.0 ** -((row % 7))
+        x = col * step + h((N, 1), 63, 1.0)
+        return x if family == "ascending" else -x
+    if family == "ties":
+        # pairs of equal entries: with the pair values c, c - t the threshold falls between, on or next to a pair as t varies
+        t = (1 + (row % 8)) / 8.0
+        x = -torch.floor(col / 2) * t
+        perm = torch.argsort(h((D,), 64))            # the same shuffle of the columns in every row
+        return x[:, perm].contiguous()
+    if family == "dominant":
+        x = base.clone()
+        lead = 1.0 + (row % 3) * 0.25                # a lead of exactly 1, 1.25, 1.5 over the runner-up
+        j = (torch.arange(N) * 5) % D
+        others = x.clone()
+        others[torch.arange(N), j] = float("-inf")
+        if D == 1:
+            return x
+        q = torch.floor(others.amax(1) * 4) / 4       # the runner-up moves onto a grid of quarters, so the lead is exact
+        x = torch.minimum(x, q.view(N, 1))
+        x[torch.arange(N), j] = q + lead.reshape(-1)
+        return x
+    if family == "shift_up":
+        return base + 1e4
+    if family == "shift_down":
+        return base - 1e4
+    if family == "prior":                            # rows multiplied by a prior in [0, 1.5^3], as the model feeds them
+        return base * ((h((N, D), 65) * 0.5 + 0.5) * 1.5 ** 3)
+    raise ValueError(family)
+
+
+def glu_inputs(N, D, extreme=False):
+    """z [N][2 D], dout [N][D]; extreme: the gate half alternates +-100 (expf overflows / underflows) with +-20 and 0 mixed in"""
+    from oracle import fill
+    z = fill.hash_tensor((N, 2 * D), 66, 3.0)
+    if extreme:
+        vals = torch.tensor([100.0, -100.0, 20.0, -20.0, 0.0, 88.8, -88.8, 104.0, -104.0])
+        idx = (torch.arange(N).view(N, 1) * 3 + torch.arange(D).view(1, D)) % len(vals)
+        z[:, D:] = vals[idx]
+    return z, fill.hash_tensor((N, D), 67)
+
+
+def entropy_inputs(N, D):
+    """a sparsemax output (exact zeros, ones and values between) and the cotangent g [1]"""
+    p, _, _ = sparsemax_ref(sparsemax_rows(N, D, "hash"))
+    M = p.float()
+    if N > 2:
+        M[1] = 0.0
+        M[2] = 1e-12                                  # small enough that eps = 1e-15 still moves the logarithm's argument
+    return M, torch.tensor([0.7])
+
+
+def ew_inputs(n):
+    from oracle import fill
+    a = fill.hash_tensor((n,), 68, 2.0)
+    b = fill.hash_tensor((n,), 69, 2.0)
+    if n > 4:
+        a[1], a[2], a[3] = 0.0, -0.0, -1.5
+    return a, b, 1.3
+
+
+def split_inputs(N, D, nd):
+    from oracle import fill
+    x = fill.hash_tensor((N, D), 70, 2.0)
+    x.view(-1)[0::7] = 0.0
+    x.view(-1)[3::11] = -0.0
+    return x, fill.hash_tensor((N, nd), 71), fill.hash_tensor((N, D - nd), 72)
+
+
+def bn_small_inputs(N, C, mean_ratio=None):
+    """x, dy [N][C], gamma, beta, rm0, rv0 [C]; mean_ratio: every channel gets mean = +-mean_ratio * std"""
+    from oracle import fill
+    h = fill.hash_tensor
+    x = h((N, C), 73, 2.0) + 0.5
+    if mean_ratio is not None:
+        c = torch.arange(C)
+        x = x + (mean_ratio * (2.0 / 3 ** 0.5) * (1 - 2 * (c % 2).float()))[None]
+    return dict(x=x, dy=h((N, C), 74), gamma=1 + 0.2 * h((C,), 75), beta=0.1 * h((C,), 76), rm0=0.1 * h((C,), 77),
+                rv0=1 + 0.5 * h((C,), 78), dg0=h((C,), 79), db0=h((C,), 80))

@@ -826,3 +826,314 @@ def test_per_slice_check_sees_what_the_whole_tensor_bar_does_not():
     print("reverse direction shifted by one step: whole-tensor figure %.3g (bar 2e-5)" % old)
     assert old > 2e-5
     assert not F64.seq_chain_ratio(y, r64["y"], r32["y"], 0).ok
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The TabNet checkers: each accepts torch's CPU fp32 evaluation of the kernel's own formula at every shape the GPU tests use
+# (sums in double where the kernel sums in double), and rejects the slips a row kernel, a ghost-batch loop or a shared
+# weight's accumulation can make.
+# ----------------------------------------------------------------------------------------------------------------------
+from oracle import fill as _fill, tabnet_ref as _T  # noqa: E402
+
+
+def _spmax32(x, dk=0):
+    """the kernel's sparsemax in fp32 (sorted prefix sums); dk: tau from the support size k + dk (clamped to 1..D)"""
+    x = x.float()
+    v = x - x.amax(1, keepdim=True)
+    srt = v.sort(1, descending=True).values
+    cum = srt.cumsum(1)
+    ks = torch.arange(1, x.shape[1] + 1, dtype=torch.float32).view(1, -1)
+    k = ((1 + ks * srt) > cum).sum(1, keepdim=True)
+    k = (k + dk).clamp(1, x.shape[1])
+    tau = (cum.gather(1, k - 1) - 1) / k.float()
+    return (v - tau).clamp_min(0)
+
+
+def _spmax_bwd32(p, dp):
+    sup = p > 0
+    vhat = (dp * sup).sum(1, keepdim=True) / sup.sum(1, keepdim=True).clamp_min(1).float()
+    return torch.where(sup, dp - vhat, torch.zeros_like(dp))
+
+
+@pytest.mark.parametrize("D", F64.SPMAX_D)
+@pytest.mark.parametrize("family", F64.SPMAX_FAMILIES)
+def test_sparsemax_checker_accepts_torch_fp32(family, D):
+    for N in F64.TAB_ROWS:
+        x = F64.sparsemax_rows(N, D, family)
+        for p in (_spmax32(x), _T.sparsemax(x)):
+            F64.check_sparsemax(x, p)
+        p = _spmax32(x)
+        dp = _fill.hash_tensor((N, D), 81)
+        F64.check_sparsemax_bwd(p, dp, _spmax_bwd32(p, dp))
+
+
+def test_sparsemax_families_reach_their_edges():
+    """the tie family puts exact ties on the threshold, the dominant family has leads of exactly 1 and none below it, and
+    the hash family reaches every support size"""
+    x = F64.sparsemax_rows(257, 5, "ties")
+    z = (x - x.amax(1, keepdim=True)).double()
+    p, _, k = F64.sparsemax_ref(x)
+    zs = z.sort(1, descending=True).values
+    tau = (zs.cumsum(1) - 1) / torch.arange(1, 6, dtype=torch.float64)
+    on = (zs[:, 1:] == tau[:, :-1]).any(1)          # z_(k+1) == tau_k: an entry exactly on the threshold
+    assert int(on.sum()) >= 16
+    xs = F64.sparsemax_rows(257, 5, "dominant").double().sort(1, descending=True).values
+    assert bool(((xs[:, 0] - xs[:, 1]) == 1).any()) and bool(((xs[:, 0] - xs[:, 1]) >= 1).all())
+    assert set(int(v) for v in F64.sparsemax_ref(F64.sparsemax_rows(513, 5, "hash"))[2]) == {1, 2, 3, 4, 5}
+
+
+@pytest.mark.parametrize("D", [3, 5, 63, 64])
+@pytest.mark.parametrize("dk", [-1, 1])
+def test_sparsemax_checker_rejects_a_support_size_off_by_one(D, dk):
+    x = F64.sparsemax_rows(257, D, "hash")
+    assert _fails(lambda: F64.check_sparsemax(x, _spmax32(x, dk)))
+    xp = F64.sparsemax_rows(257, D, "prior")
+    assert _fails(lambda: F64.check_sparsemax(xp, _spmax32(xp, dk)))
+
+
+def test_sparsemax_checkers_reject_a_skipped_row_block_and_a_wrong_mean():
+    x = F64.sparsemax_rows(513, 5, "hash")
+    p = _spmax32(x)
+    dp = _fill.hash_tensor((513, 5), 81)
+    stale = p.clone()
+    stale[256:512] = 0.0
+    assert _fails(lambda: F64.check_sparsemax(x, stale))
+    dx = _spmax_bwd32(p, dp)
+    skipped = dx.clone()
+    skipped[256:512] = 0.0
+    assert _fails(lambda: F64.check_sparsemax_bwd(p, dp, skipped))
+    assert _fails(lambda: F64.check_sparsemax_bwd(p, dp, dp - dp.mean(1, keepdim=True)))        # mean over the row, not the support
+    leak = dx.clone()
+    leak[p == 0] = 1e-30
+    assert _fails(lambda: F64.check_sparsemax_bwd(p, dp, leak))                                 # outside the support: exactly 0
+
+
+def _glu32(z, dout, swap=False, no_1ms=False):
+    D = z.shape[1] // 2
+    a, b = (z[:, D:], z[:, :D]) if swap else (z[:, :D], z[:, D:])
+    s = 1.0 / (1.0 + torch.exp(-b))
+    dzb = dout * a * s if no_1ms else dout * a * s * (1.0 - s)
+    return a * s, torch.cat([dout * s, dzb], 1)
+
+
+@pytest.mark.parametrize("extreme", [False, True])
+@pytest.mark.parametrize("D", F64.GLU_D)
+def test_glu_checker_accepts_torch_fp32_and_rejects_swapped_halves_and_a_missing_factor(D, extreme):
+    for N in F64.TAB_ROWS:
+        z, dout = F64.glu_inputs(N, D, extreme)
+        out, dz = _glu32(z, dout)
+        F64.check_glu(z, out, dout, dz)
+        zz = z.clone().requires_grad_(True)
+        o2 = zz[:, :D] * torch.sigmoid(zz[:, D:])
+        o2.backward(dout)
+        F64.check_glu(z, o2.detach(), dout, zz.grad)
+        assert _fails(lambda: F64.check_glu(z, _glu32(z, dout, swap=True)[0]))
+        if N * D > 4:
+            assert _fails(lambda: F64.check_glu(z, out, dout, _glu32(z, dout, no_1ms=True)[1]))
+    if extreme:
+        nan = out.clone()
+        nan[0, 0] = float("nan")
+        assert _fails(lambda: F64.check_glu(z, nan))
+
+
+def _entropy32(M, g, eps=F64.ENT_EPS, div=None):
+    N = M.shape[0]
+    e = torch.tensor(eps, dtype=torch.float32)
+    term = M * torch.log(M + e)
+    out = (term.double().sum() / (div or N)).float().reshape(1)
+    dM = (g / torch.tensor(float(N))) * (torch.log(M + e) + M / (M + e))
+    return out, dM
+
+
+@pytest.mark.parametrize("D", [2, 5, 64])
+def test_entropy_checker_accepts_torch_fp32_and_rejects_a_mean_over_every_element(D):
+    for N in F64.TAB_ROWS:
+        M, g = F64.entropy_inputs(N, D)
+        out, dM = _entropy32(M, g)
+        F64.check_entropy(M, out, F64.ENT_EPS, g, dM)
+        assert _fails(lambda: F64.check_entropy(M, _entropy32(M, g, div=N * D)[0]))
+        assert _fails(lambda: F64.check_entropy(M, None, F64.ENT_EPS, g, dM / D))
+    assert float(_entropy32(torch.zeros(7, D), g)[0]) == 0.0
+    F64.check_entropy(torch.zeros(7, D), torch.zeros(1))
+
+
+def _ew32(op, a, b, s):
+    s = torch.tensor(s, dtype=torch.float32)
+    return {"MUL": lambda: a * b, "ADD_SCALE": lambda: (a + b) * s, "PRIOR": lambda: b * (s - a), "RELU": lambda: a.clamp_min(0),
+            "RELU_BWD": lambda: torch.where(a > 0, b, torch.zeros_like(a)), "SCALE": lambda: a * s, "NEG_MUL": lambda: -a * b,
+            "ADD": lambda: a + b, "RSUB": lambda: s - a}[op]()
+
+
+@pytest.mark.parametrize("op", list(F64.EW_OPS))
+def test_ew_checker_accepts_torch_fp32_and_rejects_an_unwritten_tail(op):
+    for n in (1, 257, F64.EW_GRID_CAP + 257):
+        a, b, s = F64.ew_inputs(n)
+        out = _ew32(op, a, b if F64.EW_ARITY[op] == 2 else None, s)
+        F64.check_ew(op, a, b if F64.EW_ARITY[op] == 2 else None, s, out)
+    tail = out.clone()
+    tail[F64.EW_GRID_CAP:] = 0.0
+    assert _fails(lambda: F64.check_ew(op, a, b if F64.EW_ARITY[op] == 2 else None, s, tail))
+    if op in F64.EW_EXACT and op not in ("RELU", "RELU_BWD"):
+        off = out.clone()
+        off[5] = torch.nextafter(off[5], torch.tensor(float("inf")))
+        assert _fails(lambda: F64.check_ew(op, a, b if F64.EW_ARITY[op] == 2 else None, s, off))     # one ulp is not exact
+
+
+@pytest.mark.parametrize("N,D,nd", F64.SPLIT_CASES)
+def test_split_reference_is_the_slice_and_its_mask(N, D, nd):
+    x, gd, ga = F64.split_inputs(N, D, nd)
+    assert bool((x == 0).any()) or N * D < 8
+    for relu in (0, 1):
+        d, a = F64.split_ref(x, nd, relu)
+        xr = x.clone().requires_grad_(True)
+        dd = torch.relu(xr[:, :nd]) if relu else xr[:, :nd]
+        (dd * gd).sum().backward()
+        assert torch.equal(d, dd.detach()) and torch.equal(a, x[:, nd:])
+        assert torch.equal(F64.split_bwd_ref(d, gd, None, D, nd, relu), xr.grad)
+        assert torch.equal(F64.split_bwd_ref(d, None, ga, D, nd, relu)[:, nd:], ga)
+
+
+def _bn32(x, gamma, beta, rm0, rv0, momentum, eps, training, biased=False):
+    """the kernel's bn_small forward: statistics in double, stored as fp32, the affine in fp32 -> y, save, rm, rv"""
+    N, C = x.shape
+    g = torch.ones(C) if gamma is None else gamma
+    b = torch.zeros(C) if beta is None else beta
+    rm, rv = (None, None) if rm0 is None else (rm0.clone(), rv0.clone())
+    if training:
+        xd = x.double()
+        mean = xd.sum(0) / N
+        var = ((xd * xd).sum(0) / N - mean * mean).clamp_min(0)
+        if rm is not None:
+            mom = torch.tensor(momentum, dtype=torch.float32)
+            unb = var if biased or N == 1 else var * N / (N - 1.0)
+            rm = (1 - mom) * rm + mom * mean.float()
+            rv = (1 - mom) * rv + mom * unb.float()
+    else:
+        mean, var = rm0.double(), rv0.double()
+    inv = (1.0 / (var + float(torch.tensor(eps, dtype=torch.float32))).sqrt()).float()
+    m = mean.float()
+    return (x - m) * inv * g + b, torch.stack([m, inv]), rm, rv
+
+
+def _bn_bwd32(x, dy, gamma, save, training, dg0=None, db0=None):
+    N, C = x.shape
+    g = torch.ones(C) if gamma is None else gamma
+    m, inv = save[0], save[1]
+    xh = (x - m) * inv
+    s1 = dy.double().sum(0).float()
+    s2 = (dy.double() * xh.double()).sum(0).float()
+    if training:
+        dx = (g * inv) * (dy - s1 / N - xh * (s2 / N))
+    else:
+        dx = dy * (g * inv)
+    return dx, (s2 if dg0 is None else dg0 + s2), (s1 if db0 is None else db0 + s1)
+
+
+@pytest.mark.parametrize("training", [1, 0])
+@pytest.mark.parametrize("C", F64.BN_SMALL_C)
+def test_bn_small_checkers_accept_torch_fp32(C, training):
+    for N in F64.BN_SMALL_N:
+        for ratio in (None, 1e3):
+            for momentum in (0.01, 0.02):
+                d = F64.bn_small_inputs(N, C, ratio)
+                y, save, rm, rv = _bn32(d["x"], d["gamma"], d["beta"], d["rm0"], d["rv0"], momentum, 1e-5, training)
+                F64.check_bn_small_fwd(d["x"], d["gamma"], d["beta"], d["rm0"], d["rv0"], 5, momentum, 1e-5, training, y, save, rm, rv,
+                                       5 + training)
+                for acc in (0, 1):
+                    dg0, db0 = (d["dg0"], d["db0"]) if acc else (None, None)
+                    dx, dg, db = _bn_bwd32(d["x"], d["dy"], d["gamma"], save, training, dg0, db0)
+                    F64.check_bn_small_bwd(d["x"], d["dy"], d["gamma"], save, training, dx, dg, db, dg0, db0)
+
+
+def test_bn_small_checkers_reject_their_defects():
+    N, C = 65, 3
+    d = F64.bn_small_inputs(N, C)
+    args = (d["x"], d["gamma"], d["beta"], d["rm0"], d["rv0"])
+    y, save, rm, rv = _bn32(*args, 0.02, 1e-5, 1)
+    fwd = lambda y=y, save=save, rm=rm, rv=rv, nbt=6: F64.check_bn_small_fwd(*args, 5, 0.02, 1e-5, 1, y, save, rm, rv, nbt)
+    fwd()
+    assert _fails(lambda: fwd(rv=_bn32(*args, 0.02, 1e-5, 1, biased=True)[3]))          # biased variance in the running update
+    assert _fails(lambda: fwd(rm=_bn32(*args, 0.01, 1e-5, 1)[2]))                       # the other momentum
+    assert _fails(lambda: fwd(nbt=5))
+    big = F64.bn_small_inputs(513, C)
+    yb, sb, _, _ = _bn32(big["x"], big["gamma"], big["beta"], None, None, 0.02, 1e-5, 1)
+    y256, s256, _, _ = _bn32(big["x"][:256], big["gamma"], big["beta"], None, None, 0.02, 1e-5, 1)      # the stride loop not taken
+    chk = lambda y, s: F64.check_bn_small_fwd(big["x"], big["gamma"], big["beta"], None, None, None, 0.02, 1e-5, 1, y, s, None, None, None)
+    chk(yb, sb)
+    assert _fails(lambda: chk(yb, s256))
+    dx, dg, db = _bn_bwd32(big["x"], big["dy"], big["gamma"], sb, 1)
+    bwd = lambda **kw: F64.check_bn_small_bwd(big["x"], big["dy"], big["gamma"], sb, 1, **kw)
+    bwd(dx=dx, dgamma=dg, dbeta=db)
+    part = _bn_bwd32(big["x"][:512], big["dy"][:512], big["gamma"], sb, 1)
+    assert _fails(lambda: bwd(dgamma=part[1])) and _fails(lambda: bwd(dbeta=part[2]))   # the 513th row missing from the sums
+    skipped = dx.clone()
+    skipped[256:512] = 0.0
+    assert _fails(lambda: bwd(dx=skipped))
+    assert _fails(lambda: F64.check_bn_small_bwd(big["x"], big["dy"], big["gamma"], sb, 1, dgamma=dg, dg0=big["dg0"], db0=big["db0"]))
+    assert _fails(lambda: F64.check_bn_small_bwd(big["x"], big["dy"], big["gamma"], sb, 0, dx=dx))   # eval has no mean terms
+
+
+def _ghost32(d, B, vbs, training, momentum=0.02, slices=None, keep_last=False):
+    sl = slices or F64.ghost_slices(B, vbs)
+    rm, rv = d["rm0"], d["rv0"]
+    ys, saves, dxs, dg, db = [], [], [], None, None
+    for i0, i1 in sl:
+        y, save, rm_, rv_ = _bn32(d["x"][i0:i1], d["gamma"], d["beta"], rm, rv, momentum, 1e-5, training)
+        if training:
+            rm, rv = rm_, rv_
+        dx, dg_, db_ = _bn_bwd32(d["x"][i0:i1], d["dy"][i0:i1], d["gamma"], save, training, None if keep_last else dg,
+                                 None if keep_last else db)
+        dg, db = dg_, db_
+        ys.append(y); saves.append(save); dxs.append(dx)
+    return dict(y=torch.cat(ys), save=torch.stack(saves), rm=rm, rv=rv, nbt=5 + (len(sl) if training else 0), dx=torch.cat(dxs),
+                dgamma=dg, dbeta=db)
+
+
+def _ghost_check(d, B, vbs, training, o):
+    return F64.check_ghost_bn(d["x"], d["gamma"], d["beta"], d["rm0"], d["rv0"], 5, 0.02, 1e-5, vbs, training, o["y"], o["save"],
+                              o["rm"], o["rv"], o["nbt"], d["dy"], o["dx"], o["dgamma"], o["dbeta"])
+
+
+@pytest.mark.parametrize("training", [1, 0])
+@pytest.mark.parametrize("B,vbs", F64.GHOST_CASES)
+def test_ghost_bn_checker_accepts_torch_fp32_per_chunk(B, vbs, training):
+    for C in (3, 64):
+        d = F64.bn_small_inputs(B, C)
+        _ghost_check(d, B, vbs, training, _ghost32(d, B, vbs, training))
+
+
+def test_ghost_slices_are_torch_chunks():
+    assert F64.ghost_slices(130, 128) == [(0, 65), (65, 130)] and F64.ghost_slices(257, 16)[-1] == (256, 257)
+    assert F64.ghost_slices(300, 128) == [(0, 100), (100, 200), (200, 300)] and F64.ghost_slices(7, None) == [(0, 7)]
+    for B in (2, 129, 385, 50):
+        for vbs in (128, 16):
+            sizes = [c.shape[0] for c in torch.zeros(B, 1).chunk(-(-B // vbs))]
+            assert [b - a for a, b in F64.ghost_slices(B, vbs)] == sizes
+
+
+def test_ghost_bn_checker_rejects_fixed_size_slices_and_a_dropped_virtual_batch():
+    B, vbs, C = 130, 128, 3
+    d = F64.bn_small_inputs(B, C)
+    good = _ghost32(d, B, vbs, 1)
+    _ghost_check(d, B, vbs, 1, good)
+    assert _fails(lambda: _ghost_check(d, B, vbs, 1, _ghost32(d, B, vbs, 1, slices=[(0, 128), (128, 130)])))    # 128 + 2, not 65 + 65
+    last = _ghost32(d, B, vbs, 1, keep_last=True)
+    assert _fails(lambda: _ghost_check(d, B, vbs, 1, dict(good, dgamma=last["dgamma"])))                        # only the last slice's dgamma
+    assert _fails(lambda: _ghost_check(d, B, vbs, 1, dict(good, dbeta=last["dbeta"])))
+    assert _fails(lambda: _ghost_check(d, B, vbs, 1, dict(good, nbt=6)))                                        # one step per slice
+    one = _ghost32(d, B, vbs, 1, slices=[(0, 65)])
+    assert _fails(lambda: _ghost_check(d, B, vbs, 1, dict(good, rm=one["rm"])))                                 # the second update missing
+
+
+def test_shared_weight_gradient_check_rejects_a_missing_use():
+    B, In, Out = 130, 64, 128
+    pairs = [(_fill.hash_tensor((B, In), 90 + i), _fill.hash_tensor((B, Out), 95 + i)) for i in range(4)]
+    ref, A, K = F64.shared_dw_ref(pairs)
+    assert K == 4 * B
+    dw = sum(dy.t() @ x for x, dy in pairs)
+    assert F64.dot_ratio(dw, ref, A, K).ok
+    for miss in range(4):
+        part = sum(dy.t() @ x for i, (x, dy) in enumerate(pairs) if i != miss)
+        assert not F64.dot_ratio(part, ref, A, K).ok
+    twice = dw + pairs[0][1].t() @ pairs[0][0]
+    assert not F64.dot_ratio(twice, ref, A, K).ok
