@@ -24,6 +24,8 @@ class Config:
     physionet_dir = "./data/physionet"
     physionet_data_dir = "./data/physionet/training2017"
     physionet_label_file = os.path.join(physionet_dir, "REFERENCE.csv")
+    ptbxl_dir = "./data/ptb_xl"                                         # train_signal_only_ptb.py:183,223
+    ptbxl_database = os.path.join(ptbxl_dir, "ptbxl_database.csv")
 
     # Model
     num_classes = 2

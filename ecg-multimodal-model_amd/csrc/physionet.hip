@@ -7,6 +7,8 @@
 //                            record, the odd-extended record resident in LDS, the time axis cut into 64 odd-length chunks.
 //   signal_gather_augment -- out[i] = augment(src[index[i]]): the batch gather fused with augment_signal
 //                            (noise N(0, sigma^2) -> scale U[lo, hi) -> circular roll), Philox4x32-10 as in head.hip.
+//   weighted_sample       -- WeightedRandomSampler(weights, count, replacement=True) = torch.multinomial with replacement
+//                            (train_signal_only_ptb.py:230-235,241): one epoch's indices in one launch.
 #include "ops.h"
 
 namespace {
@@ -167,6 +169,8 @@ void launch_fz(const FzParams& p, size_t lds, hipStream_t st) {
 //   c0, c1 = the call's 64-bit offset;  c2 = the row's position i within the call;
 //   c3 = 0x80000000 | g  for the noise of output elements 4g .. 4g+3,  0xFFFFFFFF / 0xFFFFFFFE for the row's decisions.
 // c3 is never 0, so no counter of this kernel coincides with one of the dropout stream (c2 = c3 = 0) under the same seed.
+// weighted_sample_kernel: c0, c1 = the call's offset; c2 = the draw's position i; c3 = 0xFFFFFFFD, which is neither 0, nor a
+// row decision, nor a noise group (g < 2^28 since L <= 2^30, so 0x80000000 | g <= 0x8FFFFFFF).
 __device__ __forceinline__ void philox4(unsigned long long seed, unsigned c0, unsigned c1, unsigned c2, unsigned c3,
                                         unsigned* r) {
   const unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
@@ -273,7 +277,52 @@ __global__ __launch_bounds__(256) void signal_gather_augment_kernel(GaParams p) 
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// sampling with replacement from a weight vector
+// ------------------------------------------------------------------------------------------------
+struct WsParams {
+  const double* cdf;         // [n] inclusive prefix sum of the weights
+  long long* out;            // [count]
+  double* u_out;             // [count] or null
+  long long n, count, last;  // last: the last index of positive weight
+  unsigned long long seed, offset;
+};
+
+// One draw per thread: a 53-bit uniform from two Philox words, then the first j with cdf[j] > u * cdf[n-1] by binary search.
+// cdf[j] > x >= cdf[j-1] makes weight j positive, so an index of weight 0 is never returned; when the product rounds up to
+// cdf[n-1] itself no such j exists and the draw goes to `last`.  Every probe index lies in [0, n).
+__global__ __launch_bounds__(256) void weighted_sample_kernel(WsParams p) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.count) return;
+  unsigned r[4];
+  philox4(p.seed, (unsigned)p.offset, (unsigned)(p.offset >> 32), (unsigned)i, 0xFFFFFFFDu, r);
+  const double u = ((double)(r[0] >> 5) * 67108864.0 + (double)(r[1] >> 6)) * (1.0 / 9007199254740992.0);   // [0, 1)
+  const double x = u * p.cdf[p.n - 1];
+  long long lo = 0, hi = p.n;
+  while (lo < hi) {
+    const long long mid = lo + ((hi - lo) >> 1);
+    if (p.cdf[mid] > x) hi = mid; else lo = mid + 1;
+  }
+  p.out[i] = lo < p.n ? lo : p.last;
+  if (p.u_out) p.u_out[i] = u;
+}
+
 }  // namespace
+
+extern "C" int ecgmm_weighted_sample(const double* cdf, int64_t n, int64_t last_positive, int64_t* out, double* u_out,
+                                     int64_t count, uint64_t seed, uint64_t offset, void* stream) {
+  if (!cdf || !out) ECG_FAIL(ECGMM_ERR_SHAPE, "weighted_sample: null operand");
+  if (n < 1 || count < 1 || count > 0x7fffffffLL || last_positive < 0 || last_positive >= n)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "weighted_sample: need n >= 1, 1 <= count < 2^31, 0 <= last_positive < n (n=%lld count=%lld last=%lld)",
+             (long long)n, (long long)count, (long long)last_positive);
+  WsParams q;
+  memset(&q, 0, sizeof(q));
+  q.cdf = cdf; q.out = (long long*)out; q.u_out = u_out; q.n = n; q.count = count; q.last = last_positive;
+  q.seed = seed; q.offset = offset;
+  hipLaunchKernelGGL(weighted_sample_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream, q);
+  ECG_CHECK_LAUNCH("weighted_sample");
+  return 0;
+}
 
 extern "C" int ecgmm_signal_filter_zscore(const float* x, float* out, int S, int L, const double* b, const double* a,
                                           const double* zi, int order, int zscore, double eps, void* stream) {

@@ -20,6 +20,12 @@ struct PreParams {
   double* ws;              // [L + E][S]
   int S, L, window, order;
   double b[8], a[8], zi[8];
+  // WFDB format-16 rows (ecgmm_signal_preprocess_i16): row s = (record s / nc, channel chan[s % nc]); L is then Lf
+  const int16_t* raw;      // [R][T][nsig], the .dat payload
+  const double* gain;      // [R][nc]
+  const int* baseline;     // [R][nc]
+  int T, nsig, nc, step, out_len;
+  int chan[16];
 };
 
 __global__ __launch_bounds__(64) void signal_preprocess_kernel(PreParams p) {
@@ -82,7 +88,9 @@ __global__ __launch_bounds__(64) void signal_preprocess_kernel(PreParams p) {
 //       0..N-1 running C zero-input steps from the unit states);
 //   (3) every lane re-filters its chunk from its true entry state, writing y in place.
 // C is forced odd so the 64 lanes' chunk cursors (stride C doubles) fall in distinct LDS banks.
-template <int N>
+// I16: the loader decodes int16 frames (sample t = frame t*step, one channel of nsig) and the epilogue crops or zero-pads
+// to out_len; everything between the two is the same code for both row sources.
+template <int N, bool I16>
 __global__ __launch_bounds__(64) void signal_preprocess_lds_kernel(PreParams p) {
   extern __shared__ double sm[];
   constexpr int T = 64, PAD = 3 * (N + 1);
@@ -96,11 +104,24 @@ __global__ __launch_bounds__(64) void signal_preprocess_lds_kernel(PreParams p) 
 #pragma unroll
   for (int i = 0; i <= N; ++i) { b[i] = p.b[i]; a[i] = p.a[i]; }
 
-  const float* xr = p.x + (size_t)s * L;
-  for (int t = lane; t < L; t += T) {
-    double v = (double)xr[t];
-    if (p.sc_mean) v = (v - (double)p.sc_mean[t]) / (double)p.sc_scale[t];
-    A[t] = v;
+  if constexpr (I16) {
+    // p_signal of wfdb: (d - baseline) / gain in float64 (int16 -> double is exact); -32768 is the format's invalid-sample
+    // code and becomes NaN.  2-byte loads step*nsig*2 bytes apart: uncoalesced, and dwarfed by the recurrences below.
+    const int r = s / p.nc, c = s - r * p.nc;
+    const int16_t* xr = p.raw + (size_t)r * p.T * p.nsig + p.chan[c];
+    const double g = p.gain[s], bl = (double)p.baseline[s];
+    const size_t stride = (size_t)p.step * p.nsig;
+    for (int t = lane; t < L; t += T) {
+      const int d = xr[(size_t)t * stride];
+      A[t] = d == -32768 ? __builtin_nan("") : ((double)d - bl) / g;
+    }
+  } else {
+    const float* xr = p.x + (size_t)s * L;
+    for (int t = lane; t < L; t += T) {
+      double v = (double)xr[t];
+      if (p.sc_mean) v = (v - (double)p.sc_mean[t]) / (double)p.sc_scale[t];
+      A[t] = v;
+    }
   }
   const int C = ((E + T - 1) / T) | 1;
   if (lane < N) {  // column `lane` of A^C
@@ -199,16 +220,38 @@ __global__ __launch_bounds__(64) void signal_preprocess_lds_kernel(PreParams p) 
     }
     __syncthreads();
   }
-  float* orow = p.out + (size_t)s * L;
-  for (int t = lane; t < L; t += T) orow[t] = (float)B[PAD + t];
+  if constexpr (I16) {  // signal[:out_len], or the signal followed by zeros (train_signal_only_ptb.py:48-52)
+    float* orow = p.out + (size_t)s * p.out_len;
+    for (int t = lane; t < p.out_len; t += T) orow[t] = t < L ? (float)B[PAD + t] : 0.0f;
+  } else {
+    float* orow = p.out + (size_t)s * L;
+    for (int t = lane; t < L; t += T) orow[t] = (float)B[PAD + t];
+  }
 }
 
-template <int N>
+constexpr size_t PRE_LDS_MAX = 160 * 1024;
+// scaled copy [L] + odd-extended signal [L + 6(N+1)] + chunk states [64][8] + A^C [8][8], all fp64
+inline size_t pre_lds_bytes(int L, int order) { return ((size_t)L + L + 6 * (order + 1) + 64 * 8 + 64) * sizeof(double); }
+
+template <int N, bool I16>
 int launch_lds(const PreParams& p, size_t lds, hipStream_t st) {
-  (void)hipFuncSetAttribute((const void*)signal_preprocess_lds_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024);
-  hipLaunchKernelGGL(signal_preprocess_lds_kernel<N>, dim3(p.S), dim3(64), lds, st, p);
+  (void)hipFuncSetAttribute((const void*)signal_preprocess_lds_kernel<N, I16>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)PRE_LDS_MAX);
+  hipLaunchKernelGGL((signal_preprocess_lds_kernel<N, I16>), dim3(p.S), dim3(64), lds, st, p);
   return 0;
+}
+
+template <bool I16>
+void launch_lds_order(const PreParams& p, size_t lds, hipStream_t st) {
+  switch (p.order) {
+    case 1: launch_lds<1, I16>(p, lds, st); break;
+    case 2: launch_lds<2, I16>(p, lds, st); break;
+    case 3: launch_lds<3, I16>(p, lds, st); break;
+    case 4: launch_lds<4, I16>(p, lds, st); break;
+    case 5: launch_lds<5, I16>(p, lds, st); break;
+    case 6: launch_lds<6, I16>(p, lds, st); break;
+    default: launch_lds<7, I16>(p, lds, st); break;
+  }
 }
 
 }  // namespace
@@ -236,21 +279,51 @@ extern "C" int ecgmm_signal_preprocess(const float* x, float* out, int S, int L,
   for (int i = 0; i < order; ++i) p.zi[i] = zi[i];
   // LDS-resident chunk-parallel kernel whenever one padded signal (+ the scaled copy) fits one CU's LDS;
   // longer records take the one-lane-per-signal kernel over the global workspace.
-  const size_t lds = ((size_t)L + L + 6 * (order + 1) + 64 * 8 + 64) * sizeof(double);
-  if (lds <= 160 * 1024) {
-    hipStream_t st = (hipStream_t)stream;
-    switch (order) {
-      case 1: launch_lds<1>(p, lds, st); break;
-      case 2: launch_lds<2>(p, lds, st); break;
-      case 3: launch_lds<3>(p, lds, st); break;
-      case 4: launch_lds<4>(p, lds, st); break;
-      case 5: launch_lds<5>(p, lds, st); break;
-      case 6: launch_lds<6>(p, lds, st); break;
-      default: launch_lds<7>(p, lds, st); break;
-    }
+  const size_t lds = pre_lds_bytes(L, order);
+  if (lds <= PRE_LDS_MAX) {
+    launch_lds_order<false>(p, lds, (hipStream_t)stream);
   } else {
     hipLaunchKernelGGL(signal_preprocess_kernel, dim3(ceil_div(S, 64)), dim3(64), 0, (hipStream_t)stream, p);
   }
   ECG_CHECK_LAUNCH("signal_preprocess");
+  return 0;
+}
+
+// WFDB format-16 frames -> the PTB-XL trainer's rows, one launch (train_signal_only_ptb.py:40-53).  Every check is on the
+// host and no device address is formed from data: chan[] is validated here, gain / baseline are read at [row].
+extern "C" int ecgmm_signal_preprocess_i16(const int16_t* raw, int R, int T, int nsig, const int* chan, int nc,
+                                           const double* gain, const int* baseline, int step, float* out, int out_len,
+                                           int window, const double* b, const double* a, const double* zi, int order,
+                                           void* stream) {
+  if (order < 1 || order > 7) ECG_FAIL(ECGMM_ERR_SHAPE, "signal_preprocess_i16: filter order %d outside 1..7", order);
+  if (!raw || !chan || !gain || !baseline || !out || !b || !a || !zi)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "signal_preprocess_i16: null operand");
+  if (R < 1 || T < 1 || nsig < 1 || nc < 1 || nc > 16 || step < 1 || out_len < 1 || window < 1)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "signal_preprocess_i16: need R, T, nsig, step, out_len, window >= 1 and 1 <= nc <= 16 "
+             "(R=%d T=%d nsig=%d nc=%d step=%d out_len=%d window=%d)", R, T, nsig, nc, step, out_len, window);
+  for (int i = 0; i < nc; ++i)
+    if (chan[i] < 0 || chan[i] >= nsig)
+      ECG_FAIL(ECGMM_ERR_SHAPE, "signal_preprocess_i16: channel %d (entry %d) outside the record's %d signals", chan[i], i, nsig);
+  if ((long long)R * nc > 0x7fffffffLL) ECG_FAIL(ECGMM_ERR_SHAPE, "signal_preprocess_i16: %d x %d rows exceed the grid", R, nc);
+  const int Lf = (T + step - 1) / step;
+  if (Lf < window || Lf <= 3 * (order + 1))
+    ECG_FAIL(ECGMM_ERR_SHAPE, "signal_preprocess_i16: need Lf >= window and Lf > 3*(order+1) (T=%d step=%d Lf=%d window=%d)",
+             T, step, Lf, window);
+  if (a[0] != 1.0) ECG_FAIL(ECGMM_ERR_SHAPE, "signal_preprocess_i16: a[0] must be 1 (normalised transfer function)");
+  // a row that would take the whole 160 KiB is refused as well: Lf <= 9933 at order 5
+  const size_t lds = pre_lds_bytes(Lf, order);
+  if (lds >= PRE_LDS_MAX)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "signal_preprocess_i16: a row of %d samples does not fit one CU's LDS (largest Lf at order %d: %d); "
+             "there is no workspace route", Lf, order, (int)((PRE_LDS_MAX / sizeof(double) - 1 - 6 * (order + 1) - 64 * 8 - 64) / 2));
+  PreParams p;
+  memset(&p, 0, sizeof(p));
+  p.raw = raw; p.gain = gain; p.baseline = baseline; p.out = out;
+  p.S = R * nc; p.L = Lf; p.window = window; p.order = order;
+  p.T = T; p.nsig = nsig; p.nc = nc; p.step = step; p.out_len = out_len;
+  for (int i = 0; i < nc; ++i) p.chan[i] = chan[i];
+  for (int i = 0; i <= order; ++i) { p.b[i] = b[i]; p.a[i] = a[i]; }
+  for (int i = 0; i < order; ++i) p.zi[i] = zi[i];
+  launch_lds_order<true>(p, lds, (hipStream_t)stream);
+  ECG_CHECK_LAUNCH("signal_preprocess_i16");
   return 0;
 }

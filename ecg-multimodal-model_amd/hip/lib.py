@@ -159,6 +159,9 @@ SIGNATURES = {
     "ecgmm_axpby": (i32, [f32, vp, f32, vp, i64, vp]),
     "ecgmm_signal_preprocess_workspace": (sz, [i32, i32, i32]),
     "ecgmm_signal_preprocess": (i32, [vp, vp, i32, i32, vp, vp, i32, P(f64), P(f64), P(f64), i32, vp, sz, vp]),
+    "ecgmm_signal_preprocess_i16": (i32, [vp, i32, i32, i32, P(i32), i32, vp, vp, i32, vp, i32, i32, P(f64), P(f64), P(f64),
+                                          i32, vp]),
+    "ecgmm_weighted_sample": (i32, [vp, i64, i64, vp, vp, i64, u64, u64, vp]),
     "ecgmm_signal_filter_zscore": (i32, [vp, vp, i32, i32, P(f64), P(f64), P(f64), i32, i32, f64, vp]),
     "ecgmm_signal_gather_augment": (i32, [vp, i64, i32, vp, i32, vp, vp, i32, f32, f32, f32, f32, i32, i32, u64, u64, vp]),
     "ecgmm_glu_fwd": (i32, [vp, vp, i64, i32, vp]),
@@ -237,7 +240,9 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  # the log-spectrogram (ecgmm/spectrogram.py, csrc/spectrogram.hip)
                  "ecgmm_log_spectrogram_frames", "ecgmm_log_spectrogram",
                  # the SE MLP per-op (csrc/head_fused.hip)
-                 "ecgmm_se_mlp_fwd", "ecgmm_se_mlp_bwd")
+                 "ecgmm_se_mlp_fwd", "ecgmm_se_mlp_bwd",
+                 # the PTB-XL path (ecgmm/train_signal_only_ptb.py)
+                 "ecgmm_signal_preprocess_i16", "ecgmm_weighted_sample")
 
 _lib = None
 

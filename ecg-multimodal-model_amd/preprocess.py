@@ -123,3 +123,72 @@ def remove_baseline_drift(signal, window_size=200):
     L.check(lib.ecgmm_signal_preprocess(ptr(x), ptr(out), S, Ln, None, None, int(window_size), one, one, zi, 1,
                                         ptr(ws), ws.numel(), stream()), "remove_baseline_drift")
     return out.reshape(shape)
+
+
+def preprocess_i16(raw, channels, gain, baseline, step=2, out_len=None, window_size=200, cutoff=40, fs=250, order=5):
+    """WFDB format-16 frames -> the PTB-XL trainer's rows in one launch (train_signal_only_ptb.py:40-53): per record and
+    channel ``rdsamp`` decode ``(d - baseline) / gain`` in float64 (-32768 -> NaN) -> ``[::step]`` -> remove_baseline_drift
+    -> lowpass_filter(cutoff, fs, order) -> ``[:out_len]`` or zero padding up to ``out_len``.
+
+    raw: CUDA int16 [R, T, nsig], the ``.dat`` payloads as on disk; channels: up to 16 signal numbers; gain (float64) and
+    baseline (int) [R, len(channels)], host or device.  -> fp32 [R, len(channels), out_len] (default: all ceil(T / step))."""
+    _require_cuda(raw, "preprocess_i16")
+    if raw.dtype != torch.int16 or raw.dim() != 3 or not raw.is_contiguous():
+        raise ValueError("preprocess_i16: raw must be a contiguous int16 [R, T, nsig] tensor")
+    R, T, nsig = raw.shape
+    chan = [int(c) for c in channels]
+    nc = len(chan)
+    if not 1 <= nc <= 16:
+        raise ValueError(f"preprocess_i16: 1 to 16 channels per launch, got {nc}")
+    step = int(step)
+    if step < 1:
+        raise ValueError(f"preprocess_i16: step must be >= 1, got {step}")
+    out_len = -(-T // step) if out_len is None else int(out_len)
+    g = torch.as_tensor(np.asarray(gain.cpu() if torch.is_tensor(gain) else gain, dtype=np.float64)).reshape(-1)
+    bl = torch.as_tensor(np.asarray(baseline.cpu() if torch.is_tensor(baseline) else baseline).astype(np.int32)).reshape(-1)
+    if g.numel() != R * nc or bl.numel() != R * nc:
+        raise ValueError(f"preprocess_i16: gain and baseline must hold {R} x {nc} entries")
+    if not bool(torch.isfinite(g).all()) or bool((g == 0).any()):
+        raise ValueError("preprocess_i16: gains must be finite and non-zero")
+    g, bl = g.to(raw.device).contiguous(), bl.to(raw.device).contiguous()
+    b, a = butter_lowpass(order, cutoff / (0.5 * fs))
+    zi = lfilter_zi(b, a)
+    out = torch.empty(R, nc, max(out_len, 1), dtype=torch.float32, device=raw.device)
+    dbl = lambda v: (C.c_double * len(v))(*[float(t) for t in v])
+    L.check(L.lib().ecgmm_signal_preprocess_i16(ptr(raw), R, T, nsig, (C.c_int * nc)(*chan), nc, ptr(g), ptr(bl), step,
+                                                ptr(out), out_len, int(window_size), dbl(b), dbl(a), dbl(zi), int(order),
+                                                stream()), "signal_preprocess_i16")
+    return out
+
+
+def weight_cdf(weights):
+    """Checks of ``torch.multinomial`` (no negative, non-finite or all-zero weights) -> (float64 inclusive prefix sum,
+    last index of positive weight)."""
+    w = np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights, dtype=np.float64).reshape(-1)
+    if w.size < 1:
+        raise ValueError("weighted_sample: no weights")
+    if not np.isfinite(w).all() or (w < 0).any():
+        raise ValueError("weighted_sample: weights must be finite and non-negative (invalid multinomial distribution)")
+    if not (w > 0).any():
+        raise ValueError("weighted_sample: the weights sum to 0 (invalid multinomial distribution)")
+    cdf = np.cumsum(w)
+    if not np.isfinite(cdf[-1]):
+        raise ValueError("weighted_sample: the sum of the weights is not finite")
+    return cdf, int(np.nonzero(w > 0)[0][-1])
+
+
+def weighted_sample(cdf, last_positive, count, seed_offset=None, return_uniforms=False):
+    """``count`` indices drawn with replacement, P(j) proportional to weight j, in one launch.  cdf: CUDA float64 [n] from
+    :func:`weight_cdf`.  Randomness: the Philox stream of ``ecgmm.hip.functional`` advanced by one counter block per call,
+    or ``seed_offset=(seed, offset)``.  -> int64 [count] on the device (and the float64 uniforms the draws used)."""
+    from .hip.functional import _PhiloxState
+    _require_cuda(cdf, "weighted_sample")
+    if cdf.dtype != torch.float64 or cdf.dim() != 1 or not cdf.is_contiguous():
+        raise ValueError("weighted_sample: cdf must be a contiguous float64 vector")
+    count = int(count)
+    out = torch.empty(max(count, 1), dtype=torch.int64, device=cdf.device)
+    u = torch.empty(max(count, 1), dtype=torch.float64, device=cdf.device) if return_uniforms else None
+    seed, off = _PhiloxState.take(1) if seed_offset is None else seed_offset
+    L.check(L.lib().ecgmm_weighted_sample(ptr(cdf), cdf.numel(), int(last_positive), ptr(out), ptr(u), count, int(seed),
+                                          int(off), stream()), "weighted_sample")
+    return (out, u) if return_uniforms else out

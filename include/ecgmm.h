@@ -493,6 +493,19 @@ size_t ecgmm_signal_preprocess_workspace(int S, int L, int order);
 int ecgmm_signal_preprocess(const float* x, float* out, int S, int L, const float* sc_mean, const float* sc_scale,
                             int window, const double* b, const double* a, const double* zi, int order, void* ws,
                             size_t ws_bytes, void* stream);
+/* The same pipeline straight from WFDB format-16 frames, one launch (replaces wfdb.rdsamp(path, channels) -> [::2] ->
+ * remove_baseline_drift -> lowpass_filter -> crop or zero-pad, train_signal_only_ptb.py:40-53, per sample per epoch on CPU
+ * workers).  raw: the .dat payload of R records, int16 [R][T][nsig] as on disk; chan: nc <= 16 channel numbers (host
+ * memory, each < nsig); gain double [R][nc] and baseline int [R][nc] on the device.  Row (r, c) of out [R][nc][out_len]
+ * fp32: sample t = frame t*step of channel chan[c], Lf = ceil(T / step) samples, decoded as wfdb's p_signal
+ * (d - baseline) / gain in float64 with -32768 (the format's invalid-sample code) -> NaN, which poisons its own row only;
+ * then the moving average and filtfilt of ecgmm_signal_preprocess; out[:min(Lf, out_len)] is the result and out[Lf:] is
+ * exactly 0.0f.  One row stays resident in one CU's LDS, (2 Lf + 6 (order+1) + 576) * 8 bytes < 160 KiB (Lf <= 9933 at
+ * order 5); a longer row is refused with ECGMM_ERR_SHAPE, there is no workspace route.  Everything is checked on the host
+ * before the launch (chan[i] < nsig, Lf >= window, Lf > 3*(order+1), a[0] == 1, out_len >= 1). */
+int ecgmm_signal_preprocess_i16(const int16_t* raw, int R, int T, int nsig, const int* chan, int nc, const double* gain,
+                                const int* baseline, int step, float* out, int out_len, int window, const double* b,
+                                const double* a, const double* zi, int order, void* stream);
 
 /* PhysioNet-2017 single-lead path.  filtfilt + z-score of a whole [S][L] fp32 matrix in one launch: exactly
  * scipy.signal.filtfilt(b, a, x) (odd padding 3*(order+1), lfilter_zi initial conditions `zi`) for a general transfer
@@ -514,6 +527,15 @@ int ecgmm_signal_filter_zscore(const float* x, float* out, int S, int L, const d
 int ecgmm_signal_gather_augment(const float* src, int64_t n, int L, const int64_t* index, int B, float* out,
                                 float* decisions, int augment, float p, float sigma, float scale_lo, float scale_hi,
                                 int shift_lo, int shift_hi, uint64_t seed, uint64_t offset, void* stream);
+/* WeightedRandomSampler(weights, count, replacement=True) = torch.multinomial with replacement
+ * (train_signal_only_ptb.py:230-235,241), one launch per epoch.  cdf: the inclusive prefix sum of the n weights in float64
+ * (device); out int64 [count]; u_out (nullable) double [count], the uniform each draw used.  Draw i takes Philox4x32-10 keyed
+ * by `seed` at counter (offset, i, 0xFFFFFFFD), u = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53, and returns the first j with
+ * cdf[j] > u * cdf[n-1] (binary search); where rounding leaves no such j it returns last_positive, the last index of positive
+ * weight.  An index of weight 0 is never returned, and draw i depends on (seed, offset, i) alone.  The caller advances
+ * `offset` by one per call.  torch's own random stream is not reproduced. */
+int ecgmm_weighted_sample(const double* cdf, int64_t n, int64_t last_positive, int64_t* out, double* u_out, int64_t count,
+                          uint64_t seed, uint64_t offset, void* stream);
 
 /* SURVEY 8(f3) -- the TabNet clinical encoder of multimodal.py:109-148 (pytorch_tabnet.tab_network.TabNetNoEmbeddings:
  * third-party, source and version absent from the reference; restated from its published algorithm).  Row kernels,
