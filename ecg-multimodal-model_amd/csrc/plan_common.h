@@ -53,3 +53,26 @@ inline int se_mlp_forward(const float* m, const float* w1, const float* b1, cons
   ECG_TRY(ecg_linear_fwd(m, w1, b1, h, N, C, CR, ECGMM_ACT_RELU, nullptr, s));
   return ecg_linear_fwd(h, w2, b2, g, N, CR, C, ECGMM_ACT_SIGMOID, nullptr, s);
 }
+
+// Workspace views (ecgmm_resnet18_ws_view / ecgmm_resnet1d_ws_view): where a named tensor lies inside a plan's workspace,
+// for tests and debugging.  A plan runs its own layout_fwd / layout_bwd on ws_view_anchor() -- a base that is never
+// dereferenced (a null base makes Arena hand out null pointers) -- lists (name, pointer, bytes) and looks the name up here.
+// A null pointer marks a tensor this descriptor does not have.
+struct WsView { const char* name; const void* p; size_t bytes; };
+inline void* ws_view_anchor() {
+  alignas(256) static unsigned char anchor[256];
+  return anchor;
+}
+inline int ws_view_find(const char* who, const WsView* v, int n, const char* name, int index, size_t ws_bytes, size_t* offset,
+                        size_t* bytes) {
+  for (int i = 0; i < n; ++i) {
+    if (strcmp(v[i].name, name) != 0) continue;
+    if (!v[i].p) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: no tensor '%s' (index %d) for this descriptor", who, name, index);
+    const size_t off = (size_t)((const unsigned char*)v[i].p - (const unsigned char*)ws_view_anchor());
+    if (off + v[i].bytes > ws_bytes) ECG_FAIL(ECGMM_ERR_WORKSPACE, "%s: '%s' ends past the workspace", who, name);
+    *offset = off;
+    *bytes = v[i].bytes;
+    return 0;
+  }
+  ECG_FAIL(ECGMM_ERR_SHAPE, "%s: unknown tensor '%s' (index %d)", who, name, index);
+}

@@ -245,6 +245,64 @@ extern "C" size_t ecgmm_resnet18_bwd_workspace(const ecgmm_resnet18_desc* d) {
   return w.bytes;
 }
 
+// Offset and size of a named tensor of the forward (backward = 0) or backward workspace: a test and debugging aid that
+// launches nothing.  index: the block (0..7) for per-block tensors, 0 / 1 for X, dy, dy1, dyd, else 0.
+extern "C" int ecgmm_resnet18_ws_view(const ecgmm_resnet18_desc* d, int backward, const char* name, int index,
+                                      size_t* offset, size_t* bytes) {
+  Net18 r;
+  ECG_TRY(build(d, r));
+  if (!name || !offset || !bytes) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet18 ws_view: null argument");
+  const size_t es = dtype_size(r.d.dtype);
+  const int N = r.d.N;
+  WsView v[24];
+  int n = 0;
+  size_t total = 0;
+  if (!backward) {
+    FwdWs w;
+    layout_fwd(r, ws_view_anchor(), w);
+    total = w.bytes;
+    if (index == 0) {
+      const size_t pool = (size_t)N * r.H2 * r.W2 * 64;
+      v[n++] = {"wstem", w.wstem, ecg_stem_packed_elems(3, 7) * es};
+      v[n++] = {"y0", w.y0, (size_t)N * r.H1 * r.W1 * 64 * es};
+      v[n++] = {"coef0", w.coef0, 4 * 64 * sizeof(float)};
+      v[n++] = {"p0", w.p0, pool * es};
+      v[n++] = {"idx0", w.idx0, pool};
+      v[n++] = {"pooled", w.pooled, (size_t)N * 512 * sizeof(float)};
+    }
+    if (index >= 0 && index < 8) {
+      const Blk18& k = r.blk[index];
+      const FwdWs::B& b = w.b[index];
+      const size_t osz = (size_t)N * k.hout * k.wout * k.cout, cf = 4 * k.cout * sizeof(float);
+      const size_t w1 = (size_t)k.cout * k.cin * 9 * es, w2 = (size_t)k.cout * k.cout * 9 * es, wd = (size_t)k.cout * k.cin * es;
+      v[n++] = {"w1f", b.w1f, w1}; v[n++] = {"w1d", b.w1d, w1};
+      v[n++] = {"w2f", b.w2f, w2}; v[n++] = {"w2d", b.w2d, w2};
+      v[n++] = {"wdf", b.wdf, wd}; v[n++] = {"wdd", b.wdd, wd};
+      v[n++] = {"y1", b.y1, osz * es}; v[n++] = {"a1", b.a1, osz * es}; v[n++] = {"y2", b.y2, osz * es};
+      v[n++] = {"yd", b.yd, osz * es}; v[n++] = {"out", b.out, osz * es};
+      v[n++] = {"bits", b.bits, osz / 8};
+      v[n++] = {"coef1", b.coef1, cf}; v[n++] = {"coef2", b.coef2, cf}; v[n++] = {"coefd", b.coefd, cf};
+    }
+  } else {
+    BwdWs q;
+    layout_bwd(r, ws_view_anchor(), q);
+    total = q.bytes;
+    const size_t act = r.max_act * es;
+    const size_t big = stem_recompute(r.d.dtype) ? 0 : (size_t)N * r.H1 * r.W1 * 64 * es;
+    if (index == 0 || index == 1) {
+      v[n++] = {"X", q.X[index], act}; v[n++] = {"dy", q.dy[index], act};
+      v[n++] = {"dy1", q.dy1[index], act}; v[n++] = {"dyd", q.dyd[index], act};
+    }
+    if (index == 0) {
+      v[n++] = {"dz", q.dz, act}; v[n++] = {"da", q.da, act}; v[n++] = {"dtmp", q.dtmp, act};
+      v[n++] = {"big0", big ? q.big0 : nullptr, big}; v[n++] = {"big1", big ? q.big1 : nullptr, big};
+      v[n++] = {"dpooled", q.dpooled, (size_t)N * 512 * sizeof(float)};
+    }
+  }
+  return ws_view_find(backward ? "resnet18 ws_view (backward)" : "resnet18 ws_view (forward)", v, n, name, index, total, offset,
+                      bytes);
+}
+
 extern "C" int ecgmm_resnet18_forward(const ecgmm_resnet18_desc* d, const float* image, const void* const* params,
                                       void* const* buffers, float* feat_out, void* ws, size_t ws_bytes,
                                       void* stream_) {

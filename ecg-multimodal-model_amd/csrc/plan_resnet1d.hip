@@ -195,6 +195,68 @@ extern "C" size_t ecgmm_resnet1d_bwd_workspace(const ecgmm_resnet1d_desc* d) {
   return w.bytes;
 }
 
+// Offset and size of a named tensor of the forward (backward = 0) or backward workspace (see ecgmm_resnet18_ws_view).
+// index: the block (0..2) for per-block tensors, 0 / 1 for X, else 0.
+extern "C" int ecgmm_resnet1d_ws_view(const ecgmm_resnet1d_desc* d, int backward, const char* name, int index,
+                                      size_t* offset, size_t* bytes) {
+  Net1D r;
+  ECG_TRY(build(d, r));
+  if (!name || !offset || !bytes) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet1d ws_view: null argument");
+  const size_t es = dtype_size(r.d.dtype), f = sizeof(float);
+  const int N = r.d.N;
+  WsView v[32];
+  int n = 0;
+  size_t total = 0;
+  if (!backward) {
+    Fwd1 w;
+    layout_fwd(r, ws_view_anchor(), w);
+    total = w.bytes;
+    if (index == 0) {
+      const size_t pool = (size_t)N * r.L2 * 64;
+      v[n++] = {"wstem", w.wstem, ecg_stem_packed_elems(r.d.cin, 1) * es};
+      v[n++] = {"y0", w.y0, (size_t)N * r.L1 * 64 * es};
+      v[n++] = {"coef0", w.coef0, 4 * 64 * f};
+      v[n++] = {"p0", w.p0, pool * es};
+      v[n++] = {"idx0", w.idx0, pool};
+      v[n++] = {"pooled", w.pooled, (size_t)N * 256 * f};
+      v[n++] = {"h1", w.h1, (size_t)N * 64 * f};
+      v[n++] = {"hd", w.hd, (size_t)N * 64 * f};
+      v[n++] = {"dmask", w.dmask, (size_t)N * 64};
+    }
+    if (index >= 0 && index < 3) {
+      const Blk1& k = r.blk[index];
+      const Fwd1::B& b = w.b[index];
+      const size_t osz = (size_t)N * k.lout * k.cout, cf = 4 * k.cout * f;
+      const size_t w1 = (size_t)k.cout * k.cin * 3 * es, w2 = (size_t)k.cout * k.cout * 3 * es, wd = (size_t)k.cout * k.cin * es;
+      v[n++] = {"w1f", b.w1f, w1}; v[n++] = {"w1d", b.w1d, w1};
+      v[n++] = {"w2f", b.w2f, w2}; v[n++] = {"w2d", b.w2d, w2};
+      v[n++] = {"wdf", b.wdf, wd}; v[n++] = {"wdd", b.wdd, wd};
+      v[n++] = {"y1", b.y1, osz * es}; v[n++] = {"a1", b.a1, osz * es}; v[n++] = {"y2", b.y2, osz * es};
+      v[n++] = {"yd", b.yd, osz * es}; v[n++] = {"out", b.out, osz * es};
+      v[n++] = {"coef1", b.coef1, cf}; v[n++] = {"coef2", b.coef2, cf}; v[n++] = {"coefd", b.coefd, cf};
+      v[n++] = {"m", b.m, (size_t)N * k.cout * f}; v[n++] = {"h", b.h, (size_t)N * k.cr * f};
+      v[n++] = {"g", b.g, (size_t)N * k.cout * f};
+    }
+  } else {
+    Bwd1 q;
+    layout_bwd(r, ws_view_anchor(), q);
+    total = q.bytes;
+    const size_t act = r.max_act * es, big = (size_t)N * r.L1 * 64 * es;
+    if (index == 0 || index == 1) v[n++] = {"X", q.X[index], act};
+    if (index == 0) {
+      v[n++] = {"dz", q.dz, act}; v[n++] = {"dy", q.dy, act}; v[n++] = {"dy1", q.dy1, act}; v[n++] = {"dyd", q.dyd, act};
+      v[n++] = {"da", q.da, act}; v[n++] = {"dtmp", q.dtmp, act};
+      v[n++] = {"big0", q.big0, big}; v[n++] = {"big1", q.big1, big};
+      v[n++] = {"dpooled", q.dpooled, (size_t)N * 256 * f};
+      v[n++] = {"dh1", q.dh1, (size_t)N * 64 * f}; v[n++] = {"dfeat_h", q.dfeat_h, (size_t)N * 64 * f};
+      v[n++] = {"dg", q.dg, (size_t)N * 256 * f}; v[n++] = {"ds", q.ds, (size_t)N * 256 * f};
+      v[n++] = {"dh", q.dh, (size_t)N * 16 * f}; v[n++] = {"dm", q.dm, (size_t)N * 256 * f};
+    }
+  }
+  return ws_view_find(backward ? "resnet1d ws_view (backward)" : "resnet1d ws_view (forward)", v, n, name, index, total, offset,
+                      bytes);
+}
+
 extern "C" int ecgmm_resnet1d_forward(const ecgmm_resnet1d_desc* d, const float* signal, const void* const* params,
                                       void* const* buffers, float* feat_out, void* ws, size_t ws_bytes,
                                       void* stream_) {

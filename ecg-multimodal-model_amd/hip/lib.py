@@ -61,6 +61,7 @@ SIGNATURES = {
     "ecgmm_resnet18_backward": (i32, [P(ResNet18Desc), vp, vp, P(vp), P(vp), vp, vp, sz, i32, i32, vp]),
     "ecgmm_resnet18_backward_dx": (i32, [P(ResNet18Desc), vp, vp, P(vp), P(vp), vp, vp, sz, i32, i32, vp, vp]),
     "ecgmm_resnet18_gradcam": (i32, [P(ResNet18Desc), vp, P(vp), vp, vp, sz, vp, vp]),
+    "ecgmm_resnet18_ws_view": (i32, [P(ResNet18Desc), i32, C.c_char_p, i32, P(sz), P(sz)]),
     "ecgmm_head_fwd_workspace": (sz, [P(HeadDesc)]),
     "ecgmm_head_bwd_workspace": (sz, [P(HeadDesc)]),
     "ecgmm_head_forward": (i32, [P(HeadDesc), P(vp), P(vp), P(vp), vp, vp, vp, sz, vp]),
@@ -85,6 +86,7 @@ SIGNATURES = {
     "ecgmm_resnet1d_backward": (i32, [P(ResNet1DDesc), vp, vp, P(vp), P(vp), vp, vp, sz, i32, i32, vp]),
     "ecgmm_resnet1d_backward_dx": (i32, [P(ResNet1DDesc), vp, vp, P(vp), P(vp), vp, vp, sz, i32, i32, vp, vp]),
     "ecgmm_resnet1d_gradcam": (i32, [P(ResNet1DDesc), vp, P(vp), vp, vp, sz, vp, vp]),
+    "ecgmm_resnet1d_ws_view": (i32, [P(ResNet1DDesc), i32, C.c_char_p, i32, P(sz), P(sz)]),
     "ecgmm_nchw_to_nhwc": (i32, [i32, vp, vp, i32, i32, i64, vp]),
     "ecgmm_nhwc_to_nchw": (i32, [i32, vp, vp, i32, i32, i64, vp]),
     "ecgmm_cast": (i32, [i32, vp, vp, i64, vp]),
@@ -242,7 +244,9 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  # the SE MLP per-op (csrc/head_fused.hip)
                  "ecgmm_se_mlp_fwd", "ecgmm_se_mlp_bwd",
                  # the PTB-XL path (ecgmm/train_signal_only_ptb.py)
-                 "ecgmm_signal_preprocess_i16", "ecgmm_weighted_sample")
+                 "ecgmm_signal_preprocess_i16", "ecgmm_weighted_sample",
+                 # the workspace views of the two encoder plans (tests/test_plan_replay_*.py)
+                 "ecgmm_resnet18_ws_view", "ecgmm_resnet1d_ws_view")
 
 _lib = None
 

@@ -89,6 +89,16 @@ int ecgmm_resnet18_backward_dx(const ecgmm_resnet18_desc* d, const float* image,
  * the maximum is 0; align_corners=False. */
 int ecgmm_resnet18_gradcam(const ecgmm_resnet18_desc* d, const float* dfeat, const void* const* params, void* ws_fwd,
                            void* ws_bwd, size_t ws_bwd_bytes, float* cam, void* stream);
+/* Debugging and test aid: where a named tensor lies inside the forward (backward = 0) or backward (backward = 1) workspace
+ * of this descriptor -- *offset bytes from the workspace base, *bytes long.  Computed by the plan's own layout code; launches
+ * nothing and needs no GPU.  Forward names: wstem y0 coef0 p0 idx0 pooled (index 0) and, per block (index 0..7), w1f w1d w2f
+ * w2d wdf wdd y1 a1 y2 yd out bits coef1 coef2 coefd.  Backward names: X dy dy1 dyd (index 0 / 1), dz da dtmp big0 big1
+ * dpooled (index 0).  Activations are channels-last in the compute dtype, coef* are [4][C] fp32 (scale, shift, mean,
+ * invstd), bits one bit per element of out, idx0 one byte per pooled element.  ECGMM_ERR_SHAPE with a message for an
+ * unknown name or index and for a tensor this descriptor does not have (yd / wdf / wdd / coefd of a block without a
+ * downsample, bits in fp32, y0 / big0 / big1 under ecgmm_stem_recompute(1)). */
+int ecgmm_resnet18_ws_view(const ecgmm_resnet18_desc* d, int backward, const char* name, int index, size_t* offset,
+                           size_t* bytes);
 
 /* The ResNet18 backward runs its weight-gradient kernels on a library-owned side stream (forked from /
  * joined to `stream` with events inside each call).  0 = keep everything on the caller's stream. */
@@ -136,6 +146,11 @@ int ecgmm_resnet1d_backward_dx(const ecgmm_resnet1d_desc* d, const float* signal
 /* Grad-CAM of layer3's output along the signal: cam [N,L] fp32 (see ecgmm_resnet18_gradcam) */
 int ecgmm_resnet1d_gradcam(const ecgmm_resnet1d_desc* d, const float* dfeat, const void* const* params, void* ws_fwd,
                            void* ws_bwd, size_t ws_bwd_bytes, float* cam, void* stream);
+/* as ecgmm_resnet18_ws_view.  Forward names: wstem y0 coef0 p0 idx0 pooled h1 hd dmask (index 0) and, per block (index
+ * 0..2), w1f w1d w2f w2d wdf wdd y1 a1 y2 yd out coef1 coef2 coefd m h g.  Backward names: X (index 0 / 1), dz dy dy1 dyd
+ * da dtmp big0 big1 dpooled dh1 dfeat_h dg ds dh dm (index 0); dg ds dh dm are sized for the widest block. */
+int ecgmm_resnet1d_ws_view(const ecgmm_resnet1d_desc* d, int backward, const char* name, int index, size_t* offset,
+                           size_t* bytes);
 
 /* ---------------------------------------------------------------------------------------------
  * Inference plans (opt-in): the eval-mode forward of either encoder with every BatchNorm folded into the convolution in

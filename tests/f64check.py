@@ -1,5 +1,6 @@
 """Float64 checkers: the bf16 conv kernels (below), the BatchNorm / pooling passes, the fp32 dense tails, the LSTM
-recurrence and the TabNet clinical branch (their own sections further down, each with its bounds derived in a header comment).
+recurrence, the TabNet clinical branch and the ops that run only inside the encoder launch plans (their own sections further
+down, each with its bounds derived in a header comment).
 
 
 With the operands rounded to bf16, every product x * w is exact in float64 and so is any sum of a few million of them to
@@ -511,7 +512,13 @@ def pool_fwd_ratio(pooled, idx, y, scale, shift, bf16, name="maxpool"):
     """pooled, idx [N][OH][OW][C] as the kernel stored them against a64 = relu(y * scale + shift) in float64:
     pooled within the stored bound (K_AFFINE) of the window maximum; idx an in-image tap whose a64 is within that bound of
     the maximum; where idx names a tap that ties the maximum exactly, it is the earliest such tap (windows holding an
-    element whose sign fp32 may decide either way are left out of this last rule)."""
+    element whose sign fp32 may decide either way are left out of this last rule).
+    bf16: the taps are compared as stored, i.e. after rounding to bf16 (torch's own pooling of a bf16 activation does the
+    same), and the earliest tap whose ROUNDED value is the largest wins.  Its fp32 value then lies within one bf16 ulp -- two
+    half ulps -- below the largest fp32 value, each of the two within the accumulation term of its a64: the tap bound is
+    twice the stored bound.  (Found by tests/test_plan_replay_gpu.py: behind a BatchNorm scale below 1 several bf16 conv
+    outputs land in one bf16 cell of the activation; the hash inputs of pool_inputs, scale >= 0.7 and a negative shift, never
+    do.)"""
     y = y.double()
     z = y * scale.double() + shift.double()
     A = y.abs() * scale.double().abs() + shift.double().abs()
@@ -525,7 +532,8 @@ def pool_fwd_ratio(pooled, idx, y, scale, shift, bf16, name="maxpool"):
     ix = idx.long()
     sel = T.gather(3, ix.clamp(0, 8).unsqueeze(3)).squeeze(3)
     in_range = (ix < 9) & torch.isfinite(sel)
-    r_tap = torch.where(in_range, _ratio(mx - torch.where(in_range, sel, mx), bound), torch.full_like(mx, float("inf")))
+    r_tap = torch.where(in_range, _ratio(mx - torch.where(in_range, sel, mx), 2 * bound if bf16 else bound),
+                        torch.full_like(mx, float("inf")))
     first = (T == mx.unsqueeze(3)).double().argmax(3)
     late = in_range & (sel == mx) & (ix != first) & ~TU
     ratio = torch.where(late, torch.full_like(mx, float("inf")), torch.maximum(r_val, r_tap))
@@ -1676,3 +1684,133 @@ def bn_small_inputs(N, C, mean_ratio=None):
         x = x + (mean_ratio * (2.0 / 3 ** 0.5) * (1 - 2 * (c % 2).float()))[None]
     return dict(x=x, dy=h((N, C), 74), gamma=1 + 0.2 * h((C,), 75), beta=0.1 * h((C,), 76), rm0=0.1 * h((C,), 77),
                 rv0=1 + 0.5 * h((C,), 78), dg0=h((C,), 79), db0=h((C,), 80))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The ops that run only inside the encoder launch plans (tests/plan_replay.py): the global average pool (plain and through
+# BatchNorm coefficients), its broadcast backward, the squeeze-excite gate gradient (two-pass and merged form: the same sum)
+# and the dropout scaling.  Operands are taken as given; every K is the derived worst case of an fp32 sum taken in ANY
+# order (each summand passes through at most as many roundings as there are summands), nothing here is calibrated.
+#
+#   avgpool:       out[n][c] = (sum_r x) / R [* scale + shift].  R roundings in the sum, the division: K = R + 1, and two
+#                  more through the coefficients;  A = mean_r |x| [* |scale| + |shift|];  |got - ref| <= g_k(K) * A
+#   bcast_rows:    out[n][r][c] = v[n][c] * scale, scale the fp32 value the kernel received: K = 1, stored as round_T
+#   SE gate grad:  dg[n][c] = sum_r [mask] dout * (y * scale + shift): y * scale, + shift, the product, R in the sum:
+#                  K = R + 3;  A = sum_r [mask] |dout| (|y| |scale| + |shift|)
+#   dropout:       y = keep ? x * (1 / (1 - p)) : 0, p the fp32 value: 1 - p, the reciprocal, the product: K = 3
+# ----------------------------------------------------------------------------------------------------------------------
+K_BCAST = 1
+K_DROPOUT = 3
+
+
+def avgpool_ref(x, scale=None, shift=None):
+    """x [N][R][C] -> (ref, A, K) of the mean over R, optionally through the per-channel affine map"""
+    x = x.double()
+    R = x.shape[1]
+    ref, A, K = x.mean(1), x.abs().mean(1), R + 1
+    if scale is not None:
+        ref, A, K = ref * scale.double() + shift.double(), A * scale.double().abs() + shift.double().abs(), K + 2
+    return ref, A, K
+
+
+def plain_ratio(got, ref, A, K, name):
+    """worst |got - ref| / (g_k(K) * A) of an fp32 output; exact where A == 0"""
+    got, ref = got.double(), ref.double()
+    ratio = _ratio((got - ref).abs(), g_k(K) * A.double())
+    if ratio.numel() == 0:
+        return Report(name, 0.0, ())
+    flat = int(torch.argmax(ratio))
+    seen = torch.where(A.double() > 0, (got - ref).abs() / (U * A.double()).clamp_min(1e-300), torch.zeros_like(ref))
+    seen = seen[torch.isfinite(seen)]
+    return Report(name, float(ratio.reshape(-1)[flat]), _unravel(flat, ref.shape), float(seen.max()) if seen.numel() else 0.0)
+
+
+def check_plain(got, ref, A, K, name):
+    r = plain_ratio(got, ref, A, K, name)
+    print(r)
+    assert r.ok, str(r)
+    return r
+
+
+def check_avgpool(got, x, scale=None, shift=None, name="avgpool"):
+    ref, A, K = avgpool_ref(x, scale, shift)
+    return check_plain(got, ref, A, K, name)
+
+
+def check_bcast(got, v, R, bf16, name="bcast_rows"):
+    """got [N][R][C] as stored against v [N][C] * fp32(1 / R)"""
+    ref = (v.double() * f32(1.0 / R)).unsqueeze(1).expand(-1, R, -1)
+    return check_stored(got, ref, ref.abs(), K_BCAST, bf16, name)
+
+
+def se_gate_grad_ref(dout, mask, y, scale, shift):
+    """dout, y [N][R][C], mask [N][R][C] bool -> (ref, A, K) of dg [N][C]"""
+    d, yv = dout.double(), y.double()
+    d = torch.where(mask, d, torch.zeros_like(d))
+    z = yv * scale.double() + shift.double()
+    Az = yv.abs() * scale.double().abs() + shift.double().abs()
+    return (d * z).sum(1), (d.abs() * Az).sum(1), dout.shape[1] + 3
+
+
+def check_se_gate_grad(got, dout, mask, y, scale, shift, name="se_gate_grad"):
+    ref, A, K = se_gate_grad_ref(dout, mask, y, scale, shift)
+    return check_plain(got, ref, A, K, name)
+
+
+def dropout_ref(x, keep, p, A=None):
+    """keep ? x / (1 - p) : 0 with p as the fp32 value the kernel received; A: the magnitude behind x (default |x|)"""
+    s = 1.0 / (1.0 - f32(p))
+    k = keep.double()
+    return x.double() * k * s, (x.double().abs() if A is None else A.double()) * k * s
+
+
+def check_dropout(got, x, keep, p, name="dropout"):
+    ref, A = dropout_ref(x, keep, p)
+    return check_plain(got, ref, A, K_DROPOUT, name)
+
+
+def eval_coef_ref(gamma, beta, rm, rv, eps):
+    """BatchNorm coefficients from the running statistics as ecg_bn_eval_coef forms them in fp32:
+    invstd = 1 / sqrtf(rv + eps): the sum, the root, the division, one spare for a root that is not correctly rounded: g_k(4);
+    scale = gamma * invstd: g_k(5);  shift = beta - rm * scale: the product and the difference on top of scale's error;
+    mean = rm, exactly."""
+    g, b, rm, rv = gamma.double(), beta.double(), rm.double(), rv.double()
+    inv = 1.0 / (rv + f32(eps)).sqrt()
+    scale = g * inv
+    d_scale = g_k(5) * scale.abs()
+    shift = b - rm * scale
+    d_shift = rm.abs() * d_scale + g_k(2) * (b.abs() + (rm * scale).abs() + rm.abs() * d_scale)
+    return CoefRef(dict(scale=scale, shift=shift, mean=rm, invstd=inv),
+                   dict(scale=d_scale, shift=d_shift, mean=torch.zeros_like(rm), invstd=g_k(4) * inv))
+
+
+def check_bn_eval_bwd(dout, y, coef, bf16, K_sum, dgamma, dbeta, dy=None, dz_out=None, dbias=None, K_bias=None,
+                      maskref=None, gate=None, addc=None, name="bn_eval_bwd"):
+    """check_bn_bwd for the affine (eval-mode) backward: dy = dz * scale (K_EVAL_DY); dgamma / dbeta / dz_out / dbias as there"""
+    unsure, mask = None, None
+    if isinstance(maskref, str):
+        mask, unsure = affine_mask(y, coef[0], coef[1])
+        check_unsure(unsure, name)
+    elif maskref is not None:
+        mask = maskref.double() > 0
+    dz, A, masked = bn_dz_ref(dout, mask, gate, addc)
+    xh = xhat_ref(y, coef)
+    swing = None if unsure is None else (dout.double() * (1 if gate is None else gate.double()))
+    sums, slack, mags = bn_bwd_sums_ref(dz, A, xh, unsure, swing)
+    out = {}
+    if dbeta is not None:
+        out["dbeta"] = check_sum(dbeta, sums[0], mags[0], K_DZ + K_sum + 1, name + " dbeta", slack[0]).ratio
+        out["dgamma"] = check_sum(dgamma, sums[1], mags[1], K_DZXHAT + K_sum + 1, name + " dgamma", slack[1]).ratio
+    if dz_out is not None:
+        bad = (dz_out.double() != masked)
+        if unsure is not None:
+            bad &= ~unsure
+        assert not bool(bad.any()), "%s dz_out: %d elements are not the masked gradient" % (name, int(bad.sum()))
+        out["dz_out"] = 0.0
+    if dy is not None:
+        want, Ady = bn_eval_dy_ref(dz, A, coef[0])
+        out["dy"] = check_stored(dy, want, Ady, K_EVAL_DY, bf16, name + " dy", skip=unsure).ratio
+    if dbias is not None:
+        s = dy.double()
+        out["dbias"] = check_sum(dbias, s.sum(0), s.abs().sum(0), K_bias + 1, name + " dbias").ratio
+    return out

@@ -392,6 +392,29 @@ def test_pool_checkers_accept_torch(shape, bf16):
     F64.check_pool_bwd(dz, p["dp"], pooled, idx, bf16)
 
 
+def test_pool_checker_accepts_taps_that_tie_after_bf16_rounding():
+    """Behind a small BatchNorm scale several bf16 conv outputs land in one bf16 cell of the activation: torch's pooling of
+    the stored bf16 activation then names the earliest of them, whose float64 value is up to one bf16 ulp below the largest.
+    The checker accepts that (tap ratio above 1 of the stored bound, within the doubled tap bound) and still rejects a tap
+    two ulps below the maximum and the later of two taps that tie exactly."""
+    N, C, H, W = 2, 64, 9, 7
+    p = F64.pool_inputs(N, C, H, W, True)
+    p["scale"], p["shift"] = 0.11 * p["scale"], 1.0 + 0.05 * p["shift"]
+    pooled, idx, _ = _pool_emulate(p, True)
+    r = F64.check_pool_fwd(pooled, idx, p["y"], p["scale"], p["shift"], True)
+    assert 0.5 < r.parts["tap"] <= 1.0 and r.parts["value"] <= 1.0, r.parts      # beyond the stored bound, within two of them
+    a = (p["y"].double() * p["scale"].double() + p["shift"].double()).clamp_min(0)
+    T = F64.pool_taps(a, float("-inf"))
+    mx = T.amax(3, keepdim=True)
+    low = torch.isfinite(T) & (mx - T > 4 * F64.half_ulp_bf16(mx)) & (mx - T < 8 * F64.half_ulp_bf16(mx))
+    assert low.any()
+    n_, oh, ow, t, c_ = (int(v) for v in low.nonzero()[0])
+    bad = idx.clone()
+    bad[n_, oh, ow, c_] = t
+    r = F64.pool_fwd_ratio(pooled, bad, p["y"], p["scale"], p["shift"], True)
+    assert not r.ok and r.parts["tap"] > 2.0, r.parts
+
+
 @pytest.mark.parametrize("bf16", [False, True])
 def test_rejects_each_pooling_defect(bf16):
     N, C, H, W = 2, 64, 9, 7
@@ -1137,3 +1160,50 @@ def test_shared_weight_gradient_check_rejects_a_missing_use():
         assert not F64.dot_ratio(part, ref, A, K).ok
     twice = dw + pairs[0][1].t() @ pairs[0][0]
     assert not F64.dot_ratio(twice, ref, A, K).ok
+
+
+def test_plan_only_checkers_accept_torch_fp32_and_reject_defects():
+    """avgpool (plain and through coefficients), bcast_rows, the SE gate gradient and the dropout scaling: torch's fp32
+    evaluation passes each derived bound; a dropped row, a dropped shift, a missing 1 / R, an unmasked element and a missing
+    1 / (1 - p) are rejected"""
+    from oracle import fill
+    h = fill.hash_tensor
+    N, R, C = 3, 125, 64
+    x, sc, sh = h((N, R, C), 90, 2.0), 1 + 0.3 * h((C,), 91), 0.2 * h((C,), 92)
+    F64.check_avgpool(x.mean(1), x)
+    F64.check_avgpool(x.mean(1) * sc + sh, x, sc, sh)
+    ref, A, K = F64.avgpool_ref(x, sc, sh)
+    assert K == R + 3
+    assert not F64.plain_ratio(x[:, :-1].sum(1) / R * sc + sh, ref, A, K, "row dropped").ok
+    assert not F64.plain_ratio(x.mean(1) * sc, ref, A, K, "shift dropped").ok
+    for bf16 in (False, True):
+        v = h((N, C), 93)
+        got = F64._b((v * torch.tensor(1.0 / R)).unsqueeze(1).expand(-1, R, -1), bf16)
+        F64.check_bcast(got, v, R, bf16)
+        with pytest.raises(AssertionError):
+            F64.check_bcast(F64._b(v.unsqueeze(1).expand(-1, R, -1), bf16), v, R, bf16)
+    dout, y, mask = h((N, R, C), 94), h((N, R, C), 95, 2.0), h((N, R, C), 96) > -0.3
+    dg = (torch.where(mask, dout, torch.zeros_like(dout)) * (y * sc + sh)).sum(1)
+    F64.check_se_gate_grad(dg, dout, mask, y, sc, sh)
+    ref, A, K = F64.se_gate_grad_ref(dout, mask, y, sc, sh)
+    flip = mask.clone()
+    flip[1, 7, 5] ^= True
+    bad = (torch.where(flip, dout, torch.zeros_like(dout)) * (y * sc + sh)).sum(1)
+    assert not F64.plain_ratio(bad, ref, A, K, "one mask element").ok
+    xx, keep, p = h((N, 64), 97), h((N, 64), 98) > -0.4, 0.3
+    F64.check_dropout(torch.where(keep, xx * (1.0 / (1.0 - torch.tensor(p))), torch.zeros_like(xx)), xx, keep, p)
+    with pytest.raises(AssertionError):
+        F64.check_dropout(torch.where(keep, xx, torch.zeros_like(xx)), xx, keep, p)
+
+
+def test_eval_coef_ref_accepts_torch_fp32_and_rejects_a_swapped_statistic():
+    from oracle import fill
+    h = fill.hash_tensor
+    C = 128
+    g, b, rm, rv = 1 + 0.1 * h((C,), 101), 0.1 * h((C,), 102), 0.1 * h((C,), 103), 1 + 0.2 * h((C,), 104).abs()
+    inv = 1.0 / torch.sqrt(rv + 1e-5)
+    coef = torch.stack([g * inv, b - rm * (g * inv), rm, inv])
+    ref = F64.eval_coef_ref(g, b, rm, rv, 1e-5)
+    assert F64.coef_ratio(coef, ref).ok
+    assert not F64.coef_ratio(coef, F64.eval_coef_ref(g, b, rm, rv.flip(0), 1e-5)).ok
+
