@@ -1,6 +1,6 @@
 """Float64 checkers: the bf16 conv kernels (below), the BatchNorm / pooling passes, the fp32 dense tails, the LSTM
-recurrence, the TabNet clinical branch and the ops that run only inside the encoder launch plans (their own sections further
-down, each with its bounds derived in a header comment).
+recurrence, the TabNet clinical branch, the ops that run only inside the encoder launch plans and the fp32-operand conv
+kernels (their own sections further down, each with its bounds derived in a header comment).
 
 
 With the operands rounded to bf16, every product x * w is exact in float64 and so is any sum of a few million of them to
@@ -1814,3 +1814,103 @@ def check_bn_eval_bwd(dout, y, coef, bf16, K_sum, dgamma, dbeta, dy=None, dz_out
         s = dy.double()
         out["dbias"] = check_sum(dbias, s.sum(0), s.abs().sum(0), K_bias + 1, name + " dbias").ratio
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# fp32-operand convolutions (csrc/conv_igemm.hip, csrc/conv_wgrad.hip, csrc/conv_stem.hip with dtype fp32): operands taken
+# as given, the float64 convolution of the same operands is the answer, outputs stored as fp32.
+#
+#   derived (nothing calibrated):  |out - ref| <= g_k(K + 2) * A
+#       A: the same convolution of absolute values (+ |bias| + |addend|), K the number of summands -- Cs * taps for y / dx,
+#       the pixel count for a weight gradient.  The dense section's dot_bound: an fp32 dot product summed in ANY order (the
+#       f32-input MFMA's fma chain, split-K slabs folded afterwards), + 2 for the bias / addend add and one more operation
+#       (accumulate = 1).  ReLU keeps it (1-Lipschitz).  Where A == 0 -- a pixel a stride-2 or 1x1 convolution never reads --
+#       the result must be exact.
+#   calibrated:  y / dx  |out - ref| <= KAPPA_F32 * A;   dw  |dw - ref| <= EPS_DW_F32 * rms(ref) + TAU_DW_F32 * A  (check_dw's form)
+#       by the rule of the bf16 constants above: at most 4x the largest value measured against float64 on the MI355X over
+#       tests/test_conv_edges_f64_gpu.py, unless torch's own CPU fp32 conv2d / autograd of the same operands needs more
+#       (tests/test_f64check.py: test_fp32_conv_checker_accepts_torch_fp32); then torch sets the constant.
+#   The assertion is the smaller of the two bounds, element by element.
+#   statistics rows:  colsum_ratio, slack = the per-element bound summed over the column, sigma = g_k(chain) with the chain
+#       DERIVED from conv_igemm's epilogue: a lane adds its 4 pixels (TP = 4 fragments of a 64-pixel half tile) into s1: 4
+#       additions, row16_sum folds the 16 pixel lanes in 4 DPP butterfly levels: 4 more -> 8; s2 adds the rounding of v * v: 9.
+#       The rows themselves are summed in double by the test: 0.  (conv_stem's per-tile rows: 2 pixels per lane + 4 levels = 6,
+#       held to the same 8 / 9.)
+#
+# Measured on the MI355X over tests/test_conv_edges_f64_gpu.py (every fp32 case of groups a, b, d, e):
+#   y / dx   max |err| / A           3.07e-7  (1x1 stride-2 input gradient, 256 summands, L = 313)   -> KAPPA_F32 = 1.2e-6
+#   dw       max |err| / A           3.55e-7  (12-lead stem, 334 pixels)                             -> TAU_DW_F32 = 1.4e-6
+#   dw       max |err| / rms(ref)    8.73e-7  (7x7 stem on 1x1 images)                               -> EPS_DW_F32 = 3.4e-6
+# (4 x 3.55e-7 = 1.42e-6 and 4 x 8.73e-7 = 3.49e-6, rounded down, happen to land on the values of the bf16 TAU_DW and EPS_DW;
+#  nothing was taken over from them.)
+# torch's CPU fp32 on the operands of tests/test_f64check.py (K = 1152; 9600 pixels): y 6.1e-8, dx 9.0e-8 of A, under
+#   KAPPA_F32.  Its dw errs by up to 9.7e-7 of A (a serial sum over the pixels) and 6.1e-6 of rms(ref): the second figure is ABOVE
+#   EPS_DW_F32 taken alone, but the bound is the sum eps * rms + tau * A, and 9.7e-7 of A is under TAU_DW_F32 by itself, so
+#   torch passes on the tau term (worst ratio 0.49) and sets no constant.
+# ----------------------------------------------------------------------------------------------------------------------
+KAPPA_F32 = 1.2e-6
+EPS_DW_F32 = 3.4e-6
+TAU_DW_F32 = 1.4e-6
+STATS_CHAIN_F32 = 8          # 4 pixels per lane + the 16-lane butterfly (above)
+
+
+def f32_bound(acc_abs, K, kappa=KAPPA_F32):
+    """per-element bound of an fp32 y / dx: the smaller of the derived and the calibrated constant, times A"""
+    return min(g_k(K + 2), kappa) * acc_abs.double()
+
+
+def _f32_report(err, bound, acc_abs, name):
+    """Report of |err| against a bound tensor; the accumulation term reported is max |err| / A over the elements with A > 0"""
+    ratio = _ratio(err, bound)
+    flat = int(torch.argmax(ratio))
+    seen = torch.where(acc_abs > 0, err / acc_abs.clamp_min(1e-300), torch.zeros_like(err))
+    seen = seen[torch.isfinite(seen)]
+    return Report(name, float(ratio.reshape(-1)[flat]), _unravel(flat, err.shape), float(seen.max()) if seen.numel() else 0.0)
+
+
+def f32_ratio(out, ref, acc_abs, K, kappa=KAPPA_F32, name="out"):
+    """worst |out - ref| / bound of an fp32-operand conv output; out, ref, acc_abs: same shape.  The accumulation term
+    reported is the measured kappa"""
+    out, ref, acc_abs = out.double(), ref.double(), acc_abs.double()
+    return _f32_report((out - ref).abs(), f32_bound(acc_abs, K, kappa), acc_abs, name)
+
+
+def check_f32(out, ref, acc_abs, K, kappa=KAPPA_F32, name="out"):
+    r = f32_ratio(out, ref, acc_abs, K, kappa, name)
+    print(r)
+    assert torch.isfinite(out.double()).all(), name + ": non-finite output"
+    assert r.ok, str(r)
+    return r
+
+
+def dw_f32_ratio(dw, ref, acc_abs, K, eps=EPS_DW_F32, tau=TAU_DW_F32, name="dw"):
+    """fp32-operand weight gradient: bound = min(g_k(K + 2) * A, eps * rms(ref) + tau * A), K = the pixel count.  The
+    accumulation term reported is the measured tau; eps_seen = max |err| / rms(ref), rel_l2 for the record (not asserted:
+    the per-element bound is the stricter statement and no bar for the norm has been derived)"""
+    dw, ref, acc_abs = dw.double(), ref.double(), acc_abs.double()
+    err = (dw - ref).abs()
+    rms = float(ref.pow(2).mean().sqrt())
+    r = _f32_report(err, torch.minimum(g_k(K + 2) * acc_abs, eps * rms + tau * acc_abs), acc_abs, name)
+    fin = err[torch.isfinite(err)]
+    r.eps_seen = (float(fin.max()) if fin.numel() else 0.0) / max(rms, 1e-300)
+    r.rel_l2 = float((dw - ref).norm() / ref.norm().clamp_min(1e-300))
+    return r
+
+
+def check_dw_f32(dw, ref, acc_abs, K, eps=EPS_DW_F32, tau=TAU_DW_F32, name="dw"):
+    r = dw_f32_ratio(dw, ref, acc_abs, K, eps, tau, name)
+    print(r, " rel L2 %.3g, max|err| / rms %.3g" % (r.rel_l2, r.eps_seen))
+    assert torch.isfinite(dw.double()).all(), name + ": non-finite weight gradient"
+    assert r.ok, str(r)
+    return r
+
+
+def check_stats_f32(rows, ref, K, chain=STATS_CHAIN_F32, kappa=KAPPA_F32, name="stats"):
+    """rows [n][2][C] fp32 as an fp32 forward wrote them; ref: conv_ref64 of the same operands (+ bias); K = Cs * taps"""
+    rows = rows.double()
+    y, b = ref.y, f32_bound(ref.ay, K, kappa)
+    dims = (0, 2, 3)
+    a = check_colsums(rows[:, 0].sum(0), y.sum(dims), b.sum(dims), y.abs().sum(dims), sigma=g_k(chain), name=name + " sum y")
+    c = check_colsums(rows[:, 1].sum(0), (y * y).sum(dims), (2 * y.abs() * b + b * b).sum(dims), (y * y).sum(dims),
+                      sigma=g_k(chain + 1), name=name + " sum y^2")
+    return max(a.ratio, c.ratio)

@@ -43,6 +43,10 @@ is set by torch's CPU fp32 weight gradient, which must also pass), of the
 BatchNorm partial rows 1.0e-7 of the summed magnitudes (SIGMA = 4e-7); every bf16 output's worst ratio to its bound is the
 half-ulp rounding (0.98 - 0.997).  The whole module runs in about 8 s.
 
+Every output (y, dx, dw, statistics and reduction rows) and every workspace is NaN before the launch, and y / dx carry GUARD
+NaN elements behind the last valid one that must still be NaN afterwards (the helpers are shared with
+tests/test_conv_edges_f64_gpu.py, which runs them in fp32 as well).
+
 Inputs are generated on the device from fixed seeds and rounded to bf16: activations non-negative with exact zeros,
 gradients signed; both with an offset per image and per channel, so that reading a neighbouring image or channel gives a
 large error instead of a plausible one.
@@ -62,6 +66,8 @@ from .util import DEV, switches
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 BN_TAIL = 64
+GUARD = 64             # NaN elements behind every y / dx: a store past the last valid element shows
+TDT = {L.BF16: BF, L.F32: torch.float32}
 
 
 # ------------------------------------------------------------------------------------------------ operands and calls
@@ -81,22 +87,34 @@ def _gen(shape, seed, kind, fan_in=1):
     return t.to(BF).float()
 
 
-def _nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous().to(BF)
+def _nhwc(t, dt=L.BF16):
+    return t.permute(0, 2, 3, 1).contiguous().to(TDT[dt])
 
 
 def _nchw(t, n, h, w, c):
     return t.view(n, h, w, c).permute(0, 3, 1, 2).double()
 
 
-def _pack(w):
-    """OIHW fp32 -> (forward, dgrad) bf16 packs, by the library's packer (what the plans call)"""
+def _pack(w, dt=L.BF16):
+    """OIHW fp32 -> (forward, dgrad) packs in the compute dtype, by the library's packer (what the plans call)"""
     n = w.numel()
-    f = torch.empty(n, device=DEV, dtype=BF)
-    d = torch.empty(n, device=DEV, dtype=BF)
-    L.check(L.lib().ecgmm_pack_conv_weight(L.BF16, ptr(w.contiguous()), ptr(f), ptr(d), w.shape[0], w.shape[1],
+    f = torch.empty(n, device=DEV, dtype=TDT[dt])
+    d = torch.empty(n, device=DEV, dtype=TDT[dt])
+    L.check(L.lib().ecgmm_pack_conv_weight(dt, ptr(w.contiguous()), ptr(f), ptr(d), w.shape[0], w.shape[1],
                                            w.shape[2] * w.shape[3], stream()))
     return f, d
+
+
+def poisoned(n, dtype):
+    """n elements for a kernel to fill and GUARD more behind them, all NaN: what it leaves unwritten stays NaN (the
+    checkers assert finiteness), what it writes past the end shows in the guard"""
+    return torch.full((n + GUARD,), float("nan"), device=DEV, dtype=dtype)
+
+
+def unguard(buf, n, name):
+    torch.cuda.synchronize()
+    assert torch.isnan(buf[n:].float()).all(), name + ": written past its last element"
+    return buf[:n]
 
 
 class Geo:
@@ -117,37 +135,43 @@ def _stats_buf(g):
     return torch.full((rows, 2, g.Cout), float("nan"), device=DEV)
 
 
-def fwd(g, x, wf, bias=None, wgrows=True):
-    """-> y [N, Cout, OH, OW] float64, statistics rows [n][2][Cout]"""
+def fwd(g, x, wf, bias=None, wgrows=True, dt=L.BF16):
+    """-> y [N, Cout, OH, OW] float64, statistics rows [n][2][Cout], the NaN rows behind them"""
     lib = L.lib()
-    y = torch.empty(g.M * g.Cout, device=DEV, dtype=BF)
+    y = poisoned(g.M * g.Cout, TDT[dt])
     st = _stats_buf(g)
     if wgrows:
         n = C.c_int(0)
-        L.check(lib.ecgmm_conv_fwd_wgrows(L.BF16, C.byref(g.d), ptr(x), ptr(wf), ptr(bias), ptr(y), ptr(st), C.byref(n), 0,
+        L.check(lib.ecgmm_conv_fwd_wgrows(dt, C.byref(g.d), ptr(x), ptr(wf), ptr(bias), ptr(y), ptr(st), C.byref(n), 0,
                                           stream()))
         rows = n.value
     else:
-        L.check(lib.ecgmm_conv_fwd(L.BF16, C.byref(g.d), ptr(x), ptr(wf), ptr(bias), ptr(y), ptr(st), 0, stream()))
+        L.check(lib.ecgmm_conv_fwd(dt, C.byref(g.d), ptr(x), ptr(wf), ptr(bias), ptr(y), ptr(st), 0, stream()))
         rows = lib.ecgmm_conv_stats_rows(g.M)
-    torch.cuda.synchronize()
+    y = unguard(y, g.M * g.Cout, "y")
     assert 1 <= rows <= st.shape[0] - BN_TAIL
     return _nchw(y, g.N, g.OH, g.OW, g.Cout), st[:rows], st[rows:]
 
 
-def dgrad(g, dy, wd, addend=None):
-    dx = torch.empty(g.N * g.H * g.W * g.Cin, device=DEV, dtype=BF)
-    L.check(L.lib().ecgmm_conv_bwd_data(L.BF16, C.byref(g.d), ptr(dy), ptr(wd), ptr(addend), ptr(dx), stream()))
-    torch.cuda.synchronize()
-    return _nchw(dx, g.N, g.H, g.W, g.Cin)
+def dgrad(g, dy, wd, addend=None, dt=L.BF16):
+    n = g.N * g.H * g.W * g.Cin
+    dx = poisoned(n, TDT[dt])
+    L.check(L.lib().ecgmm_conv_bwd_data(dt, C.byref(g.d), ptr(dy), ptr(wd), ptr(addend), ptr(dx), stream()))
+    return _nchw(unguard(dx, n, "dx"), g.N, g.H, g.W, g.Cin)
 
 
-def wgrad(g, x, dy):
+def nan_workspace(nbytes):
+    """a workspace of at least nbytes whose every float is NaN: a slab the kernel leaves unwritten reaches the result"""
+    return torch.full((max(nbytes, 4) // 4 + 1,), float("nan"), device=DEV)
+
+
+def wgrad(g, x, dy, dt=L.BF16, accumulate=0, dw=None):
     lib = L.lib()
-    nb = lib.ecgmm_conv_bwd_weight_workspace(L.BF16, C.byref(g.d))
-    ws = torch.empty(max(nb, 1), device=DEV, dtype=torch.uint8)
-    dw = torch.full((g.Cout, g.Cin, g.R, g.S), float("nan"), device=DEV)
-    L.check(lib.ecgmm_conv_bwd_weight(L.BF16, C.byref(g.d), ptr(x), ptr(dy), ptr(dw), 0, ptr(ws), nb, stream()))
+    nb = lib.ecgmm_conv_bwd_weight_workspace(dt, C.byref(g.d))
+    ws = nan_workspace(nb)
+    if dw is None:
+        dw = torch.full((g.Cout, g.Cin, g.R, g.S), float("nan"), device=DEV)
+    L.check(lib.ecgmm_conv_bwd_weight(dt, C.byref(g.d), ptr(x), ptr(dy), ptr(dw), accumulate, ptr(ws), nb, stream()))
     torch.cuda.synchronize()
     return dw
 
@@ -210,10 +234,10 @@ def _entry(tag, N, H, W, Cin, Cout, R, bias_on, seed, wgrows):
     out.append(_check_fwd(tag + " conv1", y, rows, ref))
     y, rows, _ = fwd(gd, xg, wdf, bd, wgrows=False)         # (the plans' downsample forward: per-64-pixel rows)
     out.append(_check_fwd(tag + " down", y, rows, refd))
-    dx = torch.empty(N * H * W * Cin, device=DEV, dtype=BF)
+    dx = poisoned(N * H * W * Cin, BF)
     L.check(L.lib().ecgmm_conv_bwd_data_with_downsample(L.BF16, C.byref(g.d), ptr(dyg), ptr(wd), ptr(dydg), ptr(wdd),
                                                         ptr(dx), None, stream()))
-    torch.cuda.synchronize()
+    dx = unguard(dx, N * H * W * Cin, tag + " dx")
     out.append(F64.check_bf16(_nchw(dx, N, H, W, Cin), ref.dx + refd.dx, ref.adx + refd.adx, name=tag + " dx (both branches)"))
     out.append(F64.check_dw(wgrad(g, xg, dyg), ref.dw, ref.adw, name=tag + " conv1 dw"))
     out.append(F64.check_dw(wgrad(gd, xg, dydg), refd.dw, refd.adw, name=tag + " down dw"))
@@ -237,12 +261,13 @@ def _stem(tag, N, Cin, H, W, R, bias_on, seed):
     L.check(lib.ecgmm_stem_pack(L.BF16, ptr(w), ptr(pk), Cin, R, stream()))
     nrows = lib.ecgmm_stem_wg_stats_rows(N, Cin, H, W, R)
     st = torch.full((nrows + BN_TAIL, 2, 64), float("nan"), device=DEV)
-    y = torch.empty(N * OH * OW * 64, device=DEV, dtype=BF)
+    y = poisoned(N * OH * OW * 64, BF)
     L.check(lib.ecgmm_stem_fwd_wgrows(L.BF16, ptr(x), ptr(pk), ptr(b), ptr(y), ptr(st), N, Cin, H, W, R, stream()))
-    torch.cuda.synchronize()
+    y = unguard(y, N * OH * OW * 64, tag + " y")
+    assert torch.isnan(st[nrows:]).all(), tag + ": statistics rows written beyond the reported count"
     out = [_check_fwd(tag, _nchw(y, N, OH, OW, 64), st[:nrows], ref)]
     nb = lib.ecgmm_stem_bwd_weight_workspace(N, Cin, H, W, R)
-    ws = torch.empty(max(nb, 1), device=DEV, dtype=torch.uint8)
+    ws = nan_workspace(nb)
     dw = torch.full(w.shape, float("nan"), device=DEV)
     L.check(lib.ecgmm_stem_bwd_weight(L.BF16, ptr(x), ptr(_nhwc(dy)), ptr(dw), 0, ptr(ws), nb, N, Cin, H, W, R, stream()))
     torch.cuda.synchronize()
@@ -321,12 +346,12 @@ def _bnred(g, dyg, wd, seed, sep, addg=None):
     yg = _nhwc(ybn)
     mg = _nhwc(mask) if sep else yg
     rows = torch.full((512, 2, Ci), float("nan"), device=DEV)
-    dx = torch.empty(N * H * W * Ci, device=DEV, dtype=BF)
+    dx = poisoned(N * H * W * Ci, BF)
     n = C.c_int(0)
     want = lib.ecgmm_conv_bwd_data_bnred_rows(L.BF16, C.byref(g.d))
     L.check(lib.ecgmm_conv_bwd_data_bnred(L.BF16, C.byref(g.d), ptr(dyg), ptr(wd), ptr(addg), ptr(dx), ptr(yg), ptr(mg),
                                           ptr(coef), ptr(rows), C.byref(n), stream()))
-    torch.cuda.synchronize()
+    dx = unguard(dx, N * H * W * Ci, "bnred dx")
     assert n.value == want >= 1, (n.value, want)
     assert torch.isfinite(rows[:n.value]).all() and torch.isnan(rows[n.value:]).all()
     return _nchw(dx, N, H, W, Ci), rows[:n.value], ybn, mask, coef

@@ -1207,3 +1207,156 @@ def test_eval_coef_ref_accepts_torch_fp32_and_rejects_a_swapped_statistic():
     assert F64.coef_ratio(coef, ref).ok
     assert not F64.coef_ratio(coef, F64.eval_coef_ref(g, b, rm, rv.flip(0), 1e-5)).ok
 
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The fp32-operand conv checker (f32_ratio, dw_f32_ratio, check_stats_f32) at the largest K tests/test_conv_edges_f64_gpu.py
+# uses: 128 channels x 9 taps = 1152 summands for y / dx, 9600 pixels for a weight gradient.  It accepts torch's own CPU
+# fp32 conv2d / autograd with the final constants and rejects a zeroed element, a neighbour pixel's value, a dropped
+# 16-byte chunk (4 channels) of one tap, a wrong image-border row, and for dw a split counted twice and a split left out.
+# ----------------------------------------------------------------------------------------------------------------------
+K32 = 128 * 9
+DW32_PIXELS = 6 * 40 * 40
+DW32_SPLIT = 32              # fp32: 16 pixels a step, 600 steps over min(600, 512) splits: 2 steps = 32 pixels per split
+
+
+def _fp32_operands(n, cin, cout, h, w, seed):
+    """full-mantissa fp32 values: activations >= 0 with exact zeros and a per-image / per-channel offset, signed gradients"""
+    g = torch.Generator().manual_seed(seed)
+    z = torch.randn(n, cin, h, w, generator=g)
+    off = 1.0 + ((torch.arange(n).view(-1, 1) * 37 + torch.arange(cin).view(1, -1) * 11) % 64).float().view(n, cin, 1, 1) / 16
+    x = torch.where(z > 0, z + off, torch.zeros_like(z))
+    wt = torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (cin * 9)) ** 0.5
+    dy = torch.randn(n, cout, h, w, generator=g) + torch.linspace(-2, 2, n * cout).view(n, cout, 1, 1)
+    return x, wt, dy
+
+
+@pytest.fixture(scope="module")
+def case32():
+    x, w, dy = _fp32_operands(3, 128, 64, 9, 11, 21)
+    b = torch.linspace(-1, 1, 64)
+    return x, w, dy, b, F64.conv_ref64(x, w, dy, 1, (1, 1), bias=b)
+
+
+@pytest.fixture(scope="module")
+def case32_dw():
+    x, w, dy = _fp32_operands(6, 64, 64, 40, 40, 22)
+    return x, w, dy, F64.conv_ref64(x, w, dy, 1, (1, 1))
+
+
+def _torch32(x, w, dy, b=None):
+    xf, wf = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+    y = F.conv2d(xf, wf, b, padding=1)
+    y.backward(dy)
+    return y.detach(), xf.grad, wf.grad
+
+
+def test_fp32_conv_checker_accepts_torch_fp32(case32, case32_dw):
+    x, w, dy, b, ref = case32
+    y32, dx32, _ = _torch32(x, w, dy, b)
+    ry = F64.check_f32(y32, ref.y, ref.ay, K32, name="torch fp32 y")
+    rdx = F64.check_f32(dx32, ref.dx, ref.adx, 64 * 9, name="torch fp32 dx")
+    F64.check_f32(ref.y.float(), ref.y, ref.ay, K32, name="fp32(ref) y")
+    p = _pix(y32)                                  # statistics rows as the epilogue forms them: fp32 sums of 64 pixels
+    pad = torch.zeros(-p.shape[0] % 64, p.shape[1])
+    p = torch.cat([p, pad]).view(-1, 64, p.shape[1])
+    rows = torch.stack([p.sum(1), (p * p).sum(1)], 1)
+    F64.check_stats_f32(rows, ref, K32, name="torch fp32 stats")
+    bad = rows.clone()
+    bad[2] = 0
+    with pytest.raises(AssertionError):
+        F64.check_stats_f32(bad, ref, K32)
+    x, w, dy, ref = case32_dw
+    _, _, dw32 = _torch32(x, w, dy)
+    rdw = F64.check_dw_f32(dw32, ref.dw, ref.adw, DW32_PIXELS, name="torch fp32 dw")
+    F64.check_dw_f32(ref.dw.float(), ref.dw, ref.adw, DW32_PIXELS, name="fp32(ref) dw")
+    prior = torch.randn(dw32.shape, generator=torch.Generator().manual_seed(24))          # accumulate = 1 onto an independent tensor
+    F64.check_dw_f32(prior + dw32, prior.double() + ref.dw, prior.double().abs() + ref.adw, DW32_PIXELS,
+                     name="torch fp32 dw, accumulated onto a prior")
+    print("torch CPU fp32: y %.3g, dx %.3g of A; dw %.3g of A, %.3g of rms" % (ry.kappa_seen, rdx.kappa_seen, rdw.kappa_seen,
+                                                                             rdw.eps_seen))
+
+
+def test_fp32_conv_checker_demands_exactness_where_nothing_is_summed():
+    """1x1 / stride 2: the input gradient of a pixel with an odd row or column has A == 0 and must be exactly 0"""
+    x, w, dy = _fp32_operands(2, 16, 8, 9, 9, 23)
+    w = w[:, :, :1, :1].contiguous()
+    dy = dy[:, :, :5, :5].contiguous()
+    ref = F64.conv_ref64(x, w, dy, 2, (0, 0))
+    assert (ref.adx[:, :, 1::2] == 0).all() and (ref.adx[:, :, :, 1::2] == 0).all()
+    assert F64.f32_ratio(ref.dx.float(), ref.dx, ref.adx, 8).ok
+    m = ref.dx.float().clone()
+    m[1, 3, 1, 2] = 1e-30
+    assert F64.f32_ratio(m, ref.dx, ref.adx, 8).ratio == float("inf")
+    m = ref.dx.float().clone()
+    m[0, 0, 0, 1] = float("nan")
+    assert not F64.f32_ratio(m, ref.dx, ref.adx, 8).ok
+
+
+def _mutations32(x, w, ref):
+    """(name, mutated fp32 output [pixels][channels]) pairs, each a copy of fp32(ref.y) with one defect"""
+    base = _pix(ref.y.float())
+    n, _, h, wd = ref.y.shape
+    out = []
+    flat = base.reshape(-1)
+    k = int(torch.argsort(flat.abs())[flat.numel() // 2])
+    m = base.clone()
+    m.view(-1)[k] = 0
+    out.append(("one element zeroed", m))
+    m = base.clone()
+    m[150] = base[151]
+    out.append(("a pixel holds its neighbour's value", m))
+    # one 16-byte chunk (input channels 4..7) of the centre tap missing from one pixel, where those inputs are not zero
+    img, py, px = 1, 4, 5
+    assert (x[img, 4:8, py, px] != 0).any()
+    part = (x[img, 4:8, py, px].double()[None] * w[:, 4:8, 1, 1].double()).sum(1)
+    yt = ref.y.clone()
+    yt[img, :, py, px] -= part
+    out.append(("a 4-channel chunk of one tap dropped", _pix(yt.float())))
+    # image 2's top output row read the last row of image 1 instead of the zero padding above it
+    img = 2
+    xin = torch.cat([x[img - 1:img, :, h - 1:h], x[img:img + 1]], dim=2).double()
+    ytop = F.conv2d(xin, w.double(), padding=(0, 1))[:, :, 0]
+    yt = ref.y.clone()
+    yt[img, :, 0] += ytop[0] - F.conv2d(x[img:img + 1].double(), w.double(), padding=1)[0, :, 0]
+    out.append(("image-border row from the neighbouring image", _pix(yt.float())))
+    return out
+
+
+def test_fp32_conv_checker_rejects_each_defect(case32):
+    x, w, dy, b, ref = case32
+    for name, m in _mutations32(x, w, ref):
+        r = F64.f32_ratio(_unpix(m, ref.y), ref.y, ref.ay, K32, name=name)
+        print(r)
+        assert r.ratio > 1.0, "checker accepted: " + name
+    base = _pix(ref.dx.float())
+    m = base.clone()
+    m[40] = base[41]
+    assert not F64.f32_ratio(_unpix(m, ref.dx), ref.dx, ref.adx, 64 * 9).ok
+    m = base.clone()
+    m[-1, -4:] = 0                      # the last 16 bytes of the tensor left unwritten (zeros)
+    assert not F64.f32_ratio(_unpix(m, ref.dx), ref.dx, ref.adx, 64 * 9).ok
+    m[-1, -4:] = float("nan")           # ... or still holding the poison
+    assert not F64.f32_ratio(_unpix(m, ref.dx), ref.dx, ref.adx, 64 * 9).ok
+
+
+def _dw32_of_pixels(x, dy, lo, hi):
+    mask = torch.zeros(dy.shape[0] * dy.shape[2] * dy.shape[3], dtype=torch.float64)
+    mask[lo:hi] = 1
+    dym = dy.double() * mask.view(dy.shape[0], dy.shape[2], dy.shape[3]).unsqueeze(1)
+    wr = torch.zeros(dy.shape[1], x.shape[1], 3, 3, dtype=torch.float64, requires_grad=True)
+    F.conv2d(x.double(), wr, padding=1).backward(dym)
+    return wr.grad
+
+
+def test_fp32_conv_checker_rejects_weight_gradient_split_defects(case32_dw):
+    x, w, dy, ref = case32_dw
+    split = _dw32_of_pixels(x, dy, 7 * DW32_SPLIT, 8 * DW32_SPLIT)
+    for name, m in (("a split counted twice", ref.dw + split), ("a split left out", ref.dw - split),
+                    ("the last split left out", ref.dw - _dw32_of_pixels(x, dy, DW32_PIXELS - DW32_SPLIT, DW32_PIXELS))):
+        r = F64.dw_f32_ratio(m.float(), ref.dw, ref.adw, DW32_PIXELS, name="dw: " + name)
+        print(r)
+        assert not r.ok, "checker accepted: " + name
+    m = ref.dw.float().clone()
+    m[5, 7, 1, 1] = float("nan")
+    assert not F64.dw_f32_ratio(m, ref.dw, ref.adw, DW32_PIXELS).ok
