@@ -606,3 +606,101 @@ def crnn_front(x, params, buffers, training, momentum=0.1, eps=1e-5, dtype=L.F32
     """conv1..conv3 of the CRNN + permute + Flatten: ``params`` per block conv weight, conv bias, bn weight, bn bias;
     ``buffers`` per block running_mean, running_var, num_batches_tracked"""
     return CRNNFrontFn.apply(x, (training, momentum, eps, dtype), tuple(buffers), *params)
+
+
+# --------------------------------------------------------------------------------------------
+# LIME tabular (csrc/lime.hip)         reference: lime_fusion_modal_balance.py:118-160
+# --------------------------------------------------------------------------------------------
+LIME_TABLE_KEYS = ("qts", "cdf", "stats", "lim", "nbins")
+
+
+def lime_perturb(x, table, num_samples, b0=0, seed_offset=None, return_uniforms=False):
+    """Z uint8 [B, N, D], inverse fp32 [B, N, D], d2 int32 [B, N] (and the uniforms, double [B, N, D, 2]) of the rows
+    ``x`` [B, D] under the discretiser ``table`` (``QuartileDiscretizer.table(device)``: qts, cdf [D, S] float64,
+    stats [4, D, S] float64, lim [2, D, S] fp32, nbins [D] int32).  ``b0``: the index of x[0] in the caller's batch, which
+    enters the Philox counter; ``seed_offset`` None takes one offset of the library's stream."""
+    _require_cuda(x, "lime_perturb")
+    for k in LIME_TABLE_KEYS:
+        _require_cuda(table[k], "lime_perturb table")
+    x = f32c(x)
+    if x.dim() != 2:
+        raise ValueError(f"lime_perturb expects rows [B, D], got {tuple(x.shape)}")
+    B, D = x.shape
+    N, S = int(num_samples), int(table["cdf"].shape[1])
+    want = {"qts": ((D, S), torch.float64), "cdf": ((D, S), torch.float64), "stats": ((4, D, S), torch.float64),
+            "lim": ((2, D, S), torch.float32), "nbins": ((D,), torch.int32)}
+    for k, (shape, dt) in want.items():
+        t = table[k]
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"lime_perturb: table[{k!r}] must be contiguous {dt} {shape}, got {t.dtype} {tuple(t.shape)}")
+    seed, off = _PhiloxState.take(4) if seed_offset is None else seed_offset
+    Z = torch.empty(B, max(N, 0), D, dtype=torch.uint8, device=x.device)
+    inverse = torch.empty(B, max(N, 0), D, dtype=torch.float32, device=x.device)
+    d2 = torch.empty(B, max(N, 0), dtype=torch.int32, device=x.device)
+    u = torch.empty(B, max(N, 0), D, 2, dtype=torch.float64, device=x.device) if return_uniforms else None
+    L.check(L.lib().ecgmm_lime_perturb(ptr(x), ptr(table["qts"]), ptr(table["cdf"]), ptr(table["stats"]), ptr(table["lim"]),
+                                       ptr(table["nbins"]), S, B, int(b0), N, D, int(seed), int(off), ptr(Z), ptr(inverse),
+                                       ptr(d2), ptr(u), stream()), "lime_perturb")
+    return (Z, inverse, d2, u) if return_uniforms else (Z, inverse, d2)
+
+
+def lime_ridge(Z, d2, y, kernel_width, alpha, cols=None, want=("w", "score", "local_pred")):
+    """The weighted ridge fit of LIME for B samples and L labels at once: Z uint8 [B, N, D], d2 int32 [B, N],
+    y fp32 [B, L, N], cols int32 [B, K] or None (all columns).  -> dict(coef [B, L, K], intercept [B, L]) plus the
+    entries of ``want``: w [B, N], score [B, L], local_pred [B, L]."""
+    _require_cuda(Z, "lime_ridge")
+    _require_cuda(d2, "lime_ridge")
+    _require_cuda(y, "lime_ridge")
+    if Z.dtype != torch.uint8 or d2.dtype != torch.int32 or Z.dim() != 3 or y.dim() != 3:
+        raise ValueError("lime_ridge expects Z uint8 [B, N, D], d2 int32 [B, N], y [B, L, N]")
+    Z, d2, y = Z.contiguous(), d2.contiguous(), f32c(y)
+    B, N, D = Z.shape
+    Lb = y.shape[1]
+    if tuple(d2.shape) != (B, N) or tuple(y.shape) != (B, Lb, N):
+        raise ValueError(f"lime_ridge: d2 {tuple(d2.shape)} / y {tuple(y.shape)} do not match Z {tuple(Z.shape)}")
+    K = D
+    if cols is not None:
+        _require_cuda(cols, "lime_ridge")
+        if cols.dtype != torch.int32 or cols.dim() != 2 or cols.shape[0] != B:
+            raise ValueError("lime_ridge: cols must be int32 [B, K]")
+        cols = cols.contiguous()
+        K = cols.shape[1]
+    lib = L.lib()
+    nb = lib.ecgmm_lime_ridge_workspace(B, N, D)
+    if nb == 0:
+        L.check(1, "lime_ridge workspace query")
+    ws = _Scratch.get("lime_ridge", nb, Z.device)
+    f32 = dict(dtype=torch.float32, device=Z.device)
+    out = {"coef": torch.empty(B, Lb, K, **f32), "intercept": torch.empty(B, Lb, **f32)}
+    if "w" in want:
+        out["w"] = torch.empty(B, N, **f32)
+    for k in ("score", "local_pred"):
+        if k in want:
+            out[k] = torch.empty(B, Lb, **f32)
+    L.check(lib.ecgmm_lime_ridge(ptr(Z), ptr(d2), ptr(y), ptr(cols), B, N, D, K, Lb, float(kernel_width), float(alpha),
+                                 ptr(out["coef"]), ptr(out["intercept"]), ptr(out.get("w")), ptr(out.get("score")),
+                                 ptr(out.get("local_pred")), ptr(ws), ws.numel(), stream()), "lime_ridge")
+    return out
+
+
+def lime_prob(logits, label, out=None):
+    """column ``label`` of softmax(logits, dim=1); ``out``: a 1-D view of M elements (any stride) to write into"""
+    _require_cuda(logits, "lime_prob")
+    logits = f32c(logits)
+    M, Cn = logits.shape
+    if out is None:
+        out = torch.empty(M, dtype=torch.float32, device=logits.device)
+    if out.dtype != torch.float32 or out.dim() != 1 or out.shape[0] != M or not out.is_cuda:
+        raise ValueError("lime_prob: out must be a fp32 device vector of M elements")
+    L.check(L.lib().ecgmm_lime_prob(ptr(logits), M, Cn, int(label), ptr(out), out.stride(0) if M > 1 else 1, stream()),
+            "lime_prob")
+    return out
+
+
+def softmax_rows(logits):
+    """softmax(logits, dim=1) [M, C], one ``lime_prob`` launch per class (C is the number of classes: 2)"""
+    logits = f32c(logits)
+    probs = torch.empty_like(logits)
+    for c in range(logits.shape[1]):
+        lime_prob(logits, c, probs[:, c])
+    return probs

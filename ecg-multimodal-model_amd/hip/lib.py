@@ -216,6 +216,10 @@ SIGNATURES = {
     "ecgmm_crnn_front_backward": (i32, [P(CRNNFrontDesc), vp, vp, P(vp), P(vp), vp, vp, sz, vp]),
     "ecgmm_log_spectrogram_frames": (i32, [i32, i32, i32]),
     "ecgmm_log_spectrogram": (i32, [vp, i32, i32, vp, i32, i32, vp, i32, vp]),
+    "ecgmm_lime_perturb": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, u64, u64, vp, vp, vp, vp, vp]),
+    "ecgmm_lime_ridge_workspace": (sz, [i32, i32, i32]),
+    "ecgmm_lime_ridge": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "ecgmm_lime_prob": (i32, [vp, i64, i32, i32, vp, i64, vp]),
 }
 
 # Entry points of the input-gradient / Grad-CAM feature.  A library selected with ECGMM_LIB for an A/B run may predate them:
@@ -246,7 +250,9 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  # the PTB-XL path (ecgmm/train_signal_only_ptb.py)
                  "ecgmm_signal_preprocess_i16", "ecgmm_weighted_sample",
                  # the workspace views of the two encoder plans (tests/test_plan_replay_*.py)
-                 "ecgmm_resnet18_ws_view", "ecgmm_resnet1d_ws_view")
+                 "ecgmm_resnet18_ws_view", "ecgmm_resnet1d_ws_view",
+                 # LIME of the fusion head (ecgmm/lime_tabular.py, csrc/lime.hip)
+                 "ecgmm_lime_perturb", "ecgmm_lime_ridge_workspace", "ecgmm_lime_ridge", "ecgmm_lime_prob")
 
 _lib = None
 

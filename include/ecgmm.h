@@ -736,6 +736,45 @@ int ecgmm_log_spectrogram_frames(int L, int nperseg, int hop);
 int ecgmm_log_spectrogram(const float* x, int S, int L, const float* table, int nperseg, int hop, float* out, int T,
                           void* stream);
 
+/* LIME tabular of the fusion head (lime_fusion_modal_balance.py:118-160; lime 0.2.x with the defaults that call hits),
+ * csrc/lime.hip.  All pointers are device pointers.  Every entry refuses a bad shape with ECGMM_ERR_SHAPE and then writes
+ * nothing; a table or column index read on the device is range-checked before it addresses memory.
+ *
+ * ecgmm_lime_perturb -- the data_inverse of explain_instance (:158-160) for B rows at once.  x [B][D] fp32.  The quartile
+ * discretiser's table, S = the widest feature's bin count (<= 16): nbins [D]; qts [D][S] float64, the first nbins - 1 of a
+ * row are np.unique(np.percentile(...)); cdf [D][S] float64, the inclusive cumulative bin frequencies; stats [4][D][S]
+ * float64 = mean, std, min, max of each bin; lim [2][D][S] fp32 = min, max rounded to fp32 (the clamp).
+ * Outputs: Z uint8 [B][N][D] (drawn bin == bin of x), inverse fp32 [B][N][D], d2 int32 [B][N] (the zeros of a Z row),
+ * u_out (nullable) double [B][N][D][2], the two uniforms of each element.  Row n = 0 is the instance: Z = 1, inverse = x.
+ * Element (b, n, f) takes ONE Philox4x32-10 block keyed by `seed` at counter
+ *     (offset low, offset high, n, 0x40000000 | (b0 + b) << 12 | f)
+ * u_bin = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53, u_val likewise from w2, w3: it depends on (seed, offset, b0 + b, n, f)
+ * alone (b0: the index of the call's first row in the caller's batch, so chunked calls reproduce one call).  The bin is the
+ * first j with cdf[j] > u_bin * cdf[nbins - 1] (the rule of ecgmm_weighted_sample: a bin of zero frequency is never drawn);
+ * the value is mean + std * Phi^-1(Phi(a) + u_val (Phi(b) - Phi(a))), a, b = (min, max - mean) / std, in fp64 (mirrored for
+ * a > 0), rounded to fp32 and clamped to lim; it is mean where std is the bare 1e-11 offset and the common point where a == b.
+ * Needs 1 <= D <= 4096, b0 + B <= 2^18, B * N < 2^31.  The caller advances `offset` by one per explanation batch. */
+int ecgmm_lime_perturb(const float* x, const double* qts, const double* cdf, const double* stats, const float* lim,
+                       const int* nbins, int S, int B, int b0, int N, int D, uint64_t seed, uint64_t offset, uint8_t* Z,
+                       float* inverse, int* d2, double* u_out, void* stream);
+/* ecgmm_lime_ridge -- the weighted ridge of explain_instance_with_data (:158-161): per sample b and label l
+ *     w_n = sqrt(exp(-d2_n / kernel_width^2)),  (Zc^T W Zc + alpha I) beta = Zc^T W yc  with w-weighted centring,
+ * over the K kept columns cols [B][K] int32 (nullable: all D columns, K == D).  Z [B][N][D] uint8 (0 / nonzero),
+ * d2 [B][N], y [B][L][N] fp32.  Outputs: coef [B][L][K], intercept [B][L]; nullable w [B][N], score [B][L] (the weighted
+ * R^2), local_pred [B][L] = intercept + sum_k coef.  The Gram runs on the exact-fp32 MFMA with fp32 accumulation, the
+ * centring is a rank-one correction in fp64, the factorisation a blocked fp32 Cholesky shared by the L right-hand sides.
+ * A column whose entries are all equal gets the coefficient 0 exactly; a column index outside [0, D) is never addressed
+ * and its coefficient is NaN.  Needs 1 <= K <= D <= 4096, K <= 1024, 1 <= L <= 8, B <= 65535, kernel_width, alpha > 0.
+ * ecgmm_lime_ridge_workspace(B, N, D), 1 <= D <= 4096: bytes for any K <= min(D, 1024) and L <= 8 (no GPU needed; 0 with
+ * the message set when refused); too small a workspace is ECGMM_ERR_WORKSPACE. */
+size_t ecgmm_lime_ridge_workspace(int B, int N, int D);
+int ecgmm_lime_ridge(const uint8_t* Z, const int* d2, const float* y, const int* cols, int B, int N, int D, int K, int L,
+                     double kernel_width, double alpha, float* coef, float* intercept, float* w, float* score,
+                     float* local_pred, void* ws, size_t ws_bytes, void* stream);
+/* predict_fn's torch.softmax(outputs, dim=1)[:, label] (:126-131): out[m * out_stride] = softmax(logits[m])[label],
+ * logits [M][C] fp32. */
+int ecgmm_lime_prob(const float* logits, int64_t M, int C, int label, float* out, int64_t out_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
