@@ -704,3 +704,61 @@ def softmax_rows(logits):
     for c in range(logits.shape[1]):
         lime_prob(logits, c, probs[:, c])
     return probs
+
+
+def _shap_operands(what, x, bg, w1, b1, w2):
+    for t in (x, bg, w1, b1, w2):
+        _require_cuda(t, what)
+    x, bg, w1, b1, w2 = (f32c(t.detach()) for t in (x, bg, w1, b1, w2))
+    if x.dim() != 2 or bg.dim() != 2 or w1.dim() != 2 or w2.dim() != 2 or b1.dim() != 1:
+        raise ValueError(f"{what} expects x [B, D], bg [N, D], w1 [H, D], b1 [H], w2 [C, H]")
+    (B, D), N, (H, C) = x.shape, bg.shape[0], (w1.shape[0], w2.shape[0])
+    if bg.shape[1] != D or w1.shape[1] != D or b1.shape[0] != H or w2.shape[1] != H:
+        raise ValueError(f"{what}: x {tuple(x.shape)}, bg {tuple(bg.shape)}, w1 {tuple(w1.shape)}, b1 {tuple(b1.shape)}, "
+                         f"w2 {tuple(w2.shape)} do not fit together")
+    return x, bg, w1, b1, w2, B, N, D, H, C
+
+
+def _shap_workspace(B, K, D, H, C, device):
+    nb = L.lib().ecgmm_shap_mlp_workspace(B, K, D, H, C)
+    if nb == 0:
+        L.check(1, "shap workspace query")
+    return _Scratch.get("shap_mlp", nb, device)
+
+
+def shap_gradient(x, bg, ridx, t, w1, b1, w2, want_var=False, want_z=False):
+    """Expected gradients of Linear(D, H) -> ReLU -> Linear(H, C) for B samples at once on the caller's draws: x [B, D],
+    bg [N, D], ridx int32 [B, K] (background row of pair k), t fp32 [B, K] (its point t x + (1 - t) bg).
+    -> dict(phi [B, D, C]) plus var [B, D, C] (population variance over k / sqrt(K)) and z [B, K, H] where asked for."""
+    x, bg, w1, b1, w2, B, N, D, H, C = _shap_operands("shap_gradient", x, bg, w1, b1, w2)
+    _require_cuda(ridx, "shap_gradient")
+    _require_cuda(t, "shap_gradient")
+    if ridx.dtype != torch.int32 or ridx.dim() != 2 or ridx.shape[0] != B or tuple(t.shape) != tuple(ridx.shape):
+        raise ValueError("shap_gradient: ridx must be int32 [B, K] and t fp32 [B, K]")
+    ridx, t = ridx.contiguous(), f32c(t)
+    K = ridx.shape[1]
+    ws = _shap_workspace(B, K, D, H, C, x.device)
+    f32 = dict(dtype=torch.float32, device=x.device)
+    out = {"phi": torch.empty(B, D, C, **f32)}
+    if want_var:
+        out["var"] = torch.empty(B, D, C, **f32)
+    if want_z:
+        out["z"] = torch.empty(B, K, H, **f32)
+    L.check(L.lib().ecgmm_shap_gradient(ptr(x), ptr(bg), ptr(ridx), ptr(t), ptr(w1), ptr(b1), ptr(w2), B, N, K, D, H, C,
+                                        ptr(out["phi"]), ptr(out.get("var")), ptr(out.get("z")), ptr(ws), ws.numel(),
+                                        stream()), "shap_gradient")
+    return out
+
+
+def shap_deep(x, bg, w1, b1, w2, want_z=False):
+    """DeepLIFT (rescale rule) of Linear(D, H) -> ReLU -> Linear(H, C) against every background row: x [B, D], bg [N, D].
+    -> dict(phi [B, D, C]) plus zx [B, H], zb [N, H] where asked for."""
+    x, bg, w1, b1, w2, B, N, D, H, C = _shap_operands("shap_deep", x, bg, w1, b1, w2)
+    ws = _shap_workspace(B, N, D, H, C, x.device)
+    f32 = dict(dtype=torch.float32, device=x.device)
+    out = {"phi": torch.empty(B, D, C, **f32)}
+    if want_z:
+        out["zx"], out["zb"] = torch.empty(B, H, **f32), torch.empty(N, H, **f32)
+    L.check(L.lib().ecgmm_shap_deep(ptr(x), ptr(bg), ptr(w1), ptr(b1), ptr(w2), B, N, D, H, C, ptr(out["phi"]),
+                                    ptr(out.get("zx")), ptr(out.get("zb")), ptr(ws), ws.numel(), stream()), "shap_deep")
+    return out

@@ -220,6 +220,9 @@ SIGNATURES = {
     "ecgmm_lime_ridge_workspace": (sz, [i32, i32, i32]),
     "ecgmm_lime_ridge": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, vp, vp, vp, vp, vp, sz, vp]),
     "ecgmm_lime_prob": (i32, [vp, i64, i32, i32, vp, i64, vp]),
+    "ecgmm_shap_mlp_workspace": (sz, [i32, i32, i32, i32, i32]),
+    "ecgmm_shap_gradient": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "ecgmm_shap_deep": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
 }
 
 # Entry points of the input-gradient / Grad-CAM feature.  A library selected with ECGMM_LIB for an A/B run may predate them:
@@ -252,7 +255,9 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  # the workspace views of the two encoder plans (tests/test_plan_replay_*.py)
                  "ecgmm_resnet18_ws_view", "ecgmm_resnet1d_ws_view",
                  # LIME of the fusion head (ecgmm/lime_tabular.py, csrc/lime.hip)
-                 "ecgmm_lime_perturb", "ecgmm_lime_ridge_workspace", "ecgmm_lime_ridge", "ecgmm_lime_prob")
+                 "ecgmm_lime_perturb", "ecgmm_lime_ridge_workspace", "ecgmm_lime_ridge", "ecgmm_lime_prob",
+                 # SHAP of the fusion head (ecgmm/shap_explainers.py, csrc/shap.hip)
+                 "ecgmm_shap_mlp_workspace", "ecgmm_shap_gradient", "ecgmm_shap_deep")
 
 _lib = None
 

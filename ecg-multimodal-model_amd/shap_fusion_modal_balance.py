@@ -6,6 +6,7 @@ then per test sample the attribution of the 768 fusion inputs aggregated to Imag
 (:158-190).  The reference asks ``shap.GradientExplainer`` for the attributions; shap is not a dependency here, so
 ``expected_gradients`` implements the estimator GradientExplainer computes (expected gradients: for baselines x'
 from the background and alpha ~ U(0,1), E[(x - x') * df/dx(x' + alpha (x - x'))]) on the HIP ops' own autograd.
+``main(explainer="gradient" | "deep")`` runs ``ecgmm.shap_explainers`` (one fused kernel, csrc/shap.hip) instead.
 """
 import numpy as np
 import torch
@@ -100,8 +101,17 @@ def fusion_fc_chunk_norms(model):
     return tuple(float(np.linalg.norm(w[:, i * d:(i + 1) * d])) for i in range(3))
 
 
-def main(config=Config, model_path=None, max_samples_per_class=50, nsamples=64, out_csv=None, quiet=False):
+EXPLAINERS = ("autograd", "gradient", "deep")
+
+
+def main(config=Config, model_path=None, max_samples_per_class=50, nsamples=64, out_csv=None, quiet=False,
+         explainer="autograd"):
+    """explainer: "autograd" = ``expected_gradients`` above; "gradient" / "deep" = ``shap_explainers.GradientExplainer`` /
+    ``DeepExplainer`` on csrc/shap.hip (the reference's shap.GradientExplainer, and the shap.DeepExplainer of its other
+    SHAP scripts)"""
     import pandas as pd
+    if explainer not in EXPLAINERS:
+        raise ValueError(f"explainer must be one of {EXPLAINERS}, not {explainer!r}")
     device = torch.device(config.device)
     train_loader, _val_loader, test_loader = get_dataloaders(config)
     model = ECGMultimodalModel(config).to(device)
@@ -110,6 +120,10 @@ def main(config=Config, model_path=None, max_samples_per_class=50, nsamples=64, 
     model.eval()
     fusion_model = FusionClassifierWrapper(model.fusion_classifier).to(device)
     bg = get_embedding_batches(model, train_loader, device, max_samples_per_class).to(device)
+    native = None
+    if explainer != "autograd":
+        from . import shap_explainers as SE
+        native = SE.GradientExplainer(fusion_model, bg) if explainer == "gradient" else SE.DeepExplainer(fusion_model, bg)
     results, soft_weights = [], None
     for *batch, _index in test_loader:
         images, ecg_signals, clinical, labels = (t.to(device) for t in batch)
@@ -117,7 +131,12 @@ def main(config=Config, model_path=None, max_samples_per_class=50, nsamples=64, 
             feats = modal_features(model, images, ecg_signals, clinical)
             _fused, soft_weights = model.attention_fusion(*feats)
         x = torch.cat(feats, dim=1)     # the reference explains the un-weighted concatenation (:150)
-        sv = expected_gradients(fusion_model, bg, x, nsamples=nsamples)
+        if explainer == "autograd":
+            sv = expected_gradients(fusion_model, bg, x, nsamples=nsamples)
+        elif explainer == "gradient":
+            sv = torch.from_numpy(native.shap_values(x, nsamples=nsamples))
+        else:
+            sv = torch.from_numpy(native.shap_values(x))
         for row in modality_contributions(sv, [f.shape[1] for f in feats], labels.tolist()):
             row["Sample_ID"] = len(results) // sv.shape[2] + 1
             results.append(row)
@@ -139,4 +158,7 @@ if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser(description="fusion-head modality attribution")
     ap.add_argument("--model_path", type=str, default=None)
-    main(model_path=ap.parse_args().model_path)
+    ap.add_argument("--explainer", choices=EXPLAINERS, default="autograd",
+                    help="autograd: the Python expected-gradients loop; gradient / deep: the native explainers")
+    args = ap.parse_args()
+    main(model_path=args.model_path, explainer=args.explainer)

@@ -775,6 +775,36 @@ int ecgmm_lime_ridge(const uint8_t* Z, const int* d2, const float* y, const int*
  * logits [M][C] fp32. */
 int ecgmm_lime_prob(const float* logits, int64_t M, int C, int label, float* out, int64_t out_stride, void* stream);
 
+/* SHAP of the fusion head, csrc/shap.hip: the two estimators the reference asks shap for, restricted to the network they are
+ * applied to, Linear(D, H) -> ReLU -> Dropout(eval) -> Linear(H, C).  All pointers are device pointers and fp32 unless said
+ * otherwise: x [B][D], bg [N][D], W1 [H][D], b1 [H], W2 [C][H], phi [B][D][C].  Per sample b and pair k with background row r:
+ *     z = W1 p + b1,  s_c = W2[c, :] * gate(z),  G_c = W1^T s_c,  phi[b, :, c] = mean_k G_c * (x_b - bg_r).
+ * Both GEMMs run on the exact-fp32 MFMA; the sums over pairs (and of the squares) are fp64 in a fixed order that depends on
+ * k alone, stored as fp32: one call with B samples equals B calls with one, bit for bit.  No floating-point atomics.
+ * Needs B, N >= 1, 1 <= K <= 4096, 1 <= D <= 4096, 1 <= H <= 256, 1 <= C <= 8; anything else is ECGMM_ERR_SHAPE, too small
+ * a workspace ECGMM_ERR_WORKSPACE, and a refused call writes nothing.
+ * ecgmm_shap_mlp_workspace(B, K, D, H, C): bytes for either entry (K = N for ecgmm_shap_deep); needs no GPU; 0 with the
+ * message set when refused.
+ *
+ * ecgmm_shap_gradient -- shap.GradientExplainer(...).shap_values (shap_fusion_modal_balance.py:122-160; the PyTorch back
+ * end with local_smoothing = 0).  ridx int32 [B][K] and t [B][K] are the caller's draws: pair (b, k) uses r = ridx[b][k] and
+ * the point p = t x_b + (1 - t) bg_r evaluated in fp32 in exactly that form (t = 1 gives x_b, t = 0 gives bg_r bit for
+ * bit); gate = 1[z > 0].  var (nullable) [B][D][C] is shap's return_variances: the population variance over k divided by
+ * sqrt(K).  z (nullable) [B][K][H] receives the pre-activations.  A ridx outside [0, N) is never used as an address and
+ * makes that sample's phi and var NaN.
+ *
+ * ecgmm_shap_deep -- shap.DeepExplainer(...).shap_values (shap_fusion.py:62, shap_fusion_paper.py:71; the PyTorch back end:
+ * rescale rule on ReLU, plain gradient through Linear, Dropout passed through).  The pairs are all (b, n), K = N;
+ * gate = (relu(zx) - relu(zb)) / (zx - zb), and 1[zb > 0] where |zx - zb| < 1e-6 (shap's constant).  zx [B][H] and zb [N][H]
+ * (both nullable) receive the pre-activations of the rows, computed once per row by the instruction sequence that computes
+ * z of ecgmm_shap_gradient: a pair with t = 1 / t = 0 there has bit-equal z. */
+size_t ecgmm_shap_mlp_workspace(int B, int K, int D, int H, int C);
+int ecgmm_shap_gradient(const float* x, const float* bg, const int* ridx, const float* t, const float* W1, const float* b1,
+                        const float* W2, int B, int N, int K, int D, int H, int C, float* phi, float* var, float* z,
+                        void* ws, size_t ws_bytes, void* stream);
+int ecgmm_shap_deep(const float* x, const float* bg, const float* W1, const float* b1, const float* W2, int B, int N, int D,
+                    int H, int C, float* phi, float* zx, float* zb, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
