@@ -268,16 +268,31 @@ void ecg_prof_begin(int kind, double flops, double bytes, hipStream_t s);
 void ecg_prof_end(hipStream_t s);
 void ecg_tl_mark(int id, hipStream_t s);   // diagnostic step timeline (prof.hip); ids: 100 + k forward, 200 + k backward
 
-// bump allocator over a caller-owned workspace (base == nullptr: measure only)
+// What an Arena handed out under a name: a fixed-capacity table on the caller's stack (the workspace views, plan_common.h).
+struct WsTable {
+  struct Entry { const char* name; int index; size_t off, bytes; };
+  Entry e[128];   // (the ResNet18 forward workspace names up to 126 tensors)
+  int n = 0;
+  bool overflow = false;
+};
+
+// bump allocator over a caller-owned workspace (base == nullptr: measure only).  With a table attached, a take made with a
+// name (and more than zero bytes) is also recorded there as (name, index, offset, bytes); a layout loop sets `index`.
 struct Arena {
   unsigned char* base;
   size_t off;
-  explicit Arena(void* b) : base((unsigned char*)b), off(0) {}
-  template <typename T> T* take(size_t count) {
+  WsTable* table;
+  int index;
+  explicit Arena(void* b, WsTable* t = nullptr) : base((unsigned char*)b), off(0), table(t), index(0) {}
+  template <typename T> T* take(size_t count, const char* name = nullptr) {
     off = align_up(off, 256);
+    if (table && name && count) {
+      if (table->n < (int)(sizeof(table->e) / sizeof(table->e[0]))) table->e[table->n++] = {name, index, off, count * sizeof(T)};
+      else table->overflow = true;
+    }
     T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
     off += count * sizeof(T);
     return p;
   }
-  void* take_bytes(size_t bytes) { return take<unsigned char>(bytes); }
+  void* take_bytes(size_t bytes, const char* name = nullptr) { return take<unsigned char>(bytes, name); }
 };

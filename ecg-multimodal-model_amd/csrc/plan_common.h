@@ -54,25 +54,60 @@ inline int se_mlp_forward(const float* m, const float* w1, const float* b1, cons
   return ecg_linear_fwd(h, w2, b2, g, N, CR, C, ECGMM_ACT_SIGMOID, nullptr, s);
 }
 
-// Workspace views (ecgmm_resnet18_ws_view / ecgmm_resnet1d_ws_view): where a named tensor lies inside a plan's workspace,
-// for tests and debugging.  A plan runs its own layout_fwd / layout_bwd on ws_view_anchor() -- a base that is never
-// dereferenced (a null base makes Arena hand out null pointers) -- lists (name, pointer, bytes) and looks the name up here.
-// A null pointer marks a tensor this descriptor does not have.
-struct WsView { const char* name; const void* p; size_t bytes; };
-inline void* ws_view_anchor() {
-  alignas(256) static unsigned char anchor[256];
-  return anchor;
+// What one residual block of either training plan keeps for its backward.  (bits: the ReLU mask of `out`, one bit per
+// element -- ResNet18 bf16 plans; m h g: the squeeze-excite vectors -- ResNet1D_SE; the downsample set: blocks that have one;
+// null otherwise)
+struct BlockWs {
+  void *w1f, *w1d, *w2f, *w2d, *wdf, *wdd;
+  void *y1, *a1, *y2, *yd, *out;
+  unsigned char* bits;
+  float *coef1, *coef2, *coefd, *m, *h, *g;
+};
+// The block's part of a forward workspace: N samples of `pix` output pixels, cin -> cout channels, `taps`-tap convolutions,
+// es bytes per element; cr: the squeeze-excite bottleneck width (0: no SE vectors).
+inline void layout_block(Arena& a, BlockWs& b, int N, size_t pix, int cin, int cout, int taps, bool down, size_t es,
+                         bool want_bits, int cr) {
+  const size_t osz = (size_t)N * pix * cout, w1 = (size_t)cout * cin * taps * es, w2 = (size_t)cout * cout * taps * es;
+  b = BlockWs{};
+  b.w1f = a.take_bytes(w1, "w1f");
+  b.w1d = a.take_bytes(w1, "w1d");
+  b.w2f = a.take_bytes(w2, "w2f");
+  b.w2d = a.take_bytes(w2, "w2d");
+  b.y1 = a.take_bytes(osz * es, "y1");
+  b.a1 = a.take_bytes(osz * es, "a1");
+  b.y2 = a.take_bytes(osz * es, "y2");
+  b.out = a.take_bytes(osz * es, "out");
+  // bn2's backward reads these 1/16-size bytes instead of `out`
+  if (want_bits) b.bits = a.take<unsigned char>(osz / 8, "bits");
+  b.coef1 = a.take<float>(4 * cout, "coef1");
+  b.coef2 = a.take<float>(4 * cout, "coef2");
+  if (cr) {
+    b.m = a.take<float>((size_t)N * cout, "m");
+    b.h = a.take<float>((size_t)N * cr, "h");
+    b.g = a.take<float>((size_t)N * cout, "g");
+  }
+  if (down) {
+    b.wdf = a.take_bytes((size_t)cout * cin * es, "wdf");
+    b.wdd = a.take_bytes((size_t)cout * cin * es, "wdd");
+    b.yd = a.take_bytes(osz * es, "yd");
+    b.coefd = a.take<float>(4 * cout, "coefd");
+  }
 }
-inline int ws_view_find(const char* who, const WsView* v, int n, const char* name, int index, size_t ws_bytes, size_t* offset,
+
+// Workspace views (ecgmm_resnet18_ws_view / ecgmm_resnet1d_ws_view): where a named tensor lies inside a plan's workspace,
+// for tests and debugging.  A plan runs its own layout_fwd / layout_bwd with a null base and a WsTable attached to the Arena
+// (ops.h): every take made with a name is recorded as (name, index, offset, bytes), and the pair is looked up here.  A
+// tensor this descriptor does not have was never taken, so it is not in the table.
+inline int ws_view_find(const char* who, const WsTable& t, const char* name, int index, size_t ws_bytes, size_t* offset,
                         size_t* bytes) {
-  for (int i = 0; i < n; ++i) {
-    if (strcmp(v[i].name, name) != 0) continue;
-    if (!v[i].p) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: no tensor '%s' (index %d) for this descriptor", who, name, index);
-    const size_t off = (size_t)((const unsigned char*)v[i].p - (const unsigned char*)ws_view_anchor());
-    if (off + v[i].bytes > ws_bytes) ECG_FAIL(ECGMM_ERR_WORKSPACE, "%s: '%s' ends past the workspace", who, name);
-    *offset = off;
-    *bytes = v[i].bytes;
+  if (t.overflow) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: more named tensors than the view table holds", who);
+  for (int i = 0; i < t.n; ++i) {
+    const WsTable::Entry& e = t.e[i];
+    if (e.index != index || strcmp(e.name, name) != 0) continue;
+    if (e.off + e.bytes > ws_bytes) ECG_FAIL(ECGMM_ERR_WORKSPACE, "%s: '%s' ends past the workspace", who, name);
+    *offset = e.off;
+    *bytes = e.bytes;
     return 0;
   }
-  ECG_FAIL(ECGMM_ERR_SHAPE, "%s: unknown tensor '%s' (index %d)", who, name, index);
+  ECG_FAIL(ECGMM_ERR_SHAPE, "%s: no tensor '%s' (index %d) for this descriptor", who, name, index);
 }

@@ -15,7 +15,7 @@
 // Parameter table order (19): image_norm.{weight,bias}, signal_norm.{w,b}, clinical_norm.{w,b},
 //   image_classifier.{w,b}, signal_classifier.{w,b}, clinical_classifier.{w,b}, attention_fusion.weights,
 //   attention_fusion.norm.{w,b}, fusion_classifier.0.{w,b}, fusion_classifier.3.{w,b}
-#include "ops.h"
+#include "plan_common.h"
 
 namespace {
 
@@ -96,9 +96,6 @@ void layout_bwd(const ecgmm_head_desc& d, void* base, HeadBwdWs& w) {
   w.partial = a.take<float>((size_t)ecg_head_bwd_blocks(d.B) * ecg_head_partial_floats(d.dim, d.num_classes > 4 ? 4 : d.num_classes));
   w.bytes = align_up(a.off, 256);
 }
-
-inline const float* P(const void* const* params, int i) { return (const float*)params[i]; }
-inline float* G(void* const* grads, int i) { return grads ? (float*)grads[i] : nullptr; }
 
 }  // namespace
 

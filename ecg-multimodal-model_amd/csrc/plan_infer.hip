@@ -39,6 +39,33 @@ struct Rot {
   }
 };
 
+// The convolutions of one residual block in a prepared blob, either encoder: folded packed weight + folded fp32 bias.
+struct BlobConvs { void *w1, *w2, *wd; float *b1, *b2, *bd; };
+void layout_blob_convs(Arena& a, BlobConvs& b, int cin, int cout, int taps, bool down, size_t es) {
+  b.w1 = a.take_bytes((size_t)cout * cin * taps * es);
+  b.b1 = a.take<float>(cout);
+  b.w2 = a.take_bytes((size_t)cout * cout * taps * es);
+  b.b2 = a.take<float>(cout);
+  b.wd = down ? a.take_bytes((size_t)cout * cin * es) : nullptr;
+  b.bd = down ? a.take<float>(cout) : nullptr;
+}
+
+// Buffers, either encoder: region A holds the stem conv output (y0_bytes) and, once the max-pool has consumed it, three
+// rotating block buffers (act_bytes each); B0 (the max-pool's output = block 0's input) is the fourth.  A ResNet18 block with
+// a downsample branch has four live tensors (x, a1, yd, out), the others three; ResNet1D_SE: x, a1, y2 (becomes out in
+// place), yd.
+struct RotWs {
+  void* y0;
+  void* rot[4];
+};
+void layout_rot(Arena& a, RotWs& w, size_t y0_bytes, size_t act_bytes) {
+  const size_t act = align_up(act_bytes, 256);
+  unsigned char* A = (unsigned char*)a.take_bytes(y0_bytes > 3 * act ? y0_bytes : 3 * act);
+  w.y0 = A;
+  w.rot[0] = a.take_bytes(act);
+  for (int i = 0; i < 3; ++i) w.rot[1 + i] = A ? A + i * act : nullptr;
+}
+
 // ================================================================================================
 // ResNet18
 // ================================================================================================
@@ -57,7 +84,7 @@ int build18(const ecgmm_resnet18_desc* d, Net18& r) {
 
 struct Blob18 {
   void* wstem; float* bstem;
-  struct B { void *w1, *w2, *wd; float *b1, *b2, *bd; } b[8];
+  BlobConvs b[8];
   float *fcw, *fcb;
   size_t bytes;
 };
@@ -68,36 +95,21 @@ void layout_blob18(const Net18& r, void* base, Blob18& q) {
   q.bstem = a.take<float>(64);
   for (int i = 0; i < 8; ++i) {
     const Blk18& k = r.blk[i];
-    Blob18::B& b = q.b[i];
-    b.w1 = a.take_bytes((size_t)k.cout * k.cin * 9 * es);
-    b.b1 = a.take<float>(k.cout);
-    b.w2 = a.take_bytes((size_t)k.cout * k.cout * 9 * es);
-    b.b2 = a.take<float>(k.cout);
-    b.wd = k.down ? a.take_bytes((size_t)k.cout * k.cin * es) : nullptr;
-    b.bd = k.down ? a.take<float>(k.cout) : nullptr;
+    layout_blob_convs(a, q.b[i], k.cin, k.cout, 9, k.down, es);
   }
   q.fcw = a.take<float>((size_t)r.d.out_dim * 512);
   q.fcb = a.take<float>(r.d.out_dim);
   q.bytes = align_up(a.off, 256);
 }
 
-// Buffers: region A holds the stem conv output and, once the max-pool has consumed it, three rotating block buffers;
-// B0 (the max-pool's output = block 0's input) is the fourth.  A block with a downsample branch has four live tensors
-// (x, a1, yd, out), the others three.
-struct Ws18 {
-  void* y0;
-  void* rot[4];
+struct Ws18 : RotWs {
   float* pooled;
   size_t bytes;
 };
 void layout_ws18(const Net18& r, void* base, Ws18& w) {
   Arena a(base);
   const size_t es = dtype_size(r.d.dtype);
-  const size_t act = align_up(r.max_act * es, 256), y0 = (size_t)r.d.N * r.H1 * r.W1 * 64 * es;
-  unsigned char* A = (unsigned char*)a.take_bytes(y0 > 3 * act ? y0 : 3 * act);
-  w.y0 = A;
-  w.rot[0] = a.take_bytes(act);
-  for (int i = 0; i < 3; ++i) w.rot[1 + i] = A ? A + i * act : nullptr;
+  layout_rot(a, w, (size_t)r.d.N * r.H1 * r.W1 * 64 * es, r.max_act * es);
   w.pooled = a.take<float>((size_t)r.d.N * 512);
   w.bytes = align_up(a.off, 256);
 }
@@ -124,7 +136,7 @@ int build1d(const ecgmm_resnet1d_desc* d, Net1D& r) {
 
 struct Blob1D {
   void* wstem; float* bstem;
-  struct B { void *w1, *w2, *wd; float *b1, *b2, *bd, *sw1, *sb1, *sw2, *sb2; } b[3];
+  struct B : BlobConvs { float *sw1, *sb1, *sw2, *sb2; } b[3];
   float *cw1, *cb1, *cw2, *cb2;
   size_t bytes;
 };
@@ -136,12 +148,7 @@ void layout_blob1d(const Net1D& r, void* base, Blob1D& q) {
   for (int i = 0; i < 3; ++i) {
     const Blk1& k = r.blk[i];
     Blob1D::B& b = q.b[i];
-    b.w1 = a.take_bytes((size_t)k.cout * k.cin * 3 * es);
-    b.b1 = a.take<float>(k.cout);
-    b.w2 = a.take_bytes((size_t)k.cout * k.cout * 3 * es);
-    b.b2 = a.take<float>(k.cout);
-    b.wd = k.down ? a.take_bytes((size_t)k.cout * k.cin * es) : nullptr;
-    b.bd = k.down ? a.take<float>(k.cout) : nullptr;
+    layout_blob_convs(a, b, k.cin, k.cout, 3, k.down, es);
     b.sw1 = a.take<float>((size_t)k.cr * k.cout);
     b.sb1 = a.take<float>(k.cr);
     b.sw2 = a.take<float>((size_t)k.cout * k.cr);
@@ -154,20 +161,14 @@ void layout_blob1d(const Net1D& r, void* base, Blob1D& q) {
   q.bytes = align_up(a.off, 256);
 }
 
-struct Ws1D {
-  void* y0;
-  void* rot[4];   // x, a1, y2 (becomes out in place), yd
+struct Ws1D : RotWs {
   float *m, *h, *g, *pooled, *h1;
   size_t bytes;
 };
 void layout_ws1d(const Net1D& r, void* base, Ws1D& w) {
   Arena a(base);
   const size_t es = dtype_size(r.d.dtype);
-  const size_t act = align_up(r.max_act * es, 256), y0 = (size_t)r.d.N * r.L1 * 64 * es;
-  unsigned char* A = (unsigned char*)a.take_bytes(y0 > 3 * act ? y0 : 3 * act);
-  w.y0 = A;
-  w.rot[0] = a.take_bytes(act);
-  for (int i = 0; i < 3; ++i) w.rot[1 + i] = A ? A + i * act : nullptr;
+  layout_rot(a, w, (size_t)r.d.N * r.L1 * 64 * es, r.max_act * es);
   w.m = a.take<float>((size_t)r.d.N * 256);
   w.h = a.take<float>((size_t)r.d.N * 16);
   w.g = a.take<float>((size_t)r.d.N * 256);
@@ -225,7 +226,7 @@ extern "C" int ecgmm_resnet18_infer_prepare(const ecgmm_resnet18_desc* d, const 
   items[n++] = conv_item(ECG_FOLD_STEM, params, 0, nullptr, 1, buffers, 0, q.wstem, q.bstem, 64, 3, 7);
   for (int i = 0; i < 8; ++i) {
     const Blk18& k = r.blk[i];
-    const Blob18::B& b = q.b[i];
+    const BlobConvs& b = q.b[i];
     items[n++] = conv_item(ECG_FOLD_CONV, params, k.p_conv1, nullptr, k.p_bn1, buffers, k.b_bn1, b.w1, b.b1, k.cout, k.cin, 9);
     items[n++] = conv_item(ECG_FOLD_CONV, params, k.p_conv2, nullptr, k.p_bn2, buffers, k.b_bn2, b.w2, b.b2, k.cout, k.cout, 9);
     if (k.down)
@@ -267,7 +268,7 @@ extern "C" int ecgmm_resnet18_infer(const ecgmm_resnet18_desc* d, const float* i
   Rot rot = {{w.rot[0], w.rot[1], w.rot[2], w.rot[3]}, 0, 0u};
   for (int i = 0; i < 8; ++i) {
     const Blk18& k = r.blk[i];
-    const Blob18::B& b = q.b[i];
+    const BlobConvs& b = q.b[i];
     const void* cur = rot.buf[rot.cur];
     void* a1 = rot.take();
     void* yd = k.down ? rot.take() : nullptr;

@@ -30,62 +30,39 @@ int build(const ecgmm_resnet18_desc* d, Net18& r) {
 struct FwdWs {
   void* wstem;
   void* y0; float* coef0; void* p0; unsigned char* idx0;
-  struct B {
-    void *w1f, *w1d, *w2f, *w2d, *wdf, *wdd;
-    void *y1, *a1, *y2, *yd, *out;
-    unsigned char* bits;   // ReLU mask of `out`, one bit per element (bf16 plans; null otherwise)
-    float *coef1, *coef2, *coefd;
-  } b[8];
+  BlockWs b[8];
   float* pooled;
   float* stats;  // transient partial-sum rows (largest layer)
   float* stats_d;  // the same for the downsample convolutions (they run on the side stream beside conv1 / conv2)
   size_t bytes;
 };
 
-void layout_fwd(const Net18& r, void* base, FwdWs& w) {
-  Arena a(base);
+// (views: a WsTable the named takes are recorded in, see ws_view_find)
+void layout_fwd(const Net18& r, void* base, FwdWs& w, WsTable* views = nullptr) {
+  Arena a(base, views);
   const size_t es = dtype_size(r.d.dtype);
   const int N = r.d.N;
-  w.wstem = a.take_bytes(ecg_stem_packed_elems(3, 7) * es);
+  w.wstem = a.take_bytes(ecg_stem_packed_elems(3, 7) * es, "wstem");
   // (the recomputing stem never materialises the conv output)
-  w.y0 = stem_recompute(r.d.dtype) ? nullptr : a.take_bytes((size_t)N * r.H1 * r.W1 * 64 * es);
-  w.coef0 = a.take<float>(4 * 64);
-  w.p0 = a.take_bytes((size_t)N * r.H2 * r.W2 * 64 * es);
-  w.idx0 = a.take<unsigned char>((size_t)N * r.H2 * r.W2 * 64);
+  w.y0 = stem_recompute(r.d.dtype) ? nullptr : a.take_bytes((size_t)N * r.H1 * r.W1 * 64 * es, "y0");
+  w.coef0 = a.take<float>(4 * 64, "coef0");
+  w.p0 = a.take_bytes((size_t)N * r.H2 * r.W2 * 64 * es, "p0");
+  w.idx0 = a.take<unsigned char>((size_t)N * r.H2 * r.W2 * 64, "idx0");
   size_t max_rows_c = (size_t)(stem_recompute(r.d.dtype) ? ecg_stem_stats_only_rows(N, 3, r.d.H, r.d.W, 7)
                                                           : ecg_stem_stats_rows(N, 3, r.d.H, r.d.W, 7)) * 2 * 64;
   max_rows_c += (size_t)ECG_TAIL_ROWS * 2 * 64;
   size_t max_rows_d = 64;
   for (int i = 0; i < 8; ++i) {
     const Blk18& k = r.blk[i];
-    FwdWs::B& b = w.b[i];
-    size_t osz = (size_t)N * k.hout * k.wout * k.cout;
-    b.w1f = a.take_bytes((size_t)k.cout * k.cin * 9 * es);
-    b.w1d = a.take_bytes((size_t)k.cout * k.cin * 9 * es);
-    b.w2f = a.take_bytes((size_t)k.cout * k.cout * 9 * es);
-    b.w2d = a.take_bytes((size_t)k.cout * k.cout * 9 * es);
-    b.y1 = a.take_bytes(osz * es);
-    b.a1 = a.take_bytes(osz * es);
-    b.y2 = a.take_bytes(osz * es);
-    b.out = a.take_bytes(osz * es);
-    // ReLU mask of `out` as bits (bf16 training plans): bn2's backward reads these 1/16-size bytes instead of `out`
-    b.bits = es == 2 ? (unsigned char*)a.take_bytes(osz / 8) : nullptr;
-    b.coef1 = a.take<float>(4 * k.cout);
-    b.coef2 = a.take<float>(4 * k.cout);
-    if (k.down) {
-      b.wdf = a.take_bytes((size_t)k.cout * k.cin * es);
-      b.wdd = a.take_bytes((size_t)k.cout * k.cin * es);
-      b.yd = a.take_bytes(osz * es);
-      b.coefd = a.take<float>(4 * k.cout);
-    } else {
-      b.wdf = b.wdd = b.yd = nullptr;
-      b.coefd = nullptr;
-    }
+    a.index = i;
+    // (ReLU mask of `out` as bits: bf16 plans)
+    layout_block(a, w.b[i], N, (size_t)k.hout * k.wout, k.cin, k.cout, 9, k.down, es, es == 2, 0);
     size_t rows_c = (size_t)(ecg_conv_stats_rows((long)N * k.hout * k.wout) + ECG_TAIL_ROWS) * 2 * k.cout;
     if (rows_c > max_rows_c) max_rows_c = rows_c;
     if (k.down && rows_c > max_rows_d) max_rows_d = rows_c;
   }
-  w.pooled = a.take<float>((size_t)N * 512);
+  a.index = 0;
+  w.pooled = a.take<float>((size_t)N * 512, "pooled");
   w.stats = a.take<float>(max_rows_c);
   w.stats_d = a.take<float>(max_rows_d);
   w.bytes = align_up(a.off, 256);
@@ -113,24 +90,26 @@ struct BwdWs {
   size_t bytes;
 };
 
-void layout_bwd(const Net18& r, void* base, BwdWs& w) {
-  Arena a(base);
+void layout_bwd(const Net18& r, void* base, BwdWs& w, WsTable* views = nullptr) {
+  Arena a(base, views);
   const size_t es = dtype_size(r.d.dtype);
   const int N = r.d.N;
-  for (int i = 0; i < 2; ++i) w.X[i] = a.take_bytes(r.max_act * es);
-  w.dz = a.take_bytes(r.max_act * es);
-  for (int i = 0; i < 2; ++i) {
-    w.dy[i] = a.take_bytes(r.max_act * es);
-    w.dy1[i] = a.take_bytes(r.max_act * es);
-    w.dyd[i] = a.take_bytes(r.max_act * es);
+  for (a.index = 0; a.index < 2; ++a.index) w.X[a.index] = a.take_bytes(r.max_act * es, "X");
+  a.index = 0;
+  w.dz = a.take_bytes(r.max_act * es, "dz");
+  for (a.index = 0; a.index < 2; ++a.index) {
+    w.dy[a.index] = a.take_bytes(r.max_act * es, "dy");
+    w.dy1[a.index] = a.take_bytes(r.max_act * es, "dy1");
+    w.dyd[a.index] = a.take_bytes(r.max_act * es, "dyd");
   }
-  w.da = a.take_bytes(r.max_act * es);
-  w.dtmp = a.take_bytes(r.max_act * es);
+  a.index = 0;
+  w.da = a.take_bytes(r.max_act * es, "da");
+  w.dtmp = a.take_bytes(r.max_act * es, "dtmp");
   const bool recompute = stem_recompute(r.d.dtype);
   size_t big = recompute ? 0 : (size_t)N * r.H1 * r.W1 * 64;   // (recomputing stem: neither dz0 nor dy0 exist)
-  w.big0 = a.take_bytes(big * es);
-  w.big1 = a.take_bytes(big * es);
-  w.dpooled = a.take<float>((size_t)N * 512);
+  w.big0 = a.take_bytes(big * es, "big0");
+  w.big1 = a.take_bytes(big * es, "big1");
+  w.dpooled = a.take<float>((size_t)N * 512, "dpooled");
   size_t bn = ecg_bn_bwd_scratch(r.d.dtype, (long)N * r.H1 * r.W1, 64);
   size_t wg = 0;
   for (int i = 0; i < 8; ++i) {
@@ -252,55 +231,13 @@ extern "C" int ecgmm_resnet18_ws_view(const ecgmm_resnet18_desc* d, int backward
   Net18 r;
   ECG_TRY(build(d, r));
   if (!name || !offset || !bytes) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet18 ws_view: null argument");
-  const size_t es = dtype_size(r.d.dtype);
-  const int N = r.d.N;
-  WsView v[24];
-  int n = 0;
-  size_t total = 0;
-  if (!backward) {
-    FwdWs w;
-    layout_fwd(r, ws_view_anchor(), w);
-    total = w.bytes;
-    if (index == 0) {
-      const size_t pool = (size_t)N * r.H2 * r.W2 * 64;
-      v[n++] = {"wstem", w.wstem, ecg_stem_packed_elems(3, 7) * es};
-      v[n++] = {"y0", w.y0, (size_t)N * r.H1 * r.W1 * 64 * es};
-      v[n++] = {"coef0", w.coef0, 4 * 64 * sizeof(float)};
-      v[n++] = {"p0", w.p0, pool * es};
-      v[n++] = {"idx0", w.idx0, pool};
-      v[n++] = {"pooled", w.pooled, (size_t)N * 512 * sizeof(float)};
-    }
-    if (index >= 0 && index < 8) {
-      const Blk18& k = r.blk[index];
-      const FwdWs::B& b = w.b[index];
-      const size_t osz = (size_t)N * k.hout * k.wout * k.cout, cf = 4 * k.cout * sizeof(float);
-      const size_t w1 = (size_t)k.cout * k.cin * 9 * es, w2 = (size_t)k.cout * k.cout * 9 * es, wd = (size_t)k.cout * k.cin * es;
-      v[n++] = {"w1f", b.w1f, w1}; v[n++] = {"w1d", b.w1d, w1};
-      v[n++] = {"w2f", b.w2f, w2}; v[n++] = {"w2d", b.w2d, w2};
-      v[n++] = {"wdf", b.wdf, wd}; v[n++] = {"wdd", b.wdd, wd};
-      v[n++] = {"y1", b.y1, osz * es}; v[n++] = {"a1", b.a1, osz * es}; v[n++] = {"y2", b.y2, osz * es};
-      v[n++] = {"yd", b.yd, osz * es}; v[n++] = {"out", b.out, osz * es};
-      v[n++] = {"bits", b.bits, osz / 8};
-      v[n++] = {"coef1", b.coef1, cf}; v[n++] = {"coef2", b.coef2, cf}; v[n++] = {"coefd", b.coefd, cf};
-    }
-  } else {
-    BwdWs q;
-    layout_bwd(r, ws_view_anchor(), q);
-    total = q.bytes;
-    const size_t act = r.max_act * es;
-    const size_t big = stem_recompute(r.d.dtype) ? 0 : (size_t)N * r.H1 * r.W1 * 64 * es;
-    if (index == 0 || index == 1) {
-      v[n++] = {"X", q.X[index], act}; v[n++] = {"dy", q.dy[index], act};
-      v[n++] = {"dy1", q.dy1[index], act}; v[n++] = {"dyd", q.dyd[index], act};
-    }
-    if (index == 0) {
-      v[n++] = {"dz", q.dz, act}; v[n++] = {"da", q.da, act}; v[n++] = {"dtmp", q.dtmp, act};
-      v[n++] = {"big0", big ? q.big0 : nullptr, big}; v[n++] = {"big1", big ? q.big1 : nullptr, big};
-      v[n++] = {"dpooled", q.dpooled, (size_t)N * 512 * sizeof(float)};
-    }
-  }
-  return ws_view_find(backward ? "resnet18 ws_view (backward)" : "resnet18 ws_view (forward)", v, n, name, index, total, offset,
-                      bytes);
+  WsTable t;
+  FwdWs w;
+  BwdWs q;
+  if (backward) layout_bwd(r, nullptr, q, &t);
+  else layout_fwd(r, nullptr, w, &t);
+  return ws_view_find(backward ? "resnet18 ws_view (backward)" : "resnet18 ws_view (forward)", t, name, index,
+                      backward ? q.bytes : w.bytes, offset, bytes);
 }
 
 extern "C" int ecgmm_resnet18_forward(const ecgmm_resnet18_desc* d, const float* image, const void* const* params,
@@ -326,7 +263,7 @@ extern "C" int ecgmm_resnet18_forward(const ecgmm_resnet18_desc* d, const float*
     int n = 0;
     for (int i = 0; i < 8; ++i) {
       const Blk18& k = r.blk[i];
-      FwdWs::B& b = w.b[i];
+      BlockWs& b = w.b[i];
       items[n++] = {P(params, k.p_conv1), b.w1f, b.w1d, k.cout, k.cin, 9};
       items[n++] = {P(params, k.p_conv2), b.w2f, b.w2d, k.cout, k.cout, 9};
       if (k.down) items[n++] = {P(params, k.p_dconv), b.wdf, b.wdd, k.cout, k.cin, 1};
@@ -353,7 +290,7 @@ extern "C" int ecgmm_resnet18_forward(const ecgmm_resnet18_desc* d, const float*
   const void* cur = w.p0;
   for (int i = 0; i < 8; ++i) {
     const Blk18& k = r.blk[i];
-    FwdWs::B& b = w.b[i];
+    BlockWs& b = w.b[i];
     const long M = (long)N * k.hout * k.wout;
     const int rows = ecg_conv_stats_rows(M);
     ConvGeom g1 = k.conv1_geom(N);
@@ -442,7 +379,7 @@ static int r18_backward(const ecgmm_resnet18_desc* d, const float* image, const 
     } else if (st <= 8) {
       const int i = 8 - st;
       const Blk18& k = r.blk[i];
-      FwdWs::B& b = w.b[i];
+      BlockWs& b = w.b[i];
       const void* in = i == 0 ? w.p0 : w.b[i - 1].out;
       const void* dcur = q.X[(st - 1) & 1];
       void* din = q.X[st & 1];
@@ -534,7 +471,7 @@ static int r18_backward(const ecgmm_resnet18_desc* d, const float* image, const 
         // this conv1 dgrad produces the previous block's output gradient: fuse that block's bn2 reduction (see above)
         ConvEpi eb = {};
         if (fuse_here && i > 0 && ecg_conv_halo_ok(dt, 1, g1)) {
-          const FwdWs::B& pb = w.b[i - 1];
+          const BlockWs& pb = w.b[i - 1];
           eb.wg_rows = 1; eb.red_y = pb.y2; eb.red_mask = pb.out; eb.red_coef = pb.coef2; eb.red_rows = q.red2;
         }
         ECG_TRY(ecg_conv_igemm(dt, 1, g1, dy1b, b.w1d, din, nullptr, dzp, nullptr, 0, s, &eb));

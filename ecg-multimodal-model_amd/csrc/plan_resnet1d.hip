@@ -18,61 +18,37 @@ int build(const ecgmm_resnet1d_desc* d, Net1D& r) {
 
 struct Fwd1 {
   void* wstem; void* y0; float* coef0; void* p0; unsigned char* idx0;
-  struct B {
-    void *w1f, *w1d, *w2f, *w2d, *wdf, *wdd;
-    void *y1, *a1, *y2, *yd, *out;
-    float *coef1, *coef2, *coefd, *m, *h, *g;
-  } b[3];
+  BlockWs b[3];
   float *pooled, *h1, *hd;
   unsigned char* dmask;
   float* stats;
   size_t bytes;
 };
 
-void layout_fwd(const Net1D& r, void* base, Fwd1& w) {
-  Arena a(base);
+// (views: a WsTable the named takes are recorded in, see ws_view_find)
+void layout_fwd(const Net1D& r, void* base, Fwd1& w, WsTable* views = nullptr) {
+  Arena a(base, views);
   const size_t es = dtype_size(r.d.dtype);
   const int N = r.d.N;
-  w.wstem = a.take_bytes(ecg_stem_packed_elems(r.d.cin, 1) * es);
-  w.y0 = a.take_bytes((size_t)N * r.L1 * 64 * es);
-  w.coef0 = a.take<float>(4 * 64);
-  w.p0 = a.take_bytes((size_t)N * r.L2 * 64 * es);
-  w.idx0 = a.take<unsigned char>((size_t)N * r.L2 * 64);
+  w.wstem = a.take_bytes(ecg_stem_packed_elems(r.d.cin, 1) * es, "wstem");
+  w.y0 = a.take_bytes((size_t)N * r.L1 * 64 * es, "y0");
+  w.coef0 = a.take<float>(4 * 64, "coef0");
+  w.p0 = a.take_bytes((size_t)N * r.L2 * 64 * es, "p0");
+  w.idx0 = a.take<unsigned char>((size_t)N * r.L2 * 64, "idx0");
   size_t max_rows_c = (size_t)ecg_stem_stats_rows(N, r.d.cin, 1, r.d.L, 1) * 2 * 64;
   max_rows_c += (size_t)ECG_TAIL_ROWS * 2 * 64;
   for (int i = 0; i < 3; ++i) {
     const Blk1& k = r.blk[i];
-    Fwd1::B& b = w.b[i];
-    size_t osz = (size_t)N * k.lout * k.cout;
-    b.w1f = a.take_bytes((size_t)k.cout * k.cin * 3 * es);
-    b.w1d = a.take_bytes((size_t)k.cout * k.cin * 3 * es);
-    b.w2f = a.take_bytes((size_t)k.cout * k.cout * 3 * es);
-    b.w2d = a.take_bytes((size_t)k.cout * k.cout * 3 * es);
-    b.y1 = a.take_bytes(osz * es);
-    b.a1 = a.take_bytes(osz * es);
-    b.y2 = a.take_bytes(osz * es);
-    b.out = a.take_bytes(osz * es);
-    b.coef1 = a.take<float>(4 * k.cout);
-    b.coef2 = a.take<float>(4 * k.cout);
-    b.m = a.take<float>((size_t)N * k.cout);
-    b.h = a.take<float>((size_t)N * k.cr);
-    b.g = a.take<float>((size_t)N * k.cout);
-    if (k.down) {
-      b.wdf = a.take_bytes((size_t)k.cout * k.cin * es);
-      b.wdd = a.take_bytes((size_t)k.cout * k.cin * es);
-      b.yd = a.take_bytes(osz * es);
-      b.coefd = a.take<float>(4 * k.cout);
-    } else {
-      b.wdf = b.wdd = b.yd = nullptr;
-      b.coefd = nullptr;
-    }
+    a.index = i;
+    layout_block(a, w.b[i], N, (size_t)k.lout, k.cin, k.cout, 3, k.down, es, false, k.cr);
     size_t rows_c = (size_t)(ecg_conv_stats_rows((long)N * k.lout) + ECG_TAIL_ROWS) * 2 * k.cout;
     if (rows_c > max_rows_c) max_rows_c = rows_c;
   }
-  w.pooled = a.take<float>((size_t)N * 256);
-  w.h1 = a.take<float>((size_t)N * 64);
-  w.hd = a.take<float>((size_t)N * 64);
-  w.dmask = a.take<unsigned char>((size_t)N * 64);
+  a.index = 0;
+  w.pooled = a.take<float>((size_t)N * 256, "pooled");
+  w.h1 = a.take<float>((size_t)N * 64, "h1");
+  w.hd = a.take<float>((size_t)N * 64, "hd");
+  w.dmask = a.take<unsigned char>((size_t)N * 64, "dmask");
   w.stats = a.take<float>(max_rows_c);
   w.bytes = align_up(a.off, 256);
 }
@@ -88,27 +64,28 @@ struct Bwd1 {
   size_t bytes;
 };
 
-void layout_bwd(const Net1D& r, void* base, Bwd1& w) {
-  Arena a(base);
+void layout_bwd(const Net1D& r, void* base, Bwd1& w, WsTable* views = nullptr) {
+  Arena a(base, views);
   const size_t es = dtype_size(r.d.dtype);
   const int N = r.d.N;
-  for (int i = 0; i < 2; ++i) w.X[i] = a.take_bytes(r.max_act * es);
-  w.dz = a.take_bytes(r.max_act * es);
-  w.dy = a.take_bytes(r.max_act * es);
-  w.dy1 = a.take_bytes(r.max_act * es);  // own buffers for the three wgrad operands: the side stream still reads one
-  w.dyd = a.take_bytes(r.max_act * es);  // while the main stream's BatchNorm backward writes the next
-  w.da = a.take_bytes(r.max_act * es);
-  w.dtmp = a.take_bytes(r.max_act * es);
+  for (a.index = 0; a.index < 2; ++a.index) w.X[a.index] = a.take_bytes(r.max_act * es, "X");
+  a.index = 0;
+  w.dz = a.take_bytes(r.max_act * es, "dz");
+  w.dy = a.take_bytes(r.max_act * es, "dy");
+  w.dy1 = a.take_bytes(r.max_act * es, "dy1");  // own buffers for the three wgrad operands: the side stream still reads one
+  w.dyd = a.take_bytes(r.max_act * es, "dyd");  // while the main stream's BatchNorm backward writes the next
+  w.da = a.take_bytes(r.max_act * es, "da");
+  w.dtmp = a.take_bytes(r.max_act * es, "dtmp");
   size_t big = (size_t)N * r.L1 * 64;
-  w.big0 = a.take_bytes(big * es);
-  w.big1 = a.take_bytes(big * es);
-  w.dpooled = a.take<float>((size_t)N * 256);
-  w.dh1 = a.take<float>((size_t)N * 64);
-  w.dfeat_h = a.take<float>((size_t)N * 64);
-  w.dg = a.take<float>((size_t)N * 256);
-  w.ds = a.take<float>((size_t)N * 256);
-  w.dh = a.take<float>((size_t)N * 16);
-  w.dm = a.take<float>((size_t)N * 256);
+  w.big0 = a.take_bytes(big * es, "big0");
+  w.big1 = a.take_bytes(big * es, "big1");
+  w.dpooled = a.take<float>((size_t)N * 256, "dpooled");
+  w.dh1 = a.take<float>((size_t)N * 64, "dh1");
+  w.dfeat_h = a.take<float>((size_t)N * 64, "dfeat_h");
+  w.dg = a.take<float>((size_t)N * 256, "dg");
+  w.ds = a.take<float>((size_t)N * 256, "ds");
+  w.dh = a.take<float>((size_t)N * 16, "dh");
+  w.dm = a.take<float>((size_t)N * 256, "dm");
   w.dbias_scratch = a.take<float>(256);
   w.sa1 = a.take<float>((size_t)N * 256);
   w.sa2 = a.take<float>((size_t)N * 256);
@@ -202,59 +179,13 @@ extern "C" int ecgmm_resnet1d_ws_view(const ecgmm_resnet1d_desc* d, int backward
   Net1D r;
   ECG_TRY(build(d, r));
   if (!name || !offset || !bytes) ECG_FAIL(ECGMM_ERR_SHAPE, "resnet1d ws_view: null argument");
-  const size_t es = dtype_size(r.d.dtype), f = sizeof(float);
-  const int N = r.d.N;
-  WsView v[32];
-  int n = 0;
-  size_t total = 0;
-  if (!backward) {
-    Fwd1 w;
-    layout_fwd(r, ws_view_anchor(), w);
-    total = w.bytes;
-    if (index == 0) {
-      const size_t pool = (size_t)N * r.L2 * 64;
-      v[n++] = {"wstem", w.wstem, ecg_stem_packed_elems(r.d.cin, 1) * es};
-      v[n++] = {"y0", w.y0, (size_t)N * r.L1 * 64 * es};
-      v[n++] = {"coef0", w.coef0, 4 * 64 * f};
-      v[n++] = {"p0", w.p0, pool * es};
-      v[n++] = {"idx0", w.idx0, pool};
-      v[n++] = {"pooled", w.pooled, (size_t)N * 256 * f};
-      v[n++] = {"h1", w.h1, (size_t)N * 64 * f};
-      v[n++] = {"hd", w.hd, (size_t)N * 64 * f};
-      v[n++] = {"dmask", w.dmask, (size_t)N * 64};
-    }
-    if (index >= 0 && index < 3) {
-      const Blk1& k = r.blk[index];
-      const Fwd1::B& b = w.b[index];
-      const size_t osz = (size_t)N * k.lout * k.cout, cf = 4 * k.cout * f;
-      const size_t w1 = (size_t)k.cout * k.cin * 3 * es, w2 = (size_t)k.cout * k.cout * 3 * es, wd = (size_t)k.cout * k.cin * es;
-      v[n++] = {"w1f", b.w1f, w1}; v[n++] = {"w1d", b.w1d, w1};
-      v[n++] = {"w2f", b.w2f, w2}; v[n++] = {"w2d", b.w2d, w2};
-      v[n++] = {"wdf", b.wdf, wd}; v[n++] = {"wdd", b.wdd, wd};
-      v[n++] = {"y1", b.y1, osz * es}; v[n++] = {"a1", b.a1, osz * es}; v[n++] = {"y2", b.y2, osz * es};
-      v[n++] = {"yd", b.yd, osz * es}; v[n++] = {"out", b.out, osz * es};
-      v[n++] = {"coef1", b.coef1, cf}; v[n++] = {"coef2", b.coef2, cf}; v[n++] = {"coefd", b.coefd, cf};
-      v[n++] = {"m", b.m, (size_t)N * k.cout * f}; v[n++] = {"h", b.h, (size_t)N * k.cr * f};
-      v[n++] = {"g", b.g, (size_t)N * k.cout * f};
-    }
-  } else {
-    Bwd1 q;
-    layout_bwd(r, ws_view_anchor(), q);
-    total = q.bytes;
-    const size_t act = r.max_act * es, big = (size_t)N * r.L1 * 64 * es;
-    if (index == 0 || index == 1) v[n++] = {"X", q.X[index], act};
-    if (index == 0) {
-      v[n++] = {"dz", q.dz, act}; v[n++] = {"dy", q.dy, act}; v[n++] = {"dy1", q.dy1, act}; v[n++] = {"dyd", q.dyd, act};
-      v[n++] = {"da", q.da, act}; v[n++] = {"dtmp", q.dtmp, act};
-      v[n++] = {"big0", q.big0, big}; v[n++] = {"big1", q.big1, big};
-      v[n++] = {"dpooled", q.dpooled, (size_t)N * 256 * f};
-      v[n++] = {"dh1", q.dh1, (size_t)N * 64 * f}; v[n++] = {"dfeat_h", q.dfeat_h, (size_t)N * 64 * f};
-      v[n++] = {"dg", q.dg, (size_t)N * 256 * f}; v[n++] = {"ds", q.ds, (size_t)N * 256 * f};
-      v[n++] = {"dh", q.dh, (size_t)N * 16 * f}; v[n++] = {"dm", q.dm, (size_t)N * 256 * f};
-    }
-  }
-  return ws_view_find(backward ? "resnet1d ws_view (backward)" : "resnet1d ws_view (forward)", v, n, name, index, total, offset,
-                      bytes);
+  WsTable t;
+  Fwd1 w;
+  Bwd1 q;
+  if (backward) layout_bwd(r, nullptr, q, &t);
+  else layout_fwd(r, nullptr, w, &t);
+  return ws_view_find(backward ? "resnet1d ws_view (backward)" : "resnet1d ws_view (forward)", t, name, index,
+                      backward ? q.bytes : w.bytes, offset, bytes);
 }
 
 extern "C" int ecgmm_resnet1d_forward(const ecgmm_resnet1d_desc* d, const float* signal, const void* const* params,
@@ -274,7 +205,7 @@ extern "C" int ecgmm_resnet1d_forward(const ecgmm_resnet1d_desc* d, const float*
     int n = 0;
     for (int i = 0; i < 3; ++i) {
       const Blk1& k = r.blk[i];
-      Fwd1::B& b = w.b[i];
+      BlockWs& b = w.b[i];
       items[n++] = {P(params, k.p0 + T1_CONV1_W), b.w1f, b.w1d, k.cout, k.cin, 3};
       items[n++] = {P(params, k.p0 + T1_CONV2_W), b.w2f, b.w2d, k.cout, k.cout, 3};
       if (k.down) items[n++] = {P(params, k.p0 + T1_DOWN_W), b.wdf, b.wdd, k.cout, k.cin, 1};
@@ -290,7 +221,7 @@ extern "C" int ecgmm_resnet1d_forward(const ecgmm_resnet1d_desc* d, const float*
   const void* cur = w.p0;
   for (int i = 0; i < 3; ++i) {
     const Blk1& k = r.blk[i];
-    Fwd1::B& b = w.b[i];
+    BlockWs& b = w.b[i];
     const int p = k.p0, bb = k.b0;
     const long M = (long)N * k.lout;
     const int rows = ecg_conv_stats_rows(M);
@@ -360,7 +291,7 @@ static int r1d_backward(const ecgmm_resnet1d_desc* d, const float* signal, const
     } else if (st <= 3) {
       const int i = 3 - st;
       const Blk1& k = r.blk[i];
-      Fwd1::B& b = w.b[i];
+      BlockWs& b = w.b[i];
       const int p = k.p0;
       const void* in = i == 0 ? w.p0 : w.b[i - 1].out;
       const void* dcur = q.X[(st - 1) & 1];
