@@ -50,6 +50,7 @@ int ecgmm_conv_wgrad_pingpong(int on) { sw::WGRAD_PP.set(on); return 0; }
 int ecgmm_conv_wgrad_ring_enable(int on) { sw::WGRAD_RING.set(on); return 0; }
 int ecgmm_bn_fold(int on) { sw::BN_FOLD.set(on); return 0; }
 int ecgmm_bn_fold_slice(int on) { sw::BN_FOLD_SLICE.set(on); return 0; }
+int ecgmm_bn_dual(int on) { ecg_bn_dual_set(on); return 0; }   // (run time only: no environment variable, not in the table)
 int ecgmm_bn_fuse_min_pixels(int64_t m) { sw::BN_FUSE_MIN_M.set((long)m); return 0; }
 int ecgmm_stem_recompute(int on) { sw::STEM_RECOMPUTE.set(on); return 0; }
 int ecgmm_infer_down_side(int on) { sw::INFER_DOWN_SIDE.set(on); return 0; }
@@ -194,6 +195,15 @@ int ecgmm_bn_bwd_bits(int dtype, const void* dout, const uint8_t* mask_bits, con
   if (dtype != ECGMM_BF16 || !mask_bits) ECG_FAIL(ECGMM_ERR_SHAPE, "bn_bwd_bits: bf16 with a bit mask only");
   return ecg_bn_bwd(dtype, dout, nullptr, gate, addc, rows_per_sample, y, coef, gamma, dgamma, dbeta, dy, dz_out, dbias,
                     (long)M, C, (float*)scratch, S_(stream), mask_bits);
+}
+int ecgmm_bn_bwd_dual(int dtype, const void* dout, const void* maskref, const uint8_t* mask_bits, const float* gate,
+                      const float* addc, const void* y_a, const float* coef_a, const float* gamma_a, float* dgamma_a,
+                      float* dbeta_a, void* dy_a, const void* y_b, const float* coef_b, const float* gamma_b,
+                      float* dgamma_b, float* dbeta_b, void* dy_b, void* dz, float* dbias, int64_t M, int C, void* scratch_a,
+                      void* scratch_b, void* stream) {
+  return ecg_bn_bwd_dual(dtype, dout, maskref, mask_bits, gate, addc, y_a, coef_a, gamma_a, dgamma_a, dbeta_a, dy_a, y_b,
+                         coef_b, gamma_b, dgamma_b, dbeta_b, dy_b, dz, dbias, (long)M, C, (float*)scratch_a, (float*)scratch_b,
+                         S_(stream));
 }
 
 int ecgmm_conv_bwd_data_bnred(int dtype, const ecgmm_conv_desc* c, const void* dy, const void* w_dgrad,

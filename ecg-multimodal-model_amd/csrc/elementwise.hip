@@ -589,6 +589,150 @@ __global__ __launch_bounds__(BWD_THREADS) void bn_bwd_kernel(BnBwdParams p) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Dual BN backward: TWO BatchNorms (bn2 and the shortcut BatchNorm of a downsample block) differentiate the same masked
+// gradient dz = [mask] * dout.  One reduce pass and one apply pass serve both instead of a pair each:
+//   reduce : reads dout, the mask, y[0], y[1]; stores dz; writes a row set [grid][2][C] per BatchNorm
+//   apply  : reads dz, y[0], y[1]; stores dy[0], dy[1]; folds (or reads) each BatchNorm's bcoef
+// Grid, thread -> (row, 16-byte chunk) map, row walk, per-thread accumulation and the block's row sums are those of
+// bn_bwd_kernel, and every stored element is pack16 of the same fp32 expression: the results have the bits of the two
+// separate ecg_bn_bwd calls.  (sum dz is one accumulator: both row sets carry the same column 0.)
+// A sibling of bn_bwd_kernel, not one more flag on it: its instantiations keep their registers.
+// ------------------------------------------------------------------------------------------------
+struct BnBwdDualParams {
+  const void* dout;                 // reduce: the gradient before the mask; apply: dz
+  const void* maskref;              // reduce: nullable when mask_bits
+  const unsigned char* mask_bits;   // reduce: nullable (bf16)
+  void* dz;                         // reduce: the masked gradient, stored
+  const void* y[2];                 // raw conv outputs the two BatchNorms normalised
+  const float* coef[2];             // forward coef [4][C] each
+  const float* bcoef[2];            // apply without fold: [3][C] each
+  void* dy[2];                      // apply
+  float* partial[2];                // reduce: [grid][2][C] each
+  long M;
+  int C;
+  BnBwdFin fin[2];                  // apply; fin[b].partial != null: bcoef is folded from the row sets here
+};
+
+template <typename T, bool APPLY>
+__global__ __launch_bounds__(BWD_THREADS) void bn_bwd_dual_kernel(BnBwdDualParams p) {
+  constexpr int VEC = Elem<T>::VEC;
+  extern __shared__ float shm_dyn[];
+  float(*shm)[2 * VEC + 1] = reinterpret_cast<float(*)[2 * VEC + 1]>(shm_dyn);  // [BWD_THREADS][2*VEC+1] (reduce only)
+  const ChanSlice cs = chan_slice(p.C);   // (sliced only as the folded apply pass: host side)
+  const int cpr = cs.W / VEC, rpi = BWD_THREADS / cpr;
+  const int chunk = threadIdx.x % cpr, r0 = threadIdx.x / cpr;
+  const int c0 = cs.c_lo + chunk * VEC;   // GLOBAL channel
+  __shared__ double s_red[APPLY ? FIN_LDS_DOUBLES : 1];
+  __shared__ float s_bcoef[APPLY ? 2 * 3 * 512 : 1];
+  const T* dout = (const T*)p.dout;
+  const T* ya = (const T*)p.y[0];
+  const T* yb = (const T*)p.y[1];
+  const long rfirst = (long)blockIdx.x * rpi + r0;
+  const float* bc[2] = {p.bcoef[0] + c0, p.bcoef[1] + c0};
+  int bcs = p.C;
+  // (fold form: the first row's loads are issued before the folds, as in bn_bwd_kernel)
+  u32x4 pd = {}, pa = {}, pb = {};
+  bool pre = APPLY && p.fin[0].partial != nullptr && rfirst < p.M;
+  if (pre) {
+    pd = ld16s(dout + rfirst * p.C + c0);
+    pa = ld16s(ya + rfirst * p.C + c0);
+    pb = ld16s(yb + rfirst * p.C + c0);
+  }
+  if (APPLY && p.fin[0].partial) {
+    bn_bwd_fin_prologue<BWD_THREADS>(p.fin[0], p.coef[0], p.C, cs, s_bcoef, s_red);
+    bn_bwd_fin_prologue<BWD_THREADS>(p.fin[1], p.coef[1], p.C, cs, s_bcoef + 3 * 512, s_red);
+    bc[0] = s_bcoef + chunk * VEC;   // (LDS: the local channel)
+    bc[1] = s_bcoef + 3 * 512 + chunk * VEC;
+    bcs = cs.W;
+  }
+  float mean[2][VEC], inv[2][VEC], k1[2][VEC], k2[2][VEC], k3[2][VEC], a1[VEC], a2[2][VEC];
+#pragma unroll
+  for (int b = 0; b < 2; ++b) {
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      mean[b][j] = p.coef[b][2 * p.C + c0 + j];
+      inv[b][j] = p.coef[b][3 * p.C + c0 + j];
+      a1[j] = a2[b][j] = 0.f;
+      if (APPLY) {
+        k1[b][j] = bc[b][j];
+        k2[b][j] = bc[b][bcs + j];
+        k3[b][j] = bc[b][2 * bcs + j];
+      }
+    }
+  }
+  const T* mref = (const T*)p.maskref;
+  for (long r = rfirst; r < p.M; r += (long)gridDim.x * rpi) {
+    float d[VEC], va[VEC], vb[VEC];
+    if (pre) {
+      unpack16<T>(pd, d);
+      unpack16<T>(pa, va);
+      unpack16<T>(pb, vb);
+      pre = false;
+    } else {
+      const u32x4 qd = ld16s(dout + r * p.C + c0), qa = ld16s(ya + r * p.C + c0), qb = ld16s(yb + r * p.C + c0);
+      unpack16<T>(qd, d);
+      unpack16<T>(qa, va);
+      unpack16<T>(qb, vb);
+    }
+    if (!APPLY) {
+      if (VEC == 8 && p.mask_bits) {
+        const unsigned bits = p.mask_bits[r * (p.C / VEC) + c0 / VEC];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) d[j] = (bits >> j) & 1u ? d[j] : 0.f;
+      } else {
+        float m[VEC];
+        unpack16<T>(ld16s(mref + r * p.C + c0), m);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) d[j] = m[j] > 0.f ? d[j] : 0.f;
+      }
+      st16((T*)p.dz + r * p.C + c0, pack16<T>(d));
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        const float xa = (va[j] - mean[0][j]) * inv[0][j];
+        const float xb = (vb[j] - mean[1][j]) * inv[1][j];
+        a1[j] += d[j];
+        a2[0][j] += d[j] * xa;
+        a2[1][j] += d[j] * xb;
+      }
+    } else {
+      float oa[VEC], ob[VEC];
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        const float xa = (va[j] - mean[0][j]) * inv[0][j];
+        oa[j] = k1[0][j] * (d[j] - k2[0][j] - xa * k3[0][j]);
+      }
+      st16((T*)p.dy[0] + r * p.C + c0, pack16<T>(oa));
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        const float xb = (vb[j] - mean[1][j]) * inv[1][j];
+        ob[j] = k1[1][j] * (d[j] - k2[1][j] - xb * k3[1][j]);
+      }
+      st16((T*)p.dy[1] + r * p.C + c0, pack16<T>(ob));
+    }
+  }
+  if (!APPLY) {
+    // the block's row sums, one BatchNorm after the other through the same LDS tile, each in bn_bwd_kernel's order
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      if (b) __syncthreads();
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        shm[threadIdx.x][j] = a1[j];
+        shm[threadIdx.x][VEC + j] = a2[b][j];
+      }
+      __syncthreads();
+      for (int o = threadIdx.x; o < 2 * p.C; o += BWD_THREADS) {
+        int which = o / p.C, c = o % p.C;
+        int ck = c / VEC, j = c % VEC;
+        float s = 0.f;
+        for (int k = 0; k < rpi; ++k) s += shm[k * cpr + ck][which * VEC + j];
+        p.partial[b][(size_t)blockIdx.x * 2 * p.C + o] = s;
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __restrict__ partial, int rows, int C,
                                                                double count, const float* __restrict__ gamma,
                                                                const float* __restrict__ coef, float* dgamma,
@@ -1528,6 +1672,80 @@ int ecg_bn_bwd(int dtype, const void* dout, const void* maskref, const float* ga
     hipLaunchKernelGGL(rows_sum_kernel, dim3(ceil_div(C, 64)), dim3(1024), 0, stream, partial, grid, C, dbias, 0);
     ECG_CHECK_LAUNCH("rows_sum");
   }
+  return 0;
+}
+
+// ---- dual BN backward (bn_bwd_dual_kernel) ----
+// Run-time switch of the plans that use it (plan_resnet18.hip): on = one pass pair for bn2 and the shortcut BatchNorm of a
+// downsample block, off = the two separate ecg_bn_bwd calls.  Bit-identical results either way.
+static int g_bn_dual = 1;
+void ecg_bn_dual_set(int on) { g_bn_dual = on != 0; }
+bool ecg_bn_dual_on() { return g_bn_dual != 0; }
+
+template <typename T, bool APPLY>
+static void bn_bwd_dual_launch(const BnBwdDualParams& p, dim3 grid, hipStream_t stream) {
+  // (only the reduce pass sums rows through the dynamic LDS tile)
+  constexpr size_t lds = APPLY ? 0 : (size_t)BWD_THREADS * (2 * Elem<T>::VEC + 1) * sizeof(float);
+  static bool attr_set = false;
+  if (lds > 64 * 1024 && !attr_set) {
+    (void)hipFuncSetAttribute((const void*)bn_bwd_dual_kernel<T, APPLY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((bn_bwd_dual_kernel<T, APPLY>), grid, dim3(BWD_THREADS), lds, stream, p);
+}
+
+// dz = [mask] * dout, then both BatchNorm backwards of it: dy_a from (y_a, coef_a, gamma_a), dy_b from (y_b, coef_b,
+// gamma_b).  Mask: mask_bits (bf16) or maskref > 0, one of them required.  Equal, bit for bit, to
+//   ecg_bn_bwd(dout, maskref / mask_bits, ..., y_a, ..., dy_a, dz_out = dz) followed by ecg_bn_bwd(dz, no mask, ..., y_b, ..., dy_b).
+// gate / addc / dbias are not supported here (ECGMM_ERR_SHAPE when given).  scratch_a, scratch_b: one buffer per BatchNorm,
+// each what ecg_bn_bwd takes (ecg_bn_bwd_scratch bytes: partial rows [rows + tail][2][C] + bcoef [3][C]).
+int ecg_bn_bwd_dual(int dtype, const void* dout, const void* maskref, const unsigned char* mask_bits, const float* gate,
+                    const float* addc, const void* y_a, const float* coef_a, const float* gamma_a, float* dgamma_a,
+                    float* dbeta_a, void* dy_a, const void* y_b, const float* coef_b, const float* gamma_b, float* dgamma_b,
+                    float* dbeta_b, void* dy_b, void* dz, float* dbias, long M, int C, float* scratch_a, float* scratch_b,
+                    hipStream_t stream) {
+  if (!chunk_ok(C, dtype)) ECG_FAIL(ECGMM_ERR_SHAPE, "bn_bwd_dual: C=%d unsupported", C);
+  if (gate || addc || dbias) ECG_FAIL(ECGMM_ERR_SHAPE, "bn_bwd_dual: gate / addc / dbias are not supported");
+  if (dtype != ECGMM_BF16) mask_bits = nullptr;
+  if (!dout || !y_a || !y_b || !coef_a || !coef_b || !dy_a || !dy_b || !dz || !scratch_a || !scratch_b || M < 1)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "bn_bwd_dual: null operand");
+  if ((!mask_bits && !maskref) || maskref == y_a || maskref == y_b)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "bn_bwd_dual: needs the ReLU mask as bits (bf16) or as a tensor of its own");
+  const int grid = bn_bwd_rows(dtype, M, C);
+  const float* const gamma[2] = {gamma_a, gamma_b};
+  float* const dgamma[2] = {dgamma_a, dgamma_b};
+  float* const dbeta[2] = {dbeta_a, dbeta_b};
+  float* bcoef[2];
+  BnBwdDualParams p;
+  memset(&p, 0, sizeof(p));
+  p.dout = dout; p.maskref = mask_bits ? nullptr : maskref; p.mask_bits = mask_bits; p.dz = dz; p.M = M; p.C = C;
+  p.y[0] = y_a; p.y[1] = y_b; p.coef[0] = coef_a; p.coef[1] = coef_b;
+  for (int b = 0; b < 2; ++b) {
+    p.partial[b] = b ? scratch_b : scratch_a;
+    bcoef[b] = p.partial[b] + (size_t)(grid + ECG_TAIL_ROWS) * 2 * C;
+  }
+  DISPATCH_T(dtype, (bn_bwd_dual_launch<bf16_t, false>(p, grid, stream)), (bn_bwd_dual_launch<float, false>(p, grid, stream)),
+             "bn_bwd_dual");
+  ECG_CHECK_LAUNCH("bn_bwd_dual_reduce");
+  const bool fold = ecg_bn_fold_ok(C, grid);
+  dim3 agrid(grid);
+  for (int b = 0; b < 2; ++b) {
+    if (fold) {
+      p.fin[b].partial = p.partial[b]; p.fin[b].rows = grid; p.fin[b].count = (double)M; p.fin[b].gamma = gamma[b];
+      p.fin[b].dgamma = dgamma[b]; p.fin[b].dbeta = dbeta[b]; p.fin[b].centered = 0;
+    } else {
+      hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ceil_div(C, 64)), dim3(1024), 0, stream, (const float*)p.partial[b], grid, C,
+                         (double)M, gamma[b], p.coef[b], dgamma[b], dbeta[b], bcoef[b], 0);
+      ECG_CHECK_LAUNCH("bn_bwd_finalize");
+    }
+    p.bcoef[b] = bcoef[b];
+  }
+  if (fold) agrid = bn_fold_grid(dtype, M, C, bn_fold_slices(C), BWD_THREADS, 8);   // (ns == 1: == bn_bwd_rows)
+  p.dout = dz; p.maskref = nullptr; p.mask_bits = nullptr; p.dz = nullptr;
+  p.dy[0] = dy_a; p.dy[1] = dy_b;
+  DISPATCH_T(dtype, (bn_bwd_dual_launch<bf16_t, true>(p, agrid, stream)), (bn_bwd_dual_launch<float, true>(p, agrid, stream)),
+             "bn_bwd_dual");
+  ECG_CHECK_LAUNCH("bn_bwd_dual_apply");
   return 0;
 }
 

@@ -96,6 +96,16 @@ int ecg_bn_bwd(int dtype, const void* dout, const void* maskref, const float* ga
                int rows_per_sample, const void* y, const float* coef, const float* gamma, float* dgamma, float* dbeta,
                void* dy, void* dz_out, float* dbias, long M, int C, float* scratch, hipStream_t stream,
                const unsigned char* mask_bits = nullptr);
+// Two BatchNorm backwards of the same masked gradient dz = [mask] * dout (bn2 and the shortcut BatchNorm of a downsample
+// block) in one reduce + one apply pass; results bit-identical to ecg_bn_bwd(dout, mask, ..., y_a, ..., dy_a, dz) followed by
+// ecg_bn_bwd(dz, no mask, ..., y_b, ..., dy_b).  gate / addc / dbias must be null.  scratch_a, scratch_b: ecg_bn_bwd_scratch bytes each.
+int ecg_bn_bwd_dual(int dtype, const void* dout, const void* maskref, const unsigned char* mask_bits, const float* gate,
+                    const float* addc, const void* y_a, const float* coef_a, const float* gamma_a, float* dgamma_a,
+                    float* dbeta_a, void* dy_a, const void* y_b, const float* coef_b, const float* gamma_b, float* dgamma_b,
+                    float* dbeta_b, void* dy_b, void* dz, float* dbias, long M, int C, float* scratch_a, float* scratch_b,
+                    hipStream_t stream);
+void ecg_bn_dual_set(int on);   // plans: the dual form where it applies (default on) / the separate calls
+bool ecg_bn_dual_on();
 int ecg_bn_bwd_tail(int dtype, const void* dout, const void* maskref, const void* y, const float* coef,
                     const float* gamma, float* dgamma, float* dbeta, void* dy, const float* partial, int rows, long M,
                     int C, float* scratch, hipStream_t stream, const float* gate = nullptr, const float* addc = nullptr,

@@ -90,6 +90,8 @@ struct BwdWs {
   size_t bytes;
 };
 
+constexpr size_t RED_ROWS_FLOATS = (size_t)512 * 2 * 512;   // red1, red2: up to 512 rows of [2][512 channels]
+
 void layout_bwd(const Net18& r, void* base, BwdWs& w, WsTable* views = nullptr) {
   Arena a(base, views);
   const size_t es = dtype_size(r.d.dtype);
@@ -126,8 +128,8 @@ void layout_bwd(const Net18& r, void* base, BwdWs& w, WsTable* views = nullptr) 
     }
   }
   w.bn_scratch = (float*)a.take_bytes(bn);
-  w.red1 = a.take<float>((size_t)512 * 2 * 512);
-  w.red2 = a.take<float>((size_t)512 * 2 * 512);
+  w.red1 = a.take<float>(RED_ROWS_FLOATS);
+  w.red2 = a.take<float>(RED_ROWS_FLOATS);
   w.wg_ws = a.take_bytes(wg);
   w.wg_bytes = wg;
   w.stem_bytes = recompute ? ecg_stem_pool_bwd_workspace(N, 3, r.d.H, r.d.W) : ecg_stem_wgrad_workspace(N, 3, r.d.H, r.d.W, 7);
@@ -413,7 +415,21 @@ static int r18_backward(const ecgmm_resnet18_desc* d, const float* image, const 
       // out = relu(bn2(y2) + identity)
       main_wait(s, g_side.done2[0][pp]);  // the wgrad2 of two blocks ago has finished reading this dy buffer
       const void* dzp = q.dz;
-      if (fused2) {
+      // Downsample block: bn2 and the shortcut BatchNorm differentiate the same dz -- one reduce + one apply pass for both
+      // (ecg_bn_bwd_dual: dz read once instead of three times, two launches instead of four; same bits).  It writes dyd
+      // here already, so the wait for that buffer's reader of two blocks ago moves up with it.  The downsample weight
+      // gradient still forks where it did, behind conv1's: an earlier fork would only add slack to the side stream.
+      // The shortcut BatchNorm's rows and coefficients go to red2: the rows of a fused bn2 reduction are not in use here
+      // (!fused2; a downsample block's own conv1 dgrad fuses none), and the workspace keeps its size.
+      const bool dual = k.down && train && !fused2 && ecg_bn_dual_on() &&
+                        ecg_bn_bwd_scratch(dt, M, k.cout) <= RED_ROWS_FLOATS * sizeof(float);
+      if (dual) {
+        main_wait(s, g_side.done2[2][pp]);
+        ECG_TRY(ecg_bn_bwd_dual(dt, dcur, b.out, relu_bits_on() ? b.bits : nullptr, nullptr, nullptr, b.y2, b.coef2,
+                                P(params, k.p_bn2), G(grads, k.p_bn2), G(grads, k.p_bn2 + 1), dyb, b.yd, b.coefd,
+                                P(params, k.p_dbn), G(grads, k.p_dbn), G(grads, k.p_dbn + 1), dydb, q.dz, nullptr, M, k.cout,
+                                q.bn_scratch, q.red2, s));
+      } else if (fused2) {
         dzp = dcur;
         ECG_TRY(ecg_bn_bwd_tail(dt, dcur, nullptr, b.y2, b.coef2, P(params, k.p_bn2), G(grads, k.p_bn2),
                                 G(grads, k.p_bn2 + 1), dyb, q.red2, fused2_rows, M, k.cout, q.bn_scratch, s));
@@ -447,9 +463,11 @@ static int r18_backward(const ecgmm_resnet18_desc* d, const float* image, const 
       }
       if (k.down) {
         ConvGeom gd = k.down_geom(N);
-        main_wait(s, g_side.done2[2][pp]);
-        ECG_TRY(bn_bwd_mode(r.bn, dzp, nullptr, nullptr, nullptr, 1, b.yd, b.coefd, P(params, k.p_dbn), G(grads, k.p_dbn),
-                            G(grads, k.p_dbn + 1), dydb, nullptr, nullptr, M, k.cout, q.bn_scratch, s));
+        if (!dual) {
+          main_wait(s, g_side.done2[2][pp]);
+          ECG_TRY(bn_bwd_mode(r.bn, dzp, nullptr, nullptr, nullptr, 1, b.yd, b.coefd, P(params, k.p_dbn), G(grads, k.p_dbn),
+                              G(grads, k.p_dbn + 1), dydb, nullptr, nullptr, M, k.cout, q.bn_scratch, s));
+        }
         if (G(grads, k.p_dconv)) {
           if (side) side_fork(s);
           ECG_TRY(ecg_conv_wgrad(dt, gd, in, dydb, G(grads, k.p_dconv), 0, q.wg_ws, q.wg_bytes, ws));

@@ -132,6 +132,8 @@ SIGNATURES = {
     "ecgmm_bn_fold_slice": (i32, [i32]),
     "ecgmm_bn_act_from_rows_bits": (i32, [i32, vp, vp, i32, f64, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, i32, i32, vp, vp, i64, i32, vp]),
     "ecgmm_bn_bwd_bits": (i32, [i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp]),
+    "ecgmm_bn_bwd_dual": (i32, [i32] + [vp] * 19 + [i64, i32, vp, vp, vp]),
+    "ecgmm_bn_dual": (i32, [i32]),
     "ecgmm_tl_enable": (i32, [i32]),
     "ecgmm_tl_mark": (i32, [i32, vp]),
     "ecgmm_tl_collect": (i32, [i32, vp, vp]),
@@ -257,7 +259,9 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  # LIME of the fusion head (ecgmm/lime_tabular.py, csrc/lime.hip)
                  "ecgmm_lime_perturb", "ecgmm_lime_ridge_workspace", "ecgmm_lime_ridge", "ecgmm_lime_prob",
                  # SHAP of the fusion head (ecgmm/shap_explainers.py, csrc/shap.hip)
-                 "ecgmm_shap_mlp_workspace", "ecgmm_shap_gradient", "ecgmm_shap_deep")
+                 "ecgmm_shap_mlp_workspace", "ecgmm_shap_gradient", "ecgmm_shap_deep",
+                 # the dual BatchNorm backward of the downsample blocks (csrc/elementwise.hip)
+                 "ecgmm_bn_bwd_dual", "ecgmm_bn_dual")
 
 _lib = None
 

@@ -415,6 +415,20 @@ int ecgmm_bn_act_from_rows_bits(int dtype, const void* y, const float* partial, 
 int ecgmm_bn_bwd_bits(int dtype, const void* dout, const uint8_t* mask_bits, const float* gate, const float* addc,
                       int rows_per_sample, const void* y, const float* coef, const float* gamma, float* dgamma,
                       float* dbeta, void* dy, void* dz_out, float* dbias, int64_t M, int C, void* scratch, void* stream);
+/* Two BatchNorm backwards of ONE masked gradient dz = [mask] * dout in one reduce + one apply pass -- bn2 (y_a, ...) and the
+ * shortcut BatchNorm (y_b, ...) of a ResNet18 downsample block: dz is stored once and read once, two launches instead of
+ * four.  Mask: mask_bits (bf16) or maskref > 0 (a tensor of its own, not y_a / y_b); one of them is required.  Bit-identical to
+ *   ecgmm_bn_bwd(_bits)(dout, mask, ..., y_a, ..., dy_a, dz_out = dz)  followed by  ecgmm_bn_bwd(dz, no mask, ..., y_b, ..., dy_b).
+ * gate, addc and dbias are not supported: ECGMM_ERR_SHAPE unless null.  scratch_a, scratch_b: one buffer per BatchNorm of
+ * ecgmm_bn_bwd_scratch(dtype, M, C) bytes each (partial rows as ecgmm_bn_bwd leaves them in its scratch). */
+int ecgmm_bn_bwd_dual(int dtype, const void* dout, const void* maskref, const uint8_t* mask_bits, const float* gate,
+                      const float* addc, const void* y_a, const float* coef_a, const float* gamma_a, float* dgamma_a,
+                      float* dbeta_a, void* dy_a, const void* y_b, const float* coef_b, const float* gamma_b,
+                      float* dgamma_b, float* dbeta_b, void* dy_b, void* dz, float* dbias, int64_t M, int C, void* scratch_a,
+                      void* scratch_b, void* stream);
+/* ResNet18 plan, training backward of the downsample blocks: 1 = that dual pass pair (default), 0 = the two separate
+ * BatchNorm backwards.  Run time only (no environment variable).  Bit-identical results. */
+int ecgmm_bn_dual(int on);
 /* ResNet18 plan: run the stem by recompute (ecgmm_stem_stats_only / stem_pool_fwd / stem_pool_bwd; bf16 only): 1 = on,
  * 0 = the two-pass route that keeps the full-resolution conv output (default: 0.2 ms per step faster at batch 256 although
  * it moves 1.6 GB more -- the recomputing kernels are instruction-bound).  Start-up value: ECGMM_STEM_RECOMPUTE.

@@ -2,7 +2,8 @@
 a residual, full BatchNorm backward (reduce + finalize + apply) and the apply-from-rows form.  Bytes = the tensors each pass must
 move once; GB/s against the 6.29 TB/s a float4 copy reaches on this chip (MI355X_MICROARCH.md).
 The passes that fold the finalize (bn_act from rows, both backward forms) are timed with the channel-sliced launch off and on
-(ecgmm_bn_fold_slice) where it applies (C >= 256), alternating, in the same process."""
+(ecgmm_bn_fold_slice) where it applies (C >= 256), alternating, in the same process.  At the output shapes of the three
+downsample blocks: bn2's + the shortcut BatchNorm's backward as separate calls against ecgmm_bn_bwd_dual, alternating."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -56,3 +57,22 @@ for name, HW, Cn in (("l1", 56 * 56, 64), ("l2", 28 * 28, 128), ("l3", 14 * 14, 
             lib.ecgmm_bn_fold_slice(sl)
             show(label + (" [slice %d]" % sl if Cn >= 256 else ""), timeit(fn), tensors)
     lib.ecgmm_bn_fold_slice(1)
+    if Cn < 128:
+        continue
+    # downsample blocks (their output shapes): bn2's backward with the bit mask and dz_out, then the shortcut BatchNorm's backward of
+    # that dz -- two reduce + two apply launches, 11 tensor passes -- against ecgmm_bn_bwd_dual, one of each, 9 passes; alternating
+    y2s, dzs, dyds = [mk() for _ in range(K)], [torch.empty_like(os_[0]) for _ in range(K)], [torch.empty_like(os_[0]) for _ in range(K)]
+    mbits = torch.randint(0, 256, (n // 8,), dtype=torch.uint8, device="cuda:0")
+    coefd, gammad = torch.rand(4 * Cn, device="cuda:0") + 0.5, torch.rand(Cn, device="cuda:0") + 0.5
+    dgd, dbd = torch.empty(Cn, device="cuda:0"), torch.empty(Cn, device="cuda:0")
+    scratch_d = torch.empty_like(scratch)
+    def separate():
+        i = nxt()
+        rc = lib.ecgmm_bn_bwd_bits(L.BF16, ptr(rs[i]), ptr(mbits), None, None, 1, ptr(ys[i]), ptr(coef), ptr(gamma), ptr(dg), ptr(db), ptr(os_[i]), ptr(dzs[i]), None, M, Cn, ptr(scratch), stream())
+        return rc or lib.ecgmm_bn_bwd(L.BF16, ptr(dzs[i]), None, None, None, 1, ptr(y2s[i]), ptr(coefd), ptr(gammad), ptr(dgd), ptr(dbd), ptr(dyds[i]), None, None, M, Cn, ptr(scratch_d), stream())
+    def dual():
+        i = nxt()
+        return lib.ecgmm_bn_bwd_dual(L.BF16, ptr(rs[i]), None, ptr(mbits), None, None, ptr(ys[i]), ptr(coef), ptr(gamma), ptr(dg), ptr(db), ptr(os_[i]), ptr(y2s[i]), ptr(coefd), ptr(gammad), ptr(dgd), ptr(dbd), ptr(dyds[i]), ptr(dzs[i]), None, M, Cn, ptr(scratch), ptr(scratch_d), stream())
+    for _ in range(2):
+        show("bn2 + shortcut bn_bwd, separate", timeit(separate), 11)
+        show("bn2 + shortcut bn_bwd, dual", timeit(dual), 9)
