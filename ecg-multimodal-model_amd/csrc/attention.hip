@@ -1,0 +1,694 @@
+// Multi-head self-attention of nn.TransformerEncoderLayer (reference: train_physionet.py:219-220, 236;
+// multimodal_paper_modal_balance.py:127-194), forward and backward, fp32 on v_mfma_f32_16x16x4_f32, and the model's front
+// (train_physionet.py:216-217, 233-235): Conv1d(input_dim, d_model, 3, padding=1) + bias + positional embedding.
+//
+// Operands.  qkv [rows][3E] is the packed projection as linear(x, in_proj_weight, in_proj_bias) leaves it, E = heads * d;
+// row(s, n) = s * N + n (batch_first = 0) or n * S + s (batch_first = 1).  Everything is addressed by stride: no transposed
+// or head-split copy exists.  out / dout [rows][E] with the heads concatenated, lse [N][heads][S], dqkv [rows][3E].
+//
+// Tile structure.  One WAVE is one unit of work and owns a 16-row tile; a workgroup is four independent waves (no LDS, no
+// barrier).  All three kernels keep the scores TRANSPOSED with respect to the rows the wave owns, so that the MFMA result
+// registers are at once the operand of the next MFMA and nothing is transposed in LDS or by lane shuffles:
+//   forward / dQ (the wave owns 16 queries, loops over 16-key tiles):
+//     acc[r] = S[key 4 g + r][query i] = sum_c K[key][c] Q[query][c]     A = K rows, B = Q rows   (i = lane & 15, g = lane >> 4)
+//     a lane holds four keys of ONE query: the row statistics (max, sum, lse, D) are one register per lane, the reduction
+//     over a score row is 3 in-lane operations + v_permlane16_swap + v_permlane32_swap (rows 0..3 of the wave).
+//     O^T[c][query] += V[key 4 g + r][c] * P[key 4 g + r][query]: MFMA step r takes acc[r] as its B operand as it stands --
+//     the contraction index of an MFMA is a free permutation, here "k-slot g of step r is key 4 g + r".
+//   dK / dV (the wave owns 16 keys, loops over 16-query tiles): the same with the roles exchanged,
+//     acc[r] = S[query 4 g + r][key i], dV^T[c][key] += dO[query][c] Pd[query][key], dK^T[c][key] += Q[query][c] dS[query][key].
+//   The contraction over the head dimension uses the permutation "k-slot g of step s is column g * d/4 + s", so a lane loads
+//   its d/4 columns of a row as one or two float4.
+// Online softmax over the key tiles in the forward; the backward recomputes P = exp(scale * S - lse) from the stored lse and
+// D[query] = dO . O (mha_rowdot_kernel, the only workspace: one float per (n, head, query)).  No S x S tensor exists.
+// Every reduction runs in a fixed order and every output is written by exactly one lane: no atomics, identical bits per call.
+//
+// S <= 8 (the reference as written attends across its batch of 8): floor(16 / S) (n, head) pairs share one wave.  Slot i of
+// the 16 query (key) slots is pair i / S, position i % S; a score between slots of different pairs is masked like a key past
+// the end.  Each pair's probabilities, outputs and gradients are the same arithmetic as alone in a tile.
+//
+// Dropout on the probabilities: Philox4x32-10 (the generator of head.hip / lime.hip), one block per four consecutive keys,
+//   counter = (offset low, offset high, n * heads + head, 0xC0000000 | query * ceil(S / 4) + key / 4), word key % 4,
+//   keep iff (word >> 8) * 2^-24 >= p: a function of (seed, offset, n, head, query, key) alone.  c3 is none of 0 (dropout),
+//   0x4....... (LIME), 0x8....... (augmentation noise), 0xFFFFFFFD..F (row decisions).  Needs S <= 32768.
+#include "ops.h"
+
+#include <math.h>
+
+namespace {
+
+struct MhaGeo {
+  int S, N, heads, E, P, tiles, G, SB;   // P = N * heads pairs, tiles = ceil(S / 16), G pairs per wave (0: one tile of one pair)
+  long long rs, rn;                      // row(s, n) = s * rs + n * rn
+  float scale, p_drop, inv_keep;
+  unsigned long long seed, offset;
+};
+
+// One of the 16 row slots of a tile.  `row`, `h` and `si` always address a real row (an empty slot is clamped onto the last
+// position / pair), so loads need no guard: what an empty slot reads is finite and is multiplied by a probability or a
+// score gradient that the mask has set to zero, or belongs to a row that is never stored.
+struct Slot {
+  int pair, s, h;      // pair = n * heads + h
+  long long row, si;   // row(s, n); pair * S + s (lse, D)
+  bool ok;
+};
+
+// the (n, head) of a pair: two integer divisions, kept out of the tile loops (Unit below)
+__device__ __forceinline__ void mha_split(const MhaGeo& g, int pair, int& n, int& h) {
+  n = pair / g.heads;
+  h = pair - n * g.heads;
+}
+
+// what a wave owns: one 16-row tile of one pair (n, h), or -- packed, g.G != 0 -- the pairs u * G .. u * G + G - 1
+struct Unit {
+  int u, tile, n, h;
+};
+
+// PK: the packed form (g.G != 0), a template parameter so that the tile loops of the long sequences carry none of its code
+template <bool PK>
+__device__ __forceinline__ Unit mha_unit(const MhaGeo& g, long long unit) {
+  Unit o;
+  if (PK) { o.u = (int)unit; o.tile = 0; o.n = o.h = 0; }
+  else {
+    o.u = (int)(unit / g.tiles);
+    o.tile = (int)(unit - (long long)o.u * g.tiles);
+    mha_split(g, o.u, o.n, o.h);
+  }
+  return o;
+}
+
+// slot idx (0..15) of tile `tile` of the unit
+template <bool PK>
+__device__ __forceinline__ Slot mha_slot(const MhaGeo& g, const Unit& w, int tile, int idx) {
+  Slot o;
+  int n, pc, sc;
+  if (PK) {
+    const int k = idx / g.S;
+    o.pair = w.u * g.G + k;
+    o.s = idx - k * g.S;
+    o.ok = k < g.G && o.pair < g.P;
+    pc = o.pair < g.P ? o.pair : g.P - 1;
+    sc = o.s;
+    mha_split(g, pc, n, o.h);
+  } else {
+    o.pair = pc = w.u;
+    o.s = tile * 16 + idx;
+    o.ok = o.s < g.S;
+    sc = o.ok ? o.s : g.S - 1;
+    n = w.n;
+    o.h = w.h;
+  }
+  o.row = (long long)sc * g.rs + (long long)n * g.rn;
+  o.si = (long long)pc * g.S + sc;
+  return o;
+}
+
+// Philox4x32-10 exactly as in lime.hip
+__device__ __forceinline__ void philox4(unsigned long long seed, unsigned c0, unsigned c1, unsigned c2, unsigned c3,
+                                        unsigned* r) {
+  const unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const unsigned hi0 = __umulhi(M0, c0), lo0 = M0 * c0;
+    const unsigned hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
+    const unsigned n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+}
+
+__device__ __forceinline__ void mha_block(const MhaGeo& g, int pair, int i, int jb, unsigned* r) {
+  philox4(g.seed, (unsigned)g.offset, (unsigned)(g.offset >> 32), (unsigned)pair,
+          0xC0000000u | (unsigned)(i * g.SB + jb), r);
+}
+
+__device__ __forceinline__ bool mha_keep_word(const MhaGeo& g, unsigned w) {
+  return (float)(w >> 8) * (1.f / 16777216.f) >= g.p_drop;
+}
+
+__device__ __forceinline__ bool mha_keep(const MhaGeo& g, int pair, int i, int j) {
+  unsigned r[4];
+  mha_block(g, pair, i, j >> 2, r);
+  return mha_keep_word(g, r[j & 3]);
+}
+
+// all-reduce over the four 16-lane rows of the wave (lanes i, i + 16, i + 32, i + 48); both lanes of an exchange evaluate
+// the same commutative operation on the same two values, so every lane ends with the same bits
+__device__ __forceinline__ float rows_max(float v) {
+  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  const float w = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
+  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(w), __float_as_uint(w), false, false);
+  return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
+}
+
+__device__ __forceinline__ float rows_sum(float v) {
+  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  const float w = __uint_as_float(a[0]) + __uint_as_float(a[1]);
+  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(w), __float_as_uint(w), false, false);
+  return __uint_as_float(b[0]) + __uint_as_float(b[1]);
+}
+
+// the lane's HD / 4 columns of a row
+template <int CW>
+__device__ __forceinline__ void load_cols(const float* p, float* v) {
+#pragma unroll
+  for (int q = 0; q < CW / 4; ++q) {
+    const float4 t = *reinterpret_cast<const float4*>(p + 4 * q);
+    v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// forward
+// ------------------------------------------------------------------------------------------------
+template <int HD, bool PK>
+__global__ __launch_bounds__(256) void mha_fwd_kernel(MhaGeo g, const float* __restrict__ qkv, float* __restrict__ out,
+                                                      float* __restrict__ lse, long long units) {
+  constexpr int CW = HD / 4, NT = HD / 16;
+  const long long unit = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (unit >= units) return;   // wave-uniform; the kernel has no barrier
+  const int lane = threadIdx.x & 63, i16 = lane & 15, g4 = lane >> 4;
+  const Unit u = mha_unit<PK>(g, unit);
+  const int qtile = u.tile;
+  const int E3 = 3 * g.E;
+  const Slot q = mha_slot<PK>(g, u, qtile, i16);
+  const int hq = q.h;
+  float qv[CW];
+  load_cols<CW>(qkv + q.row * E3 + hq * HD + g4 * CW, qv);
+  f32x4 o[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) o[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.f;
+  const int ktiles = PK ? 1 : g.tiles;
+  for (int kt = 0; kt < ktiles; ++kt) {
+    const Slot ka = mha_slot<PK>(g, u, kt, i16);
+    float kv[CW];
+    load_cols<CW>(qkv + ka.row * E3 + g.E + ka.h * HD + g4 * CW, kv);
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < CW; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kv[s], qv[s], acc, 0, 0, 0);
+    Slot kr[4];
+    float sc[4];
+    float mt = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      kr[r] = mha_slot<PK>(g, u, kt, g4 * 4 + r);
+      const bool valid = kr[r].ok && q.ok && (!PK || kr[r].pair == q.pair);
+      sc[r] = valid ? acc[r] * g.scale : -INFINITY;
+      mt = fmaxf(mt, sc[r]);
+    }
+    mt = rows_max(mt);
+    const float mn = fmaxf(m, mt), ms = mn == -INFINITY ? 0.f : mn;
+    const float alpha = expf(m - ms);
+    float p[4], ls = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      p[r] = expf(sc[r] - ms);
+      ls += p[r];
+    }
+    ls = rows_sum(ls);
+    l = l * alpha + ls;
+    m = mn;
+    if (g.p_drop > 0.f) {
+      int prev = -1;
+      unsigned w[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int jb = kr[r].s >> 2;
+        if (jb != prev || r == 0) { mha_block(g, q.pair, q.s, jb, w); prev = jb; }
+        p[r] = mha_keep_word(g, w[kr[r].s & 3]) ? p[r] * g.inv_keep : 0.f;
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      o[t] *= alpha;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float v = qkv[kr[r].row * E3 + 2 * g.E + kr[r].h * HD + t * 16 + i16];
+        o[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(v, p[r], o[t], 0, 0, 0);
+      }
+    }
+  }
+  if (!q.ok) return;
+  float* dst = out + q.row * g.E + hq * HD + g4 * 4;
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+    *reinterpret_cast<float4*>(dst + t * 16) = make_float4(o[t][0] / l, o[t][1] / l, o[t][2] / l, o[t][3] / l);
+  if (g4 == 0) lse[q.si] = m + logf(l);
+}
+
+// ------------------------------------------------------------------------------------------------
+// backward
+// ------------------------------------------------------------------------------------------------
+// D[pair][s] = dout[row] . out[row] over the head's columns, one thread per (pair, s), a fixed serial order
+template <int HD>
+__global__ __launch_bounds__(256) void mha_rowdot_kernel(MhaGeo g, const float* __restrict__ out,
+                                                         const float* __restrict__ dout, float* __restrict__ D) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long long)g.P * g.S) return;
+  const int pair = (int)(e / g.S), s = (int)(e - (long long)pair * g.S);
+  int n, h;
+  mha_split(g, pair, n, h);
+  const long long off = ((long long)s * g.rs + (long long)n * g.rn) * g.E + h * HD;
+  float acc = 0.f;
+#pragma unroll
+  for (int c = 0; c < HD; c += 4) {
+    const float4 a = *reinterpret_cast<const float4*>(dout + off + c), b = *reinterpret_cast<const float4*>(out + off + c);
+    acc += a.x * b.x;
+    acc += a.y * b.y;
+    acc += a.z * b.z;
+    acc += a.w * b.w;
+  }
+  D[e] = acc;
+}
+
+// the wave owns 16 keys: dK and dV
+template <int HD, bool PK>
+__global__ __launch_bounds__(256) void mha_bwd_kv_kernel(MhaGeo g, const float* __restrict__ qkv,
+                                                         const float* __restrict__ lse, const float* __restrict__ D,
+                                                         const float* __restrict__ dout, float* __restrict__ dqkv,
+                                                         long long units) {
+  constexpr int CW = HD / 4, NT = HD / 16;
+  const long long unit = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (unit >= units) return;
+  const int lane = threadIdx.x & 63, i16 = lane & 15, g4 = lane >> 4;
+  const Unit u = mha_unit<PK>(g, unit);
+  const int ktile = u.tile;
+  const int E3 = 3 * g.E;
+  const Slot k = mha_slot<PK>(g, u, ktile, i16);
+  const int hk = k.h;
+  float kv[CW], vv[CW];
+  load_cols<CW>(qkv + k.row * E3 + g.E + hk * HD + g4 * CW, kv);
+  load_cols<CW>(qkv + k.row * E3 + 2 * g.E + hk * HD + g4 * CW, vv);
+  f32x4 dk[NT], dv[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) dk[t] = dv[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int qtiles = PK ? 1 : g.tiles;
+  for (int qt = 0; qt < qtiles; ++qt) {
+    const Slot qa = mha_slot<PK>(g, u, qt, i16);
+    const int ha = qa.h;
+    float qv[CW], dov[CW];
+    load_cols<CW>(qkv + qa.row * E3 + ha * HD + g4 * CW, qv);
+    load_cols<CW>(dout + qa.row * g.E + ha * HD + g4 * CW, dov);
+    f32x4 as = f32x4{0.f, 0.f, 0.f, 0.f}, ap = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < CW; ++s) {
+      as = __builtin_amdgcn_mfma_f32_16x16x4f32(qv[s], kv[s], as, 0, 0, 0);
+      ap = __builtin_amdgcn_mfma_f32_16x16x4f32(dov[s], vv[s], ap, 0, 0, 0);
+    }
+    Slot qr[4];
+    float pd[4], ds[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      qr[r] = mha_slot<PK>(g, u, qt, g4 * 4 + r);
+      const bool valid = qr[r].ok && k.ok && (!PK || qr[r].pair == k.pair);
+      const float lr = lse[qr[r].si], dr = D[qr[r].si];
+      const float p = valid ? expf(as[r] * g.scale - lr) : 0.f;
+      float dp = ap[r];
+      pd[r] = p;
+      if (g.p_drop > 0.f) {
+        const bool keep = valid && mha_keep(g, k.pair, qr[r].s, k.s);
+        pd[r] = keep ? p * g.inv_keep : 0.f;
+        dp = keep ? dp * g.inv_keep : 0.f;
+      }
+      ds[r] = valid ? p * (dp - dr) : 0.f;
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const long long row = qr[r].row;
+        const int col = qr[r].h * HD + t * 16 + i16;
+        const float a_do = dout[row * g.E + col];
+        const float a_q = qkv[row * E3 + col];
+        dv[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_do, pd[r], dv[t], 0, 0, 0);
+        dk[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_q, ds[r], dk[t], 0, 0, 0);
+      }
+    }
+  }
+  if (!k.ok) return;
+  float* dst = dqkv + k.row * E3 + hk * HD + g4 * 4;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    *reinterpret_cast<float4*>(dst + g.E + t * 16) =
+        make_float4(dk[t][0] * g.scale, dk[t][1] * g.scale, dk[t][2] * g.scale, dk[t][3] * g.scale);
+    *reinterpret_cast<float4*>(dst + 2 * g.E + t * 16) = make_float4(dv[t][0], dv[t][1], dv[t][2], dv[t][3]);
+  }
+}
+
+// the wave owns 16 queries: dQ
+template <int HD, bool PK>
+__global__ __launch_bounds__(256) void mha_bwd_q_kernel(MhaGeo g, const float* __restrict__ qkv,
+                                                        const float* __restrict__ lse, const float* __restrict__ D,
+                                                        const float* __restrict__ dout, float* __restrict__ dqkv,
+                                                        long long units) {
+  constexpr int CW = HD / 4, NT = HD / 16;
+  const long long unit = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (unit >= units) return;
+  const int lane = threadIdx.x & 63, i16 = lane & 15, g4 = lane >> 4;
+  const Unit u = mha_unit<PK>(g, unit);
+  const int qtile = u.tile;
+  const int E3 = 3 * g.E;
+  const Slot q = mha_slot<PK>(g, u, qtile, i16);
+  const int hq = q.h;
+  float qv[CW], dov[CW];
+  load_cols<CW>(qkv + q.row * E3 + hq * HD + g4 * CW, qv);
+  load_cols<CW>(dout + q.row * g.E + hq * HD + g4 * CW, dov);
+  const float lq = lse[q.si], dq_row = D[q.si];
+  f32x4 dq[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) dq[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int ktiles = PK ? 1 : g.tiles;
+  for (int kt = 0; kt < ktiles; ++kt) {
+    const Slot ka = mha_slot<PK>(g, u, kt, i16);
+    const int ha = ka.h;
+    float kv[CW], vv[CW];
+    load_cols<CW>(qkv + ka.row * E3 + g.E + ha * HD + g4 * CW, kv);
+    load_cols<CW>(qkv + ka.row * E3 + 2 * g.E + ha * HD + g4 * CW, vv);
+    f32x4 as = f32x4{0.f, 0.f, 0.f, 0.f}, ap = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < CW; ++s) {
+      as = __builtin_amdgcn_mfma_f32_16x16x4f32(kv[s], qv[s], as, 0, 0, 0);
+      ap = __builtin_amdgcn_mfma_f32_16x16x4f32(vv[s], dov[s], ap, 0, 0, 0);
+    }
+    Slot kr[4];
+    float ds[4];
+    int prev = -1;
+    unsigned w[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      kr[r] = mha_slot<PK>(g, u, kt, g4 * 4 + r);
+      const bool valid = kr[r].ok && q.ok && (!PK || kr[r].pair == q.pair);
+      const float p = valid ? expf(as[r] * g.scale - lq) : 0.f;
+      float dp = ap[r];
+      if (g.p_drop > 0.f) {
+        const int jb = kr[r].s >> 2;
+        if (jb != prev || r == 0) { mha_block(g, q.pair, q.s, jb, w); prev = jb; }
+        dp = mha_keep_word(g, w[kr[r].s & 3]) ? dp * g.inv_keep : 0.f;
+      }
+      ds[r] = valid ? p * (dp - dq_row) : 0.f;
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float a_k = qkv[kr[r].row * E3 + g.E + kr[r].h * HD + t * 16 + i16];
+        dq[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_k, ds[r], dq[t], 0, 0, 0);
+      }
+    }
+  }
+  if (!q.ok) return;
+  float* dst = dqkv + q.row * E3 + hq * HD + g4 * 4;
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+    *reinterpret_cast<float4*>(dst + t * 16) =
+        make_float4(dq[t][0] * g.scale, dq[t][1] * g.scale, dq[t][2] * g.scale, dq[t][3] * g.scale);
+}
+
+// mask [N][heads][S][S] bytes: one thread per (pair, query, block of four keys)
+__global__ __launch_bounds__(256) void mha_keep_mask_kernel(MhaGeo g, unsigned char* __restrict__ mask) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long per = (long long)g.S * g.SB;
+  if (e >= (long long)g.P * per) return;
+  const int pair = (int)(e / per);
+  const long long rem = e - (long long)pair * per;
+  const int i = (int)(rem / g.SB), jb = (int)(rem - (long long)i * g.SB);
+  unsigned r[4];
+  mha_block(g, pair, i, jb, r);
+  unsigned char* dst = mask + ((long long)pair * g.S + i) * g.S;
+#pragma unroll
+  for (int w = 0; w < 4; ++w)
+    if (4 * jb + w < g.S) dst[4 * jb + w] = mha_keep_word(g, r[w]) ? 1 : 0;
+}
+
+// 0 when the descriptor is accepted, else the message is set
+static int mha_geo(const ecgmm_mha_desc* d, const char* what, MhaGeo* out) {
+  if (!d) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: null descriptor", what);
+  if (d->S < 1 || d->N < 1 || d->heads < 1 || (d->head_dim != 16 && d->head_dim != 32) ||
+      (d->batch_first != 0 && d->batch_first != 1) || !(d->p_drop >= 0.f && d->p_drop < 1.f))
+    ECG_FAIL(ECGMM_ERR_SHAPE,
+             "%s: need S, N, heads >= 1, head_dim 16 or 32, batch_first 0 or 1, 0 <= p_drop < 1 (S=%d N=%d heads=%d "
+             "head_dim=%d batch_first=%d p_drop=%g)", what, d->S, d->N, d->heads, d->head_dim, d->batch_first, (double)d->p_drop);
+  const long long P = (long long)d->N * d->heads, E = (long long)d->heads * d->head_dim, tiles = (d->S + 15) / 16;
+  if (P > 0x7fffffffLL || E > (1 << 20) || P * tiles > 0x7fffffffLL * 4 || P * d->S > 0x7fffffffLL * 256)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "%s: N * heads * ceil(S / 16) beyond the launch grid (S=%d N=%d heads=%d)", what, d->S, d->N,
+             d->heads);
+  if (d->p_drop > 0.f && d->S > 32768)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "%s: dropout needs S <= 32768 (the Philox counter), S=%d", what, d->S);
+  MhaGeo g;
+  memset(&g, 0, sizeof(g));
+  g.S = d->S; g.N = d->N; g.heads = d->heads; g.E = (int)E; g.P = (int)P; g.tiles = (int)tiles;
+  g.G = d->S <= 8 ? 16 / d->S : 0;
+  g.SB = (d->S + 3) / 4;
+  g.rs = d->batch_first ? 1 : d->N;
+  g.rn = d->batch_first ? d->S : 1;
+  g.scale = 1.f / sqrtf((float)d->head_dim);
+  g.p_drop = d->p_drop;
+  g.inv_keep = 1.f / (1.f - d->p_drop);
+  *out = g;
+  return 0;
+}
+
+static long long mha_units(const MhaGeo& g) {
+  return g.G ? ((long long)g.P + g.G - 1) / g.G : (long long)g.P * g.tiles;
+}
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// ------------------------------------------------------------------------------------------------
+// embedding: y[b][l][c] = bias[c] + sum_{ci, k} w[c][ci][k] x[b][ci][l + k - 1] + pos[l][c]
+// ------------------------------------------------------------------------------------------------
+constexpr int EMB_MAX_CIN = 12;
+constexpr int EMB_ROWS = 64;   // rows of (b, l) per partial sum of the weight gradient
+
+__global__ __launch_bounds__(256) void embed1d_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                          const float* __restrict__ bias, const float* __restrict__ pos,
+                                                          float* __restrict__ y, int B, int Cin, int L, int Dm) {
+  const long long total = (long long)B * L * Dm;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+    const int c = (int)(e % Dm);
+    const long long row = e / Dm;
+    const int l = (int)(row % L), b = (int)(row / L);
+    float acc = bias[c];
+    for (int ci = 0; ci < Cin; ++ci) {
+      const float* xr = x + ((long long)b * Cin + ci) * L;
+      const float* wr = w + ((long long)c * Cin + ci) * 3;
+      if (l > 0) acc += wr[0] * xr[l - 1];
+      acc += wr[1] * xr[l];
+      if (l + 1 < L) acc += wr[2] * xr[l + 1];
+    }
+    y[e] = acc + pos[(long long)l * Dm + c];
+  }
+}
+
+// grid (chunks, ceil(Dm / 64)), one wave: lane = channel, EMB_ROWS rows in order -> partial[chunk][3 Cin + 1][Dm]
+__global__ __launch_bounds__(64) void embed1d_wgrad_rows_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                                float* __restrict__ partial, int B, int Cin, int L, int Dm) {
+  const int c = blockIdx.y * 64 + threadIdx.x;
+  const long long rows = (long long)B * L, r0 = (long long)blockIdx.x * EMB_ROWS;
+  float acc[3 * EMB_MAX_CIN], accb = 0.f;
+#pragma unroll
+  for (int j = 0; j < 3 * EMB_MAX_CIN; ++j) acc[j] = 0.f;
+  for (int q = 0; q < EMB_ROWS; ++q) {
+    const long long row = r0 + q;
+    if (row >= rows) break;
+    const int l = (int)(row % L), b = (int)(row / L);
+    const float g = c < Dm ? dy[row * Dm + c] : 0.f;
+    accb += g;
+#pragma unroll
+    for (int ci = 0; ci < EMB_MAX_CIN; ++ci) {
+      if (ci < Cin) {
+        const float* xr = x + ((long long)b * Cin + ci) * L;
+        acc[3 * ci] += g * (l > 0 ? xr[l - 1] : 0.f);
+        acc[3 * ci + 1] += g * xr[l];
+        acc[3 * ci + 2] += g * (l + 1 < L ? xr[l + 1] : 0.f);
+      }
+    }
+  }
+  if (c >= Dm) return;
+  const int J = 3 * Cin + 1;
+  float* dst = partial + (long long)blockIdx.x * J * Dm + c;
+#pragma unroll
+  for (int j = 0; j < 3 * EMB_MAX_CIN; ++j)
+    if (j < 3 * Cin) dst[(long long)j * Dm] = acc[j];
+  dst[(long long)(J - 1) * Dm] = accb;
+}
+
+// one thread per (j, c): the chunks in order
+__global__ __launch_bounds__(256) void embed1d_wgrad_sum_kernel(const float* __restrict__ partial, int chunks, int Cin,
+                                                                int Dm, float* __restrict__ dw, float* __restrict__ db) {
+  const int J = 3 * Cin + 1;
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= J * Dm) return;
+  const int j = e / Dm, c = e - j * Dm;
+  float acc = 0.f;
+  for (int k = 0; k < chunks; ++k) acc += partial[((long long)k * J + j) * Dm + c];
+  if (j == J - 1) {
+    if (db) db[c] = acc;
+  } else if (dw) {
+    dw[(long long)c * 3 * Cin + j] = acc;
+  }
+}
+
+// dpos [pos_len][Dm]: rows below L are the sum over the batch (in order), the others zero
+__global__ __launch_bounds__(256) void embed1d_dpos_kernel(const float* __restrict__ dy, float* __restrict__ dpos, int B,
+                                                           int L, int Dm, int pos_len) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long long)pos_len * Dm) return;
+  const long long l = e / Dm;
+  float acc = 0.f;
+  if (l < L)
+    for (int b = 0; b < B; ++b) acc += dy[(long long)b * L * Dm + e];
+  dpos[e] = acc;
+}
+
+// one wave per (b, l): dx[b][ci][l] = sum_k sum_c w[c][ci][k] dy[b][l + 1 - k][c]
+__global__ __launch_bounds__(256) void embed1d_dx_kernel(const float* __restrict__ dy, const float* __restrict__ w,
+                                                         float* __restrict__ dx, int B, int Cin, int L, int Dm) {
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= (long long)B * L) return;   // wave-uniform
+  const int lane = threadIdx.x & 63;
+  const int l = (int)(row % L), b = (int)(row / L);
+  for (int ci = 0; ci < Cin; ++ci) {
+    float acc = 0.f;
+    for (int k = 0; k < 3; ++k) {
+      const int ls = l + 1 - k;
+      if (ls < 0 || ls >= L) continue;
+      const float* g = dy + ((long long)b * L + ls) * Dm;
+      for (int c = lane; c < Dm; c += 64) acc += w[((long long)c * Cin + ci) * 3 + k] * g[c];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (lane == 0) dx[((long long)b * Cin + ci) * L + l] = acc;
+  }
+}
+
+static int embed_check(const char* what, int B, int Cin, int L, int Dm) {
+  if (B < 1 || L < 1 || Cin < 1 || Cin > EMB_MAX_CIN || Dm < 1 || Dm > 4096 || (long long)B * L > 0x7fffffffLL)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "%s: need B, L >= 1, 1 <= input_dim <= %d, 1 <= d_model <= 4096, B * L < 2^31 (B=%d input_dim=%d "
+             "L=%d d_model=%d)", what, EMB_MAX_CIN, B, Cin, L, Dm);
+  return 0;
+}
+
+static size_t embed_ws(int B, int Cin, int L, int Dm) {
+  const size_t chunks = ((size_t)B * L + EMB_ROWS - 1) / EMB_ROWS;
+  return align_up(chunks * (3 * (size_t)Cin + 1) * Dm * sizeof(float), 256);
+}
+
+}  // namespace
+
+extern "C" size_t ecgmm_mha_bwd_workspace(const ecgmm_mha_desc* d) {
+  MhaGeo g;
+  if (mha_geo(d, "mha_bwd_workspace", &g) != 0) return 0;
+  return align_up((size_t)g.P * g.S * sizeof(float), 256);
+}
+
+extern "C" int ecgmm_mha_forward(const ecgmm_mha_desc* d, const float* qkv, float* out, float* lse, uint64_t seed,
+                                 uint64_t offset, void* stream) {
+  MhaGeo g;
+  ECG_TRY(mha_geo(d, "mha_forward", &g));
+  if (!qkv || !out || !lse) ECG_FAIL(ECGMM_ERR_SHAPE, "mha_forward: null operand");
+  if (!aligned16(qkv) || !aligned16(out)) ECG_FAIL(ECGMM_ERR_SHAPE, "mha_forward: qkv and out must be 16-byte aligned");
+  g.seed = seed; g.offset = offset;
+  const long long units = mha_units(g);
+  const dim3 grid((unsigned)((units + 3) / 4));
+  auto* fn = d->head_dim == 16 ? (g.G ? mha_fwd_kernel<16, true> : mha_fwd_kernel<16, false>)
+                               : (g.G ? mha_fwd_kernel<32, true> : mha_fwd_kernel<32, false>);
+  hipLaunchKernelGGL(fn, grid, dim3(256), 0, (hipStream_t)stream, g, qkv, out, lse, units);
+  ECG_CHECK_LAUNCH("mha_forward");
+  return 0;
+}
+
+extern "C" int ecgmm_mha_backward(const ecgmm_mha_desc* d, const float* qkv, const float* out, const float* lse,
+                                  const float* dout, float* dqkv, void* ws, size_t ws_bytes, uint64_t seed, uint64_t offset,
+                                  void* stream) {
+  MhaGeo g;
+  ECG_TRY(mha_geo(d, "mha_backward", &g));
+  if (!qkv || !out || !lse || !dout || !dqkv || !ws) ECG_FAIL(ECGMM_ERR_SHAPE, "mha_backward: null operand");
+  if (!aligned16(qkv) || !aligned16(out) || !aligned16(dout) || !aligned16(dqkv))
+    ECG_FAIL(ECGMM_ERR_SHAPE, "mha_backward: qkv, out, dout and dqkv must be 16-byte aligned");
+  const size_t need = align_up((size_t)g.P * g.S * sizeof(float), 256);
+  if (ws_bytes < need) ECG_FAIL(ECGMM_ERR_WORKSPACE, "mha_backward: workspace of %zu bytes, %zu needed", ws_bytes, need);
+  g.seed = seed; g.offset = offset;
+  hipStream_t st = (hipStream_t)stream;
+  float* D = (float*)ws;
+  const long long units = mha_units(g);
+  const dim3 grid((unsigned)((units + 3) / 4)), grid_d((unsigned)(((long long)g.P * g.S + 255) / 256));
+  auto* fn_d = d->head_dim == 16 ? mha_rowdot_kernel<16> : mha_rowdot_kernel<32>;
+  auto* fn_kv = d->head_dim == 16 ? (g.G ? mha_bwd_kv_kernel<16, true> : mha_bwd_kv_kernel<16, false>)
+                                  : (g.G ? mha_bwd_kv_kernel<32, true> : mha_bwd_kv_kernel<32, false>);
+  auto* fn_q = d->head_dim == 16 ? (g.G ? mha_bwd_q_kernel<16, true> : mha_bwd_q_kernel<16, false>)
+                                 : (g.G ? mha_bwd_q_kernel<32, true> : mha_bwd_q_kernel<32, false>);
+  hipLaunchKernelGGL(fn_d, grid_d, dim3(256), 0, st, g, out, dout, D);
+  ECG_CHECK_LAUNCH("mha_backward rowdot");
+  hipLaunchKernelGGL(fn_kv, grid, dim3(256), 0, st, g, qkv, lse, D, dout, dqkv, units);
+  ECG_CHECK_LAUNCH("mha_backward dK dV");
+  hipLaunchKernelGGL(fn_q, grid, dim3(256), 0, st, g, qkv, lse, D, dout, dqkv, units);
+  ECG_CHECK_LAUNCH("mha_backward dQ");
+  return 0;
+}
+
+extern "C" int ecgmm_mha_keep_mask(const ecgmm_mha_desc* d, uint8_t* mask, uint64_t seed, uint64_t offset, void* stream) {
+  MhaGeo g;
+  ECG_TRY(mha_geo(d, "mha_keep_mask", &g));
+  if (!mask) ECG_FAIL(ECGMM_ERR_SHAPE, "mha_keep_mask: null operand");
+  if (d->S > 32768) ECG_FAIL(ECGMM_ERR_SHAPE, "mha_keep_mask: needs S <= 32768, S=%d", d->S);
+  const long long n = (long long)g.P * g.S * g.SB;
+  if (n > 0x7fffffffLL * 256) ECG_FAIL(ECGMM_ERR_SHAPE, "mha_keep_mask: N * heads * S * S / 4 beyond the launch grid");
+  g.seed = seed; g.offset = offset;
+  hipLaunchKernelGGL(mha_keep_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, mask);
+  ECG_CHECK_LAUNCH("mha_keep_mask");
+  return 0;
+}
+
+extern "C" int ecgmm_embed1d_fwd(const float* x, const float* w, const float* bias, const float* pos, float* y, int B,
+                                 int Cin, int L, int Dm, void* stream) {
+  ECG_TRY(embed_check("embed1d_fwd", B, Cin, L, Dm));
+  if (!x || !w || !bias || !pos || !y) ECG_FAIL(ECGMM_ERR_SHAPE, "embed1d_fwd: null operand");
+  const long long total = (long long)B * L * Dm;
+  const long long blocks = (total + 255) / 256;
+  hipLaunchKernelGGL(embed1d_fwd_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0,
+                     (hipStream_t)stream, x, w, bias, pos, y, B, Cin, L, Dm);
+  ECG_CHECK_LAUNCH("embed1d_fwd");
+  return 0;
+}
+
+extern "C" size_t ecgmm_embed1d_bwd_workspace(int B, int Cin, int L, int Dm) {
+  if (embed_check("embed1d_bwd_workspace", B, Cin, L, Dm) != 0) return 0;
+  return embed_ws(B, Cin, L, Dm);
+}
+
+extern "C" int ecgmm_embed1d_bwd(const float* x, const float* w, const float* dy, float* dw, float* db, float* dpos,
+                                 float* dx, int B, int Cin, int L, int Dm, int pos_len, void* ws, size_t ws_bytes,
+                                 void* stream) {
+  ECG_TRY(embed_check("embed1d_bwd", B, Cin, L, Dm));
+  if (!x || !w || !dy) ECG_FAIL(ECGMM_ERR_SHAPE, "embed1d_bwd: null operand");
+  if (dpos && pos_len < L) ECG_FAIL(ECGMM_ERR_SHAPE, "embed1d_bwd: pos_len=%d below L=%d", pos_len, L);
+  hipStream_t st = (hipStream_t)stream;
+  if (dw || db) {
+    const size_t need = embed_ws(B, Cin, L, Dm);
+    if (!ws || ws_bytes < need)
+      ECG_FAIL(ECGMM_ERR_WORKSPACE, "embed1d_bwd: workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0, need);
+    const int chunks = (int)(((long long)B * L + EMB_ROWS - 1) / EMB_ROWS);
+    hipLaunchKernelGGL(embed1d_wgrad_rows_kernel, dim3((unsigned)chunks, (unsigned)ceil_div(Dm, 64)), dim3(64), 0, st, x, dy,
+                       (float*)ws, B, Cin, L, Dm);
+    ECG_CHECK_LAUNCH("embed1d_bwd rows");
+    hipLaunchKernelGGL(embed1d_wgrad_sum_kernel, dim3((unsigned)ceil_div((long)(3 * Cin + 1) * Dm, 256)), dim3(256), 0, st,
+                       (const float*)ws, chunks, Cin, Dm, dw, db);
+    ECG_CHECK_LAUNCH("embed1d_bwd sum");
+  }
+  if (dpos) {
+    hipLaunchKernelGGL(embed1d_dpos_kernel, dim3((unsigned)ceil_div((long)pos_len * Dm, 256)), dim3(256), 0, st, dy, dpos, B,
+                       L, Dm, pos_len);
+    ECG_CHECK_LAUNCH("embed1d_bwd dpos");
+  }
+  if (dx) {
+    hipLaunchKernelGGL(embed1d_dx_kernel, dim3((unsigned)(((long long)B * L + 3) / 4)), dim3(256), 0, st, dy, w, dx, B, Cin, L,
+                       Dm);
+    ECG_CHECK_LAUNCH("embed1d_bwd dx");
+  }
+  return 0;
+}

@@ -762,3 +762,126 @@ def shap_deep(x, bg, w1, b1, w2, want_z=False):
     L.check(L.lib().ecgmm_shap_deep(ptr(x), ptr(bg), ptr(w1), ptr(b1), ptr(w2), B, N, D, H, C, ptr(out["phi"]),
                                     ptr(out.get("zx")), ptr(out.get("zb")), ptr(ws), ws.numel(), stream()), "shap_deep")
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# Transformer encoder pieces      reference: train_physionet.py:216-220, 233-236 (nn.TransformerEncoderLayer);
+#                                 multimodal_paper_modal_balance.py:127-194
+# --------------------------------------------------------------------------------------------
+def _aligned16(t):
+    """the attention kernels read rows as float4: a view that starts off a 16-byte boundary is copied (plumbing)"""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class MultiHeadAttentionFn(torch.autograd.Function):
+    """out [rows, E] = concat_heads(softmax(Q K^T / sqrt(d)) V) of the packed projection qkv [rows, 3E] (csrc/attention.hip).
+    Saves qkv, out and one log-sum-exp per score row; the backward recomputes the probabilities and, with dropout, the keep
+    decisions from the call's (seed, offset)."""
+
+    @staticmethod
+    def forward(ctx, qkv, cfg):
+        S, N, heads, batch_first, p = cfg
+        _require_cuda(qkv, "multi_head_attention")
+        if qkv.dim() != 2 or qkv.shape[0] != S * N or qkv.shape[1] % (3 * heads):
+            raise RuntimeError(f"multi_head_attention: qkv must be [S * N, 3 * E] with E a multiple of heads, got "
+                               f"{tuple(qkv.shape)} for S={S} N={N} heads={heads}")
+        qkv = _aligned16(f32c(qkv))
+        E = qkv.shape[1] // 3
+        desc = L.MHADesc(S, N, heads, E // heads, int(batch_first), float(p))
+        out = torch.empty(S * N, E, device=qkv.device, dtype=torch.float32)
+        lse = torch.empty(N * heads * S, device=qkv.device, dtype=torch.float32)
+        seed, off = _PhiloxState.take(4) if p > 0 else (0, 0)
+        L.check(L.lib().ecgmm_mha_forward(C.byref(desc), ptr(qkv), ptr(out), ptr(lse), seed, off, stream()), "mha_forward")
+        ctx.desc, ctx.rng = desc, (seed, off)
+        ctx.save_for_backward(qkv, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        desc = ctx.desc
+        dout = _aligned16(f32c(dout))
+        dqkv = torch.empty_like(qkv)
+        lib = L.lib()
+        ws = _Scratch.get("mha_bwd", lib.ecgmm_mha_bwd_workspace(C.byref(desc)), qkv.device)
+        L.check(lib.ecgmm_mha_backward(C.byref(desc), ptr(qkv), ptr(out), ptr(lse), ptr(dout), ptr(dqkv), ptr(ws),
+                                       ws.numel(), ctx.rng[0], ctx.rng[1], stream()), "mha_backward")
+        return dqkv, None
+
+
+def multi_head_attention(qkv, S, N, heads, batch_first=False, p=0.0, training=False):
+    """Self-attention on the packed projection ``qkv`` [S * N, 3E] (row ``s * N + n``, or ``n * S + s`` with
+    ``batch_first``) -> [S * N, E], heads concatenated.  ``p``: dropout on the attention weights, in training only; its
+    Philox offset comes from :func:`manual_seed`'s stream."""
+    p = float(p) if training else 0.0
+    return MultiHeadAttentionFn.apply(qkv, (int(S), int(N), int(heads), bool(batch_first), p))
+
+
+class AddFn(torch.autograd.Function):
+    """a + b through ecgmm_ew (the residual connections of the encoder layer)."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        _require_cuda(a, "add")
+        _require_cuda(b, "add")
+        a, b = f32c(a), f32c(b)
+        if a.shape != b.shape:
+            raise RuntimeError(f"add: shapes {tuple(a.shape)} and {tuple(b.shape)} differ")
+        out = torch.empty_like(a)
+        L.check(L.lib().ecgmm_ew(7, ptr(a), ptr(b), ptr(out), a.numel(), 0.0, stream()), "ew add")   # ECGMM_EW_ADD
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        return dy, dy
+
+
+def add(a, b):
+    return AddFn.apply(a, b)
+
+
+class Embed1dFn(torch.autograd.Function):
+    """[B, Cin, L] -> [B, L, D]: Conv1d(Cin, D, 3, padding=1) + bias, channels last, + pos[0, :L] in one launch."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, pos):
+        for t in (x, weight, bias, pos):
+            _require_cuda(t, "embed1d")
+        x = f32c(x)
+        if x.dim() != 3 or weight.dim() != 3 or weight.shape[1] != x.shape[1] or weight.shape[2] != 3:
+            raise RuntimeError(f"embed1d: x {tuple(x.shape)} / weight {tuple(weight.shape)}: need [B, Cin, L] and [D, Cin, 3]")
+        B, Cin, Ln = x.shape
+        D = weight.shape[0]
+        if pos.dim() != 3 or pos.shape[0] != 1 or pos.shape[2] != D or pos.shape[1] < Ln:
+            raise RuntimeError(f"embed1d: pos {tuple(pos.shape)} must be [1, >= {Ln}, {D}]")
+        for p in (weight, bias, pos):
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError("embed1d: parameters must be contiguous fp32")
+        y = torch.empty(B, Ln, D, device=x.device, dtype=torch.float32)
+        L.check(L.lib().ecgmm_embed1d_fwd(ptr(x), ptr(weight), ptr(bias), ptr(pos), ptr(y), B, Cin, Ln, D, stream()),
+                "embed1d_fwd")
+        ctx.params = (weight, bias, pos)
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        weight, bias, pos = ctx.params
+        B, Cin, Ln = x.shape
+        D = weight.shape[0]
+        dy = f32c(dy)
+        need = ctx.needs_input_grad
+        dx = torch.empty_like(x) if need[0] else None
+        dw = grad_sink(weight) if need[1] else None
+        db = grad_sink(bias) if need[2] else None
+        dpos = grad_sink(pos) if need[3] else None
+        lib = L.lib()
+        ws = _Scratch.get("embed1d", lib.ecgmm_embed1d_bwd_workspace(B, Cin, Ln, D), x.device)
+        L.check(lib.ecgmm_embed1d_bwd(ptr(x), ptr(weight), ptr(dy), ptr(dw), ptr(db), ptr(dpos), ptr(dx), B, Cin, Ln, D,
+                                      pos.shape[1], ptr(ws), ws.numel(), stream()), "embed1d_bwd")
+        return dx, None, None, None
+
+
+def embed1d(x, weight, bias, pos):
+    return Embed1dFn.apply(x, weight, bias, pos)

@@ -42,6 +42,10 @@ class LSTMDesc(C.Structure):
     _fields_ = [(n, i32) for n in ("B", "T", "In", "H", "layers", "bidirectional", "batch_first", "save_for_backward")]
 
 
+class MHADesc(C.Structure):
+    _fields_ = [(n, i32) for n in ("S", "N", "heads", "head_dim", "batch_first")] + [("p_drop", f32)]
+
+
 class CRNNFrontDesc(C.Structure):
     _fields_ = [("B", i32), ("F", i32), ("T", i32), ("dtype", i32), ("training", i32), ("bn_momentum", f32), ("bn_eps", f32)]
 
@@ -225,6 +229,13 @@ SIGNATURES = {
     "ecgmm_shap_mlp_workspace": (sz, [i32, i32, i32, i32, i32]),
     "ecgmm_shap_gradient": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "ecgmm_shap_deep": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "ecgmm_mha_bwd_workspace": (sz, [P(MHADesc)]),
+    "ecgmm_mha_forward": (i32, [P(MHADesc), vp, vp, vp, u64, u64, vp]),
+    "ecgmm_mha_backward": (i32, [P(MHADesc), vp, vp, vp, vp, vp, vp, sz, u64, u64, vp]),
+    "ecgmm_mha_keep_mask": (i32, [P(MHADesc), vp, u64, u64, vp]),
+    "ecgmm_embed1d_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "ecgmm_embed1d_bwd_workspace": (sz, [i32, i32, i32, i32]),
+    "ecgmm_embed1d_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
 }
 
 # Entry points of the input-gradient / Grad-CAM feature.  A library selected with ECGMM_LIB for an A/B run may predate them:
@@ -261,7 +272,10 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  # SHAP of the fusion head (ecgmm/shap_explainers.py, csrc/shap.hip)
                  "ecgmm_shap_mlp_workspace", "ecgmm_shap_gradient", "ecgmm_shap_deep",
                  # the dual BatchNorm backward of the downsample blocks (csrc/elementwise.hip)
-                 "ecgmm_bn_bwd_dual", "ecgmm_bn_dual")
+                 "ecgmm_bn_bwd_dual", "ecgmm_bn_dual",
+                 # the Transformer encoder (ecgmm.hip.nn.TransformerEncoder, csrc/attention.hip)
+                 "ecgmm_mha_bwd_workspace", "ecgmm_mha_forward", "ecgmm_mha_backward", "ecgmm_mha_keep_mask",
+                 "ecgmm_embed1d_fwd", "ecgmm_embed1d_bwd_workspace", "ecgmm_embed1d_bwd")
 
 _lib = None
 

@@ -186,3 +186,133 @@ class LSTM(nn.Module):
     def extra_repr(self):
         return (f"{self.input_size}, {self.hidden_size}, num_layers={self.num_layers}, batch_first={self.batch_first}, "
                 f"bidirectional={self.bidirectional}")
+
+
+class MultiheadAttention(nn.Module):
+    """``torch.nn.MultiheadAttention`` restricted to what ``nn.TransformerEncoderLayer`` asks of it (train_physionet.py:219):
+    self-attention with packed ``in_proj_weight`` / ``in_proj_bias`` and ``out_proj``, torch's names, shapes and
+    initialisation.  ``forward(x)`` -> ``(output, None)``; the attention weights are never formed."""
+
+    def __init__(self, embed_dim, num_heads, dropout=0.0, bias=True, add_bias_kv=False, add_zero_attn=False, kdim=None,
+                 vdim=None, batch_first=False):
+        super().__init__()
+        for name, value, only in (("bias", bias, True), ("add_bias_kv", add_bias_kv, False),
+                                  ("add_zero_attn", add_zero_attn, False)):
+            if value != only:
+                raise ValueError(f"MultiheadAttention: {name}={value} is not supported (only {name}={only})")
+        for name, value in (("kdim", kdim), ("vdim", vdim)):
+            if value is not None and value != embed_dim:
+                raise ValueError(f"MultiheadAttention: {name}={value} is not supported (self-attention only: {name}=embed_dim)")
+        if embed_dim < 1 or num_heads < 1 or embed_dim % num_heads:
+            raise ValueError("MultiheadAttention: embed_dim must be divisible by num_heads")
+        if embed_dim // num_heads not in (16, 32):
+            raise ValueError(f"MultiheadAttention: head_dim={embed_dim // num_heads} is not supported (embed_dim / num_heads "
+                             "must be 16 or 32)")
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError(f"MultiheadAttention: dropout={dropout} must lie in [0, 1)")
+        self.embed_dim, self.num_heads, self.dropout, self.batch_first = embed_dim, num_heads, float(dropout), batch_first
+        self.head_dim = embed_dim // num_heads
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * embed_dim, embed_dim))
+        self.in_proj_bias = nn.Parameter(torch.empty(3 * embed_dim))
+        self.out_proj = Linear(embed_dim, embed_dim)
+        self._reset_parameters()
+
+    def _reset_parameters(self):
+        nn.init.xavier_uniform_(self.in_proj_weight)
+        nn.init.constant_(self.in_proj_bias, 0.0)
+        nn.init.constant_(self.out_proj.bias, 0.0)
+
+    def forward(self, query, key=None, value=None, key_padding_mask=None, need_weights=False, attn_mask=None,
+                is_causal=False):
+        for name, t in (("key", key), ("value", value)):
+            if t is not None and t is not query:
+                raise ValueError(f"MultiheadAttention: a separate {name} is not supported (self-attention only)")
+        for name, t in (("key_padding_mask", key_padding_mask), ("attn_mask", attn_mask)):
+            if t is not None:
+                raise ValueError(f"MultiheadAttention: {name} is not supported (no masks)")
+        if is_causal:
+            raise ValueError("MultiheadAttention: is_causal=True is not supported (no masks)")
+        if need_weights:
+            raise ValueError("MultiheadAttention: need_weights=True is not supported (the weights are never formed)")
+        if query.dim() != 3 or query.shape[2] != self.embed_dim:
+            raise ValueError(f"MultiheadAttention: input must be 3-D with {self.embed_dim} features, got {tuple(query.shape)}")
+        return self._attend(query.reshape(-1, self.embed_dim), query.shape).reshape(query.shape), None
+
+    def _attend(self, x2, shape):
+        """x2 [rows, E], the rows of a tensor of ``shape`` -> [rows, E]"""
+        S, N = (shape[1], shape[0]) if self.batch_first else (shape[0], shape[1])
+        qkv = HF.linear(x2, self.in_proj_weight, self.in_proj_bias)
+        a = HF.multi_head_attention(qkv, S, N, self.num_heads, self.batch_first, self.dropout, self.training)
+        return HF.linear(a, self.out_proj.weight, self.out_proj.bias)
+
+
+class TransformerEncoderLayer(nn.Module):
+    """``torch.nn.TransformerEncoderLayer``, post-norm with ReLU (train_physionet.py:219): existing ops around the attention
+    kernel -- ``linear`` (ReLU in ``linear1``'s epilogue), ``dropout``, the residual adds through ``ecgmm_ew``,
+    ``layer_norm``.  torch's sub-module names, so ``state_dict``s move in both directions."""
+
+    def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0.1, activation="relu", layer_norm_eps=1e-5,
+                 batch_first=False, norm_first=False, bias=True):
+        super().__init__()
+        if norm_first:
+            raise ValueError("TransformerEncoderLayer: norm_first=True is not supported (only post-norm)")
+        if not (activation == "relu" or activation is torch.relu or activation is nn.functional.relu or
+                isinstance(activation, nn.ReLU)):
+            raise ValueError(f"TransformerEncoderLayer: activation={activation!r} is not supported (only relu)")
+        if not bias:
+            raise ValueError("TransformerEncoderLayer: bias=False is not supported (only bias=True)")
+        self.self_attn = MultiheadAttention(d_model, nhead, dropout=dropout, batch_first=batch_first)
+        self.linear1 = Linear(d_model, dim_feedforward)
+        self.dropout = nn.Dropout(dropout)
+        self.linear2 = Linear(dim_feedforward, d_model)
+        self.norm_first = False
+        self.norm1 = LayerNorm(d_model, eps=layer_norm_eps)
+        self.norm2 = LayerNorm(d_model, eps=layer_norm_eps)
+        self.dropout1 = nn.Dropout(dropout)
+        self.dropout2 = nn.Dropout(dropout)
+
+    def forward(self, src, src_mask=None, src_key_padding_mask=None, is_causal=False):
+        for name, t in (("src_mask", src_mask), ("src_key_padding_mask", src_key_padding_mask)):
+            if t is not None:
+                raise ValueError(f"TransformerEncoderLayer: {name} is not supported (no masks)")
+        if is_causal:
+            raise ValueError("TransformerEncoderLayer: is_causal=True is not supported (no masks)")
+        E = self.self_attn.embed_dim
+        if src.dim() != 3 or src.shape[2] != E:
+            raise ValueError(f"TransformerEncoderLayer: input must be 3-D with {E} features, got {tuple(src.shape)}")
+        t = self.training
+        x = src.reshape(-1, E)
+        a = HF.dropout(self.self_attn._attend(x, src.shape), self.dropout1.p, t and self.dropout1.training)
+        x = self.norm1(HF.add(x, a))
+        h = HF.dropout(self.linear1(x, act=L.ACT_RELU), self.dropout.p, t and self.dropout.training)
+        f = HF.dropout(self.linear2(h), self.dropout2.p, t and self.dropout2.training)
+        return self.norm2(HF.add(x, f)).reshape(src.shape)
+
+
+class TransformerEncoder(nn.Module):
+    """``torch.nn.TransformerEncoder``: ``num_layers`` deep copies of ``encoder_layer`` under ``layers.{i}`` (so, as in
+    torch, every layer starts from the same initial weights)."""
+
+    def __init__(self, encoder_layer, num_layers, norm=None, enable_nested_tensor=True, mask_check=True):
+        super().__init__()
+        import copy
+        if not isinstance(encoder_layer, TransformerEncoderLayer):
+            raise ValueError("TransformerEncoder: encoder_layer must be an ecgmm.hip.nn.TransformerEncoderLayer")
+        if norm is not None:
+            raise ValueError("TransformerEncoder: norm is not supported (only norm=None)")
+        if num_layers < 1:
+            raise ValueError("TransformerEncoder: num_layers must be >= 1")
+        self.layers = nn.ModuleList([copy.deepcopy(encoder_layer) for _ in range(num_layers)])
+        self.num_layers = num_layers
+        self.norm = None
+
+    def forward(self, src, mask=None, src_key_padding_mask=None, is_causal=None):
+        for name, t in (("mask", mask), ("src_key_padding_mask", src_key_padding_mask)):
+            if t is not None:
+                raise ValueError(f"TransformerEncoder: {name} is not supported (no masks)")
+        if is_causal:
+            raise ValueError("TransformerEncoder: is_causal=True is not supported (no masks)")
+        x = src
+        for layer in self.layers:
+            x = layer(x)
+        return x

@@ -5,9 +5,11 @@ The reference filters every sample again at every ``__getitem__`` on the CPU (4t
 ``filter_zscore`` launch (the result is a pure function of the record, so caching it changes nothing); per batch one
 ``gather_augment`` launch gathers the rows and applies ``augment_signal`` on the device.  The model, loss, optimizer and
 schedule are the reference's: ``ResNet1D_SE`` on ``[B, 1, 3000]``, ``FocalLoss(1, 2)``, Adam(1e-3), OneCycleLR per batch.
+``main(model="transformer")`` trains the reference's one-line alternative instead (train_physionet.py:276),
+:class:`ECGTransformer1D` on the native attention kernels.
 
 Not carried over: ``resample_signal`` (the reference never reaches it: ``orig_fs == target_fs`` at its only call site),
-the unused ``ECGTransformer1D``, plots.  ``wfdb`` is replaced by :func:`read_record`, ``keras`` by :func:`pad_sequences`.
+plots.  ``wfdb`` is replaced by :func:`read_record`, ``keras`` by :func:`pad_sequences`.
 """
 import csv
 import os
@@ -21,6 +23,7 @@ from . import preprocess as PP
 from .config import Config
 from .hip import functional as HF
 from .hip import lib as L
+from .hip import nn as HN
 from .hip.functional import _require_cuda, ptr, stream
 from .optim import FusedAdam
 from .signal_model import FocalLoss, ResNet1D_SE
@@ -30,6 +33,50 @@ MAX_LEN = 3000
 # train_physionet.py:113-118: 80 % train, the remaining 20 % halved into validation and test
 SPLIT = (0.2, 0.5)
 AUG_DEFAULTS = dict(p=0.5, sigma=0.01, scale=(0.8, 1.2), shift=(-10, 10))   # train_physionet.py:47-58
+
+
+# --------------------------------------------------------------------------------------------
+# the Transformer alternative                               reference: train_physionet.py:211-240, 276
+# --------------------------------------------------------------------------------------------
+class ECGTransformer1D(torch.nn.Module):
+    """``ECGTransformer1D`` of the reference with its attribute names, shapes and initialisation, so ``state_dict``s move in
+    both directions: Conv1d(input_dim, d_model, 3, padding=1) + ``pos_embedding`` (one launch, ``HF.embed1d``) -> a post-norm
+    ``TransformerEncoder`` -> mean over the positions -> Linear-ReLU-Dropout-Linear.
+
+    The reference builds its encoder layers with torch's default ``batch_first=False`` and feeds them ``[B, L, d_model]``
+    (:219, :236), so attention runs ACROSS THE BATCH: the sequence is the B samples of the batch and each of the L positions
+    is an independent attention "batch" element.  A sample's logits therefore depend on the other samples of its batch, in
+    eval mode too.  That is reproduced here as it is, not corrected."""
+
+    def __init__(self, input_dim=1, seq_len=3000, num_classes=2, d_model=128, nhead=4, num_layers=2, dim_feedforward=256):
+        super().__init__()
+        self.conv = HN.Conv1d(input_dim, d_model, kernel_size=3, padding=1)
+        self.pos_embedding = torch.nn.Parameter(torch.zeros(1, seq_len, d_model))
+        encoder_layer = HN.TransformerEncoderLayer(d_model=d_model, nhead=nhead, dim_feedforward=dim_feedforward)
+        self.transformer_encoder = HN.TransformerEncoder(encoder_layer, num_layers=num_layers)
+        self.global_pool = torch.nn.AdaptiveAvgPool1d(1)   # (executed as HF.seq_mean over the positions)
+        self.classifier = HN.Sequential(torch.nn.Flatten(), HN.Linear(d_model, 64), torch.nn.ReLU(), torch.nn.Dropout(0.3),
+                                        HN.Linear(64, num_classes))
+
+    def forward(self, x):
+        _require_cuda(x, "ECGTransformer1D")
+        if x.dim() != 3 or x.shape[1] != self.conv.in_channels:
+            raise ValueError(f"ECGTransformer1D expects [B, {self.conv.in_channels}, L], got {tuple(x.shape)}")
+        if x.shape[2] > self.pos_embedding.shape[1]:
+            raise ValueError(f"ECGTransformer1D: L={x.shape[2]} exceeds seq_len={self.pos_embedding.shape[1]}")
+        x = HF.embed1d(x, self.conv.weight, self.conv.bias, self.pos_embedding)   # [B, L, d_model]
+        x = self.transformer_encoder(x)                                            # sequence axis = B, as the reference
+        return self.classifier(HF.seq_mean(x))
+
+
+def build_model(model="resnet", num_classes=2, config=Config, seq_len=MAX_LEN):
+    """The network ``main`` trains: ``"resnet"`` = ``ResNet1D_SE`` (train_physionet.py:275), ``"transformer"`` =
+    :class:`ECGTransformer1D` (:276)."""
+    if model == "resnet":
+        return ResNet1D_SE(num_classes=num_classes, compute_dtype=getattr(config, "compute_dtype", "bf16"))
+    if model == "transformer":
+        return ECGTransformer1D(seq_len=seq_len, num_classes=num_classes)
+    raise ValueError(f"model={model!r}: expected 'resnet' or 'transformer'")
 
 
 # --------------------------------------------------------------------------------------------
@@ -303,8 +350,10 @@ def evaluate(model, loader, num_classes=2, predictor=None):
 
 
 def main(config=Config, num_epochs=30, batch_size=8, quiet=False, use_predictor=False, num_classes=2, label_map=LABEL_MAP,
-         augment=True, split=SPLIT):
-    """``use_predictor``: run the validation and test passes through an ``ecgmm.inference.Predictor`` (BatchNorm-folded
+         augment=True, split=SPLIT, model="resnet", max_len=MAX_LEN):
+    """``model``: ``"resnet"`` (the reference's choice) or ``"transformer"`` (its commented alternative, :276); ``max_len``:
+    the length every record is padded or cut to.
+    ``use_predictor``: run the validation and test passes through an ``ecgmm.inference.Predictor`` (BatchNorm-folded
     inference plan), refreshed after every training epoch and after every checkpoint load.  Default off.
     -> (history, {"best": metrics, "last": metrics}, checkpoint directory)."""
     torch.manual_seed(config.seed)
@@ -313,8 +362,10 @@ def main(config=Config, num_epochs=30, batch_size=8, quiet=False, use_predictor=
     device = torch.device(config.device)
     if not quiet:
         print(f"Using device: {device}")
-    train_loader, val_loader, test_loader = get_signalonly_dataloaders(config, batch_size, label_map, augment, split)
-    model = ResNet1D_SE(num_classes=num_classes, compute_dtype=getattr(config, "compute_dtype", "bf16")).to(device)
+    train_loader, val_loader, test_loader = get_signalonly_dataloaders(config, batch_size, label_map, augment, split, max_len)
+    if use_predictor and model != "resnet":
+        raise ValueError("use_predictor=True needs model='resnet' (the inference plan is the ResNet1D_SE's)")
+    model = build_model(model, num_classes, config, max_len).to(device)
     criterion = FocalLoss(alpha=1.0, gamma=2.0)
     optimizer = FusedAdam(model.parameters(), lr=0.001)
     scheduler = torch.optim.lr_scheduler.OneCycleLR(optimizer, max_lr=0.001, steps_per_epoch=len(train_loader),

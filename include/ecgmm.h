@@ -819,6 +819,52 @@ int ecgmm_shap_gradient(const float* x, const float* bg, const int* ridx, const 
 int ecgmm_shap_deep(const float* x, const float* bg, const float* W1, const float* b1, const float* W2, int B, int N, int D,
                     int H, int C, float* phi, float* zx, float* zb, void* ws, size_t ws_bytes, void* stream);
 
+/* Multi-head self-attention of nn.TransformerEncoderLayer, csrc/attention.hip: softmax(Q K^T / sqrt(head_dim)) V per
+ * (n, head), fp32, products on the exact-fp32 MFMA.  S is the sequence length and N the attention batch AS TORCH SEES
+ * THEM: train_physionet.py:219 builds the layer with batch_first = False and :236 feeds it [B, L, E], so there S = B and
+ * N = L; multimodal_paper_modal_balance.py:135 uses batch_first = True.  All pointers are device pointers, 16-byte aligned:
+ *   qkv  [rows][3E], E = heads * head_dim, as linear(x, in_proj_weight, in_proj_bias) leaves it; row(s, n) = s * N + n
+ *        (batch_first = 0) or n * S + s (batch_first = 1); read by stride, never copied or transposed
+ *   out  [rows][E], heads concatenated: the input of out_proj;  lse [N][heads][S]: log-sum-exp of each scaled score row
+ *   dout [rows][E];  dqkv [rows][3E]: every element WRITTEN (dQ, dK, dV), each reduced in a fixed order, no atomics
+ * No S x S tensor is formed: online softmax over 16-key tiles forward; the backward recomputes the probabilities from lse
+ * and needs one float per (n, head, query) of workspace (ecgmm_mha_bwd_workspace: no GPU needed, 0 with the message set on
+ * a bad descriptor).  Two identical calls give identical bits.
+ * p_drop > 0: dropout on the normalised probabilities, kept ones scaled by 1 / (1 - p_drop).  The decision for
+ * (n, head, query i, key j) is word j % 4 of the Philox4x32-10 block keyed by `seed` at counter
+ *     (offset low, offset high, n * heads + head, 0xC0000000 | i * ceil(S / 4) + j / 4),  keep iff (word >> 8) * 2^-24 >= p_drop;
+ * the backward regenerates it from the same (seed, offset), nothing is stored.  ecgmm_mha_keep_mask writes the decisions
+ * as bytes [N][heads][S][S] (tests and small shapes).  The caller advances `offset` by one per forward call.
+ * Needs S, N, heads >= 1, head_dim 16 or 32, batch_first 0 or 1, 0 <= p_drop < 1, S <= 32768 when p_drop > 0; anything
+ * else is ECGMM_ERR_SHAPE and writes nothing.  No attention or key-padding mask. */
+typedef struct {
+  int S, N, heads, head_dim, batch_first;
+  float p_drop;
+} ecgmm_mha_desc;
+/* train_physionet.py:219-220, 236 (its loss.backward()) */
+size_t ecgmm_mha_bwd_workspace(const ecgmm_mha_desc* d);
+/* train_physionet.py:219-220, 236: self_attn of each encoder layer */
+int ecgmm_mha_forward(const ecgmm_mha_desc* d, const float* qkv, float* out, float* lse, uint64_t seed, uint64_t offset,
+                      void* stream);
+/* train_physionet.py:219-220, 236: the self_attn part of loss.backward() */
+int ecgmm_mha_backward(const ecgmm_mha_desc* d, const float* qkv, const float* out, const float* lse, const float* dout,
+                       float* dqkv, void* ws, size_t ws_bytes, uint64_t seed, uint64_t offset, void* stream);
+/* train_physionet.py:219 (dropout = 0.1 of the layer, applied to the attention weights) */
+int ecgmm_mha_keep_mask(const ecgmm_mha_desc* d, uint8_t* mask, uint64_t seed, uint64_t offset, void* stream);
+
+/* The front of ECGTransformer1D (train_physionet.py:216-217, 233-235) as one launch: Conv1d(Cin, Dm, 3, padding = 1) + bias
+ * written straight as [B][L][Dm] with pos[l][c] added.  x [B][Cin][L], w [Dm][Cin][3], bias [Dm], pos [>= L][Dm], fp32.
+ * Backward: dy [B][L][Dm]; dw [Dm][Cin][3], db [Dm], dpos [pos_len][Dm] (rows >= L are written as zero) and dx [B][Cin][L]
+ * are each nullable (not computed) and otherwise WRITTEN, sums in a fixed order.  dw / db need the workspace
+ * (ecgmm_embed1d_bwd_workspace: no GPU needed, 0 with the message set when refused).
+ * Needs B, L >= 1, 1 <= Cin <= 12, 1 <= Dm <= 4096, pos_len >= L; else ECGMM_ERR_SHAPE and nothing is written. */
+int ecgmm_embed1d_fwd(const float* x, const float* w, const float* bias, const float* pos, float* y, int B, int Cin, int L,
+                      int Dm, void* stream);
+/* train_physionet.py:216-217, 233-235 (its loss.backward()) */
+size_t ecgmm_embed1d_bwd_workspace(int B, int Cin, int L, int Dm);
+int ecgmm_embed1d_bwd(const float* x, const float* w, const float* dy, float* dw, float* db, float* dpos, float* dx, int B,
+                      int Cin, int L, int Dm, int pos_len, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
