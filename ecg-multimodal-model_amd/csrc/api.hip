@@ -315,6 +315,12 @@ int ecgmm_se_gate_grad(int dtype, const void* dout, const void* maskref, const v
                        int N, int R, int C, void* stream) {
   return ecg_se_gate_grad(dtype, dout, maskref, y, coef, dg, N, R, C, S_(stream));
 }
+int ecgmm_se_gate_bn(int dtype, const void* dout, const void* maskref, const void* y, const float* coef, void* dz, float* dg,
+                     float* a1, float* a2, float* a3, int N, int R, int C, void* stream) {
+  if (!dout || !maskref || !y || !coef || !dz || !dg || !a1 || !a2 || !a3) ECG_FAIL(ECGMM_ERR_SHAPE, "se_gate_bn: null operand");
+  if (N < 1 || R < 1) ECG_FAIL(ECGMM_ERR_SHAPE, "se_gate_bn: N=%d R=%d", N, R);
+  return ecg_se_gate_bn(dtype, dout, maskref, y, coef, dz, dg, a1, a2, a3, N, R, C, S_(stream));
+}
 
 // ---- squeeze-excite MLP, per-op (head_fused.hip; SEBlock.fc, PMB:35-46): the fused kernels whatever ECGMM_SE_MLP_FUSED says ----
 static int se_mlp_shape(const char* what, int N, int C, int CR) {

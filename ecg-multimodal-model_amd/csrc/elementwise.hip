@@ -810,6 +810,117 @@ __global__ __launch_bounds__(1024) void rows_sum_kernel(const float* __restrict_
 // ------------------------------------------------------------------------------------------------
 // 3x3 / stride 2 / pad 1 max-pool fused with BN apply + ReLU (stem of both encoders; H may be 1)
 // ------------------------------------------------------------------------------------------------
+// One thread = TWO horizontally adjacent outputs (ow0 = 2 k, ow0 + 1) x one 16-B channel chunk, from a 3 x 5 window of inputs:
+// columns 0..2 are the taps kw = 0..2 of the first output, columns 2..4 those of the second, and the shared column 2 is
+// loaded and transformed once: 15 loads and BN + ReLU + key transforms for two outputs instead of 18, and the index
+// arithmetic once per pair.  The pass is bound by its VALU work (about 900 instructions per output chunk with a thread per
+// output, against 565 MB of traffic at the image shape), which is what the pairing cuts.
+// ALL window loads are issued before the first of them is used.  A tap outside the image is not branched around (a branch
+// per tap left one load in flight per wave and a wait behind each); its coordinates are CLAMPED into the image, so the load
+// stays inside the tensor, and the loaded value is taken out of the running afterwards: a clamped duplicate would carry an
+// earlier tap code and steal ties.  NR = 3 window rows, or 1 for the 1-D use (H == 1: only the middle row, taps 3..5,
+// exists), a launch constant decided outside the loads.  With an odd OW the last thread of a row has one output: its
+// columns 3, 4 are clamped like any other, the caller does not store the second result.
+// Stand-alone at 256 x 112 x 112 x 64, bf16, alternating builds: branch per tap 168-185 us, batched loads with a thread
+// per output 154-170 us, this form 142-149 us (profiles/ew_loads_ab.txt).
+template <typename T, int NR>
+__device__ __forceinline__ void pool_window2(const T* __restrict__ y, const float* scv, const float* shv, int n, int oh,
+                                             int ow0, int H, int W, int C, int c0, float (*best)[Elem<T>::VEC],
+                                             int (*bi)[Elem<T>::VEC]) {
+  constexpr int VEC = Elem<T>::VEC;
+  constexpr int KH0 = NR == 1 ? 1 : 0;
+  u32x4 q[NR * 5];
+  bool in[NR * 5];
+#pragma unroll
+  for (int kh = 0; kh < NR; ++kh) {
+    const int h = oh * 2 - 1 + KH0 + kh;
+    const int hc = min(max(h, 0), H - 1);
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+      const int w = ow0 * 2 - 1 + c;
+      const int wc = min(max(w, 0), W - 1);
+      in[kh * 5 + c] = h == hc && w == wc;
+      q[kh * 5 + c] = ld16(y + (((size_t)n * H + hc) * W + wc) * C + c0);
+    }
+  }
+  // (left to itself the scheduler sinks most of the loads between the taps' arithmetic, two or three in flight at a time)
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (sizeof(T) == 2) {
+    // bf16: post-ReLU values are >= 0, so their bf16 bit patterns order like the values.  One sortable key per
+    // channel, (bits << 4) | (15 - tap): a single unsigned max implements "largest value, earliest tap on ties".
+    // Every in-image key is >= 7; an out-of-image tap's key is forced to 0 (value mask and tap code both 0) and never wins.
+    unsigned key[2][VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) key[0][j] = key[1][j] = 0u;
+#pragma unroll
+    for (int kh = 0; kh < NR; ++kh) {
+#pragma unroll
+      for (int c = 0; c < 5; ++c) {
+        const int t = kh * 5 + c;
+        float f[VEC];
+        unpack16<T>(q[t], f);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) f[j] = fmaxf(f[j] * scv[j] + shv[j], 0.f);
+        const u32x4 r = pack16<bf16_t>(f);  // rounded as stored; (-0 cannot win: sign bit masked off)
+        const unsigned m = in[t] ? 0x7fffu : 0u;
+        // the tap codes of this column in the first (kw = c) and the second output (kw = c - 2)
+        const unsigned tc0 = in[t] ? 15u - (unsigned)((KH0 + kh) * 3 + c) : 0u;
+        const unsigned tc1 = in[t] ? 15u - (unsigned)((KH0 + kh) * 3 + c - 2) : 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const unsigned lo = (r[k] & m) << 4, hi = ((r[k] >> 16) & m) << 4;
+          if (c <= 2) {
+            key[0][2 * k] = max(key[0][2 * k], lo | tc0);
+            key[0][2 * k + 1] = max(key[0][2 * k + 1], hi | tc0);
+          }
+          if (c >= 2) {
+            key[1][2 * k] = max(key[1][2 * k], lo | tc1);
+            key[1][2 * k + 1] = max(key[1][2 * k + 1], hi | tc1);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        best[o][j] = __uint_as_float((key[o][j] >> 4) << 16);
+        bi[o][j] = 15 - (int)(key[o][j] & 15u);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        best[o][j] = -INFINITY;
+        bi[o][j] = 0;
+      }
+    }
+#pragma unroll
+    for (int kh = 0; kh < NR; ++kh) {
+#pragma unroll
+      for (int c = 0; c < 5; ++c) {   // (per output its taps still come in the order kh, kw: the earliest wins a tie)
+        const int t = kh * 5 + c;
+        float f[VEC];
+        unpack16<T>(q[t], f);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          float a = fmaxf(f[j] * scv[j] + shv[j], 0.f);
+          if (c <= 2 && in[t] && a > best[0][j]) {
+            best[0][j] = a;
+            bi[0][j] = (KH0 + kh) * 3 + c;
+          }
+          if (c >= 2 && in[t] && a > best[1][j]) {
+            best[1][j] = a;
+            bi[1][j] = (KH0 + kh) * 3 + c - 2;
+          }
+        }
+      }
+    }
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(EW_THREADS) void bnrelu_maxpool_kernel(const T* __restrict__ y,
                                                                     const float* __restrict__ coef, T* __restrict__ out,
@@ -817,90 +928,41 @@ __global__ __launch_bounds__(EW_THREADS) void bnrelu_maxpool_kernel(const T* __r
                                                                     int W, int C, int OH, int OW) {
   constexpr int VEC = Elem<T>::VEC;
   const int cpr = C / VEC;
-  long total = (long)N * OH * OW * cpr;
+  const int OWP = (OW + 1) / 2;   // output pairs per row
+  long total = (long)N * OH * OWP * cpr;
+  // the grid stride is a multiple of the block, the block a multiple of cpr (chunk_ok): a thread keeps its channel chunk over
+  // all its trips, and the chunk's coefficients stay in registers
+  const int c0 = (int)(((long)blockIdx.x * blockDim.x + threadIdx.x) % cpr) * VEC;
+  float scv[VEC], shv[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    scv[j] = coef[c0 + j];
+    shv[j] = coef[C + c0 + j];
+  }
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    int chunk = (int)(i % cpr);
-    long pix = i / cpr;
-    int ow = (int)(pix % OW);
-    long t = pix / OW;
+    long pp = i / cpr;
+    int ow0 = (int)(pp % OWP) * 2;
+    long t = pp / OWP;
     int oh = (int)(t % OH), n = (int)(t / OH);
-    int c0 = chunk * VEC;
-    float best[VEC];
-    int bi[VEC];
-    if constexpr (sizeof(T) == 2) {
-      // bf16: post-ReLU values are >= 0, so their bf16 bit patterns order like the values.  One sortable key per
-      // channel, (bits << 4) | (15 - tap): a single unsigned max implements "largest value, earliest tap on ties".
-      unsigned key[VEC];
-      float scv[VEC], shv[VEC];
+    float best[2][VEC];
+    int bi[2][VEC];
+    if (H == 1) pool_window2<T, 1>(y, scv, shv, n, oh, ow0, H, W, C, c0, best, bi);
+    else pool_window2<T, 3>(y, scv, shv, n, oh, ow0, H, W, C, c0, best, bi);
+    const long pix = ((long)n * OH + oh) * OW + ow0;
 #pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        key[j] = 0u;
-        scv[j] = coef[c0 + j];
-        shv[j] = coef[C + c0 + j];
-      }
+    for (int o = 0; o < 2; ++o) {
+      if (ow0 + o >= OW) break;
+      st16(out + (pix + o) * C + c0, pack16<T>(best[o]));
+      // the VEC argmax bytes of this chunk go out as one 8-B (bf16) / 4-B (f32) store
+      unsigned pk[VEC / 4];
 #pragma unroll
-      for (int kh = 0; kh < 3; ++kh) {
-        int h = oh * 2 - 1 + kh;
-        if ((unsigned)h >= (unsigned)H) continue;
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw) {
-          int w = ow * 2 - 1 + kw;
-          if ((unsigned)w >= (unsigned)W) continue;
-          float f[VEC];
-          unpack16<T>(ld16(y + (((size_t)n * H + h) * W + w) * C + c0), f);
-#pragma unroll
-          for (int j = 0; j < VEC; ++j) f[j] = fmaxf(f[j] * scv[j] + shv[j], 0.f);
-          const u32x4 r = pack16<bf16_t>(f);  // rounded as stored; (-0 cannot win: sign bit masked off)
-          const unsigned tcode = 15u - (unsigned)(kh * 3 + kw);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            key[2 * q] = max(key[2 * q], ((r[q] & 0x7fffu) << 4) | tcode);
-            key[2 * q + 1] = max(key[2 * q + 1], (((r[q] >> 16) & 0x7fffu) << 4) | tcode);
-          }
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        best[j] = __uint_as_float((key[j] >> 4) << 16);
-        bi[j] = 15 - (int)(key[j] & 15u);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        best[j] = -INFINITY;
-        bi[j] = 0;
-      }
-#pragma unroll
-      for (int kh = 0; kh < 3; ++kh) {
-        int h = oh * 2 - 1 + kh;
-        if ((unsigned)h >= (unsigned)H) continue;
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw) {
-          int w = ow * 2 - 1 + kw;
-          if ((unsigned)w >= (unsigned)W) continue;
-          float f[VEC];
-          unpack16<T>(ld16(y + (((size_t)n * H + h) * W + w) * C + c0), f);
-#pragma unroll
-          for (int j = 0; j < VEC; ++j) {
-            float a = fmaxf(f[j] * coef[c0 + j] + coef[C + c0 + j], 0.f);
-            if (a > best[j]) {
-              best[j] = a;
-              bi[j] = kh * 3 + kw;
-            }
-          }
-        }
-      }
+      for (int q = 0; q < VEC / 4; ++q)
+        pk[q] = (unsigned)bi[o][4 * q] | ((unsigned)bi[o][4 * q + 1] << 8) | ((unsigned)bi[o][4 * q + 2] << 16) |
+                ((unsigned)bi[o][4 * q + 3] << 24);
+      unsigned* ip = reinterpret_cast<unsigned*>(idx + (pix + o) * C + c0);
+      if constexpr (VEC == 8) *reinterpret_cast<uint2*>(ip) = make_uint2(pk[0], pk[1]);
+      else ip[0] = pk[0];
     }
-    st16(out + pix * C + c0, pack16<T>(best));
-    // the VEC argmax bytes of this chunk go out as one 8-B (bf16) / 4-B (f32) store
-    unsigned pk[VEC / 4];
-#pragma unroll
-    for (int q = 0; q < VEC / 4; ++q)
-      pk[q] = (unsigned)bi[4 * q] | ((unsigned)bi[4 * q + 1] << 8) | ((unsigned)bi[4 * q + 2] << 16) |
-              ((unsigned)bi[4 * q + 3] << 24);
-    unsigned* ip = reinterpret_cast<unsigned*>(idx + pix * C + c0);
-    if constexpr (VEC == 8) *reinterpret_cast<uint2*>(ip) = make_uint2(pk[0], pk[1]);
-    else ip[0] = pk[0];
   }
 }
 
@@ -1176,7 +1238,30 @@ __global__ __launch_bounds__(EW_THREADS) void sample_reduce_kernel(const T* __re
     sf[j] = (SEGATE || coef) ? coef[C + c0 + j] : 0.f;
   }
   int r = slice;
-  if (!SEGATE) {   // four rows in flight per thread (one load per iteration ran at 3.3 TB/s)
+  // four rows in flight per thread (one load per iteration ran at 3.3 TB/s): all loads of the group first, then the
+  // arithmetic in row order, so that each accumulator sees the rows r = slice, slice + nsl, ... as a one-row walk does
+  if (SEGATE) {
+    for (; r + 3 * nsl < R; r += 4 * nsl) {
+      u32x4 q[4], qm[4], qv[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const size_t o = ((size_t)n * R + r + u * nsl) * C + c0;
+        q[u] = ld16(x + o);
+        qm[u] = ld16(maskref + o);
+        qv[u] = ld16(y + o);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        float f[VEC], m[VEC], v[VEC];
+        unpack16<T>(q[u], f);
+        unpack16<T>(qm[u], m);
+        unpack16<T>(qv[u], v);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j)
+          if (m[j] > 0.f) acc[j] += f[j] * (v[j] * sc[j] + sf[j]);
+      }
+    }
+  } else {
     for (; r + 3 * nsl < R; r += 4 * nsl) {
       u32x4 q[4];
 #pragma unroll
@@ -1192,16 +1277,19 @@ __global__ __launch_bounds__(EW_THREADS) void sample_reduce_kernel(const T* __re
   }
   for (; r < R; r += nsl) {
     const size_t o = ((size_t)n * R + r) * C + c0;
-    float f[VEC];
-    unpack16<T>(ld16(x + o), f);
+    const u32x4 q = ld16(x + o);
     if (SEGATE) {
-      float m[VEC], v[VEC];
-      unpack16<T>(ld16(maskref + o), m);
-      unpack16<T>(ld16(y + o), v);
+      const u32x4 qm = ld16(maskref + o), qv = ld16(y + o);
+      float f[VEC], m[VEC], v[VEC];
+      unpack16<T>(q, f);
+      unpack16<T>(qm, m);
+      unpack16<T>(qv, v);
 #pragma unroll
       for (int j = 0; j < VEC; ++j)
         if (m[j] > 0.f) acc[j] += f[j] * (v[j] * sc[j] + sf[j]);
     } else {
+      float f[VEC];
+      unpack16<T>(q, f);
 #pragma unroll
       for (int j = 0; j < VEC; ++j) acc[j] += f[j];
     }
@@ -1247,12 +1335,12 @@ __global__ __launch_bounds__(EW_THREADS) void se_gate_bn_kernel(const T* __restr
     mu[j] = coef[2 * C + c0 + j];
     ag[j] = a1[j] = a2[j] = a3[j] = 0.f;
   }
-  for (int r = slice; r < R; r += nsl) {
-    const size_t o = ((size_t)n * R + r) * C + c0;
+  // one row: the three chunks at offset o, already loaded
+  auto row = [&](size_t o, const u32x4& qd, const u32x4& qm, const u32x4& qv) __attribute__((always_inline)) {
     float f[VEC], m[VEC], v[VEC];
-    unpack16<T>(ld16(dout + o), f);
-    unpack16<T>(ld16(maskref + o), m);
-    unpack16<T>(ld16(y + o), v);
+    unpack16<T>(qd, f);
+    unpack16<T>(qm, m);
+    unpack16<T>(qv, v);
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
       f[j] = m[j] > 0.f ? f[j] : 0.f;
@@ -1263,6 +1351,27 @@ __global__ __launch_bounds__(EW_THREADS) void se_gate_bn_kernel(const T* __restr
       a3[j] += yc;
     }
     st16(dz + o, pack16<T>(f));
+  };
+  // four rows in flight per thread, as in sample_reduce_kernel: the twelve loads of the group first, then the rows in order
+  // (one block per sample is 4 waves per CU at batch 256: with one row's loads in flight each, the pass ran at 3.1 TB/s)
+  int r = slice;
+  for (; r + 3 * nsl < R; r += 4 * nsl) {
+    u32x4 qd[4], qm[4], qv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const size_t o = ((size_t)n * R + r + u * nsl) * C + c0;
+      qd[u] = ld16(dout + o);
+      qm[u] = ld16(maskref + o);
+      qv[u] = ld16(y + o);
+    }
+    __builtin_amdgcn_sched_barrier(0);   // (else the scheduler sinks eight of the loads between the rows' stores)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) row(((size_t)n * R + r + u * nsl) * C + c0, qd[u], qm[u], qv[u]);
+  }
+  for (; r < R; r += nsl) {
+    const size_t o = ((size_t)n * R + r) * C + c0;
+    const u32x4 qd = ld16(dout + o), qm = ld16(maskref + o), qv = ld16(y + o);
+    row(o, qd, qm, qv);
   }
   float* const outs[4] = {dg, a1o, a2o, a3o};
 #pragma unroll
@@ -1879,7 +1988,7 @@ int ecg_bnrelu_maxpool(int dtype, const void* y, const float* coef, void* out, u
   if (!chunk_ok(C, dtype)) ECG_FAIL(ECGMM_ERR_SHAPE, "maxpool: C=%d unsupported", C);
   int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
   int vec = dtype == ECGMM_BF16 ? 8 : 4;
-  int grid = ew_grid((long)N * OH * OW * (C / vec), EW_THREADS);
+  int grid = ew_grid((long)N * OH * ((OW + 1) / 2) * (C / vec), EW_THREADS);   // a thread per pair of outputs
   DISPATCH_T(dtype,
              hipLaunchKernelGGL(bnrelu_maxpool_kernel<bf16_t>, dim3(grid), dim3(EW_THREADS), 0, stream,
                                 (const bf16_t*)y, coef, (bf16_t*)out, idx, N, H, W, C, OH, OW),

@@ -146,6 +146,7 @@ SIGNATURES = {
     "ecgmm_avgpool": (i32, [i32, vp, vp, i32, i32, i32, vp, vp]),
     "ecgmm_bcast_rows": (i32, [i32, vp, vp, i32, i32, i32, f32, vp]),
     "ecgmm_se_gate_grad": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "ecgmm_se_gate_bn": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "ecgmm_se_mlp_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "ecgmm_se_mlp_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp]),
     "ecgmm_linear_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
@@ -275,7 +276,9 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  "ecgmm_bn_bwd_dual", "ecgmm_bn_dual",
                  # the Transformer encoder (ecgmm.hip.nn.TransformerEncoder, csrc/attention.hip)
                  "ecgmm_mha_bwd_workspace", "ecgmm_mha_forward", "ecgmm_mha_backward", "ecgmm_mha_keep_mask",
-                 "ecgmm_embed1d_fwd", "ecgmm_embed1d_bwd_workspace", "ecgmm_embed1d_bwd")
+                 "ecgmm_embed1d_fwd", "ecgmm_embed1d_bwd_workspace", "ecgmm_embed1d_bwd",
+                 # the merged SE / BatchNorm backward's first pass, per op (csrc/elementwise.hip)
+                 "ecgmm_se_gate_bn")
 
 _lib = None
 

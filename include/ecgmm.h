@@ -452,6 +452,12 @@ int ecgmm_avgpool(int dtype, const void* x, float* out, int N, int R, int C, con
 int ecgmm_bcast_rows(int dtype, const float* v, void* out, int N, int R, int C, float scale, void* stream);
 int ecgmm_se_gate_grad(int dtype, const void* dout, const void* maskref, const void* y, const float* coef, float* dg,
                        int N, int R, int C, void* stream);
+/* the first pass of the merged SE / BatchNorm backward the ResNet1D_SE plan runs, per op: ONE read of dout, maskref and y
+ * [N][R][C] gives dz = [maskref > 0] * dout (stored, [N][R][C]), dg [N][C] (the sum of ecgmm_se_gate_grad) and the per-sample
+ * sums a1 = sum_r dz, a2 = sum_r dz * (y - mean), a3 = sum_r (y - mean), each [N][C] fp32; coef [4][C] as ecgmm_bn_finalize
+ * writes it. */
+int ecgmm_se_gate_bn(int dtype, const void* dout, const void* maskref, const void* y, const float* coef, void* dz, float* dg,
+                     float* a1, float* a2, float* a3, int N, int R, int C, void* stream);
 /* SEBlock.fc (PMB:35-46) on the pooled means m [N][C], fp32, one kernel forward and two backward (the kernels the ResNet1D_SE
  * and inference plans use, whatever ECGMM_SE_MLP_FUSED says): h [N][CR] = relu(m W1^T + b1), g [N][C] = sigmoid(h W2^T + b2),
  * w1 [CR][C], w2 [C][CR].  Backward: ds [N][C] = dg * g * (1 - g) and dh [N][CR] = (ds W2) * [h > 0] are caller-provided

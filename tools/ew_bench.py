@@ -3,12 +3,19 @@ a residual, full BatchNorm backward (reduce + finalize + apply) and the apply-fr
 move once; GB/s against the 6.29 TB/s a float4 copy reaches on this chip (MI355X_MICROARCH.md).
 The passes that fold the finalize (bn_act from rows, both backward forms) are timed with the channel-sliced launch off and on
 (ecgmm_bn_fold_slice) where it applies (C >= 256), alternating, in the same process.  At the output shapes of the three
-downsample blocks: bn2's + the shortcut BatchNorm's backward as separate calls against ecgmm_bn_bwd_dual, alternating."""
-import ctypes as C, os, sys
+downsample blocks: bn2's + the shortcut BatchNorm's backward as separate calls against ecgmm_bn_bwd_dual, alternating.
+The stem's fused BatchNorm + ReLU + max-pool at the image and the signal shape (bytes: y read once, pooled and argmax bytes
+written; the 2.25x window re-reads are cache traffic, not counted) and the SE gate pass ecgmm_se_gate_bn at the three widths of
+the signal encoder (three tensors read, dz written).
+--cases bn,pool,se picks the groups (default: all); ECGMM_LIB picks another build of the library for an A/B in one call."""
+import argparse, ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from ecgmm.hip import lib as L
 from ecgmm.hip.functional import ptr, stream
+ap = argparse.ArgumentParser()
+ap.add_argument("--cases", default="bn,pool,se")
+cases = ap.parse_args().cases.split(",")
 lib = L.lib()
 B = 256
 def timeit(fn, n=30):
@@ -20,7 +27,8 @@ def timeit(fn, n=30):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / n * 1e3
 flush = torch.empty(512 << 20, dtype=torch.uint8, device="cuda:0")
-for name, HW, Cn in (("l1", 56 * 56, 64), ("l2", 28 * 28, 128), ("l3", 14 * 14, 256), ("l4", 7 * 7, 512)):
+LAYERS = (("l1", 56 * 56, 64), ("l2", 28 * 28, 128), ("l3", 14 * 14, 256), ("l4", 7 * 7, 512))
+for name, HW, Cn in (LAYERS if "bn" in cases else ()):
     M = B * HW
     n = M * Cn
     mk = lambda: torch.randn(n, device="cuda:0").to(torch.bfloat16)
@@ -76,3 +84,46 @@ for name, HW, Cn in (("l1", 56 * 56, 64), ("l2", 28 * 28, 128), ("l3", 14 * 14, 
     for _ in range(2):
         show("bn2 + shortcut bn_bwd, separate", timeit(separate), 11)
         show("bn2 + shortcut bn_bwd, dual", timeit(dual), 9)
+
+def rotating(n_bytes_per_set):
+    return max(2, int(600e6 // n_bytes_per_set))
+bf = torch.bfloat16
+for name, H, W in ((("pool image", 112, 112), ("pool signal", 1, 2500)) if "pool" in cases else ()):
+    Cn = 64
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    n_in, n_out = B * H * W * Cn, B * OH * OW * Cn
+    K = rotating(n_in * 2 + n_out * 3)
+    ys = [torch.randn(n_in, device="cuda:0").to(bf) for _ in range(K)]
+    ps = [torch.empty(n_out, device="cuda:0", dtype=bf) for _ in range(K)]
+    ix = [torch.empty(n_out, device="cuda:0", dtype=torch.uint8) for _ in range(K)]
+    coef = torch.rand(4 * Cn, device="cuda:0") + 0.5
+    it = [0]
+    def pool():
+        it[0] = (it[0] + 1) % K
+        i = it[0]
+        return lib.ecgmm_bnrelu_maxpool(L.BF16, ptr(ys[i]), ptr(coef), ptr(ps[i]), ptr(ix[i]), B, H, W, Cn, stream())
+    nbytes = n_in * 2 + n_out * 3
+    for _ in range(2):
+        us = timeit(pool)
+        print(f"{name} {B} x {H} x {W} x {Cn} bnrelu_maxpool            {us:7.1f} us  {nbytes / us / 1e6:6.2f} TB/s ({nbytes / 1e6:.0f} MB, {K} buffer sets in rotation)")
+for R, Cn in (((1250, 64), (625, 128), (313, 256)) if "se" in cases else ()):
+    n = B * R * Cn
+    K = rotating(n * 2 * 4)
+    mk = lambda: torch.randn(n, device="cuda:0").to(bf)
+    ds, ms, ys, zs = [mk() for _ in range(K)], [mk() for _ in range(K)], [mk() for _ in range(K)], [torch.empty(n, device="cuda:0", dtype=bf) for _ in range(K)]
+    coef = torch.rand(4 * Cn, device="cuda:0") + 0.5
+    dg, a1, a2, a3 = (torch.empty(B * Cn, device="cuda:0") for _ in range(4))
+    it = [0]
+    def se():
+        it[0] = (it[0] + 1) % K
+        i = it[0]
+        return lib.ecgmm_se_gate_bn(L.BF16, ptr(ds[i]), ptr(ms[i]), ptr(ys[i]), ptr(coef), ptr(zs[i]), ptr(dg), ptr(a1), ptr(a2), ptr(a3), B, R, Cn, stream())
+    def gg():
+        it[0] = (it[0] + 1) % K
+        i = it[0]
+        return lib.ecgmm_se_gate_grad(L.BF16, ptr(ds[i]), ptr(ms[i]), ptr(ys[i]), ptr(coef), ptr(dg), B, R, Cn, stream())
+    for _ in range(2):
+        us = timeit(se)
+        print(f"se {B} x {R} x {Cn} se_gate_bn                          {us:7.1f} us  {4 * n * 2 / us / 1e6:6.2f} TB/s (4 x {n * 2 / 1e6:.0f} MB, {K} buffer sets in rotation)")
+        us = timeit(gg)
+        print(f"se {B} x {R} x {Cn} se_gate_grad                        {us:7.1f} us  {3 * n * 2 / us / 1e6:6.2f} TB/s (3 x {n * 2 / 1e6:.0f} MB, {K} buffer sets in rotation)")
