@@ -161,10 +161,15 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_res_relu_kernel(const T* y,
   }
 }
 
-inline bool chunk_ok(int C, int dtype, int threads) {
+// rows of whole 16-byte chunks: all relu_maxpool_kernel needs (it finds chunk and pixel of every element by division)
+inline bool vec_ok(int C, int dtype) {
   const int vec = dtype == ECGMM_BF16 ? 8 : 4;
-  if (C < vec || C % vec) return false;
-  const int cpr = C / vec;
+  return C >= vec && C % vec == 0;
+}
+// ... and a workgroup that is whole rows of them: gate_res_relu_kernel's threads keep one chunk each (rpi = threads / cpr)
+inline bool chunk_ok(int C, int dtype, int threads) {
+  if (!vec_ok(C, dtype)) return false;
+  const int cpr = C / (dtype == ECGMM_BF16 ? 8 : 4);
   return cpr <= threads && threads % cpr == 0;
 }
 
@@ -215,7 +220,7 @@ int ecg_relu_maxpool(int dtype, const void* y, void* out, int N, int H, int W, i
   if (dtype != ECGMM_BF16 && dtype != ECGMM_F32) ECG_FAIL(ECGMM_ERR_DTYPE, "relu_maxpool: bad dtype %d", dtype);
   if (!y || !out) ECG_FAIL(ECGMM_ERR_SHAPE, "relu_maxpool: null operand");
   if (N < 1 || H < 1 || W < 1) ECG_FAIL(ECGMM_ERR_SHAPE, "relu_maxpool: bad shape %d x %d x %d", N, H, W);
-  if (!chunk_ok(C, dtype, 256)) ECG_FAIL(ECGMM_ERR_SHAPE, "relu_maxpool: C=%d unsupported", C);
+  if (!vec_ok(C, dtype)) ECG_FAIL(ECGMM_ERR_SHAPE, "relu_maxpool: C=%d unsupported", C);
   const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
   const int vec = dtype == ECGMM_BF16 ? 8 : 4;
   long blocks = ((long)N * OH * OW * (C / vec) + 255) / 256;

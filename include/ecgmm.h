@@ -646,7 +646,7 @@ int ecgmm_fold_conv_bn(int dtype, int layout, const float* w, const float* conv_
                        const float* running_mean, const float* running_var, float eps, void* w_out, float* b_out,
                        float* scale_out, int Cout, int Cin, int RS, void* stream);
 /* nn.ReLU + nn.MaxPool2d(3, 2, 1) (torchvision resnet stem) / nn.MaxPool1d(3, 2, 1) (PMB:103, H = 1) of a channels-last
- * tensor: ecgmm_bnrelu_maxpool without coefficients and without the argmax bytes. */
+ * tensor: ecgmm_bnrelu_maxpool without coefficients and without the argmax bytes.  C: any multiple of 8 (bf16) / 4 (fp32). */
 int ecgmm_relu_maxpool(int dtype, const void* y, void* out, int N, int H, int W, int C, void* stream);
 /* out = relu(y * gate[row / rows_per_sample][c] + res): `out = self.se(out); out += identity; out = self.relu(out)`,
  * PMB:88-92, with bn2 already folded into y.  out may be y. */

@@ -1,6 +1,7 @@
 """Float64 checkers: the bf16 conv kernels (below), the BatchNorm / pooling passes, the fp32 dense tails, the LSTM
-recurrence, the TabNet clinical branch, the ops that run only inside the encoder launch plans and the fp32-operand conv
-kernels (their own sections further down, each with its bounds derived in a header comment).
+recurrence, the TabNet clinical branch, the ops that run only inside the encoder launch plans, the fp32-operand conv
+kernels and the two elementwise passes of the inference plans (their own sections further down, each with its bounds
+derived in a header comment).
 
 
 With the operands rounded to bf16, every product x * w is exact in float64 and so is any sum of a few million of them to
@@ -44,9 +45,12 @@ DW_REL_L2 = 1e-5
 
 
 def half_ulp_bf16(v):
-    """half an ulp of the bf16 binade |v| lies in (0 where v == 0): 2^(e - 9) for |v| = m * 2^e, m in [0.5, 1)"""
+    """half an ulp of the bf16 binade |v| lies in (0 where v == 0): 2^(e - 9) for |v| = m * 2^e, m in [0.5, 1).
+    Below the smallest normal number 2^-126 bf16 is evenly spaced by 2^-133 (its subnormals share fp32's exponent range), so
+    the half ulp stays at 2^-134 there.  (Found by tests/test_infer_chain_gpu.py: a squeeze-excite gate that saturates to a
+    subnormal fp32 value gives a subnormal product, which the device rounds to the nearest bf16 subnormal as torch does.)"""
     v = v.abs().double()
-    e = torch.frexp(v).exponent
+    e = torch.frexp(v).exponent.clamp_min(-125)
     return torch.where(v > 0, torch.ldexp(torch.ones_like(v), e - 9), torch.zeros_like(v))
 
 
@@ -1914,3 +1918,78 @@ def check_stats_f32(rows, ref, K, chain=STATS_CHAIN_F32, kappa=KAPPA_F32, name="
     c = check_colsums(rows[:, 1].sum(0), (y * y).sum(dims), (2 * y.abs() * b + b * b).sum(dims), (y * y).sum(dims),
                       sigma=g_k(chain + 1), name=name + " sum y^2")
     return max(a.ratio, c.ratio)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The two elementwise passes only the inference plans run (csrc/infer_fold.hip), tensors channels-last.
+#
+#   relu_maxpool:   out = max(0, max over the in-image taps of the 3x3 / stride 2 / pad 1 window), H may be 1.  The kernel only
+#                   compares stored values and writes one of them, or 0, so the float64 window maximum of the STORED input,
+#                   clamped at 0, is the answer and the bar is exact equality.  No output carries a sign bit (a window of
+#                   -0.0 or of negative values gives +0) and a NaN tap never wins: it is skipped like a tap outside the image.
+#   gate_res_relu:  out = max(0, y * gate[row // rows_per_sample] + res), A = |y| |gate| + |res|: a product and a sum, two
+#                   roundings of A at most whether or not the compiler contracts them -- fp32 check_f32 with K = 2 summands
+#                   (g_k(4), below KAPPA_F32), bf16 the one-sided ReLU bound of tests/infer_ref.py with KAPPA unchanged (2 u
+#                   is 1.2e-7 of A).  Nothing is calibrated.
+# ----------------------------------------------------------------------------------------------------------------------
+def relu_maxpool_ref(y):
+    """y [N][H][W][C] as stored (any float dtype) -> float64 [N][OH][OW][C]: max(0, window maximum), NaN taps skipped"""
+    y = y.double()
+    N, H, W, C = y.shape
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    p = torch.full((N, 2 * OH + 1, 2 * OW + 1, C), float("-inf"), dtype=torch.float64, device=y.device)
+    p[:, 1:H + 1, 1:W + 1] = torch.where(torch.isnan(y), torch.full_like(y, float("-inf")), y)
+    ref = torch.zeros((N, OH, OW, C), dtype=torch.float64, device=y.device)
+    for kh in range(3):
+        for kw in range(3):
+            ref = torch.maximum(ref, p[:, kh:kh + 2 * OH:2, kw:kw + 2 * OW:2])
+    return ref
+
+
+def relu_maxpool_ratio(out, y_stored, N, H, W, C, bf16, name="relu_maxpool"):
+    """out [N][OH][OW][C] (or flat) as the kernel stored it against relu_maxpool_ref of the stored input: ratio 0 where
+    every element is the reference exactly, is finite and has no sign bit; inf otherwise.  .bad counts the elements"""
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    want = torch.bfloat16 if bf16 else torch.float32
+    assert out.dtype == want and y_stored.dtype == want, "%s: tensors are not in the stored type" % name
+    ref = relu_maxpool_ref(y_stored.reshape(N, H, W, C))
+    got = out.reshape(N, OH, OW, C).double()
+    bad = ~(got == ref) | torch.signbit(got)
+    r = Report(name, 0.0, ())
+    r.bad = int(bad.sum())
+    if r.bad:
+        r.ratio, r.where = float("inf"), _unravel(int(torch.argmax(bad.reshape(-1).to(torch.uint8))), ref.shape)
+    return r
+
+
+def check_relu_maxpool(out, y_stored, N, H, W, C, bf16, name="relu_maxpool"):
+    r = relu_maxpool_ratio(out, y_stored, N, H, W, C, bf16, name)
+    print(r, "%d elements differ" % r.bad)
+    assert r.ok, "%s: %d elements are not max(0, window maximum) of the stored input, first at %s" % (name, r.bad, r.where)
+    return r
+
+
+def gate_res_relu_ref(y, gate, res, rows_per_sample):
+    """y, res [M][C] as stored, gate [N][C] fp32 -> (the float64 value BEFORE the ReLU, A)"""
+    y, res = y.double(), res.double()
+    g = per_row(gate, rows_per_sample, y.shape[0])
+    return y * g + res, y.abs() * g.abs() + res.abs()
+
+
+def gate_res_relu_ratio(out, y, gate, res, rows_per_sample, bf16, name="gate_res_relu"):
+    pre, A = gate_res_relu_ref(y, gate, res, rows_per_sample)
+    out = out.reshape(pre.shape)
+    if bf16:
+        from .infer_ref import relu_bf16_ratio      # (infer_ref imports this module)
+        return relu_bf16_ratio(out, pre, A, name=name)
+    assert bool((out.double() >= 0).all()), name + ": negative value after ReLU"
+    return f32_ratio(out, pre.clamp_min(0), A, 2, name=name)
+
+
+def check_gate_res_relu(out, y, gate, res, rows_per_sample, bf16, name="gate_res_relu"):
+    """(out >= 0 rejects NaN as well)"""
+    r = gate_res_relu_ratio(out, y, gate, res, rows_per_sample, bf16, name)
+    print(r)
+    assert torch.isfinite(out.double()).all(), name + ": non-finite output"
+    assert r.ok, str(r)
+    return r

@@ -62,6 +62,13 @@ def test_half_ulp():
     # every fp32 -> bf16 rounding stays within it (what a kernel's epilogue does)
     t = torch.randn(100000, generator=torch.Generator().manual_seed(1)) * 100
     assert ((t.to(torch.bfloat16).double() - t.double()).abs() <= F64.half_ulp_bf16(t)).all()
+    # ... also below 2^-126, where bf16 is evenly spaced by 2^-133: the binade rule alone (2^(e - 9)) is too small there
+    s = torch.rand(100000, generator=torch.Generator().manual_seed(2), dtype=torch.float64) * 2.0 ** -126
+    s32 = s.float()
+    assert bool((s32 > 0).any()) and F64.half_ulp_bf16(torch.tensor([2.0 ** -126, 2.0 ** -130, 2.0 ** -140], dtype=torch.float64)).tolist() == [2.0 ** -134] * 3
+    err = (s32.to(torch.bfloat16).double() - s32.double()).abs()
+    assert (err <= F64.half_ulp_bf16(s32)).all()
+    assert (err > torch.ldexp(torch.ones_like(s), torch.frexp(s32.double()).exponent - 9)).any()
 
 
 def test_accepts_the_exact_answer_rounded_and_torch_fp32(case):
@@ -1360,3 +1367,119 @@ def test_fp32_conv_checker_rejects_weight_gradient_split_defects(case32_dw):
     m = ref.dw.float().clone()
     m[5, 7, 1, 1] = float("nan")
     assert not F64.dw_f32_ratio(m, ref.dw, ref.adw, DW32_PIXELS).ok
+
+
+# ---- the two passes of the inference plans (csrc/infer_fold.hip): relu_maxpool, gate_res_relu ----
+def _pool_emul(y, shift=0, flat_pad=False, clamp=True):
+    """relu_maxpool_kernel restated in torch on the stored type: best = 0 (or -inf: no ReLU); best = f > best ? f : best over
+    the in-image taps.  shift: the window starts at 2 * o - 1 + shift; flat_pad: no bounds check on the column, so a tap
+    outside the row reads its neighbour in memory (the previous row's last pixel, the next row's first)"""
+    N, H, W, C = y.shape
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    flat = y.float().reshape(N * H * W, C)
+    n = torch.arange(N).view(N, 1, 1)
+    oh, ow = torch.arange(OH).view(1, OH, 1), torch.arange(OW).view(1, 1, OW)
+    best = torch.full((N, OH, OW, C), 0.0 if clamp else float("-inf"))
+    for kh in range(3):
+        for kw in range(3):
+            h, w = oh * 2 - 1 + shift + kh, ow * 2 - 1 + shift + kw
+            inside = (h >= 0) & (h < H) & ((w >= 0) & (w < W) if not flat_pad else torch.ones_like(w, dtype=torch.bool))
+            idx = ((n * H + h) * W + w).expand(N, OH, OW)
+            inside = (inside & (idx >= 0) & (idx < N * H * W)).expand(N, OH, OW)
+            f = flat[idx.clamp(0, N * H * W - 1)]
+            take = inside.unsqueeze(3) & (f > best)
+            best = torch.where(take, f, best)
+    return best.to(y.dtype)
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("shape", [(2, 7, 9, 8), (1, 8, 8, 16), (1, 1, 37, 8), (3, 1, 2, 8), (1, 1, 1, 8), (2, 2, 1, 8)])
+def test_relu_maxpool_checker_accepts_the_kernel_restated_in_torch(shape, bf16):
+    N, H, W, C = shape
+    dt = torch.bfloat16 if bf16 else torch.float32
+    y = _fill.hash_tensor(shape, 1201, 2.0).to(dt)
+    F64.check_relu_maxpool(_pool_emul(y), y, N, H, W, C, bf16)
+    neg = -y.abs()
+    neg[0, 0, 0, :4] = -0.0
+    out = _pool_emul(neg)
+    assert not bool(torch.signbit(out).any()) and not bool(out.any())
+    F64.check_relu_maxpool(out, neg, N, H, W, C, bf16, "all negative")
+    nan = y.clone()
+    nan[0, H // 2, W // 2, 3] = float("nan")
+    F64.check_relu_maxpool(_pool_emul(nan), nan, N, H, W, C, bf16, "one NaN tap")
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["fp32", "bf16"])
+def test_relu_maxpool_checker_rejects_each_defect(bf16):
+    N, H, W, C = 2, 7, 9, 8
+    dt = torch.bfloat16 if bf16 else torch.float32
+    y = _fill.hash_tensor((N, H, W, C), 1202, 2.0).to(dt)
+    good = _pool_emul(y)
+    assert F64.relu_maxpool_ratio(good, y, N, H, W, C, bf16).ok
+    minus0 = good.clone()
+    minus0[good == 0] = -0.0
+    assert bool((good == 0).any())
+    nan = y.clone()
+    nan[1, 3, 4, 2] = float("nan")
+    wins = _pool_emul(nan).clone()
+    wins[1, 2, 2, 2] = float("nan")
+    for name, bad, src in (("window shifted by one", _pool_emul(y, shift=1), y),
+                           ("padding read as the neighbour in memory", _pool_emul(y, flat_pad=True), y),
+                           ("ReLU omitted", _pool_emul(y, clamp=False), y),
+                           ("-0 stored", minus0, y), ("a NaN tap wins", wins, nan),
+                           ("every element one ulp up", torch.nextafter(good.float(), torch.tensor(9.0)).to(dt) if not bf16
+                            else (good.view(torch.int16) + (good > 0).to(torch.int16)).view(dt), y)):
+        r = F64.relu_maxpool_ratio(bad, src, N, H, W, C, bf16, name)
+        print(r, r.bad)
+        assert not r.ok, "checker accepted: " + name
+    with pytest.raises(AssertionError):
+        F64.check_relu_maxpool(_pool_emul(y, shift=1), y, N, H, W, C, bf16)
+
+
+def _gate_case(bf16):
+    N, rps, C = 3, 13, 16
+    dt = torch.bfloat16 if bf16 else torch.float32
+    h = _fill.hash_tensor
+    y, res = h((N * rps, C), 1203, 2.0).to(dt), h((N * rps, C), 1204, 1.5).to(dt)
+    gate = 0.5 + 0.6 * h((N, C), 1205)
+    gate[0, 1], gate[2, 0] = 0.0, -0.75
+    return y, gate, res, rps, dt
+
+
+def _gate_emul(y, gate, res, rps, dt, row_off=0, relu=True, use_res=True, fused=False):
+    """gate_res_relu_kernel restated in torch: fp32 arithmetic on the stored operands (fused: the product not rounded),
+    rounded once to the stored type.  row_off: the gate row is (r + row_off) // rps"""
+    M = y.shape[0]
+    row = ((torch.arange(M) + row_off) // rps).clamp(0, gate.shape[0] - 1)
+    g = gate[row]
+    r = res.float() if use_res else torch.zeros_like(res.float())
+    v = (y.double() * g.double() + r.double()).float() if fused else y.float() * g + r
+    return (v.clamp_min(0) if relu else v).to(dt)
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["fp32", "bf16"])
+def test_gate_res_relu_checker_accepts_torch_and_rejects_each_defect(bf16):
+    y, gate, res, rps, dt = _gate_case(bf16)
+    for fused in (False, True):
+        F64.check_gate_res_relu(_gate_emul(y, gate, res, rps, dt, fused=fused), y, gate, res, rps, bf16)
+
+    def rejected(out):
+        try:
+            return not F64.gate_res_relu_ratio(out, y, gate, res, rps, bf16).ok
+        except AssertionError:      # (a negative value after the ReLU)
+            return True
+    good = _gate_emul(y, gate, res, rps, dt)
+    assert not rejected(good)
+    for name, bad in (("gate row of the next sample at the boundary", _gate_emul(y, gate, res, rps, dt, row_off=1)),
+                      ("gate row of the previous sample at the boundary", _gate_emul(y, gate, res, rps, dt, row_off=-1)),
+                      ("ReLU omitted", _gate_emul(y, gate, res, rps, dt, relu=False)),
+                      ("res dropped", _gate_emul(y, gate, res, rps, dt, use_res=False))):
+        assert rejected(bad), "checker accepted: " + name
+    # only the rows at a rows_per_sample boundary differ in the first two: the checker must see a single row
+    one = good.clone()
+    one[rps - 1] = _gate_emul(y, gate, res, rps, dt, row_off=1)[rps - 1]
+    assert rejected(one), "checker accepted one boundary row gated by its neighbour"
+    nan = good.clone()
+    nan[5, 3] = float("nan")
+    with pytest.raises(AssertionError):
+        F64.check_gate_res_relu(nan, y, gate, res, rps, bf16)

@@ -3,7 +3,12 @@ at the step's layer shapes, the encoders through ``ecgmm.inference.Predictor`` a
 behaviour (batch independence, determinism, no side effects, stale weights, workspace) and the callers.
 
 Tolerances are those of the tests of the eval path being shadowed (tests/test_models_gpu.py, tests/test_ops_gpu.py,
-tests/f64check.py); the new constants FOLD_F32_REL / FOLD_F32_BIAS_REL are calibrated below by the rule of tests/f64check.py."""
+tests/f64check.py); the new constants FOLD_F32_REL / FOLD_F32_BIAS_REL are calibrated below by the rule of tests/f64check.py.
+
+Not here but in tests/test_infer_chain_gpu.py: ecgmm_relu_maxpool and ecgmm_gate_res_relu element by element, every op of
+both plans against float64 at ragged shapes (odd extents, 999-sample records, N = 3, the smallest input), and the plans'
+features bit for bit against the same network built from the per-op entry points (tests/infer_chain.py).  Cases of that
+kind belong there."""
 import ctypes as C
 
 import numpy as np
