@@ -87,7 +87,11 @@ __global__ void axpby_kernel(float a, const float* __restrict__ x, float b, floa
 // LayerNorm (+ optional attention-fusion scale/concat in front of it).  One wave per row.
 // Inputs: up to 3 segments src[m][B][dims[m]] each scaled by sw[m] (sw == null -> one segment, scale 1)
 // ------------------------------------------------------------------------------------------------
-constexpr int LN_MAXD = 1024;  // 16 values per lane
+// NK values per lane: 16 (rows up to 1024 wide) everywhere but the concatenation of three 512-wide branches, the widest the
+// head admits (ecg_head_fused_ok), which its per-op form (ECGMM_HEAD_FUSED=0, or a batch the row kernels refuse) normalises
+// here: 24
+constexpr int LN_MAXD = 1536;
+constexpr int ln_nk(int D) { return D <= 1024 ? 16 : 24; }
 
 struct LnParams {
   const float* seg[3];
@@ -120,6 +124,7 @@ __device__ __forceinline__ float seg_load(const LnParams& p, const float* sw, in
   return sw ? v * sw[m] : v;
 }
 
+template <int NK>
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(LnParams p) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -131,10 +136,10 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(LnParams p) {
     if (p.soft_w && blockIdx.x == 0 && threadIdx.x < 3) p.soft_w[threadIdx.x] = swv[threadIdx.x];
   }
   if (row >= p.B) return;
-  float v[LN_MAXD / 64];
+  float v[NK];
   float s = 0.f;
 #pragma unroll
-  for (int k = 0; k < LN_MAXD / 64; ++k) {
+  for (int k = 0; k < NK; ++k) {
     int c = lane + 64 * k;
     v[k] = c < p.D ? seg_load(p, sw, row, c) : 0.f;
     s += v[k];
@@ -142,14 +147,14 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(LnParams p) {
   float mean = wave_sum(s) / (float)p.D;
   float q = 0.f;
 #pragma unroll
-  for (int k = 0; k < LN_MAXD / 64; ++k) {
+  for (int k = 0; k < NK; ++k) {
     int c = lane + 64 * k;
     float d = c < p.D ? v[k] - mean : 0.f;
     q += d * d;
   }
   float rstd = rsqrtf(wave_sum(q) / (float)p.D + p.eps);
 #pragma unroll
-  for (int k = 0; k < LN_MAXD / 64; ++k) {
+  for (int k = 0; k < NK; ++k) {
     int c = lane + 64 * k;
     if (c < p.D) p.out[(size_t)row * p.D + c] = (v[k] - mean) * rstd * p.gamma[c] + p.beta[c];
   }
@@ -167,9 +172,10 @@ struct LnBwdParams {
   float* partial;        // [grid][2*D + 4]: dgamma, dbeta, dwraw[3] (+pad)
 };
 
+template <int NK>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(LnBwdParams q) {
   const LnParams& p = q.f;
-  __shared__ float sh[4][2 * LN_MAXD + 4];
+  __shared__ float sh[4][2 * 64 * NK + 4];   // (NK = 24: 49 KB)
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   float swv[3];
   const float* sw = nullptr;
@@ -177,15 +183,15 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(LnBwdParams q) {
     softmax3(p.fusion_w, swv);
     sw = swv;
   }
-  float ag[LN_MAXD / 64], ab[LN_MAXD / 64], aw[3] = {0.f, 0.f, 0.f};
+  float ag[NK], ab[NK], aw[3] = {0.f, 0.f, 0.f};
 #pragma unroll
-  for (int k = 0; k < LN_MAXD / 64; ++k) ag[k] = ab[k] = 0.f;
+  for (int k = 0; k < NK; ++k) ag[k] = ab[k] = 0.f;
   for (int row = blockIdx.x * 4 + wv; row < p.B; row += gridDim.x * 4) {
     float mean = p.stat[2 * row], rstd = p.stat[2 * row + 1];
-    float xh[LN_MAXD / 64], dg[LN_MAXD / 64];
+    float xh[NK], dg[NK];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-    for (int k = 0; k < LN_MAXD / 64; ++k) {
+    for (int k = 0; k < NK; ++k) {
       int c = lane + 64 * k;
       if (c < p.D) {
         xh[k] = (seg_load(p, sw, row, c) - mean) * rstd;
@@ -202,7 +208,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(LnBwdParams q) {
     s1 = wave_sum(s1) / (float)p.D;
     s2 = wave_sum(s2) / (float)p.D;
 #pragma unroll
-    for (int k = 0; k < LN_MAXD / 64; ++k) {
+    for (int k = 0; k < NK; ++k) {
       int c = lane + 64 * k;
       if (c >= p.D) continue;
       float dx = rstd * (dg[k] - s1 - xh[k] * s2);  // grad wrt the (scaled) concat element
@@ -223,7 +229,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(LnBwdParams q) {
     }
   }
 #pragma unroll
-  for (int k = 0; k < LN_MAXD / 64; ++k) {
+  for (int k = 0; k < NK; ++k) {
     int c = lane + 64 * k;
     if (c < p.D) {
       sh[wv][c] = ag[k];
@@ -518,7 +524,8 @@ int ecg_layernorm_fwd(const float* const* seg, const int* dims, int nseg, const 
                       const float* beta, float* out, float* stat, float* soft_w, int B, float eps, hipStream_t s) {
   LnParams p;
   ECG_TRY(fill_ln(p, seg, dims, nseg, fusion_w, gamma, beta, out, stat, soft_w, B, eps));
-  hipLaunchKernelGGL(layernorm_fwd_kernel, dim3(ceil_div(B, 4)), dim3(256), 0, s, p);
+  if (ln_nk(p.D) == 16) hipLaunchKernelGGL(layernorm_fwd_kernel<16>, dim3(ceil_div(B, 4)), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(layernorm_fwd_kernel<24>, dim3(ceil_div(B, 4)), dim3(256), 0, s, p);
   ECG_CHECK_LAUNCH("layernorm_fwd");
   return 0;
 }
@@ -540,7 +547,8 @@ int ecg_layernorm_bwd(const float* const* seg, const int* dims, int nseg, const 
   q.dseg_accumulate = dseg_accumulate;
   q.partial = scratch;
   int grid = ln_bwd_grid(B);
-  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(grid), dim3(256), 0, s, q);
+  if (ln_nk(q.f.D) == 16) hipLaunchKernelGGL(layernorm_bwd_kernel<16>, dim3(grid), dim3(256), 0, s, q);
+  else hipLaunchKernelGGL(layernorm_bwd_kernel<24>, dim3(grid), dim3(256), 0, s, q);
   ECG_CHECK_LAUNCH("layernorm_bwd");
   hipLaunchKernelGGL(layernorm_bwd_finalize_kernel, dim3(ceil_div(2 * q.f.D, 256)), dim3(256), 0, s, scratch, grid,
                      q.f.D, dgamma, dbeta, fusion_w, dfusion_w);

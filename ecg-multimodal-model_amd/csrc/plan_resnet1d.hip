@@ -87,10 +87,10 @@ void layout_bwd(const Net1D& r, void* base, Bwd1& w, WsTable* views = nullptr) {
   w.dh = a.take<float>((size_t)N * 16, "dh");
   w.dm = a.take<float>((size_t)N * 256, "dm");
   w.dbias_scratch = a.take<float>(256);
-  w.sa1 = a.take<float>((size_t)N * 256);
-  w.sa2 = a.take<float>((size_t)N * 256);
-  w.sa3 = a.take<float>((size_t)N * 256);
-  w.se_rows = a.take<float>((size_t)ecg_se_bn_nrows() * 2 * 256);
+  w.sa1 = a.take<float>((size_t)N * 256, "sa1");   // (named: only the merged form writes these four, which is how a test
+  w.sa2 = a.take<float>((size_t)N * 256, "sa2");   //  started with ECGMM_SE_MERGE=0 sees that the two-pass form ran)
+  w.sa3 = a.take<float>((size_t)N * 256, "sa3");
+  w.se_rows = a.take<float>((size_t)ecg_se_bn_nrows() * 2 * 256, "se_rows");
   size_t bn = ecg_bn_bwd_scratch(r.d.dtype, (long)N * r.L1, 64);
   size_t wg = 0;
   size_t lin = ecg_linear_bwd_scratch(N, 256, 64);

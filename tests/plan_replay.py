@@ -61,11 +61,17 @@ class Blk:
 class Net:
     """kind "r18": ResNet18 on [N, 3, H, W];  kind "r1d": ResNet1D_SE on [N, cin, L] (H = 1, W = L).
     fused2: the blocks whose bn2 reduction was fused into the next block's conv1 input gradient (ResNet18 with
-    ECGMM_BN_FUSE_MIN_M below their pixel count): their dcur arrives masked and dz is never written."""
+    ECGMM_BN_FUSE_MIN_M below their pixel count): their dcur arrives masked and dz is never written.
+    What the plan was started with is the caller's to say (this module does not import the library):
+    bits: the forward stored the ReLU mask of every `out` as bits (None: a ResNet18 bf16 training plan does, ECGMM_RELU_BITS
+    on); stem_fused: the training stem backward ran as one pool + BatchNorm pass (ECGMM_STEM_FUSE on), else as max-pool
+    backward into big0 and a BatchNorm backward from there, as the eval form always does."""
 
-    def __init__(self, kind, N, cin, H, W, bf16, training=True, eps=1e-5, momentum=0.1, dropout_p=0.0, fused2=()):
+    def __init__(self, kind, N, cin, H, W, bf16, training=True, eps=1e-5, momentum=0.1, dropout_p=0.0, fused2=(), bits=None,
+                 stem_fused=True):
         self.kind, self.N, self.cin, self.H, self.W, self.bf16, self.training = kind, N, cin, H, W, bf16, training
         self.eps, self.momentum, self.dropout_p, self.fused2 = eps, momentum, dropout_p, set(fused2)
+        self.stem_fused = bool(stem_fused)
         self.se = kind == "r1d"
         self.kh = 3 if kind == "r18" else 1
         self.pad = (self.kh // 2, 1)
@@ -77,7 +83,7 @@ class Net:
         if kind == "r18":
             self.stem_w, self.stem_b, self.stem_bn = "conv1.weight", None, "bn1"
             spec = [("layer%d.%d." % (l + 1, b), 64 << l, 2 if (b == 0 and l > 0) else 1) for l in range(4) for b in range(2)]
-            self.bits = bf16 and training
+            self.bits = bool(bf16 and training) if bits is None else bool(bits)
             self.feat_c = 512
         else:
             self.stem_w, self.stem_b, self.stem_bn = "initial.0.weight", "initial.0.bias", "initial.1"
@@ -103,10 +109,12 @@ class Net:
 
 
 class Rep:
-    """worst ratio per op class, for the docstring figures (print with show())"""
+    """worst ratio per op class, for the docstring figures (print with show()), and which branch of the replay the stored
+    data selected (paths: "blk3 din" -> "folded" / "dtmp", "stem bwd" -> "one pass" / "two passes")"""
 
     def __init__(self):
         self.worst = {}
+        self.paths = {}
 
     def __call__(self, cls, r):
         for v in (r.values() if isinstance(r, dict) else [r]):
@@ -358,9 +366,11 @@ def replay_backward_stage(net, T, S, G, P, x, dfeat, st, dx=None, rep=None):
             rep("dw", _chk_dw(net, G[nm["cd"]], rd.dw, rd.adw, M, tag + "dwd"))
             dtmp = act(S["dtmp"], N, k.cin, k.hin, k.win)
             if bool(torch.isnan(dtmp).all()):      # the fold ran: one rounding of the sum of both input gradients
+                rep.paths[tag + "din"] = "folded"
                 r1 = F.conv_ref64(inp, w1, dy1, stride=k.stride, padding=net.pad)
                 want, A, Kx = r1.dx + rd.dx, r1.adx + rd.adx, Kx + k.cout + 1
             else:                                   # two roundings, through dtmp
+                rep.paths[tag + "din"] = "dtmp"
                 rep("dgrad", _chk_conv(net, dtmp, rd.dx, rd.adx, k.cout, tag + "dtmp"))
                 r1 = F.conv_ref64(inp, w1, dy1, stride=k.stride, padding=net.pad, addend=dtmp)
                 want, A = r1.dx, r1.adx
@@ -386,7 +396,10 @@ def replay_backward_stage(net, T, S, G, P, x, dfeat, st, dx=None, rep=None):
     big1 = cl(big1n)
     assert torch.isfinite(big1).all() and torch.isfinite(dgam).all() and torch.isfinite(dbet).all(), "stem bwd: non-finite values"
     dbias = None if net.stem_b is None else G[net.stem_b]
-    if net.training:
+    big0 = cl(act(S["big0"], N, 64, H1, W1))
+    if net.training and net.stem_fused:
+        rep.paths["stem bwd"] = "one pass"
+        assert bool(torch.isnan(big0).all()), "stem big0: written although the stem backward ran as one pass"
         (s1, s2), (m1, m2) = F.pool_red_ref(dp0, p0, c0)
         rep("stem_bwd", F.check_sum(dbet, s1, m1, MP + 1, "stem pool_bn_bwd dbeta"))
         rep("stem_bwd", F.check_sum(dgam, s2, m2, F.K_POOL_RED + MP + 1, "stem pool_bn_bwd dgamma"))
@@ -398,7 +411,10 @@ def replay_backward_stage(net, T, S, G, P, x, dfeat, st, dx=None, rep=None):
             s = big1.double().reshape(-1, 64)
             rep("stem_bwd", F.check_sum(dbias, s.sum(0), s.abs().sum(0), M + 1, "stem pool_bn_bwd dbias"))
     else:
-        big0 = cl(act(S["big0"], N, 64, H1, W1))
+        # two passes: the max-pool + ReLU backward into big0, then the BatchNorm backward of the plan's mode from the stored
+        # big0 (training: the full form with its two sums; eval: the affine form), the 1-D stem conv's dbias from big1
+        rep.paths["stem bwd"] = "two passes"
+        assert torch.isfinite(big0).all(), "stem maxpool bwd big0: non-finite values"
         rep("stem_bwd", F.check_pool_bwd(big0, dp0, p0, idx0, bf, "stem maxpool bwd big0"))
         rep("bn_bwd", _bn_bwd(net, big0.reshape(-1, 64), y0.reshape(-1, 64), c0, gam, dgam, dbet, big1.reshape(-1, 64), "stem bn bwd",
                               dbias=dbias))

@@ -399,6 +399,13 @@ def test_c_halo_limit_table():
 # of 3 or 9 taps (1 with ECGMM_WGRAD_GROUPS=1, for 1x1 filters and for fp32); steps_per_split = ceil(steps / ns); split i takes
 # steps [i * sps, (i + 1) * sps) cut at `steps`, so trailing splits are short or empty -- and must still write zeros to
 # their slab, which the reduce kernel sums.  The workspace is sized for groups = 1.
+# A process started with ECGMM_WGRAD_WGS=6 (leg halo_generic_wgs6 of tests/startup_legs.py) has 6 slots in place of the 512:
+# ns = min(steps, ceil(6 / groups / tiles)), geometries the default never produces.  bf16 with one channel tile: ns = 3, several
+# steps per split (empty_splits 3 x 100, partial_last_step 4 + 4 + 2, 15_steps 3 x 5, ring_w63 3 x 42, ring_w64_refused 43 + 43 +
+# 42; w3_ring_refused has one step: ns = 1).  fp32 with one channel tile: ns = 6 (600 / 30 / 252 steps in splits of 100 / 5 / 42;
+# partial_last_step 19 steps as 4 x 4 + 3 and one EMPTY split; ring_w64_refused 256 as 5 x 43 + 41; w3_ring_refused 2 steps, ns = 2).  Two tiles (partial_channel_tiles, stride2): bf16
+# ns = 2 (2 + 1 and 3 + 3 steps), fp32 ns = 3 (2 + 2 + 1 and 4 + 4 + 3).  odd_steps_two_groups (16 tiles) and 1x1_stride2, 1x3_130
+# (8 tiles each): ns = 1, a single split over 48, 2 and 13 steps (fp32: 96, 4 and 25) -- the slab is the result.
 D_CASES = {
     # M = 9600.  bf16: 300 steps, ns = 256, sps = 2: 150 splits of 2 steps (one per group), 106 EMPTY.  groups = 1: ns = 300.
     # fp32: 600 steps, ns = 512, sps = 2: 300 used, 212 empty

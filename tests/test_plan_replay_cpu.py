@@ -304,7 +304,7 @@ def build(net, model, x, dfeat, slip=None, fold=True):
     M = N * H1 * W1
     gam = P[net.stem_bn + ".weight"]
     c0 = T["coef0"]
-    if net.training:
+    if net.training and net.stem_fused:
         g_ = torch.where(p0 > 0, dX, torch.zeros_like(dX))
         dbet = g_.sum((0, 2, 3))
         rsc = torch.where(c0[0] != 0, 1.0 / c0[0], torch.zeros_like(c0[0]))
@@ -313,13 +313,24 @@ def build(net, model, x, dfeat, slip=None, fold=True):
         xh = (y0 - _ch(c0[2])) * _ch(c0[3])
         big1 = st_(_ch(gam * c0[3]) * (dz0 - _ch(dbet / M) - xh * _ch(dgam / M)))
     else:
+        # two passes (eval, or training without the fused pass): max-pool backward into big0, BatchNorm backward of the mode
         big0 = st_(_unpool(dX, p0, idx0, H1, W1))
+        if slip == "big0_tap":                  # the largest element lands one column beside the tap idx0 names
+            n_, c_, h_, w_ = PR.F._unravel(int(big0.abs().argmax()), big0.shape)
+            w2_ = w_ + 1 if w_ + 1 < W1 else w_ - 1
+            big0[n_, c_, h_, w2_] += big0[n_, c_, h_, w_]
+            big0[n_, c_, h_, w_] = 0
         put(S["big0"], big0)
         big1, dgam, dbet = _bn_bwd(net, big0, y0, c0, gam)
+        if slip == "big1_affine":               # the eval formula behind a training forward
+            big1 = big0 * _ch(c0[0])
         big1 = st_(big1)
     G[net.stem_bn + ".weight"], G[net.stem_bn + ".bias"] = dgam, dbet
     if net.stem_b is not None:
         G[net.stem_b] = big1.sum((0, 2, 3))
+        if slip == "dbias_short":               # one row (the largest) never added
+            r_ = PR.rows(big1)
+            G[net.stem_b] = G[net.stem_b] - r_[int(r_.abs().sum(1).argmax())]
     put(S["big1"], big1)
     _, gw0 = _conv_bwd(xr, _w(net, P[net.stem_w]), big1, 2, net.stem_pad)
     G[net.stem_w] = gw0.reshape(P[net.stem_w].shape)
@@ -399,6 +410,80 @@ def test_replay_rejects_a_slip_and_names_the_op(slip, kind, bf16):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# the training stem in two passes (a plan started with ECGMM_STEM_FUSE=0) and a plan that stores no ReLU bits
+# (ECGMM_RELU_BITS=0): what the caller tells Net
+# ----------------------------------------------------------------------------------------------------------------------
+def two_pass(kind, bf16):
+    net, model, x, dfeat = make(kind, bf16)
+    net.stem_fused = False
+    return net, model, x, dfeat
+
+
+@pytest.mark.parametrize("kind,bf16", CASES, ids=IDS)
+def test_replay_accepts_the_training_stem_in_two_passes(kind, bf16):
+    net, model, x, dfeat = two_pass(kind, bf16)
+    stem = [net.n_stages - 1]
+    two = build(net, model, x, dfeat)
+    rep = replay_all(net, two, x, dfeat, stages=stem, forward=False)
+    assert rep.paths == {"stem bwd": "two passes"} and max(rep.worst.values()) <= 1.0
+    assert {"stem_bwd", "bn_bwd", "dw", "stem_dx"} <= set(rep.worst)
+    # the same dicts told to be the one-pass form: big0 is there although nothing should have written it
+    net.stem_fused = True
+    with pytest.raises(AssertionError, match="stem big0: written"):
+        replay_all(net, two, x, dfeat, stages=stem, forward=False)
+    # and the one-pass dicts told to be two passes: big0 was never written
+    one = build(net, model, x, dfeat)
+    rep = replay_all(net, one, x, dfeat, stages=stem, forward=False)
+    assert rep.paths == {"stem bwd": "one pass"}
+    net.stem_fused = False
+    with pytest.raises(AssertionError, match="stem maxpool bwd big0"):
+        replay_all(net, one, x, dfeat, stages=stem, forward=False)
+
+
+# planted error -> (kinds, the op the replay must name)
+STEM_SLIPS = {
+    "big0_tap": (("r18", "r1d"), r"stem maxpool bwd big0"),
+    "big1_affine": (("r18", "r1d"), r"stem bn bwd dy"),
+    "dbias_short": (("r1d",), r"stem bn bwd dbias"),
+}
+STEM_SLIP_PARAMS = [(s, k, bf) for s, v in STEM_SLIPS.items() for k in v[0] for bf in (False, True)]
+
+
+@pytest.mark.parametrize("slip,kind,bf16", STEM_SLIP_PARAMS,
+                         ids=["%s-%s-%s" % (s, k, "bf16" if b else "fp32") for s, k, b in STEM_SLIP_PARAMS])
+def test_replay_rejects_a_slip_in_the_two_pass_training_stem(slip, kind, bf16):
+    net, model, x, dfeat = two_pass(kind, bf16)
+    built = build(net, model, x, dfeat, slip=slip)
+    with pytest.raises(AssertionError) as e:
+        replay_all(net, built, x, dfeat, stages=[net.n_stages - 1], forward=False)
+    assert re.search(STEM_SLIPS[slip][1], str(e.value)), str(e.value)[:400]
+
+
+def test_the_downsample_branch_taken_is_reported():
+    net, model, x, dfeat = make("r18", True)
+    for fold, want in ((True, "folded"), (False, "dtmp")):
+        rep = replay_all(net, build(net, model, x, dfeat, fold=fold), x, dfeat, stages=[2, 3], forward=False)
+        assert rep.paths == {"blk6 din": want}, rep.paths       # (stage 2 = block 6, layer4.0; block 5 has no downsample)
+
+
+def test_bits_are_checked_only_where_the_plan_stores_them():
+    net, model, x, dfeat = make("r18", True)
+    assert net.bits and not make("r18", False)[0].bits and not make("r18", True, training=False)[0].bits
+    built = build(net, model, x, dfeat, slip="bits_flip")
+    N, cin, H, W = R18_SHAPE
+    for bits in (None, True):
+        with pytest.raises(AssertionError, match="blk3 bits: 1 bits"):
+            replay_all(PR.Net("r18", N, cin, H, W, True, bits=bits), built, x, dfeat, stages=[])
+    off = PR.Net("r18", N, cin, H, W, True, bits=False)
+    assert not off.bits
+    rep = replay_all(off, built, x, dfeat, stages=[])
+    assert "bits" not in rep.worst and max(rep.worst.values()) <= 1.0
+    # (a plan that stores none has none to hand over either)
+    T = {k: v for k, v in built[0].items() if k[0] != "bits"}
+    replay_all(off, (T,) + built[1:], x, dfeat, stages=[])
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # the workspace views (host-only entry points of the built library)
 # ----------------------------------------------------------------------------------------------------------------------
 def _view(lib, fn, d, backward, name, index):
@@ -437,6 +522,9 @@ def expected_views(net):
         v.update({(1, n, 0): actb for n in ("dy", "dy1", "dyd")})
         v.update({(1, "dh1", 0): N * 64 * f, (1, "dfeat_h", 0): N * 64 * f, (1, "dg", 0): N * 256 * f, (1, "ds", 0): N * 256 * f,
                   (1, "dh", 0): N * 16 * f, (1, "dm", 0): N * 256 * f})
+        # what only the merged SE / BatchNorm backward pass writes: per-sample sums and its 16 reduction rows [2][256]
+        v.update({(1, n, 0): N * 256 * f for n in ("sa1", "sa2", "sa3")})
+        v[(1, "se_rows", 0)] = 16 * 2 * 256 * f
     v.update({(1, "big0", 0): big, (1, "big1", 0): big, (1, "dpooled", 0): N * net.feat_c * f})
     return v
 
@@ -481,7 +569,7 @@ def test_workspace_views_lie_inside_the_workspace_and_do_not_overlap(kind, bf16,
     if not (kind == "r18" and bf16):
         missing.append((0, "bits", 0))
     if kind == "r18":
-        missing += [(0, "m", 0), (1, "dg", 0), (0, "wdd", 1), (0, "yd", 7)]
+        missing += [(0, "m", 0), (1, "dg", 0), (1, "sa1", 0), (1, "se_rows", 0), (0, "wdd", 1), (0, "yd", 7)]
     for bw, name, index in missing:
         rc, _, _ = _view(lib, fn, d, bw, name, index)
         assert rc == 1 and name.encode() in lib.ecgmm_last_error(), (name, index, rc)

@@ -16,6 +16,12 @@ adds one shape per plan where they do run: ResNet18 (2, 3, 128, 128) -- blocks 0
 successor is a stride-1 block of 2048 / 512 pixels; asserted from the geometry rule and against the library's own answer) --
 and ResNet1D_SE (2, 1, 1021) (256 / 128 pooled samples per signal).
 
+Which path the library took is read from the stored data as well (staged() -> Plan.seen, one PATHS line per run): the fused
+stem backward leaves big0 all 0xFF, the merged SE pass writes sa1 / sa2 / sa3 / se_rows, a folded downsample gradient leaves
+dtmp unwritten, a plan that stores no ReLU bits leaves the bits views alone; each is held to the switches this process was
+started with (Net.bits and Net.stem_fused come from ECGMM_RELU_BITS and ECGMM_STEM_FUSE).  The other value of every
+start-up-only switch runs these same checks in a child process: tests/startup_legs.py, tests/test_startup_legs_gpu.py.
+
 Measured on the MI355X, worst |err| / bound per op class over every case and run of this file (1 is a bf16 rounding tie: the
 stored rounding term alone; 0 is an exact comparison; print them with -s, REPLAY lines):
 
@@ -65,6 +71,7 @@ OUT_DIM = {"r18": 16, "r1d": 5}
 PREFIX = {"r18": "ecgmm_resnet18", "r1d": "ecgmm_resnet1d"}
 SHAPES = {"r18": [(3, 3, 72, 104), (2, 3, 96, 160)], "r1d": [(3, 1, 999), (2, 12, 1000)]}
 HALO_SHAPES = {"r18": (2, 3, 128, 128), "r1d": (2, 1, 1021)}
+SE_MERGED_ONLY = ("sa1", "sa2", "sa3", "se_rows")      # backward-workspace tensors only the merged SE / bn2 pass writes
 
 
 def ff(t):
@@ -93,7 +100,12 @@ class Plan:
             model = fill.hash_fill_module(O.ResNet1D_SE(cin, OUT_DIM[kind]), "replay1d.")
             self.x = fill.hash_tensor(shape, 813, 1.7).to(DEV)
             self.desc = L.ResNet1DDesc(N, cin, W, OUT_DIM[kind], dt, int(training), 0.1, 1e-5, DROP_P, SEED, OFFSET)
-        self.net = PR.Net(kind, N, cin, H, W, bf16, training, dropout_p=DROP_P if kind == "r1d" else 0.0)
+        # what this process was started with (both are read once at start-up): whether the forward stores the ReLU bits and
+        # whether the training stem backward is one pass; the replay holds the stored data to either
+        on = lambda name: bool(switch_get(self.lib, name))
+        self.net = PR.Net(kind, N, cin, H, W, bf16, training, dropout_p=DROP_P if kind == "r1d" else 0.0,
+                          bits=bf16 and training and on("ECGMM_RELU_BITS"), stem_fused=on("ECGMM_STEM_FUSE"))
+        self.seen = {}
         self.dfeat = fill.hash_tensor((N, OUT_DIM[kind]), 812).to(DEV)
         self.names = [n for n, _ in model.named_parameters()]
         self.P = {n: p.detach().to(DEV).contiguous() for n, p in model.named_parameters()}
@@ -139,7 +151,7 @@ class Plan:
             names = [("X", 1 - keep)] + [(n, 0) for n in ("dz", "da", "dtmp", "big0", "big1", "dpooled")]
             names += [(n, i) for n in ("dy", "dy1", "dyd") for i in ((0, 1) if self.net.dual else (0,))]
             if self.net.se:
-                names += [(n, 0) for n in ("dh1", "dfeat_h", "dg", "ds", "dh", "dm")]
+                names += [(n, 0) for n in ("dh1", "dfeat_h", "dg", "ds", "dh", "dm") + SE_MERGED_ONLY]
             for n, i in names:
                 ff(self.raw(1, n, i))
         for n, v in self.arena.views.items():
@@ -164,6 +176,10 @@ class Plan:
         ws, total = (self.wb, self.nb) if backward else (self.wf, self.nf)
         assert off + nbytes <= total
         return ws.view(torch.uint8)[off:off + nbytes]
+
+    def untouched(self, backward, name, index=0):
+        """every byte of the view is still the 0xFF it was filled with"""
+        return bool((self.raw(backward, name, index) == 0xFF).all())
 
     def act(self, backward, name, index, Cn, H, W):
         t = self.raw(backward, name, index).view(TDT[self.dt])
@@ -217,10 +233,25 @@ class Plan:
         return {n: self.arena.views["g:" + n].clone() for n in self.names}
 
 
-def staged(plan, rep):
-    """forward + replay, then the backward one stage per call with a replay after each; returns (feat, {grad name: tensor}, dx)"""
+def bits_untouched(plan, when):
+    """a plan that promised no ReLU bits (eval, or started with ECGMM_RELU_BITS=0) has the views and must leave them alone"""
     net = plan.net
+    if net.kind == "r18" and net.bf16 and not net.bits:
+        for k in net.blocks:
+            assert plan.untouched(0, "bits", k.i), "block %d: bits written %s although the plan stores none" % (k.i, when)
+        return True
+    return False
+
+
+def staged(plan, rep):
+    """forward + replay, then the backward one stage per call with a replay after each; returns (feat, {grad name: tensor}, dx).
+    plan.seen: which workspace tensors each stage left written, byte by byte -- the evidence of the path the library took
+    (big0: the two-pass stem; dtmp: the unfolded downsample gradient; sa1..se_rows: the merged SE form; dz; bits)"""
+    net = plan.net
+    nb = len(net.blocks)
+    seen = plan.seen = dict(dz={}, dtmp={}, se_merged={}, big0=None, bits=None)
     feat = plan.forward()
+    seen["bits"] = "none after the forward" if bits_untouched(plan, "by the forward") else "written" if net.bits else None
     T = plan.read_forward()
     PR.replay_forward(net, T, plan.P, plan.B0, plan.B, plan.x.view(net.N, net.cin, net.H, net.W), feat, rep)
     before = plan.wf.clone()
@@ -237,6 +268,17 @@ def staged(plan, rep):
         else:
             assert bool(torch.isnan(dxs).all()), "stage %d wrote the input gradient" % st
         PR.replay_backward_stage(net, T, S, G, plan.P, x4, plan.dfeat, st, dxs.view(x4.shape) if last else None, rep)
+        if 1 <= st <= nb:
+            k = net.blocks[nb - st]
+            seen["dz"][k.i] = not plan.untouched(1, "dz")
+            if k.down:
+                seen["dtmp"][k.i] = not plan.untouched(1, "dtmp")
+            if net.se:
+                wrote = [not plan.untouched(1, n) for n in SE_MERGED_ONLY]
+                assert all(wrote) or not any(wrote), "block %d: %s written in part: %s" % (k.i, SE_MERGED_ONLY, wrote)
+                seen["se_merged"][k.i] = wrote[0]
+        elif last:
+            seen["big0"] = not plan.untouched(1, "big0")
         for n, g in G.items():
             if bool(torch.isfinite(g).all()):
                 assert n not in final, "%s written by two stages" % n
@@ -246,17 +288,45 @@ def staged(plan, rep):
         plan.fill_backward(keep=st & 1)
     assert sorted(final) == sorted(plan.names), set(plan.names) - set(final)
     assert same_bits(before, plan.wf), "the backward wrote into the forward workspace"
+    if bits_untouched(plan, "by the backward"):
+        seen["bits"] = "none after the forward, none after the backward"
+    # the paths in effect in this process (the environment it was started with), held against the stored data
+    lib = plan.lib
+    assert seen["big0"] == (not (net.training and switch_get(lib, "ECGMM_STEM_FUSE"))), "stem big0 written: %s" % seen["big0"]
+    assert rep.paths["stem bwd"] == ("two passes" if seen["big0"] else "one pass")
+    if net.se:
+        merged = bool(net.training and switch_get(lib, "ECGMM_SE_MERGE"))
+        assert seen["se_merged"] == {k.i: merged for k in net.blocks}, "merged SE pass ran on blocks %s" % seen["se_merged"]
+    for k in net.blocks:
+        if k.down:      # (with ECGMM_DOWN_FOLD on, which blocks fold is the igemm kernel's decision: the replay follows dtmp)
+            assert rep.paths["blk%d din" % k.i] == ("dtmp" if seen["dtmp"][k.i] else "folded")
+            assert seen["dtmp"][k.i] or switch_get(lib, "ECGMM_DOWN_FOLD"), "block %d folded with ECGMM_DOWN_FOLD=0" % k.i
+        assert seen["dz"][k.i] == (k.i not in net.fused2), "block %d: dz written %s, fused2 %s" % (k.i, seen["dz"][k.i], net.fused2)
     return feat, final, dx, T
 
 
-def fused_blocks(plan):
-    """ResNet18 blocks whose bn2 reduction is fused into the next block's conv1 input gradient when ECGMM_BN_FUSE_MIN_M = 0:
+def show_paths(plan, what):
+    """one PATHS line per run: what the stored data says about the branches taken"""
+    s = plan.seen
+    on = lambda d: ",".join(str(i) for i in sorted(d) if d[i]) or "-"
+    print("PATHS %s: stem big0 %s; dz written on blocks %s; dtmp written on blocks %s of %s; merged SE scratch written on "
+          "blocks %s; fused bn2 reductions %s; bits %s" % (what, "written (two passes)" if s["big0"] else "0xFF (one pass)",
+                                                           on(s["dz"]), on(s["dtmp"]), sorted(s["dtmp"]), on(s["se_merged"]),
+                                                           sorted(plan.net.fused2), s["bits"]))
+
+
+def fused_blocks(plan, capable_only=False):
+    """ResNet18 blocks whose bn2 reduction is fused into the next block's conv1 input gradient (ECGMM_BN_FUSE_MIN_M = 0 in the
+    runs that have any; the threshold in effect is part of the rule):
     the rule of plan_resnet18.hip (bf16 training, the next block has no downsample and its conv1 input gradient runs on the
     halo kernel: stride-1 3x3, pixels a multiple of 256, channels of 64 / 128, 256 + 2 (W + 1) halo rows within 384 / 320),
-    checked against the library's own answer (ecgmm_conv_bwd_data_bnred_rows) under the switches in effect"""
+    checked against the library's own answer (ecgmm_conv_bwd_data_bnred_rows) under the switches in effect.  That query says
+    what the kernel can do; whether the plan asks it to is the plan's own switch: none with ECGMM_BN_FUSE=0 (capable_only:
+    the blocks the kernel could serve, whatever that switch says)"""
     net = plan.net
     if net.kind != "r18" or not net.bf16 or not net.training:
         return set()
+    plan_fuses = bool(switch_get(plan.lib, "ECGMM_BN_FUSE"))
     out = set()
     for k in net.blocks[:-1]:
         nx = net.blocks[k.i + 1]
@@ -264,7 +334,7 @@ def fused_blocks(plan):
                 and 256 + 2 * (nx.win + 1) <= (320 if nx.cin > 64 else 384))
         d = L.ConvDesc(net.N, nx.hin, nx.win, nx.cin, nx.cout, 3, 3, nx.stride, 1, 1)
         assert rule == (plan.lib.ecgmm_conv_bwd_data_bnred_rows(L.BF16, C.byref(d)) > 0), "block %d" % k.i
-        if rule:
+        if rule and (capable_only or (plan_fuses and net.N * k.hout * k.wout >= switch_get(plan.lib, "ECGMM_BN_FUSE_MIN_M"))):
             out.add(k.i)
     return out
 
@@ -281,6 +351,7 @@ def test_plan_replays_against_float64_default_switches(kind, shape, dt):
     rep = PR.Rep()
     feat, final, dx, _ = staged(plan, rep)
     rep.show("%s %s %s default" % (kind, shape, "bf16" if dt == L.BF16 else "fp32"))
+    show_paths(plan, "%s %s %s default" % (kind, shape, "bf16" if dt == L.BF16 else "fp32"))
     # the whole backward in one call
     plan.fill_backward()
     plan.backward(0, plan.net.n_stages)
@@ -293,7 +364,9 @@ def test_plan_replays_against_float64_default_switches(kind, shape, dt):
     feat2 = plan.forward()
     assert same_bits(feat, feat2) and same_bits(ws1, plan.wf), "the second forward differs from the first"
     # absent tensors
-    absent = [(0, "yd", 0), (0, "coefd", 0), (0, "nonsense", 0), (1, "X", 2)] + ([] if plan.net.bits else [(0, "bits", 0)])
+    # (the bits views belong to the layout of every bf16 ResNet18 plan, whether or not this process writes them)
+    absent = [(0, "yd", 0), (0, "coefd", 0), (0, "nonsense", 0), (1, "X", 2)]
+    absent += [] if (kind == "r18" and dt == L.BF16) else [(0, "bits", 0)]
     for bw, name, index in absent:
         assert plan.view(bw, name, index)[0] == 1 and name.encode() in plan.lib.ecgmm_last_error(), (name, index)
 
