@@ -9,10 +9,11 @@ import numpy as np
 import torch
 
 from . import preprocess as PP
+from . import training as T
 from .config import Config
 from .hip.functional import _require_cuda
 from .signal_model import ResNet1D_SE, find_best_threshold
-from .train_signal_only_ptb import LENGTH, PTBXLLoader
+from .train_signal_only_ptb import LENGTH
 
 LABEL_MAP = {"Normal": 0, "Abnormal": 1}      # evaluation_signal.py:76
 
@@ -73,7 +74,7 @@ def get_digitized_test_loader(config=Config):
     ecg_signals = ecg_signals.loc[ecg_signals.index.isin(common)]
     ecg_scaler = StandardScaler().fit(ecg_signals)
     test_ds = DigitizedECGDataset(common, labels_df, ecg_signals, ecg_scaler, device=config.device)
-    return PTBXLLoader(test_ds, batch_size=8)
+    return PP.PTBXLLoader(test_ds, batch_size=8)
 
 
 def main(model_path, config=Config, quiet=False, use_predictor=False):
@@ -88,13 +89,8 @@ def main(model_path, config=Config, quiet=False, use_predictor=False):
     if use_predictor:
         from .inference import Predictor
         fwd = Predictor(model)
-    all_probs, all_labels = [], []
-    with torch.no_grad():
-        for signals, labels in test_loader:
-            probs = torch.softmax(fwd(signals).float(), dim=1)[:, 1]
-            all_probs.append(probs.cpu().numpy())
-            all_labels.append(labels.cpu().numpy())
-    y_true, y_prob = np.concatenate(all_labels), np.concatenate(all_probs)
+    y_true, y_prob, _, _ = T.predict(fwd, test_loader)
+    y_prob = y_prob[:, 1]
     best_t = float(find_best_threshold(y_true, y_prob))
     y_pred = (y_prob >= best_t).astype(int)
     res = dict(threshold=best_t, auc=float(roc_auc_score(y_true, y_prob)), f1=float(f1_score(y_true, y_pred)),

@@ -13,7 +13,8 @@ import numpy as np
 import torch
 
 from .hip import lib as L
-from .hip.functional import _Scratch, _require_cuda, ptr, stream
+from .hip.functional import _PhiloxState, _Scratch, _require_cuda, ptr, stream
+from .training import ResidentLoader
 
 
 def butter_lowpass(order, wn):
@@ -181,7 +182,6 @@ def weighted_sample(cdf, last_positive, count, seed_offset=None, return_uniforms
     """``count`` indices drawn with replacement, P(j) proportional to weight j, in one launch.  cdf: CUDA float64 [n] from
     :func:`weight_cdf`.  Randomness: the Philox stream of ``ecgmm.hip.functional`` advanced by one counter block per call,
     or ``seed_offset=(seed, offset)``.  -> int64 [count] on the device (and the float64 uniforms the draws used)."""
-    from .hip.functional import _PhiloxState
     _require_cuda(cdf, "weighted_sample")
     if cdf.dtype != torch.float64 or cdf.dim() != 1 or not cdf.is_contiguous():
         raise ValueError("weighted_sample: cdf must be a contiguous float64 vector")
@@ -192,3 +192,49 @@ def weighted_sample(cdf, last_positive, count, seed_offset=None, return_uniforms
     L.check(L.lib().ecgmm_weighted_sample(ptr(cdf), cdf.numel(), int(last_positive), ptr(out), ptr(u), count, int(seed),
                                           int(off), stream()), "weighted_sample")
     return (out, u) if return_uniforms else out
+
+
+def gather_augment(src, index, augment=False, p=0.5, sigma=0.01, scale=(0.8, 1.2), shift=(-10, 10),
+                   return_decisions=False, seed_offset=None, check_index=True):
+    """``out[i] = augment_signal(src[index[i]])`` in one launch; ``augment=False`` is the plain gather.
+
+    src: CUDA fp32 [n, L]; index: int64 [B], on the host (checked there, then uploaded) or on the device (checked with one
+    device read unless ``check_index=False``).  Randomness comes from the Philox stream of ``ecgmm.hip.functional``
+    (``manual_seed``), advanced by one counter block per call; ``seed_offset=(seed, offset)`` pins it instead.
+    -> out [B, L] (and the decision record [B, 4]: noise flag, scale or 1, shift or 0, decisions as bits 1 / 2 / 4)."""
+    _require_cuda(src, "gather_augment")
+    if src.dim() != 2 or src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError("gather_augment: src must be a contiguous float32 [n, L] tensor")
+    index = torch.as_tensor(index)
+    if index.dtype != torch.int64 or index.dim() != 1 or index.numel() < 1:
+        raise ValueError("gather_augment: index must be a non-empty int64 vector")
+    n, Ln = src.shape
+    if check_index:
+        lo, hi = int(index.min()), int(index.max())
+        if lo < 0 or hi >= n:
+            raise IndexError(f"gather_augment: index range [{lo}, {hi}] outside the {n} rows of src")
+    index = index.to(src.device).contiguous()
+    B = index.numel()
+    out = torch.empty(B, Ln, dtype=torch.float32, device=src.device)
+    dec = torch.empty(B, 4, dtype=torch.float32, device=src.device) if return_decisions else None
+    seed, off = (0, 0)
+    if augment:
+        seed, off = _PhiloxState.take(1) if seed_offset is None else seed_offset
+    L.check(L.lib().ecgmm_signal_gather_augment(ptr(src), n, Ln, ptr(index), B, ptr(out), ptr(dec), int(bool(augment)),
+                                                float(p), float(sigma), float(scale[0]), float(scale[1]), int(shift[0]),
+                                                int(shift[1]), int(seed), int(off), stream()), "signal_gather_augment")
+    return (out, dec) if return_decisions else out
+
+
+class PTBXLLoader(ResidentLoader):
+    """Batches ``(signals [B, leads, length], labels [B])`` of a dataset whose ``signals`` [n, leads, length] fp32 and
+    ``labels`` [n] are resident on the device (``PTBXLSignalDataset``, ``DigitizedECGDataset``), one plain gather launch each.
+    Under a ``sampler`` the epoch has ``len(sampler)`` samples and ``last_order`` holds the indices it drew."""
+
+    def __init__(self, dataset, batch_size=16, shuffle=False, generator=None, drop_last=False, sampler=None):
+        super().__init__(dataset, batch_size, shuffle, generator, drop_last, sampler)
+
+    def batch(self, idx):
+        ds = self.dataset
+        x = gather_augment(ds.signals.view(len(ds), -1), idx, augment=False, check_index=False)
+        return x.view(idx.numel(), *ds.signals.shape[1:]), ds.labels[idx]

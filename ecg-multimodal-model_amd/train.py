@@ -2,6 +2,8 @@
 paper_modal_balance model).  Like the reference's train.py:14 it builds ``multimodal.ECGMultimodalModel`` (TabNet
 clinical branch, widths 512 / 128 / 32) unless another ``model_cls`` is passed.
 
+This module holds the step (``step_loss``, ``run_epoch``), the test metrics (``evaluate``) and the policy values; the epoch
+loop, the checkpoint test loop and the metric helpers are ``ecgmm.training``'s.
 Reproduces the reference loop: seed 42; encoders frozen by default as train.py:35-40 does (pass
 ``freeze_encoders=False`` for the end-to-end step of train_kfold.py:42); Adam(lr=Config.lr) on the
 trainable parameters; per step zero_grad -> forward -> CE(fusion_logits) + 0.1 * var_loss ->
@@ -12,11 +14,10 @@ The reference's 4-vs-5 tuple unpacking defect (train.py:60 vs dataset.py:74) is 
 loops unpack ``*batch, index``.  TensorBoard is optional (not installed in this image).
 """
 import os
-import time
 
-import numpy as np
 import torch
 
+from . import training as T
 from .config import Config
 from .dataset import get_dataloaders
 from .hip import functional as HF
@@ -40,35 +41,27 @@ def step_loss(outputs, labels):
 
 def run_epoch(model, loader, device, optimizer=None, predictor=None):
     """``predictor`` (optional, validation only): an ``ecgmm.inference.Predictor`` of ``model`` whose weights are current
-    (``refresh()`` after training); the forward then runs through the inference plans.  Default: the model's own forward."""
+    (``refresh()`` after training); the forward then runs through the inference plans.  Default: the model's own forward.
+    -> (mean loss, mean var_loss, accuracy)."""
     train = optimizer is not None
     if train and predictor is not None:
         raise ValueError("run_epoch: a Predictor has no backward; pass it for validation passes only")
     model.train(train)
-    tot, tot_var, correct, n = 0.0, 0.0, 0, 0
-    ctx = torch.enable_grad() if train else torch.no_grad()
-    with ctx:
-        for *batch, _index in loader:
-            images, ecg, clinical, labels = (t.to(device) for t in batch)
-            if train:
-                optimizer.zero_grad()
-            outputs = model(images, ecg, clinical) if predictor is None else predictor(images, ecg, clinical)
-            loss = step_loss(outputs, labels)
-            if train:
-                loss.backward()
-                optimizer.step()
-            tot += loss.item()
-            tot_var += outputs[4].item()
-            correct += outputs[3].argmax(1).eq(labels).sum().item()
-            n += labels.size(0)
-    k = max(len(loader), 1)
-    return tot / k, tot_var / k, correct / max(n, 1)
+    forward = model if predictor is None else predictor
+
+    def step(batch):
+        *inputs, _index = batch
+        images, ecg, clinical, labels = (t.to(device) for t in inputs)
+        outputs = forward(images, ecg, clinical)
+        return step_loss(outputs, labels), outputs[3], labels, {"var_loss": outputs[4]}
+
+    loss, acc, extras = T.run_epoch(loader, step, optimizer)
+    return loss, extras.get("var_loss", 0.0), acc
 
 
 def evaluate(model, loader, device, predictor=None):
     """train.py:173-260: softmax[:,1] probabilities, accuracy / F1 / AUC on the test split.
     ``predictor`` (optional): an ``ecgmm.inference.Predictor`` of ``model`` with current weights; default: ``model`` itself."""
-    from sklearn.metrics import f1_score, roc_auc_score
     model.eval()
     y_true, y_prob, y_pred = [], [], []
     with torch.no_grad():
@@ -79,20 +72,13 @@ def evaluate(model, loader, device, predictor=None):
             y_true += labels.cpu().tolist()
             y_prob += prob[:, 1].tolist()
             y_pred += prob.argmax(1).tolist()
-    acc = float(np.mean(np.array(y_true) == np.array(y_pred)))
-    f1 = float(f1_score(y_true, y_pred, zero_division=0))
-    try:
-        auc = float(roc_auc_score(y_true, y_prob))
-    except ValueError:
-        auc = float("nan")
-    return {"accuracy": acc, "f1": f1, "auc": auc}
+    return T.binary_metrics(y_true, y_prob, y_pred)
 
 
 def main(config=Config, freeze_encoders=True, num_epochs=None, quiet=False, model_cls=None, use_predictor=False):
     """``use_predictor``: run the validation and test passes through an ``ecgmm.inference.Predictor`` (BatchNorm-folded
     inference plans), refreshed after every training epoch and after every checkpoint load.  Default off."""
-    torch.manual_seed(config.seed)
-    HF.manual_seed(config.seed)
+    T.seed_all(config.seed)
     device = torch.device(config.device)
     if not quiet:
         print(f"Using device: {device}")
@@ -107,55 +93,42 @@ def main(config=Config, freeze_encoders=True, num_epochs=None, quiet=False, mode
                 p.requires_grad = False
     optimizer = FusedAdam(filter(lambda p: p.requires_grad, model.parameters()), lr=config.lr)
 
-    modeltime = time.strftime("%m%d_%H%M%S", time.localtime())
-    writer = _writer(f"runs/{modeltime}")
-    ckpt_dir = os.path.join(config.checkpoint_dir, modeltime)
-    os.makedirs(ckpt_dir, exist_ok=True)
-
+    ckpt_dir = T.run_dir(config.checkpoint_dir)
+    writer = _writer(f"runs/{os.path.basename(ckpt_dir)}")
     predictor = None
     if use_predictor:
         from .inference import Predictor
         predictor = Predictor(model)
-    min_val, early, lr_ctr, history = float("inf"), 0, 0, []
-    for epoch in range(num_epochs or config.num_epochs):
-        tr_loss, _, tr_acc = run_epoch(model, train_loader, device, optimizer)
-        if predictor is not None:
-            predictor.refresh()   # (the optimizer wrote the weights through raw pointers: nothing else can tell)
-        va_loss, va_var, va_acc = run_epoch(model, val_loader, device, predictor=predictor)
-        history.append(dict(epoch=epoch + 1, train_loss=tr_loss, train_acc=tr_acc, val_loss=va_loss, val_acc=va_acc))
+
+    def on_epoch(h, extras):
         if not quiet:
-            print(f"[{epoch + 1}] train {tr_loss:.4f}/{tr_acc:.4f}  val {va_loss:.4f}/{va_acc:.4f}")
+            print(f"[{h['epoch']}] train {h['train_loss']:.4f}/{h['train_acc']:.4f}  val {h['val_loss']:.4f}/{h['val_acc']:.4f}")
         if writer is not None:
-            writer.add_scalar("Loss/Train", tr_loss, epoch)
-            writer.add_scalar("Loss/Val", va_loss, epoch)
-            writer.add_scalar("VarLoss/Val", va_var, epoch)
-            writer.add_scalar("Accuracy/Train", tr_acc, epoch)
-            writer.add_scalar("Accuracy/Val", va_acc, epoch)
+            epoch = h["epoch"] - 1
+            writer.add_scalar("Loss/Train", h["train_loss"], epoch)
+            writer.add_scalar("Loss/Val", h["val_loss"], epoch)
+            writer.add_scalar("VarLoss/Val", extras["var_loss"], epoch)
+            writer.add_scalar("Accuracy/Train", h["train_acc"], epoch)
+            writer.add_scalar("Accuracy/Val", h["val_acc"], epoch)
             w = torch.softmax(model.attention_fusion.weights.detach().float().cpu(), 0)
             for name, v in zip(("Image", "Signal", "Clinical"), w.tolist()):
                 writer.add_scalar(f"AttentionWeights/{name}", v, epoch)
-        torch.save(model.state_dict(), os.path.join(ckpt_dir, "last.pth"))
-        if va_loss < min_val:   # train.py:145-151: epochN.pth and best.pth only on improvement
-            min_val, early, lr_ctr = va_loss, 0, 0
-            torch.save(model.state_dict(), os.path.join(ckpt_dir, f"epoch{epoch + 1}.pth"))
-            torch.save(model.state_dict(), os.path.join(ckpt_dir, "best.pth"))
-        else:
-            early += 1
-            lr_ctr += 1
-            if lr_ctr >= 2:  # manual LR / 10 (train.py:157-163)
-                for g in optimizer.param_groups:
-                    g["lr"] /= 10
-                lr_ctr = 0
-            if early >= config.patience:
-                break
-    results = {}
-    for tag in ("best", "last"):
-        model.load_state_dict(torch.load(os.path.join(ckpt_dir, f"{tag}.pth"), map_location=device))
-        if predictor is not None:
-            predictor.refresh()
-        results[tag] = evaluate(model, test_loader, device, predictor=predictor)
-        if not quiet:
-            print(f"test[{tag}]: {results[tag]}")
+
+    def one_pass(loader, **kw):
+        loss, var, acc = run_epoch(model, loader, device, **kw)
+        return loss, acc, {"var_loss": var}
+
+    # train.py:145-151: epochN.pth and best.pth only on improvement; :157-163: manual LR / 10 after 2 non-improving epochs
+    history = T.fit(model, optimizer, lambda: one_pass(train_loader, optimizer=optimizer),
+                    lambda: one_pass(val_loader, predictor=predictor), ckpt_dir, num_epochs or config.num_epochs,
+                    patience=config.patience, lr_decay_after=2, best_names=("epoch{epoch}.pth", "best.pth"),
+                    predictor=predictor, on_epoch=on_epoch)
+    # (best.pth is missing when no epoch improved on inf: that raises here, as it always did)
+    results = T.test_checkpoints(model, ckpt_dir, ("best", "last"), lambda: evaluate(model, test_loader, device, predictor),
+                                 predictor, skip_missing=False)
+    if not quiet:
+        for tag, res in results.items():
+            print(f"test[{tag}]: {res}")
     if writer is not None:
         writer.close()
     return history, results, ckpt_dir

@@ -1,12 +1,11 @@
 """Image-only ResNet18 classifier and its training loop (reference: train_image_only.py:92-310;
-BASELINE config 2).  ``ImageOnlyClassifier`` keeps the ``image_encoder.*`` state_dict prefix."""
-import os
-import time
-
+BASELINE config 2).  ``ImageOnlyClassifier`` keeps the ``image_encoder.*`` state_dict prefix.  The loop itself (last.pth
+every epoch, best.pth on a lower validation loss, stop after ``Config.patience`` misses) is ``ecgmm.training.fit``."""
 import torch
 import torch.nn as nn
 from torch.utils.data import DataLoader, Dataset
 
+from . import training as T
 from .config import Config
 from .hip import functional as HF
 from .hip import nn as hnn
@@ -53,51 +52,35 @@ def get_imageonly_dataloaders():
 
 
 def main(num_epochs=None, quiet=False):
-    torch.manual_seed(Config.seed)
-    HF.manual_seed(Config.seed)
+    """-> ([(train loss, train accuracy, val loss, val accuracy) per epoch], checkpoint directory)"""
+    T.seed_all(Config.seed)
     device = torch.device(Config.device)
     train_loader, val_loader, test_loader = get_imageonly_dataloaders()
     model = ImageOnlyClassifier().to(device)
     optimizer = FusedAdam(model.parameters(), lr=Config.lr)          # :111
-    modeltime = time.strftime("%m%d_%H%M%S", time.localtime())
-    ckpt_dir = os.path.join(Config.checkpoint_dir, modeltime)
-    os.makedirs(ckpt_dir, exist_ok=True)
-    min_val, stop_ctr, hist = float("inf"), 0, []
-    for epoch in range(num_epochs or Config.num_epochs):
+    ckpt_dir = T.run_dir(Config.checkpoint_dir)
+
+    def step(batch):
+        images, labels = batch[0].to(device), batch[1].to(device)
+        out = model(images)
+        return HF.cross_entropy(out, labels), out, labels             # nn.CrossEntropyLoss(), :110
+
+    def train_pass():
         model.train()
-        tl, correct, total = 0.0, 0, 0
-        for images, labels in train_loader:
-            images, labels = images.to(device), labels.to(device)
-            optimizer.zero_grad()
-            out = model(images)
-            loss = HF.cross_entropy(out, labels)                      # nn.CrossEntropyLoss(), :110
-            loss.backward()
-            optimizer.step()
-            tl += loss.item()
-            correct += out.argmax(1).eq(labels).sum().item()
-            total += labels.size(0)
+        return T.run_epoch(train_loader, step, optimizer)
+
+    def val_pass():
         model.eval()
-        vl, vc, vt = 0.0, 0, 0
-        with torch.no_grad():
-            for images, labels in val_loader:
-                images, labels = images.to(device), labels.to(device)
-                out = model(images)
-                vl += HF.cross_entropy(out, labels).item()
-                vc += out.argmax(1).eq(labels).sum().item()
-                vt += labels.size(0)
-        avg_val = vl / max(len(val_loader), 1)
-        hist.append((tl / max(len(train_loader), 1), correct / max(total, 1), avg_val, vc / max(vt, 1)))
+        return T.run_epoch(val_loader, step)
+
+    def on_epoch(h, _extras):
         if not quiet:
-            print(f"epoch {epoch + 1}: train {hist[-1][0]:.4f}/{hist[-1][1]:.3f} val {avg_val:.4f}/{hist[-1][3]:.3f}")
-        torch.save(model.state_dict(), os.path.join(ckpt_dir, "last.pth"))
-        if avg_val < min_val:
-            min_val, stop_ctr = avg_val, 0
-            torch.save(model.state_dict(), os.path.join(ckpt_dir, "best.pth"))
-        else:
-            stop_ctr += 1
-            if stop_ctr >= Config.patience:
-                break
-    return hist, ckpt_dir
+            print(f"epoch {h['epoch']}: train {h['train_loss']:.4f}/{h['train_acc']:.3f} "
+                  f"val {h['val_loss']:.4f}/{h['val_acc']:.3f}")
+
+    history = T.fit(model, optimizer, train_pass, val_pass, ckpt_dir, num_epochs or Config.num_epochs,
+                    patience=Config.patience, on_epoch=on_epoch)
+    return [(h["train_loss"], h["train_acc"], h["val_loss"], h["val_acc"]) for h in history], ckpt_dir
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 """Nested stratified cross-validation harness (reference: train_kfold.py:20-181, dataset_kfold.py).
 
 Outer ``Config.k_outer`` folds for testing, inner ``Config.k_inner`` folds for model selection; every inner run is the
-reference's loop (Adam(lr), CE on the fusion logits, best_inner.pth on the lowest validation loss, LR / 10 after two
+reference's loop through ``ecgmm.training.fit`` (Adam(lr), CE on the fusion logits, best_inner.pth on the lowest validation loss, LR / 10 after two
 non-improving epochs, early stop after ``Config.patience``); the outer fold's test AUC is taken with best_inner.pth,
 as the reference does (:163-171, i.e. the checkpoint of the LAST inner fold that improved).  Scalers are fitted on the
 training part of each split (:25-29, :156-160).  Works on the synthetic generator (default) and on the reference's
@@ -10,13 +10,13 @@ The reference unpacks the model output as one tensor (:58-59) although the model
 logits (output [3]) are what the criterion and the AUC see.
 """
 import os
-import time
 
 import numpy as np
 import torch
 from torch.utils.data import DataLoader, Subset
 
 from . import dataset as D
+from . import training as T
 from .config import Config
 from .hip import functional as HF
 from .multimodal_paper_modal_balance import ECGMultimodalModel
@@ -54,55 +54,38 @@ def make_loader(config, ctx, positions, fit_positions, shuffle):
 
 
 def _epoch(model, loader, device, optimizer=None):
-    train = optimizer is not None
-    model.train(train)
-    tot, correct, n = 0.0, 0, 0
-    with (torch.enable_grad() if train else torch.no_grad()):
-        for *batch, _index in loader:
-            images, ecg, clinical, labels = (t.to(device) for t in batch)
-            if train:
-                optimizer.zero_grad()
-            logits = model(images, ecg, clinical)[3]
-            loss = HF.cross_entropy(logits, labels)
-            if train:
-                loss.backward()
-                optimizer.step()
-            tot += loss.item()
-            correct += logits.argmax(1).eq(labels).sum().item()
-            n += labels.size(0)
-    return tot / max(len(loader), 1), correct / max(n, 1)
+    model.train(optimizer is not None)
+
+    def step(batch):
+        *inputs, _index = batch
+        images, ecg, clinical, labels = (t.to(device) for t in inputs)
+        logits = model(images, ecg, clinical)[3]
+        return HF.cross_entropy(logits, labels), logits, labels
+
+    return T.run_epoch(loader, step, optimizer)
 
 
 def train_inner(config, ctx, train_pos, val_pos, fold_dir, num_epochs=None, quiet=True):
+    """-> (lowest validation loss, path of best_inner.pth or None when no epoch improved on inf)"""
     device = torch.device(config.device)
     train_loader = make_loader(config, ctx, train_pos, train_pos, True)
     val_loader = make_loader(config, ctx, val_pos, train_pos, False)
     model = ECGMultimodalModel(config).to(device)
     optimizer = FusedAdam(model.parameters(), lr=config.lr)
-    min_val, early, lr_ctr, best = float("inf"), 0, 0, None
-    for epoch in range(num_epochs or config.num_epochs):
-        tr_loss, tr_acc = _epoch(model, train_loader, device, optimizer)
-        va_loss, va_acc = _epoch(model, val_loader, device)
+
+    def on_epoch(h, _extras):
         if not quiet:
-            print(f"  [{epoch + 1}] train {tr_loss:.4f}/{tr_acc:.3f}  val {va_loss:.4f}/{va_acc:.3f}")
-        if va_loss < min_val:
-            best = os.path.join(fold_dir, "best_inner.pth")
-            torch.save(model.state_dict(), best)
-            min_val, early, lr_ctr = va_loss, 0, 0
-        else:
-            early += 1
-            lr_ctr += 1
-            if lr_ctr >= 2:
-                for g in optimizer.param_groups:
-                    g["lr"] /= 10
-                lr_ctr = 0
-            if early >= config.patience:
-                break
-    return min_val, best
+            print(f"  [{h['epoch']}] train {h['train_loss']:.4f}/{h['train_acc']:.3f}  val {h['val_loss']:.4f}/{h['val_acc']:.3f}")
+
+    history = T.fit(model, optimizer, lambda: _epoch(model, train_loader, device, optimizer),
+                    lambda: _epoch(model, val_loader, device), fold_dir, num_epochs or config.num_epochs,
+                    patience=config.patience, lr_decay_after=2, save_last=None, best_names=("best_inner.pth",),
+                    on_epoch=on_epoch)
+    improved = [h["val_loss"] for h in history if h["val_loss"] < float("inf")]   # (a NaN fails the comparison too)
+    return (min(improved), os.path.join(fold_dir, "best_inner.pth")) if improved else (float("inf"), None)
 
 
 def test_outer(model, test_loader, device):
-    from sklearn.metrics import roc_auc_score
     model.eval()
     labels_all, probs_all = [], []
     with torch.no_grad():
@@ -111,19 +94,15 @@ def test_outer(model, test_loader, device):
             probs = torch.softmax(model(images, ecg, clinical)[3].float().cpu(), dim=1)[:, 1]
             probs_all += probs.tolist()
             labels_all += labels.cpu().tolist()
-    try:
-        return float(roc_auc_score(labels_all, probs_all))
-    except ValueError:   # a fold with one class only
-        return float("nan")
+    return T.auc_or_nan(labels_all, probs_all)   # NaN: a fold with one class only
 
 
 def main(config=Config, num_epochs=None, quiet=False):
     from sklearn.model_selection import StratifiedKFold
-    torch.manual_seed(config.seed)
-    HF.manual_seed(config.seed)
+    T.seed_all(config.seed)
     ctx, labels, positions = get_all_data(config)
     device = torch.device(config.device)
-    ckpt = os.path.join(config.checkpoint_dir, time.strftime("%m%d_%H%M%S", time.localtime()))
+    ckpt = T.run_dir(config.checkpoint_dir)
     outer = StratifiedKFold(n_splits=config.k_outer, shuffle=True, random_state=config.seed)
     outer_aucs = []
     for of, (train_val_pos, test_pos) in enumerate(outer.split(positions, labels)):

@@ -8,25 +8,30 @@ schedule are the reference's: ``ResNet1D_SE`` on ``[B, 1, 3000]``, ``FocalLoss(1
 ``main(model="transformer")`` trains the reference's one-line alternative instead (train_physionet.py:276),
 :class:`ECGTransformer1D` on the native attention kernels.
 
+This module holds the model alternative, the device pre-processing, the record reader, the resident dataset and loader and
+the policy values; the epoch loop, the checkpoint test loop and the metrics are ``ecgmm.training``'s, the gather launch is
+``ecgmm.preprocess.gather_augment``.
+
 Not carried over: ``resample_signal`` (the reference never reaches it: ``orig_fs == target_fs`` at its only call site),
 plots.  ``wfdb`` is replaced by :func:`read_record`, ``keras`` by :func:`pad_sequences`.
 """
 import csv
 import os
 import re
-import time
 
 import numpy as np
 import torch
 
 from . import preprocess as PP
+from . import training as T
 from .config import Config
 from .hip import functional as HF
-from .hip import lib as L
 from .hip import nn as HN
-from .hip.functional import _require_cuda, ptr, stream
+from .hip.functional import _require_cuda
 from .optim import FusedAdam
+from .preprocess import gather_augment   # noqa: F401 -- its home is ecgmm.preprocess; this name is part of this module
 from .signal_model import FocalLoss, ResNet1D_SE
+from .training import split_indices      # noqa: F401 -- train_physionet.py:112-118; shared with the other PhysioNet / PTB-XL trainers
 
 LABEL_MAP = {"N": 0, "AF": 1, "O": 1}      # train_physionet.py:93 ('~' records are dropped at :92)
 MAX_LEN = 3000
@@ -106,38 +111,6 @@ def preprocess_signal(raw_signal, orig_fs=300, target_fs=300):
     _require_cuda(raw_signal, "preprocess_signal")
     b, a = _band(16, 149, orig_fs, 4)
     return PP.filter_zscore(raw_signal, b, a, zscore=True, eps=1e-8)
-
-
-def gather_augment(src, index, augment=False, p=0.5, sigma=0.01, scale=(0.8, 1.2), shift=(-10, 10),
-                   return_decisions=False, seed_offset=None, check_index=True):
-    """``out[i] = augment_signal(src[index[i]])`` in one launch; ``augment=False`` is the plain gather.
-
-    src: CUDA fp32 [n, L]; index: int64 [B], on the host (checked there, then uploaded) or on the device (checked with one
-    device read unless ``check_index=False``).  Randomness comes from the Philox stream of ``ecgmm.hip.functional``
-    (``manual_seed``), advanced by one counter block per call; ``seed_offset=(seed, offset)`` pins it instead.
-    -> out [B, L] (and the decision record [B, 4]: noise flag, scale or 1, shift or 0, decisions as bits 1 / 2 / 4)."""
-    _require_cuda(src, "gather_augment")
-    if src.dim() != 2 or src.dtype != torch.float32 or not src.is_contiguous():
-        raise ValueError("gather_augment: src must be a contiguous float32 [n, L] tensor")
-    index = torch.as_tensor(index)
-    if index.dtype != torch.int64 or index.dim() != 1 or index.numel() < 1:
-        raise ValueError("gather_augment: index must be a non-empty int64 vector")
-    n, Ln = src.shape
-    if check_index:
-        lo, hi = int(index.min()), int(index.max())
-        if lo < 0 or hi >= n:
-            raise IndexError(f"gather_augment: index range [{lo}, {hi}] outside the {n} rows of src")
-    index = index.to(src.device).contiguous()
-    B = index.numel()
-    out = torch.empty(B, Ln, dtype=torch.float32, device=src.device)
-    dec = torch.empty(B, 4, dtype=torch.float32, device=src.device) if return_decisions else None
-    seed, off = (0, 0)
-    if augment:
-        seed, off = HF._PhiloxState.take(1) if seed_offset is None else seed_offset
-    L.check(L.lib().ecgmm_signal_gather_augment(ptr(src), n, Ln, ptr(index), B, ptr(out), ptr(dec), int(bool(augment)),
-                                                float(p), float(sigma), float(scale[0]), float(scale[1]), int(shift[0]),
-                                                int(shift[1]), int(seed), int(off), stream()), "signal_gather_augment")
-    return (out, dec) if return_decisions else out
 
 
 def augment_signal(signal, **kw):
@@ -247,17 +220,6 @@ def load_records(config=Config, label_map=LABEL_MAP, quiet=True):
     return signals, np.array(labels, dtype=np.int64)
 
 
-def split_indices(labels, seed=Config.seed, split=SPLIT):
-    """Stratified train / val / test indices: ``train_test_split(test_size=split[0])`` then the held-out part split again
-    with ``test_size=split[1]``, both seeded with ``seed`` (train_physionet.py:112-118)."""
-    from sklearn.model_selection import train_test_split
-    labels = np.asarray(labels)
-    idx = np.arange(len(labels))
-    train_idx, temp_idx, _, temp_y = train_test_split(idx, labels, test_size=split[0], stratify=labels, random_state=seed)
-    val_idx, test_idx = train_test_split(temp_idx, test_size=split[1], stratify=temp_y, random_state=seed)
-    return train_idx, val_idx, test_idx
-
-
 # --------------------------------------------------------------------------------------------
 # dataset + loader (device resident)
 # --------------------------------------------------------------------------------------------
@@ -285,28 +247,17 @@ class SignalOnlyDataset:
         return sig, self.labels[idx]
 
 
-class DeviceSignalLoader:
+class DeviceSignalLoader(T.ResidentLoader):
     """Batches of a :class:`SignalOnlyDataset`: ``(signals [B, L] fp32 on the device, labels [B] on the device)``, one
     ``gather_augment`` launch per batch (augmentation as the dataset says).  ``shuffle``: a ``torch.randperm`` of the seeded
     ``generator`` per epoch, kept in ``last_order``."""
 
     def __init__(self, dataset, batch_size=8, shuffle=False, generator=None, drop_last=False):
-        self.dataset, self.batch_size, self.shuffle, self.drop_last = dataset, int(batch_size), shuffle, drop_last
-        self.generator = generator
-        self.last_order = None
+        super().__init__(dataset, batch_size, shuffle, generator, drop_last)
 
-    def __len__(self):
-        n, b = len(self.dataset), self.batch_size
-        return n // b if self.drop_last else (n + b - 1) // b
-
-    def __iter__(self):
-        ds, n = self.dataset, len(self.dataset)
-        order = torch.randperm(n, generator=self.generator) if self.shuffle else torch.arange(n)
-        self.last_order = order
-        order_dev = order.to(ds.signals.device)   # in range by construction: one upload per epoch, no per-batch check
-        for k in range(len(self)):
-            idx = order_dev[k * self.batch_size:(k + 1) * self.batch_size]
-            yield gather_augment(ds.signals, idx, augment=ds.augment, check_index=False, **AUG_DEFAULTS), ds.labels[idx]
+    def batch(self, idx):
+        ds = self.dataset
+        return gather_augment(ds.signals, idx, augment=ds.augment, check_index=False, **AUG_DEFAULTS), ds.labels[idx]
 
 
 def get_signalonly_dataloaders(config=Config, batch_size=8, label_map=LABEL_MAP, augment=True, split=SPLIT, max_len=MAX_LEN):
@@ -326,27 +277,15 @@ def get_signalonly_dataloaders(config=Config, batch_size=8, label_map=LABEL_MAP,
 def evaluate(model, loader, num_classes=2, predictor=None):
     """Softmax probabilities of the split -> accuracy / F1 / AUC (binary: class-1 probability thresholded at 0.5,
     train_physionet.py:359-379; more classes: argmax, macro F1, one-vs-rest AUC, train_physionet_multi.py:312-330)."""
-    from sklearn.metrics import f1_score, roc_auc_score
     model.eval()
-    y_true, y_prob = [], []
-    with torch.no_grad():
-        for signals, labels in loader:
-            logits = (model if predictor is None else predictor)(signals.unsqueeze(1))
-            y_prob.append(torch.softmax(logits.float(), dim=1).cpu().numpy())
-            y_true.append(labels.cpu().numpy())
-    y_true, y_prob = np.concatenate(y_true), np.concatenate(y_prob)
+    y_true, y_prob, _, _ = T.predict(model if predictor is None else predictor, loader, lambda x: x.unsqueeze(1))
     if num_classes == 2:
-        y_pred = (y_prob[:, 1] >= 0.5).astype(int)
-        f1 = float(f1_score(y_true, y_pred, zero_division=0))
-    else:
-        y_pred = np.argmax(y_prob, axis=1)
-        f1 = float(f1_score(y_true, y_pred, average="macro", zero_division=0))
-    try:
-        auc = float(roc_auc_score(y_true, y_prob[:, 1]) if num_classes == 2 else
-                    roc_auc_score(y_true, y_prob, multi_class="ovr"))
-    except ValueError:
-        auc = float("nan")
-    return {"accuracy": float((y_true == y_pred).mean()), "f1": f1, "auc": auc}
+        return T.binary_metrics(y_true, y_prob[:, 1], (y_prob[:, 1] >= 0.5).astype(int))
+    from sklearn.metrics import f1_score
+    y_pred = np.argmax(y_prob, axis=1)
+    return {"accuracy": float((y_true == y_pred).mean()),
+            "f1": float(f1_score(y_true, y_pred, average="macro", zero_division=0)),
+            "auc": T.auc_or_nan(y_true, y_prob, multi_class="ovr")}
 
 
 def main(config=Config, num_epochs=30, batch_size=8, quiet=False, use_predictor=False, num_classes=2, label_map=LABEL_MAP,
@@ -356,9 +295,7 @@ def main(config=Config, num_epochs=30, batch_size=8, quiet=False, use_predictor=
     ``use_predictor``: run the validation and test passes through an ``ecgmm.inference.Predictor`` (BatchNorm-folded
     inference plan), refreshed after every training epoch and after every checkpoint load.  Default off.
     -> (history, {"best": metrics, "last": metrics}, checkpoint directory)."""
-    torch.manual_seed(config.seed)
-    np.random.seed(config.seed)
-    HF.manual_seed(config.seed)
+    T.seed_all(config.seed, numpy=True)
     device = torch.device(config.device)
     if not quiet:
         print(f"Using device: {device}")
@@ -370,58 +307,38 @@ def main(config=Config, num_epochs=30, batch_size=8, quiet=False, use_predictor=
     optimizer = FusedAdam(model.parameters(), lr=0.001)
     scheduler = torch.optim.lr_scheduler.OneCycleLR(optimizer, max_lr=0.001, steps_per_epoch=len(train_loader),
                                                     epochs=num_epochs)
-    ckpt_dir = os.path.join(config.checkpoint_dir, time.strftime("%m%d_%H%M%S"))
-    os.makedirs(ckpt_dir, exist_ok=True)
+    ckpt_dir = T.run_dir(config.checkpoint_dir)
     predictor = None
     if use_predictor:
         from .inference import Predictor
         predictor = Predictor(model)
-    min_val, history = float("inf"), []
-    for epoch in range(num_epochs):
+
+    def step(batch, forward=model):
+        signals, labels = batch
+        out = forward(signals.unsqueeze(1))   # [B, L] -> [B, 1, L]
+        return criterion(out, labels), out, labels
+
+    def train_pass():
         model.train()
-        tl, correct, total = 0.0, 0, 0
-        for signals, labels in train_loader:
-            optimizer.zero_grad()
-            out = model(signals.unsqueeze(1))   # [B, L] -> [B, 1, L]
-            loss = criterion(out, labels)
-            loss.backward()
-            optimizer.step()
-            scheduler.step()
-            tl += loss.item()
-            correct += out.argmax(1).eq(labels).sum().item()
-            total += labels.size(0)
+        result = T.run_epoch(train_loader, step, optimizer, scheduler)
         model.eval()
-        if predictor is not None:
-            predictor.refresh()
-        vl, vc, vt = 0.0, 0, 0
-        with torch.no_grad():
-            for signals, labels in val_loader:
-                out = (model if predictor is None else predictor)(signals.unsqueeze(1))
-                vl += criterion(out, labels).item()
-                vc += out.argmax(1).eq(labels).sum().item()   # accumulated (the reference's `=` at :326 is a bug)
-                vt += labels.size(0)
-        avg = vl / max(len(val_loader), 1)
-        history.append(dict(epoch=epoch + 1, train_loss=tl / max(len(train_loader), 1), train_acc=correct / max(total, 1),
-                            val_loss=avg, val_acc=vc / max(vt, 1)))
+        return result
+
+    def val_pass():   # the accuracy is accumulated over the batches (the reference's `=` at :326 is a bug)
+        return T.run_epoch(val_loader, step if predictor is None else lambda batch: step(batch, predictor))
+
+    def on_epoch(h, _extras):
         if not quiet:
-            h = history[-1]
-            print(f"[{epoch + 1}] train {h['train_loss']:.4f}/{h['train_acc']:.4f}  val {avg:.4f}/{h['val_acc']:.4f}")
-        torch.save(model.state_dict(), os.path.join(ckpt_dir, "last.pth"))
-        if avg < min_val:   # train_physionet.py:335-341
-            min_val = avg
-            torch.save(model.state_dict(), os.path.join(ckpt_dir, "best.pth"))
-            torch.save(model.state_dict(), os.path.join(ckpt_dir, f"best_signal_only_epoch{epoch + 1}.pth"))
-    results = {}
-    for tag in ("best", "last"):
-        path = os.path.join(ckpt_dir, f"{tag}.pth")
-        if not os.path.exists(path):   # no epoch improved on inf (a NaN validation loss): nothing was saved as best
-            continue
-        model.load_state_dict(torch.load(path, map_location=device))
-        if predictor is not None:
-            predictor.refresh()
-        results[tag] = evaluate(model, test_loader, num_classes, predictor=predictor)
-        if not quiet:
-            print(f"test[{tag}]: {results[tag]}")
+            print(f"[{h['epoch']}] train {h['train_loss']:.4f}/{h['train_acc']:.4f}  val {h['val_loss']:.4f}/{h['val_acc']:.4f}")
+
+    # train_physionet.py:335-341: best.pth and best_signal_only_epochN.pth on a lower validation loss; no early stop
+    history = T.fit(model, optimizer, train_pass, val_pass, ckpt_dir, num_epochs,
+                    best_names=("best.pth", "best_signal_only_epoch{epoch}.pth"), predictor=predictor, on_epoch=on_epoch)
+    results = T.test_checkpoints(model, ckpt_dir, ("best", "last"),
+                                 lambda: evaluate(model, test_loader, num_classes, predictor=predictor), predictor)
+    if not quiet:
+        for tag, res in results.items():
+            print(f"test[{tag}]: {res}")
     return history, results, ckpt_dir
 
 

@@ -12,21 +12,19 @@ the class-1 softmax probability.
 Not carried over: the plots and the classification report.  The validation loader is not shuffled (the reference's
 ``shuffle=True`` at :164 changes nothing it reports: it only permutes the rows the validation loss and accuracy are
 accumulated over).  ``wfdb`` / ``pandas`` are replaced by :mod:`ecgmm.train_physionet`'s record
-reader and label table, which this module reuses.  NEW: ``config.physionet2_max_len`` (default ``None``) truncates longer
+reader and label table, which this module reuses; the loader base, the epoch loop and the metrics are ``ecgmm.training``'s.  NEW: ``config.physionet2_max_len`` (default ``None``) truncates longer
 records at the end before the transform.
 """
-import os
-import time
-
 import numpy as np
 import torch
 
+from . import training as T
 from .config import Config
 from .crnn import CRNN, FocalLoss
-from .hip import functional as HF
 from .optim import FusedAdam
 from .spectrogram import NPERSEG, compute_log_spectrogram, stft_frames
-from .train_physionet import LABEL_MAP, SPLIT, load_records, pad_sequences, read_labels, split_indices  # noqa: F401
+from .train_physionet import LABEL_MAP, SPLIT, load_records, pad_sequences, read_labels  # noqa: F401 -- the record reader
+from .training import split_indices
 
 
 def build_spectrograms(signals, device, chunk=1024):
@@ -64,26 +62,17 @@ class SpectrogramDataset:
         return self.spectrograms[self.indices[idx]], self.labels[idx]
 
 
-class DeviceSpectrogramLoader:
+class DeviceSpectrogramLoader(T.ResidentLoader):
     """Batches of a :class:`SpectrogramDataset`: ``(spectrograms [B, 1, 33, T] fp32, labels [B])``, both on the device.
     ``shuffle``: a ``torch.randperm`` of the seeded ``generator`` per epoch, kept in ``last_order``.  The last partial batch
     is kept (``DataLoader``'s default, which the reference uses)."""
 
     def __init__(self, dataset, batch_size=Config.batch_size, shuffle=False, generator=None):
-        self.dataset, self.batch_size, self.shuffle, self.generator = dataset, int(batch_size), shuffle, generator
-        self.last_order = None
+        super().__init__(dataset, batch_size, shuffle, generator)
 
-    def __len__(self):
-        return (len(self.dataset) + self.batch_size - 1) // self.batch_size
-
-    def __iter__(self):
-        ds, n = self.dataset, len(self.dataset)
-        order = torch.randperm(n, generator=self.generator) if self.shuffle else torch.arange(n)
-        self.last_order = order
-        order_dev = order.to(ds.indices.device)
-        for k in range(len(self)):
-            idx = order_dev[k * self.batch_size:(k + 1) * self.batch_size]
-            yield ds.spectrograms.index_select(0, ds.indices[idx]), ds.labels[idx]
+    def batch(self, idx):
+        ds = self.dataset
+        return ds.spectrograms.index_select(0, ds.indices[idx]), ds.labels[idx]
 
 
 def get_spectrogram_dataloaders(config=Config, batch_size=None, label_map=LABEL_MAP, split=SPLIT, chunk=1024):
@@ -105,30 +94,16 @@ def get_spectrogram_dataloaders(config=Config, batch_size=None, label_map=LABEL_
 def evaluate(model, loader):
     """train_physionet2.py:233-257: argmax predictions and the class-1 softmax probability of the split ->
     accuracy / binary F1 / ROC-AUC (NaN where sklearn cannot define it: one class only)."""
-    from sklearn.metrics import f1_score, roc_auc_score
     model.eval()
-    y_true, y_pred, y_prob = [], [], []
-    with torch.no_grad():
-        for spec, labels in loader:
-            logits = model(spec).float()
-            y_prob.append(torch.softmax(logits, dim=1)[:, 1].cpu().numpy())
-            y_pred.append(logits.argmax(1).cpu().numpy())
-            y_true.append(labels.cpu().numpy())
-    y_true, y_pred, y_prob = np.concatenate(y_true), np.concatenate(y_pred), np.concatenate(y_prob)
-    try:
-        auc = float(roc_auc_score(y_true, y_prob))
-    except ValueError:
-        auc = float("nan")
-    return {"accuracy": float((y_true == y_pred).mean()), "f1": float(f1_score(y_true, y_pred, zero_division=0)), "auc": auc}
+    y_true, y_prob, y_pred, _ = T.predict(model, loader)
+    return T.binary_metrics(y_true, y_prob[:, 1], y_pred)
 
 
 def main(config=Config, num_epochs=None, batch_size=None, quiet=False):
     """-> (history, {"best": metrics, "last": metrics}, checkpoint directory)."""
     num_epochs = config.num_epochs if num_epochs is None else num_epochs
     batch_size = config.batch_size if batch_size is None else batch_size
-    torch.manual_seed(config.seed)
-    np.random.seed(config.seed)
-    HF.manual_seed(config.seed)
+    T.seed_all(config.seed, numpy=True)
     device = torch.device(config.device)
     if not quiet:
         print(f"Using device: {device}")
@@ -136,48 +111,31 @@ def main(config=Config, num_epochs=None, batch_size=None, quiet=False):
     model = CRNN(compute_dtype=getattr(config, "compute_dtype", "bf16")).to(device)
     criterion = FocalLoss()
     optimizer = FusedAdam(model.parameters(), lr=config.lr)
-    ckpt_dir = os.path.join(config.checkpoint_dir, time.strftime("%m%d_%H%M%S"))
-    os.makedirs(ckpt_dir, exist_ok=True)
-    min_val, history = float("inf"), []
-    for epoch in range(num_epochs):
+    ckpt_dir = T.run_dir(config.checkpoint_dir)
+
+    def step(batch):
+        spec, labels = batch
+        out = model(spec)
+        return criterion(out, labels), out, labels
+
+    def train_pass():
         model.train()
-        tl, correct, total = 0.0, 0, 0
-        for spec, labels in train_loader:
-            optimizer.zero_grad()
-            out = model(spec)
-            loss = criterion(out, labels)
-            loss.backward()
-            optimizer.step()
-            tl += loss.item()
-            correct += out.argmax(1).eq(labels).sum().item()
-            total += labels.size(0)
-        torch.save(model.state_dict(), os.path.join(ckpt_dir, "last.pth"))
+        return T.run_epoch(train_loader, step, optimizer)
+
+    def val_pass():
         model.eval()
-        vl, vc, vt = 0.0, 0, 0
-        with torch.no_grad():
-            for spec, labels in val_loader:
-                out = model(spec)
-                vl += criterion(out, labels).item()
-                vc += out.argmax(1).eq(labels).sum().item()
-                vt += labels.size(0)
-        avg = vl / max(len(val_loader), 1)
-        history.append(dict(epoch=epoch + 1, train_loss=tl / max(len(train_loader), 1), train_acc=correct / max(total, 1),
-                            val_loss=avg, val_acc=vc / max(vt, 1)))
+        return T.run_epoch(val_loader, step)
+
+    def on_epoch(h, _extras):
         if not quiet:
-            h = history[-1]
-            print(f"[{epoch + 1}] train {h['train_loss']:.4f}/{h['train_acc']:.4f}  val {avg:.4f}/{h['val_acc']:.4f}")
-        if avg < min_val:   # train_physionet2.py:220-222
-            min_val = avg
-            torch.save(model.state_dict(), os.path.join(ckpt_dir, "best.pth"))
-    results = {}
-    for tag in ("best", "last"):
-        path = os.path.join(ckpt_dir, f"{tag}.pth")
-        if not os.path.exists(path):   # no epoch improved on inf (a NaN validation loss): nothing was saved as best
-            continue
-        model.load_state_dict(torch.load(path, map_location=device))
-        results[tag] = evaluate(model, test_loader)
-        if not quiet:
-            print(f"test[{tag}]: {results[tag]}")
+            print(f"[{h['epoch']}] train {h['train_loss']:.4f}/{h['train_acc']:.4f}  val {h['val_loss']:.4f}/{h['val_acc']:.4f}")
+
+    # train_physionet2.py:220-222: best.pth on a lower validation loss; no scheduler, no early stop
+    history = T.fit(model, optimizer, train_pass, val_pass, ckpt_dir, num_epochs, on_epoch=on_epoch)
+    results = T.test_checkpoints(model, ckpt_dir, ("best", "last"), lambda: evaluate(model, test_loader))
+    if not quiet:
+        for tag, res in results.items():
+            print(f"test[{tag}]: {res}")
     return history, results, ckpt_dir
 
 

@@ -1,14 +1,12 @@
 """12-lead signal-only trainer (reference: train_signal_12_af.py:238-444; BASELINE config 5):
 ResNet1D_SE(input_channels=12) + FocalLoss(1, 2) + Adam(1e-3) + OneCycleLR(max_lr=1e-3) stepped per
-batch.  Data: synthetic [12, L] series (the reference's per-patient xlsx files are private)."""
-import os
-import time
-
+batch; last.pth every epoch, best.pth on a lower validation loss, stop after 5 misses (``ecgmm.training.fit``).
+Data: synthetic [12, L] series (the reference's per-patient xlsx files are private)."""
 import torch
 from torch.utils.data import DataLoader, Dataset
 
+from . import training as T
 from .config import Config
-from .hip import functional as HF
 from .optim import FusedAdam
 from .signal_model import FocalLoss, ResNet1D_SE
 
@@ -36,8 +34,8 @@ def get_signalonly_dataloaders(batch_size=8, length=5000):
 
 
 def main(epochs=30, batch_size=8, length=5000, quiet=False):
-    torch.manual_seed(42)
-    HF.manual_seed(42)
+    """-> ([(train loss, train accuracy, val loss, val accuracy) per epoch], checkpoint directory)"""
+    T.seed_all(42)
     device = torch.device(Config.device)
     train_loader, val_loader, test_loader = get_signalonly_dataloaders(batch_size, length)
     model = ResNet1D_SE(input_channels=12, compute_dtype=getattr(Config, "compute_dtype", "bf16")).to(device)
@@ -45,45 +43,28 @@ def main(epochs=30, batch_size=8, length=5000, quiet=False):
     optimizer = FusedAdam(model.parameters(), lr=0.001)
     scheduler = torch.optim.lr_scheduler.OneCycleLR(optimizer, max_lr=0.001, steps_per_epoch=len(train_loader),
                                                     epochs=epochs)
-    ckpt_dir = os.path.join("./checkpoints", time.strftime("%m%d_%H%M%S"))
-    os.makedirs(ckpt_dir, exist_ok=True)
-    min_val, early, hist = float("inf"), 0, []
-    for epoch in range(epochs):
+    ckpt_dir = T.run_dir("./checkpoints")
+
+    def step(batch):
+        signals, labels = batch[0].to(device), batch[1].to(device)
+        out = model(signals)
+        return criterion(out, labels), out, labels
+
+    def train_pass():
         model.train()
-        tl, correct, total = 0.0, 0, 0
-        for signals, labels in train_loader:
-            signals, labels = signals.to(device), labels.to(device)
-            optimizer.zero_grad()
-            out = model(signals)
-            loss = criterion(out, labels)
-            loss.backward()
-            optimizer.step()
-            scheduler.step()
-            tl += loss.item()
-            correct += out.argmax(1).eq(labels).sum().item()
-            total += labels.size(0)
+        return T.run_epoch(train_loader, step, optimizer, scheduler)
+
+    def val_pass():   # the accuracy is accumulated over the batches (the reference's `=` at :295 is a bug)
         model.eval()
-        vl, vc, vt = 0.0, 0, 0
-        with torch.no_grad():
-            for signals, labels in val_loader:
-                signals, labels = signals.to(device), labels.to(device)
-                out = model(signals)
-                vl += criterion(out, labels).item()
-                vc += out.argmax(1).eq(labels).sum().item()   # accumulated (the reference's `=` at :295 is a bug)
-                vt += labels.size(0)
-        avg = vl / max(len(val_loader), 1)
-        hist.append((tl / max(len(train_loader), 1), correct / max(total, 1), avg, vc / max(vt, 1)))
+        return T.run_epoch(val_loader, step)
+
+    def on_epoch(h, _extras):
         if not quiet:
-            print(f"epoch {epoch + 1}: train {hist[-1][0]:.4f}/{hist[-1][1]:.3f} val {avg:.4f}/{hist[-1][3]:.3f}")
-        torch.save(model.state_dict(), os.path.join(ckpt_dir, "last.pth"))
-        if avg < min_val:
-            min_val, early = avg, 0
-            torch.save(model.state_dict(), os.path.join(ckpt_dir, "best.pth"))
-        else:
-            early += 1
-            if early >= 5:
-                break
-    return hist, ckpt_dir
+            print(f"epoch {h['epoch']}: train {h['train_loss']:.4f}/{h['train_acc']:.3f} "
+                  f"val {h['val_loss']:.4f}/{h['val_acc']:.3f}")
+
+    history = T.fit(model, optimizer, train_pass, val_pass, ckpt_dir, epochs, patience=5, on_epoch=on_epoch)
+    return [(h["train_loss"], h["train_acc"], h["val_loss"], h["val_acc"]) for h in history], ckpt_dir
 
 
 if __name__ == "__main__":

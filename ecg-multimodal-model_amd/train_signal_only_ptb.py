@@ -10,6 +10,9 @@ the indices on the device and one gather launch per batch collects the rows.  Mo
 reference's: ``ResNet1D_SE`` on ``[B, 1, 2476]``, ``FocalLoss()``, Adam(1e-3), ``OneCycleLR(epochs=30)`` stepped per batch
 while 10 epochs run (train_signal_only_ptb.py:254,257: the schedule never leaves its first third; kept).
 
+This module holds the record reader, the labels, the resident dataset, the sampler and the policy values; the loader is
+``ecgmm.preprocess.PTBXLLoader`` (shared with ``evaluation_signal``), the epoch loop and the metrics are ``ecgmm.training``'s.
+
 ``wfdb`` is replaced by :func:`read_header` / :func:`read_record_i16` / :func:`rdsamp` (format 16, one ``.dat`` per record),
 ``pandas`` by the ``csv`` module, ``eval`` of the ``scp_codes`` column by ``ast.literal_eval``.  Not carried over: the figures
 (confusion matrix, ROC curve); the 100 Hz ``filename_lr`` records; WFDB formats other than 16.
@@ -18,17 +21,17 @@ import ast
 import csv
 import os
 import re
-import time
 
 import numpy as np
 import torch
 
 from . import preprocess as PP
+from . import training as T
 from .config import Config
-from .hip import functional as HF
 from .optim import FusedAdam
+from .preprocess import PTBXLLoader   # noqa: F401 -- shared with evaluation_signal; this name is part of this module
 from .signal_model import FocalLoss, ResNet1D_SE, find_best_threshold
-from .train_physionet import DeviceSignalLoader, gather_augment, split_indices
+from .training import split_indices
 
 LENGTH = 2476
 SPLIT = (0.4, 0.5)             # train_signal_only_ptb.py:227-228: 60 % train, the remaining 40 % halved
@@ -277,39 +280,6 @@ class DeviceWeightedSampler:
         return PP.weighted_sample(self._cdf, self.last_positive, self.num_samples, seed_offset, return_uniforms)
 
 
-class PTBXLLoader(DeviceSignalLoader):
-    """:class:`DeviceSignalLoader` over a :class:`PTBXLSignalDataset` with an optional ``sampler``: batches
-    ``(signals [B, leads, length], labels [B])`` on the device, one gather launch each.  Under a sampler the epoch has
-    ``len(sampler)`` samples and ``last_order`` holds the indices it drew; without one the order is the parent's."""
-
-    def __init__(self, dataset, batch_size=16, shuffle=False, generator=None, drop_last=False, sampler=None):
-        if sampler is not None and shuffle:
-            raise ValueError("PTBXLLoader: sampler and shuffle are mutually exclusive")   # as torch's DataLoader
-        super().__init__(dataset, batch_size, shuffle, generator, drop_last)
-        self.sampler = sampler
-
-    def _count(self):
-        return len(self.dataset) if self.sampler is None else len(self.sampler)
-
-    def __len__(self):
-        n, b = self._count(), self.batch_size
-        return n // b if self.drop_last else (n + b - 1) // b
-
-    def __iter__(self):
-        ds, n = self.dataset, len(self.dataset)
-        if self.sampler is not None:
-            order_dev = self.sampler.sample()          # in [0, n) by construction of the kernel: no per-batch check
-            self.last_order = order_dev.cpu()
-        else:
-            order = torch.randperm(n, generator=self.generator) if self.shuffle else torch.arange(n)
-            self.last_order, order_dev = order, order.to(ds.signals.device)
-        flat = ds.signals.view(n, -1)
-        for k in range(len(self)):
-            idx = order_dev[k * self.batch_size:(k + 1) * self.batch_size]
-            x = gather_augment(flat, idx, augment=False, check_index=False)
-            yield x.view(idx.numel(), *ds.signals.shape[1:]), ds.labels[idx]
-
-
 def get_ptbxl_dataloaders(config=Config, batch_size=16, length=LENGTH, leads=(1,), split=SPLIT):
     """train (weighted sampler) / val / test loaders, train_signal_only_ptb.py:183-243."""
     records, labels = load_ptbxl(config)
@@ -326,31 +296,10 @@ def get_ptbxl_dataloaders(config=Config, batch_size=16, length=LENGTH, leads=(1,
 # --------------------------------------------------------------------------------------------
 # training                                                          reference: :247-328
 # --------------------------------------------------------------------------------------------
-def _probabilities(model, loader, criterion=None, predictor=None):
-    """-> (labels, class-1 probabilities, mean batch loss or None) of a loader, in eval mode"""
-    y_true, y_prob, loss, fwd = [], [], 0.0, model if predictor is None else predictor
-    with torch.no_grad():
-        for signals, labels in loader:
-            out = fwd(signals)
-            if criterion is not None:
-                loss += criterion(out, labels).item()
-            y_prob.append(torch.softmax(out.float(), dim=1)[:, 1].cpu().numpy())
-            y_true.append(labels.cpu().numpy())
-    return np.concatenate(y_true), np.concatenate(y_prob), (loss / max(len(loader), 1) if criterion is not None else None)
-
-
 def make_scheduler(optimizer, steps_per_epoch, schedule_epochs=30):
     """train_signal_only_ptb.py:254: the cycle is sized for 30 epochs whatever the number of epochs that run (:257 runs 10,
     so the learning rate is still rising when training stops).  Kept as the reference has it."""
     return torch.optim.lr_scheduler.OneCycleLR(optimizer, max_lr=0.001, steps_per_epoch=steps_per_epoch, epochs=schedule_epochs)
-
-
-def _auc(y_true, y_prob):
-    from sklearn.metrics import roc_auc_score
-    try:
-        return float(roc_auc_score(y_true, y_prob))
-    except ValueError:     # one class only, or NaN probabilities
-        return float("nan")
 
 
 def main(config=Config, num_epochs=10, schedule_epochs=30, batch_size=16, quiet=False, use_predictor=False, length=LENGTH,
@@ -358,13 +307,10 @@ def main(config=Config, num_epochs=10, schedule_epochs=30, batch_size=16, quiet=
     """``use_predictor``: validation and test run through an ``ecgmm.inference.Predictor`` (BatchNorm-folded inference
     plan), refreshed after every training epoch and after the checkpoint load.  Default off.
     -> (history, test metrics with the classification report as text, checkpoint directory)."""
-    from sklearn.metrics import classification_report, f1_score
-    torch.manual_seed(config.seed)
-    np.random.seed(config.seed)
-    HF.manual_seed(config.seed)
+    from sklearn.metrics import classification_report
+    T.seed_all(config.seed, numpy=True)
     device = torch.device(config.device)
-    ckpt_dir = os.path.join(config.checkpoint_dir, "signal", time.strftime("%m%d_%H%M%S"))
-    os.makedirs(ckpt_dir, exist_ok=True)
+    ckpt_dir = T.run_dir(config.checkpoint_dir, "signal")
     train_loader, val_loader, test_loader = get_ptbxl_dataloaders(config, batch_size, length, leads, split)
     if not quiet:
         print(f"Train: {len(train_loader.dataset)} | Val: {len(val_loader.dataset)} | Test: {len(test_loader.dataset)}")
@@ -376,41 +322,40 @@ def main(config=Config, num_epochs=10, schedule_epochs=30, batch_size=16, quiet=
     if use_predictor:
         from .inference import Predictor
         predictor = Predictor(model)
-    best_val_loss, history = float("inf"), []
-    for epoch in range(num_epochs):
+    forward = model if predictor is None else predictor
+
+    def step(batch):
+        signals, labels = batch
+        out = model(signals)
+        return criterion(out, labels), out, labels
+
+    def train_pass():   # the reference reports no training accuracy: one host read per step, the loss
         model.train()
-        train_loss = 0.0
-        for signals, labels in train_loader:
-            optimizer.zero_grad()
-            loss = criterion(model(signals), labels)
-            loss.backward()
-            optimizer.step()
-            scheduler.step()
-            train_loss += loss.item()
+        result = T.run_epoch(train_loader, step, optimizer, scheduler, count_correct=False)
         model.eval()
-        if predictor is not None:
-            predictor.refresh()
-        y_true, y_prob, val_loss = _probabilities(model, val_loader, criterion, predictor)
-        history.append(dict(epoch=epoch + 1, train_loss=train_loss / max(len(train_loader), 1), val_loss=val_loss,
-                            val_auc=_auc(y_true, y_prob)))
+        return result
+
+    def val_pass():
+        y_true, y_prob, _, val_loss = T.predict(forward, val_loader, criterion=criterion)
+        return val_loss, None, {"val_auc": T.auc_or_nan(y_true, y_prob[:, 1])}
+
+    def on_epoch(h, extras):
+        h.update(extras)
         if not quiet:
-            h = history[-1]
-            print(f"Epoch [{epoch + 1}] | Train Loss: {h['train_loss']:.4f} | Val Loss: {val_loss:.4f} | Val AUC: {h['val_auc']:.4f}")
-        if val_loss < best_val_loss:   # :289-291
-            torch.save(model.state_dict(), os.path.join(ckpt_dir, "best.pth"))
-            best_val_loss = val_loss
+            print(f"Epoch [{h['epoch']}] | Train Loss: {h['train_loss']:.4f} | Val Loss: {h['val_loss']:.4f} | "
+                  f"Val AUC: {h['val_auc']:.4f}")
+
+    # :289-291: best.pth on a lower validation loss, nothing else is saved
+    history = T.fit(model, optimizer, train_pass, val_pass, ckpt_dir, num_epochs, save_last=None, predictor=predictor,
+                    on_epoch=on_epoch)
+    # best.pth is absent only when no validation loss was below inf (NaN): then there are no results
+    scored = T.test_checkpoints(model, ckpt_dir, ("best",), lambda: T.predict(forward, test_loader), predictor)
     results = {}
-    best = os.path.join(ckpt_dir, "best.pth")
-    if os.path.exists(best):           # absent only when no validation loss was below inf (NaN)
-        model.load_state_dict(torch.load(best, map_location=device))
-        model.eval()
-        if predictor is not None:
-            predictor.refresh()
-        y_true, y_prob, _ = _probabilities(model, test_loader, None, predictor)
+    if scored:
+        y_true, y_prob = scored["best"][0], scored["best"][1][:, 1]
         best_t = float(find_best_threshold(y_true, y_prob))
         y_pred = (y_prob >= best_t).astype(int)
-        results = dict(threshold=best_t, accuracy=float((y_true == y_pred).mean()),
-                       f1=float(f1_score(y_true, y_pred, zero_division=0)), auc=_auc(y_true, y_prob),
+        results = dict(threshold=best_t, **T.binary_metrics(y_true, y_prob, y_pred),
                        report=classification_report(y_true, y_pred, labels=[0, 1], target_names=["Normal", "AF"],
                                                     zero_division=0))
         if not quiet:
