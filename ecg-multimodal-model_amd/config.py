@@ -61,3 +61,4 @@ class Config:
     synthetic_test_size = 32
     num_workers = 0
     physionet2_max_len = None       # train_physionet2: truncate longer records before the spectrogram (None: keep all)
+    physionet2_use_lengths = False  # train_physionet2: each record's own length to the BiLSTM and the mean over time

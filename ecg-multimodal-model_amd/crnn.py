@@ -47,7 +47,11 @@ class CRNN(nn.Module):
             buffers += [bn.running_mean, bn.running_var, bn.num_batches_tracked]
         return params, buffers
 
-    def forward(self, x):
+    def forward(self, x, lengths=None):
+        """``x [B, 1, F, T]``.  ``lengths``: the valid spectrogram frames of each record (``x`` zero-padded behind them).
+        The LSTM and the mean over time then take ``clamp(lengths // 8, 1, T // 8)`` steps per record -- three floor pools
+        give exactly ``// 8`` -- so the recurrence neither runs through the padding nor averages it in.  The convolution
+        front end and its BatchNorm statistics stay as they are, padding included: that is the reference's arithmetic."""
         if not x.is_cuda:
             raise RuntimeError(f"CRNN: tensor is on {x.device}; the HIP library is the only compute path (no CPU fallback) "
                                "-- move the model and inputs to a ROCm device")
@@ -62,5 +66,11 @@ class CRNN(nn.Module):
         params, buffers = self._front_tables()
         bn = self.conv1.block[1]
         seq = HF.crnn_front(x, params, buffers, self.training, bn.momentum, bn.eps, self._dtype)
-        out, _ = self.bilstm(seq)
-        return self.classifier(HF.seq_mean(out))
+        if lengths is None:
+            out, _ = self.bilstm(seq)
+            return self.classifier(HF.seq_mean(out))
+        steps = seq.shape[1]
+        lengths = HF.check_lengths(lengths, x.shape[0], x.shape[3]).to(x.device)
+        lengths = torch.clamp(lengths // 8, 1, steps).to(torch.int32)
+        out, _ = self.bilstm(seq, lengths=lengths)
+        return self.classifier(HF.seq_mean(out, lengths))

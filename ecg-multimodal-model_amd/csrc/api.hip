@@ -411,13 +411,31 @@ size_t ecgmm_lstm_fwd_workspace(const ecgmm_lstm_desc* d) { return ecg_lstm_fwd_
 size_t ecgmm_lstm_bwd_workspace(const ecgmm_lstm_desc* d) { return ecg_lstm_bwd_workspace(d); }
 int ecgmm_lstm_forward(const ecgmm_lstm_desc* d, const float* x, const float* const* params, const float* h0,
                        const float* c0, float* y, float* hn, float* cn, void* ws, size_t ws_bytes, void* stream) {
-  return ecg_lstm_forward(d, x, params, h0, c0, y, hn, cn, ws, ws_bytes, S_(stream));
+  return ecg_lstm_forward(d, x, nullptr, params, h0, c0, y, hn, cn, ws, ws_bytes, S_(stream));
 }
 int ecgmm_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const float* const* params, const float* h0,
                         const float* c0, const float* dy, const float* dhn, const float* dcn, const void* ws, float* dx,
                         float* const* grads, float* dh0, float* dc0, void* scratch, size_t scratch_bytes, void* stream) {
-  return ecg_lstm_backward(d, x, params, h0, c0, dy, dhn, dcn, ws, dx, grads, dh0, dc0, scratch, scratch_bytes,
+  return ecg_lstm_backward(d, x, nullptr, params, h0, c0, dy, dhn, dcn, ws, dx, grads, dh0, dc0, scratch, scratch_bytes,
                            S_(stream));
+}
+int ecgmm_lstm_forward_varlen(const ecgmm_lstm_desc* d, const float* x, const int32_t* lengths, const float* const* params,
+                              const float* h0, const float* c0, float* y, float* hn, float* cn, void* ws, size_t ws_bytes,
+                              void* stream) {
+  return ecg_lstm_forward(d, x, lengths, params, h0, c0, y, hn, cn, ws, ws_bytes, S_(stream));
+}
+int ecgmm_lstm_backward_varlen(const ecgmm_lstm_desc* d, const float* x, const int32_t* lengths, const float* const* params,
+                               const float* h0, const float* c0, const float* dy, const float* dhn, const float* dcn,
+                               const void* ws, float* dx, float* const* grads, float* dh0, float* dc0, void* scratch,
+                               size_t scratch_bytes, void* stream) {
+  return ecg_lstm_backward(d, x, lengths, params, h0, c0, dy, dhn, dcn, ws, dx, grads, dh0, dc0, scratch, scratch_bytes,
+                           S_(stream));
+}
+int ecgmm_seq_mean_varlen_fwd(const float* x, const int32_t* lengths, float* out, int B, int T, int C, void* stream) {
+  return ecg_seq_mean_varlen_fwd(x, lengths, out, B, T, C, S_(stream));
+}
+int ecgmm_seq_mean_varlen_bwd(const float* dy, const int32_t* lengths, float* dx, int B, int T, int C, void* stream) {
+  return ecg_seq_mean_varlen_bwd(dy, lengths, dx, B, T, C, S_(stream));
 }
 
 // ---- CRNN front end, per-op (crnn_front.hip; train_physionet2.py:55-65, 87-93) ----

@@ -19,6 +19,19 @@
 // Any H works: H % 4 != 0 (or a W_hh that is not 16-byte aligned) takes 4-byte W_hh loads in the forward.
 // LSTM_MAX_H = 384: the backward stages 16 x (4 Hp + 4) gate gradients + 2 x 16 x (Hp + 4) carries in LDS (Hp = H rounded
 // up to 16) = 148 KiB at H = 384 of the 160 KiB of a CU; the forward needs 3 x 16 x (Hp + 4) floats (73 KiB).
+//
+// Variable lengths (ecg_lstm_forward / _backward with lengths != null) are the VL = true instantiations of the same two
+// kernels; VL = false computes what it computed before there were lengths, bit for bit.  Row b is live at step t iff
+// t < lengths[b] (clamped to [0, T]), in both directions: torch's packed LSTM re-padded.  A workgroup keeps its 16 lengths behind its other LDS arrays (+ 64 B) and runs
+// only tmax = max of them steps (uniform over the workgroup: every barrier is reached by every thread).
+//   forward   dead row: h copied to the other buffer, c left, y = 0, hprev = the held h (finite: the dW_hh GEMM reads every
+//             row of hprev, and 0 * NaN is NaN).  Steps tmax .. T-1 of the slice get y = 0, hprev = 0 before the walk.
+//             h_n is the buffer of parity tmax, not T.
+//   backward  the executed steps in the opposite order; c_{t-1} = c0 at the ROW's first step (t = 0 forward, t = len-1
+//             reverse); dead row: dgates = 0 (and over tmax .. T-1: the GEMMs read all B T rows), dc and dh carries kept.
+//             The cell arithmetic is one code path for both instantiations, contraction pinned (see the kernel): lengths
+//             all T give the fixed call's bits.
+// The projection / gradient GEMMs stay over all B T rows; padded x meets exact zeros there, so it must be finite.
 #include "ops.h"
 
 namespace {
@@ -46,6 +59,7 @@ struct LstmFwdDir {
 };
 struct LstmFwdArgs {
   LstmFwdDir d[2];
+  const int* lengths;   // [B] or null (VL kernels only)
   int B, T, H, ldo, batch_first, save;
 };
 
@@ -64,6 +78,7 @@ struct LstmBwdDir {
 };
 struct LstmBwdArgs {
   LstmBwdDir d[2];
+  const int* lengths;   // [B] or null (VL kernels only)
   int B, T, H, ldo, batch_first;
 };
 
@@ -71,7 +86,22 @@ __device__ __forceinline__ size_t seq_row(int b, int t, int B, int T, int batch_
   return batch_first ? (size_t)b * T + t : (size_t)t * B + b;
 }
 
-template <bool V4>
+// the slice's 16 lengths, clamped to [0, T] (0 for rows >= B), into LDS; call before the set-up barrier
+__device__ __forceinline__ void load_slice_lengths(int* len, const int* lengths, int b0, int B, int T) {
+  if (threadIdx.x < LSTM_ROWS) {
+    const int b = b0 + threadIdx.x;
+    int l = b < B ? lengths[b] : 0;
+    len[threadIdx.x] = l < 0 ? 0 : (l > T ? T : l);
+  }
+}
+__device__ __forceinline__ int slice_tmax(const int* len) {
+  int m = 0;
+#pragma unroll
+  for (int r = 0; r < LSTM_ROWS; ++r) m = len[r] > m ? len[r] : m;
+  return m;
+}
+
+template <bool V4, bool VL>
 __global__ __launch_bounds__(LSTM_THREADS) void lstm_seq_fwd_kernel(LstmFwdArgs a) {
   extern __shared__ float lstm_lds[];
   const LstmFwdDir& p = a.d[blockIdx.y];
@@ -89,12 +119,27 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_seq_fwd_kernel(LstmFwdArgs 
     hb[LSTM_ROWS * HS + e] = 0.f;
     cb[e] = ok && p.c0 ? p.c0[(size_t)(b0 + b) * H + j] : 0.f;
   }
+  int* len = reinterpret_cast<int*>(lstm_lds + 3 * LSTM_ROWS * HS);   // [16], VL only
+  if (VL) load_slice_lengths(len, a.lengths, b0, B, T);
   __syncthreads();
+  const int tmax = VL ? slice_tmax(len) : T;   // executed steps: uniform over the workgroup
+  int lr[4];                                   // lengths of this lane's four rows of the C/D tile
+#pragma unroll
+  for (int r = 0; r < 4; ++r) lr[r] = VL ? len[g4 * 4 + r] : T;
+  if (VL) {   // steps tmax .. T-1 of the slice: y = 0 and a finite hprev
+    const int nb = B - b0 < LSTM_ROWS ? B - b0 : LSTM_ROWS;
+    for (int e = tid; e < (T - tmax) * nb * H; e += LSTM_THREADS) {
+      const int tt = tmax + e / (nb * H), q = e % (nb * H), b = b0 + q / H, j = q % H;
+      const size_t row = seq_row(b, tt, B, T, a.batch_first);
+      p.out[row * a.ldo + j] = 0.f;
+      if (a.save) p.hprev[row * H + j] = 0.f;
+    }
+  }
 
   const size_t HH = (size_t)H * H;
   const int G4 = 4 * H;
-  for (int s = 0; s < T; ++s) {
-    const int t = p.reverse ? T - 1 - s : s;
+  for (int s = 0; s < tmax; ++s) {
+    const int t = p.reverse ? tmax - 1 - s : s;
     const float* hc = hb + (s & 1) * LSTM_ROWS * HS;
     float* hx = hb + ((s + 1) & 1) * LSTM_ROWS * HS;
     for (int ht = wave; ht * 16 < Hp; ht += LSTM_WAVES) {
@@ -150,6 +195,14 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_seq_fwd_kernel(LstmFwdArgs 
         const float gg = tanhf(acc[2][r] + xg[2][r] + bh[2]);
         const float og = sigmoidf_(acc[3][r] + xg[3][r] + bh[3]);
         const float hp = hc[bl * HS + j];
+        if (VL && t >= lr[r]) {   // dead row: hold h and c, y = 0; the held h is the finite hprev the dW_hh GEMM reads
+          hx[bl * HS + j] = hp;
+          if (rok[r]) {
+            p.out[row[r] * a.ldo + j] = 0.f;
+            if (a.save) p.hprev[row[r] * H + j] = hp;
+          }
+          continue;
+        }
         const float c = fg * cb[bl * HS + j] + ig * gg;
         const float h = og * tanhf(c);
         cb[bl * HS + j] = jok ? c : 0.f;
@@ -168,7 +221,7 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_seq_fwd_kernel(LstmFwdArgs 
     __syncthreads();
   }
 
-  const float* hl = hb + (T & 1) * LSTM_ROWS * HS;
+  const float* hl = hb + (tmax & 1) * LSTM_ROWS * HS;   // the buffer the last executed step wrote (h0 when none ran)
   for (int e = tid; e < LSTM_ROWS * H; e += LSTM_THREADS) {
     const int b = e / H, j = e - b * H;
     if (b0 + b < B) {
@@ -178,6 +231,7 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_seq_fwd_kernel(LstmFwdArgs 
   }
 }
 
+template <bool VL>
 __global__ __launch_bounds__(LSTM_THREADS) void lstm_seq_bwd_kernel(LstmBwdArgs a) {
   extern __shared__ float lstm_lds[];
   const LstmBwdDir& p = a.d[blockIdx.y];
@@ -196,12 +250,25 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_seq_bwd_kernel(LstmBwdArgs 
     dhb[e] = ok && p.dhn ? p.dhn[(size_t)(b0 + b) * H + j] : 0.f;
     dcb[e] = ok && p.dcn ? p.dcn[(size_t)(b0 + b) * H + j] : 0.f;
   }
+  int* len = reinterpret_cast<int*>(dcb + LSTM_ROWS * HS);   // [16], VL only
+  if (VL) load_slice_lengths(len, a.lengths, b0, B, T);
   __syncthreads();
+  const int tmax = VL ? slice_tmax(len) : T;   // the steps the forward executed: uniform over the workgroup
+  int lr[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) lr[r] = VL ? len[g4 * 4 + r] : T;
 
   const int G4 = 4 * H;
-  for (int s = 0; s < T; ++s) {
-    const int t = p.reverse ? s : T - 1 - s;          // the forward walk, backwards
-    const bool first = s == T - 1;                    // the forward's first step: c_{t-1} = c0
+  if (VL) {   // steps tmax .. T-1 of the slice: the GEMMs after this kernel read all B T rows of dgates
+    const int nb = B - b0 < LSTM_ROWS ? B - b0 : LSTM_ROWS;
+    for (int e = tid; e < (T - tmax) * nb * G4; e += LSTM_THREADS) {
+      const int tt = tmax + e / (nb * G4), q = e % (nb * G4), b = b0 + q / G4, n = q % G4;
+      p.dgates[seq_row(b, tt, B, T, a.batch_first) * G4 + n] = 0.f;
+    }
+  }
+  for (int s = 0; s < tmax; ++s) {
+    const int t = p.reverse ? s : tmax - 1 - s;       // the forward walk, backwards
+    const bool first = s == tmax - 1;                 // (fixed lengths) the forward's first step: c_{t-1} = c0
     const int tp = p.reverse ? t + 1 : t - 1;
     for (int ht = wave; ht * 16 < Hp; ht += LSTM_WAVES) {
       const int j = ht * 16 + i16;
@@ -210,21 +277,37 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_seq_bwd_kernel(LstmBwdArgs 
       for (int r = 0; r < 4; ++r) {
         const int bl = g4 * 4 + r, b = b0 + bl;
         float di = 0.f, df = 0.f, dg = 0.f, dop = 0.f, dcp = 0.f;
+        // A dead row (VL) runs the same arithmetic on whatever its position holds (in bounds; the result is dropped by the
+        // selects below) instead of branching around it: the live rows' arithmetic then compiles to the contractions of the
+        // fixed kernel, so that lengths all T, and a row alone at T = its length, give the fixed call's bits.
+        const bool live = !VL || t < lr[r];
         if (jok && b < B) {
+          // Contraction is off in this block and the two fused multiply-adds the fixed kernel has always compiled to
+          // (1 - tanh^2 c, and dc) are spelled out: left to the compiler, the VL instantiation fuses other products than the
+          // fixed one (they land in different basic blocks), and lengths all T would differ from the fixed call in the last bit.
+          // From here on these two fmas and the unfused products DEFINE the backward's arithmetic, for both instantiations: they
+          // no longer follow a compiler's choice, and a change to them changes the results of the fixed entry point too.
+#pragma clang fp contract(off)
           const size_t row = seq_row(b, t, B, T, a.batch_first);
           const float* gp = p.gates + row * G4 + j;
           const float ig = gp[0], fg = gp[H], gg = gp[2 * H], og = gp[3 * H];
           const float c = p.csave[row * H + j];
-          const float cp = first ? (p.c0 ? p.c0[(size_t)b * H + j] : 0.f)
-                                 : p.csave[seq_row(b, tp, B, T, a.batch_first) * H + j];
+          // with lengths the ROW's first forward step: t = 0 forward, t = len - 1 reverse (a dead row: no step t +- 1 read)
+          const bool rfirst = VL ? (!live || (p.reverse ? t == lr[r] - 1 : t == 0)) : first;
+          const float cp = rfirst ? (p.c0 ? p.c0[(size_t)b * H + j] : 0.f)
+                                  : p.csave[seq_row(b, tp, B, T, a.batch_first) * H + j];
           const float dh = (p.dy ? p.dy[row * a.ldo + j] : 0.f) + dhb[bl * HS + j];
           const float tc = tanhf(c);
-          const float dc = dcb[bl * HS + j] + dh * og * (1.f - tc * tc);
+          const float dc = __builtin_fmaf(dh * og, __builtin_fmaf(-tc, tc, 1.f), dcb[bl * HS + j]);
           dop = dh * tc * og * (1.f - og);
           di = dc * gg * ig * (1.f - ig);
           df = dc * cp * fg * (1.f - fg);
           dg = dc * ig * (1.f - gg * gg);
           dcp = dc * fg;
+          if (VL) {   // dead row: exact-zero gate gradients, the dc carry kept (dh: below); dy there is not used
+            di = live ? di : 0.f; df = live ? df : 0.f; dg = live ? dg : 0.f; dop = live ? dop : 0.f;
+            dcp = live ? dcp : dcb[bl * HS + j];
+          }
           float* dq = p.dgates + row * G4 + j;
           dq[0] = di; dq[H] = df; dq[2 * H] = dg; dq[3 * H] = dop;
         }
@@ -258,7 +341,9 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_seq_bwd_kernel(LstmBwdArgs 
           for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[g][u], wv[g][u], acc[g], 0, 0, 0);
       }
 #pragma unroll
-      for (int r = 0; r < 4; ++r) dhb[(g4 * 4 + r) * HS + k] = (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]);
+      for (int r = 0; r < 4; ++r)
+        if (!VL || t < lr[r])   // a dead row keeps its dh carry
+          dhb[(g4 * 4 + r) * HS + k] = (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]);
     }
     __syncthreads();
   }
@@ -272,10 +357,36 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_seq_bwd_kernel(LstmBwdArgs 
   }
 }
 
-inline size_t fwd_lds(int H) { const int Hp = (H + 15) & ~15; return (size_t)3 * LSTM_ROWS * (Hp + 4) * sizeof(float); }
-inline size_t bwd_lds(int H) {
+// out[b][c] = sum_{t < len_b} x[b][t][c] / len_b, t in order; one thread per (b, c), consecutive c in a wave
+__global__ __launch_bounds__(256) void seq_mean_varlen_fwd_kernel(const float* __restrict__ x, const int* __restrict__ lengths,
+                                                                  float* __restrict__ out, int T, int C) {
+  const int b = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  int l = lengths[b];
+  l = l < 0 ? 0 : (l > T ? T : l);
+  const float* xp = x + (size_t)b * T * C + c;
+  float acc = 0.f;
+  for (int t = 0; t < l; ++t) acc += xp[(size_t)t * C];
+  out[(size_t)b * C + c] = l > 0 ? acc / (float)l : 0.f;
+}
+// dx[b][t][c] = t < len_b ? dy[b][c] / len_b : 0
+__global__ __launch_bounds__(256) void seq_mean_varlen_bwd_kernel(const float* __restrict__ dy, const int* __restrict__ lengths,
+                                                                  float* __restrict__ dx, int T, int C) {
+  const int b = blockIdx.z, t = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  int l = lengths[b];
+  l = l < 0 ? 0 : (l > T ? T : l);
+  dx[((size_t)b * T + t) * C + c] = t < l ? dy[(size_t)b * C + c] / (float)l : 0.f;
+}
+
+// vl: + the slice's 16 lengths behind the float arrays (148 288 B in the backward at H = 384)
+inline size_t fwd_lds(int H, bool vl = false) {
   const int Hp = (H + 15) & ~15;
-  return (size_t)LSTM_ROWS * ((4 * Hp + 4) + 2 * (Hp + 4)) * sizeof(float);
+  return (size_t)3 * LSTM_ROWS * (Hp + 4) * sizeof(float) + (vl ? LSTM_ROWS * sizeof(int) : 0);
+}
+inline size_t bwd_lds(int H, bool vl = false) {
+  const int Hp = (H + 15) & ~15;
+  return (size_t)LSTM_ROWS * ((4 * Hp + 4) + 2 * (Hp + 4)) * sizeof(float) + (vl ? LSTM_ROWS * sizeof(int) : 0);
 }
 
 int check_desc(const ecgmm_lstm_desc* d, const char* what) {
@@ -362,9 +473,10 @@ BwdLayout bwd_layout(const ecgmm_lstm_desc* d, void* scratch) {
 bool lds_attr_done = false;
 void set_lds_attrs() {
   if (lds_attr_done) return;
-  (void)hipFuncSetAttribute((const void*)lstm_seq_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void)hipFuncSetAttribute((const void*)lstm_seq_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void)hipFuncSetAttribute((const void*)lstm_seq_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  const void* fns[] = {(const void*)lstm_seq_fwd_kernel<true, false>, (const void*)lstm_seq_fwd_kernel<false, false>,
+                       (const void*)lstm_seq_fwd_kernel<true, true>,  (const void*)lstm_seq_fwd_kernel<false, true>,
+                       (const void*)lstm_seq_bwd_kernel<false>,       (const void*)lstm_seq_bwd_kernel<true>};
+  for (const void* fn : fns) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   lds_attr_done = true;
 }
 
@@ -379,8 +491,9 @@ size_t ecg_lstm_bwd_workspace(const ecgmm_lstm_desc* d) {
   return bwd_layout(d, nullptr).bytes;
 }
 
-int ecg_lstm_forward(const ecgmm_lstm_desc* d, const float* x, const float* const* params, const float* h0,
-                     const float* c0, float* y, float* hn, float* cn, void* ws, size_t ws_bytes, hipStream_t s) {
+int ecg_lstm_forward(const ecgmm_lstm_desc* d, const float* x, const int* lengths, const float* const* params,
+                     const float* h0, const float* c0, float* y, float* hn, float* cn, void* ws, size_t ws_bytes,
+                     hipStream_t s) {
   ECG_TRY(check_desc(d, "lstm_forward"));
   if (!x || !params || !y) ECG_FAIL(ECGMM_ERR_SHAPE, "lstm_forward: x, params and y must not be null");
   const FwdLayout f = fwd_layout(d, ws);
@@ -397,6 +510,7 @@ int ecg_lstm_forward(const ecgmm_lstm_desc* d, const float* x, const float* cons
     LstmFwdArgs a;
     memset(&a, 0, sizeof(a));
     a.B = B; a.T = T; a.H = H; a.ldo = D * H; a.batch_first = d->batch_first; a.save = d->save_for_backward;
+    a.lengths = lengths;
     bool v4 = H % 4 == 0;
     for (int k = 0; k < D; ++k) {
       const float* const* pr = params + (size_t)(l * D + k) * 4;   // w_ih, w_hh, b_ih, b_hh
@@ -416,16 +530,19 @@ int ecg_lstm_forward(const ecgmm_lstm_desc* d, const float* x, const float* cons
     const dim3 grid(ceil_div(B, LSTM_ROWS), D);
     // 2 (4H x H) FLOPs per batch row and step; W_hh once per step and slice from L2 (not HBM: 0 algorithmic bytes beyond
     // the projections, the saved tensors and the output)
-    if (v4) hipLaunchKernelGGL(lstm_seq_fwd_kernel<true>, grid, dim3(LSTM_THREADS), fwd_lds(H), s, a);
-    else hipLaunchKernelGGL(lstm_seq_fwd_kernel<false>, grid, dim3(LSTM_THREADS), fwd_lds(H), s, a);
+    if (lengths) {
+      if (v4) hipLaunchKernelGGL((lstm_seq_fwd_kernel<true, true>), grid, dim3(LSTM_THREADS), fwd_lds(H, true), s, a);
+      else hipLaunchKernelGGL((lstm_seq_fwd_kernel<false, true>), grid, dim3(LSTM_THREADS), fwd_lds(H, true), s, a);
+    } else if (v4) hipLaunchKernelGGL((lstm_seq_fwd_kernel<true, false>), grid, dim3(LSTM_THREADS), fwd_lds(H), s, a);
+    else hipLaunchKernelGGL((lstm_seq_fwd_kernel<false, false>), grid, dim3(LSTM_THREADS), fwd_lds(H), s, a);
     ECG_CHECK_LAUNCH("lstm_seq_fwd");
   }
   return 0;
 }
 
-int ecg_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const float* const* params, const float* h0,
-                      const float* c0, const float* dy, const float* dhn, const float* dcn, const void* ws, float* dx,
-                      float* const* grads, float* dh0, float* dc0, void* scratch, size_t scratch_bytes,
+int ecg_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const int* lengths, const float* const* params,
+                      const float* h0, const float* c0, const float* dy, const float* dhn, const float* dcn, const void* ws,
+                      float* dx, float* const* grads, float* dh0, float* dc0, void* scratch, size_t scratch_bytes,
                       hipStream_t s) {
   ECG_TRY(check_desc(d, "lstm_backward"));
   if (!d->save_for_backward) ECG_FAIL(ECGMM_ERR_SHAPE, "lstm_backward: the forward ran with save_for_backward = 0");
@@ -446,6 +563,7 @@ int ecg_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const float* con
     LstmBwdArgs a;
     memset(&a, 0, sizeof(a));
     a.B = B; a.T = T; a.H = H; a.ldo = D * H; a.batch_first = d->batch_first;
+    a.lengths = lengths;
     for (int k = 0; k < D; ++k) {
       const float* const* pr = params + (size_t)(l * D + k) * 4;
       if (!pr[0] || !pr[1]) ECG_FAIL(ECGMM_ERR_SHAPE, "lstm_backward: null weight (layer %d)", l);
@@ -461,7 +579,9 @@ int ecg_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const float* con
       q.dc0 = dc0 ? dc0 + (size_t)(l * D + k) * BH : nullptr;
       q.reverse = k;
     }
-    hipLaunchKernelGGL(lstm_seq_bwd_kernel, dim3(ceil_div(B, LSTM_ROWS), D), dim3(LSTM_THREADS), bwd_lds(H), s, a);
+    const dim3 grid(ceil_div(B, LSTM_ROWS), D);
+    if (lengths) hipLaunchKernelGGL(lstm_seq_bwd_kernel<true>, grid, dim3(LSTM_THREADS), bwd_lds(H, true), s, a);
+    else hipLaunchKernelGGL(lstm_seq_bwd_kernel<false>, grid, dim3(LSTM_THREADS), bwd_lds(H), s, a);
     ECG_CHECK_LAUNCH("lstm_seq_bwd");
     float* dst = l > 0 ? w.dyb[l & 1] : dx;   // dx of layer l is the dy of layer l - 1
     for (int k = 0; k < D; ++k) {
@@ -481,5 +601,22 @@ int ecg_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const float* con
       if (gbh) ECG_TRY(ecg_rows_sum(w.dgates[k], rows, 4 * H, gbh, 0, s));
     }
   }
+  return 0;
+}
+
+int ecg_seq_mean_varlen_fwd(const float* x, const int* lengths, float* out, int B, int T, int C, hipStream_t s) {
+  if (!x || !lengths || !out) ECG_FAIL(ECGMM_ERR_SHAPE, "seq_mean_varlen_fwd: x, lengths and out must not be null");
+  if (B < 1 || T < 1 || C < 1 || B > 65535) ECG_FAIL(ECGMM_ERR_SHAPE, "seq_mean_varlen_fwd: B=%d (1..65535) T=%d C=%d", B, T, C);
+  hipLaunchKernelGGL(seq_mean_varlen_fwd_kernel, dim3(ceil_div(C, 256), B), dim3(256), 0, s, x, lengths, out, T, C);
+  ECG_CHECK_LAUNCH("seq_mean_varlen_fwd");
+  return 0;
+}
+
+int ecg_seq_mean_varlen_bwd(const float* dy, const int* lengths, float* dx, int B, int T, int C, hipStream_t s) {
+  if (!dy || !lengths || !dx) ECG_FAIL(ECGMM_ERR_SHAPE, "seq_mean_varlen_bwd: dy, lengths and dx must not be null");
+  if (B < 1 || T < 1 || C < 1 || B > 65535 || T > 65535)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "seq_mean_varlen_bwd: B=%d T=%d (1..65535 each) C=%d", B, T, C);
+  hipLaunchKernelGGL(seq_mean_varlen_bwd_kernel, dim3(ceil_div(C, 256), T, B), dim3(256), 0, s, dy, lengths, dx, T, C);
+  ECG_CHECK_LAUNCH("seq_mean_varlen_bwd");
   return 0;
 }

@@ -247,11 +247,17 @@ int ecg_linear_bwd(const float* dz, const float* x, const float* w, float* dx, f
 // lstm.hip: nn.LSTM plans (projection GEMMs through ecg_linear_*, the recurrence on lstm_seq_fwd / lstm_seq_bwd kernels)
 size_t ecg_lstm_fwd_workspace(const ecgmm_lstm_desc* d);
 size_t ecg_lstm_bwd_workspace(const ecgmm_lstm_desc* d);
-int ecg_lstm_forward(const ecgmm_lstm_desc* d, const float* x, const float* const* params, const float* h0,
-                     const float* c0, float* y, float* hn, float* cn, void* ws, size_t ws_bytes, hipStream_t s);
-int ecg_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const float* const* params, const float* h0,
-                      const float* c0, const float* dy, const float* dhn, const float* dcn, const void* ws, float* dx,
-                      float* const* grads, float* dh0, float* dc0, void* scratch, size_t scratch_bytes, hipStream_t s);
+// lengths: device int32 [B] or null (null: the fixed-length kernels, the code of before there were lengths)
+int ecg_lstm_forward(const ecgmm_lstm_desc* d, const float* x, const int* lengths, const float* const* params,
+                     const float* h0, const float* c0, float* y, float* hn, float* cn, void* ws, size_t ws_bytes,
+                     hipStream_t s);
+int ecg_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const int* lengths, const float* const* params,
+                      const float* h0, const float* c0, const float* dy, const float* dhn, const float* dcn, const void* ws,
+                      float* dx, float* const* grads, float* dh0, float* dc0, void* scratch, size_t scratch_bytes,
+                      hipStream_t s);
+// mean over each row's own steps of x [B][T][C] and its backward (fixed summation order; len 0 gives 0)
+int ecg_seq_mean_varlen_fwd(const float* x, const int* lengths, float* out, int B, int T, int C, hipStream_t s);
+int ecg_seq_mean_varlen_bwd(const float* dy, const int* lengths, float* dx, int B, int T, int C, hipStream_t s);
 
 // crnn_front.hip: the CRNN front end's own kernels (train_physionet2.py:55-65, 87-93).  Conv2d(1, 32, 5, pad 2) straight from
 // the [N][H][W] fp32 spectrogram; the 5x5 weight gradient (Cin, Cout multiples of 32); [BatchNorm -> ReLU -> MaxPool2d(2)]

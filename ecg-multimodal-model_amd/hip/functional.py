@@ -442,14 +442,41 @@ def _grad_wanted(p):
         return True
 
 
+def check_lengths(lengths, B, T):
+    """Sequence lengths of a padded ``[B, T, ...]`` batch -> an ``int32 [B]`` tensor (pure host code; the caller moves it).
+    A list / tuple / array or a CPU integer tensor is validated as torch validates ``pack_padded_sequence``: shape ``[B]``,
+    an integer dtype, ``1 <= len <= T``, else ``ValueError`` naming the first offending index.  A device integer tensor is
+    taken as given (reading it would be a host sync) and converted to ``int32``: the kernels clamp its values to
+    ``[0, T]``, and a clamped 0 is a row without live steps (``y = 0``, ``h_n = h_0``, a mean of 0)."""
+    if isinstance(lengths, torch.Tensor):
+        t = lengths
+    else:
+        try:
+            t = torch.as_tensor(lengths)
+        except Exception as e:
+            raise ValueError(f"lengths: not convertible to a tensor ({e})") from None
+    if t.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise ValueError(f"lengths: dtype {t.dtype} is not an integer type")
+    if tuple(t.shape) != (B,):
+        raise ValueError(f"lengths: shape {tuple(t.shape)}, expected ({B},) (one length per batch row)")
+    if t.device.type != "cpu":
+        return t.to(torch.int32)
+    bad = ((t < 1) | (t > T)).nonzero()
+    if bad.numel():
+        i = int(bad[0])
+        raise ValueError(f"lengths[{i}] = {int(t[i])} is outside 1..T = {T}")
+    return t.to(torch.int32)
+
+
 class LSTMFn(torch.autograd.Function):
     """y, h_n, c_n = LSTM(x, h0, c0; params).  ``params`` in torch's ``_flat_weights`` order (per layer, per direction:
     w_ih, w_hh, b_ih, b_hh).  The forward keeps its workspace (activated gates, c_t, h_{t-1}) on ``ctx`` only when some
-    input requires grad; the backward reads it and writes parameter gradients into their sinks."""
+    input requires grad; the backward reads it and writes parameter gradients into their sinks.  ``cfg`` may carry a fifth
+    entry, the device ``int32 [B]`` lengths (or ``None``): the ``_varlen`` entry points, else the fixed ones."""
 
     @staticmethod
     def forward(ctx, x, h0, c0, cfg, *params):
-        hidden, layers, bidirectional, batch_first = cfg
+        hidden, layers, bidirectional, batch_first, lengths = (tuple(cfg) + (None,))[:5]
         _require_cuda(x, "lstm")
         for t in (h0, c0) + params:
             if t is not None:
@@ -481,10 +508,18 @@ class LSTMFn(torch.autograd.Function):
         y = torch.empty(yshape, device=x.device, dtype=torch.float32)
         hn = torch.empty(layers * D, B, hidden, device=x.device, dtype=torch.float32)
         cn = torch.empty_like(hn)
-        L.check(lib.ecgmm_lstm_forward(C.byref(desc), ptr(x), _ptr_table(params), ptr(h0), ptr(c0), ptr(y), ptr(hn),
-                                       ptr(cn), ptr(ws), ws.numel(), stream()), "lstm_forward")
+        if lengths is None:
+            L.check(lib.ecgmm_lstm_forward(C.byref(desc), ptr(x), _ptr_table(params), ptr(h0), ptr(c0), ptr(y), ptr(hn),
+                                           ptr(cn), ptr(ws), ws.numel(), stream()), "lstm_forward")
+        else:
+            if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,) or lengths.device != x.device:
+                raise RuntimeError(f"lstm: lengths must be int32 [{B}] on {x.device} (HF.check_lengths)")
+            lengths = lengths.contiguous()
+            L.check(lib.ecgmm_lstm_forward_varlen(C.byref(desc), ptr(x), ptr(lengths), _ptr_table(params), ptr(h0),
+                                                  ptr(c0), ptr(y), ptr(hn), ptr(cn), ptr(ws), ws.numel(), stream()),
+                    "lstm_forward_varlen")
         if save:
-            ctx.desc, ctx.ws, ctx.params = desc, ws, params
+            ctx.desc, ctx.ws, ctx.params, ctx.lengths = desc, ws, params, lengths
             ctx.save_for_backward(x, h0, c0)
             ctx.set_materialize_grads(False)
         return y, hn, cn
@@ -503,17 +538,36 @@ class LSTMFn(torch.autograd.Function):
         lib = L.lib()
         nb = lib.ecgmm_lstm_bwd_workspace(C.byref(desc))
         scratch = _Scratch.get("lstm_bwd", nb, x.device)
-        L.check(lib.ecgmm_lstm_backward(C.byref(desc), ptr(x), _ptr_table(params), ptr(h0), ptr(c0), ptr(dy), ptr(dhn),
-                                        ptr(dcn), ptr(ctx.ws), ptr(dx), _ptr_table(sinks), ptr(dh0), ptr(dc0),
-                                        ptr(scratch), scratch.numel(), stream()), "lstm_backward")
+        if ctx.lengths is None:
+            L.check(lib.ecgmm_lstm_backward(C.byref(desc), ptr(x), _ptr_table(params), ptr(h0), ptr(c0), ptr(dy), ptr(dhn),
+                                            ptr(dcn), ptr(ctx.ws), ptr(dx), _ptr_table(sinks), ptr(dh0), ptr(dc0),
+                                            ptr(scratch), scratch.numel(), stream()), "lstm_backward")
+        else:
+            L.check(lib.ecgmm_lstm_backward_varlen(C.byref(desc), ptr(x), ptr(ctx.lengths), _ptr_table(params), ptr(h0),
+                                                   ptr(c0), ptr(dy), ptr(dhn), ptr(dcn), ptr(ctx.ws), ptr(dx),
+                                                   _ptr_table(sinks), ptr(dh0), ptr(dc0), ptr(scratch), scratch.numel(),
+                                                   stream()), "lstm_backward_varlen")
         return (dx, dh0, dc0, None) + (None,) * len(params)
 
 
-def lstm(x, hx, params, hidden_size, num_layers=1, bidirectional=False, batch_first=False):
-    """``torch.nn.LSTM`` forward (with bias, no dropout, no projection): returns ``(output, (h_n, c_n))``."""
+def lstm(x, hx, params, hidden_size, num_layers=1, bidirectional=False, batch_first=False, lengths=None):
+    """``torch.nn.LSTM`` forward (with bias, no dropout, no projection): returns ``(output, (h_n, c_n))``.
+
+    ``lengths`` (one per batch row, see :func:`check_lengths`): ``x`` stays padded and the result is
+    ``pad_packed_sequence(lstm(pack_padded_sequence(x, lengths, enforce_sorted=False), hx), total_length=T)``: the output is
+    exactly 0 from each row's length on, ``h_n / c_n`` are the states after each row's last own step, and no gradient sees
+    the padding.  The padding of ``x`` must be finite (it meets exact zeros in the GEMMs).  A slice of 16 consecutive rows
+    runs as many serial steps as its longest row: rows ordered by length free their CUs early, but a layer still lasts as
+    long as the longest slice, and no time was gained at B = 256."""
     h0, c0 = (None, None) if hx is None else hx
-    y, hn, cn = LSTMFn.apply(x, h0, c0, (int(hidden_size), int(num_layers), bool(bidirectional), bool(batch_first)),
-                             *params)
+    cfg = (int(hidden_size), int(num_layers), bool(bidirectional), bool(batch_first))
+    if lengths is not None:
+        if not isinstance(x, torch.Tensor) or x.dim() != 3:
+            raise RuntimeError("lstm: input must be a 3-D (batched) tensor")
+        _require_cuda(x, "lstm")
+        B, T = (x.shape[0], x.shape[1]) if batch_first else (x.shape[1], x.shape[0])
+        cfg += (check_lengths(lengths, B, T).to(x.device),)
+    y, hn, cn = LSTMFn.apply(x, h0, c0, cfg, *params)
     return y, (hn, cn)
 
 
@@ -547,8 +601,38 @@ class SeqMeanFn(torch.autograd.Function):
         return dx
 
 
-def seq_mean(x):
-    return SeqMeanFn.apply(x)
+class SeqMeanVarlenFn(torch.autograd.Function):
+    """mean over each row's own ``lengths[b]`` steps of a [B, T, C] fp32 sequence (ecgmm_seq_mean_varlen_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, lengths):
+        _require_cuda(x, "seq_mean")
+        x = f32c(x)
+        B, T, Cn = x.shape
+        out = torch.empty(B, Cn, device=x.device, dtype=torch.float32)
+        L.check(L.lib().ecgmm_seq_mean_varlen_fwd(ptr(x), ptr(lengths), ptr(out), B, T, Cn, stream()), "seq_mean_varlen_fwd")
+        ctx.shape, ctx.lengths = (B, T, Cn), lengths
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, T, Cn = ctx.shape
+        dy = f32c(dy)
+        dx = torch.empty(B, T, Cn, device=dy.device, dtype=torch.float32)
+        L.check(L.lib().ecgmm_seq_mean_varlen_bwd(ptr(dy), ptr(ctx.lengths), ptr(dx), B, T, Cn, stream()),
+                "seq_mean_varlen_bwd")
+        return dx, None
+
+
+def seq_mean(x, lengths=None):
+    """mean over the time axis of ``x [B, T, C]``; with ``lengths`` (:func:`check_lengths`) over each row's own first
+    ``lengths[b]`` steps, the gradient exactly 0 behind them."""
+    if lengths is None:
+        return SeqMeanFn.apply(x)
+    _require_cuda(x, "seq_mean")
+    if x.dim() != 3:
+        raise RuntimeError(f"seq_mean: input must be [B, T, C], got {tuple(x.shape)}")
+    return SeqMeanVarlenFn.apply(x, check_lengths(lengths, x.shape[0], x.shape[1]).to(x.device).contiguous())
 
 
 # --------------------------------------------------------------------------------------------

@@ -208,6 +208,11 @@ SIGNATURES = {
     "ecgmm_lstm_bwd_workspace": (sz, [P(LSTMDesc)]),
     "ecgmm_lstm_forward": (i32, [P(LSTMDesc), vp, P(vp), vp, vp, vp, vp, vp, vp, sz, vp]),
     "ecgmm_lstm_backward": (i32, [P(LSTMDesc), vp, P(vp), vp, vp, vp, vp, vp, vp, vp, P(vp), vp, vp, vp, sz, vp]),
+    "ecgmm_lstm_forward_varlen": (i32, [P(LSTMDesc), vp, vp, P(vp), vp, vp, vp, vp, vp, vp, sz, vp]),
+    "ecgmm_lstm_backward_varlen": (i32, [P(LSTMDesc), vp, vp, P(vp), vp, vp, vp, vp, vp, vp, vp, P(vp), vp, vp, vp, sz,
+                                         vp]),
+    "ecgmm_seq_mean_varlen_fwd": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "ecgmm_seq_mean_varlen_bwd": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "ecgmm_conv5_in1_stats_rows": (i32, [i32, i32, i32]),
     "ecgmm_conv5_in1_fwd": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "ecgmm_conv5_in1_bwd_weight_workspace": (sz, [i32, i32, i32]),
@@ -278,7 +283,10 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  "ecgmm_mha_bwd_workspace", "ecgmm_mha_forward", "ecgmm_mha_backward", "ecgmm_mha_keep_mask",
                  "ecgmm_embed1d_fwd", "ecgmm_embed1d_bwd_workspace", "ecgmm_embed1d_bwd",
                  # the merged SE / BatchNorm backward's first pass, per op (csrc/elementwise.hip)
-                 "ecgmm_se_gate_bn")
+                 "ecgmm_se_gate_bn",
+                 # variable-length sequences: lengths in the LSTM, the masked mean (csrc/lstm.hip)
+                 "ecgmm_lstm_forward_varlen", "ecgmm_lstm_backward_varlen", "ecgmm_seq_mean_varlen_fwd",
+                 "ecgmm_seq_mean_varlen_bwd")
 
 _lib = None
 

@@ -173,15 +173,17 @@ class LSTM(nn.Module):
         for p in self.parameters():
             nn.init.uniform_(p, -bound, bound)
 
-    def forward(self, x, hx=None):
+    def forward(self, x, hx=None, lengths=None):
+        """``lengths`` (a list, a CPU or a device integer tensor, one per batch row): ``x`` stays padded and the result is
+        torch's for the packed sequence, re-padded to ``T`` (:func:`ecgmm.hip.functional.lstm`)."""
         if isinstance(x, nn.utils.rnn.PackedSequence):
-            raise TypeError("LSTM: a PackedSequence input is not supported (pass a padded tensor)")
+            raise TypeError("LSTM: a PackedSequence input is not supported: pass the padded tensor and lengths=")
         if x.dim() != 3:
             raise ValueError(f"LSTM: input must be 3-D (batched); unbatched {x.dim()}-D input is not supported")
         if x.shape[2] != self.input_size:
             raise ValueError(f"LSTM: input has {x.shape[2]} features, expected input_size={self.input_size}")
         params = [getattr(self, n) for n in self._flat_names]
-        return HF.lstm(x, hx, params, self.hidden_size, self.num_layers, self.bidirectional, self.batch_first)
+        return HF.lstm(x, hx, params, self.hidden_size, self.num_layers, self.bidirectional, self.batch_first, lengths)
 
     def extra_repr(self):
         return (f"{self.input_size}, {self.hidden_size}, num_layers={self.num_layers}, batch_first={self.batch_first}, "

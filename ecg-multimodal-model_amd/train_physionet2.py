@@ -13,7 +13,10 @@ Not carried over: the plots and the classification report.  The validation loade
 ``shuffle=True`` at :164 changes nothing it reports: it only permutes the rows the validation loss and accuracy are
 accumulated over).  ``wfdb`` / ``pandas`` are replaced by :mod:`ecgmm.train_physionet`'s record
 reader and label table, which this module reuses; the loader base, the epoch loop and the metrics are ``ecgmm.training``'s.  NEW: ``config.physionet2_max_len`` (default ``None``) truncates longer
-records at the end before the transform.
+records at the end before the transform.  NEW: ``main(use_lengths=True)`` / ``config.physionet2_use_lengths`` hands each
+record's own frame count to ``CRNN.forward(x, lengths)``, so the BiLSTM stops where the record does and the mean over time
+leaves the padding out; each batch's rows are then ordered by length (:class:`DeviceSpectrogramLoader`).  Off by default:
+the reference runs through the padding.
 """
 import numpy as np
 import torch
@@ -45,12 +48,28 @@ def build_spectrograms(signals, device, chunk=1024):
     return out
 
 
-class SpectrogramDataset:
-    """One split as an index set over the shared spectrogram tensor (train_physionet2.py:41-48, 163-165 copy the rows)."""
+def spectrogram_frames(signals):
+    """``stft_frames(len(record))`` per record, int64 (host): the frames of :func:`build_spectrograms`' rows that are the
+    record's own; those behind them are the transform of the zero padding."""
+    return np.asarray([stft_frames(len(s)) for s in signals], dtype=np.int64)
 
-    def __init__(self, indices, labels, spectrograms):
+
+class SpectrogramDataset:
+    """One split as an index set over the shared spectrogram tensor (train_physionet2.py:41-48, 163-165 copy the rows).
+    ``frames`` (optional): the valid frames of every row of ``spectrograms``, as :func:`spectrogram_frames` gives them."""
+
+    def __init__(self, indices, labels, spectrograms, frames=None):
         device = spectrograms.device
         self.spectrograms = spectrograms
+        self.frames_host = self.frames = None
+        if frames is not None:
+            frames = np.asarray(frames)
+            if frames.shape != (spectrograms.shape[0],) or frames.dtype.kind not in "iu":
+                raise ValueError(f"SpectrogramDataset: frames must be {spectrograms.shape[0]} integers, one per spectrogram")
+            if frames.min() < 1 or frames.max() > spectrograms.shape[-1]:
+                raise ValueError(f"SpectrogramDataset: frames outside 1..{spectrograms.shape[-1]}")
+            self.frames_host = torch.as_tensor(frames[np.asarray(indices)], dtype=torch.int32)   # per split row, as labels
+            self.frames = self.frames_host.to(device)
         self.indices = torch.as_tensor(np.asarray(indices), dtype=torch.long, device=device)
         self.labels_host = torch.as_tensor(np.asarray(labels)[np.asarray(indices)], dtype=torch.long)
         self.labels = self.labels_host.to(device)
@@ -65,19 +84,35 @@ class SpectrogramDataset:
 class DeviceSpectrogramLoader(T.ResidentLoader):
     """Batches of a :class:`SpectrogramDataset`: ``(spectrograms [B, 1, 33, T] fp32, labels [B])``, both on the device.
     ``shuffle``: a ``torch.randperm`` of the seeded ``generator`` per epoch, kept in ``last_order``.  The last partial batch
-    is kept (``DataLoader``'s default, which the reference uses)."""
+    is kept (``DataLoader``'s default, which the reference uses).
 
-    def __init__(self, dataset, batch_size=Config.batch_size, shuffle=False, generator=None):
+    A dataset with ``frames`` yields ``((spectrograms, frames [B] int32), labels)``.  ``sort_by_length`` (default: on exactly
+    then) orders the rows of each batch by descending frames, a stable sort of the batch's index slice: the batches hold the
+    rows they would hold anyway, and the LSTM's slices of 16 consecutive rows become homogeneous in length, so that the short
+    slices leave their CUs early.  That saves CU time, not latency: a layer lasts as long as the batch's longest slice, and
+    at B = 256 no time was gained.  Without frames the batches are as before."""
+
+    def __init__(self, dataset, batch_size=Config.batch_size, shuffle=False, generator=None, sort_by_length=None):
         super().__init__(dataset, batch_size, shuffle, generator)
+        has = getattr(dataset, "frames", None) is not None
+        if sort_by_length and not has:
+            raise ValueError("DeviceSpectrogramLoader: sort_by_length needs a dataset with frames")
+        self.sort_by_length = has if sort_by_length is None else bool(sort_by_length)
 
     def batch(self, idx):
         ds = self.dataset
-        return ds.spectrograms.index_select(0, ds.indices[idx]), ds.labels[idx]
+        if getattr(ds, "frames", None) is None:
+            return ds.spectrograms.index_select(0, ds.indices[idx]), ds.labels[idx]
+        if self.sort_by_length:
+            idx = idx[torch.sort(ds.frames[idx], descending=True, stable=True).indices]
+        return (ds.spectrograms.index_select(0, ds.indices[idx]), ds.frames[idx]), ds.labels[idx]
 
 
-def get_spectrogram_dataloaders(config=Config, batch_size=None, label_map=LABEL_MAP, split=SPLIT, chunk=1024):
+def get_spectrogram_dataloaders(config=Config, batch_size=None, label_map=LABEL_MAP, split=SPLIT, chunk=1024,
+                                use_lengths=False):
     """train / val / test :class:`DeviceSpectrogramLoader` over one resident tensor (train_physionet2.py:128-165): labels
-    N -> 0, AF / O -> 1, '~' dropped; stratified 80 / 10 / 10 with ``config.seed``; only the train split is shuffled."""
+    N -> 0, AF / O -> 1, '~' dropped; stratified 80 / 10 / 10 with ``config.seed``; only the train split is shuffled.
+    ``use_lengths``: the datasets carry :func:`spectrogram_frames` and the loaders yield ``((spec, frames), labels)``."""
     batch_size = config.batch_size if batch_size is None else batch_size
     signals, labels = load_records(config, label_map)
     max_len = getattr(config, "physionet2_max_len", None)
@@ -86,28 +121,33 @@ def get_spectrogram_dataloaders(config=Config, batch_size=None, label_map=LABEL_
     train_idx, val_idx, test_idx = split_indices(labels, config.seed, split)
     spec = build_spectrograms(signals, torch.device(config.device), chunk)
     gen = torch.Generator().manual_seed(config.seed)
-    return (DeviceSpectrogramLoader(SpectrogramDataset(train_idx, labels, spec), batch_size, shuffle=True, generator=gen),
-            DeviceSpectrogramLoader(SpectrogramDataset(val_idx, labels, spec), batch_size),
-            DeviceSpectrogramLoader(SpectrogramDataset(test_idx, labels, spec), batch_size))
+    frames = spectrogram_frames(signals) if use_lengths else None
+    return (DeviceSpectrogramLoader(SpectrogramDataset(train_idx, labels, spec, frames), batch_size, shuffle=True,
+                                    generator=gen),
+            DeviceSpectrogramLoader(SpectrogramDataset(val_idx, labels, spec, frames), batch_size),
+            DeviceSpectrogramLoader(SpectrogramDataset(test_idx, labels, spec, frames), batch_size))
 
 
 def evaluate(model, loader):
     """train_physionet2.py:233-257: argmax predictions and the class-1 softmax probability of the split ->
     accuracy / binary F1 / ROC-AUC (NaN where sklearn cannot define it: one class only)."""
     model.eval()
-    y_true, y_prob, y_pred, _ = T.predict(model, loader)
+    # a loader with frames yields (spec, frames) as the inputs
+    y_true, y_prob, y_pred, _ = T.predict(lambda inputs: model(*inputs) if isinstance(inputs, tuple) else model(inputs), loader)
     return T.binary_metrics(y_true, y_prob[:, 1], y_pred)
 
 
-def main(config=Config, num_epochs=None, batch_size=None, quiet=False):
-    """-> (history, {"best": metrics, "last": metrics}, checkpoint directory)."""
+def main(config=Config, num_epochs=None, batch_size=None, quiet=False, use_lengths=False):
+    """-> (history, {"best": metrics, "last": metrics}, checkpoint directory).  ``use_lengths`` or
+    ``config.physionet2_use_lengths`` (both off by default): the CRNN gets every record's own length (module docstring)."""
+    use_lengths = bool(use_lengths or getattr(config, "physionet2_use_lengths", False))
     num_epochs = config.num_epochs if num_epochs is None else num_epochs
     batch_size = config.batch_size if batch_size is None else batch_size
     T.seed_all(config.seed, numpy=True)
     device = torch.device(config.device)
     if not quiet:
         print(f"Using device: {device}")
-    train_loader, val_loader, test_loader = get_spectrogram_dataloaders(config, batch_size)
+    train_loader, val_loader, test_loader = get_spectrogram_dataloaders(config, batch_size, use_lengths=use_lengths)
     model = CRNN(compute_dtype=getattr(config, "compute_dtype", "bf16")).to(device)
     criterion = FocalLoss()
     optimizer = FusedAdam(model.parameters(), lr=config.lr)
@@ -115,7 +155,7 @@ def main(config=Config, num_epochs=None, batch_size=None, quiet=False):
 
     def step(batch):
         spec, labels = batch
-        out = model(spec)
+        out = model(*spec) if use_lengths else model(spec)
         return criterion(out, labels), out, labels
 
     def train_pass():

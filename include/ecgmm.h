@@ -680,6 +680,38 @@ int ecgmm_lstm_forward(const ecgmm_lstm_desc* d, const float* x, const float* co
 int ecgmm_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const float* const* params, const float* h0,
                         const float* c0, const float* dy, const float* dhn, const float* dcn, const void* ws, float* dx,
                         float* const* grads, float* dh0, float* dc0, void* scratch, size_t scratch_bytes, void* stream);
+/* Variable-length form: x stays padded ([B,T,In] or [T,B,In]) and lengths [B] (device int32) says where each row ends.
+ * It equals pad_packed_sequence(lstm(pack_padded_sequence(x, lengths, enforce_sorted=False), hx), total_length=T) for
+ * every layer and direction, as a masked hold: at step t row b is live iff t < lengths[b], in both directions.
+ *   live row            the cell of ecgmm_lstm_forward.
+ *   dead row, forward   h and c keep their values and y[b,t] = 0.  The reverse direction so carries h0 / c0 untouched down
+ *                       to t = lengths[b]-1 and starts there; hn / cn are the states after the row's last live step
+ *                       (t = lengths[b]-1 forward, t = 0 reverse).
+ *   dead row, backward  gate gradients are exact zeros, the dh / dc carries pass through, dy there is ignored: dx is exactly
+ *                       zero at padded positions and no parameter gradient sees them.
+ * lengths are clamped to [0, T] on the device (no host sync).  A length-0 row gives y = 0, hn = h0, cn = c0, dx = 0,
+ * dh0 = dhn, dc0 = dcn.  lengths = null is exactly ecgmm_lstm_forward / ecgmm_lstm_backward, bit for bit (the same
+ * kernels); so is, in value, lengths all equal to T.  The backward takes the lengths the forward ran with.
+ * A slice of 16 consecutive batch rows runs only max(lengths of the slice) recurrence steps.  Rows ordered by length so save
+ * CU time (short slices retire early), NOT latency while every slice has a CU of its own: a layer lasts as long as its
+ * longest slice, and at B = 256 no gain was measured; latency only beyond 2048 rows per direction pair or with
+ * other work on the idle CUs.  The projection and gradient GEMMs stay over all B*T rows, where padded x is multiplied by exact
+ * zeros: PADDED x MUST BE FINITE (dy at padded positions is never read into arithmetic and may be anything).
+ * Workspace and scratch sizes are those of ecgmm_lstm_fwd_workspace / ecgmm_lstm_bwd_workspace. */
+/* train_physionet2.py:94-95: x, (h_n, c_n) = self.lstm(x) on records of unequal length */
+int ecgmm_lstm_forward_varlen(const ecgmm_lstm_desc* d, const float* x, const int32_t* lengths, const float* const* params,
+                              const float* h0, const float* c0, float* y, float* hn, float* cn, void* ws, size_t ws_bytes,
+                              void* stream);
+/* train_physionet2.py:94-95: the nn.LSTM part of loss.backward() on records of unequal length */
+int ecgmm_lstm_backward_varlen(const ecgmm_lstm_desc* d, const float* x, const int32_t* lengths, const float* const* params,
+                               const float* h0, const float* c0, const float* dy, const float* dhn, const float* dcn,
+                               const void* ws, float* dx, float* const* grads, float* dh0, float* dc0, void* scratch,
+                               size_t scratch_bytes, void* stream);
+/* train_physionet2.py:94-95: x.mean(dim=1) over each row's own steps: out[b,c] = sum_{t < len_b} x[b,t,c] / len_b, x [B,T,C]
+ * fp32, lengths [B] device int32 clamped to [0, T]; len_b = 0 gives 0.  Any C >= 1; the sum runs t = 0, 1, ... in order. */
+int ecgmm_seq_mean_varlen_fwd(const float* x, const int32_t* lengths, float* out, int B, int T, int C, void* stream);
+/* train_physionet2.py:94-95 (its loss.backward()): dx[b,t,c] = t < len_b ? dy[b,c] / len_b : 0 (exact zeros). */
+int ecgmm_seq_mean_varlen_bwd(const float* dy, const int32_t* lengths, float* dx, int B, int T, int C, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * CRNN convolutional front end, per-op (train_physionet2.py:55-65, 87-93): three ConvBlocks
