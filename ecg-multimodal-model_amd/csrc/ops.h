@@ -3,6 +3,10 @@
 #include "common.h"
 #include "switches.h"
 
+// preprocess.hip: how many lanes of the chunked filtfilt kernels (preprocess.hip, physionet.hip) run the recurrences, from the
+// denominator a[0..order] (a[0] = 1) and the padded record length E alone: 64, 32, 16, 8, 4, 2 or 1 (sequential)
+int ecg_iir_lanes(const double* a, int order, int E);
+
 // conv_igemm.hip
 int ecg_conv_stats_rows(long M);
 // Optional epilogue extras of a convolution launch (the encoder plans use them; the C ABI passes none).

@@ -20,6 +20,7 @@ struct FzParams {
   const float* x;   // [S][L]
   float* out;       // [S][L]
   int S, L, zscore;
+  int nl;           // lanes that run the recurrences (ecg_iir_lanes): 64, 32, .., 2, or 1 = the sequential pass
   double eps;
   double b[9], a[9], zi[8];
 };
@@ -35,6 +36,9 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 //   (2) lane 0 chains the true chunk-entry states  z_{t+1} = A^C z_t + s_t  (A^C built once by lanes 0..N-1);
 //   (3) every lane re-filters its chunk from its true entry state, writing y in place.
 // C is odd, so the 64 lanes' cursors (stride C doubles) fall in distinct LDS banks.  Both directions run in place.
+// As in signal_preprocess_lds_kernel only p.nl lanes run the recurrences (C = ceil(E / nl) | 1): the chain is exact only
+// algebraically, and ecg_iir_lanes keeps its rounding under the fp32 result's.  nl = 1 is the sequential pass, without A^C; the
+// lanes >= nl help with the loads, the extension, the z-score and the stores.
 template <int N>
 __global__ __launch_bounds__(64) void signal_filter_zscore_kernel(FzParams p) {
   extern __shared__ double sm[];
@@ -50,8 +54,9 @@ __global__ __launch_bounds__(64) void signal_filter_zscore_kernel(FzParams p) {
 
   const float* xr = p.x + (size_t)s * L;
   for (int t = lane; t < L; t += T) B[PAD + t] = (double)xr[t];
-  const int C = ((E + T - 1) / T) | 1;
-  if (lane < N) {  // column `lane` of A^C: C zero-input steps from the unit state
+  const int nl = p.nl;
+  const int C = ((E + nl - 1) / nl) | 1;
+  if (lane < N && nl > 1) {  // column `lane` of A^C: C zero-input steps from the unit state
     double z[N];
 #pragma unroll
     for (int i = 0; i < N; ++i) z[i] = i == lane ? 1.0 : 0.0;
@@ -71,12 +76,12 @@ __global__ __launch_bounds__(64) void signal_filter_zscore_kernel(FzParams p) {
   }
   __syncthreads();
 
-  const int k0 = lane * C, k1 = min(E, k0 + C);
+  const int k0 = lane < nl ? min(E, lane * C) : E, k1 = min(E, k0 + C);   // lanes >= nl own no chunk
 #pragma unroll 1
   for (int pass = 0; pass < 2; ++pass) {
     auto at = [&](int k) -> double& { return B[pass ? E - 1 - k : k]; };
     double z[N];
-    if (k0 < E && k1 - k0 == C) {  // a full chunk hands a state on
+    if (nl > 1 && k0 < E && k1 - k0 == C) {  // a full chunk hands a state on
 #pragma unroll
       for (int i = 0; i < N; ++i) z[i] = 0.0;
       for (int k = k0; k < k1; ++k) {
@@ -102,7 +107,11 @@ __global__ __launch_bounds__(64) void signal_filter_zscore_kernel(FzParams p) {
         for (int j = 0; j < N; ++j) m[i][j] = Mx[i * 8 + j];
 #pragma unroll
       for (int i = 0; i < N; ++i) z[i] = p.zi[i] * e0;
-      const int nchunks = (E + C - 1) / C;   // <= 64
+      const int nchunks = nl > 1 ? (E + C - 1) / C : 0;   // <= nl
+      if (nl == 1) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) st[i] = z[i];
+      }
       for (int t = 0; t < nchunks; ++t) {
         double sv[N], zn[N];
 #pragma unroll
@@ -340,6 +349,7 @@ extern "C" int ecgmm_signal_filter_zscore(const float* x, float* out, int S, int
   p.x = x; p.out = out; p.S = S; p.L = L; p.zscore = zscore ? 1 : 0; p.eps = eps;
   for (int i = 0; i <= order; ++i) { p.b[i] = b[i]; p.a[i] = a[i]; }
   for (int i = 0; i < order; ++i) p.zi[i] = zi[i];
+  p.nl = ecg_iir_lanes(a, order, L + 6 * (order + 1));
   hipStream_t st = (hipStream_t)stream;
   switch (order) {
     case 1: launch_fz<1>(p, lds, st); break;

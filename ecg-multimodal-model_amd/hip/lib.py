@@ -172,6 +172,7 @@ SIGNATURES = {
                                           i32, vp]),
     "ecgmm_weighted_sample": (i32, [vp, i64, i64, vp, vp, i64, u64, u64, vp]),
     "ecgmm_signal_filter_zscore": (i32, [vp, vp, i32, i32, P(f64), P(f64), P(f64), i32, i32, f64, vp]),
+    "ecgmm_signal_filter_lanes": (i32, [P(f64), i32, i32]),
     "ecgmm_signal_gather_augment": (i32, [vp, i64, i32, vp, i32, vp, vp, i32, f32, f32, f32, f32, i32, i32, u64, u64, vp]),
     "ecgmm_glu_fwd": (i32, [vp, vp, i64, i32, vp]),
     "ecgmm_glu_bwd": (i32, [vp, vp, vp, i64, i32, vp]),
@@ -286,7 +287,9 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  "ecgmm_se_gate_bn",
                  # variable-length sequences: lengths in the LSTM, the masked mean (csrc/lstm.hip)
                  "ecgmm_lstm_forward_varlen", "ecgmm_lstm_backward_varlen", "ecgmm_seq_mean_varlen_fwd",
-                 "ecgmm_seq_mean_varlen_bwd")
+                 "ecgmm_seq_mean_varlen_bwd",
+                 # the lane rule of the chunked filtfilt kernels (csrc/preprocess.hip)
+                 "ecgmm_signal_filter_lanes")
 
 _lib = None
 

@@ -551,6 +551,13 @@ int ecgmm_signal_preprocess_i16(const int16_t* raw, int R, int T, int nsig, cons
  * order 8), longer records are refused. */
 int ecgmm_signal_filter_zscore(const float* x, float* out, int S, int L, const double* b, const double* a,
                                const double* zi, int order, int zscore, double eps, void* stream);
+/* Accuracy contract of the three filtfilt entry points above (ecgmm_signal_preprocess, _i16, ecgmm_signal_filter_zscore): for
+ * any order and cutoff the float64 arithmetic adds at most one fp32 half-ulp at the row's scale to scipy's sequential float64
+ * filtfilt, wherever that itself is this accurate.  The kernels cut a record into chunks that run on nl lanes and chain the
+ * chunk states; the chain loses digits for a narrow-band, high-order design, so nl = 64, 32, 16, 8, 4, 2 or 1 (the sequential
+ * pass) is chosen on the host from (a, L) alone.  This returns the nl those entry points use for a record of L samples
+ * (needs no GPU); 0 with the message set for a null a, a[0] != 1, an order outside 1..8 or L < 1. */
+int ecgmm_signal_filter_lanes(const double* a, int order, int L);
 /* The per-step batch gather fused with augment_signal (train_physionet.py:47-60): out[i][:] = augment(src[index[i]][:]),
  * src [n][L] fp32, index int64 [B], out [B][L] fp32.  augment = 0: the plain gather.  augment = 1, per row i: three
  * Bernoulli(p) decisions in the reference's order -- add N(0, sigma^2) noise per sample point; multiply by a uniform on

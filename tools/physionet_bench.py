@@ -3,9 +3,11 @@ calls, medians of the per-call round means --
   (a) filter_zscore on [8528, 3000] (the challenge's training-set size),
   (b) gather_augment at B = 8 / 256 / 512 (augmentation on and off),
   (c) a ResNet1D_SE training step at [B, 1, 3000] fed by the device loader,
+  (d) ecgmm.preprocess.preprocess_signal (baseline removal + default low-pass) on [256, 5000], under the same protocol,
 and the reference pipeline restated with scipy / numpy per sample (filtfilt + z-score; augment_signal) on the host's
 CPUs (a pool of --cpus processes, as DataLoader workers would run it) as the baseline for (a) and (b).
-Writes profiles/physionet_bench.json and prints it."""
+Writes profiles/physionet_bench.json and prints it.  --front-only: (a) and (d) alone, the two filtfilt launches, printed and
+not written (an A/B of two builds of the library: ECGMM_LIB selects the build)."""
 import argparse
 import json
 import os
@@ -91,6 +93,7 @@ def main():
     ap.add_argument("--cpus", type=int, default=16)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "physionet_bench.json"))
     ap.add_argument("--skip-cpu", action="store_true")
+    ap.add_argument("--front-only", action="store_true")
     args = ap.parse_args()
     import torch
     from ecgmm import train_physionet as TP
@@ -107,6 +110,15 @@ def main():
     r = with_floor(timed(lambda: TP.preprocess_signal(raw), torch), S * Ln * 8)
     r["records_per_s"] = round(S / r["ms_median"] * 1e3, 1)
     res["filter_zscore_8528x3000"] = r
+
+    from ecgmm import preprocess as PP
+    sig = torch.randn(256, 5000, generator=g).to(dev)
+    r = with_floor(timed(lambda: PP.preprocess_signal(sig), torch), 256 * 5000 * 8)
+    r["signals_per_s"] = round(256 / r["ms_median"] * 1e3, 1)
+    res["preprocess_signal_256x5000"] = r
+    if args.front_only:
+        print(json.dumps(res))
+        return
 
     src = TP.preprocess_signal(raw)
     HF.manual_seed(1)
