@@ -3,9 +3,8 @@ numpy / scipy / sklearn.  lime itself is not installed; DESIGN.md section 21 is 
 Nothing here calls the HIP library."""
 import numpy as np
 
-M0, M1 = 0xD2511F53, 0xCD9E8D57
-W0, W1 = 0x9E3779B9, 0xBB67AE85
-MASK = 0xFFFFFFFF
+from .philox_ref import MASK, philox4x32_10, u53  # noqa: F401  (the one host copy; test_lime_cpu.py holds it to the known answers)
+
 SEED = 20261019          # the Philox seed of the GPU tests (chosen on the CPU: tests/test_lime_cpu.py checks its uniforms)
 
 
@@ -21,25 +20,6 @@ def crafted_background():
     # sorted[0 .. 20] = 0 and the median is interpolated half way to sorted[21]: the bin (0, median] is empty
     bg[:, 4] = np.where(np.arange(M) < 21, 0.0, 5.0 + np.arange(M))
     return bg
-
-
-def philox4x32_10(key, ctr):
-    """key (k0, k1), ctr (c0, c1, c2, c3): integers or uint64 arrays holding 32-bit values (broadcast) -> four uint64 arrays"""
-    k0, k1 = (np.asarray(k, dtype=np.uint64) for k in key)
-    c0, c1, c2, c3 = np.broadcast_arrays(*[np.asarray(c, dtype=np.uint64) for c in ctr])
-    m = np.uint64(MASK)
-    s32 = np.uint64(32)
-    for _ in range(10):
-        p0, p1 = np.uint64(M0) * c0, np.uint64(M1) * c2
-        hi0, lo0, hi1, lo1 = p0 >> s32, p0 & m, p1 >> s32, p1 & m
-        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
-        k0, k1 = (k0 + np.uint64(W0)) & m, (k1 + np.uint64(W1)) & m
-    return c0, c1, c2, c3
-
-
-def u53(a, b):
-    """the 53-bit uniform of ecgmm_weighted_sample from two words"""
-    return ((a >> np.uint64(5)).astype(np.float64) * 67108864.0 + (b >> np.uint64(6)).astype(np.float64)) / 9007199254740992.0
 
 
 def perturb_uniforms(seed, offset, b, n, f):

@@ -1,4 +1,8 @@
-"""Helpers shared by the GPU parity tests: call the C ABI with torch tensors, convert layouts."""
+"""Helpers shared by the GPU parity tests: call the C ABI with torch tensors, convert layouts.
+
+to_nhwc, from_nhwc and pack_weight go through the library's own ecgmm_nchw_to_nhwc, ecgmm_nhwc_to_nchw and
+ecgmm_pack_conv_weight; tests/test_exact_kernels_gpu.py checks those three kernels bit for bit (layout, bf16 rounding of
+unrounded operands, exact widening), so the float64 checks that use these helpers stand on tested ground."""
 import contextlib
 import ctypes as C
 
