@@ -27,10 +27,21 @@
 // the 16 query (key) slots is pair i / S, position i % S; a score between slots of different pairs is masked like a key past
 // the end.  Each pair's probabilities, outputs and gradients are the same arithmetic as alone in a tile.
 //
+// Lengths (VL, the _varlen entry points): lengths[n] (device int32, clamped to [0, S] here) live positions per attention-batch
+// element, the same in every head; key_padding_mask[n][s] = s >= lengths[n] plus exact zeros in the padding.  A slot at or
+// past the length is empty: it is clamped onto position lengths[n] - 1 (so nothing is ever loaded from a padded row of qkv
+// or dout, which may hold NaN) and masked like a key past the end.  The tile loops run ceil(lengths[n] / 16) tiles.  A unit
+// whose own tile lies wholly in the padding loads nothing and stores its zeros: out, lse, dQ of a padded query and dK, dV
+// of a padded key are exact zeros, D of a padded query is 0.  A live row sees the arithmetic and the tile order of the
+// same row alone with S = lengths[n].  VL is a template parameter beside PK: the instantiations without lengths carry none
+// of this.  Packed form: every slot reads its own pair's length; a pair of length 0 has no live row to clamp onto, so
+// its loads are replaced by zeros (Slot::ld).
+//
 // Dropout on the probabilities: Philox4x32-10 (the generator of head.hip / lime.hip), one block per four consecutive keys,
 //   counter = (offset low, offset high, n * heads + head, 0xC0000000 | query * ceil(S / 4) + key / 4), word key % 4,
 //   keep iff (word >> 8) * 2^-24 >= p: a function of (seed, offset, n, head, query, key) alone.  c3 is none of 0 (dropout),
-//   0x4....... (LIME), 0x8....... (augmentation noise), 0xFFFFFFFD..F (row decisions).  Needs S <= 32768.
+//   0x4....... (LIME), 0x8....... (augmentation noise), 0xFFFFFFFD..F (row decisions).  Needs S <= 32768.  With lengths the
+//   stride stays ceil(S / 4) of the padded S: the decision does not depend on the lengths.
 #include "ops.h"
 
 #include <math.h>
@@ -51,7 +62,16 @@ struct Slot {
   int pair, s, h;      // pair = n * heads + h
   long long row, si;   // row(s, n); pair * S + s (lse, D)
   bool ok;
+  // lengths only: `ok` is "live" (s < lengths[n]); `real` is a position of the padded tensor, live or padding, and wrow /
+  // wsi are its own row(s, n) / pair * S + s, where its zeros are stored; `ld` is false when the pair has no live row at all
+  bool real, ld;
+  long long wrow, wsi;
 };
+
+__device__ __forceinline__ int mha_len(const MhaGeo& g, const int* __restrict__ lens, int n) {
+  const int v = lens[n];
+  return v < 0 ? 0 : (v > g.S ? g.S : v);
+}
 
 // the (n, head) of a pair: two integer divisions, kept out of the tile loops (Unit below)
 __device__ __forceinline__ void mha_split(const MhaGeo& g, int pair, int& n, int& h) {
@@ -62,45 +82,77 @@ __device__ __forceinline__ void mha_split(const MhaGeo& g, int pair, int& n, int
 // what a wave owns: one 16-row tile of one pair (n, h), or -- packed, g.G != 0 -- the pairs u * G .. u * G + G - 1
 struct Unit {
   int u, tile, n, h;
+  int len;   // lengths, one pair per unit: the live positions of n (wave-uniform)
 };
 
 // PK: the packed form (g.G != 0), a template parameter so that the tile loops of the long sequences carry none of its code
-template <bool PK>
-__device__ __forceinline__ Unit mha_unit(const MhaGeo& g, long long unit) {
+template <bool PK, bool VL>
+__device__ __forceinline__ Unit mha_unit(const MhaGeo& g, long long unit, const int* __restrict__ lens) {
   Unit o;
+  o.len = g.S;
   if (PK) { o.u = (int)unit; o.tile = 0; o.n = o.h = 0; }
   else {
     o.u = (int)(unit / g.tiles);
     o.tile = (int)(unit - (long long)o.u * g.tiles);
     mha_split(g, o.u, o.n, o.h);
+    if (VL) o.len = __builtin_amdgcn_readfirstlane(mha_len(g, lens, o.n));
   }
   return o;
 }
 
 // slot idx (0..15) of tile `tile` of the unit
-template <bool PK>
-__device__ __forceinline__ Slot mha_slot(const MhaGeo& g, const Unit& w, int tile, int idx) {
+template <bool PK, bool VL>
+__device__ __forceinline__ Slot mha_slot(const MhaGeo& g, const Unit& w, int tile, int idx, const int* __restrict__ lens) {
   Slot o;
   int n, pc, sc;
+  o.ld = true;
   if (PK) {
     const int k = idx / g.S;
     o.pair = w.u * g.G + k;
     o.s = idx - k * g.S;
-    o.ok = k < g.G && o.pair < g.P;
+    o.ok = o.real = k < g.G && o.pair < g.P;
     pc = o.pair < g.P ? o.pair : g.P - 1;
     sc = o.s;
     mha_split(g, pc, n, o.h);
+    if (VL) {
+      const int len = mha_len(g, lens, n);
+      o.ok = o.real && o.s < len;
+      o.ld = len > 0;
+      sc = o.s < len ? o.s : (len > 0 ? len - 1 : 0);
+    }
   } else {
     o.pair = pc = w.u;
     o.s = tile * 16 + idx;
-    o.ok = o.s < g.S;
-    sc = o.ok ? o.s : g.S - 1;
+    o.ok = o.s < (VL ? w.len : g.S);
+    o.real = o.s < g.S;
+    sc = o.ok ? o.s : (VL ? w.len : g.S) - 1;
     n = w.n;
     o.h = w.h;
   }
   o.row = (long long)sc * g.rs + (long long)n * g.rn;
   o.si = (long long)pc * g.S + sc;
+  if (VL) {
+    const int sw = o.real ? o.s : 0;
+    o.wrow = (long long)sw * g.rs + (long long)n * g.rn;
+    o.wsi = (long long)pc * g.S + sw;
+  } else {
+    o.wrow = o.row;
+    o.wsi = o.si;
+  }
   return o;
+}
+
+// the tiles a unit loops over: all of them, or those that hold a live position of its pair
+template <bool PK, bool VL>
+__device__ __forceinline__ int mha_loop_tiles(const MhaGeo& g, const Unit& w) {
+  return PK ? 1 : (VL ? (w.len + 15) >> 4 : g.tiles);
+}
+
+// lengths: true when none of the unit's own 16 slots (`own` = the lane's slot lane & 15) is live, so that it only stores zeros
+template <bool PK, bool VL>
+__device__ __forceinline__ bool mha_idle(const Unit& w, const Slot& own) {
+  if (!VL) return false;
+  return PK ? !__any(own.ok) : w.tile * 16 >= w.len;
 }
 
 // Philox4x32-10 exactly as in lime.hip
@@ -161,32 +213,57 @@ __device__ __forceinline__ void load_cols(const float* p, float* v) {
   }
 }
 
+// GD (the packed form with lengths): a slot whose pair has no live row reads zeros instead
+template <int CW, bool GD>
+__device__ __forceinline__ void load_cols(const float* p, float* v, bool ld) {
+  if (!GD || ld) load_cols<CW>(p, v);
+  else {
+#pragma unroll
+    for (int q = 0; q < CW; ++q) v[q] = 0.f;
+  }
+}
+
+template <bool GD>
+__device__ __forceinline__ float load_one(const float* p, bool ld) {
+  return !GD || ld ? *p : 0.f;
+}
+
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
-template <int HD, bool PK>
+template <int HD, bool PK, bool VL>
 __global__ __launch_bounds__(256) void mha_fwd_kernel(MhaGeo g, const float* __restrict__ qkv, float* __restrict__ out,
-                                                      float* __restrict__ lse, long long units) {
+                                                      float* __restrict__ lse, long long units,
+                                                      const int* __restrict__ lens) {
   constexpr int CW = HD / 4, NT = HD / 16;
+  constexpr bool GD = PK && VL;
   const long long unit = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (unit >= units) return;   // wave-uniform; the kernel has no barrier
   const int lane = threadIdx.x & 63, i16 = lane & 15, g4 = lane >> 4;
-  const Unit u = mha_unit<PK>(g, unit);
+  const Unit u = mha_unit<PK, VL>(g, unit, lens);
   const int qtile = u.tile;
   const int E3 = 3 * g.E;
-  const Slot q = mha_slot<PK>(g, u, qtile, i16);
+  const Slot q = mha_slot<PK, VL>(g, u, qtile, i16, lens);
   const int hq = q.h;
+  if (mha_idle<PK, VL>(u, q)) {   // wave-uniform: every query of the tile is padding
+    if (!q.real) return;
+    float* dst = out + q.wrow * g.E + hq * HD + g4 * 4;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) *reinterpret_cast<float4*>(dst + t * 16) = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (g4 == 0) lse[q.wsi] = 0.f;
+    return;
+  }
   float qv[CW];
-  load_cols<CW>(qkv + q.row * E3 + hq * HD + g4 * CW, qv);
+  load_cols<CW, GD>(qkv + q.row * E3 + hq * HD + g4 * CW, qv, q.ld);
   f32x4 o[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) o[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = -INFINITY, l = 0.f;
-  const int ktiles = PK ? 1 : g.tiles;
+  const int ktiles = mha_loop_tiles<PK, VL>(g, u);
   for (int kt = 0; kt < ktiles; ++kt) {
-    const Slot ka = mha_slot<PK>(g, u, kt, i16);
+    const Slot ka = mha_slot<PK, VL>(g, u, kt, i16, lens);
     float kv[CW];
-    load_cols<CW>(qkv + ka.row * E3 + g.E + ka.h * HD + g4 * CW, kv);
+    load_cols<CW, GD>(qkv + ka.row * E3 + g.E + ka.h * HD + g4 * CW, kv, ka.ld);
     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < CW; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kv[s], qv[s], acc, 0, 0, 0);
@@ -195,7 +272,7 @@ __global__ __launch_bounds__(256) void mha_fwd_kernel(MhaGeo g, const float* __r
     float mt = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      kr[r] = mha_slot<PK>(g, u, kt, g4 * 4 + r);
+      kr[r] = mha_slot<PK, VL>(g, u, kt, g4 * 4 + r, lens);
       const bool valid = kr[r].ok && q.ok && (!PK || kr[r].pair == q.pair);
       sc[r] = valid ? acc[r] * g.scale : -INFINITY;
       mt = fmaxf(mt, sc[r]);
@@ -227,31 +304,42 @@ __global__ __launch_bounds__(256) void mha_fwd_kernel(MhaGeo g, const float* __r
       o[t] *= alpha;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float v = qkv[kr[r].row * E3 + 2 * g.E + kr[r].h * HD + t * 16 + i16];
+        const float v = load_one<GD>(qkv + kr[r].row * E3 + 2 * g.E + kr[r].h * HD + t * 16 + i16, kr[r].ld);
         o[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(v, p[r], o[t], 0, 0, 0);
       }
     }
   }
-  if (!q.ok) return;
-  float* dst = out + q.row * g.E + hq * HD + g4 * 4;
+  if (!q.real) return;
+  if (VL && !q.ok) {   // a padded query beside live ones: l = 0 here
+    m = 0.f;
+    l = 1.f;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) o[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  float* dst = out + q.wrow * g.E + hq * HD + g4 * 4;
 #pragma unroll
   for (int t = 0; t < NT; ++t)
     *reinterpret_cast<float4*>(dst + t * 16) = make_float4(o[t][0] / l, o[t][1] / l, o[t][2] / l, o[t][3] / l);
-  if (g4 == 0) lse[q.si] = m + logf(l);
+  if (g4 == 0) lse[q.wsi] = m + logf(l);
 }
 
 // ------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------
 // D[pair][s] = dout[row] . out[row] over the head's columns, one thread per (pair, s), a fixed serial order
-template <int HD>
+template <int HD, bool VL>
 __global__ __launch_bounds__(256) void mha_rowdot_kernel(MhaGeo g, const float* __restrict__ out,
-                                                         const float* __restrict__ dout, float* __restrict__ D) {
+                                                         const float* __restrict__ dout, float* __restrict__ D,
+                                                         const int* __restrict__ lens) {
   const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
   if (e >= (long long)g.P * g.S) return;
   const int pair = (int)(e / g.S), s = (int)(e - (long long)pair * g.S);
   int n, h;
   mha_split(g, pair, n, h);
+  if (VL && s >= mha_len(g, lens, n)) {   // a padded query: dout there is never read
+    D[e] = 0.f;
+    return;
+  }
   const long long off = ((long long)s * g.rs + (long long)n * g.rn) * g.E + h * HD;
   float acc = 0.f;
 #pragma unroll
@@ -266,33 +354,44 @@ __global__ __launch_bounds__(256) void mha_rowdot_kernel(MhaGeo g, const float* 
 }
 
 // the wave owns 16 keys: dK and dV
-template <int HD, bool PK>
+template <int HD, bool PK, bool VL>
 __global__ __launch_bounds__(256) void mha_bwd_kv_kernel(MhaGeo g, const float* __restrict__ qkv,
                                                          const float* __restrict__ lse, const float* __restrict__ D,
                                                          const float* __restrict__ dout, float* __restrict__ dqkv,
-                                                         long long units) {
+                                                         long long units, const int* __restrict__ lens) {
   constexpr int CW = HD / 4, NT = HD / 16;
+  constexpr bool GD = PK && VL;
   const long long unit = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (unit >= units) return;
   const int lane = threadIdx.x & 63, i16 = lane & 15, g4 = lane >> 4;
-  const Unit u = mha_unit<PK>(g, unit);
+  const Unit u = mha_unit<PK, VL>(g, unit, lens);
   const int ktile = u.tile;
   const int E3 = 3 * g.E;
-  const Slot k = mha_slot<PK>(g, u, ktile, i16);
+  const Slot k = mha_slot<PK, VL>(g, u, ktile, i16, lens);
   const int hk = k.h;
+  if (mha_idle<PK, VL>(u, k)) {   // wave-uniform: every key of the tile is padding
+    if (!k.real) return;
+    float* dst = dqkv + k.wrow * E3 + hk * HD + g4 * 4;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      *reinterpret_cast<float4*>(dst + g.E + t * 16) = make_float4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<float4*>(dst + 2 * g.E + t * 16) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    return;
+  }
   float kv[CW], vv[CW];
-  load_cols<CW>(qkv + k.row * E3 + g.E + hk * HD + g4 * CW, kv);
-  load_cols<CW>(qkv + k.row * E3 + 2 * g.E + hk * HD + g4 * CW, vv);
+  load_cols<CW, GD>(qkv + k.row * E3 + g.E + hk * HD + g4 * CW, kv, k.ld);
+  load_cols<CW, GD>(qkv + k.row * E3 + 2 * g.E + hk * HD + g4 * CW, vv, k.ld);
   f32x4 dk[NT], dv[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) dk[t] = dv[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int qtiles = PK ? 1 : g.tiles;
+  const int qtiles = mha_loop_tiles<PK, VL>(g, u);
   for (int qt = 0; qt < qtiles; ++qt) {
-    const Slot qa = mha_slot<PK>(g, u, qt, i16);
+    const Slot qa = mha_slot<PK, VL>(g, u, qt, i16, lens);
     const int ha = qa.h;
     float qv[CW], dov[CW];
-    load_cols<CW>(qkv + qa.row * E3 + ha * HD + g4 * CW, qv);
-    load_cols<CW>(dout + qa.row * g.E + ha * HD + g4 * CW, dov);
+    load_cols<CW, GD>(qkv + qa.row * E3 + ha * HD + g4 * CW, qv, qa.ld);
+    load_cols<CW, GD>(dout + qa.row * g.E + ha * HD + g4 * CW, dov, qa.ld);
     f32x4 as = f32x4{0.f, 0.f, 0.f, 0.f}, ap = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < CW; ++s) {
@@ -303,7 +402,7 @@ __global__ __launch_bounds__(256) void mha_bwd_kv_kernel(MhaGeo g, const float* 
     float pd[4], ds[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      qr[r] = mha_slot<PK>(g, u, qt, g4 * 4 + r);
+      qr[r] = mha_slot<PK, VL>(g, u, qt, g4 * 4 + r, lens);
       const bool valid = qr[r].ok && k.ok && (!PK || qr[r].pair == k.pair);
       const float lr = lse[qr[r].si], dr = D[qr[r].si];
       const float p = valid ? expf(as[r] * g.scale - lr) : 0.f;
@@ -322,15 +421,19 @@ __global__ __launch_bounds__(256) void mha_bwd_kv_kernel(MhaGeo g, const float* 
       for (int r = 0; r < 4; ++r) {
         const long long row = qr[r].row;
         const int col = qr[r].h * HD + t * 16 + i16;
-        const float a_do = dout[row * g.E + col];
-        const float a_q = qkv[row * E3 + col];
+        const float a_do = load_one<GD>(dout + row * g.E + col, qr[r].ld);
+        const float a_q = load_one<GD>(qkv + row * E3 + col, qr[r].ld);
         dv[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_do, pd[r], dv[t], 0, 0, 0);
         dk[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_q, ds[r], dk[t], 0, 0, 0);
       }
     }
   }
-  if (!k.ok) return;
-  float* dst = dqkv + k.row * E3 + hk * HD + g4 * 4;
+  if (!k.real) return;
+  if (VL && !k.ok) {   // a padded key beside live ones
+#pragma unroll
+    for (int t = 0; t < NT; ++t) dk[t] = dv[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  float* dst = dqkv + k.wrow * E3 + hk * HD + g4 * 4;
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     *reinterpret_cast<float4*>(dst + g.E + t * 16) =
@@ -340,34 +443,42 @@ __global__ __launch_bounds__(256) void mha_bwd_kv_kernel(MhaGeo g, const float* 
 }
 
 // the wave owns 16 queries: dQ
-template <int HD, bool PK>
+template <int HD, bool PK, bool VL>
 __global__ __launch_bounds__(256) void mha_bwd_q_kernel(MhaGeo g, const float* __restrict__ qkv,
                                                         const float* __restrict__ lse, const float* __restrict__ D,
                                                         const float* __restrict__ dout, float* __restrict__ dqkv,
-                                                        long long units) {
+                                                        long long units, const int* __restrict__ lens) {
   constexpr int CW = HD / 4, NT = HD / 16;
+  constexpr bool GD = PK && VL;
   const long long unit = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (unit >= units) return;
   const int lane = threadIdx.x & 63, i16 = lane & 15, g4 = lane >> 4;
-  const Unit u = mha_unit<PK>(g, unit);
+  const Unit u = mha_unit<PK, VL>(g, unit, lens);
   const int qtile = u.tile;
   const int E3 = 3 * g.E;
-  const Slot q = mha_slot<PK>(g, u, qtile, i16);
+  const Slot q = mha_slot<PK, VL>(g, u, qtile, i16, lens);
   const int hq = q.h;
+  if (mha_idle<PK, VL>(u, q)) {   // wave-uniform: every query of the tile is padding
+    if (!q.real) return;
+    float* dst = dqkv + q.wrow * E3 + hq * HD + g4 * 4;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) *reinterpret_cast<float4*>(dst + t * 16) = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
   float qv[CW], dov[CW];
-  load_cols<CW>(qkv + q.row * E3 + hq * HD + g4 * CW, qv);
-  load_cols<CW>(dout + q.row * g.E + hq * HD + g4 * CW, dov);
+  load_cols<CW, GD>(qkv + q.row * E3 + hq * HD + g4 * CW, qv, q.ld);
+  load_cols<CW, GD>(dout + q.row * g.E + hq * HD + g4 * CW, dov, q.ld);
   const float lq = lse[q.si], dq_row = D[q.si];
   f32x4 dq[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) dq[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int ktiles = PK ? 1 : g.tiles;
+  const int ktiles = mha_loop_tiles<PK, VL>(g, u);
   for (int kt = 0; kt < ktiles; ++kt) {
-    const Slot ka = mha_slot<PK>(g, u, kt, i16);
+    const Slot ka = mha_slot<PK, VL>(g, u, kt, i16, lens);
     const int ha = ka.h;
     float kv[CW], vv[CW];
-    load_cols<CW>(qkv + ka.row * E3 + g.E + ha * HD + g4 * CW, kv);
-    load_cols<CW>(qkv + ka.row * E3 + 2 * g.E + ha * HD + g4 * CW, vv);
+    load_cols<CW, GD>(qkv + ka.row * E3 + g.E + ha * HD + g4 * CW, kv, ka.ld);
+    load_cols<CW, GD>(qkv + ka.row * E3 + 2 * g.E + ha * HD + g4 * CW, vv, ka.ld);
     f32x4 as = f32x4{0.f, 0.f, 0.f, 0.f}, ap = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < CW; ++s) {
@@ -380,7 +491,7 @@ __global__ __launch_bounds__(256) void mha_bwd_q_kernel(MhaGeo g, const float* _
     unsigned w[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      kr[r] = mha_slot<PK>(g, u, kt, g4 * 4 + r);
+      kr[r] = mha_slot<PK, VL>(g, u, kt, g4 * 4 + r, lens);
       const bool valid = kr[r].ok && q.ok && (!PK || kr[r].pair == q.pair);
       const float p = valid ? expf(as[r] * g.scale - lq) : 0.f;
       float dp = ap[r];
@@ -395,13 +506,17 @@ __global__ __launch_bounds__(256) void mha_bwd_q_kernel(MhaGeo g, const float* _
     for (int t = 0; t < NT; ++t) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float a_k = qkv[kr[r].row * E3 + g.E + kr[r].h * HD + t * 16 + i16];
+        const float a_k = load_one<GD>(qkv + kr[r].row * E3 + g.E + kr[r].h * HD + t * 16 + i16, kr[r].ld);
         dq[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_k, ds[r], dq[t], 0, 0, 0);
       }
     }
   }
-  if (!q.ok) return;
-  float* dst = dqkv + q.row * E3 + hq * HD + g4 * 4;
+  if (!q.real) return;
+  if (VL && !q.ok) {   // a padded query beside live ones
+#pragma unroll
+    for (int t = 0; t < NT; ++t) dq[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  float* dst = dqkv + q.wrow * E3 + hq * HD + g4 * 4;
 #pragma unroll
   for (int t = 0; t < NT; ++t)
     *reinterpret_cast<float4*>(dst + t * 16) =
@@ -586,49 +701,78 @@ extern "C" size_t ecgmm_mha_bwd_workspace(const ecgmm_mha_desc* d) {
   return align_up((size_t)g.P * g.S * sizeof(float), 256);
 }
 
-extern "C" int ecgmm_mha_forward(const ecgmm_mha_desc* d, const float* qkv, float* out, float* lse, uint64_t seed,
-                                 uint64_t offset, void* stream) {
+// the instantiation of a kernel template for (head_dim, packed, with lengths)
+#define MHA_PICK(kernel, hd, pk, vl)                                                               \
+  ((hd) == 16 ? ((pk) ? ((vl) ? kernel<16, true, true> : kernel<16, true, false>)                  \
+                      : ((vl) ? kernel<16, false, true> : kernel<16, false, false>))               \
+              : ((pk) ? ((vl) ? kernel<32, true, true> : kernel<32, true, false>)                  \
+                      : ((vl) ? kernel<32, false, true> : kernel<32, false, false>)))
+
+static int mha_forward_impl(const char* what, const ecgmm_mha_desc* d, const float* qkv, const int32_t* lengths, float* out,
+                            float* lse, uint64_t seed, uint64_t offset, void* stream) {
   MhaGeo g;
-  ECG_TRY(mha_geo(d, "mha_forward", &g));
-  if (!qkv || !out || !lse) ECG_FAIL(ECGMM_ERR_SHAPE, "mha_forward: null operand");
-  if (!aligned16(qkv) || !aligned16(out)) ECG_FAIL(ECGMM_ERR_SHAPE, "mha_forward: qkv and out must be 16-byte aligned");
+  ECG_TRY(mha_geo(d, what, &g));
+  if (!qkv || !out || !lse) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: null operand", what);
+  if (!aligned16(qkv) || !aligned16(out)) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: qkv and out must be 16-byte aligned", what);
   g.seed = seed; g.offset = offset;
   const long long units = mha_units(g);
   const dim3 grid((unsigned)((units + 3) / 4));
-  auto* fn = d->head_dim == 16 ? (g.G ? mha_fwd_kernel<16, true> : mha_fwd_kernel<16, false>)
-                               : (g.G ? mha_fwd_kernel<32, true> : mha_fwd_kernel<32, false>);
-  hipLaunchKernelGGL(fn, grid, dim3(256), 0, (hipStream_t)stream, g, qkv, out, lse, units);
-  ECG_CHECK_LAUNCH("mha_forward");
+  auto* fn = MHA_PICK(mha_fwd_kernel, d->head_dim, g.G != 0, lengths != nullptr);
+  hipLaunchKernelGGL(fn, grid, dim3(256), 0, (hipStream_t)stream, g, qkv, out, lse, units, (const int*)lengths);
+  ECG_CHECK_LAUNCH(what);
   return 0;
 }
 
-extern "C" int ecgmm_mha_backward(const ecgmm_mha_desc* d, const float* qkv, const float* out, const float* lse,
-                                  const float* dout, float* dqkv, void* ws, size_t ws_bytes, uint64_t seed, uint64_t offset,
-                                  void* stream) {
+static int mha_backward_impl(const char* what, const ecgmm_mha_desc* d, const float* qkv, const int32_t* lengths,
+                             const float* out, const float* lse, const float* dout, float* dqkv, void* ws, size_t ws_bytes,
+                             uint64_t seed, uint64_t offset, void* stream) {
   MhaGeo g;
-  ECG_TRY(mha_geo(d, "mha_backward", &g));
-  if (!qkv || !out || !lse || !dout || !dqkv || !ws) ECG_FAIL(ECGMM_ERR_SHAPE, "mha_backward: null operand");
+  ECG_TRY(mha_geo(d, what, &g));
+  if (!qkv || !out || !lse || !dout || !dqkv || !ws) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: null operand", what);
   if (!aligned16(qkv) || !aligned16(out) || !aligned16(dout) || !aligned16(dqkv))
-    ECG_FAIL(ECGMM_ERR_SHAPE, "mha_backward: qkv, out, dout and dqkv must be 16-byte aligned");
+    ECG_FAIL(ECGMM_ERR_SHAPE, "%s: qkv, out, dout and dqkv must be 16-byte aligned", what);
   const size_t need = align_up((size_t)g.P * g.S * sizeof(float), 256);
-  if (ws_bytes < need) ECG_FAIL(ECGMM_ERR_WORKSPACE, "mha_backward: workspace of %zu bytes, %zu needed", ws_bytes, need);
+  if (ws_bytes < need) ECG_FAIL(ECGMM_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", what, ws_bytes, need);
   g.seed = seed; g.offset = offset;
   hipStream_t st = (hipStream_t)stream;
   float* D = (float*)ws;
   const long long units = mha_units(g);
   const dim3 grid((unsigned)((units + 3) / 4)), grid_d((unsigned)(((long long)g.P * g.S + 255) / 256));
-  auto* fn_d = d->head_dim == 16 ? mha_rowdot_kernel<16> : mha_rowdot_kernel<32>;
-  auto* fn_kv = d->head_dim == 16 ? (g.G ? mha_bwd_kv_kernel<16, true> : mha_bwd_kv_kernel<16, false>)
-                                  : (g.G ? mha_bwd_kv_kernel<32, true> : mha_bwd_kv_kernel<32, false>);
-  auto* fn_q = d->head_dim == 16 ? (g.G ? mha_bwd_q_kernel<16, true> : mha_bwd_q_kernel<16, false>)
-                                 : (g.G ? mha_bwd_q_kernel<32, true> : mha_bwd_q_kernel<32, false>);
-  hipLaunchKernelGGL(fn_d, grid_d, dim3(256), 0, st, g, out, dout, D);
-  ECG_CHECK_LAUNCH("mha_backward rowdot");
-  hipLaunchKernelGGL(fn_kv, grid, dim3(256), 0, st, g, qkv, lse, D, dout, dqkv, units);
-  ECG_CHECK_LAUNCH("mha_backward dK dV");
-  hipLaunchKernelGGL(fn_q, grid, dim3(256), 0, st, g, qkv, lse, D, dout, dqkv, units);
-  ECG_CHECK_LAUNCH("mha_backward dQ");
+  const bool vl = lengths != nullptr, pk = g.G != 0;
+  const int* lens = (const int*)lengths;
+  auto* fn_d = d->head_dim == 16 ? (vl ? mha_rowdot_kernel<16, true> : mha_rowdot_kernel<16, false>)
+                                 : (vl ? mha_rowdot_kernel<32, true> : mha_rowdot_kernel<32, false>);
+  auto* fn_kv = MHA_PICK(mha_bwd_kv_kernel, d->head_dim, pk, vl);
+  auto* fn_q = MHA_PICK(mha_bwd_q_kernel, d->head_dim, pk, vl);
+  hipLaunchKernelGGL(fn_d, grid_d, dim3(256), 0, st, g, out, dout, D, lens);
+  ECG_CHECK_LAUNCH(what);
+  hipLaunchKernelGGL(fn_kv, grid, dim3(256), 0, st, g, qkv, lse, D, dout, dqkv, units, lens);
+  ECG_CHECK_LAUNCH(what);
+  hipLaunchKernelGGL(fn_q, grid, dim3(256), 0, st, g, qkv, lse, D, dout, dqkv, units, lens);
+  ECG_CHECK_LAUNCH(what);
   return 0;
+}
+
+extern "C" int ecgmm_mha_forward(const ecgmm_mha_desc* d, const float* qkv, float* out, float* lse, uint64_t seed,
+                                 uint64_t offset, void* stream) {
+  return mha_forward_impl("mha_forward", d, qkv, nullptr, out, lse, seed, offset, stream);
+}
+
+extern "C" int ecgmm_mha_backward(const ecgmm_mha_desc* d, const float* qkv, const float* out, const float* lse,
+                                  const float* dout, float* dqkv, void* ws, size_t ws_bytes, uint64_t seed, uint64_t offset,
+                                  void* stream) {
+  return mha_backward_impl("mha_backward", d, qkv, nullptr, out, lse, dout, dqkv, ws, ws_bytes, seed, offset, stream);
+}
+
+extern "C" int ecgmm_mha_forward_varlen(const ecgmm_mha_desc* d, const float* qkv, const int32_t* lengths, float* out,
+                                        float* lse, uint64_t seed, uint64_t offset, void* stream) {
+  return mha_forward_impl("mha_forward_varlen", d, qkv, lengths, out, lse, seed, offset, stream);
+}
+
+extern "C" int ecgmm_mha_backward_varlen(const ecgmm_mha_desc* d, const float* qkv, const int32_t* lengths, const float* out,
+                                         const float* lse, const float* dout, float* dqkv, void* ws, size_t ws_bytes,
+                                         uint64_t seed, uint64_t offset, void* stream) {
+  return mha_backward_impl("mha_backward_varlen", d, qkv, lengths, out, lse, dout, dqkv, ws, ws_bytes, seed, offset, stream);
 }
 
 extern "C" int ecgmm_mha_keep_mask(const ecgmm_mha_desc* d, uint8_t* mask, uint64_t seed, uint64_t offset, void* stream) {

@@ -860,11 +860,12 @@ def _aligned16(t):
 class MultiHeadAttentionFn(torch.autograd.Function):
     """out [rows, E] = concat_heads(softmax(Q K^T / sqrt(d)) V) of the packed projection qkv [rows, 3E] (csrc/attention.hip).
     Saves qkv, out and one log-sum-exp per score row; the backward recomputes the probabilities and, with dropout, the keep
-    decisions from the call's (seed, offset)."""
+    decisions from the call's (seed, offset).  ``cfg`` may carry a sixth entry, the device ``int32 [N]`` lengths (or
+    ``None``): the ``_varlen`` entry points, else the fixed ones; the lengths are kept for the backward."""
 
     @staticmethod
     def forward(ctx, qkv, cfg):
-        S, N, heads, batch_first, p = cfg
+        S, N, heads, batch_first, p, lengths = (tuple(cfg) + (None,))[:6]
         _require_cuda(qkv, "multi_head_attention")
         if qkv.dim() != 2 or qkv.shape[0] != S * N or qkv.shape[1] % (3 * heads):
             raise RuntimeError(f"multi_head_attention: qkv must be [S * N, 3 * E] with E a multiple of heads, got "
@@ -875,8 +876,15 @@ class MultiHeadAttentionFn(torch.autograd.Function):
         out = torch.empty(S * N, E, device=qkv.device, dtype=torch.float32)
         lse = torch.empty(N * heads * S, device=qkv.device, dtype=torch.float32)
         seed, off = _PhiloxState.take(4) if p > 0 else (0, 0)
-        L.check(L.lib().ecgmm_mha_forward(C.byref(desc), ptr(qkv), ptr(out), ptr(lse), seed, off, stream()), "mha_forward")
-        ctx.desc, ctx.rng = desc, (seed, off)
+        if lengths is None:
+            L.check(L.lib().ecgmm_mha_forward(C.byref(desc), ptr(qkv), ptr(out), ptr(lse), seed, off, stream()), "mha_forward")
+        else:
+            if lengths.dtype != torch.int32 or tuple(lengths.shape) != (N,) or lengths.device != qkv.device:
+                raise RuntimeError(f"multi_head_attention: lengths must be int32 [{N}] on {qkv.device} (HF.check_lengths)")
+            lengths = lengths.contiguous()
+            L.check(L.lib().ecgmm_mha_forward_varlen(C.byref(desc), ptr(qkv), ptr(lengths), ptr(out), ptr(lse), seed, off,
+                                                     stream()), "mha_forward_varlen")
+        ctx.desc, ctx.rng, ctx.lengths = desc, (seed, off), lengths
         ctx.save_for_backward(qkv, out, lse)
         return out
 
@@ -888,17 +896,33 @@ class MultiHeadAttentionFn(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         lib = L.lib()
         ws = _Scratch.get("mha_bwd", lib.ecgmm_mha_bwd_workspace(C.byref(desc)), qkv.device)
-        L.check(lib.ecgmm_mha_backward(C.byref(desc), ptr(qkv), ptr(out), ptr(lse), ptr(dout), ptr(dqkv), ptr(ws),
-                                       ws.numel(), ctx.rng[0], ctx.rng[1], stream()), "mha_backward")
+        if ctx.lengths is None:
+            L.check(lib.ecgmm_mha_backward(C.byref(desc), ptr(qkv), ptr(out), ptr(lse), ptr(dout), ptr(dqkv), ptr(ws),
+                                           ws.numel(), ctx.rng[0], ctx.rng[1], stream()), "mha_backward")
+        else:
+            L.check(lib.ecgmm_mha_backward_varlen(C.byref(desc), ptr(qkv), ptr(ctx.lengths), ptr(out), ptr(lse), ptr(dout),
+                                                  ptr(dqkv), ptr(ws), ws.numel(), ctx.rng[0], ctx.rng[1], stream()),
+                    "mha_backward_varlen")
         return dqkv, None
 
 
-def multi_head_attention(qkv, S, N, heads, batch_first=False, p=0.0, training=False):
+def multi_head_attention(qkv, S, N, heads, batch_first=False, p=0.0, training=False, lengths=None):
     """Self-attention on the packed projection ``qkv`` [S * N, 3E] (row ``s * N + n``, or ``n * S + s`` with
     ``batch_first``) -> [S * N, E], heads concatenated.  ``p``: dropout on the attention weights, in training only; its
-    Philox offset comes from :func:`manual_seed`'s stream."""
+    Philox offset comes from :func:`manual_seed`'s stream.
+
+    ``lengths`` (one per attention-batch element ``n``, see :func:`check_lengths`): positions ``s >= lengths[n]`` are padding,
+    torch's ``key_padding_mask[n, s] = s >= lengths[n]``: no query attends to them, their own output rows are exact zeros and
+    so are their rows of the gradient.  Padded rows of ``qkv`` (and of the incoming gradient) are never read and may hold
+    anything.  A device tensor is not synced: the kernels clamp it to ``[0, S]`` (a 0 makes everything of ``n`` zero)."""
     p = float(p) if training else 0.0
-    return MultiHeadAttentionFn.apply(qkv, (int(S), int(N), int(heads), bool(batch_first), p))
+    cfg = (int(S), int(N), int(heads), bool(batch_first), p)
+    if lengths is not None:
+        if not (isinstance(lengths, torch.Tensor) and lengths.dtype == torch.int32 and tuple(lengths.shape) == (int(N),)
+                and lengths.device == qkv.device):
+            lengths = check_lengths(lengths, int(N), int(S)).to(qkv.device)
+        cfg += (lengths,)
+    return MultiHeadAttentionFn.apply(qkv, cfg)
 
 
 class AddFn(torch.autograd.Function):

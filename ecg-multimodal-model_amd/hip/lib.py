@@ -240,6 +240,8 @@ SIGNATURES = {
     "ecgmm_mha_forward": (i32, [P(MHADesc), vp, vp, vp, u64, u64, vp]),
     "ecgmm_mha_backward": (i32, [P(MHADesc), vp, vp, vp, vp, vp, vp, sz, u64, u64, vp]),
     "ecgmm_mha_keep_mask": (i32, [P(MHADesc), vp, u64, u64, vp]),
+    "ecgmm_mha_forward_varlen": (i32, [P(MHADesc), vp, vp, vp, vp, u64, u64, vp]),
+    "ecgmm_mha_backward_varlen": (i32, [P(MHADesc), vp, vp, vp, vp, vp, vp, vp, sz, u64, u64, vp]),
     "ecgmm_embed1d_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "ecgmm_embed1d_bwd_workspace": (sz, [i32, i32, i32, i32]),
     "ecgmm_embed1d_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
@@ -289,7 +291,9 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  "ecgmm_lstm_forward_varlen", "ecgmm_lstm_backward_varlen", "ecgmm_seq_mean_varlen_fwd",
                  "ecgmm_seq_mean_varlen_bwd",
                  # the lane rule of the chunked filtfilt kernels (csrc/preprocess.hip)
-                 "ecgmm_signal_filter_lanes")
+                 "ecgmm_signal_filter_lanes",
+                 # lengths in the attention kernels (csrc/attention.hip)
+                 "ecgmm_mha_forward_varlen", "ecgmm_mha_backward_varlen")
 
 _lib = None
 

@@ -225,26 +225,40 @@ class MultiheadAttention(nn.Module):
         nn.init.constant_(self.out_proj.bias, 0.0)
 
     def forward(self, query, key=None, value=None, key_padding_mask=None, need_weights=False, attn_mask=None,
-                is_causal=False):
+                is_causal=False, *, lengths=None):
+        """``lengths`` (keyword only; a list, a CPU or a device integer tensor, one per attention-batch element: dimension 0
+        of the input with ``batch_first``, dimension 1 otherwise): positions at or behind an element's length are padding,
+        torch's ``key_padding_mask[n, s] = s >= lengths[n]`` (:func:`ecgmm.hip.functional.multi_head_attention`).  The
+        projections run over all rows, so PADDED INPUT MUST BE FINITE; the attention output is exactly zero at padded
+        positions, the module's output there is ``out_proj.bias``."""
         for name, t in (("key", key), ("value", value)):
             if t is not None and t is not query:
                 raise ValueError(f"MultiheadAttention: a separate {name} is not supported (self-attention only)")
         for name, t in (("key_padding_mask", key_padding_mask), ("attn_mask", attn_mask)):
             if t is not None:
-                raise ValueError(f"MultiheadAttention: {name} is not supported (no masks)")
+                raise ValueError(f"MultiheadAttention: {name} is not supported (no masks; for padding pass lengths=)")
         if is_causal:
             raise ValueError("MultiheadAttention: is_causal=True is not supported (no masks)")
         if need_weights:
             raise ValueError("MultiheadAttention: need_weights=True is not supported (the weights are never formed)")
         if query.dim() != 3 or query.shape[2] != self.embed_dim:
             raise ValueError(f"MultiheadAttention: input must be 3-D with {self.embed_dim} features, got {tuple(query.shape)}")
-        return self._attend(query.reshape(-1, self.embed_dim), query.shape).reshape(query.shape), None
+        lengths = self._lengths(lengths, query)
+        return self._attend(query.reshape(-1, self.embed_dim), query.shape, lengths).reshape(query.shape), None
 
-    def _attend(self, x2, shape):
-        """x2 [rows, E], the rows of a tensor of ``shape`` -> [rows, E]"""
+    def _lengths(self, lengths, x):
+        """``lengths`` of a 3-D input ``x`` -> ``None`` or the device ``int32 [N]`` tensor the kernels take, validated once
+        (:func:`ecgmm.hip.functional.check_lengths`; a device tensor is taken as given)"""
+        if lengths is None:
+            return None
+        S, N = (x.shape[1], x.shape[0]) if self.batch_first else (x.shape[0], x.shape[1])
+        return HF.check_lengths(lengths, N, S).to(x.device)
+
+    def _attend(self, x2, shape, lengths=None):
+        """x2 [rows, E], the rows of a tensor of ``shape`` -> [rows, E]; ``lengths``: as :meth:`_lengths` returns them"""
         S, N = (shape[1], shape[0]) if self.batch_first else (shape[0], shape[1])
         qkv = HF.linear(x2, self.in_proj_weight, self.in_proj_bias)
-        a = HF.multi_head_attention(qkv, S, N, self.num_heads, self.batch_first, self.dropout, self.training)
+        a = HF.multi_head_attention(qkv, S, N, self.num_heads, self.batch_first, self.dropout, self.training, lengths)
         return HF.linear(a, self.out_proj.weight, self.out_proj.bias)
 
 
@@ -273,18 +287,24 @@ class TransformerEncoderLayer(nn.Module):
         self.dropout1 = nn.Dropout(dropout)
         self.dropout2 = nn.Dropout(dropout)
 
-    def forward(self, src, src_mask=None, src_key_padding_mask=None, is_causal=False):
+    def forward(self, src, src_mask=None, src_key_padding_mask=None, is_causal=False, *, lengths=None):
+        """``lengths`` (keyword only): one length per attention-batch element (dimension 0 of ``src`` with ``batch_first``,
+        dimension 1 otherwise), as :meth:`MultiheadAttention.forward` takes them: padded positions are never keys.
+        Everything around the attention (projections, residual adds, LayerNorm, feed-forward) runs over all rows, so
+        PADDED ``src`` MUST BE FINITE and the padded rows of the output are not zero; nothing live depends on them, and
+        their gradient is zero when the loss ignores them."""
         for name, t in (("src_mask", src_mask), ("src_key_padding_mask", src_key_padding_mask)):
             if t is not None:
-                raise ValueError(f"TransformerEncoderLayer: {name} is not supported (no masks)")
+                raise ValueError(f"TransformerEncoderLayer: {name} is not supported (no masks; for padding pass lengths=)")
         if is_causal:
             raise ValueError("TransformerEncoderLayer: is_causal=True is not supported (no masks)")
         E = self.self_attn.embed_dim
         if src.dim() != 3 or src.shape[2] != E:
             raise ValueError(f"TransformerEncoderLayer: input must be 3-D with {E} features, got {tuple(src.shape)}")
+        lengths = self.self_attn._lengths(lengths, src)
         t = self.training
         x = src.reshape(-1, E)
-        a = HF.dropout(self.self_attn._attend(x, src.shape), self.dropout1.p, t and self.dropout1.training)
+        a = HF.dropout(self.self_attn._attend(x, src.shape, lengths), self.dropout1.p, t and self.dropout1.training)
         x = self.norm1(HF.add(x, a))
         h = HF.dropout(self.linear1(x, act=L.ACT_RELU), self.dropout.p, t and self.dropout.training)
         f = HF.dropout(self.linear2(h), self.dropout2.p, t and self.dropout2.training)
@@ -308,13 +328,17 @@ class TransformerEncoder(nn.Module):
         self.num_layers = num_layers
         self.norm = None
 
-    def forward(self, src, mask=None, src_key_padding_mask=None, is_causal=None):
+    def forward(self, src, mask=None, src_key_padding_mask=None, is_causal=None, *, lengths=None):
+        """``lengths`` (keyword only): one length per attention-batch element, validated once and passed to every layer
+        (:meth:`TransformerEncoderLayer.forward`: padded ``src`` must be finite, padded output rows are not zero)."""
         for name, t in (("mask", mask), ("src_key_padding_mask", src_key_padding_mask)):
             if t is not None:
-                raise ValueError(f"TransformerEncoder: {name} is not supported (no masks)")
+                raise ValueError(f"TransformerEncoder: {name} is not supported (no masks; for padding pass lengths=)")
         if is_causal:
             raise ValueError("TransformerEncoder: is_causal=True is not supported (no masks)")
+        if lengths is not None and src.dim() == 3:
+            lengths = self.layers[0].self_attn._lengths(lengths, src)
         x = src
         for layer in self.layers:
-            x = layer(x)
+            x = layer(x) if lengths is None else layer(x, lengths=lengths)
         return x

@@ -6,7 +6,9 @@ The reference filters every sample again at every ``__getitem__`` on the CPU (4t
 ``gather_augment`` launch gathers the rows and applies ``augment_signal`` on the device.  The model, loss, optimizer and
 schedule are the reference's: ``ResNet1D_SE`` on ``[B, 1, 3000]``, ``FocalLoss(1, 2)``, Adam(1e-3), OneCycleLR per batch.
 ``main(model="transformer")`` trains the reference's one-line alternative instead (train_physionet.py:276),
-:class:`ECGTransformer1D` on the native attention kernels.
+:class:`ECGTransformer1D` on the native attention kernels; ``time_attention=True`` lets it attend along each record's
+positions instead of across the batch, and ``use_lengths=True`` then hands it every record's own length, so that the zero
+padding of a short record is neither attended to nor averaged.
 
 This module holds the model alternative, the device pre-processing, the record reader, the resident dataset and loader and
 the policy values; the epoch loop, the checkpoint test loop and the metrics are ``ecgmm.training``'s, the gather launch is
@@ -51,36 +53,62 @@ class ECGTransformer1D(torch.nn.Module):
     The reference builds its encoder layers with torch's default ``batch_first=False`` and feeds them ``[B, L, d_model]``
     (:219, :236), so attention runs ACROSS THE BATCH: the sequence is the B samples of the batch and each of the L positions
     is an independent attention "batch" element.  A sample's logits therefore depend on the other samples of its batch, in
-    eval mode too.  That is reproduced here as it is, not corrected."""
+    eval mode too.  That is reproduced here as it is, not corrected: it is the default.
 
-    def __init__(self, input_dim=1, seq_len=3000, num_classes=2, d_model=128, nhead=4, num_layers=2, dim_feedforward=256):
+    ``time_attention=True`` builds the layers with ``batch_first=True`` instead, the reference's own intended design
+    (multimodal_paper_modal_balance.py:133-140): every sample attends along its own L positions and its logits depend on
+    nothing else in the batch.  Parameter names and shapes are the same in both modes, so checkpoints move between them.
+    Only then does ``forward(x, lengths=...)`` make sense: one length per sample (``HF.check_lengths``), the positions behind
+    it are never keys and do not enter the mean over the positions, and the padded samples of ``x`` are replaced by zeros
+    before the convolution (its 3-tap window at the last live position reaches one sample into the padding).  A sample's
+    logits then depend on its own live samples alone, bit for bit."""
+
+    def __init__(self, input_dim=1, seq_len=3000, num_classes=2, d_model=128, nhead=4, num_layers=2, dim_feedforward=256,
+                 time_attention=False):
         super().__init__()
+        self.time_attention = bool(time_attention)
         self.conv = HN.Conv1d(input_dim, d_model, kernel_size=3, padding=1)
         self.pos_embedding = torch.nn.Parameter(torch.zeros(1, seq_len, d_model))
-        encoder_layer = HN.TransformerEncoderLayer(d_model=d_model, nhead=nhead, dim_feedforward=dim_feedforward)
+        encoder_layer = HN.TransformerEncoderLayer(d_model=d_model, nhead=nhead, dim_feedforward=dim_feedforward,
+                                                   batch_first=self.time_attention)
         self.transformer_encoder = HN.TransformerEncoder(encoder_layer, num_layers=num_layers)
         self.global_pool = torch.nn.AdaptiveAvgPool1d(1)   # (executed as HF.seq_mean over the positions)
         self.classifier = HN.Sequential(torch.nn.Flatten(), HN.Linear(d_model, 64), torch.nn.ReLU(), torch.nn.Dropout(0.3),
                                         HN.Linear(64, num_classes))
 
-    def forward(self, x):
+    def forward(self, x, lengths=None):
+        if lengths is not None and not self.time_attention:
+            raise ValueError("ECGTransformer1D: lengths needs time_attention=True (attention across the batch has no "
+                             "per-sample length)")
+        if lengths is not None and isinstance(x, torch.Tensor) and x.dim() == 3:
+            lengths = HF.check_lengths(lengths, x.shape[0], x.shape[2]).to(x.device)
         _require_cuda(x, "ECGTransformer1D")
         if x.dim() != 3 or x.shape[1] != self.conv.in_channels:
             raise ValueError(f"ECGTransformer1D expects [B, {self.conv.in_channels}, L], got {tuple(x.shape)}")
         if x.shape[2] > self.pos_embedding.shape[1]:
             raise ValueError(f"ECGTransformer1D: L={x.shape[2]} exceeds seq_len={self.pos_embedding.shape[1]}")
+        if lengths is not None:
+            # the conv's right tap at a record's last live position reads the first padded sample: the padding of the raw
+            # input is set to zero (plumbing on [B, C, L]), so that nothing live depends on what the padding holds
+            live = torch.arange(x.shape[2], device=x.device)[None, None, :] < lengths[:, None, None]
+            x = x.masked_fill(~live, 0.0)
         x = HF.embed1d(x, self.conv.weight, self.conv.bias, self.pos_embedding)   # [B, L, d_model]
-        x = self.transformer_encoder(x)                                            # sequence axis = B, as the reference
-        return self.classifier(HF.seq_mean(x))
+        if lengths is None:
+            x = self.transformer_encoder(x)                 # sequence axis = B as the reference, or L with time_attention
+            return self.classifier(HF.seq_mean(x))
+        x = self.transformer_encoder(x, lengths=lengths)
+        return self.classifier(HF.seq_mean(x, lengths))
 
 
-def build_model(model="resnet", num_classes=2, config=Config, seq_len=MAX_LEN):
+def build_model(model="resnet", num_classes=2, config=Config, seq_len=MAX_LEN, time_attention=False):
     """The network ``main`` trains: ``"resnet"`` = ``ResNet1D_SE`` (train_physionet.py:275), ``"transformer"`` =
-    :class:`ECGTransformer1D` (:276)."""
+    :class:`ECGTransformer1D` (:276), with ``time_attention`` attending along the positions."""
     if model == "resnet":
+        if time_attention:
+            raise ValueError("time_attention=True needs model='transformer'")
         return ResNet1D_SE(num_classes=num_classes, compute_dtype=getattr(config, "compute_dtype", "bf16"))
     if model == "transformer":
-        return ECGTransformer1D(seq_len=seq_len, num_classes=num_classes)
+        return ECGTransformer1D(seq_len=seq_len, num_classes=num_classes, time_attention=time_attention)
     raise ValueError(f"model={model!r}: expected 'resnet' or 'transformer'")
 
 
@@ -225,13 +253,23 @@ def load_records(config=Config, label_map=LABEL_MAP, quiet=True):
 # --------------------------------------------------------------------------------------------
 class SignalOnlyDataset:
     """One split, resident on the device: padded to ``max_len`` on the host, uploaded once, band-pass filtered and
-    z-scored once (train_physionet.py:63-86 does both per sample per epoch).  ``signals`` [n, max_len] fp32, ``labels`` [n]."""
+    z-scored once (train_physionet.py:63-86 does both per sample per epoch).  ``signals`` [n, max_len] fp32, ``labels`` [n].
+    ``with_lengths``: the dataset also carries ``lengths`` [n] int32 on the device (``lengths_host`` on the host),
+    ``min(len(record), max_len)`` per record: the samples of a row that are the record's own.  The filter and the z-score
+    still run over the padded row, as the reference's do."""
 
-    def __init__(self, indices, labels, ecg_signals, augment=True, max_len=MAX_LEN, split="train", device=None):
+    def __init__(self, indices, labels, ecg_signals, augment=True, max_len=MAX_LEN, split="train", device=None,
+                 with_lengths=False):
         device = torch.device(device or Config.device)
         self.labels_host = torch.as_tensor(np.asarray(labels)[np.asarray(indices)], dtype=torch.long)
         self.ecg_signals_padded = pad_sequences([ecg_signals[i] for i in indices], maxlen=max_len, dtype="float32",
                                                 padding="post", truncating="post")
+        self.lengths_host = self.lengths = None
+        if with_lengths:
+            self.lengths_host = torch.as_tensor([min(len(ecg_signals[i]), int(max_len)) for i in indices], dtype=torch.int32)
+            if self.lengths_host.numel() and int(self.lengths_host.min()) < 1:
+                raise ValueError("SignalOnlyDataset: an empty record has no length to attend over")
+            self.lengths = self.lengths_host.to(device)
         self.max_len, self.split = max_len, split
         self.augment = bool(augment) and split == "train"
         self.signals = preprocess_signal(torch.from_numpy(self.ecg_signals_padded).to(device), orig_fs=300, target_fs=300)
@@ -250,22 +288,34 @@ class SignalOnlyDataset:
 class DeviceSignalLoader(T.ResidentLoader):
     """Batches of a :class:`SignalOnlyDataset`: ``(signals [B, L] fp32 on the device, labels [B] on the device)``, one
     ``gather_augment`` launch per batch (augmentation as the dataset says).  ``shuffle``: a ``torch.randperm`` of the seeded
-    ``generator`` per epoch, kept in ``last_order``."""
+    ``generator`` per epoch, kept in ``last_order``.
+
+    A dataset with ``lengths`` yields ``((signals, lengths [B] int32), labels)``, the shape ``train_physionet2``'s loader
+    uses.  The augmentation is unchanged: its circular roll of at most 10 samples turns the whole padded row, so it moves at
+    most 10 samples across the record's end (up to 10 samples of the record into the padding's far end or the start, and as
+    many zeros of the padding into the live part); the length is not adjusted for it."""
 
     def __init__(self, dataset, batch_size=8, shuffle=False, generator=None, drop_last=False):
         super().__init__(dataset, batch_size, shuffle, generator, drop_last)
 
     def batch(self, idx):
         ds = self.dataset
-        return gather_augment(ds.signals, idx, augment=ds.augment, check_index=False, **AUG_DEFAULTS), ds.labels[idx]
+        signals = gather_augment(ds.signals, idx, augment=ds.augment, check_index=False, **AUG_DEFAULTS)
+        if getattr(ds, "lengths", None) is None:
+            return signals, ds.labels[idx]
+        return (signals, ds.lengths[idx]), ds.labels[idx]
 
 
-def get_signalonly_dataloaders(config=Config, batch_size=8, label_map=LABEL_MAP, augment=True, split=SPLIT, max_len=MAX_LEN):
-    """train / val / test :class:`DeviceSignalLoader` (train_physionet.py:89-132; batch 8, only the train split shuffled)."""
+def get_signalonly_dataloaders(config=Config, batch_size=8, label_map=LABEL_MAP, augment=True, split=SPLIT, max_len=MAX_LEN,
+                               use_lengths=False):
+    """train / val / test :class:`DeviceSignalLoader` (train_physionet.py:89-132; batch 8, only the train split shuffled).
+    ``use_lengths``: the datasets carry every record's ``min(len(record), max_len)`` and the loaders yield
+    ``((signals, lengths), labels)``."""
     signals, labels = load_records(config, label_map)
     train_idx, val_idx, test_idx = split_indices(labels, config.seed, split)
     device = torch.device(config.device)
-    mk = lambda idx, name: SignalOnlyDataset(idx, labels, signals, augment=augment, max_len=max_len, split=name, device=device)
+    mk = lambda idx, name: SignalOnlyDataset(idx, labels, signals, augment=augment, max_len=max_len, split=name, device=device,
+                                             with_lengths=use_lengths)
     gen = torch.Generator().manual_seed(config.seed)
     return (DeviceSignalLoader(mk(train_idx, "train"), batch_size, shuffle=True, generator=gen),
             DeviceSignalLoader(mk(val_idx, "val"), batch_size), DeviceSignalLoader(mk(test_idx, "test"), batch_size))
@@ -278,7 +328,11 @@ def evaluate(model, loader, num_classes=2, predictor=None):
     """Softmax probabilities of the split -> accuracy / F1 / AUC (binary: class-1 probability thresholded at 0.5,
     train_physionet.py:359-379; more classes: argmax, macro F1, one-vs-rest AUC, train_physionet_multi.py:312-330)."""
     model.eval()
-    y_true, y_prob, _, _ = T.predict(model if predictor is None else predictor, loader, lambda x: x.unsqueeze(1))
+    forward = model if predictor is None else predictor
+    if getattr(loader.dataset, "lengths", None) is not None:   # the loader yields (signals, lengths) as the inputs
+        y_true, y_prob, _, _ = T.predict(lambda inputs: forward(inputs[0].unsqueeze(1), inputs[1]), loader)
+    else:
+        y_true, y_prob, _, _ = T.predict(forward, loader, lambda x: x.unsqueeze(1))
     if num_classes == 2:
         return T.binary_metrics(y_true, y_prob[:, 1], (y_prob[:, 1] >= 0.5).astype(int))
     from sklearn.metrics import f1_score
@@ -289,20 +343,32 @@ def evaluate(model, loader, num_classes=2, predictor=None):
 
 
 def main(config=Config, num_epochs=30, batch_size=8, quiet=False, use_predictor=False, num_classes=2, label_map=LABEL_MAP,
-         augment=True, split=SPLIT, model="resnet", max_len=MAX_LEN):
+         augment=True, split=SPLIT, model="resnet", max_len=MAX_LEN, time_attention=False, use_lengths=False):
     """``model``: ``"resnet"`` (the reference's choice) or ``"transformer"`` (its commented alternative, :276); ``max_len``:
     the length every record is padded or cut to.
     ``use_predictor``: run the validation and test passes through an ``ecgmm.inference.Predictor`` (BatchNorm-folded
     inference plan), refreshed after every training epoch and after every checkpoint load.  Default off.
+    ``time_attention`` or ``config.physionet_time_attention`` (off by default; ``model="transformer"`` only): the encoder
+    attends along each record's positions instead of across the batch (:class:`ECGTransformer1D`).
+    ``use_lengths`` or ``config.physionet_use_lengths`` (off by default; needs ``time_attention``): the loaders carry
+    ``min(len(record), max_len)`` per record and the model gets it, so the zero padding of a short record is neither
+    attended to nor averaged (:class:`DeviceSignalLoader` on what the augmentation's roll does at the record's end).
     -> (history, {"best": metrics, "last": metrics}, checkpoint directory)."""
+    time_attention = bool(time_attention or getattr(config, "physionet_time_attention", False))
+    use_lengths = bool(use_lengths or getattr(config, "physionet_use_lengths", False))
+    if (time_attention or use_lengths) and model == "resnet":
+        raise ValueError("time_attention / use_lengths need model='transformer' (the ResNet1D_SE has neither)")
+    if use_lengths and not time_attention:
+        raise ValueError("use_lengths=True needs time_attention=True (attention across the batch has no per-record length)")
     T.seed_all(config.seed, numpy=True)
     device = torch.device(config.device)
     if not quiet:
         print(f"Using device: {device}")
-    train_loader, val_loader, test_loader = get_signalonly_dataloaders(config, batch_size, label_map, augment, split, max_len)
+    train_loader, val_loader, test_loader = get_signalonly_dataloaders(config, batch_size, label_map, augment, split, max_len,
+                                                                       **({"use_lengths": True} if use_lengths else {}))
     if use_predictor and model != "resnet":
         raise ValueError("use_predictor=True needs model='resnet' (the inference plan is the ResNet1D_SE's)")
-    model = build_model(model, num_classes, config, max_len).to(device)
+    model = build_model(model, num_classes, config, max_len, **({"time_attention": True} if time_attention else {})).to(device)
     criterion = FocalLoss(alpha=1.0, gamma=2.0)
     optimizer = FusedAdam(model.parameters(), lr=0.001)
     scheduler = torch.optim.lr_scheduler.OneCycleLR(optimizer, max_lr=0.001, steps_per_epoch=len(train_loader),
@@ -315,7 +381,11 @@ def main(config=Config, num_epochs=30, batch_size=8, quiet=False, use_predictor=
 
     def step(batch, forward=model):
         signals, labels = batch
-        out = forward(signals.unsqueeze(1))   # [B, L] -> [B, 1, L]
+        if use_lengths:
+            signals, lengths = signals
+            out = forward(signals.unsqueeze(1), lengths)
+        else:
+            out = forward(signals.unsqueeze(1))   # [B, L] -> [B, 1, L]
         return criterion(out, labels), out, labels
 
     def train_pass():

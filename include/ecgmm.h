@@ -881,7 +881,8 @@ int ecgmm_shap_deep(const float* x, const float* bg, const float* W1, const floa
  * the backward regenerates it from the same (seed, offset), nothing is stored.  ecgmm_mha_keep_mask writes the decisions
  * as bytes [N][heads][S][S] (tests and small shapes).  The caller advances `offset` by one per forward call.
  * Needs S, N, heads >= 1, head_dim 16 or 32, batch_first 0 or 1, 0 <= p_drop < 1, S <= 32768 when p_drop > 0; anything
- * else is ECGMM_ERR_SHAPE and writes nothing.  No attention or key-padding mask. */
+ * else is ECGMM_ERR_SHAPE and writes nothing.  No attention mask and no causal mask; a key-padding mask only in the form
+ * of one length per attention-batch element (the _varlen entry points below). */
 typedef struct {
   int S, N, heads, head_dim, batch_first;
   float p_drop;
@@ -896,6 +897,31 @@ int ecgmm_mha_backward(const ecgmm_mha_desc* d, const float* qkv, const float* o
                        float* dqkv, void* ws, size_t ws_bytes, uint64_t seed, uint64_t offset, void* stream);
 /* train_physionet.py:219 (dropout = 0.1 of the layer, applied to the attention weights) */
 int ecgmm_mha_keep_mask(const ecgmm_mha_desc* d, uint8_t* mask, uint64_t seed, uint64_t offset, void* stream);
+/* Variable-length form: qkv, out, dout and dqkv stay padded ([rows][..] of the padded S) and lengths [N] (device int32) says
+ * how many positions of attention-batch element n are live, s < lengths[n], the same in every head.  It equals torch's
+ * key_padding_mask[n][s] = s >= lengths[n] on the live rows, plus exact zeros in the padding:
+ *   live query     softmax over the live keys only; the arithmetic and the order of the 16-key tiles are those of
+ *                  ecgmm_mha_forward on that element alone with S = lengths[n] (at S > 8 and lengths[n] > 8: the same bits)
+ *   padded query   its out row is exactly 0, its lse 0, its dQ row exactly 0
+ *   padded key     its dK and dV rows are exactly 0
+ * lengths are clamped to [0, S] on the device (no host sync); lengths[n] = 0 makes everything of n zero.  Every element of
+ * out, lse and dqkv is WRITTEN, as without lengths.  Padded rows of qkv and dout are never read into arithmetic that reaches
+ * an output (empty tile slots read position lengths[n] - 1 instead): THEY MAY HOLD ANYTHING, NaN included.
+ * Work follows the lengths: the key loop of the forward and dQ kernels and the query loop of the dK / dV kernel run
+ * ceil(lengths[n] / 16) tiles, and a unit whose own 16 rows are all padding only stores its zeros.
+ * Dropout: the decision stays the function of (seed, offset, n, head, query, key) above with ceil(S / 4) of the PADDED S as the
+ * stride, so ecgmm_mha_keep_mask of the same descriptor describes the launch (its entries at padded positions are unused).
+ * The packed form (S <= 8) takes lengths too.  lengths = null is exactly ecgmm_mha_forward / ecgmm_mha_backward, bit for bit
+ * (the same kernel instantiations); so is lengths all equal to S.  The backward takes the lengths the forward ran with and
+ * the workspace of ecgmm_mha_bwd_workspace.  No atomics: two identical calls give identical bits. */
+/* multimodal_paper_modal_balance.py:133-140, 145 (batch_first = True: attention over the positions) on records of unequal
+ * length */
+int ecgmm_mha_forward_varlen(const ecgmm_mha_desc* d, const float* qkv, const int32_t* lengths, float* out, float* lse,
+                             uint64_t seed, uint64_t offset, void* stream);
+/* multimodal_paper_modal_balance.py:133-140, 145 (its loss.backward()) */
+int ecgmm_mha_backward_varlen(const ecgmm_mha_desc* d, const float* qkv, const int32_t* lengths, const float* out,
+                              const float* lse, const float* dout, float* dqkv, void* ws, size_t ws_bytes, uint64_t seed,
+                              uint64_t offset, void* stream);
 
 /* The front of ECGTransformer1D (train_physionet.py:216-217, 233-235) as one launch: Conv1d(Cin, Dm, 3, padding = 1) + bias
  * written straight as [B][L][Dm] with pos[l][c] added.  x [B][Cin][L], w [Dm][Cin][3], bias [Dm], pos [>= L][Dm], fp32.

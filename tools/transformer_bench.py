@@ -17,6 +17,12 @@ FLOPs: forward 4 S^2 d per (n, head); backward 10 S^2 d (the two passes recomput
 dQ), over the exact-f32 MFMA peak of DESIGN section 4.1 (157.3 TFLOP/s).
 
     python tools/transformer_bench.py [--rounds 7] [--reps 10] [--out profiles/transformer_bench.json]
+
+--lengths: the same three measurements of OURS at bf_3000 and bf_750 with one length per attention-batch element, drawn
+uniformly from [S / 4, S] under a fixed seed, as drawn ("unsorted") and in descending order ("sorted"), beside the all-full run
+without lengths of the same process ("full").  Reported with them: sum(len^2) / (N S^2), the share of the score tiles that
+hold a live (query, key) pair, which the attention time should follow; the layer also keeps its projections, LayerNorms and
+feed-forward over all rows.  Default output profiles/transformer_bench_lengths.json.
 """
 import argparse
 import json
@@ -28,6 +34,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--out", default=None)
+ap.add_argument("--lengths", action="store_true", help="time the kernels with per-element lengths (see the module docstring)")
 args = ap.parse_args()
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -53,10 +60,49 @@ def timed(fn, reps):
     return e0.elapsed_time(e1) / reps
 
 
+def lengths_variants():
+    """{name: (fn, flops or None)} and {shape: description of its lengths} for --lengths"""
+    variants, drawn = {}, {}
+    gen = torch.Generator().manual_seed(20170)
+    for name in ("bf_3000", "bf_750"):
+        S, N, E, heads, ff, bf = SHAPES[name]
+        d = E // heads
+        ours = HN.TransformerEncoderLayer(E, heads, ff, dropout=0.0, batch_first=bf).to(dev).train()
+        x = torch.randn(N, S, E, device=dev)
+        gy = torch.randn(N, S, E, device=dev)
+        qkv = torch.randn(S * N, 3 * E, device=dev)
+        ga = torch.randn(S * N, E, device=dev)
+        unsorted = torch.randint(S // 4, S + 1, (N,), generator=gen, dtype=torch.int32)
+        share = float((unsorted.double() ** 2).sum() / (N * float(S) ** 2))
+        drawn[name] = {"lengths": unsorted.tolist(), "work_share_sum_len2_over_N_S2": share}
+        full_flops = 4.0 * S * S * d * N * heads
+        for tag, ln in (("full", None), ("unsorted", unsorted.to(dev)),
+                        ("sorted", torch.sort(unsorted, descending=True).values.to(dev))):
+            flops = full_flops * (1.0 if ln is None else share)
+
+            def attn_fwd(qkv=qkv, S=S, N=N, heads=heads, ln=ln):
+                with torch.no_grad():
+                    HF.multi_head_attention(qkv, S, N, heads, True, lengths=ln)
+
+            def attn_fwd_bwd(qkv=qkv, ga=ga, S=S, N=N, heads=heads, ln=ln):
+                t = qkv.detach().requires_grad_()
+                HF.multi_head_attention(t, S, N, heads, True, lengths=ln).backward(ga)
+
+            def layer(ours=ours, x=x, gy=gy, ln=ln):
+                HF.release_grads(ours)
+                t = x.detach().requires_grad_()
+                (ours(t) if ln is None else ours(t, lengths=ln)).backward(gy)
+
+            variants[f"{name}/{tag}/attention_fwd"] = (attn_fwd, flops)
+            variants[f"{name}/{tag}/attention_fwd_bwd"] = (attn_fwd_bwd, 3.5 * flops)
+            variants[f"{name}/{tag}/layer_fwd_bwd"] = (layer, None)
+    return variants, drawn
+
+
 def main():
     torch.manual_seed(0)
-    variants = {}
-    for name, (S, N, E, heads, ff, bf) in SHAPES.items():
+    variants, drawn = lengths_variants() if args.lengths else ({}, None)
+    for name, (S, N, E, heads, ff, bf) in ({} if args.lengths else SHAPES).items():
         d = E // heads
         ours = HN.TransformerEncoderLayer(E, heads, ff, dropout=0.0, batch_first=bf).to(dev).train()
         ref = nn.TransformerEncoderLayer(E, heads, ff, dropout=0.0, batch_first=bf).to(dev).train()
@@ -105,6 +151,10 @@ def main():
             rounds[k].append(timed(fn, args.reps))
     res = {"shapes": {k: dict(zip(("S", "N", "E", "heads", "dim_feedforward", "batch_first"), v)) for k, v in SHAPES.items()},
            "rounds": args.rounds, "reps": args.reps, "peak_f32_mfma_tflops": PEAK_F32 / 1e12, "variants": {}}
+    if drawn is not None:
+        res["lengths"] = drawn
+        for name, dsc in drawn.items():
+            print(f"{name}: sum(len^2) / (N S^2) = {dsc['work_share_sum_len2_over_N_S2']:.4f}", flush=True)
     for k, (fn, flops) in variants.items():
         ms = statistics.median(rounds[k])
         v = res["variants"][k] = {"ms_median": ms, "ms_min": min(rounds[k]), "ms_max": max(rounds[k])}
@@ -114,7 +164,14 @@ def main():
             v["fraction_of_f32_mfma_peak"] = flops / (ms * 1e-3) / PEAK_F32
             line += f"  {v['gflop']:8.2f} GFLOP = {100 * v['fraction_of_f32_mfma_peak']:.2f} % of the f32 MFMA peak"
         print(line, flush=True)
-    out = args.out or os.path.join(ROOT, "profiles", "transformer_bench.json")
+    if drawn is not None:   # each lengths run over the full run of the same shape
+        for k, v in res["variants"].items():
+            name, tag, what = k.split("/")
+            if tag != "full":
+                v["time_over_full"] = v["ms_median"] / res["variants"][f"{name}/full/{what}"]["ms_median"]
+                print(f"{k:38s} {v['time_over_full']:.3f} of the full run's time", flush=True)
+    out = args.out or os.path.join(ROOT, "profiles", "transformer_bench_lengths.json" if args.lengths else
+                                   "transformer_bench.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
         json.dump(res, f, indent=1)
