@@ -539,6 +539,170 @@ __global__ __launch_bounds__(256) void mha_keep_mask_kernel(MhaGeo g, unsigned c
     if (4 * jb + w < g.S) dst[4 * jb + w] = mha_keep_word(g, r[w]) ? 1 : 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// attention maps and the attention-rollout step (ecgmm_mha_weights / ecgmm_mha_rollout_step)
+// ------------------------------------------------------------------------------------------------
+// Both rebuild p[n,h,i,j] = expf(scale q_i . k_j - lse[n,h,i]) from qkv and the lse the forward stored, the expression of
+// the backward kernels, BEFORE dropout (p_drop is ignored: torch's maps in training mode are the dropped ones; in eval mode
+// and at dropout 0 there is no difference).  One wave owns one 16-row tile of ONE attention-batch element n and loops over
+// the heads inside, so the head average needs no second pass.  Never packed: at S <= 8 a wave holds the one partial tile
+// of one n (these are not training kernels; the slots of the other 16 - S rows are empty).  With lengths, live queries
+// hold the softmax over the live keys and everything in the padding is an exact 0 -- torch's padded QUERY rows still attend
+// to the live keys; here they are zero, as the padded rows of ecgmm_mha_forward_varlen are.
+template <bool VL>
+__device__ __forceinline__ Unit map_unit(const MhaGeo& g, long long unit, const int* __restrict__ lens) {
+  Unit o;
+  o.n = (int)(unit / g.tiles);
+  o.tile = (int)(unit - (long long)o.n * g.tiles);
+  o.h = 0;
+  o.u = o.n * g.heads;   // the pair of head 0: head h is at si + h * S
+  o.len = VL ? __builtin_amdgcn_readfirstlane(mha_len(g, lens, o.n)) : g.S;
+  return o;
+}
+
+// four consecutive keys j0 .. j0 + 3 of one row of a map: one 16-byte store where S % 4 == 0 (then all four lie on one
+// side of S), else element by element
+__device__ __forceinline__ void map_store4(float* __restrict__ row, int j0, int S, bool vec, float a, float b, float c,
+                                           float d) {
+  if (vec) {
+    if (j0 < S) *reinterpret_cast<float4*>(row + j0) = make_float4(a, b, c, d);
+  } else {
+    if (j0 < S) row[j0] = a;
+    if (j0 + 1 < S) row[j0 + 1] = b;
+    if (j0 + 2 < S) row[j0 + 2] = c;
+    if (j0 + 3 < S) row[j0 + 3] = d;
+  }
+}
+
+// the wave owns 16 queries of n: w [N][heads][S][S] (PH) or the head average [N][S][S], sum over h = 0, 1, .. then one
+// multiplication by inv_heads.  The transposed score layout of the forward: a lane holds four consecutive keys of one query.
+template <int HD, bool VL, bool PH>
+__global__ __launch_bounds__(256) void mha_weights_kernel(MhaGeo g, const float* __restrict__ qkv,
+                                                          const float* __restrict__ lse, float* __restrict__ w,
+                                                          long long units, const int* __restrict__ lens, float inv_heads,
+                                                          int vec) {
+  constexpr int CW = HD / 4, HB = 4;
+  const long long unit = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (unit >= units) return;   // wave-uniform; the kernel has no barrier
+  const int lane = threadIdx.x & 63, i16 = lane & 15, g4 = lane >> 4;
+  const Unit u = map_unit<VL>(g, unit, lens);
+  const int E3 = 3 * g.E;
+  const Slot q = mha_slot<false, VL>(g, u, u.tile, i16, lens);
+  const long long SS = (long long)g.S * g.S;
+  // the query's row of head 0 (PH) or of the average
+  float* dst = w + (long long)u.n * (PH ? g.heads : 1) * SS + (long long)(q.real ? q.s : 0) * g.S;
+  const int nmaps = PH ? g.heads : 1;
+  if (mha_idle<false, VL>(u, q)) {   // wave-uniform: every query of the tile is padding
+    if (!q.real) return;
+    for (int h = 0; h < nmaps; ++h)
+      for (int kt = 0; kt < g.tiles; ++kt) map_store4(dst + h * SS, kt * 16 + g4 * 4, g.S, vec, 0.f, 0.f, 0.f, 0.f);
+    return;
+  }
+  const int ktiles = mha_loop_tiles<false, VL>(g, u);
+  for (int kt = 0; kt < ktiles; ++kt) {
+    const Slot ka = mha_slot<false, VL>(g, u, kt, i16, lens);
+    const int j0 = kt * 16 + g4 * 4;
+    float sum[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int h0 = 0; h0 < g.heads; h0 += HB) {
+      // the loads of HB heads are issued together (N * ceil(S / 16) waves: little else hides their latency); a head past
+      // the last one is clamped onto it, adds exact zeros to the sum and stores nothing
+      float qv[HB][CW], kv[HB][CW], lq[HB];
+#pragma unroll
+      for (int b = 0; b < HB; ++b) {
+        const int h = min(h0 + b, g.heads - 1);
+        load_cols<CW>(qkv + q.row * E3 + h * HD + g4 * CW, qv[b]);
+        load_cols<CW>(qkv + ka.row * E3 + g.E + h * HD + g4 * CW, kv[b]);
+        lq[b] = lse[q.si + (long long)h * g.S];
+      }
+#pragma unroll
+      for (int b = 0; b < HB; ++b) {
+        const int h = h0 + b;
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < CW; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kv[b][s], qv[b][s], acc, 0, 0, 0);
+        float p[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const bool valid = q.ok && j0 + r < u.len && h < g.heads;
+          p[r] = valid ? expf(acc[r] * g.scale - lq[b]) : 0.f;
+          sum[r] += p[r];
+        }
+        if (PH && q.real && h < g.heads) map_store4(dst + h * SS, j0, g.S, vec, p[0], p[1], p[2], p[3]);
+      }
+    }
+    if (!PH && q.real)
+      map_store4(dst, j0, g.S, vec, sum[0] * inv_heads, sum[1] * inv_heads, sum[2] * inv_heads, sum[3] * inv_heads);
+  }
+  if (VL && q.real) {   // the key tiles wholly behind the length
+    for (int h = 0; h < nmaps; ++h)
+      for (int kt = ktiles; kt < g.tiles; ++kt) map_store4(dst + h * SS, kt * 16 + g4 * 4, g.S, vec, 0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+// the wave owns 16 keys of n:  y[n][j] = a v[n][j] + (1 - a) inv_heads sum_h sum_i v[n][i] p[n,h,i,j], v and y [N][S].
+// The score layout of mha_bwd_kv_kernel: acc[r] = S[query 4 g + r][key i16].  A lane's partial sum runs over the heads,
+// the query tiles inside and its four queries inside those, by fmaf; then one all-reduce over the four lane rows.  With
+// lengths a padded v is never read and a padded y is exact 0; the order of the live terms is that of the element alone.
+template <int HD, bool VL>
+__global__ __launch_bounds__(256) void mha_rollout_step_kernel(MhaGeo g, const float* __restrict__ qkv,
+                                                               const float* __restrict__ lse, const float* __restrict__ v,
+                                                               float* __restrict__ y, long long units,
+                                                               const int* __restrict__ lens, float a, float inv_heads) {
+  constexpr int CW = HD / 4, QB = 4;
+  const long long unit = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (unit >= units) return;
+  const int lane = threadIdx.x & 63, i16 = lane & 15, g4 = lane >> 4;
+  const Unit u = map_unit<VL>(g, unit, lens);
+  const int E3 = 3 * g.E;
+  const Slot k = mha_slot<false, VL>(g, u, u.tile, i16, lens);
+  const float* vn = v + (long long)u.n * g.S;
+  float* yn = y + (long long)u.n * g.S;
+  if (mha_idle<false, VL>(u, k)) {   // wave-uniform: every key of the tile is padding
+    if (k.real && g4 == 0) yn[k.s] = 0.f;
+    return;
+  }
+  float part = 0.f;
+  const int qtiles = mha_loop_tiles<false, VL>(g, u);
+  const int last = u.len - 1;   // an empty query slot is clamped onto the last live position (u.len = S without lengths)
+  for (int h = 0; h < g.heads; ++h) {   // the head outside: its 16 keys are loaded once
+    float kv[CW];
+    load_cols<CW>(qkv + k.row * E3 + g.E + h * HD + g4 * CW, kv);
+    const float* lh = lse + ((long long)u.u + h) * g.S;
+    const float* qh = qkv + (long long)u.n * g.rn * E3 + h * HD + g4 * CW;
+    for (int q0 = 0; q0 < qtiles; q0 += QB) {
+      // the loads of QB query tiles are issued together: with N * ceil(S / 16) waves there is little else to hide their
+      // latency behind.  A tile past the last one is clamped like an empty slot and adds exact zeros.
+      float qv[QB][CW], lr[QB][4], vr[QB][4];
+#pragma unroll
+      for (int b = 0; b < QB; ++b) {
+        const int t16 = (q0 + b) * 16;
+        load_cols<CW>(qh + (long long)min(t16 + i16, last) * g.rs * E3, qv[b]);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int sc = min(t16 + g4 * 4 + r, last);
+          lr[b][r] = lh[sc];
+          vr[b][r] = vn[sc];
+        }
+      }
+#pragma unroll
+      for (int b = 0; b < QB; ++b) {
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < CW; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(qv[b][s], kv[s], acc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const bool ok = (q0 + b) * 16 + g4 * 4 + r <= last && k.ok;
+          const float p = ok ? expf(acc[r] * g.scale - lr[b][r]) : 0.f;
+          part = fmaf(ok ? vr[b][r] : 0.f, p, part);
+        }
+      }
+    }
+  }
+  part = rows_sum(part);
+  if (!k.real || g4 != 0) return;
+  yn[k.s] = k.ok ? fmaf(a, vn[k.s], (1.f - a) * (part * inv_heads)) : 0.f;
+}
+
 // 0 when the descriptor is accepted, else the message is set
 static int mha_geo(const ecgmm_mha_desc* d, const char* what, MhaGeo* out) {
   if (!d) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: null descriptor", what);
@@ -785,6 +949,48 @@ extern "C" int ecgmm_mha_keep_mask(const ecgmm_mha_desc* d, uint8_t* mask, uint6
   g.seed = seed; g.offset = offset;
   hipLaunchKernelGGL(mha_keep_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, mask);
   ECG_CHECK_LAUNCH("mha_keep_mask");
+  return 0;
+}
+
+extern "C" int ecgmm_mha_weights(const ecgmm_mha_desc* d, const float* qkv, const float* lse, const int32_t* lengths,
+                                 float* weights, int per_head, void* stream) {
+  MhaGeo g;
+  ECG_TRY(mha_geo(d, "mha_weights", &g));
+  if (!qkv || !lse || !weights) ECG_FAIL(ECGMM_ERR_SHAPE, "mha_weights: null operand");
+  if (!aligned16(qkv)) ECG_FAIL(ECGMM_ERR_SHAPE, "mha_weights: qkv must be 16-byte aligned");
+  if (per_head != 0 && per_head != 1) ECG_FAIL(ECGMM_ERR_SHAPE, "mha_weights: per_head must be 0 or 1, got %d", per_head);
+  const long long units = (long long)g.N * g.tiles;
+  const dim3 grid((unsigned)((units + 3) / 4));
+  const bool vl = lengths != nullptr;
+  const int vec = g.S % 4 == 0 && aligned16(weights);
+  auto* fn = d->head_dim == 16
+                 ? (vl ? (per_head ? mha_weights_kernel<16, true, true> : mha_weights_kernel<16, true, false>)
+                       : (per_head ? mha_weights_kernel<16, false, true> : mha_weights_kernel<16, false, false>))
+                 : (vl ? (per_head ? mha_weights_kernel<32, true, true> : mha_weights_kernel<32, true, false>)
+                       : (per_head ? mha_weights_kernel<32, false, true> : mha_weights_kernel<32, false, false>));
+  hipLaunchKernelGGL(fn, grid, dim3(256), 0, (hipStream_t)stream, g, qkv, lse, weights, units, (const int*)lengths,
+                     1.f / (float)g.heads, vec);
+  ECG_CHECK_LAUNCH("mha_weights");
+  return 0;
+}
+
+extern "C" int ecgmm_mha_rollout_step(const ecgmm_mha_desc* d, const float* qkv, const float* lse, const int32_t* lengths,
+                                      const float* v_in, float* v_out, float residual, void* stream) {
+  MhaGeo g;
+  ECG_TRY(mha_geo(d, "mha_rollout_step", &g));
+  if (!qkv || !lse || !v_in || !v_out) ECG_FAIL(ECGMM_ERR_SHAPE, "mha_rollout_step: null operand");
+  if (!aligned16(qkv)) ECG_FAIL(ECGMM_ERR_SHAPE, "mha_rollout_step: qkv must be 16-byte aligned");
+  if (!(residual >= 0.f && residual < 1.f))
+    ECG_FAIL(ECGMM_ERR_SHAPE, "mha_rollout_step: need 0 <= residual < 1, got %g", (double)residual);
+  if (v_in == v_out) ECG_FAIL(ECGMM_ERR_SHAPE, "mha_rollout_step: v_out must not be v_in (every unit reads all of v_in)");
+  const long long units = (long long)g.N * g.tiles;
+  const dim3 grid((unsigned)((units + 3) / 4));
+  const bool vl = lengths != nullptr;
+  auto* fn = d->head_dim == 16 ? (vl ? mha_rollout_step_kernel<16, true> : mha_rollout_step_kernel<16, false>)
+                               : (vl ? mha_rollout_step_kernel<32, true> : mha_rollout_step_kernel<32, false>);
+  hipLaunchKernelGGL(fn, grid, dim3(256), 0, (hipStream_t)stream, g, qkv, lse, v_in, v_out, units, (const int*)lengths,
+                     residual, 1.f / (float)g.heads);
+  ECG_CHECK_LAUNCH("mha_rollout_step");
   return 0;
 }
 

@@ -12,7 +12,12 @@ runs behind an eval-mode forward (csrc/plan_resnet18.hip, plan_resnet1d.hip, con
                          d logit / d A_c, bilinearly upsampled to the input size (align_corners=False).  After a global
                          average pool that gradient is constant over space, so only the head's backward runs, not the
                          convolutions' (csrc/gradcam.hip);
-  * ``encoder_grad_cam`` the same for a stand-alone ``ResNet18`` / ``ResNet1D_SE`` classifier.
+  * ``encoder_grad_cam`` the same for a stand-alone ``ResNet18`` / ``ResNet1D_SE`` classifier;
+  * ``attention_maps``   the attention weights of every encoder layer of an ``ECGTransformer1D``, rebuilt from what its
+                         forward stored (csrc/attention.hip: ``ecgmm_mha_weights``);
+  * ``attention_rollout`` the relevance of each input sample to the mean-pooled representation of an ``ECGTransformer1D``
+                         with ``time_attention`` (Abnar & Zuidema 2020), one row vector per record and no S x S matrix
+                         (``ecgmm_mha_rollout_step``).
 Everything numeric runs in libecgmm_hip.so; there is no CPU path.
 """
 import os
@@ -115,6 +120,56 @@ def encoder_grad_cam(encoder, x, target=None):
     with _Frozen(encoder), _recorded((encoder,)), torch.no_grad():
         logits = encoder(x)
         return E.plan_grad_cam(encoder._spec, _seed(logits, target))
+
+
+def _attention_records(model, x, lengths):
+    """one eval-mode forward of an ``ECGTransformer1D`` with a sink -> the attention record of every layer, first to last"""
+    _require_cuda(x, "attention maps input")
+    if not hasattr(model, "transformer_encoder"):
+        raise ValueError("attention maps need an ECGTransformer1D (a model with a transformer_encoder)")
+    sink = []
+    with _Frozen(model), torch.no_grad():
+        model(x, lengths, attention_sink=sink) if lengths is not None else model(x, attention_sink=sink)
+    return sink
+
+
+def attention_maps(model, x, lengths=None, average=True):
+    """The attention weights of every encoder layer of an ``ECGTransformer1D`` on ``x`` [B, input_dim, L], in eval mode
+    (no dropout): a list with one ``[N, S, S]`` tensor per layer (``average``: the mean over the heads, torch's
+    ``average_attn_weights``) or ``[N, heads, S, S]``, rows = queries, columns = keys.  With ``time_attention`` N = B and
+    S = L: a map over the record's positions, with ``lengths`` exact zeros in the padded rows and columns; without it the
+    model attends across the batch, N = L and S = B.  Each layer's map takes ``4 * N * S * S`` bytes (times ``heads`` per
+    head) -- 36 MB per record at L = 3000: for long records use :func:`attention_rollout`, which never forms it.
+    Detached, no gradient."""
+    from .hip import functional as HF
+    return [HF.attention_weights(**rec, average=average) for rec in _attention_records(model, x, lengths)]
+
+
+def attention_rollout(model, x, lengths=None, residual=0.5):
+    """Attention rollout (Abnar & Zuidema 2020) of the mean-pooled representation of an ``ECGTransformer1D`` with
+    ``time_attention`` -> ``[B, L]`` fp32: the relevance of each input sample, >= 0, summing to 1 per record, exactly 0 behind
+    ``lengths``.  Each layer is taken as ``residual * I + (1 - residual) * A`` with ``A`` its head-averaged attention map
+    (``residual`` in [0, 1); 0.5 is the paper's equal weighting of the skip connection); the model ends in the mean over
+    the live positions, so the row vector ``1 / len`` is carried from the last layer to the first, one
+    ``ecgmm_mha_rollout_step`` per layer, and no S x S matrix is formed.  The embedding (a 3-tap convolution plus the
+    positional embedding) keeps positions, so the vector lies over the raw signal.  One eval-mode forward.  Detached."""
+    from .hip import functional as HF
+    residual = float(residual)
+    if not 0.0 <= residual < 1.0:
+        raise ValueError(f"attention_rollout: residual={residual} must lie in [0, 1)")
+    if not getattr(model, "time_attention", False):
+        raise ValueError("attention_rollout needs time_attention=True (attention across the batch has no per-record map)")
+    records = _attention_records(model, x, lengths)
+    B, Ln = x.shape[0], x.shape[2]
+    if lengths is None:
+        v = torch.full((B, Ln), 1.0 / Ln, device=x.device, dtype=torch.float32)
+    else:
+        n = records[0]["lengths"].to(torch.float32)[:, None]                  # validated by the forward: 1 <= n <= L
+        v = torch.where(torch.arange(Ln, device=x.device)[None, :] < n, 1.0 / n, torch.zeros_like(n))
+    for rec in reversed(records):
+        v = HF.attention_rollout_step(rec["qkv"], rec["lse"], v, rec["S"], rec["N"], rec["heads"], rec["batch_first"],
+                                      rec["lengths"], residual)
+    return v
 
 
 def overlay(image, cam, alpha=0.5):

@@ -861,11 +861,13 @@ class MultiHeadAttentionFn(torch.autograd.Function):
     """out [rows, E] = concat_heads(softmax(Q K^T / sqrt(d)) V) of the packed projection qkv [rows, 3E] (csrc/attention.hip).
     Saves qkv, out and one log-sum-exp per score row; the backward recomputes the probabilities and, with dropout, the keep
     decisions from the call's (seed, offset).  ``cfg`` may carry a sixth entry, the device ``int32 [N]`` lengths (or
-    ``None``): the ``_varlen`` entry points, else the fixed ones; the lengths are kept for the backward."""
+    ``None``): the ``_varlen`` entry points, else the fixed ones; the lengths are kept for the backward.  A true seventh
+    entry also returns the log-sum-exp ``[N * heads * S]``, marked non-differentiable (the attention maps are rebuilt from
+    it); the launches are the same."""
 
     @staticmethod
     def forward(ctx, qkv, cfg):
-        S, N, heads, batch_first, p, lengths = (tuple(cfg) + (None,))[:6]
+        S, N, heads, batch_first, p, lengths, want_lse = (tuple(cfg) + (None, False))[:7]
         _require_cuda(qkv, "multi_head_attention")
         if qkv.dim() != 2 or qkv.shape[0] != S * N or qkv.shape[1] % (3 * heads):
             raise RuntimeError(f"multi_head_attention: qkv must be [S * N, 3 * E] with E a multiple of heads, got "
@@ -886,10 +888,13 @@ class MultiHeadAttentionFn(torch.autograd.Function):
                                                      stream()), "mha_forward_varlen")
         ctx.desc, ctx.rng, ctx.lengths = desc, (seed, off), lengths
         ctx.save_for_backward(qkv, out, lse)
+        if want_lse:
+            ctx.mark_non_differentiable(lse)
+            return out, lse
         return out
 
     @staticmethod
-    def backward(ctx, dout):
+    def backward(ctx, dout, _dlse=None):
         qkv, out, lse = ctx.saved_tensors
         desc = ctx.desc
         dout = _aligned16(f32c(dout))
@@ -906,7 +911,7 @@ class MultiHeadAttentionFn(torch.autograd.Function):
         return dqkv, None
 
 
-def multi_head_attention(qkv, S, N, heads, batch_first=False, p=0.0, training=False, lengths=None):
+def multi_head_attention(qkv, S, N, heads, batch_first=False, p=0.0, training=False, *, return_lse=False, lengths=None):
     """Self-attention on the packed projection ``qkv`` [S * N, 3E] (row ``s * N + n``, or ``n * S + s`` with
     ``batch_first``) -> [S * N, E], heads concatenated.  ``p``: dropout on the attention weights, in training only; its
     Philox offset comes from :func:`manual_seed`'s stream.
@@ -914,15 +919,77 @@ def multi_head_attention(qkv, S, N, heads, batch_first=False, p=0.0, training=Fa
     ``lengths`` (one per attention-batch element ``n``, see :func:`check_lengths`): positions ``s >= lengths[n]`` are padding,
     torch's ``key_padding_mask[n, s] = s >= lengths[n]``: no query attends to them, their own output rows are exact zeros and
     so are their rows of the gradient.  Padded rows of ``qkv`` (and of the incoming gradient) are never read and may hold
-    anything.  A device tensor is not synced: the kernels clamp it to ``[0, S]`` (a 0 makes everything of ``n`` zero)."""
+    anything.  A device tensor is not synced: the kernels clamp it to ``[0, S]`` (a 0 makes everything of ``n`` zero).
+
+    ``return_lse`` (keyword only, as ``lengths`` now is beside it): -> ``(out, lse)``, ``lse`` [N * heads * S] the log-sum-exp of every score row as the forward wrote it
+    (non-differentiable): what :func:`attention_weights` and :func:`attention_rollout_step` rebuild the maps from.  Off, the
+    call is what it always was."""
     p = float(p) if training else 0.0
     cfg = (int(S), int(N), int(heads), bool(batch_first), p)
-    if lengths is not None:
-        if not (isinstance(lengths, torch.Tensor) and lengths.dtype == torch.int32 and tuple(lengths.shape) == (int(N),)
-                and lengths.device == qkv.device):
-            lengths = check_lengths(lengths, int(N), int(S)).to(qkv.device)
+    lengths = _mha_lengths(lengths, qkv, N, S)
+    if lengths is not None or return_lse:
         cfg += (lengths,)
+    if return_lse:
+        cfg += (True,)
     return MultiHeadAttentionFn.apply(qkv, cfg)
+
+
+def _mha_lengths(lengths, qkv, N, S):
+    """``None`` or the device ``int32 [N]`` tensor the attention kernels take (validated unless it already is one)"""
+    if lengths is None:
+        return None
+    if not (isinstance(lengths, torch.Tensor) and lengths.dtype == torch.int32 and tuple(lengths.shape) == (int(N),)
+            and lengths.device == qkv.device):
+        lengths = check_lengths(lengths, int(N), int(S)).to(qkv.device)
+    return lengths.contiguous()
+
+
+def _maps_operands(what, qkv, lse, S, N, heads, batch_first, lengths):
+    """the checked operands of the two map entry points -> (qkv, lse, desc, lengths)"""
+    _require_cuda(qkv, what)
+    _require_cuda(lse, what)
+    S, N, heads = int(S), int(N), int(heads)
+    if qkv.dim() != 2 or qkv.shape[0] != S * N or qkv.shape[1] % (3 * heads):
+        raise RuntimeError(f"{what}: qkv must be [S * N, 3 * E] with E a multiple of heads, got {tuple(qkv.shape)} for "
+                           f"S={S} N={N} heads={heads}")
+    if lse.numel() != N * heads * S:
+        raise RuntimeError(f"{what}: lse must hold N * heads * S = {N * heads * S} values, got {tuple(lse.shape)}")
+    qkv, lse = _aligned16(f32c(qkv.detach())), f32c(lse.detach())
+    desc = L.MHADesc(S, N, heads, qkv.shape[1] // 3 // heads, int(bool(batch_first)), 0.0)
+    return qkv, lse, desc, _mha_lengths(lengths, qkv, N, S)
+
+
+def attention_weights(qkv, lse, S, N, heads, batch_first=False, lengths=None, average=True):
+    """The attention weights of :func:`multi_head_attention` on ``qkv``, rebuilt from the ``lse`` it returned
+    (``return_lse=True``; ``ecgmm_mha_weights``): ``[N, S, S]`` averaged over the heads (``average``, torch's
+    ``average_attn_weights``) or ``[N, heads, S, S]``, always (query row, key column).  These are the probabilities before
+    dropout.  With ``lengths`` the padded query rows and key columns are exact zeros (torch's padded query rows still attend).
+    ``4 * N * S * S`` bytes (times ``heads`` per head).  The result is detached and carries no gradient."""
+    qkv, lse, desc, lengths = _maps_operands("attention_weights", qkv, lse, S, N, heads, batch_first, lengths)
+    shape = (desc.N, desc.S, desc.S) if average else (desc.N, desc.heads, desc.S, desc.S)
+    w = torch.empty(shape, device=qkv.device, dtype=torch.float32)
+    L.check(L.lib().ecgmm_mha_weights(C.byref(desc), ptr(qkv), ptr(lse), ptr(lengths), ptr(w), 0 if average else 1, stream()),
+            "mha_weights")
+    return w
+
+
+def attention_rollout_step(qkv, lse, v, S, N, heads, batch_first=False, lengths=None, residual=0.5):
+    """One step of attention rollout of the row vectors ``v`` [N, S] through one attention layer (``ecgmm_mha_rollout_step``):
+    ``residual * v + (1 - residual) * v @ mean_h P`` with ``P`` the layer's attention weights, rebuilt from ``qkv`` and the
+    ``lse`` of its forward without forming them.  ``0 <= residual < 1``.  With ``lengths`` padded ``v`` is never read and the
+    padded result is exact 0.  The result is detached and carries no gradient."""
+    residual = float(residual)
+    if not 0.0 <= residual < 1.0:
+        raise ValueError(f"attention_rollout_step: residual={residual} must lie in [0, 1)")
+    qkv, lse, desc, lengths = _maps_operands("attention_rollout_step", qkv, lse, S, N, heads, batch_first, lengths)
+    _require_cuda(v, "attention_rollout_step")
+    if tuple(v.shape) != (desc.N, desc.S):
+        raise RuntimeError(f"attention_rollout_step: v must be [N, S] = [{desc.N}, {desc.S}], got {tuple(v.shape)}")
+    v = f32c(v.detach())
+    y = torch.empty_like(v)
+    L.check(L.lib().ecgmm_mha_rollout_step(C.byref(desc), ptr(qkv), ptr(lse), ptr(lengths), ptr(v), ptr(y), residual,
+                                           stream()), "mha_rollout_step")
+    return y
 
 
 class AddFn(torch.autograd.Function):

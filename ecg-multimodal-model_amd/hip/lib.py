@@ -242,6 +242,8 @@ SIGNATURES = {
     "ecgmm_mha_keep_mask": (i32, [P(MHADesc), vp, u64, u64, vp]),
     "ecgmm_mha_forward_varlen": (i32, [P(MHADesc), vp, vp, vp, vp, u64, u64, vp]),
     "ecgmm_mha_backward_varlen": (i32, [P(MHADesc), vp, vp, vp, vp, vp, vp, vp, sz, u64, u64, vp]),
+    "ecgmm_mha_weights": (i32, [P(MHADesc), vp, vp, vp, vp, i32, vp]),
+    "ecgmm_mha_rollout_step": (i32, [P(MHADesc), vp, vp, vp, vp, vp, f32, vp]),
     "ecgmm_embed1d_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "ecgmm_embed1d_bwd_workspace": (sz, [i32, i32, i32, i32]),
     "ecgmm_embed1d_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
@@ -293,7 +295,9 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  # the lane rule of the chunked filtfilt kernels (csrc/preprocess.hip)
                  "ecgmm_signal_filter_lanes",
                  # lengths in the attention kernels (csrc/attention.hip)
-                 "ecgmm_mha_forward_varlen", "ecgmm_mha_backward_varlen")
+                 "ecgmm_mha_forward_varlen", "ecgmm_mha_backward_varlen",
+                 # attention maps and the rollout step (ecgmm.explain.attention_maps / attention_rollout)
+                 "ecgmm_mha_weights", "ecgmm_mha_rollout_step")
 
 _lib = None
 

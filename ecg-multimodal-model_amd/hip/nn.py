@@ -254,12 +254,37 @@ class MultiheadAttention(nn.Module):
         S, N = (x.shape[1], x.shape[0]) if self.batch_first else (x.shape[0], x.shape[1])
         return HF.check_lengths(lengths, N, S).to(x.device)
 
-    def _attend(self, x2, shape, lengths=None):
-        """x2 [rows, E], the rows of a tensor of ``shape`` -> [rows, E]; ``lengths``: as :meth:`_lengths` returns them"""
+    def _attend(self, x2, shape, lengths=None, sink=None):
+        """x2 [rows, E], the rows of a tensor of ``shape`` -> [rows, E]; ``lengths``: as :meth:`_lengths` returns them.
+        ``sink`` (a list): a record of this attention is appended -- detached ``qkv`` and ``lse`` and ``S``, ``N``, ``heads``,
+        ``batch_first``, ``lengths``, the arguments of :func:`ecgmm.hip.functional.attention_weights`; the launches and the
+        result are the same with and without it."""
         S, N = (shape[1], shape[0]) if self.batch_first else (shape[0], shape[1])
         qkv = HF.linear(x2, self.in_proj_weight, self.in_proj_bias)
-        a = HF.multi_head_attention(qkv, S, N, self.num_heads, self.batch_first, self.dropout, self.training, lengths)
+        if sink is None:
+            a = HF.multi_head_attention(qkv, S, N, self.num_heads, self.batch_first, self.dropout, self.training,
+                                        lengths=lengths)
+        else:
+            a, lse = HF.multi_head_attention(qkv, S, N, self.num_heads, self.batch_first, self.dropout, self.training,
+                                             lengths=lengths, return_lse=True)
+            sink.append({"qkv": qkv.detach(), "lse": lse.detach(), "S": S, "N": N, "heads": self.num_heads,
+                         "batch_first": self.batch_first, "lengths": lengths})
         return HF.linear(a, self.out_proj.weight, self.out_proj.bias)
+
+    def attention_weights(self, x, *, lengths=None, average_attn_weights=True):
+        """The attention weights of ``forward(x, lengths=lengths)``: ``[N, S, S]`` averaged over the heads, or
+        ``[N, heads, S, S]`` with ``average_attn_weights=False`` -- what torch's ``need_weights=True`` returns, computed from
+        the forward's stored log-sum-exp by ``ecgmm_mha_weights`` (``forward(need_weights=True)`` itself stays refused: the
+        forward never forms them).  Always the probabilities BEFORE dropout, also in training mode.  With ``lengths`` the
+        padded query rows and key columns are exact zeros.  Detached, no gradient."""
+        if x.dim() != 3 or x.shape[2] != self.embed_dim:
+            raise ValueError(f"MultiheadAttention: input must be 3-D with {self.embed_dim} features, got {tuple(x.shape)}")
+        S, N = (x.shape[1], x.shape[0]) if self.batch_first else (x.shape[0], x.shape[1])
+        lengths = self._lengths(lengths, x)
+        with torch.no_grad():   # no dropout: the log-sum-exp does not depend on it, and no Philox offset is taken
+            qkv = HF.linear(x.reshape(-1, self.embed_dim), self.in_proj_weight, self.in_proj_bias)
+            _, lse = HF.multi_head_attention(qkv, S, N, self.num_heads, self.batch_first, lengths=lengths, return_lse=True)
+        return HF.attention_weights(qkv, lse, S, N, self.num_heads, self.batch_first, lengths, average_attn_weights)
 
 
 class TransformerEncoderLayer(nn.Module):
@@ -287,8 +312,10 @@ class TransformerEncoderLayer(nn.Module):
         self.dropout1 = nn.Dropout(dropout)
         self.dropout2 = nn.Dropout(dropout)
 
-    def forward(self, src, src_mask=None, src_key_padding_mask=None, is_causal=False, *, lengths=None):
-        """``lengths`` (keyword only): one length per attention-batch element (dimension 0 of ``src`` with ``batch_first``,
+    def forward(self, src, src_mask=None, src_key_padding_mask=None, is_causal=False, *, lengths=None, attention_sink=None):
+        """``attention_sink`` (keyword only; a list): the layer appends the record of its attention
+        (:meth:`MultiheadAttention._attend`), from which ``ecgmm.explain`` rebuilds the maps; the output is bit-identical with
+        and without it.  ``lengths`` (keyword only): one length per attention-batch element (dimension 0 of ``src`` with ``batch_first``,
         dimension 1 otherwise), as :meth:`MultiheadAttention.forward` takes them: padded positions are never keys.
         Everything around the attention (projections, residual adds, LayerNorm, feed-forward) runs over all rows, so
         PADDED ``src`` MUST BE FINITE and the padded rows of the output are not zero; nothing live depends on them, and
@@ -304,7 +331,8 @@ class TransformerEncoderLayer(nn.Module):
         lengths = self.self_attn._lengths(lengths, src)
         t = self.training
         x = src.reshape(-1, E)
-        a = HF.dropout(self.self_attn._attend(x, src.shape, lengths), self.dropout1.p, t and self.dropout1.training)
+        a = HF.dropout(self.self_attn._attend(x, src.shape, lengths, attention_sink), self.dropout1.p,
+                       t and self.dropout1.training)
         x = self.norm1(HF.add(x, a))
         h = HF.dropout(self.linear1(x, act=L.ACT_RELU), self.dropout.p, t and self.dropout.training)
         f = HF.dropout(self.linear2(h), self.dropout2.p, t and self.dropout2.training)
@@ -328,9 +356,10 @@ class TransformerEncoder(nn.Module):
         self.num_layers = num_layers
         self.norm = None
 
-    def forward(self, src, mask=None, src_key_padding_mask=None, is_causal=None, *, lengths=None):
+    def forward(self, src, mask=None, src_key_padding_mask=None, is_causal=None, *, lengths=None, attention_sink=None):
         """``lengths`` (keyword only): one length per attention-batch element, validated once and passed to every layer
-        (:meth:`TransformerEncoderLayer.forward`: padded ``src`` must be finite, padded output rows are not zero)."""
+        (:meth:`TransformerEncoderLayer.forward`: padded ``src`` must be finite, padded output rows are not zero).
+        ``attention_sink`` (keyword only; a list): every layer appends the record of its attention, first layer first."""
         for name, t in (("mask", mask), ("src_key_padding_mask", src_key_padding_mask)):
             if t is not None:
                 raise ValueError(f"TransformerEncoder: {name} is not supported (no masks; for padding pass lengths=)")
@@ -340,5 +369,8 @@ class TransformerEncoder(nn.Module):
             lengths = self.layers[0].self_attn._lengths(lengths, src)
         x = src
         for layer in self.layers:
-            x = layer(x) if lengths is None else layer(x, lengths=lengths)
+            kw = {} if lengths is None else {"lengths": lengths}
+            if attention_sink is not None:
+                kw["attention_sink"] = attention_sink
+            x = layer(x, **kw)
         return x

@@ -61,7 +61,11 @@ class ECGTransformer1D(torch.nn.Module):
     Only then does ``forward(x, lengths=...)`` make sense: one length per sample (``HF.check_lengths``), the positions behind
     it are never keys and do not enter the mean over the positions, and the padded samples of ``x`` are replaced by zeros
     before the convolution (its 3-tap window at the last live position reaches one sample into the padding).  A sample's
-    logits then depend on its own live samples alone, bit for bit."""
+    logits then depend on its own live samples alone, bit for bit.
+
+    ``forward(x, lengths, attention_sink=[])``: every encoder layer appends the record of its attention to the list
+    (``ecgmm.hip.nn.TransformerEncoderLayer``), what ``ecgmm.explain.attention_maps`` / ``attention_rollout`` work from; the
+    logits are bit-identical with and without it."""
 
     def __init__(self, input_dim=1, seq_len=3000, num_classes=2, d_model=128, nhead=4, num_layers=2, dim_feedforward=256,
                  time_attention=False):
@@ -76,7 +80,7 @@ class ECGTransformer1D(torch.nn.Module):
         self.classifier = HN.Sequential(torch.nn.Flatten(), HN.Linear(d_model, 64), torch.nn.ReLU(), torch.nn.Dropout(0.3),
                                         HN.Linear(64, num_classes))
 
-    def forward(self, x, lengths=None):
+    def forward(self, x, lengths=None, attention_sink=None):
         if lengths is not None and not self.time_attention:
             raise ValueError("ECGTransformer1D: lengths needs time_attention=True (attention across the batch has no "
                              "per-sample length)")
@@ -93,10 +97,11 @@ class ECGTransformer1D(torch.nn.Module):
             live = torch.arange(x.shape[2], device=x.device)[None, None, :] < lengths[:, None, None]
             x = x.masked_fill(~live, 0.0)
         x = HF.embed1d(x, self.conv.weight, self.conv.bias, self.pos_embedding)   # [B, L, d_model]
+        sink = {} if attention_sink is None else {"attention_sink": attention_sink}
         if lengths is None:
-            x = self.transformer_encoder(x)                 # sequence axis = B as the reference, or L with time_attention
+            x = self.transformer_encoder(x, **sink)         # sequence axis = B as the reference, or L with time_attention
             return self.classifier(HF.seq_mean(x))
-        x = self.transformer_encoder(x, lengths=lengths)
+        x = self.transformer_encoder(x, lengths=lengths, **sink)
         return self.classifier(HF.seq_mean(x, lengths))
 
 
@@ -343,7 +348,8 @@ def evaluate(model, loader, num_classes=2, predictor=None):
 
 
 def main(config=Config, num_epochs=30, batch_size=8, quiet=False, use_predictor=False, num_classes=2, label_map=LABEL_MAP,
-         augment=True, split=SPLIT, model="resnet", max_len=MAX_LEN, time_attention=False, use_lengths=False):
+         augment=True, split=SPLIT, model="resnet", max_len=MAX_LEN, time_attention=False, use_lengths=False,
+         rollout_samples=0):
     """``model``: ``"resnet"`` (the reference's choice) or ``"transformer"`` (its commented alternative, :276); ``max_len``:
     the length every record is padded or cut to.
     ``use_predictor``: run the validation and test passes through an ``ecgmm.inference.Predictor`` (BatchNorm-folded
@@ -353,9 +359,19 @@ def main(config=Config, num_epochs=30, batch_size=8, quiet=False, use_predictor=
     ``use_lengths`` or ``config.physionet_use_lengths`` (off by default; needs ``time_attention``): the loaders carry
     ``min(len(record), max_len)`` per record and the model gets it, so the zero padding of a short record is neither
     attended to nor averaged (:class:`DeviceSignalLoader` on what the augmentation's roll does at the record's end).
+    ``rollout_samples=k`` > 0 (needs ``model="transformer"`` with ``time_attention``): after the test pass, with the weights
+    it ended on, ``attention_rollout.npz`` is written into the run directory for the first ``k`` test records:
+    ``relevance`` [k, L] (``ecgmm.explain.attention_rollout``), ``lengths`` [k] (``max_len`` without ``use_lengths``),
+    ``labels`` [k] and ``probs`` [k, classes].  The default 0 writes nothing.
     -> (history, {"best": metrics, "last": metrics}, checkpoint directory)."""
     time_attention = bool(time_attention or getattr(config, "physionet_time_attention", False))
     use_lengths = bool(use_lengths or getattr(config, "physionet_use_lengths", False))
+    rollout_samples = int(rollout_samples)
+    if rollout_samples < 0:
+        raise ValueError(f"rollout_samples={rollout_samples} must be >= 0")
+    if rollout_samples and not (model == "transformer" and time_attention):
+        raise ValueError("rollout_samples needs model='transformer' and time_attention=True (attention rollout is the "
+                         "transformer's map over each record's own positions)")
     if (time_attention or use_lengths) and model == "resnet":
         raise ValueError("time_attention / use_lengths need model='transformer' (the ResNet1D_SE has neither)")
     if use_lengths and not time_attention:
@@ -409,7 +425,31 @@ def main(config=Config, num_epochs=30, batch_size=8, quiet=False, use_predictor=
     if not quiet:
         for tag, res in results.items():
             print(f"test[{tag}]: {res}")
+    if rollout_samples:
+        path = write_attention_rollout(model, test_loader.dataset, rollout_samples, ckpt_dir)
+        if not quiet:
+            print(f"attention rollout of the first test records -> {path}")
     return history, results, ckpt_dir
+
+
+def write_attention_rollout(model, dataset, k, out_dir, residual=0.5):
+    """``attention_rollout.npz`` in ``out_dir`` for the first ``k`` records of ``dataset`` (a :class:`SignalOnlyDataset`):
+    ``relevance`` [k, L], ``lengths`` [k], ``labels`` [k], ``probs`` [k, classes] -> the file's path"""
+    from .explain import attention_rollout
+    k = min(int(k), len(dataset))
+    x = dataset.signals[:k].unsqueeze(1)
+    lengths = None if dataset.lengths is None else dataset.lengths[:k]
+    relevance = attention_rollout(model, x, lengths, residual=residual)
+    was_training = model.training
+    model.eval()
+    with torch.no_grad():
+        logits = model(x) if lengths is None else model(x, lengths)
+    model.train(was_training)
+    path = os.path.join(out_dir, "attention_rollout.npz")
+    np.savez(path, relevance=relevance.cpu().numpy(),
+             lengths=(np.full(k, x.shape[2], dtype=np.int32) if lengths is None else dataset.lengths_host[:k].numpy()),
+             labels=dataset.labels_host[:k].numpy(), probs=torch.softmax(logits.float(), dim=1).cpu().numpy())
+    return path
 
 
 if __name__ == "__main__":

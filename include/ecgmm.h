@@ -922,6 +922,30 @@ int ecgmm_mha_forward_varlen(const ecgmm_mha_desc* d, const float* qkv, const in
 int ecgmm_mha_backward_varlen(const ecgmm_mha_desc* d, const float* qkv, const int32_t* lengths, const float* out,
                               const float* lse, const float* dout, float* dqkv, void* ws, size_t ws_bytes, uint64_t seed,
                               uint64_t offset, void* stream);
+/* Attention maps and attention rollout, from the qkv the forward read and the lse it wrote (the backward's own recomputation):
+ *     p[n,h,i,j] = exp(scale q_i . k_j - lse[n,h,i]),  the normalised probabilities BEFORE dropout.
+ * p_drop of the descriptor is validated and then ignored: in eval mode and at dropout 0 these are torch's attention weights;
+ * in training mode torch returns the dropped, rescaled weights and these stay the undropped ones.
+ * ecgmm_mha_weights: weights [N][heads][S][S] (per_head = 1) or the head average [N][S][S] (per_head = 0, torch's
+ *   average_attn_weights = True): the heads h = 0, 1, .. summed in that order in fp32, then ONE multiplication by the fp32
+ *   1 / heads.  The layout is always (query row, key column), whatever batch_first says of qkv.  Every element is WRITTEN.
+ * ecgmm_mha_rollout_step: v_in, v_out [N][S] fp32 (v_out != v_in),
+ *     v_out[n][j] = residual v_in[n][j] + (1 - residual) (1 / heads) sum_h sum_i v_in[n][i] p[n,h,i,j],   0 <= residual < 1:
+ *   one step of attention rollout (Abnar & Zuidema 2020) of a ROW vector through a I + (1 - a) mean_h P, without the S x S
+ *   matrix and without a workspace.  residual outside [0, 1) is ECGMM_ERR_SHAPE.
+ * lengths (nullable, device int32 [N], clamped to [0, S], the lengths the forward ran with): a live query row holds the
+ * softmax over the live keys; padded query rows and padded key columns of the weights are exact 0 (torch's padded QUERY rows
+ * still attend to the live keys: here they do not exist); padded v_in is never read and padded v_out is exact 0; padded rows
+ * of qkv are never read; a tile wholly in the padding loads nothing, and the loops run ceil(lengths[n] / 16) tiles.  At
+ * S > 8 and lengths[n] > 8 element n has the bits of the same element alone with S = lengths[n]; lengths = null equals
+ * lengths all S bit for bit.  Any S >= 1 (S <= 8 runs as one partial tile per n).  Each output element is written by one
+ * lane, every sum runs in a fixed order, no atomics: two identical calls give identical bits.  A refused call writes nothing. */
+/* train_physionet.py:219-220, 236; multimodal_paper_modal_balance.py:133-140: the attention weights of each self_attn */
+int ecgmm_mha_weights(const ecgmm_mha_desc* d, const float* qkv, const float* lse, const int32_t* lengths, float* weights,
+                      int per_head, void* stream);
+/* train_physionet.py:219-220, 236; multimodal_paper_modal_balance.py:133-140: the rollout of the mean-pooled output */
+int ecgmm_mha_rollout_step(const ecgmm_mha_desc* d, const float* qkv, const float* lse, const int32_t* lengths,
+                           const float* v_in, float* v_out, float residual, void* stream);
 
 /* The front of ECGTransformer1D (train_physionet.py:216-217, 233-235) as one launch: Conv1d(Cin, Dm, 3, padding = 1) + bias
  * written straight as [B][L][Dm] with pos[l][c] added.  x [B][Cin][L], w [Dm][Cin][3], bias [Dm], pos [>= L][Dm], fp32.

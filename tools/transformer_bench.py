@@ -23,6 +23,10 @@ uniformly from [S / 4, S] under a fixed seed, as drawn ("unsorted") and in desce
 without lengths of the same process ("full").  Reported with them: sum(len^2) / (N S^2), the share of the score tiles that
 hold a live (query, key) pair, which the attention time should follow; the layer also keeps its projections, LayerNorms and
 feed-forward over all rows.  Default output profiles/transformer_bench_lengths.json.
+
+--maps: at bf_3000 and bf_750, the head-averaged attention map (ecgmm_mha_weights, 4 N S^2 bytes written) and one rollout step
+(ecgmm_mha_rollout_step) from the qkv and the lse of a forward, beside the attention forward of the same process.  Both redo
+the forward's QK^T half and its exponentials (2 S^2 d FLOPs per (n, head)).  Default output profiles/transformer_bench_maps.json.
 """
 import argparse
 import json
@@ -35,6 +39,7 @@ ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--out", default=None)
 ap.add_argument("--lengths", action="store_true", help="time the kernels with per-element lengths (see the module docstring)")
+ap.add_argument("--maps", action="store_true", help="time the attention maps and the rollout step (see the module docstring)")
 args = ap.parse_args()
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -99,10 +104,39 @@ def lengths_variants():
     return variants, drawn
 
 
+def maps_variants():
+    """{name: (fn, flops)} for --maps"""
+    variants = {}
+    for name in ("bf_3000", "bf_750"):
+        S, N, E, heads, _ff, bf = SHAPES[name]
+        qkv = torch.randn(S * N, 3 * E, device=dev)
+        v = torch.full((N, S), 1.0 / S, device=dev)
+        with torch.no_grad():
+            _, lse = HF.multi_head_attention(qkv, S, N, heads, bf, return_lse=True)
+        flops = 4.0 * S * S * (E // heads) * N * heads
+
+        def attn_fwd(qkv=qkv, S=S, N=N, heads=heads, bf=bf):
+            with torch.no_grad():
+                HF.multi_head_attention(qkv, S, N, heads, bf)
+
+        def weights(qkv=qkv, lse=lse, S=S, N=N, heads=heads, bf=bf):
+            HF.attention_weights(qkv, lse, S, N, heads, bf)
+
+        def step(qkv=qkv, lse=lse, v=v, S=S, N=N, heads=heads, bf=bf):
+            HF.attention_rollout_step(qkv, lse, v, S, N, heads, bf)
+
+        variants[name + "/attention_fwd"] = (attn_fwd, flops)
+        variants[name + "/weights_averaged"] = (weights, flops / 2)
+        variants[name + "/rollout_step"] = (step, flops / 2)
+    return variants
+
+
 def main():
     torch.manual_seed(0)
     variants, drawn = lengths_variants() if args.lengths else ({}, None)
-    for name, (S, N, E, heads, ff, bf) in ({} if args.lengths else SHAPES).items():
+    if args.maps:
+        variants = maps_variants()
+    for name, (S, N, E, heads, ff, bf) in ({} if args.lengths or args.maps else SHAPES).items():
         d = E // heads
         ours = HN.TransformerEncoderLayer(E, heads, ff, dropout=0.0, batch_first=bf).to(dev).train()
         ref = nn.TransformerEncoderLayer(E, heads, ff, dropout=0.0, batch_first=bf).to(dev).train()
@@ -164,14 +198,20 @@ def main():
             v["fraction_of_f32_mfma_peak"] = flops / (ms * 1e-3) / PEAK_F32
             line += f"  {v['gflop']:8.2f} GFLOP = {100 * v['fraction_of_f32_mfma_peak']:.2f} % of the f32 MFMA peak"
         print(line, flush=True)
+    if args.maps:   # each over the attention forward of the same shape
+        for k, v in res["variants"].items():
+            name, what = k.split("/")
+            if what != "attention_fwd":
+                v["time_over_attention_fwd"] = v["ms_median"] / res["variants"][name + "/attention_fwd"]["ms_median"]
+                print(f"{k:38s} {v['time_over_attention_fwd']:.3f} of the attention forward's time", flush=True)
     if drawn is not None:   # each lengths run over the full run of the same shape
         for k, v in res["variants"].items():
             name, tag, what = k.split("/")
             if tag != "full":
                 v["time_over_full"] = v["ms_median"] / res["variants"][f"{name}/full/{what}"]["ms_median"]
                 print(f"{k:38s} {v['time_over_full']:.3f} of the full run's time", flush=True)
-    out = args.out or os.path.join(ROOT, "profiles", "transformer_bench_lengths.json" if args.lengths else
-                                   "transformer_bench.json")
+    out = args.out or os.path.join(ROOT, "profiles", "transformer_bench_maps.json" if args.maps else
+                                   "transformer_bench_lengths.json" if args.lengths else "transformer_bench.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
         json.dump(res, f, indent=1)
