@@ -51,7 +51,12 @@ class CRNN(nn.Module):
         """``x [B, 1, F, T]``.  ``lengths``: the valid spectrogram frames of each record (``x`` zero-padded behind them).
         The LSTM and the mean over time then take ``clamp(lengths // 8, 1, T // 8)`` steps per record -- three floor pools
         give exactly ``// 8`` -- so the recurrence neither runs through the padding nor averages it in.  The convolution
-        front end and its BatchNorm statistics stay as they are, padding included: that is the reference's arithmetic."""
+        front end and its BatchNorm statistics stay as they are, padding included: that is the reference's arithmetic.
+        An ``x`` that requires a gradient gets it, in training and in eval mode (``explain.spectrogram_gradients``)."""
+        return self._tail(self._front(x), lengths, x.shape[3])[0]
+
+    def _front(self, x):
+        """conv1..conv3 + permute + Flatten as one launch plan: ``x [B, 1, F, T]`` -> ``seq [B, T // 8, 512]`` fp32"""
         if not x.is_cuda:
             raise RuntimeError(f"CRNN: tensor is on {x.device}; the HIP library is the only compute path (no CPU fallback) "
                                "-- move the model and inputs to a ROCm device")
@@ -65,12 +70,17 @@ class CRNN(nn.Module):
             raise ValueError(f"CRNN: T={x.shape[3]} time bins; three 2x2 pools need at least 8")
         params, buffers = self._front_tables()
         bn = self.conv1.block[1]
-        seq = HF.crnn_front(x, params, buffers, self.training, bn.momentum, bn.eps, self._dtype)
+        return HF.crnn_front(x, params, buffers, self.training, bn.momentum, bn.eps, self._dtype)
+
+    def _tail(self, seq, lengths, frames):
+        """Everything behind the front end: BiLSTM, mean over time, classifier on ``seq [B, T // 8, 512]`` of a spectrogram
+        of ``frames`` = T columns -> (logits, the int32 live steps per record or None).  ``forward`` ends in it, and
+        ``explain.spectrogram_grad_cam`` starts a graph at ``seq`` with it."""
         if lengths is None:
             out, _ = self.bilstm(seq)
-            return self.classifier(HF.seq_mean(out))
+            return self.classifier(HF.seq_mean(out)), None
         steps = seq.shape[1]
-        lengths = HF.check_lengths(lengths, x.shape[0], x.shape[3]).to(x.device)
+        lengths = HF.check_lengths(lengths, seq.shape[0], frames).to(seq.device)
         lengths = torch.clamp(lengths // 8, 1, steps).to(torch.int32)
         out, _ = self.bilstm(seq, lengths=lengths)
-        return self.classifier(HF.seq_mean(out, lengths))
+        return self.classifier(HF.seq_mean(out, lengths)), lengths

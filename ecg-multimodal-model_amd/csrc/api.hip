@@ -449,6 +449,17 @@ int ecgmm_conv5_in1_bwd_weight(int dtype, const float* x, const void* dy, float*
                                size_t ws_bytes, int N, int H, int W, void* stream) {
   return ecg_conv5_in1_wgrad(dtype, x, dy, dw_oihw, dbias, accumulate, ws, ws_bytes, N, H, W, S_(stream));
 }
+int ecgmm_conv5_in1_bwd_data(int dtype, const void* dy, const float* w_oihw, float* dx, int N, int H, int W, void* stream) {
+  return ecg_conv5_in1_dgrad(dtype, dy, w_oihw, dx, N, H, W, S_(stream));
+}
+void ecgmm_conv5_in1_bwd_data_tile(int H, int* strip, int* row_step, int* rows) {
+  ecg_conv5_in1_dgrad_tile(H, strip, row_step, rows);
+}
+size_t ecgmm_crnn_gradcam_workspace(int B, int Tp, int Fp, int C) { return ecg_crnn_gradcam_workspace(B, Tp, Fp, C); }
+int ecgmm_crnn_gradcam(const float* seq, const float* dseq, const int32_t* steps, const int32_t* frames, void* ws,
+                       size_t ws_bytes, float* cam, int B, int Tp, int C, int Fp, int F, int T, void* stream) {
+  return ecg_crnn_gradcam(seq, dseq, steps, frames, ws, ws_bytes, cam, B, Tp, C, Fp, F, T, S_(stream));
+}
 size_t ecgmm_conv5_bwd_weight_workspace(int dtype, const ecgmm_conv_desc* c) {
   if (!c) { ecg_set_error("conv5_bwd_weight_workspace: null desc"); return 0; }
   return ecg_conv5_wgrad_workspace(dtype, geom_of(c));

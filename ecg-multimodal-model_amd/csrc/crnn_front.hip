@@ -10,6 +10,8 @@
 //                           implicit-GEMM epilogue does (conv_igemm.hip), so all three blocks follow one convention.
 //   conv5_in1_wgrad_kernel  its weight + bias gradient: a workgroup walks (image row, 64-column) tiles; the 5 x 68 x patch
 //                           and the 64 x 32 dy tile of a tile sit in LDS; thread (channel, slot) owns taps slot + 8k.
+//   conv5_in1_dgrad_kernel  its input gradient (what spectrogram.requires_grad_() gives): column strips, a rolling window of
+//                           dy rows in LDS, thread = pixel x 8 channels, VALU fma (the GEMM has N = 1), fp32 out
 //   conv5_wgrad_kernel      weight gradient of a 5x5 pad-2 stride-1 convolution, Cin and Cout multiples of 32.  GEMM view
 //                           per tap: dw[co][ci] = sum_pixels dy[p][co] x[p + tap][ci]; pixels are the MFMA K index.  A
 //                           workgroup owns a 32 x 32 (co, ci) tile of ALL 25 taps and walks bands of 32 pixels of one
@@ -182,6 +184,118 @@ __global__ __launch_bounds__(256) void conv5_in1_wgrad_reduce_kernel(const float
     if (dw) dw[co * C5_TAPS + tap] = (accumulate ? dw[co * C5_TAPS + tap] : 0.f) + (float)s;
   } else if (db) {
     db[co] = (accumulate ? db[co] : 0.f) + (float)s;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Conv2d(1, 32, 5, pad 2) input gradient: dx[n][h][w] = sum_{co, r, s} dy[n][h+2-r][w+2-s][co] * w[co][r][s].
+// A workgroup owns DG_STRIP columns of one image and walks down its rows DG_RSTEP at a time.  The DG_WIN = DG_RSTEP + 4
+// dy rows a trip reads sit in an LDS ring, so a row is fetched from memory once per strip (plus the four halo rows
+// where two workgroups of a strip meet); a trip issues the global loads of the next trip's rows before its own
+// arithmetic and parks them in the ring after it.  Thread = one pixel x 8 channels, as the forward; the four threads of a
+// pixel are the four lanes of a DPP quad and fold in a fixed order.
+// LDS layout: a ring row is NH planes of [DG_COLS][4] 16-byte chunks, plane = which of a thread's NH chunks (bf16: one
+// chunk of 8 channels; fp32: two chunks of 4 channels, 16 channels apart).  A wave's ds_read_b128 then covers 16 pixels x
+// 64 B = 1 KiB contiguous in both dtypes: no two lanes on one bank, no padding needed.  The weights sit beside it in the
+// threads' channel order ([tap][quad lane][8]): four addresses per wave, broadcast.  They are re-read every trip: the loop
+// over the tap columns stays rolled, because unrolled the compiler keeps a thread's 25 x 8 weights in registers across the
+// row loop (430 of them, one wave per SIMD), which measured three times slower than two to four waves and the re-reads.
+// Two output rows per trip share every dy read (30 chunk reads for 50 taps) and every weight read.
+// ------------------------------------------------------------------------------------------------
+constexpr int DG_STRIP = 64;                 // columns of a strip = pixels of a workgroup (4 threads per pixel)
+constexpr int DG_COLS = DG_STRIP + 4;
+constexpr int DG_RSTEP = 2;                  // output rows per trip
+constexpr int DG_WIN = DG_RSTEP + 4;         // dy rows of a trip = ring slots
+constexpr int DG_ROWS_MAX = 64;              // output rows of a workgroup at most
+
+template <typename T>
+__global__ __launch_bounds__(IN1_THREADS) void conv5_in1_dgrad_kernel(const T* __restrict__ dy, const float* __restrict__ w,
+                                                                     float* __restrict__ dx, int H, int W, int strips,
+                                                                     int hchunks, int rows_per) {
+  constexpr int VEC = Elem<T>::VEC;          // channels per 16-byte chunk
+  constexpr int NH = 8 / VEC;                // chunks of a thread's 8 channels
+  constexpr int CH = IN1_C / VEC;            // chunks of a pixel
+  constexpr int ROWCH = DG_COLS * CH;        // chunks of a ring row
+  constexpr int PF = (DG_RSTEP * ROWCH + IN1_THREADS - 1) / IN1_THREADS;   // chunks a thread fetches per trip
+  __shared__ u32x4 dys[DG_WIN * NH * DG_COLS * 4];
+  __shared__ float ws[C5_TAPS][4][8];
+  const int tid = threadIdx.x, p = tid >> 2, q = tid & 3;
+  for (int i = tid; i < C5_TAPS * IN1_C; i += IN1_THREADS) {
+    const int tap = i / IN1_C, ql = (i % IN1_C) / 8, k = i % 8;
+    const int co = (k / VEC) * (4 * VEC) + ql * VEC + k % VEC;   // channel k of quad lane ql
+    ws[tap][ql][k] = round_operand<T>(w[co * C5_TAPS + tap]);
+  }
+  const int strip = blockIdx.x % strips, t = blockIdx.x / strips;
+  const int n = t / hchunks, h0 = (t % hchunks) * rows_per, h1 = min(H, h0 + rows_per);
+  const int w0 = strip * DG_STRIP;
+  const T* img = dy + (long)n * H * W * IN1_C;
+  u32x4 v[PF];
+  // rows row0 .. row0 + DG_RSTEP - 1 of the strip (with its two halo columns each side), zeros outside the image
+  auto fetch = [&](int row0) {
+#pragma unroll
+    for (int k = 0; k < PF; ++k) {
+      const int i = tid + k * IN1_THREADS;
+      const int hh = row0 + i / ROWCH, ww = w0 - 2 + (i % ROWCH) / CH;
+      v[k] = (u32x4){0u, 0u, 0u, 0u};
+      if (i < DG_RSTEP * ROWCH && (unsigned)hh < (unsigned)H && (unsigned)ww < (unsigned)W)
+        v[k] = *reinterpret_cast<const u32x4*>(img + ((long)hh * W + ww) * IN1_C + (i % CH) * VEC);
+    }
+  };
+  auto park = [&](int row0) {
+#pragma unroll
+    for (int k = 0; k < PF; ++k) {
+      const int i = tid + k * IN1_THREADS;
+      if (i >= DG_RSTEP * ROWCH) continue;
+      const int slot = (row0 + i / ROWCH - (h0 - 2)) % DG_WIN, col = (i % ROWCH) / CH, c = i % CH;
+      dys[((slot * NH + c / 4) * DG_COLS + col) * 4 + c % 4] = v[k];
+    }
+  };
+  for (int r0 = h0 - 2; r0 < h0 - 2 + DG_WIN; r0 += DG_RSTEP) {
+    fetch(r0);
+    park(r0);
+  }
+  __syncthreads();
+  for (int h = h0; h < h1; h += DG_RSTEP) {
+    const bool more = h + DG_RSTEP < h1;   // (uniform)
+    if (more) fetch(h + DG_WIN - 2);
+    const int sb = (h - h0) % DG_WIN;
+    float acc[DG_RSTEP][8];
+#pragma unroll
+    for (int o = 0; o < DG_RSTEP; ++o)
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc[o][k] = 0.f;
+#pragma unroll 1   // (rolled on purpose: see the weights above)
+    for (int s = 0; s < 5; ++s) {
+      float d[DG_WIN][8];
+#pragma unroll
+      for (int j = 0; j < DG_WIN; ++j) {
+        const int slot = sb + j < DG_WIN ? sb + j : sb + j - DG_WIN;
+#pragma unroll
+        for (int hf = 0; hf < NH; ++hf)
+          unpack16<T>(dys[((slot * NH + hf) * DG_COLS + p + 4 - s) * 4 + q], d[j] + hf * VEC);
+      }
+#pragma unroll
+      for (int r = 0; r < 5; ++r) {
+        float wv[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) wv[k] = ws[r * 5 + s][q][k];
+#pragma unroll
+        for (int o = 0; o < DG_RSTEP; ++o)   // dy row h + o + 2 - r = ring row o + 4 - r of this trip
+#pragma unroll
+          for (int k = 0; k < 8; ++k) acc[o][k] = fmaf(d[o + 4 - r][k], wv[k], acc[o][k]);
+      }
+    }
+#pragma unroll
+    for (int o = 0; o < DG_RSTEP; ++o) {
+      float sum = ((acc[o][0] + acc[o][1]) + (acc[o][2] + acc[o][3])) + ((acc[o][4] + acc[o][5]) + (acc[o][6] + acc[o][7]));
+      sum += dpp_mov<0xB1>(sum);   // quad_perm [1,0,3,2]
+      sum += dpp_mov<0x4E>(sum);   // quad_perm [2,3,0,1]: every lane of the quad holds the pixel's total
+      if (q == 0 && w0 + p < W && h + o < h1) dx[((long)n * H + h + o) * W + w0 + p] = sum;
+    }
+    if (!more) break;
+    __syncthreads();   // every thread has read the rows this trip retires
+    park(h + DG_WIN - 2);
+    __syncthreads();
   }
 }
 
@@ -562,6 +676,33 @@ int ecg_conv5_in1_wgrad(int dtype, const float* x, const void* dy, float* dw, fl
   hipLaunchKernelGGL(conv5_in1_wgrad_reduce_kernel, dim3(ceil_div(IN1_ROW, 256)), dim3(256), 0, s, (const float*)ws, blocks,
                      dw, db, accumulate);
   ECG_CHECK_LAUNCH("conv5_in1_wgrad_reduce");
+  return 0;
+}
+
+// rows of a workgroup: the height in equal parts of at most DG_ROWS_MAX rows, rounded up to whole trips
+static int in1_dgrad_rows(int H) {
+  const int parts = ceil_div(H, DG_ROWS_MAX);
+  return ceil_div(ceil_div(H, parts), DG_RSTEP) * DG_RSTEP;
+}
+void ecg_conv5_in1_dgrad_tile(int H, int* strip, int* row_step, int* rows) {
+  if (strip) *strip = DG_STRIP;
+  if (row_step) *row_step = DG_RSTEP;
+  if (rows) *rows = H >= 1 ? in1_dgrad_rows(H) : 0;
+}
+int ecg_conv5_in1_dgrad(int dtype, const void* dy, const float* w, float* dx, int N, int H, int W, hipStream_t s) {
+  ECG_TRY(in1_check(dtype, N, H, W, "conv5_in1_bwd_data"));
+  if (!dy || !w || !dx) ECG_FAIL(ECGMM_ERR_SHAPE, "conv5_in1_bwd_data: dy, w and dx must not be null");
+  if ((uintptr_t)dy % 16) ECG_FAIL(ECGMM_ERR_SHAPE, "conv5_in1_bwd_data: dy must be 16-byte aligned");
+  const int strips = ceil_div(W, DG_STRIP), rows_per = in1_dgrad_rows(H), hchunks = ceil_div(H, rows_per);
+  const long blocks = (long)N * hchunks * strips;   // <= N H W <= 2^31 / 32 (in1_check)
+  const dim3 grid((unsigned)blocks);
+  if (dtype == ECGMM_BF16)
+    hipLaunchKernelGGL(conv5_in1_dgrad_kernel<bf16_t>, grid, dim3(IN1_THREADS), 0, s, (const bf16_t*)dy, w, dx, H, W, strips,
+                       hchunks, rows_per);
+  else
+    hipLaunchKernelGGL(conv5_in1_dgrad_kernel<float>, grid, dim3(IN1_THREADS), 0, s, (const float*)dy, w, dx, H, W, strips,
+                       hchunks, rows_per);
+  ECG_CHECK_LAUNCH("conv5_in1_dgrad");
   return 0;
 }
 

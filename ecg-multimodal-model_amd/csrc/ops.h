@@ -124,6 +124,11 @@ int ecg_bn_small_eval_bwd(const float* x, const float* dy, const float* gamma, c
 // gradcam.hip: relu(channel-weighted sum) / per-sample max, bilinear upsample (align_corners=False) to [N][H][W]
 int ecg_gradcam(int dtype, const void* act, const float* dpooled, float* small, float* out, int N, int Hs, int Ws, int C,
                 int H, int W, hipStream_t stream);
+// the same map from a gradient that varies over space (no global average pool in front of the head): the CRNN's
+// sequence layout seq / dseq [B][Tp][C * Fp]; ws = channel weights [B][C] | coarse map [B][Fp][Tp]
+size_t ecg_crnn_gradcam_workspace(int B, int Tp, int Fp, int C);
+int ecg_crnn_gradcam(const float* seq, const float* dseq, const int* steps, const int* frames, void* ws, size_t ws_bytes,
+                     float* cam, int B, int Tp, int C, int Fp, int F, int T, hipStream_t stream);
 int ecg_se_gate_bn(int dtype, const void* dout, const void* maskref, const void* y, const float* coef, void* dz,
                    float* dg, float* a1, float* a2, float* a3, int N, int R, int C, hipStream_t stream);
 int ecg_se_bn_nrows();   // rows ecg_se_bn_rows writes ([rows][2][C])
@@ -271,6 +276,9 @@ int ecg_conv5_in1_fwd(int dtype, const float* x, const float* w, const float* bi
 size_t ecg_conv5_in1_wgrad_workspace(int N, int H, int W);
 int ecg_conv5_in1_wgrad(int dtype, const float* x, const void* dy, float* dw, float* db, int accumulate, void* ws,
                         size_t ws_bytes, int N, int H, int W, hipStream_t s);
+// dx [N][H][W] fp32 from dy [N][H][W][32] (compute dtype, 16-byte aligned) and w [32][1][5][5]; every element written
+int ecg_conv5_in1_dgrad(int dtype, const void* dy, const float* w, float* dx, int N, int H, int W, hipStream_t s);
+void ecg_conv5_in1_dgrad_tile(int H, int* strip, int* row_step, int* rows);
 size_t ecg_conv5_wgrad_workspace(int dtype, const ConvGeom& g);
 int ecg_conv5_wgrad(int dtype, const ConvGeom& g, const void* x, const void* dy, float* dw, int accumulate, void* ws,
                     size_t ws_bytes, hipStream_t s);

@@ -149,11 +149,13 @@ int ecgmm_crnn_front_forward(const ecgmm_crnn_front_desc* d, const float* spec, 
   return 0;
 }
 
-int ecgmm_crnn_front_backward(const ecgmm_crnn_front_desc* d, const float* spec, const float* dseq, const void* const* params,
-                              void* const* grads, void* ws_fwd, void* ws_bwd, size_t ws_bwd_bytes, void* stream) {
+int ecgmm_crnn_front_backward_dx(const ecgmm_crnn_front_desc* d, const float* spec, const float* dseq,
+                                 const void* const* params, void* const* grads, void* ws_fwd, void* ws_bwd,
+                                 size_t ws_bwd_bytes, float* dspec, void* stream) {
   NetC n;
   ECG_TRY(netc_build(d, n, "crnn_front_backward"));
   if (!spec || !dseq || !params || !ws_fwd) ECG_FAIL(ECGMM_ERR_SHAPE, "crnn_front_backward: null operand");
+  if (dspec && !params[0]) ECG_FAIL(ECGMM_ERR_SHAPE, "crnn_front_backward: null parameter 0 (the input gradient reads conv1's weight)");
   const FwdC f = fwd_carve(n, ws_fwd);
   const BwdC b = bwd_carve(n, ws_bwd);
   ECG_NEED(ws_bwd, ws_bwd_bytes, b.bytes, "crnn_front_backward: workspace");
@@ -167,6 +169,7 @@ int ecgmm_crnn_front_backward(const ecgmm_crnn_front_desc* d, const float* spec,
     if (i == 0) {
       if (G(grads, 0) || G(grads, 1))   // (dbias was written above; the weight gradient alone here)
         ECG_TRY(ecg_conv5_in1_wgrad(dt, spec, b.dy[0], G(grads, 0), nullptr, 0, b.wg_ws, b.wg_bytes, B, k.h, k.w, s));
+      if (dspec) ECG_TRY(ecg_conv5_in1_dgrad(dt, b.dy[0], P(params, 0), dspec, B, k.h, k.w, s));
       break;
     }
     ECG_TRY(ecg_conv_igemm(dt, 1, k.geom(B), b.dy[i], f.wd[i], b.dx[i], nullptr, nullptr, nullptr, 0, s));
@@ -174,6 +177,11 @@ int ecgmm_crnn_front_backward(const ecgmm_crnn_front_desc* d, const float* spec,
       ECG_TRY(ecg_conv5_wgrad(dt, k.geom(B), f.pool[i - 1], b.dy[i], G(grads, k.p0), 0, b.wg_ws, b.wg_bytes, s));
   }
   return 0;
+}
+
+int ecgmm_crnn_front_backward(const ecgmm_crnn_front_desc* d, const float* spec, const float* dseq, const void* const* params,
+                              void* const* grads, void* ws_fwd, void* ws_bwd, size_t ws_bwd_bytes, void* stream) {
+  return ecgmm_crnn_front_backward_dx(d, spec, dseq, params, grads, ws_fwd, ws_bwd, ws_bwd_bytes, nullptr, stream);
 }
 
 }  // extern "C"

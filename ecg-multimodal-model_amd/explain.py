@@ -17,7 +17,13 @@ runs behind an eval-mode forward (csrc/plan_resnet18.hip, plan_resnet1d.hip, con
                          forward stored (csrc/attention.hip: ``ecgmm_mha_weights``);
   * ``attention_rollout`` the relevance of each input sample to the mean-pooled representation of an ``ECGTransformer1D``
                          with ``time_attention`` (Abnar & Zuidema 2020), one row vector per record and no S x S matrix
-                         (``ecgmm_mha_rollout_step``).
+                         (``ecgmm_mha_rollout_step``);
+  * ``spectrogram_gradients`` d (class logit) / d (log-spectrogram) of the ``CRNN`` of ``train_physionet2`` -- what
+                         ``spectrogram.requires_grad_()`` gives in the reference (train_physionet2.py:59, 70): the front
+                         end's plan returns the input gradient (csrc/crnn_front.hip: ``ecgmm_conv5_in1_bwd_data``);
+  * ``spectrogram_grad_cam`` the [B, F, T] map over the spectrogram from the CRNN's last ConvBlock.  No average pool
+                         stands in front of that head, so the gradient varies over space and is read
+                         (csrc/gradcam.hip: ``ecgmm_crnn_gradcam``); only the LSTM's and the head's backward run.
 Everything numeric runs in libecgmm_hip.so; there is no CPU path.
 """
 import os
@@ -170,6 +176,48 @@ def attention_rollout(model, x, lengths=None, residual=0.5):
         v = HF.attention_rollout_step(rec["qkv"], rec["lse"], v, rec["S"], rec["N"], rec["heads"], rec["batch_first"],
                                       rec["lengths"], residual)
     return v
+
+
+def _require_crnn(model, who):
+    if not all(hasattr(model, name) for name in ("conv1", "conv2", "conv3", "bilstm")):
+        raise ValueError(f"{who} needs a CRNN (a model with conv1..conv3 and a bilstm), got {type(model).__name__}")
+
+
+def spectrogram_gradients(model, x, lengths=None, target=None):
+    """d (logit of ``target``) / d ``x`` of a ``CRNN`` on log-spectrograms ``x [B, 1, F, T]`` -> ``[B, 1, F, T]`` fp32,
+    each record its own: which time and which frequency band carried the decision.  ``lengths`` as in ``CRNN.forward``
+    (the gradient just behind a record's end is not zero: the convolutions see the padding); ``target`` an int, a [B]
+    tensor, or None = the predicted class.  Eval mode, parameters frozen, no ``.grad`` touched: the chain of input
+    gradients alone runs (``ecgmm_crnn_front_backward_dx``), no weight gradient."""
+    _require_crnn(model, "spectrogram_gradients")
+    _require_cuda(x, "spectrogram_gradients input")
+    with _Frozen(model):
+        xs = x.detach().float().requires_grad_(True)
+        logits = model(xs) if lengths is None else model(xs, lengths)
+        (grad,) = torch.autograd.grad(logits, [xs], grad_outputs=_seed(logits, target))
+    return grad
+
+
+def spectrogram_grad_cam(model, x, lengths=None, target=None):
+    """Grad-CAM of a ``CRNN``'s last ConvBlock over the log-spectrogram ``x [B, 1, F, T]`` -> ``[B, F, T]`` fp32 in [0, 1],
+    exactly 0 at ``t >= lengths[b]``.  The front end runs without a graph; the graph starts at its output ``seq``, so only
+    the LSTM's, the mean's and the classifier's backward run, no convolution's.  There is no global average pool in front
+    of this head: the gradient varies over space and ``ecgmm_crnn_gradcam`` takes its mean per channel itself."""
+    from .hip import functional as HF
+    _require_crnn(model, "spectrogram_grad_cam")
+    _require_cuda(x, "spectrogram_grad_cam input")
+    with _Frozen(model):
+        with torch.no_grad():
+            seq = model._front(x)
+        seq = seq.detach().requires_grad_(True)
+        logits, steps = model._tail(seq, lengths, x.shape[3])
+        (dseq,) = torch.autograd.grad(logits, [seq], grad_outputs=_seed(logits, target))
+        frames = None
+        if lengths is not None:
+            frames = HF.check_lengths(lengths, x.shape[0], x.shape[3]).to(x.device)
+            frames = torch.clamp(frames, 1, x.shape[3]).to(torch.int32)
+        channels = model.conv3.block[0].weight.shape[0]
+        return HF.crnn_grad_cam(seq.detach(), dseq, steps, frames, x.shape[2], x.shape[3], channels)
 
 
 def overlay(image, cam, alpha=0.5):

@@ -640,7 +640,9 @@ def seq_mean(x, lengths=None):
 # --------------------------------------------------------------------------------------------
 class CRNNFrontFn(torch.autograd.Function):
     """seq [B, T/8, 128*(F/8)] = front end(x [B,1,F,T]; 12 params, 9 buffers).  Holds the forward workspace on ``ctx``; the
-    backward writes the parameter gradients into their sinks.  No input gradient: the spectrogram is data."""
+    backward writes the parameter gradients into their sinks, and returns d / d x when the spectrogram requires a gradient
+    (``ecgmm_crnn_front_backward_dx``: the Cin = 1 convolution's input gradient runs only then), behind a training-mode or
+    an eval-mode forward."""
 
     @staticmethod
     def forward(ctx, x, cfg, buffers, *params):
@@ -679,11 +681,48 @@ class CRNNFrontFn(torch.autograd.Function):
         sinks = [grad_sink(p) if ctx.needs_input_grad[3 + i] else None for i, p in enumerate(params)]
         nb = lib.ecgmm_crnn_front_bwd_workspace(C.byref(desc))
         bws = _Scratch.get("crnn_front_bwd", nb, dseq.device)
-        L.check(lib.ecgmm_crnn_front_backward(C.byref(desc), ptr(ctx.x), ptr(dseq), _ptr_table(params), _ptr_table(sinks),
-                                              ptr(ctx.ws), ptr(bws), bws.numel(), stream()), "crnn_front backward")
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(ctx.x)
+            L.check(lib.ecgmm_crnn_front_backward_dx(C.byref(desc), ptr(ctx.x), ptr(dseq), _ptr_table(params),
+                                                     _ptr_table(sinks), ptr(ctx.ws), ptr(bws), bws.numel(), ptr(dx), stream()),
+                    "crnn_front backward")
+        else:
+            L.check(lib.ecgmm_crnn_front_backward(C.byref(desc), ptr(ctx.x), ptr(dseq), _ptr_table(params), _ptr_table(sinks),
+                                                  ptr(ctx.ws), ptr(bws), bws.numel(), stream()), "crnn_front backward")
         if desc.training:
             ctx.ws = None
-        return (None, None, None) + (None,) * len(params)
+        return (dx, None, None) + (None,) * len(params)
+
+
+def crnn_grad_cam(seq, dseq, steps, frames, F, T, channels=128):
+    """Grad-CAM of the CRNN's last ConvBlock on the spectrogram (``ecgmm_crnn_gradcam``): ``seq``, ``dseq`` [B, Tp, C*Fp]
+    fp32 (the front end's output, the chosen logit's gradient w.r.t. it), ``steps`` / ``frames`` int32 [B] or None (live
+    steps 1..Tp, live spectrogram frames 1..T) -> ``[B, F, T]`` fp32 in [0, 1], exactly 0 at ``t >= frames[b]``."""
+    _require_cuda(seq, "crnn_grad_cam seq")
+    _require_cuda(dseq, "crnn_grad_cam dseq")
+    seq, dseq = f32c(seq), f32c(dseq)
+    if seq.dim() != 3 or seq.shape != dseq.shape or seq.shape[2] % channels:
+        raise ValueError(f"crnn_grad_cam: seq {tuple(seq.shape)} / dseq {tuple(dseq.shape)} must both be "
+                         f"[B, Tp, {channels}*Fp]")
+    B, Tp, Fp = seq.shape[0], seq.shape[1], seq.shape[2] // channels
+    tabs = []
+    for t, what in ((steps, "steps"), (frames, "frames")):
+        if t is not None:
+            _require_cuda(t, "crnn_grad_cam " + what)
+            if t.dtype != torch.int32 or t.shape != (B,):
+                raise ValueError(f"crnn_grad_cam: {what} must be int32 [{B}], got {t.dtype} {tuple(t.shape)}")
+            t = t.contiguous()
+        tabs.append(t)
+    lib = L.lib()
+    nb = lib.ecgmm_crnn_gradcam_workspace(B, Tp, Fp, channels)
+    if nb == 0:
+        L.check(1, "crnn_gradcam workspace query")
+    ws = _Scratch.get("crnn_gradcam", nb, seq.device)
+    cam = torch.empty(B, F, T, device=seq.device, dtype=torch.float32)
+    L.check(lib.ecgmm_crnn_gradcam(ptr(seq), ptr(dseq), ptr(tabs[0]), ptr(tabs[1]), ptr(ws), ws.numel(), ptr(cam), B, Tp,
+                                   channels, Fp, int(F), int(T), stream()), "crnn_gradcam")
+    return cam
 
 
 def crnn_front(x, params, buffers, training, momentum=0.1, eps=1e-5, dtype=L.F32):

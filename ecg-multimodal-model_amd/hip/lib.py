@@ -227,6 +227,11 @@ SIGNATURES = {
     "ecgmm_crnn_front_bwd_workspace": (sz, [P(CRNNFrontDesc)]),
     "ecgmm_crnn_front_forward": (i32, [P(CRNNFrontDesc), vp, P(vp), P(vp), vp, vp, sz, vp]),
     "ecgmm_crnn_front_backward": (i32, [P(CRNNFrontDesc), vp, vp, P(vp), P(vp), vp, vp, sz, vp]),
+    "ecgmm_crnn_front_backward_dx": (i32, [P(CRNNFrontDesc), vp, vp, P(vp), P(vp), vp, vp, sz, vp, vp]),
+    "ecgmm_conv5_in1_bwd_data": (i32, [i32, vp, vp, vp, i32, i32, i32, vp]),
+    "ecgmm_conv5_in1_bwd_data_tile": (None, [i32, P(i32), P(i32), P(i32)]),
+    "ecgmm_crnn_gradcam_workspace": (sz, [i32, i32, i32, i32]),
+    "ecgmm_crnn_gradcam": (i32, [vp, vp, vp, vp, vp, sz, vp, i32, i32, i32, i32, i32, i32, vp]),
     "ecgmm_log_spectrogram_frames": (i32, [i32, i32, i32]),
     "ecgmm_log_spectrogram": (i32, [vp, i32, i32, vp, i32, i32, vp, i32, vp]),
     "ecgmm_lime_perturb": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, u64, u64, vp, vp, vp, vp, vp]),
@@ -297,7 +302,10 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  # lengths in the attention kernels (csrc/attention.hip)
                  "ecgmm_mha_forward_varlen", "ecgmm_mha_backward_varlen",
                  # attention maps and the rollout step (ecgmm.explain.attention_maps / attention_rollout)
-                 "ecgmm_mha_weights", "ecgmm_mha_rollout_step")
+                 "ecgmm_mha_weights", "ecgmm_mha_rollout_step",
+                 # saliency of the spectrogram CRNN (ecgmm.explain.spectrogram_gradients / spectrogram_grad_cam)
+                 "ecgmm_crnn_front_backward_dx", "ecgmm_conv5_in1_bwd_data", "ecgmm_conv5_in1_bwd_data_tile",
+                 "ecgmm_crnn_gradcam_workspace", "ecgmm_crnn_gradcam")
 
 _lib = None
 

@@ -16,7 +16,8 @@ reader and label table, which this module reuses; the loader base, the epoch loo
 records at the end before the transform.  NEW: ``main(use_lengths=True)`` / ``config.physionet2_use_lengths`` hands each
 record's own frame count to ``CRNN.forward(x, lengths)``, so the BiLSTM stops where the record does and the mean over time
 leaves the padding out; each batch's rows are then ordered by length (:class:`DeviceSpectrogramLoader`).  Off by default:
-the reference runs through the padding.
+the reference runs through the padding.  NEW: ``main(saliency_samples=k)`` / ``config.physionet2_saliency_samples`` writes the
+input gradients and the Grad-CAM maps of the first ``k`` test spectrograms beside the checkpoints (off by default).
 """
 import numpy as np
 import torch
@@ -137,10 +138,16 @@ def evaluate(model, loader):
     return T.binary_metrics(y_true, y_prob[:, 1], y_pred)
 
 
-def main(config=Config, num_epochs=None, batch_size=None, quiet=False, use_lengths=False):
+def main(config=Config, num_epochs=None, batch_size=None, quiet=False, use_lengths=False, saliency_samples=0):
     """-> (history, {"best": metrics, "last": metrics}, checkpoint directory).  ``use_lengths`` or
-    ``config.physionet2_use_lengths`` (both off by default): the CRNN gets every record's own length (module docstring)."""
+    ``config.physionet2_use_lengths`` (both off by default): the CRNN gets every record's own length (module docstring).
+    ``saliency_samples=k`` > 0 (or ``config.physionet2_saliency_samples``): after the test pass, with the weights it ended
+    on, ``spectrogram_saliency.npz`` is written into the run directory for the first ``k`` test records
+    (:func:`write_spectrogram_saliency`).  The default 0 writes nothing."""
     use_lengths = bool(use_lengths or getattr(config, "physionet2_use_lengths", False))
+    saliency_samples = int(saliency_samples or getattr(config, "physionet2_saliency_samples", 0) or 0)
+    if saliency_samples < 0:
+        raise ValueError(f"saliency_samples={saliency_samples} must be >= 0")
     num_epochs = config.num_epochs if num_epochs is None else num_epochs
     batch_size = config.batch_size if batch_size is None else batch_size
     T.seed_all(config.seed, numpy=True)
@@ -176,7 +183,37 @@ def main(config=Config, num_epochs=None, batch_size=None, quiet=False, use_lengt
     if not quiet:
         for tag, res in results.items():
             print(f"test[{tag}]: {res}")
+    if saliency_samples:
+        path = write_spectrogram_saliency(model, test_loader.dataset, saliency_samples, ckpt_dir)
+        if not quiet:
+            print(f"spectrogram saliency of the first test records -> {path}")
     return history, results, ckpt_dir
+
+
+def write_spectrogram_saliency(model, dataset, k, out_dir):
+    """``spectrogram_saliency.npz`` in ``out_dir`` for the first ``k`` records of ``dataset`` (a
+    :class:`SpectrogramDataset`): ``grad_cam`` [k, F, T] and ``gradients`` [k, F, T] of the predicted class
+    (``ecgmm.explain.spectrogram_grad_cam`` / ``spectrogram_gradients``), ``frames`` [k] (T without frames in the dataset),
+    ``labels`` [k], ``probs`` [k, 2] -> the file's path"""
+    import os
+
+    from .explain import spectrogram_grad_cam, spectrogram_gradients
+    k = min(int(k), len(dataset))
+    x = dataset.spectrograms.index_select(0, dataset.indices[:k])
+    frames = None if dataset.frames is None else dataset.frames[:k]
+    was_training = model.training
+    model.eval()
+    with torch.no_grad():
+        logits = model(x) if frames is None else model(x, frames)
+    model.train(was_training)
+    target = logits.argmax(dim=1)       # one class for both maps
+    cam = spectrogram_grad_cam(model, x, frames, target)
+    grads = spectrogram_gradients(model, x, frames, target)
+    path = os.path.join(out_dir, "spectrogram_saliency.npz")
+    np.savez(path, grad_cam=cam.cpu().numpy(), gradients=grads[:, 0].cpu().numpy(),
+             frames=(np.full(k, x.shape[3], dtype=np.int32) if frames is None else dataset.frames_host[:k].numpy()),
+             labels=dataset.labels_host[:k].numpy(), probs=torch.softmax(logits.float(), dim=1).cpu().numpy())
+    return path
 
 
 if __name__ == "__main__":

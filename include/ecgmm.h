@@ -735,10 +735,19 @@ int ecgmm_conv5_in1_stats_rows(int N, int H, int W);
 int ecgmm_conv5_in1_fwd(int dtype, const float* x, const float* w_oihw, const float* bias, void* y, float* stats, int N, int H,
                         int W, void* stream);
 /* train_physionet2.py:59, 70 (its loss.backward()): dw_oihw [32,1,5,5] and dbias [32] fp32 (either nullable) from x and
- * dy [N,H,W,32] (compute dtype).  accumulate != 0 adds into both.  No input gradient: the spectrogram is data. */
+ * dy [N,H,W,32] (compute dtype).  accumulate != 0 adds into both.  The input gradient is ecgmm_conv5_in1_bwd_data. */
 size_t ecgmm_conv5_in1_bwd_weight_workspace(int N, int H, int W);
 int ecgmm_conv5_in1_bwd_weight(int dtype, const float* x, const void* dy, float* dw_oihw, float* dbias, int accumulate, void* ws,
                                size_t ws_bytes, int N, int H, int W, void* stream);
+/* train_physionet2.py:59, 70 (what spectrogram.requires_grad_() gives there): the input gradient
+ *   dx[n][h][w] = sum_{co < 32} sum_{r,s < 5} dy[n][h+2-r][w+2-s][co] * w[co][0][r][s],   taps outside the image dropped.
+ * dy [N,H,W,32] compute dtype (16-byte aligned), w_oihw [32,1,5,5] fp32 (rounded to bf16 under ECGMM_BF16, as the forward
+ * rounds it), dx [N,H,W] fp32 (Cin = 1: NCHW == NHWC, the spectrogram's own layout).  Products and sums are fp32 in a
+ * fixed order, no atomics; every element of dx is written.  Refused like ecgmm_conv5_in1_fwd: dtype, bad input, null.
+ * ecgmm_conv5_in1_bwd_data_tile: the kernel's tiling at height H (each nullable): columns of a strip, rows of a trip, rows
+ * of a workgroup -- for tests and tools that want shapes across its boundaries; needs no GPU. */
+int ecgmm_conv5_in1_bwd_data(int dtype, const void* dy, const float* w_oihw, float* dx, int N, int H, int W, void* stream);
+void ecgmm_conv5_in1_bwd_data_tile(int H, int* strip, int* row_step, int* rows);
 /* train_physionet2.py:59, 71-72 (their loss.backward()): weight gradient of a 5x5, stride 1, pad 2 convolution with Cin and
  * Cout multiples of 32: dw_oihw [Cout,Cin,5,5] fp32 from x [N,H,W,Cin] and dy [N,H,W,Cout] (compute dtype).  accumulate as
  * in ecgmm_conv_bwd_weight.  The workspace query needs no GPU and returns 0 on a descriptor it does not serve. */
@@ -777,9 +786,34 @@ size_t ecgmm_crnn_front_fwd_workspace(const ecgmm_crnn_front_desc* d);
 size_t ecgmm_crnn_front_bwd_workspace(const ecgmm_crnn_front_desc* d);
 int ecgmm_crnn_front_forward(const ecgmm_crnn_front_desc* d, const float* spec, const void* const* params,
                              void* const* buffers, float* seq_out, void* ws, size_t ws_bytes, void* stream);
-/* train_physionet2.py:55-65, 87-93 (their loss.backward()); no input gradient: the spectrogram is data */
+/* train_physionet2.py:55-65, 87-93 (their loss.backward()); the spectrogram's own gradient: ecgmm_crnn_front_backward_dx */
 int ecgmm_crnn_front_backward(const ecgmm_crnn_front_desc* d, const float* spec, const float* dseq, const void* const* params,
                               void* const* grads, void* ws_fwd, void* ws_bwd, size_t ws_bwd_bytes, void* stream);
+/* The same with the input gradient (train_physionet2.py:55-65, 87-93 with spectrogram.requires_grad_()): dspec [B,1,F,T]
+ * fp32, written whole.  dspec == NULL is ecgmm_crnn_front_backward: same launches, same bits.  Works behind a training-mode
+ * and an eval-mode forward; the workspace and its query are ecgmm_crnn_front_bwd_workspace's.  With every grads[i] NULL (or
+ * grads NULL) no weight-gradient kernel runs: the chain of input gradients alone. */
+int ecgmm_crnn_front_backward_dx(const ecgmm_crnn_front_desc* d, const float* spec, const float* dseq,
+                                 const void* const* params, void* const* grads, void* ws_fwd, void* ws_bwd,
+                                 size_t ws_bwd_bytes, float* dspec, void* stream);
+
+/* Grad-CAM of the CRNN's last ConvBlock on the spectrogram (csrc/gradcam.hip).  There is no global average pool in front of
+ * the CRNN's head, so the gradient varies over space and is an operand: seq, dseq [B][Tp][C*Fp] fp32 are the front end's
+ * output and the gradient of the chosen logit w.r.t. it, feature index c*Fp + f (permute(0,3,1,2) + Flatten(2) of the
+ * activation A[b][c][f][t], train_physionet2.py:92-93).
+ *   a[b][c]    = (1 / (Tp*Fp)) * sum_{t,f} dseq[b][t][c*Fp+f]                  (fixed order)
+ *   m[b][f][t] = relu(sum_c a[b][c] * seq[b][t][c*Fp+f]),  m[b] /= max m[b]     (a true division: the maximum becomes
+ *                exactly 1; all zero when the maximum is 0)
+ *   cam [B][F][T] = bilinear upsample of m from (Fp, Tp) to (F, T), align_corners=False
+ * steps (nullable, int32 [B], 1..Tp): the live steps of each record; only t < steps[b] is read from either operand (the
+ * variable-length LSTM leaves exact zeros behind it, so the sums are the same, and padded NaN is never touched) and m is
+ * exactly 0 behind it.  frames (nullable, int32 [B], 1..T): the live spectrogram frames; columns t >= frames[b] of cam are
+ * set to exactly 0.  Neither is range-checked on the device: values outside their range are the caller's error.
+ * ws: ecgmm_crnn_gradcam_workspace bytes (needs no GPU; 0 with the message set for extents < 1).  Refused with a message:
+ * null seq / dseq / cam, an extent < 1, a short workspace. */
+size_t ecgmm_crnn_gradcam_workspace(int B, int Tp, int Fp, int C);
+int ecgmm_crnn_gradcam(const float* seq, const float* dseq, const int32_t* steps, const int32_t* frames, void* ws,
+                       size_t ws_bytes, float* cam, int B, int Tp, int C, int Fp, int F, int T, void* stream);
 
 /* The log-spectrogram in front of the CRNN (train_physionet2.py:30-34): np.log1p(np.abs(scipy.signal.stft(x, fs, window,
  * nperseg=64, noverlap = 64 - hop)[2])) with scipy's defaults (boundary='zeros', padded=True, one-sided, scaling='spectrum',

@@ -2,7 +2,12 @@
 dtypes at B = 256, F = 33, T = 573, next to the same modules through torch / MIOpen on the same card.  Prints one JSON line.
 Warm-up first, then `--reps` repetitions timed with device events; the median is reported.
 `--spectrogram` times only the log-spectrogram launch at `--records` x `--length` samples, next to the reference's
-per-record scipy.signal.stft loop on the host, with the launch's algorithmic bytes and FLOP."""
+per-record scipy.signal.stft loop on the host, with the launch's algorithmic bytes and FLOP.
+`--saliency` times what the spectrogram's input gradient costs, per compute dtype at the same shape: the front
+end's plan backward without and with `dspec` (ecgmm_crnn_front_backward / _dx behind one training-mode forward, the two
+alternated rep by rep), ecgmm_conv5_in1_bwd_data alone on a dy of that shape, and a device copy of the same dy bytes (read
+once, written once) -- the floor of a kernel that must read dy once, measured in the same run and not taken from a data sheet.
+Under ECGMM_LIB naming a build without the input gradient only the plan backward is timed (an A/B of the unchanged path)."""
 import argparse
 import json
 import os
@@ -51,6 +56,76 @@ def spectrogram(a):
     print(json.dumps(out))
 
 
+def saliency(a):
+    import ctypes as C
+
+    from ecgmm.crnn import CRNN
+    from ecgmm.hip import functional as HF
+    from ecgmm.hip import lib as L
+    ptr, stream = HF.ptr, HF.stream
+    dev = torch.device("cuda:0")
+    lib = L.lib()
+    B, Fq, T = a.batch, a.F, a.T
+    x = torch.randn(B, 1, Fq, T, device=dev)
+    has_dx = hasattr(C.CDLL(L.LIB_PATH), "ecgmm_crnn_front_backward_dx")
+    out = {"shape": [B, Fq, T], "device": torch.cuda.get_device_name(0), "reps": a.reps, "lib": os.path.basename(L.LIB_PATH)}
+    for cd in ("bf16", "fp32"):
+        net = CRNN(compute_dtype=cd).to(dev).train()
+        params, buffers = net._front_tables()
+        desc = L.CRNNFrontDesc(B, Fq, T, net._dtype, 1, 0.1, 1e-5)
+        ws = HF.new_bytes(lib.ecgmm_crnn_front_fwd_workspace(C.byref(desc)), dev)
+        bws = HF.new_bytes(lib.ecgmm_crnn_front_bwd_workspace(C.byref(desc)), dev)
+        seq = torch.empty(B, T // 8, 128 * (Fq // 8), device=dev)
+        L.check(lib.ecgmm_crnn_front_forward(C.byref(desc), ptr(x), HF._ptr_table(params), HF._ptr_table(buffers), ptr(seq),
+                                             ptr(ws), ws.numel(), stream()), "crnn_front forward")
+        g = torch.randn_like(seq)
+        sinks = [torch.empty_like(p) for p in params]
+        dspec = torch.empty_like(x)
+        ptab, gtab = HF._ptr_table(params), HF._ptr_table(sinks)
+        esz = 2 if cd == "bf16" else 4
+        dy = torch.randn(B * Fq * T * 32, device=dev).to(torch.bfloat16 if cd == "bf16" else torch.float32)
+        dy2, dx = torch.empty_like(dy), torch.empty(B, Fq, T, device=dev)
+        w = params[0].detach()
+
+        def bwd():
+            L.check(lib.ecgmm_crnn_front_backward(C.byref(desc), ptr(x), ptr(g), ptab, gtab, ptr(ws), ptr(bws), bws.numel(),
+                                                  stream()), "crnn_front backward")
+
+        def bwd_dx():
+            L.check(lib.ecgmm_crnn_front_backward_dx(C.byref(desc), ptr(x), ptr(g), ptab, gtab, ptr(ws), ptr(bws), bws.numel(),
+                                                     ptr(dspec), stream()), "crnn_front backward_dx")
+
+        def kernel():
+            L.check(lib.ecgmm_conv5_in1_bwd_data(net._dtype, ptr(dy), ptr(w), ptr(dx), B, Fq, T, stream()), "conv5_in1_bwd_data")
+
+        def copy():
+            dy2.copy_(dy)
+        fns = {"front_bwd": bwd, "front_bwd_dx": bwd_dx, "conv5_in1_bwd_data": kernel, "copy_dy": copy}
+        if not has_dx:      # an ECGMM_LIB build from before the input gradient: the plan backward alone, for an A/B of it
+            fns = {"front_bwd": bwd}
+        for _ in range(a.warmup):
+            for fn in fns.values():
+                fn()
+        torch.cuda.synchronize()
+        ms = {k: [] for k in fns}
+        for _ in range(a.reps):            # alternated rep by rep: drift hits every variant alike
+            for k, fn in fns.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); fn(); e1.record()
+                torch.cuda.synchronize()
+                ms[k].append(e0.elapsed_time(e1))
+        r = {k: {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v)} for k, v in ms.items()}
+        out[cd] = r
+        if not has_dx:
+            continue
+        r["dy_bytes"] = dy.numel() * esz
+        r["dy_GB_per_s_kernel"] = r["dy_bytes"] / r["conv5_in1_bwd_data"]["median_ms"] / 1e6
+        r["dy_GB_per_s_copy_read"] = r["dy_bytes"] / r["copy_dy"]["median_ms"] / 1e6
+        r["kernel_over_copy"] = r["conv5_in1_bwd_data"]["median_ms"] / r["copy_dy"]["median_ms"]
+        r["fma_TFLOP_per_s"] = 2 * 800 * B * Fq * T / r["conv5_in1_bwd_data"]["median_ms"] / 1e9
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
@@ -59,11 +134,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--spectrogram", action="store_true")
+    ap.add_argument("--saliency", action="store_true")
     ap.add_argument("--records", type=int, default=1024)
     ap.add_argument("--length", type=int, default=18286)
     a = ap.parse_args()
     if a.spectrogram:
         return spectrogram(a)
+    if a.saliency:
+        return saliency(a)
     from ecgmm.crnn import CRNN
     from ecgmm.hip import functional as HF
     from ecgmm.optim import FusedAdam
