@@ -65,3 +65,4 @@ class Config:
     physionet2_saliency_samples = 0  # train_physionet2: input gradients + Grad-CAM of the first k test spectrograms (npz)
     physionet_time_attention = False  # train_physionet, model="transformer": attend along the positions (batch_first=True)
     physionet_use_lengths = False     # train_physionet, with time attention: each record's own length to the encoder and the mean
+    physionet_target_fs = None        # train_physionet(_multi, 2): resample records whose header names another rate to this one

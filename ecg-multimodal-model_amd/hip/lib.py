@@ -173,6 +173,9 @@ SIGNATURES = {
     "ecgmm_weighted_sample": (i32, [vp, i64, i64, vp, vp, i64, u64, u64, vp]),
     "ecgmm_signal_filter_zscore": (i32, [vp, vp, i32, i32, P(f64), P(f64), P(f64), i32, i32, f64, vp]),
     "ecgmm_signal_filter_lanes": (i32, [P(f64), i32, i32]),
+    "ecgmm_signal_resample_len": (i32, [i32, f64]),
+    "ecgmm_signal_resample_workspace": (sz, [i32, i32, i32]),
+    "ecgmm_signal_resample": (i32, [vp, i32, i32, vp, i32, f64, vp, i32, vp, vp, sz, vp]),
     "ecgmm_signal_gather_augment": (i32, [vp, i64, i32, vp, i32, vp, vp, i32, f32, f32, f32, f32, i32, i32, u64, u64, vp]),
     "ecgmm_glu_fwd": (i32, [vp, vp, i64, i32, vp]),
     "ecgmm_glu_bwd": (i32, [vp, vp, vp, i64, i32, vp]),
@@ -305,7 +308,9 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  "ecgmm_mha_weights", "ecgmm_mha_rollout_step",
                  # saliency of the spectrogram CRNN (ecgmm.explain.spectrogram_gradients / spectrogram_grad_cam)
                  "ecgmm_crnn_front_backward_dx", "ecgmm_conv5_in1_bwd_data", "ecgmm_conv5_in1_bwd_data_tile",
-                 "ecgmm_crnn_gradcam_workspace", "ecgmm_crnn_gradcam")
+                 "ecgmm_crnn_gradcam_workspace", "ecgmm_crnn_gradcam",
+                 # Fourier resampling (ecgmm.preprocess.resample, csrc/resample.hip)
+                 "ecgmm_signal_resample_len", "ecgmm_signal_resample_workspace", "ecgmm_signal_resample")
 
 _lib = None
 

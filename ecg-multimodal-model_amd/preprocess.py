@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from .hip import lib as L
-from .hip.functional import _PhiloxState, _Scratch, _require_cuda, ptr, stream
+from .hip.functional import _PhiloxState, _Scratch, _require_cuda, check_lengths, ptr, stream
 from .training import ResidentLoader
 
 
@@ -77,6 +77,62 @@ def filter_zscore(x, b, a, zscore=True, eps=1e-8):
     L.check(L.lib().ecgmm_signal_filter_zscore(ptr(x2), ptr(out), S, Ln, dbl(b), dbl(a), dbl(zi), n - 1, int(bool(zscore)),
                                                float(eps), stream()), "signal_filter_zscore")
     return out.reshape(shape)
+
+
+def resample_len(n, ratio):
+    """Samples of a record of ``n`` samples resampled by ``ratio = target_fs / orig_fs``: the library's
+    ``(int)((double)n * ratio)``, which is the reference's ``int(len(signal) * (target_fs / orig_fs))``.  Needs no GPU."""
+    r = L.lib().ecgmm_signal_resample_len(int(n), float(ratio))
+    if r < 0:
+        raise ValueError(L.lib().ecgmm_last_error().decode())
+    return r
+
+
+def resample(x, num=None, *, ratio=None, lengths=None):
+    """``scipy.signal.resample(x, num)`` (Fourier method) per record of a CUDA float tensor [..., L]: fp64 arithmetic, fp32
+    result, deterministic (csrc/resample.hip; train_physionet.py:35-39).  Exactly one of ``num`` and ``ratio``:
+
+    ``num``                 every record goes L -> num; -> [..., num].  ``num == L`` returns the records' own bits.
+    ``ratio``               every record goes L -> ``resample_len(L, ratio)``.
+    ``ratio`` + ``lengths`` one length per record (``HF.check_lengths``): record s is resampled over its own first
+                            ``lengths[s]`` samples (the rest of the row is never read) to ``resample_len(lengths[s], ratio)``
+                            samples, followed by exact zeros; -> ([..., T_out], out_lengths int32 on the device),
+                            ``T_out = resample_len(L, ratio)``.
+    L and the output length are at most 65536."""
+    if (num is None) == (ratio is None):
+        raise ValueError("resample: give exactly one of num and ratio")
+    if lengths is not None and ratio is None:
+        raise ValueError("resample: lengths needs ratio (every record gets its own number of samples)")
+    if x.dim() < 1 or x.shape[-1] < 1 or x.numel() < 1:
+        raise ValueError(f"resample: x must be [..., L] with L >= 1 and at least one record, got {tuple(x.shape)}")
+    _require_cuda(x, "resample")
+    shape = x.shape
+    x2 = x.reshape(-1, shape[-1]).float().contiguous()
+    S, Ln = x2.shape
+    if ratio is not None:
+        ratio = float(ratio)
+        if not (np.isfinite(ratio) and ratio > 0):
+            raise ValueError(f"resample: ratio={ratio} must be finite and > 0")
+        T_out = resample_len(Ln, ratio)
+    else:
+        T_out = int(num)
+    if T_out < 1:
+        raise ValueError(f"resample: the output needs at least one sample (L={Ln}, num={T_out})")
+    lens = None
+    if lengths is not None:
+        lens = check_lengths(lengths, S, Ln).to(x2.device).contiguous()
+    lib = L.lib()
+    nb = lib.ecgmm_signal_resample_workspace(S, Ln, T_out)
+    if nb == 0:
+        raise ValueError(lib.ecgmm_last_error().decode())
+    ws = _Scratch.get("resample", nb, x2.device)
+    out = torch.empty(S, T_out, dtype=torch.float32, device=x2.device)
+    out_len = torch.empty(S, dtype=torch.int32, device=x2.device) if lens is not None else None
+    L.check(lib.ecgmm_signal_resample(ptr(x2), S, Ln, ptr(lens), 0 if lens is not None else T_out,
+                                      ratio if lens is not None else 0.0, ptr(out), T_out, ptr(out_len), ptr(ws), ws.numel(),
+                                      stream()), "signal_resample")
+    out = out.reshape(*shape[:-1], T_out)
+    return out if lens is None else (out, out_len.reshape(shape[:-1]))
 
 
 def lfilter_zi(b, a):

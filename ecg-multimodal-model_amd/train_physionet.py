@@ -14,8 +14,10 @@ This module holds the model alternative, the device pre-processing, the record r
 the policy values; the epoch loop, the checkpoint test loop and the metrics are ``ecgmm.training``'s, the gather launch is
 ``ecgmm.preprocess.gather_augment``.
 
-Not carried over: ``resample_signal`` (the reference never reaches it: ``orig_fs == target_fs`` at its only call site),
-plots.  ``wfdb`` is replaced by :func:`read_record`, ``keras`` by :func:`pad_sequences`.
+``resample_signal`` (train_physionet.py:35-39) is :func:`resample_signal` on the device (``ecgmm.preprocess.resample``,
+csrc/resample.hip); the reference's three steps for unequal rates are :func:`preprocess_resampled`, and
+``load_records(target_fs=...)`` moves every record whose header names another sampling rate to ``target_fs`` before it is
+padded.  Not carried over: plots.  ``wfdb`` is replaced by :func:`read_record`, ``keras`` by :func:`pad_sequences`.
 """
 import csv
 import os
@@ -139,11 +141,36 @@ def bandpass_filter(signal, lowcut=16, highcut=149, fs=300, order=4):
 def preprocess_signal(raw_signal, orig_fs=300, target_fs=300):
     """bandpass_filter -> z_score_normalize in one launch.  raw_signal: CUDA float tensor [..., L]."""
     if orig_fs != target_fs:
-        raise NotImplementedError("preprocess_signal: resample_signal (orig_fs != target_fs) is not part of this path; the "
-                                  "reference never reaches it (train_physionet.py:81 passes 300 / 300)")
+        raise NotImplementedError("preprocess_signal: this is the one-launch filter + z-score of equal rates; for "
+                                  "orig_fs != target_fs use preprocess_resampled (band-pass, resample_signal, z-score) or "
+                                  "resample_signal itself")
     _require_cuda(raw_signal, "preprocess_signal")
     b, a = _band(16, 149, orig_fs, 4)
     return PP.filter_zscore(raw_signal, b, a, zscore=True, eps=1e-8)
+
+
+def _rate_ratio(orig_fs, target_fs):
+    if not (np.isfinite(orig_fs) and np.isfinite(target_fs) and orig_fs > 0 and target_fs > 0):
+        raise ValueError(f"resample_signal: sampling rates must be finite and > 0 (orig_fs={orig_fs}, target_fs={target_fs})")
+    return target_fs / orig_fs      # in Python floats, as the reference writes it
+
+
+def resample_signal(signal, orig_fs, target_fs=300):
+    """train_physionet.py:35-39 per record of a CUDA tensor [..., L]: ``signal`` itself when the rates are equal, else
+    ``scipy.signal.resample(signal, int(L * (target_fs / orig_fs)))`` (``ecgmm.preprocess.resample``: fp64 inside)."""
+    if orig_fs == target_fs:
+        return signal
+    ratio = _rate_ratio(orig_fs, target_fs)
+    _require_cuda(signal, "resample_signal")
+    return PP.resample(signal, ratio=ratio)
+
+
+def preprocess_resampled(raw_signal, orig_fs, target_fs=300):
+    """The reference's three steps for unequal rates (train_physionet.py:41-45): bandpass_filter at ``orig_fs`` ->
+    resample_signal -> z_score_normalize.  raw_signal: CUDA float tensor [..., L] -> [..., int(L * (target_fs / orig_fs))]."""
+    _require_cuda(raw_signal, "preprocess_resampled")
+    filtered = bandpass_filter(raw_signal, 16, 149, orig_fs, 4)
+    return z_score_normalize(resample_signal(filtered, orig_fs, target_fs))
 
 
 def augment_signal(signal, **kw):
@@ -206,6 +233,19 @@ def read_record(path):
     return ((val - np.array(baselines, dtype=np.float64)[:, None]) / np.array(gains)[:, None]).T
 
 
+def read_fs(path):
+    """Sampling frequency of one record: field 3 of the first line of ``NAME.hea`` (``NAME nsig fs[/counter] nsamp ...``);
+    ``None`` for a ``.npy`` record, which carries none."""
+    if path.endswith(".npy") or (not os.path.exists(path + ".hea") and os.path.exists(path + ".npy")):
+        return None
+    with open(path + ".hea") as f:
+        lines = [ln.strip() for ln in f if ln.strip() and not ln.startswith("#")]
+    fld = lines[0].split()
+    if len(fld) < 3:
+        return 250.0                # WFDB's default where the record line names no frequency
+    return float(fld[2].split("/")[0])
+
+
 def read_labels(label_file, label_map=LABEL_MAP):
     """REFERENCE.csv (``record,label``, no header) -> [(record, class)] for the labels in ``label_map``; the rest ('~') dropped."""
     rows = []
@@ -237,20 +277,49 @@ def synthetic_records(config=Config, label_map=LABEL_MAP):
     return signals, np.array(labels, dtype=np.int64)
 
 
-def load_records(config=Config, label_map=LABEL_MAP, quiet=True):
+def load_records(config=Config, label_map=LABEL_MAP, quiet=True, target_fs=None):
     """-> (list of 1-D float64 signals, int64 labels): lead 0 of every record of REFERENCE.csv that loads
-    (train_physionet.py:91-109; a record that fails to load is skipped with a warning)."""
+    (train_physionet.py:91-109; a record that fails to load is skipped with a warning).
+    ``target_fs=None``: the records as they are read (host code only).  A number: every record whose header (:func:`read_fs`)
+    names another sampling rate is resampled over its own length to ``int(len * (target_fs / fs))`` samples on
+    ``config.device`` (:func:`resample_records`); the synthetic records and ``.npy`` records carry no rate and stay."""
     if getattr(config, "synthetic", False):
         return synthetic_records(config, label_map)
-    signals, labels = [], []
+    signals, labels, rates = [], [], []
     for name, lab in read_labels(config.physionet_label_file, label_map):
         try:
-            signals.append(read_record(os.path.join(config.physionet_data_dir, name))[:, 0])
+            path = os.path.join(config.physionet_data_dir, name)
+            signals.append(read_record(path)[:, 0])
             labels.append(lab)
+            rates.append(None if target_fs is None else read_fs(path))
         except Exception as e:   # noqa: BLE001 -- as the reference: any failure skips the record
             if not quiet:
                 print(f"Warning: Failed to load record {name}: {e}")
+    if target_fs is not None:
+        signals = resample_records(signals, rates, target_fs, torch.device(config.device))
     return signals, np.array(labels, dtype=np.int64)
+
+
+def resample_records(signals, rates, target_fs, device, chunk=256):
+    """Every record i with ``rates[i]`` neither ``None`` nor ``target_fs`` -> ``resample_signal`` over its own length, the
+    others untouched.  Records of one rate go up in chunks of ``chunk`` rows, zero-padded to the chunk's longest record, and
+    come back through the lengths form of ``ecgmm.preprocess.resample`` as float64 numpy like the rest."""
+    out = list(signals)
+    by_rate = {}
+    for i, fs in enumerate(rates):
+        if fs is not None and fs != target_fs and len(signals[i]) > 0:
+            by_rate.setdefault(fs, []).append(i)
+    for fs, idx in sorted(by_rate.items()):
+        ratio = _rate_ratio(fs, target_fs)
+        for c0 in range(0, len(idx), chunk):
+            part = idx[c0:c0 + chunk]
+            lens = [len(signals[i]) for i in part]
+            rows = pad_sequences([signals[i] for i in part], maxlen=max(lens), dtype="float32")
+            y, n = PP.resample(torch.from_numpy(rows).to(device), ratio=ratio, lengths=lens)
+            y, n = y.cpu().numpy(), n.cpu().numpy()
+            for row, i in enumerate(part):
+                out[i] = y[row, :n[row]].astype(np.float64)
+    return out
 
 
 # --------------------------------------------------------------------------------------------
@@ -312,11 +381,11 @@ class DeviceSignalLoader(T.ResidentLoader):
 
 
 def get_signalonly_dataloaders(config=Config, batch_size=8, label_map=LABEL_MAP, augment=True, split=SPLIT, max_len=MAX_LEN,
-                               use_lengths=False):
+                               use_lengths=False, target_fs=None):
     """train / val / test :class:`DeviceSignalLoader` (train_physionet.py:89-132; batch 8, only the train split shuffled).
     ``use_lengths``: the datasets carry every record's ``min(len(record), max_len)`` and the loaders yield
-    ``((signals, lengths), labels)``."""
-    signals, labels = load_records(config, label_map)
+    ``((signals, lengths), labels)``.  ``target_fs``: :func:`load_records`."""
+    signals, labels = load_records(config, label_map, **({} if target_fs is None else {"target_fs": target_fs}))
     train_idx, val_idx, test_idx = split_indices(labels, config.seed, split)
     device = torch.device(config.device)
     mk = lambda idx, name: SignalOnlyDataset(idx, labels, signals, augment=augment, max_len=max_len, split=name, device=device,
@@ -349,7 +418,7 @@ def evaluate(model, loader, num_classes=2, predictor=None):
 
 def main(config=Config, num_epochs=30, batch_size=8, quiet=False, use_predictor=False, num_classes=2, label_map=LABEL_MAP,
          augment=True, split=SPLIT, model="resnet", max_len=MAX_LEN, time_attention=False, use_lengths=False,
-         rollout_samples=0):
+         rollout_samples=0, target_fs=None):
     """``model``: ``"resnet"`` (the reference's choice) or ``"transformer"`` (its commented alternative, :276); ``max_len``:
     the length every record is padded or cut to.
     ``use_predictor``: run the validation and test passes through an ``ecgmm.inference.Predictor`` (BatchNorm-folded
@@ -363,10 +432,13 @@ def main(config=Config, num_epochs=30, batch_size=8, quiet=False, use_predictor=
     it ended on, ``attention_rollout.npz`` is written into the run directory for the first ``k`` test records:
     ``relevance`` [k, L] (``ecgmm.explain.attention_rollout``), ``lengths`` [k] (``max_len`` without ``use_lengths``),
     ``labels`` [k] and ``probs`` [k, classes].  The default 0 writes nothing.
+    ``target_fs`` or ``config.physionet_target_fs`` (default ``None``: records as read): every record whose header names
+    another sampling rate is resampled to it on the device before padding (:func:`load_records`).
     -> (history, {"best": metrics, "last": metrics}, checkpoint directory)."""
     time_attention = bool(time_attention or getattr(config, "physionet_time_attention", False))
     use_lengths = bool(use_lengths or getattr(config, "physionet_use_lengths", False))
     rollout_samples = int(rollout_samples)
+    target_fs = target_fs if target_fs is not None else getattr(config, "physionet_target_fs", None)
     if rollout_samples < 0:
         raise ValueError(f"rollout_samples={rollout_samples} must be >= 0")
     if rollout_samples and not (model == "transformer" and time_attention):
@@ -381,7 +453,8 @@ def main(config=Config, num_epochs=30, batch_size=8, quiet=False, use_predictor=
     if not quiet:
         print(f"Using device: {device}")
     train_loader, val_loader, test_loader = get_signalonly_dataloaders(config, batch_size, label_map, augment, split, max_len,
-                                                                       **({"use_lengths": True} if use_lengths else {}))
+                                                                       **({"use_lengths": True} if use_lengths else {}),
+                                                                       **({} if target_fs is None else {"target_fs": target_fs}))
     if use_predictor and model != "resnet":
         raise ValueError("use_predictor=True needs model='resnet' (the inference plan is the ResNet1D_SE's)")
     model = build_model(model, num_classes, config, max_len, **({"time_attention": True} if time_attention else {})).to(device)

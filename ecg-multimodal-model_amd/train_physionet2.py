@@ -110,12 +110,14 @@ class DeviceSpectrogramLoader(T.ResidentLoader):
 
 
 def get_spectrogram_dataloaders(config=Config, batch_size=None, label_map=LABEL_MAP, split=SPLIT, chunk=1024,
-                                use_lengths=False):
+                                use_lengths=False, target_fs=None):
     """train / val / test :class:`DeviceSpectrogramLoader` over one resident tensor (train_physionet2.py:128-165): labels
     N -> 0, AF / O -> 1, '~' dropped; stratified 80 / 10 / 10 with ``config.seed``; only the train split is shuffled.
-    ``use_lengths``: the datasets carry :func:`spectrogram_frames` and the loaders yield ``((spec, frames), labels)``."""
+    ``use_lengths``: the datasets carry :func:`spectrogram_frames` and the loaders yield ``((spec, frames), labels)``.
+    ``target_fs`` (or ``config.physionet_target_fs``): ``train_physionet.load_records``."""
     batch_size = config.batch_size if batch_size is None else batch_size
-    signals, labels = load_records(config, label_map)
+    target_fs = target_fs if target_fs is not None else getattr(config, "physionet_target_fs", None)
+    signals, labels = load_records(config, label_map, **({} if target_fs is None else {"target_fs": target_fs}))
     max_len = getattr(config, "physionet2_max_len", None)
     if max_len is not None:
         signals = [s[:max_len] for s in signals]

@@ -27,13 +27,15 @@ def find_best_threshold(y_true, y_prob, num_classes=3):
     return best_t
 
 
-def get_signalonly_dataloaders(config=Config, batch_size=8):
-    return TP.get_signalonly_dataloaders(config, batch_size, label_map=LABEL_MAP, augment=False, split=SPLIT)
+def get_signalonly_dataloaders(config=Config, batch_size=8, target_fs=None):
+    return TP.get_signalonly_dataloaders(config, batch_size, label_map=LABEL_MAP, augment=False, split=SPLIT,
+                                         **({} if target_fs is None else {"target_fs": target_fs}))
 
 
-def main(config=Config, num_epochs=30, batch_size=8, quiet=False, use_predictor=False):
+def main(config=Config, num_epochs=30, batch_size=8, quiet=False, use_predictor=False, target_fs=None):
+    """``target_fs`` (or ``config.physionet_target_fs``): ``train_physionet.load_records``."""
     return TP.main(config, num_epochs, batch_size, quiet, use_predictor, num_classes=3, label_map=LABEL_MAP, augment=False,
-                   split=SPLIT)
+                   split=SPLIT, **({} if target_fs is None else {"target_fs": target_fs}))
 
 
 if __name__ == "__main__":

@@ -558,6 +558,32 @@ int ecgmm_signal_filter_zscore(const float* x, float* out, int S, int L, const d
  * pass) is chosen on the host from (a, L) alone.  This returns the nl those entry points use for a record of L samples
  * (needs no GPU); 0 with the message set for a null a, a[0] != 1, an order outside 1..8 or L < 1. */
 int ecgmm_signal_filter_lanes(const double* a, int order, int L);
+/* resample_signal (train_physionet.py:35-39, train_physionet_multi.py:32-36) = scipy.signal.resample(x, num), the Fourier
+ * method, for a whole [S][L] fp32 matrix (csrc/resample.hip): with X = rfft(x), m = min(N, num), K = m / 2 + 1,
+ *   y[j] = (X[0] + sum_{1 <= k < K} w_k 2 Re(X[k] e^{2 pi i k j / num})) / N,
+ * w_k = 1 except at k = m / 2 with m even, where the term is 2 Re X[k] (-1)^j (num < N) or Re X[k] cos(2 pi k j / num)
+ * (num > N).  Two direct sums in fp64 through the workspace X [S][min(L, T_out) / 2 + 1] complex doubles, fp32 result; every
+ * sum in a fixed order, no atomics: two calls give the same bits, and a row's bits depend on that row alone (not on S, its
+ * neighbours or L).  num == N copies the row bit for bit.  Accuracy: tests/resample_bounds.py.
+ *   without lengths  every row goes L -> num (1 <= num <= T_out); ratio is ignored; out_lengths must be null
+ *   with lengths     device int32 [S], clamped to [0, L] on the device: row s is resampled over its first N_s = lengths[s]
+ *                    samples to num_s = (int)((double)N_s * ratio) samples, ratio = target_fs / orig_fs as a double, which
+ *                    is Python's int(len * (target_fs / orig_fs)); num must be 0 and T_out >= (int)(L * ratio);
+ *                    out_lengths (nullable, device int32 [S]) receives num_s; x at and beyond N_s is never read (NaN allowed)
+ * out [S][T_out] is exactly 0 from num_s on; a row with N_s = 0 or num_s = 0 is all zeros.  With all lengths equal to L the
+ * bits are those of the call without lengths and num = (int)(L * ratio).
+ * Needs S >= 1 and 1 <= L, T_out <= 65536, a 16-byte aligned workspace of ecgmm_signal_resample_workspace bytes (no GPU
+ * needed; 0 with the message set when refused), a finite ratio > 0 with lengths; anything else (null x / out / ws included)
+ * is ECGMM_ERR_SHAPE before any launch, and nothing is written.
+ * ecgmm_signal_resample_len (no GPU needed): (int)((double)n * ratio), the length of the resampled record; -1 with the
+ * message set for n < 0, a ratio that is not finite and > 0, or a result beyond an int. */
+/* train_physionet.py:35-39: num = int(len(signal) * (target_fs / orig_fs)) */
+int ecgmm_signal_resample_len(int n, double ratio);
+/* train_physionet.py:35-39 */
+size_t ecgmm_signal_resample_workspace(int S, int L, int T_out);
+/* train_physionet.py:35-39: resample(signal, num) */
+int ecgmm_signal_resample(const float* x, int S, int L, const int32_t* lengths, int num, double ratio, float* out, int T_out,
+                          int32_t* out_lengths, void* ws, size_t ws_bytes, void* stream);
 /* The per-step batch gather fused with augment_signal (train_physionet.py:47-60): out[i][:] = augment(src[index[i]][:]),
  * src [n][L] fp32, index int64 [B], out [B][L] fp32.  augment = 0: the plain gather.  augment = 1, per row i: three
  * Bernoulli(p) decisions in the reference's order -- add N(0, sigma^2) noise per sample point; multiply by a uniform on

@@ -7,7 +7,9 @@ calls, medians of the per-call round means --
 and the reference pipeline restated with scipy / numpy per sample (filtfilt + z-score; augment_signal) on the host's
 CPUs (a pool of --cpus processes, as DataLoader workers would run it) as the baseline for (a) and (b).
 Writes profiles/physionet_bench.json and prints it.  --front-only: (a) and (d) alone, the two filtfilt launches, printed and
-not written (an A/B of two builds of the library: ECGMM_LIB selects the build)."""
+not written (an A/B of two builds of the library: ECGMM_LIB selects the build).  --resample: the Fourier resampler alone
+(DESIGN section 29), 5000 -> 3000 at S = 256 and the lengths form on the synthetic records' lengths (2000 .. 18000, ratio
+0.6), 3 rounds x 3 calls, next to scipy.signal.resample on the same rows in one host process; written to --out."""
 import argparse
 import json
 import os
@@ -63,19 +65,19 @@ def cpu_baseline(kind, n_per_proc, procs):
     return wall / (n_per_proc * procs)
 
 
-def timed(fn, torch):
-    for _ in range(3):
+def timed(fn, torch, rounds=ROUNDS, calls=CALLS, warm=3):
+    for _ in range(warm):
         fn()
     torch.cuda.synchronize()
     per_call = []
-    for _ in range(ROUNDS):
+    for _ in range(rounds):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        for _ in range(CALLS):
+        for _ in range(calls):
             fn()
         e1.record()
         torch.cuda.synchronize()
-        per_call.append(e0.elapsed_time(e1) / CALLS)
+        per_call.append(e0.elapsed_time(e1) / calls)
     return {"ms_median": round(statistics.median(per_call), 5), "ms_min": round(min(per_call), 5),
             "ms_max": round(max(per_call), 5)}
 
@@ -88,12 +90,51 @@ def with_floor(r, nbytes):
     return r
 
 
+def resample_bench(torch, dev):
+    """the resampler's one-time cost: device milliseconds per call, twiddle products per second, and scipy on the host"""
+    from scipy.signal import resample
+    from ecgmm import preprocess as PP
+    res = {"rounds": 3, "calls_per_round": 3, "device": torch.cuda.get_device_name(0)}
+    g = torch.Generator().manual_seed(2)
+    S, N, num = 256, 5000, 3000
+    x = torch.randn(S, N, generator=g)
+    xd = x.to(dev)
+    r = timed(lambda: PP.resample(xd, num), torch, 3, 3, 1)
+    K = min(N, num) // 2 + 1
+    products = S * (N * K + K * num)
+    r["twiddle_products"] = products
+    r["Gproducts_per_s"] = round(products / r["ms_median"] / 1e6, 1)
+    t0 = time.perf_counter()
+    resample(x.numpy().astype(np.float64), num, axis=1)
+    r["scipy_host_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+    res["resample_256x5000_to_3000"] = r
+
+    rng = np.random.RandomState(42)
+    lengths = rng.randint(2000, 18001, size=S)
+    Lmax = int(lengths.max())
+    rows = torch.randn(S, Lmax, generator=g)
+    rd, ld = rows.to(dev), torch.as_tensor(lengths, dtype=torch.int32, device=dev)
+    r = timed(lambda: PP.resample(rd, ratio=0.6, lengths=ld), torch, 3, 3, 1)
+    nums = [int(n * 0.6) for n in lengths]
+    products = int(sum((n * (m // 2 + 1) + (m // 2 + 1) * m) for n, m in zip(lengths.tolist(), nums)))
+    r["twiddle_products"] = products
+    r["Gproducts_per_s"] = round(products / r["ms_median"] / 1e6, 1)
+    r["records_per_s"] = round(S / r["ms_median"] * 1e3, 1)
+    t0 = time.perf_counter()
+    for i, n in enumerate(lengths):
+        resample(rows[i, :n].numpy().astype(np.float64), nums[i])
+    r["scipy_host_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+    res["resample_lengths_256x2000_18000_ratio0.6"] = r
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cpus", type=int, default=16)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "physionet_bench.json"))
     ap.add_argument("--skip-cpu", action="store_true")
     ap.add_argument("--front-only", action="store_true")
+    ap.add_argument("--resample", action="store_true")
     args = ap.parse_args()
     import torch
     from ecgmm import train_physionet as TP
@@ -102,6 +143,14 @@ def main():
     from ecgmm.signal_model import FocalLoss, ResNet1D_SE
     assert torch.cuda.is_available(), "physionet_bench needs the GPU (there is no CPU path to time)"
     dev = torch.device("cuda:0")
+    if args.resample:
+        res = resample_bench(torch, dev)
+        out = args.out if args.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "physionet_resample_bench.json")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        return
     res = {"rounds": ROUNDS, "calls_per_round": CALLS, "device": torch.cuda.get_device_name(0)}
 
     S, Ln = 8528, 3000
