@@ -291,10 +291,24 @@ int ecgmm_fold_conv_bn(int dtype, int layout, const float* w, const float* conv_
                        const float* running_mean, const float* running_var, float eps, void* w_out, float* b_out,
                        float* scale_out, int Cout, int Cin, int RS, void* stream) {
   if (layout != 0 && layout != 1) ECG_FAIL(ECGMM_ERR_SHAPE, "fold_conv_bn: layout %d (0 = forward pack, 1 = stem pack)", layout);
+  if (dtype != ECGMM_BF16 && dtype != ECGMM_F32) ECG_FAIL(ECGMM_ERR_DTYPE, "fold_conv_bn: bad dtype %d", dtype);
+  if (layout == 0 && RS > 9)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "fold_conv_bn: %d taps unsupported (1..9; a 5x5 convolution folds through ecgmm_fold_conv5_bn)", RS);
   EcgFoldItem it = {};
   it.kind = layout == 1 ? ECG_FOLD_STEM : ECG_FOLD_CONV;
   it.w = w; it.conv_bias = conv_bias; it.gamma = gamma; it.beta = beta; it.rm = running_mean; it.rv = running_var;
   it.wout = w_out; it.bout = b_out; it.scale_out = scale_out; it.Cout = Cout; it.Cin = Cin; it.RS = RS;
+  return ecg_fold_batch(dtype, &it, 1, eps, S_(stream));
+}
+int ecgmm_fold_conv5_bn(int dtype, int layout, const float* w, const float* conv_bias, const float* gamma, const float* beta,
+                        const float* running_mean, const float* running_var, float eps, void* w_out, float* b_out,
+                        float* scale_out, int Cout, int Cin, void* stream) {
+  if (layout != 0 && layout != 1)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "fold_conv5_bn: layout %d (0 = forward pack, 1 = OIHW fp32)", layout);
+  EcgFoldItem it = {};
+  it.kind = layout == 1 ? ECG_FOLD_OIHW : ECG_FOLD_CONV;
+  it.w = w; it.conv_bias = conv_bias; it.gamma = gamma; it.beta = beta; it.rm = running_mean; it.rv = running_var;
+  it.wout = w_out; it.bout = b_out; it.scale_out = scale_out; it.Cout = Cout; it.Cin = Cin; it.RS = 25;
   return ecg_fold_batch(dtype, &it, 1, eps, S_(stream));
 }
 int ecgmm_relu_maxpool(int dtype, const void* y, void* out, int N, int H, int W, int C, void* stream) {
@@ -472,6 +486,13 @@ int ecgmm_conv5_bwd_weight(int dtype, const ecgmm_conv_desc* c, const void* x, c
 int ecgmm_bnrelu_maxpool2(int dtype, const void* y, const float* coef, void* out, uint8_t* idx, int N, int H, int W, int C,
                           int seq_layout, void* stream) {
   return ecg_bnrelu_maxpool2(dtype, y, coef, out, idx, N, H, W, C, seq_layout, S_(stream));
+}
+int ecgmm_relu_maxpool2(int dtype, const void* y, void* out, int N, int H, int W, int C, int seq_layout, void* stream) {
+  return ecg_relu_maxpool2(dtype, y, out, N, H, W, C, seq_layout, S_(stream));
+}
+int ecgmm_conv5_in1_relu_pool2(int dtype, const float* x, const float* w_oihw, const float* bias, void* out, int N, int H,
+                               int W, void* stream) {
+  return ecg_conv5_in1_relu_pool2(dtype, x, w_oihw, bias, out, N, H, W, S_(stream));
 }
 size_t ecgmm_pool2_bn_bwd_workspace(int N, int H, int W, int C) { return ecg_pool2_bn_bwd_workspace(N, H, W, C); }
 int ecgmm_pool2_bn_bwd(int dtype, const void* dp, const uint8_t* idx, const void* y, const float* coef, int training,

@@ -26,6 +26,10 @@
 //   pool2_bwd_*             backward of [BatchNorm -> ReLU -> MaxPool2d(2)]: reduction over the pooled positions, fixed-
 //                           order finalize, apply pass over all N H W conv outputs (rows / columns the floor dropped get a
 //                           zero pooled gradient but stay in the BatchNorm sums).
+//   relu_pool2_kernel       inference: max(0, MaxPool2d(2)) of a convolution whose BatchNorm is folded into it (no
+//                           coefficients, no argmax bytes), 16-byte channel chunks; same two output layouts
+//   conv5_in1_relu_pool2_kernel  inference: Conv2d(1, 32, 5) + bias + ReLU + MaxPool2d(2) in one kernel, the [B,F,T,32]
+//                           tensor never written; bit-identical to conv5_in1_fwd_kernel + relu_pool2_kernel
 //
 // Every split reduction goes through per-workgroup partial rows and a fixed-order second pass: no float atomics.
 #include "ops.h"
@@ -620,6 +624,140 @@ long p2_chunk(long pixels, int C) {
   return c > least ? c : least;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Inference forms (plan_infer.hip): the BatchNorm is folded into the convolution, so a block ends in max(0, max over the
+// 2x2 window); no coefficients, no argmax bytes.
+// ------------------------------------------------------------------------------------------------
+// relu -> MaxPool2d(2), floor semantics.  Thread = one pooled pixel x one 16-byte channel chunk: four 16-byte loads, one
+// 16-byte store; seq: the chunk's floats go PH apart into seq[n][pw][c * PH + ph], as pool2_fwd_kernel writes it.
+template <typename T>
+__global__ __launch_bounds__(P2_THREADS) void relu_pool2_kernel(const T* __restrict__ y, void* __restrict__ out, int N, int H,
+                                                               int W, int C, int PH, int PW, int seq) {
+  constexpr int VEC = Elem<T>::VEC;
+  const int cpr = C / VEC;
+  const long total = (long)N * PH * PW * cpr;
+  const long i = (long)blockIdx.x * P2_THREADS + threadIdx.x;
+  if (i >= total) return;
+  const int c0 = (int)(i % cpr) * VEC;
+  const long q = i / cpr;
+  const int pw = (int)(q % PW);
+  const long t = q / PW;
+  const int ph = (int)(t % PH);
+  const long n = t / PH;
+  float best[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) best[j] = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int h = 2 * ph + (k >> 1), w = 2 * pw + (k & 1);
+    float f[VEC];
+    unpack16<T>(*reinterpret_cast<const u32x4*>(y + ((n * H + h) * W + w) * C + c0), f);
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) best[j] = f[j] > best[j] ? f[j] : best[j];   // (a NaN input never wins, -0 never wins)
+  }
+  if (seq) {
+    float* o = reinterpret_cast<float*>(out) + ((n * PW + pw) * C + c0) * PH + ph;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) o[(long)j * PH] = best[j];
+  } else {
+    *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(out) + q * C + c0) = pack16<T>(best);
+  }
+}
+
+// Conv2d(1, 32, 5, pad 2) + bias + ReLU + MaxPool2d(2) in one kernel: [N][H][W] fp32 -> [N][H/2][W/2][32].
+// Thread = one POOLED pixel x 8 channels (four threads per pixel, as conv5_in1_fwd_kernel).  It reads the 6x6 input patch
+// of its 2x2 window once into registers (instead of four 5x5 patches) and keeps the window's four conv outputs in 32
+// accumulators, so a weight read from LDS feeds four fma instead of one: the two-launch form spends a ds_read_b128 per
+// four fma, this one per sixteen.  Rows / columns the floor drops are never computed; nothing but the pooled tensor is
+// written.
+// Every conv output is accumulated exactly as conv5_in1_fwd_kernel accumulates it: operands rounded the same way, one fmaf
+// per tap in the order (r, then s), the bias added after the taps.  A tap outside the image is a zero in the patch:
+// fmaf(0, w, acc) == acc bit for bit for any finite w (acc starts at +0 and a sum is -0 only if both terms are, so acc is
+// never -0), which is the skipped tap of conv5_in1_fwd_kernel.  Rounding to the compute dtype is monotone, so it commutes
+// with the maxima: max over the fp32 sums, max with 0 (same comparison as relu_pool2_kernel), ONE rounding at the store --
+// the bits of conv5_in1_fwd (no statistics) followed by relu_pool2.
+constexpr int FP_PASSES = 8;         // passes per workgroup (64 pooled pixels each)
+
+template <typename T>
+__global__ __launch_bounds__(IN1_THREADS) void conv5_in1_relu_pool2_kernel(const float* __restrict__ x,
+                                                                          const float* __restrict__ w,
+                                                                          const float* __restrict__ bias, T* __restrict__ out,
+                                                                          int N, int H, int W, int PH, int PW) {
+  __shared__ float ws[C5_TAPS][IN1_C];
+  const int tid = threadIdx.x;
+  for (int i = tid; i < C5_TAPS * IN1_C; i += IN1_THREADS) {
+    const int tap = i / IN1_C, co = i % IN1_C;
+    ws[tap][co] = round_operand<T>(w[co * C5_TAPS + tap]);   // OIHW [32][1][5][5]
+  }
+  __syncthreads();
+  const int slot = tid >> 2, cg = (tid & 3) * 8;
+  const long Q = (long)N * PH * PW;
+  float bv[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) bv[j] = bias ? bias[cg + j] : 0.f;
+  for (int pass = 0; pass < FP_PASSES; ++pass) {
+    const long q = ((long)blockIdx.x * FP_PASSES + pass) * IN1_PIX + slot;
+    if (q >= Q) break;
+    const int pw = (int)(q % PW);
+    const long t = q / PW;
+    const int ph = (int)(t % PH);
+    const float* img = x + (t / PH) * (long)H * W;
+    const int h0 = 2 * ph - 2, w0 = 2 * pw - 2;
+    // the 36 loads are unconditional (address clamped into the image, value dropped where the tap lies outside), so they
+    // are all in flight before the first wait instead of one branch and one wait each
+    float patch[6][6];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+      const int hh = h0 + a;
+      const bool hok = (unsigned)hh < (unsigned)H;
+      const float* row = img + (long)min(max(hh, 0), H - 1) * W;
+#pragma unroll
+      for (int b = 0; b < 6; ++b) {
+        const int ww = w0 + b;
+        const float v = row[min(max(ww, 0), W - 1)];
+        patch[a][b] = (hok && (unsigned)ww < (unsigned)W) ? round_operand<T>(v) : 0.f;
+      }
+    }
+    float acc[4][8];
+#pragma unroll
+    for (int o = 0; o < 4; ++o)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[o][j] = 0.f;
+#pragma unroll
+    for (int r = 0; r < 5; ++r) {
+#pragma unroll
+      for (int s = 0; s < 5; ++s) {
+        float wv[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) wv[j] = ws[r * 5 + s][cg + j];
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+          const float xv = patch[(o >> 1) + r][(o & 1) + s];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) acc[o][j] = fmaf(xv, wv[j], acc[o][j]);
+        }
+      }
+    }
+    float best[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) best[j] = 0.f;
+#pragma unroll
+    for (int o = 0; o < 4; ++o)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float v = acc[o][j] + bv[j];
+        best[j] = v > best[j] ? v : best[j];
+      }
+    T* o = out + q * IN1_C + cg;
+    if (sizeof(T) == 2) {
+      *reinterpret_cast<u32x4*>(o) = pack16<bf16_t>(best);
+    } else {
+      *reinterpret_cast<u32x4*>(o) = pack16<float>(best);
+      *reinterpret_cast<u32x4*>(o + 4) = pack16<float>(best + 4);
+    }
+  }
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -744,6 +882,42 @@ int ecg_bnrelu_maxpool2(int dtype, const void* y, const float* coef, void* out, 
   else
     hipLaunchKernelGGL(pool2_fwd_kernel<float>, grid, dim3(P2_THREADS), 0, s, (const float*)y, coef, out, idx, N, H, W, C, PH, PW, seq_layout);
   ECG_CHECK_LAUNCH("bnrelu_maxpool2");
+  return 0;
+}
+
+int ecg_relu_maxpool2(int dtype, const void* y, void* out, int N, int H, int W, int C, int seq_layout, hipStream_t s) {
+  if (dtype != ECGMM_BF16 && dtype != ECGMM_F32) ECG_FAIL(ECGMM_ERR_DTYPE, "relu_maxpool2: bad dtype %d", dtype);
+  if (!y || !out) ECG_FAIL(ECGMM_ERR_SHAPE, "relu_maxpool2: y and out must not be null");
+  const int vec = dtype == ECGMM_BF16 ? 8 : 4;
+  if (N < 1 || H < 2 || W < 2 || C < vec || C % vec)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "relu_maxpool2: N=%d H=%d W=%d C=%d (H, W >= 2; C a multiple of %d)", N, H, W, C, vec);
+  if ((long)N * H * W * C / 4 > 0x7fffffffL) ECG_FAIL(ECGMM_ERR_SHAPE, "relu_maxpool2: tensor too large");
+  if ((uintptr_t)y % 16 || (!seq_layout && (uintptr_t)out % 16))
+    ECG_FAIL(ECGMM_ERR_SHAPE, "relu_maxpool2: y and out must be 16-byte aligned");
+  const int PH = H / 2, PW = W / 2;
+  const long total = (long)N * PH * PW * (C / vec);
+  const dim3 grid(ceil_div(total, P2_THREADS));
+  if (dtype == ECGMM_BF16)
+    hipLaunchKernelGGL(relu_pool2_kernel<bf16_t>, grid, dim3(P2_THREADS), 0, s, (const bf16_t*)y, out, N, H, W, C, PH, PW, seq_layout);
+  else
+    hipLaunchKernelGGL(relu_pool2_kernel<float>, grid, dim3(P2_THREADS), 0, s, (const float*)y, out, N, H, W, C, PH, PW, seq_layout);
+  ECG_CHECK_LAUNCH("relu_maxpool2");
+  return 0;
+}
+
+int ecg_conv5_in1_relu_pool2(int dtype, const float* x, const float* w, const float* bias, void* out, int N, int H, int W,
+                             hipStream_t s) {
+  ECG_TRY(in1_check(dtype, N, H, W, "conv5_in1_relu_pool2"));
+  if (H < 2 || W < 2) ECG_FAIL(ECGMM_ERR_SHAPE, "conv5_in1_relu_pool2: %dx%d (a 2x2 pool needs H, W >= 2)", H, W);
+  if (!x || !w || !out) ECG_FAIL(ECGMM_ERR_SHAPE, "conv5_in1_relu_pool2: x, w and out must not be null");
+  if ((uintptr_t)out % 16) ECG_FAIL(ECGMM_ERR_SHAPE, "conv5_in1_relu_pool2: out must be 16-byte aligned");
+  const int PH = H / 2, PW = W / 2;
+  const dim3 grid(ceil_div((long)N * PH * PW, IN1_PIX * FP_PASSES));
+  if (dtype == ECGMM_BF16)
+    hipLaunchKernelGGL(conv5_in1_relu_pool2_kernel<bf16_t>, grid, dim3(IN1_THREADS), 0, s, x, w, bias, (bf16_t*)out, N, H, W, PH, PW);
+  else
+    hipLaunchKernelGGL(conv5_in1_relu_pool2_kernel<float>, grid, dim3(IN1_THREADS), 0, s, x, w, bias, (float*)out, N, H, W, PH, PW);
+  ECG_CHECK_LAUNCH("conv5_in1_relu_pool2");
   return 0;
 }
 

@@ -32,7 +32,14 @@ struct FoldBatch {
   float eps;
 };
 
-constexpr int FOLD_T = 32, FOLD_RS_MAX = 9, FOLD_COPY_PER_BLOCK = 2048;
+constexpr int FOLD_T = 32, FOLD_RS_MAX = 25, FOLD_COPY_PER_BLOCK = 2048;
+// the staging tile of a ECG_FOLD_CONV block: FOLD_T output channels of up to 9 taps (every 3x3 / 1x3 / 1x1 convolution), or
+// FOLD_CO_WIDE output channels of up to FOLD_RS_MAX taps (the CRNN's 5x5 blocks), FOLD_T input channels each, rows padded by 1
+constexpr int FOLD_RS_NARROW = 9, FOLD_CO_WIDE = 8;
+constexpr int FOLD_TILE = FOLD_T * (FOLD_T * FOLD_RS_NARROW + 1);
+static_assert(FOLD_CO_WIDE * (FOLD_T * FOLD_RS_MAX + 1) <= FOLD_TILE, "the wide tile must fit the staging buffer");
+__host__ __device__ inline int fold_co_rows(int RS) { return RS <= FOLD_RS_NARROW ? FOLD_T : FOLD_CO_WIDE; }
+__host__ __device__ inline int fold_row_stride(int RS) { return FOLD_T * (RS <= FOLD_RS_NARROW ? FOLD_RS_NARROW : FOLD_RS_MAX) + 1; }
 
 __device__ __forceinline__ float fold_scale(const FoldBatch& b, int t, int co) {
   return b.gamma[t][co] / sqrtf(b.rv[t][co] + b.eps);
@@ -43,13 +50,16 @@ __device__ __forceinline__ void fold_bias(const FoldBatch& b, int t, int co, flo
   if (b.sout[t]) b.sout[t][co] = sc;
 }
 
-// kind ECG_FOLD_CONV: one block = a 32 (co) x 32 (ci) tile of one tensor with all its taps, staged through LDS as in
-// pack_weight_batch_kernel (elementwise.hip): OIHW rows read in contiguous runs, [co][tap][ci] written 32 ci at a time.
+// kind ECG_FOLD_CONV: one block = a 32 (co) x 32 (ci) tile of one tensor with all its taps (8 x 32 above 9 taps), staged
+// through LDS as in pack_weight_batch_kernel (elementwise.hip): OIHW rows read in contiguous runs, [co][tap][ci] written
+// 32 ci at a time.
 // kind ECG_FOLD_STEM: one block = one output channel of the stem layout [64][KP], k = (c * R + r) * 8 + s (conv_stem.hip).
 // kind ECG_FOLD_COPY: fp32 copy of a dense tensor (the fc / SE / classifier weights an inference plan reads from its blob).
+// kind ECG_FOLD_OIHW: w * scale[cout] in the layout it came in, fp32 out (FOLD_COPY_PER_BLOCK elements per block; the first
+//                     block writes the biases).
 template <typename T>
 __global__ __launch_bounds__(256) void fold_batch_kernel(FoldBatch b) {
-  __shared__ float tile[FOLD_T][FOLD_T * FOLD_RS_MAX + 1];
+  __shared__ float tile[FOLD_TILE];
   __shared__ float s_scale[FOLD_T];
   int t = 0;
   while (t + 1 < b.n && (int)blockIdx.x >= b.blk0[t + 1]) ++t;
@@ -60,6 +70,16 @@ __global__ __launch_bounds__(256) void fold_batch_kernel(FoldBatch b) {
     float* out = (float*)b.wout[t];
     for (long i = (long)lb * FOLD_COPY_PER_BLOCK + threadIdx.x; i < n && i < (long)(lb + 1) * FOLD_COPY_PER_BLOCK; i += 256)
       out[i] = b.w[t][i];
+    return;
+  }
+  if (kind == ECG_FOLD_OIHW) {
+    const int per = b.cin[t] * b.rs[t];   // elements per output channel
+    const long n = (long)b.cout[t] * per;
+    float* out = (float*)b.wout[t];
+    for (long i = (long)lb * FOLD_COPY_PER_BLOCK + threadIdx.x; i < n && i < (long)(lb + 1) * FOLD_COPY_PER_BLOCK; i += 256)
+      out[i] = b.w[t][i] * fold_scale(b, t, (int)(i / per));
+    if (lb == 0)
+      for (int co = threadIdx.x; co < b.cout[t]; co += 256) fold_bias(b, t, co, fold_scale(b, t, co));
     return;
   }
   if (kind == ECG_FOLD_STEM) {
@@ -78,8 +98,9 @@ __global__ __launch_bounds__(256) void fold_batch_kernel(FoldBatch b) {
   const float* __restrict__ w = b.w[t];
   T* __restrict__ fwd = (T*)b.wout[t];
   const int ci_tiles = (Cin + FOLD_T - 1) / FOLD_T;
-  const int co0 = (lb / ci_tiles) * FOLD_T, ci0 = (lb % ci_tiles) * FOLD_T;
-  const int nci = min(FOLD_T, Cin - ci0), nco = min(FOLD_T, Cout - co0);
+  const int co_rows = fold_co_rows(RS), stride = fold_row_stride(RS);
+  const int co0 = (lb / ci_tiles) * co_rows, ci0 = (lb % ci_tiles) * FOLD_T;
+  const int nci = min(FOLD_T, Cin - ci0), nco = min(co_rows, Cout - co0);
   const int run = nci * RS;
   if (threadIdx.x < nco) {
     const float sc = fold_scale(b, t, co0 + threadIdx.x);
@@ -89,12 +110,12 @@ __global__ __launch_bounds__(256) void fold_batch_kernel(FoldBatch b) {
   __syncthreads();
   for (int i = threadIdx.x; i < nco * run; i += 256) {
     const int co = i / run, k = i - co * run;
-    tile[co][k] = w[((size_t)(co0 + co) * Cin + ci0) * RS + k] * s_scale[co];
+    tile[co * stride + k] = w[((size_t)(co0 + co) * Cin + ci0) * RS + k] * s_scale[co];
   }
   __syncthreads();
   for (int i = threadIdx.x; i < nco * RS * FOLD_T; i += 256) {
     const int ci = i % FOLD_T, ct = i / FOLD_T, tap = ct % RS, co = ct / RS;
-    if (ci < nci) Elem<T>::st(fwd + ((size_t)(co0 + co) * RS + tap) * Cin + ci0 + ci, tile[co][ci * RS + tap]);
+    if (ci < nci) Elem<T>::st(fwd + ((size_t)(co0 + co) * RS + tap) * Cin + ci0 + ci, tile[co * stride + ci * RS + tap]);
   }
 }
 
@@ -200,7 +221,10 @@ int ecg_fold_batch(int dtype, const EcgFoldItem* items, int n, float eps, hipStr
         blocks += 64;
       } else if (it.kind == ECG_FOLD_CONV) {
         if (it.RS < 1 || it.RS > FOLD_RS_MAX) ECG_FAIL(ECGMM_ERR_SHAPE, "fold: %d taps unsupported (1..%d)", it.RS, FOLD_RS_MAX);
-        blocks += ceil_div(it.Cout, FOLD_T) * ceil_div(it.Cin, FOLD_T);
+        blocks += ceil_div(it.Cout, fold_co_rows(it.RS)) * ceil_div(it.Cin, FOLD_T);
+      } else if (it.kind == ECG_FOLD_OIHW) {
+        if (it.RS < 1 || (long)it.Cout * it.Cin * it.RS > 0x7fffffffL) ECG_FAIL(ECGMM_ERR_SHAPE, "fold: item %d has %d taps", i, it.RS);
+        blocks += ceil_div((long)it.Cout * it.Cin * it.RS, FOLD_COPY_PER_BLOCK);
       } else {
         ECG_FAIL(ECGMM_ERR_SHAPE, "fold: item %d has kind %d", i, it.kind);
       }

@@ -1,5 +1,6 @@
-// The two encoder networks described once: per-block channel counts, strides, parameter- / buffer-table indices and
-// geometry.  Every launch plan (plan_resnet18.hip, plan_resnet1d.hip, plan_infer.hip) walks these records.
+// The two encoder networks and the CRNN front end described once: per-block channel counts, strides, parameter- /
+// buffer-table indices and geometry.  Every launch plan (plan_resnet18.hip, plan_resnet1d.hip, plan_crnn.hip,
+// plan_infer.hip) walks these records.
 // A record is built in two steps: *_static() fills what the weights depend on (dtype, table indices, channel counts,
 // strides) and *_shape() adds what depends on N and the input size.  Both take the message prefix of the calling plan;
 // what else a plan validates (out_dim, bn_eps, ...) stays with that plan's entry points.
@@ -171,4 +172,57 @@ inline int net1d_shape(Net1D& r, const char* who) {
     l = k.lout;
   }
   return 0;
+}
+
+// ================================================================================================
+// CRNN front end (train_physionet2.py:55-65, 87-93): three blocks Conv2d(k = 5, pad = 2, bias) -> BatchNorm2d -> ReLU ->
+// MaxPool2d(2).  Parameter table (12): per block conv weight, conv bias, bn weight, bn bias; buffer table (9): per block
+// running_mean, running_var, num_batches_tracked.  Walked by plan_crnn.hip (training plan) and plan_infer.hip.
+// ================================================================================================
+struct BlkC {
+  int cin, cout, h, w, ph, pw;   // conv input = output extent (h, w), pooled extent (ph, pw)
+  int p0, b0;
+  long pixels(int B) const { return (long)B * h * w; }
+  long pooled(int B) const { return (long)B * ph * pw; }
+  ConvGeom geom(int B) const { return make_geom(B, h, w, cin, cout, 5, 5, 1, 2, 2); }
+};
+struct NetC {
+  ecgmm_crnn_front_desc d;
+  BnCfg bn;
+  BlkC blk[3];
+};
+
+inline int netc_static(const ecgmm_crnn_front_desc* d, NetC& r, const char* who) {
+  if (!d) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: null desc", who);
+  ECG_TRY(desc_dtype_ok(d->dtype, who));
+  r.d = *d;
+  r.bn = {d->dtype, d->training, d->bn_momentum, d->bn_eps};
+  int cin = 1;
+  for (int i = 0; i < 3; ++i) {
+    BlkC& k = r.blk[i];
+    k.cin = cin; k.cout = 32 << i; k.p0 = 4 * i; k.b0 = 3 * i;
+    k.h = k.w = k.ph = k.pw = 0;
+    cin = k.cout;
+  }
+  return 0;
+}
+
+inline int netc_shape(NetC& r, const char* who) {
+  const ecgmm_crnn_front_desc& d = r.d;
+  if (d.B < 1) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: B = %d", who, d.B);
+  if (d.F < 8) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: F = %d (three 2x2 pools need F >= 8)", who, d.F);
+  if (d.T < 8) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: T = %d (three 2x2 pools need T >= 8)", who, d.T);
+  if ((long)d.B * d.F * d.T > 0x7fffffffL / 32) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: input too large", who);
+  int h = d.F, w = d.T;
+  for (int i = 0; i < 3; ++i) {
+    BlkC& k = r.blk[i];
+    k.h = h; k.w = w; k.ph = h / 2; k.pw = w / 2;
+    h = k.ph; w = k.pw;
+  }
+  return 0;
+}
+
+inline int netc_build(const ecgmm_crnn_front_desc* d, NetC& r, const char* who) {
+  ECG_TRY(netc_static(d, r, who));
+  return netc_shape(r, who);
 }

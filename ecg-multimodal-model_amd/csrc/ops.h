@@ -160,13 +160,15 @@ int ecg_pack_weight_batch(int dtype, const EcgPackItem* items, int n, hipStream_
 constexpr int ECG_FOLD_MAX = 32;
 enum { ECG_FOLD_CONV = 0,    // OIHW / OIL fp32 -> forward pack [Cout][RS][Cin] (the layout of ecg_pack_weight)
        ECG_FOLD_STEM = 1,    // [64][Cin][R][7] fp32 -> stem pack (ecg_stem_pack); RS = R (1 or 7)
-       ECG_FOLD_COPY = 2 };  // plain fp32 copy of Cout x Cin floats (dense-tail weights kept beside the folded ones)
+       ECG_FOLD_COPY = 2,    // plain fp32 copy of Cout x Cin floats (dense-tail weights kept beside the folded ones)
+       ECG_FOLD_OIHW = 3 };  // OIHW fp32 -> OIHW fp32 whatever the dtype: the weight of a kernel that rounds its operands
+                             // itself (the CRNN's Cin = 1 convolution), so that rounding stays the only one
 struct EcgFoldItem {
   int kind;
   const float* w;
   const float* conv_bias;                 // nullable
   const float *gamma, *beta, *rm, *rv;    // the BatchNorm (unused by ECG_FOLD_COPY)
-  void* wout;                             // compute dtype (fp32 for ECG_FOLD_COPY)
+  void* wout;                             // compute dtype (fp32 for ECG_FOLD_COPY and ECG_FOLD_OIHW)
   float* bout;                            // [Cout] fp32
   float* scale_out;                       // nullable: the scale the kernel used, [Cout] fp32
   int Cout, Cin, RS;
@@ -284,6 +286,12 @@ int ecg_conv5_wgrad(int dtype, const ConvGeom& g, const void* x, const void* dy,
                     size_t ws_bytes, hipStream_t s);
 int ecg_bnrelu_maxpool2(int dtype, const void* y, const float* coef, void* out, unsigned char* idx, int N, int H, int W, int C,
                         int seq_layout, hipStream_t s);
+// inference forms (BatchNorm folded into the convolution): max(0, MaxPool2d(2)) without coefficients / argmax bytes, C a
+// multiple of 8 (bf16) / 4 (fp32), same output layouts as ecg_bnrelu_maxpool2; and block 1 as one kernel,
+// [N][H][W] fp32 -> [N][H/2][W/2][32], the bits of ecg_conv5_in1_fwd(stats = null) + ecg_relu_maxpool2
+int ecg_relu_maxpool2(int dtype, const void* y, void* out, int N, int H, int W, int C, int seq_layout, hipStream_t s);
+int ecg_conv5_in1_relu_pool2(int dtype, const float* x, const float* w, const float* bias, void* out, int N, int H, int W,
+                             hipStream_t s);
 size_t ecg_pool2_bn_bwd_workspace(int N, int H, int W, int C);
 int ecg_pool2_bn_bwd(int dtype, const void* dp, const unsigned char* idx, const void* y, const float* coef, int training,
                      float* dgamma, float* dbeta, void* dy, float* dbias, int N, int H, int W, int C, int seq_layout, void* ws,

@@ -6,38 +6,7 @@
 
 namespace {
 
-// The three blocks described once.  Parameter table (12): per block conv weight, conv bias, bn weight, bn bias;
-// buffer table (9): per block running_mean, running_var, num_batches_tracked.
-struct BlkC {
-  int cin, cout, h, w, ph, pw;   // conv input = output extent (h, w), pooled extent (ph, pw)
-  int p0, b0;
-  long pixels(int B) const { return (long)B * h * w; }
-  long pooled(int B) const { return (long)B * ph * pw; }
-  ConvGeom geom(int B) const { return make_geom(B, h, w, cin, cout, 5, 5, 1, 2, 2); }
-};
-struct NetC {
-  ecgmm_crnn_front_desc d;
-  BnCfg bn;
-  BlkC blk[3];
-};
-
-int netc_build(const ecgmm_crnn_front_desc* d, NetC& r, const char* who) {
-  if (!d) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: null desc", who);
-  ECG_TRY(desc_dtype_ok(d->dtype, who));
-  if (d->B < 1) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: B = %d", who, d->B);
-  if (d->F < 8) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: F = %d (three 2x2 pools need F >= 8)", who, d->F);
-  if (d->T < 8) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: T = %d (three 2x2 pools need T >= 8)", who, d->T);
-  if ((long)d->B * d->F * d->T > 0x7fffffffL / 32) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: input too large", who);
-  r.d = *d;
-  r.bn = {d->dtype, d->training, d->bn_momentum, d->bn_eps};
-  int h = d->F, w = d->T, cin = 1;
-  for (int i = 0; i < 3; ++i) {
-    BlkC& k = r.blk[i];
-    k.cin = cin; k.cout = 32 << i; k.h = h; k.w = w; k.ph = h / 2; k.pw = w / 2; k.p0 = 4 * i; k.b0 = 3 * i;
-    cin = k.cout; h = k.ph; w = k.pw;
-  }
-  return 0;
-}
+// The three blocks are described once, in net_desc.h (NetC, BlkC, netc_build): the inference plan walks the same record.
 
 int stats_rows_of(const NetC& n, int i) {
   const BlkC& k = n.blk[i];

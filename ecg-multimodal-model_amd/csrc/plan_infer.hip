@@ -1,4 +1,4 @@
-// Inference plans of both encoders (gfx950): eval-mode forwards with every BatchNorm folded into the convolution in front
+// Inference plans of both encoders and of the CRNN front end (gfx950): eval-mode forwards with every BatchNorm folded into the convolution in front
 // of it and bias / residual / ReLU applied in the convolution's epilogue.  Opt-in beside the training plans
 // (plan_resnet18.hip, plan_resnet1d.hip), which stay what `model.eval()` runs and what a backward or Grad-CAM needs.
 //
@@ -14,6 +14,7 @@
 // ResNet1D_SE block: a1 as above; y2 = conv2'(a1) + b2'; gate = SE(mean_L y2); [yd]; out = relu(y2 * gate + (yd | x)) in
 //   place.  The squeeze needs the whole y2 of a sample, so that last pass cannot be a convolution epilogue.
 // Stem: stem_fwd(w', b') -> relu_maxpool (no coefficients, no argmax bytes).
+// CRNN front end (at the end of this file): three folded 5x5 blocks, conv + max(0, 2x2 max-pool), block 1 as one kernel.
 //
 // Workspace: the stem output, the pooled tensor and a fixed set of rotating block buffers of the largest block activation
 // instead of one saved set per block; the rotating buffers alias the stem output, which is dead once the max-pool has read it.
@@ -388,4 +389,114 @@ extern "C" int ecgmm_resnet1d_infer(const ecgmm_resnet1d_desc* d, const float* s
   ECG_TRY(ecg_avgpool(dt, rot.buf[rot.cur], w.pooled, N, r.blk[2].lout, 256, nullptr, s));
   ECG_TRY(ecg_linear_fwd(w.pooled, q.cw1, q.cb1, w.h1, N, 256, 64, ECGMM_ACT_RELU, nullptr, s));
   return ecg_linear_fwd(w.h1, q.cw2, q.cb2, feat_out, N, 64, r.d.num_classes, 0, nullptr, s);
+}
+
+// ---- CRNN front end ------------------------------------------------------------------------------------------------
+// conv1..conv3 of `CRNN` (train_physionet2.py:55-65, 87-93) with the BatchNorms folded: each block is one convolution
+// followed by max(0, max over the 2x2 window).  Five launches: block 1 as ONE kernel (crnn_front.hip: the [B,F,T,32]
+// tensor, the largest of the model, is never written), then conv_igemm (bias epilogue, no statistics) + relu_maxpool2 for
+// blocks 2 and 3, the last one straight into the LSTM's layout.  The training plan's eval mode (plan_crnn.hip) stays what
+// a backward needs.
+namespace {
+
+int buildc_static(const ecgmm_crnn_front_desc* d, NetC& r) {
+  ECG_TRY(netc_static(d, r, "crnn_front infer"));
+  if (!(d->bn_eps >= 0.f)) ECG_FAIL(ECGMM_ERR_SHAPE, "crnn_front infer: bn_eps %g", (double)d->bn_eps);
+  return 0;
+}
+int buildc(const ecgmm_crnn_front_desc* d, NetC& r) {
+  ECG_TRY(buildc_static(d, r));
+  return netc_shape(r, "crnn_front infer");
+}
+
+// folded weights: block 1 fp32 OIHW (its kernel rounds the operands itself), blocks 2, 3 the forward pack; fp32 biases
+struct BlobC {
+  void* w[3];
+  float* b[3];
+  size_t bytes;
+};
+void layout_blobc(const NetC& r, void* base, BlobC& q) {
+  Arena a(base);
+  const size_t es = dtype_size(r.d.dtype);
+  for (int i = 0; i < 3; ++i) {
+    const BlkC& k = r.blk[i];
+    q.w[i] = a.take_bytes((size_t)k.cout * k.cin * 25 * (i == 0 ? sizeof(float) : es));
+    q.b[i] = a.take<float>(k.cout);
+  }
+  q.bytes = align_up(a.off, 256);
+}
+
+// pooled outputs of blocks 1, 2 and raw conv outputs of blocks 2, 3; nothing else
+struct WsC {
+  void* pool[2];
+  void* y[3];
+  size_t bytes;
+};
+void layout_wsc(const NetC& r, void* base, WsC& w) {
+  Arena a(base);
+  const size_t es = dtype_size(r.d.dtype);
+  w.y[0] = nullptr;
+  for (int i = 0; i < 3; ++i) {
+    const BlkC& k = r.blk[i];
+    if (i > 0) w.y[i] = a.take_bytes((size_t)k.pixels(r.d.B) * k.cout * es);
+    if (i < 2) w.pool[i] = a.take_bytes((size_t)k.pooled(r.d.B) * k.cout * es);
+  }
+  w.bytes = align_up(a.off, 256);
+}
+
+}  // namespace
+
+extern "C" size_t ecgmm_crnn_front_infer_prepared_bytes(const ecgmm_crnn_front_desc* d) {
+  NetC r;
+  if (buildc_static(d, r)) return 0;
+  BlobC q;
+  layout_blobc(r, nullptr, q);
+  return q.bytes;
+}
+
+extern "C" int ecgmm_crnn_front_infer_prepare(const ecgmm_crnn_front_desc* d, const void* const* params,
+                                              const void* const* buffers, void* blob, size_t blob_bytes, void* stream_) {
+  NetC r;
+  ECG_TRY(buildc_static(d, r));
+  ECG_TRY(check_tables(params, 12, buffers, 9, "crnn_front infer prepare"));
+  BlobC q;
+  layout_blobc(r, blob, q);
+  ECG_NEED(blob, blob_bytes, q.bytes, "crnn_front infer prepare: blob");
+  EcgFoldItem items[3];
+  for (int i = 0; i < 3; ++i) {
+    const BlkC& k = r.blk[i];
+    items[i] = conv_item(i == 0 ? ECG_FOLD_OIHW : ECG_FOLD_CONV, params, k.p0, P(params, k.p0 + 1), k.p0 + 2, buffers, k.b0,
+                         q.w[i], q.b[i], k.cout, k.cin, 25);
+  }
+  return ecg_fold_batch(r.d.dtype, items, 3, r.d.bn_eps, (hipStream_t)stream_);
+}
+
+extern "C" size_t ecgmm_crnn_front_infer_workspace(const ecgmm_crnn_front_desc* d) {
+  NetC r;
+  if (buildc(d, r)) return 0;
+  WsC w;
+  layout_wsc(r, nullptr, w);
+  return w.bytes;
+}
+
+extern "C" int ecgmm_crnn_front_infer(const ecgmm_crnn_front_desc* d, const float* spec, const void* blob, size_t blob_bytes,
+                                      float* seq_out, void* ws, size_t ws_bytes, void* stream_) {
+  hipStream_t s = (hipStream_t)stream_;
+  NetC r;
+  ECG_TRY(buildc(d, r));
+  if (!spec || !seq_out) ECG_FAIL(ECGMM_ERR_SHAPE, "crnn_front infer: null spectrogram / output");
+  BlobC q;
+  layout_blobc(r, const_cast<void*>(blob), q);
+  ECG_NEED(blob, blob_bytes, q.bytes, "crnn_front infer: blob");
+  WsC w;
+  layout_wsc(r, ws, w);
+  ECG_NEED(ws, ws_bytes, w.bytes, "crnn_front infer: workspace");
+  const int dt = r.d.dtype, B = r.d.B;
+  ECG_TRY(ecg_conv5_in1_relu_pool2(dt, spec, (const float*)q.w[0], q.b[0], w.pool[0], B, r.blk[0].h, r.blk[0].w, s));
+  for (int i = 1; i < 3; ++i) {
+    const BlkC& k = r.blk[i];
+    ECG_TRY(ecg_conv_igemm(dt, 0, k.geom(B), w.pool[i - 1], q.w[i], w.y[i], q.b[i], nullptr, nullptr, 0, s));
+    ECG_TRY(ecg_relu_maxpool2(dt, w.y[i], i < 2 ? w.pool[i] : (void*)seq_out, B, k.h, k.w, k.cout, i == 2, s));
+  }
+  return 0;
 }

@@ -235,6 +235,13 @@ SIGNATURES = {
     "ecgmm_conv5_in1_bwd_data_tile": (None, [i32, P(i32), P(i32), P(i32)]),
     "ecgmm_crnn_gradcam_workspace": (sz, [i32, i32, i32, i32]),
     "ecgmm_crnn_gradcam": (i32, [vp, vp, vp, vp, vp, sz, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "ecgmm_relu_maxpool2": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "ecgmm_conv5_in1_relu_pool2": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "ecgmm_fold_conv5_bn": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, vp]),
+    "ecgmm_crnn_front_infer_prepared_bytes": (sz, [P(CRNNFrontDesc)]),
+    "ecgmm_crnn_front_infer_prepare": (i32, [P(CRNNFrontDesc), P(vp), P(vp), vp, sz, vp]),
+    "ecgmm_crnn_front_infer_workspace": (sz, [P(CRNNFrontDesc)]),
+    "ecgmm_crnn_front_infer": (i32, [P(CRNNFrontDesc), vp, vp, sz, vp, vp, sz, vp]),
     "ecgmm_log_spectrogram_frames": (i32, [i32, i32, i32]),
     "ecgmm_log_spectrogram": (i32, [vp, i32, i32, vp, i32, i32, vp, i32, vp]),
     "ecgmm_lime_perturb": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, u64, u64, vp, vp, vp, vp, vp]),
@@ -310,7 +317,11 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  "ecgmm_crnn_front_backward_dx", "ecgmm_conv5_in1_bwd_data", "ecgmm_conv5_in1_bwd_data_tile",
                  "ecgmm_crnn_gradcam_workspace", "ecgmm_crnn_gradcam",
                  # Fourier resampling (ecgmm.preprocess.resample, csrc/resample.hip)
-                 "ecgmm_signal_resample_len", "ecgmm_signal_resample_workspace", "ecgmm_signal_resample")
+                 "ecgmm_signal_resample_len", "ecgmm_signal_resample_workspace", "ecgmm_signal_resample",
+                 # the CRNN front end's inference plan (ecgmm.inference.Predictor(CRNN), csrc/plan_infer.hip)
+                 "ecgmm_relu_maxpool2", "ecgmm_conv5_in1_relu_pool2", "ecgmm_fold_conv5_bn",
+                 "ecgmm_crnn_front_infer_prepared_bytes", "ecgmm_crnn_front_infer_prepare",
+                 "ecgmm_crnn_front_infer_workspace", "ecgmm_crnn_front_infer")
 
 _lib = None
 

@@ -22,11 +22,17 @@ was trained further: call :meth:`Predictor.refresh` after the weights changed (`
 Until then it keeps returning the answer of the weights it was prepared from.  The snapshot covers both encoders and
 the multimodal head; the clinical branch (a few small dense layers, or TabNet) runs the model's own eval forward on the
 live parameters.
+
+**The spectrogram CRNN** (``ecgmm.crnn.CRNN``, ``train_physionet2``): ``Predictor(model)(x, lengths=None)``.  The three
+ConvBlocks run as ``ecgmm_crnn_front_infer`` (csrc/plan_infer.hip: block 1 as one conv + ReLU + pool kernel, no
+``[B, F, T, 32]`` tensor, no argmax bytes, no per-call weight packs); the LSTM (no saves), the mean over time and the
+classifier run on snapshots of their parameters, so the whole answer is stale until ``refresh()``.
 """
 import ctypes as C
 
 import torch
 
+from .crnn import CRNN
 from .hip import encoders as E
 from .hip import lib as L
 from .hip.functional import _Scratch, _require_cuda, f32c, new_bytes, ptr, stream
@@ -114,6 +120,90 @@ class _EncoderPlan:
         return int(getattr(L.lib(), self.prefix + "_infer_workspace")(C.byref(desc)))
 
 
+class _CRNNPlan:
+    """The spectrogram ``CRNN`` (ecgmm/crnn.py): the three ConvBlocks through ``ecgmm_crnn_front_infer`` (folded blob, 5
+    launches, no ``[B, F, T, 32]`` tensor), then the LSTM, the mean over time and the classifier on ``detach().clone()``
+    snapshots of their parameters -- so the WHOLE answer is that of the weights the plan was prepared from."""
+
+    def __init__(self, model):
+        self.model = model
+        cls = list(model.classifier)
+        if len(cls) != 4 or not isinstance(cls[1], torch.nn.ReLU) or not isinstance(cls[2], torch.nn.Dropout):
+            raise RuntimeError("Predictor(CRNN): the classifier is not the Linear-ReLU-Dropout-Linear layout")
+        self.blob = None
+        self.refresh()
+
+    def _desc(self, B, F, T):
+        return L.CRNNFrontDesc(B, F, T, self.dtype, 0, 0.0, self.eps)
+
+    def refresh(self):
+        m = self.model
+        params, buffers = m._front_tables()
+        lstm = [getattr(m.bilstm, n) for n in m.bilstm._flat_names]
+        dense = [m.classifier[0].weight, m.classifier[0].bias, m.classifier[3].weight, m.classifier[3].bias]
+        for t in params + buffers + lstm + dense:
+            _require_cuda(t, "Predictor(CRNN) parameter")
+        for p in params:
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError("Predictor(CRNN): parameters must be contiguous fp32")
+        self.dtype, self.eps = E.dtype_code(m.compute_dtype), float(m.conv1.block[1].eps)
+        lib = L.lib()
+        desc = self._desc(0, 0, 0)
+        nb = lib.ecgmm_crnn_front_infer_prepared_bytes(C.byref(desc))
+        if nb == 0:
+            L.check(1, "crnn_front prepared-size query")
+        dev = params[0].device
+        with torch.cuda.device(dev), torch.no_grad():
+            # a NEW blob and new snapshots: a forward already enqueued with the old ones keeps reading consistent weights
+            blob = new_bytes(nb, dev)
+            L.check(lib.ecgmm_crnn_front_infer_prepare(C.byref(desc), E._table(params), E._table(buffers), ptr(blob),
+                                                       blob.numel(), stream()), "crnn_front infer prepare")
+            self._lstm = [p.detach().clone() for p in lstm]
+            self._dense = [p.detach().clone() for p in dense]
+        self.blob = blob
+
+    def front(self, x):
+        """``x [B, 1, F, T]`` -> ``seq [B, T // 8, 128 * (F // 8)]`` fp32; the shape errors are ``CRNN._front``'s"""
+        m = self.model
+        _require_cuda(x, "Predictor(CRNN)")
+        if E.dtype_code(m.compute_dtype) != self.dtype:
+            raise RuntimeError(f"Predictor(CRNN): the model's compute dtype is now {m.compute_dtype!r} but the weights "
+                               "were prepared in another one -- call refresh()")
+        if x.dim() != 4 or x.shape[1] != 1:
+            raise ValueError(f"CRNN expects a log-spectrogram [B,1,F,T], got {tuple(x.shape)}")
+        B, _, F, T = x.shape
+        if 128 * (F // 8) != m.bilstm.input_size:
+            raise ValueError(f"CRNN: F={F} frequency bins give {128 * (F // 8)} features per time step after three 2x2 "
+                             f"pools, but the LSTM takes {m.bilstm.input_size} (F must be 32..39)")
+        if T < 8:
+            raise ValueError(f"CRNN: T={T} time bins; three 2x2 pools need at least 8")
+        x = f32c(x)
+        desc = self._desc(B, F, T)
+        lib = L.lib()
+        nb = lib.ecgmm_crnn_front_infer_workspace(C.byref(desc))
+        if nb == 0:
+            L.check(1, "crnn_front infer workspace query")
+        ws = _Scratch.get("ecgmm_crnn_front_infer", nb, x.device)   # transient: nothing in it outlives the call
+        self.blob.record_stream(torch.cuda.current_stream(x.device))
+        seq = torch.empty(B, T // 8, 128 * (F // 8), device=x.device, dtype=torch.float32)
+        L.check(lib.ecgmm_crnn_front_infer(C.byref(desc), ptr(x), ptr(self.blob), self.blob.numel(), ptr(seq), ptr(ws),
+                                           ws.numel(), stream()), "crnn_front infer")
+        return seq
+
+    def __call__(self, x, lengths=None):
+        from .hip import functional as HF
+        m = self.model
+        seq = self.front(x)
+        rnn = m.bilstm
+        if lengths is not None:   # CRNN._tail's rule: three floor pools give exactly // 8
+            lengths = HF.check_lengths(lengths, seq.shape[0], x.shape[3]).to(seq.device)
+            lengths = torch.clamp(lengths // 8, 1, seq.shape[1]).to(torch.int32)
+        # under no_grad nothing requires a gradient, so the LSTM keeps no saves (save = 0)
+        out, _ = HF.lstm(seq, None, self._lstm, rnn.hidden_size, rnn.num_layers, rnn.bidirectional, rnn.batch_first, lengths)
+        w1, b1, w2, b2 = self._dense
+        return HF.linear(HF.linear(HF.seq_mean(out, lengths), w1, b1, L.ACT_RELU), w2, b2)   # eval: no dropout
+
+
 def _find_encoder(model):
     if isinstance(model, (ResNet18, ResNet1D_SE)):
         return model
@@ -126,23 +216,27 @@ def _find_encoder(model):
 class Predictor:
     """Eval-mode forward of ``model`` through the inference plans.
 
-    ``model``: an ``ECGMultimodalModel`` (either variant), a ``ResNet18`` / ``ImageOnlyClassifier`` or a ``ResNet1D_SE``,
-    on a ROCm device.  Construction prepares the folded weights; :meth:`refresh` prepares them again (see the module
-    docstring: nothing can detect stale weights for you).  Calling the predictor never changes ``model.training``, a
-    running statistic or a ``.grad``.
+    ``model``: an ``ECGMultimodalModel`` (either variant), a ``ResNet18`` / ``ImageOnlyClassifier``, a ``ResNet1D_SE`` or
+    the spectrogram ``CRNN``, on a ROCm device.  Construction prepares the folded weights; :meth:`refresh` prepares them
+    again (see the module docstring: nothing can detect stale weights for you).  Calling the predictor never changes
+    ``model.training``, a running statistic or a ``.grad``.  A ``CRNN`` predictor is called as the model is,
+    ``predictor(x, lengths=None)``; its snapshot covers the front end, the LSTM and the classifier.
     """
 
     def __init__(self, model):
         self.model = model
         self.multimodal = isinstance(model, ECGMultimodalModel)
-        if self.multimodal:
+        self.crnn = isinstance(model, CRNN)
+        if self.crnn:
+            self.encoder = _CRNNPlan(model)
+        elif self.multimodal:
             self.image, self.signal = _EncoderPlan(model.image_encoder), _EncoderPlan(model.signal_encoder)
             self._snapshot_head()
         else:
             enc = _find_encoder(model)
             if enc is None:
                 raise TypeError(f"Predictor: unsupported model {type(model).__name__} (ECGMultimodalModel, ResNet18, "
-                                "ImageOnlyClassifier or ResNet1D_SE)")
+                                "ImageOnlyClassifier, ResNet1D_SE or CRNN)")
             self.encoder = _EncoderPlan(enc)
 
     def _snapshot_head(self):
@@ -160,7 +254,15 @@ class Predictor:
         return self
 
     @torch.no_grad()
-    def __call__(self, *inputs):
+    def __call__(self, *inputs, lengths=None):
+        if self.crnn:
+            if len(inputs) == 2 and lengths is None:
+                inputs, lengths = inputs[:1], inputs[1]
+            if len(inputs) != 1:
+                raise TypeError(f"Predictor(CRNN) takes (spectrogram, lengths=None), got {len(inputs)} inputs")
+            return self.encoder(inputs[0], lengths)
+        if lengths is not None:
+            raise TypeError(f"Predictor({type(self.model).__name__}) takes no lengths")
         if not self.multimodal:
             if len(inputs) != 1:
                 raise TypeError(f"Predictor({type(self.model).__name__}) takes one input, got {len(inputs)}")
@@ -207,15 +309,20 @@ class Predictor:
         """Softmax probabilities of a whole loader, in loader order.
 
         Batches are ``(*inputs, labels)`` or ``(*inputs, labels, index)`` with three inputs for the multimodal model and
-        one otherwise (the dataset classes of this package).  -> ``(prob [n, classes], labels [n], index [n])`` CPU
-        tensors; without an index column the index is the running position."""
+        one otherwise (the dataset classes of this package); for a ``CRNN`` the one input is the spectrogram or the pair
+        ``(spectrogram, frames)`` a loader with lengths yields (``train_physionet2.DeviceSpectrogramLoader``).
+        -> ``(prob [n, classes], labels [n], index [n])`` CPU tensors; without an index column the index is the running
+        position."""
         n_in = 3 if self.multimodal else 1
         device = device or next(self.model.parameters()).device
         probs, labels, index, seen = [], [], [], 0
         for batch in loader:
             if len(batch) not in (n_in + 1, n_in + 2):
                 raise ValueError(f"predict_proba: a batch of {len(batch)} tensors; expected {n_in} inputs, labels[, index]")
-            logits = self.logits(*(t.to(device) for t in batch[:n_in]))
+            inputs = batch[:n_in]
+            if self.crnn and isinstance(inputs[0], (tuple, list)):   # ((spec, frames), labels)
+                inputs = tuple(inputs[0])
+            logits = self.logits(*(t.to(device) for t in inputs))
             probs.append(torch.softmax(logits.float().cpu(), dim=1))
             labels.append(torch.as_tensor(batch[n_in]).cpu())
             b = probs[-1].shape[0]

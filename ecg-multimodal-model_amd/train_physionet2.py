@@ -18,6 +18,9 @@ record's own frame count to ``CRNN.forward(x, lengths)``, so the BiLSTM stops wh
 leaves the padding out; each batch's rows are then ordered by length (:class:`DeviceSpectrogramLoader`).  Off by default:
 the reference runs through the padding.  NEW: ``main(saliency_samples=k)`` / ``config.physionet2_saliency_samples`` writes the
 input gradients and the Grad-CAM maps of the first ``k`` test spectrograms beside the checkpoints (off by default).
+NEW: ``main(use_predictor=True)`` / ``config.physionet2_use_predictor`` runs the validation and test passes through
+``ecgmm.inference.Predictor`` (the front end's BatchNorm-folded inference plan) instead of the training plan's eval mode
+(off by default).
 """
 import numpy as np
 import torch
@@ -131,22 +134,36 @@ def get_spectrogram_dataloaders(config=Config, batch_size=None, label_map=LABEL_
             DeviceSpectrogramLoader(SpectrogramDataset(test_idx, labels, spec, frames), batch_size))
 
 
-def evaluate(model, loader):
+def predict_split(model, loader, predictor=None):
+    """-> (labels [n], softmax probabilities [n, 2], argmax predictions [n]) of the split, numpy, from the model's eval
+    forward or, with ``predictor`` (an ``ecgmm.inference.Predictor`` of ``model``), from its inference plan."""
+    model.eval()
+    forward = model if predictor is None else predictor
+    # a loader with frames yields (spec, frames) as the inputs
+    y_true, y_prob, y_pred, _ = T.predict(lambda inputs: forward(*inputs) if isinstance(inputs, tuple) else forward(inputs), loader)
+    return y_true, y_prob, y_pred
+
+
+def evaluate(model, loader, predictor=None):
     """train_physionet2.py:233-257: argmax predictions and the class-1 softmax probability of the split ->
     accuracy / binary F1 / ROC-AUC (NaN where sklearn cannot define it: one class only)."""
-    model.eval()
-    # a loader with frames yields (spec, frames) as the inputs
-    y_true, y_prob, y_pred, _ = T.predict(lambda inputs: model(*inputs) if isinstance(inputs, tuple) else model(inputs), loader)
+    y_true, y_prob, y_pred = predict_split(model, loader, predictor)
     return T.binary_metrics(y_true, y_prob[:, 1], y_pred)
 
 
-def main(config=Config, num_epochs=None, batch_size=None, quiet=False, use_lengths=False, saliency_samples=0):
+def main(config=Config, num_epochs=None, batch_size=None, quiet=False, use_lengths=False, saliency_samples=0,
+         use_predictor=False):
     """-> (history, {"best": metrics, "last": metrics}, checkpoint directory).  ``use_lengths`` or
     ``config.physionet2_use_lengths`` (both off by default): the CRNN gets every record's own length (module docstring).
     ``saliency_samples=k`` > 0 (or ``config.physionet2_saliency_samples``): after the test pass, with the weights it ended
     on, ``spectrogram_saliency.npz`` is written into the run directory for the first ``k`` test records
-    (:func:`write_spectrogram_saliency`).  The default 0 writes nothing."""
+    (:func:`write_spectrogram_saliency`).  The default 0 writes nothing.
+    ``use_predictor`` or ``config.physionet2_use_predictor`` (both off by default): the validation and test passes run
+    through an ``ecgmm.inference.Predictor`` (BatchNorm-folded inference plan of the front end, no saves), refreshed after
+    every training epoch and after every checkpoint load; the saliency dump keeps the model's own forward, which is what
+    a backward needs."""
     use_lengths = bool(use_lengths or getattr(config, "physionet2_use_lengths", False))
+    use_predictor = bool(use_predictor or getattr(config, "physionet2_use_predictor", False))
     saliency_samples = int(saliency_samples or getattr(config, "physionet2_saliency_samples", 0) or 0)
     if saliency_samples < 0:
         raise ValueError(f"saliency_samples={saliency_samples} must be >= 0")
@@ -162,9 +179,14 @@ def main(config=Config, num_epochs=None, batch_size=None, quiet=False, use_lengt
     optimizer = FusedAdam(model.parameters(), lr=config.lr)
     ckpt_dir = T.run_dir(config.checkpoint_dir)
 
-    def step(batch):
+    predictor = None
+    if use_predictor:
+        from .inference import Predictor
+        predictor = Predictor(model)
+
+    def step(batch, forward=model):
         spec, labels = batch
-        out = model(*spec) if use_lengths else model(spec)
+        out = forward(*spec) if use_lengths else forward(spec)
         return criterion(out, labels), out, labels
 
     def train_pass():
@@ -173,15 +195,16 @@ def main(config=Config, num_epochs=None, batch_size=None, quiet=False, use_lengt
 
     def val_pass():
         model.eval()
-        return T.run_epoch(val_loader, step)
+        return T.run_epoch(val_loader, step if predictor is None else lambda batch: step(batch, predictor))
 
     def on_epoch(h, _extras):
         if not quiet:
             print(f"[{h['epoch']}] train {h['train_loss']:.4f}/{h['train_acc']:.4f}  val {h['val_loss']:.4f}/{h['val_acc']:.4f}")
 
     # train_physionet2.py:220-222: best.pth on a lower validation loss; no scheduler, no early stop
-    history = T.fit(model, optimizer, train_pass, val_pass, ckpt_dir, num_epochs, on_epoch=on_epoch)
-    results = T.test_checkpoints(model, ckpt_dir, ("best", "last"), lambda: evaluate(model, test_loader))
+    history = T.fit(model, optimizer, train_pass, val_pass, ckpt_dir, num_epochs, predictor=predictor, on_epoch=on_epoch)
+    results = T.test_checkpoints(model, ckpt_dir, ("best", "last"),
+                                 lambda: evaluate(model, test_loader, predictor=predictor), predictor)
     if not quiet:
         for tag, res in results.items():
             print(f"test[{tag}]: {res}")

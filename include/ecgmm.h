@@ -823,6 +823,40 @@ int ecgmm_crnn_front_backward_dx(const ecgmm_crnn_front_desc* d, const float* sp
                                  const void* const* params, void* const* grads, void* ws_fwd, void* ws_bwd,
                                  size_t ws_bwd_bytes, float* dspec, void* stream);
 
+/* ---- inference forms of the CRNN front end: every BatchNorm folded into its convolution (eval mode, no backward) ----
+ * nn.ReLU + nn.MaxPool2d(2) (train_physionet2.py:61-62) behind a convolution that already carries its BatchNorm:
+ * ecgmm_bnrelu_maxpool2 without coefficients and without argmax bytes, out = max(0, max of the 2x2 window), floor
+ * semantics.  y [N,H,W,C] compute dtype; out [N,H/2,W/2,C] compute dtype or, with seq_layout != 0, the fp32 LSTM layout
+ * seq[n][w][c * (H/2) + h].  C: any multiple of 8 (bf16) / 4 (fp32); y (and a channels-last out) 16-byte aligned.
+ * A bad dtype, H < 2, W < 2 and null operands are refused with a message. */
+int ecgmm_relu_maxpool2(int dtype, const void* y, void* out, int N, int H, int W, int C, int seq_layout, void* stream);
+/* train_physionet2.py:57-62 of the first block, BatchNorm folded into w / bias: Conv2d(1, 32, 5, pad 2) + bias + ReLU +
+ * MaxPool2d(2) as ONE kernel.  x [N,H,W] fp32, w_oihw [32,1,5,5] fp32 (rounded to bf16 under ECGMM_BF16, as
+ * ecgmm_conv5_in1_fwd rounds it), bias [32] fp32 (nullable), out [N,H/2,W/2,32] compute dtype (16-byte aligned).  Bit for
+ * bit ecgmm_conv5_in1_fwd(stats = NULL) followed by ecgmm_relu_maxpool2 (for finite weights), without the [N,H,W,32]
+ * tensor: no conv output of a row / column the floor drops is computed.  H, W >= 2. */
+int ecgmm_conv5_in1_relu_pool2(int dtype, const float* x, const float* w_oihw, const float* bias, void* out, int N, int H,
+                               int W, void* stream);
+/* ecgmm_fold_conv_bn for a 5x5 convolution (25 taps): layout 0 = the forward pack [Cout][25][Cin] in the compute dtype
+ * (what ecgmm_conv_fwd_fused reads), layout 1 = OIHW fp32 whatever the dtype (what ecgmm_conv5_in1_* read: those kernels
+ * round their operands themselves, so that stays the single rounding).  Same formulas, same nullable operands. */
+int ecgmm_fold_conv5_bn(int dtype, int layout, const float* w, const float* conv_bias, const float* gamma, const float* beta,
+                        const float* running_mean, const float* running_var, float eps, void* w_out, float* b_out,
+                        float* scale_out, int Cout, int Cin, void* stream);
+/* The three blocks as an inference plan, in the shape of ecgmm_resnet1d_infer*: prepare folds the 12 parameters and 9
+ * buffers of ecgmm_crnn_front_forward into a blob (one launch; the blob depends on dtype and bn_eps, not on B, F, T: fp32
+ * folded conv1 weight, packed folded weights of blocks 2 and 3 in the compute dtype, three fp32 biases); infer reads the
+ * blob and the spectrogram alone and writes seq_out [B, T/8, 128 * (F/8)] fp32 in 5 launches.  The workspace holds the two
+ * pooled tensors and the conv outputs of blocks 2 and 3 -- no [B,F,T,32] tensor, no argmax bytes, no statistics rows.
+ * desc.training and desc.bn_momentum are ignored.  F < 8, T < 8, an unknown dtype, null operands, a short blob or
+ * workspace are refused with a message; the size queries need no GPU and return 0 on a bad descriptor. */
+size_t ecgmm_crnn_front_infer_prepared_bytes(const ecgmm_crnn_front_desc* d);
+int ecgmm_crnn_front_infer_prepare(const ecgmm_crnn_front_desc* d, const void* const* params, const void* const* buffers,
+                                   void* blob, size_t blob_bytes, void* stream);
+size_t ecgmm_crnn_front_infer_workspace(const ecgmm_crnn_front_desc* d);
+int ecgmm_crnn_front_infer(const ecgmm_crnn_front_desc* d, const float* spec, const void* blob, size_t blob_bytes,
+                           float* seq_out, void* ws, size_t ws_bytes, void* stream);
+
 /* Grad-CAM of the CRNN's last ConvBlock on the spectrogram (csrc/gradcam.hip).  There is no global average pool in front of
  * the CRNN's head, so the gradient varies over space and is an operand: seq, dseq [B][Tp][C*Fp] fp32 are the front end's
  * output and the gradient of the chosen logit w.r.t. it, feature index c*Fp + f (permute(0,3,1,2) + Flatten(2) of the
