@@ -297,6 +297,17 @@ int ecg_pool2_bn_bwd(int dtype, const void* dp, const unsigned char* idx, const 
                      float* dgamma, float* dbeta, void* dy, float* dbias, int N, int H, int W, int C, int seq_layout, void* ws,
                      size_t ws_bytes, hipStream_t s);
 
+// transformer_infer.hip: the forward-only tails of a post-norm encoder layer (exact-fp32 MFMA, a wave owns 16 whole rows):
+// out = LayerNorm(res + a W^T + bias) and out = LayerNorm(x + relu(x W1^T + b1) W2^T + b2); 16 <= E <= 256, K / FF <= 4096,
+// all multiples of 16; every operand 16-byte aligned; out must not alias an input
+int ecg_linear_res_ln(const float* a, const float* w, const float* bias, const float* res, const float* gamma,
+                      const float* beta, float* out, long R, int K, int E, float eps, hipStream_t s);
+int ecg_ffn_res_ln(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* gamma,
+                   const float* beta, float* out, long R, int E, int FF, float eps, hipStream_t s);
+// out[b][ci][l] = l < lengths[b] ? x[b][ci][l] : 0; and a constant int32 vector
+int ecg_mask_pad_rows(const float* x, const int* lengths, float* out, int B, int Cin, int L, hipStream_t s);
+int ecg_fill_i32(int* out, int v, int n, hipStream_t s);
+
 // prof.hip
 enum { ECG_PROF_IGEMM_FWD = 0, ECG_PROF_IGEMM_DGRAD = 1, ECG_PROF_WGRAD = 2, ECG_PROF_STEM_FWD = 3, ECG_PROF_STEM_WGRAD = 4,
        ECG_PROF_IGEMM_F32_FWD = 5, ECG_PROF_IGEMM_F32_DGRAD = 6 };  // exact-fp32 instantiation (other MFMA peak): own kinds

@@ -14,7 +14,8 @@
 // ResNet1D_SE block: a1 as above; y2 = conv2'(a1) + b2'; gate = SE(mean_L y2); [yd]; out = relu(y2 * gate + (yd | x)) in
 //   place.  The squeeze needs the whole y2 of a sample, so that last pass cannot be a convolution epilogue.
 // Stem: stem_fwd(w', b') -> relu_maxpool (no coefficients, no argmax bytes).
-// CRNN front end (at the end of this file): three folded 5x5 blocks, conv + max(0, 2x2 max-pool), block 1 as one kernel.
+// CRNN front end (behind the encoders): three folded 5x5 blocks, conv + max(0, 2x2 max-pool), block 1 as one kernel.
+// ECGTransformer1D (at the end of this file): four launches per encoder layer on the fused tails of transformer_infer.hip.
 //
 // Workspace: the stem output, the pooled tensor and a fixed set of rotating block buffers of the largest block activation
 // instead of one saved set per block; the rotating buffers alias the stem output, which is dead once the max-pool has read it.
@@ -499,4 +500,193 @@ extern "C" int ecgmm_crnn_front_infer(const ecgmm_crnn_front_desc* d, const floa
     ECG_TRY(ecg_relu_maxpool2(dt, w.y[i], i < 2 ? w.pool[i] : (void*)seq_out, B, k.h, k.w, k.cout, i == 2, s));
   }
   return 0;
+}
+
+// ---- ECGTransformer1D ----------------------------------------------------------------------------------------------
+// The eval forward of `ECGTransformer1D` (train_physionet.py:211-240): embed, then per layer FOUR launches -- in_proj,
+// attention, out_proj + residual + norm1 (ecg_linear_res_ln), feed-forward + residual + norm2 (ecg_ffn_res_ln) -- where the
+// training composition of ecgmm.hip.nn.TransformerEncoderLayer takes nine, then the mean over the positions and the
+// Linear-ReLU-Linear classifier.  Nothing is kept for a backward: three [R, E] buffers rotate through all layers (x, the
+// attention output, the next x), qkv and lse are reused by every layer and the [R, ff] hidden activation never exists.
+namespace {
+
+constexpr int TFM_HIDDEN = 64;        // the classifier's hidden width (train_physionet.py:227)
+constexpr int TFM_LAYER_PARAMS = 12;
+
+int buildt_static(const ecgmm_transformer_infer_desc* d, const char* who) {
+  if (!d) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: null descriptor", who);
+  if (d->layers < 1 || d->layers > 64) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: layers=%d (needs 1 <= layers <= 64)", who, d->layers);
+  if (d->classes < 1 || d->classes > 4096) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: classes=%d (needs 1 <= classes <= 4096)", who, d->classes);
+  if (d->input_dim < 1 || d->input_dim > 12)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "%s: input_dim=%d (needs 1 <= input_dim <= 12)", who, d->input_dim);
+  if (d->E < 16 || d->E > 256 || d->E % 16)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "%s: E=%d (needs a multiple of 16 with 16 <= E <= 256)", who, d->E);
+  if (d->ff < 16 || d->ff > 4096 || d->ff % 16)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "%s: ff=%d (needs a multiple of 16 with 16 <= ff <= 4096)", who, d->ff);
+  if (d->heads < 1 || d->E % d->heads || (d->E / d->heads != 16 && d->E / d->heads != 32))
+    ECG_FAIL(ECGMM_ERR_SHAPE, "%s: heads=%d with E=%d (E / heads must be 16 or 32)", who, d->heads, d->E);
+  if (d->batch_first != 0 && d->batch_first != 1) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: batch_first=%d (0 or 1)", who, d->batch_first);
+  if (!(d->eps >= 0.f)) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: eps %g (needs eps >= 0)", who, (double)d->eps);
+  if (d->L < 1 || d->L > (1 << 24)) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: L=%d (needs 1 <= L <= 2^24)", who, d->L);
+  return 0;
+}
+int buildt(const ecgmm_transformer_infer_desc* d, const char* who) {
+  ECG_TRY(buildt_static(d, who));
+  if (d->B < 1 || d->B > 65535) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: B=%d (needs 1 <= B <= 65535)", who, d->B);
+  if ((double)d->B * d->L * 3.0 * d->E > 2147483647.0)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "%s: B * L * 3E = %.0f elements is too large", who, (double)d->B * d->L * 3.0 * d->E);
+  return 0;
+}
+
+struct BlobT {
+  struct Layer { float *in_w, *in_b, *out_w, *out_b, *w1, *b1, *w2, *b2, *g1, *be1, *g2, *be2; };
+  float *conv_w, *conv_b, *cw1, *cb1, *cw2, *cb2, *pos;
+  size_t bytes;
+};
+// entry i of the parameter table <-> (destination, floats), in the table's order; the positional table is the blob's LAST
+// entry, so every other offset is independent of L
+struct CopyT { float* dst; size_t n; };
+int layout_blobt(const ecgmm_transformer_infer_desc& d, void* base, BlobT& q, CopyT* items) {
+  Arena a(base);
+  const size_t E = d.E, ff = d.ff;
+  int n = 0;
+  auto take = [&](size_t count, int slot) {
+    float* p = a.take<float>(count);
+    if (items) items[slot] = {p, count};
+    return p;
+  };
+  q.conv_w = take(E * d.input_dim * 3, 0);
+  q.conv_b = take(E, 1);
+  n = 3;
+  for (int l = 0; l < d.layers; ++l) {
+    const size_t sizes[TFM_LAYER_PARAMS] = {3 * E * E, 3 * E, E * E, E, ff * E, ff, E * ff, E, E, E, E, E};
+    for (int j = 0; j < TFM_LAYER_PARAMS; ++j) take(sizes[j], n++);
+  }
+  q.cw1 = take(TFM_HIDDEN * E, n++);
+  q.cb1 = take(TFM_HIDDEN, n++);
+  q.cw2 = take((size_t)d.classes * TFM_HIDDEN, n++);
+  q.cb2 = take(d.classes, n++);
+  q.pos = take((size_t)d.L * E, 2);
+  q.bytes = align_up(a.off, 256);
+  return n;
+}
+// the layers' tensors again, from the same walk (the Arena is deterministic): layer l of a blob at `base`
+BlobT::Layer blobt_layer(const ecgmm_transformer_infer_desc& d, void* base, int layer) {
+  Arena a(base);
+  const size_t E = d.E, ff = d.ff;
+  a.take<float>(E * d.input_dim * 3);
+  a.take<float>(E);
+  BlobT::Layer k = {};
+  for (int l = 0; l <= layer; ++l) {
+    k.in_w = a.take<float>(3 * E * E); k.in_b = a.take<float>(3 * E);
+    k.out_w = a.take<float>(E * E);    k.out_b = a.take<float>(E);
+    k.w1 = a.take<float>(ff * E);      k.b1 = a.take<float>(ff);
+    k.w2 = a.take<float>(E * ff);      k.b2 = a.take<float>(E);
+    k.g1 = a.take<float>(E);           k.be1 = a.take<float>(E);
+    k.g2 = a.take<float>(E);           k.be2 = a.take<float>(E);
+  }
+  return k;
+}
+
+// x / nxt / att: [R, E] each (att first holds the zero-padded copy of the raw input: input_dim <= 12 < E); qkv [R, 3E];
+// lse [R heads]; the tail's [B, E], [B, 64] and [B] int32.  Nothing here depends on layers or on ff.
+struct WsT {
+  float *x, *nxt, *att, *qkv, *lse, *pooled, *h1;
+  int* lens;
+  size_t bytes;
+};
+void layout_wst(const ecgmm_transformer_infer_desc& d, void* base, WsT& w) {
+  Arena a(base);
+  const size_t R = (size_t)d.B * d.L, E = d.E;
+  w.x = a.take<float>(R * E);
+  w.nxt = a.take<float>(R * E);
+  w.att = a.take<float>(R * E);
+  w.qkv = a.take<float>(R * 3 * E);
+  w.lse = a.take<float>(R * d.heads);
+  w.pooled = a.take<float>((size_t)d.B * E);
+  w.h1 = a.take<float>((size_t)d.B * TFM_HIDDEN);
+  w.lens = a.take<int>(d.B);
+  w.bytes = align_up(a.off, 256);
+}
+inline bool avgpool_width_ok(int C) { return C % 4 == 0 && 256 % (C / 4) == 0; }   // the widths ecg_avgpool takes in fp32
+
+}  // namespace
+
+extern "C" size_t ecgmm_transformer_infer_prepared_bytes(const ecgmm_transformer_infer_desc* d) {
+  if (buildt_static(d, "transformer infer")) return 0;
+  BlobT q;
+  layout_blobt(*d, nullptr, q, nullptr);
+  return q.bytes;
+}
+
+extern "C" int ecgmm_transformer_infer_prepare(const ecgmm_transformer_infer_desc* d, const void* const* params, void* blob,
+                                               size_t blob_bytes, void* stream_) {
+  ECG_TRY(buildt_static(d, "transformer infer prepare"));
+  const int np = 3 + TFM_LAYER_PARAMS * d->layers + 4;
+  if (!params) ECG_FAIL(ECGMM_ERR_SHAPE, "transformer infer prepare: null parameter table");
+  for (int i = 0; i < np; ++i)
+    if (!params[i]) ECG_FAIL(ECGMM_ERR_SHAPE, "transformer infer prepare: parameter %d is null", i);
+  BlobT q;
+  CopyT items[3 + TFM_LAYER_PARAMS * 64 + 4];
+  layout_blobt(*d, blob, q, items);
+  ECG_NEED(blob, blob_bytes, q.bytes, "transformer infer prepare: blob");
+  for (int i = 0; i < np; ++i) {
+    hipError_t e = hipMemcpyAsync(items[i].dst, params[i], items[i].n * sizeof(float), hipMemcpyDeviceToDevice,
+                                  (hipStream_t)stream_);
+    if (e != hipSuccess) ECG_FAIL(ECGMM_ERR_LAUNCH, "transformer infer prepare: copy of parameter %d: %s", i, hipGetErrorString(e));
+  }
+  return 0;
+}
+
+extern "C" size_t ecgmm_transformer_infer_workspace(const ecgmm_transformer_infer_desc* d) {
+  if (buildt(d, "transformer infer")) return 0;
+  WsT w;
+  layout_wst(*d, nullptr, w);
+  return w.bytes;
+}
+
+extern "C" int ecgmm_transformer_infer(const ecgmm_transformer_infer_desc* d, const float* x, const int32_t* lengths,
+                                       const void* blob, size_t blob_bytes, float* logits, void* ws, size_t ws_bytes,
+                                       void* stream_) {
+  hipStream_t s = (hipStream_t)stream_;
+  ECG_TRY(buildt(d, "transformer infer"));
+  if (!x || !logits) ECG_FAIL(ECGMM_ERR_SHAPE, "transformer infer: null input / output");
+  if (lengths && !d->batch_first)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "transformer infer: lengths need batch_first = 1 (attention across the batch has no per-record length)");
+  BlobT q;
+  layout_blobt(*d, const_cast<void*>(blob), q, nullptr);
+  ECG_NEED(blob, blob_bytes, q.bytes, "transformer infer: blob");
+  WsT w;
+  layout_wst(*d, ws, w);
+  ECG_NEED(ws, ws_bytes, w.bytes, "transformer infer: workspace");
+  const int B = d->B, L = d->L, E = d->E;
+  const long R = (long)B * L;
+
+  if (lengths) {   // the conv's right tap at a record's last live position reads the first padded sample
+    ECG_TRY(ecg_mask_pad_rows(x, lengths, w.att, B, d->input_dim, L, s));
+    x = w.att;
+  }
+  ECG_TRY(ecgmm_embed1d_fwd(x, q.conv_w, q.conv_b, q.pos, w.x, B, d->input_dim, L, E, stream_));
+  ecgmm_mha_desc m = {};
+  m.S = d->batch_first ? L : B;
+  m.N = d->batch_first ? B : L;
+  m.heads = d->heads; m.head_dim = E / d->heads; m.batch_first = d->batch_first; m.p_drop = 0.f;
+  for (int l = 0; l < d->layers; ++l) {
+    const BlobT::Layer k = blobt_layer(*d, const_cast<void*>(blob), l);
+    ECG_TRY(ecg_linear_fwd(w.x, k.in_w, k.in_b, w.qkv, (int)R, E, 3 * E, 0, nullptr, s));
+    if (lengths) ECG_TRY(ecgmm_mha_forward_varlen(&m, w.qkv, lengths, w.att, w.lse, 0, 0, stream_));
+    else ECG_TRY(ecgmm_mha_forward(&m, w.qkv, w.att, w.lse, 0, 0, stream_));
+    ECG_TRY(ecg_linear_res_ln(w.att, k.out_w, k.out_b, w.x, k.g1, k.be1, w.nxt, R, E, E, d->eps, s));
+    ECG_TRY(ecg_ffn_res_ln(w.nxt, k.w1, k.b1, k.w2, k.b2, k.g2, k.be2, w.x, R, E, d->ff, d->eps, s));
+  }
+  if (lengths) {
+    ECG_TRY(ecg_seq_mean_varlen_fwd(w.x, lengths, w.pooled, B, L, E, s));
+  } else if (avgpool_width_ok(E)) {
+    ECG_TRY(ecg_avgpool(ECGMM_F32, w.x, w.pooled, B, L, E, nullptr, s));
+  } else {   // a width the pooling kernel does not take: the masked mean over every record's full length
+    ECG_TRY(ecg_fill_i32(w.lens, L, B, s));
+    ECG_TRY(ecg_seq_mean_varlen_fwd(w.x, w.lens, w.pooled, B, L, E, s));
+  }
+  ECG_TRY(ecg_linear_fwd(w.pooled, q.cw1, q.cb1, w.h1, B, E, TFM_HIDDEN, ECGMM_ACT_RELU, nullptr, s));
+  return ecg_linear_fwd(w.h1, q.cw2, q.cb2, logits, B, TFM_HIDDEN, d->classes, 0, nullptr, s);
 }

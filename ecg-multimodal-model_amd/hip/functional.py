@@ -1099,3 +1099,56 @@ class Embed1dFn(torch.autograd.Function):
 
 def embed1d(x, weight, bias, pos):
     return Embed1dFn.apply(x, weight, bias, pos)
+
+
+# --------------------------------------------------------------------------------------------
+# forward-only tails of a post-norm encoder layer (csrc/transformer_infer.hip)     reference: train_physionet.py:219-220, 236
+# --------------------------------------------------------------------------------------------
+def _forward_only(what, tensors):
+    """the fused tails keep nothing for a backward: refuse an input that would want one"""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError(f"{what} is forward-only (it saves nothing for a backward): call it under torch.no_grad() or "
+                           "detach its inputs; training goes through ecgmm.hip.nn.TransformerEncoderLayer")
+    out = []
+    for t in tensors:
+        _require_cuda(t, what)
+        out.append(_aligned16(f32c(t.detach())))
+    return out
+
+
+def linear_res_ln(a, weight, bias, res, gamma, beta, eps=1e-5):
+    """``LayerNorm(res + a @ weight.T + bias)`` over the last axis as ONE launch (``ecgmm_linear_res_ln``): ``a`` [R, K],
+    ``weight`` [E, K], ``res`` [R, E] -> [R, E] -- ``out_proj`` + residual + ``norm1`` of an encoder layer in eval mode.
+    Forward-only.  ``E`` a multiple of 16 up to 256, ``K`` a multiple of 16 up to 4096."""
+    a, weight, bias, res, gamma, beta = _forward_only("linear_res_ln", (a, weight, bias, res, gamma, beta))
+    if a.dim() != 2 or weight.dim() != 2 or res.dim() != 2 or a.shape[1] != weight.shape[1] or \
+            tuple(res.shape) != (a.shape[0], weight.shape[0]):
+        raise RuntimeError(f"linear_res_ln: a {tuple(a.shape)}, weight {tuple(weight.shape)}, res {tuple(res.shape)}: need "
+                           "[R, K], [E, K] and [R, E]")
+    E = weight.shape[0]
+    for name, t in (("bias", bias), ("gamma", gamma), ("beta", beta)):
+        if tuple(t.shape) != (E,):
+            raise RuntimeError(f"linear_res_ln: {name} {tuple(t.shape)} must be [{E}]")
+    out = torch.empty_like(res)
+    L.check(L.lib().ecgmm_linear_res_ln(ptr(a), ptr(weight), ptr(bias), ptr(res), ptr(gamma), ptr(beta), ptr(out), a.shape[0],
+                                        a.shape[1], E, float(eps), stream()), "linear_res_ln")
+    return out
+
+
+def ffn_res_ln(x, w1, b1, w2, b2, gamma, beta, eps=1e-5):
+    """``LayerNorm(x + relu(x @ w1.T + b1) @ w2.T + b2)`` as ONE launch (``ecgmm_ffn_res_ln``): ``x`` [R, E], ``w1`` [ff, E],
+    ``w2`` [E, ff] -> [R, E] -- the feed-forward block + residual + ``norm2`` of an encoder layer in eval mode; the hidden
+    activation is never stored.  Forward-only.  ``E`` a multiple of 16 up to 256, ``ff`` a multiple of 16 up to 4096."""
+    x, w1, b1, w2, b2, gamma, beta = _forward_only("ffn_res_ln", (x, w1, b1, w2, b2, gamma, beta))
+    if x.dim() != 2 or w1.dim() != 2 or w2.dim() != 2 or w1.shape[1] != x.shape[1] or \
+            tuple(w2.shape) != (x.shape[1], w1.shape[0]):
+        raise RuntimeError(f"ffn_res_ln: x {tuple(x.shape)}, w1 {tuple(w1.shape)}, w2 {tuple(w2.shape)}: need [R, E], [ff, E] "
+                           "and [E, ff]")
+    E, ff = x.shape[1], w1.shape[0]
+    for name, t, n in (("b1", b1, ff), ("b2", b2, E), ("gamma", gamma, E), ("beta", beta, E)):
+        if tuple(t.shape) != (n,):
+            raise RuntimeError(f"ffn_res_ln: {name} {tuple(t.shape)} must be [{n}]")
+    out = torch.empty_like(x)
+    L.check(L.lib().ecgmm_ffn_res_ln(ptr(x), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(gamma), ptr(beta), ptr(out), x.shape[0], E,
+                                     ff, float(eps), stream()), "ffn_res_ln")
+    return out

@@ -50,6 +50,10 @@ class CRNNFrontDesc(C.Structure):
     _fields_ = [("B", i32), ("F", i32), ("T", i32), ("dtype", i32), ("training", i32), ("bn_momentum", f32), ("bn_eps", f32)]
 
 
+class TransformerInferDesc(C.Structure):
+    _fields_ = [(n, i32) for n in ("B", "L", "input_dim", "E", "heads", "ff", "layers", "classes", "batch_first")] + [("eps", f32)]
+
+
 P = C.POINTER
 # name -> (restype, argtypes).  Must list every function declared in include/ecgmm.h
 # (tests/test_abi.py parses the header and checks the two agree).
@@ -262,6 +266,12 @@ SIGNATURES = {
     "ecgmm_embed1d_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "ecgmm_embed1d_bwd_workspace": (sz, [i32, i32, i32, i32]),
     "ecgmm_embed1d_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
+    "ecgmm_linear_res_ln": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, f32, vp]),
+    "ecgmm_ffn_res_ln": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, f32, vp]),
+    "ecgmm_transformer_infer_prepared_bytes": (sz, [P(TransformerInferDesc)]),
+    "ecgmm_transformer_infer_prepare": (i32, [P(TransformerInferDesc), P(vp), vp, sz, vp]),
+    "ecgmm_transformer_infer_workspace": (sz, [P(TransformerInferDesc)]),
+    "ecgmm_transformer_infer": (i32, [P(TransformerInferDesc), vp, vp, vp, sz, vp, vp, sz, vp]),
 }
 
 # Entry points of the input-gradient / Grad-CAM feature.  A library selected with ECGMM_LIB for an A/B run may predate them:
@@ -321,7 +331,10 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  # the CRNN front end's inference plan (ecgmm.inference.Predictor(CRNN), csrc/plan_infer.hip)
                  "ecgmm_relu_maxpool2", "ecgmm_conv5_in1_relu_pool2", "ecgmm_fold_conv5_bn",
                  "ecgmm_crnn_front_infer_prepared_bytes", "ecgmm_crnn_front_infer_prepare",
-                 "ecgmm_crnn_front_infer_workspace", "ecgmm_crnn_front_infer")
+                 "ecgmm_crnn_front_infer_workspace", "ecgmm_crnn_front_infer",
+                 # the transformer's fused layer tails and inference plan (ecgmm.inference.Predictor(ECGTransformer1D))
+                 "ecgmm_linear_res_ln", "ecgmm_ffn_res_ln", "ecgmm_transformer_infer_prepared_bytes",
+                 "ecgmm_transformer_infer_prepare", "ecgmm_transformer_infer_workspace", "ecgmm_transformer_infer")
 
 _lib = None
 

@@ -27,6 +27,14 @@ live parameters.
 ConvBlocks run as ``ecgmm_crnn_front_infer`` (csrc/plan_infer.hip: block 1 as one conv + ReLU + pool kernel, no
 ``[B, F, T, 32]`` tensor, no argmax bytes, no per-call weight packs); the LSTM (no saves), the mean over time and the
 classifier run on snapshots of their parameters, so the whole answer is stale until ``refresh()``.
+
+**The transformer** (``ecgmm.train_physionet.ECGTransformer1D``, both ``time_attention`` modes):
+``Predictor(model)(x, lengths=None)``.  The whole forward is ONE call of ``ecgmm_transformer_infer`` on a blob that holds a
+copy of every parameter: embed, then four launches per encoder layer (``in_proj``, attention, ``out_proj`` + residual +
+``norm1`` as ``ecgmm_linear_res_ln``, the feed-forward block + residual + ``norm2`` as ``ecgmm_ffn_res_ln``) where the
+model's own eval forward takes nine, the mean over the positions and the classifier.  The workspace rotates three
+``[B L, d_model]`` buffers through all layers; the ``[B L, dim_feedforward]`` hidden activation is never stored.  The
+attention records ``ecgmm.explain`` works from (``attention_sink``) are not offered: it keeps using the model's forward.
 """
 import ctypes as C
 
@@ -38,6 +46,7 @@ from .hip import lib as L
 from .hip.functional import _Scratch, _require_cuda, f32c, new_bytes, ptr, stream
 from .image_encoder import ResNet18
 from .multimodal_paper_modal_balance import ECGMultimodalModel, ResNet1D_SE
+from .train_physionet import ECGTransformer1D
 
 __all__ = ["Predictor"]
 
@@ -204,6 +213,109 @@ class _CRNNPlan:
         return HF.linear(HF.linear(HF.seq_mean(out, lengths), w1, b1, L.ACT_RELU), w2, b2)   # eval: no dropout
 
 
+class _TransformerPlan:
+    """``ECGTransformer1D`` (ecgmm/train_physionet.py) through ``ecgmm_transformer_infer`` (csrc/plan_infer.hip): one blob
+    with a copy of every parameter, four launches per encoder layer, rotating buffers -- the WHOLE answer is that of the
+    weights the plan was prepared from."""
+
+    LAYER = ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight", "self_attn.out_proj.bias",
+             "linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias", "norm1.weight", "norm1.bias", "norm2.weight",
+             "norm2.bias")
+
+    def __init__(self, model):
+        self.model = model
+        layers = list(model.transformer_encoder.layers)
+        attn = layers[0].self_attn
+        self.E, self.heads, self.ff = attn.embed_dim, attn.num_heads, layers[0].linear1.out_features
+        if self.E > 256 or self.E % 16:
+            raise ValueError(f"Predictor(ECGTransformer1D): d_model={self.E} is not supported by the fused layer tails (a "
+                             "multiple of 16 with d_model <= 256)")
+        if self.ff % 16 or self.ff > 4096:
+            raise ValueError(f"Predictor(ECGTransformer1D): dim_feedforward={self.ff} is not supported by the fused layer "
+                             "tails (a multiple of 16 with dim_feedforward <= 4096)")
+        cls = list(model.classifier)
+        if len(cls) != 5 or not isinstance(cls[2], torch.nn.ReLU) or not isinstance(cls[3], torch.nn.Dropout) or \
+                cls[1].out_features != 64:
+            raise RuntimeError("Predictor(ECGTransformer1D): the classifier is not the Flatten-Linear(64)-ReLU-Dropout-Linear "
+                               "layout")
+        self.blob = None
+        self.refresh()
+
+    def _params(self):
+        m = self.model
+        sd = dict(m.named_parameters())
+        names = ["conv.weight", "conv.bias", "pos_embedding"]
+        for i in range(len(m.transformer_encoder.layers)):
+            names += [f"transformer_encoder.layers.{i}.{n}" for n in self.LAYER]
+        names += ["classifier.1.weight", "classifier.1.bias", "classifier.4.weight", "classifier.4.bias"]
+        return [sd[n] for n in names]
+
+    def _desc(self, B, L_):
+        return L.TransformerInferDesc(B, L_, self.input_dim, self.E, self.heads, self.ff, self.layers, self.classes,
+                                      int(self.batch_first), self.eps)
+
+    def refresh(self):
+        m = self.model
+        params = self._params()
+        for p in params:
+            _require_cuda(p, "Predictor(ECGTransformer1D) parameter")
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError("Predictor(ECGTransformer1D): parameters must be contiguous fp32")
+        layers = list(m.transformer_encoder.layers)
+        eps = {float(n.eps) for k in layers for n in (k.norm1, k.norm2)}
+        if len(eps) != 1:
+            raise RuntimeError("Predictor(ECGTransformer1D): the LayerNorms do not share one eps")
+        self.input_dim, self.layers, self.classes = m.conv.in_channels, len(layers), m.classifier[4].out_features
+        self.batch_first, self.eps, self.seq_len = bool(m.time_attention), eps.pop(), m.pos_embedding.shape[1]
+        lib = L.lib()
+        desc = self._desc(0, self.seq_len)
+        nb = lib.ecgmm_transformer_infer_prepared_bytes(C.byref(desc))
+        if nb == 0:
+            L.check(1, "transformer prepared-size query")
+        dev = params[0].device
+        with torch.cuda.device(dev), torch.no_grad():
+            # a NEW blob: a forward already enqueued with the old one (another stream) keeps reading consistent weights
+            blob = new_bytes(nb, dev)
+            L.check(lib.ecgmm_transformer_infer_prepare(C.byref(desc), E._table(params), ptr(blob), blob.numel(), stream()),
+                    "transformer infer prepare")
+        self.blob, self._blob_len = blob, self.seq_len
+
+    def __call__(self, x, lengths=None):
+        from .hip import functional as HF
+        m = self.model
+        if lengths is not None and not self.batch_first:
+            raise ValueError("ECGTransformer1D: lengths needs time_attention=True (attention across the batch has no "
+                             "per-sample length)")
+        _require_cuda(x, "Predictor(ECGTransformer1D)")
+        if bool(m.time_attention) != self.batch_first:
+            raise RuntimeError("Predictor(ECGTransformer1D): the model's time_attention changed since the plan was prepared "
+                               "-- call refresh()")
+        if x.dim() != 3 or x.shape[1] != self.input_dim:
+            raise ValueError(f"ECGTransformer1D expects [B, {self.input_dim}, L], got {tuple(x.shape)}")
+        B, _, Ln = x.shape
+        if Ln > self._blob_len:
+            raise ValueError(f"ECGTransformer1D: L={Ln} exceeds seq_len={self._blob_len}")
+        if lengths is not None:
+            lengths = HF.check_lengths(lengths, B, Ln).to(x.device).contiguous()
+        x = f32c(x)
+        # the blob's positional table has seq_len rows and is its last entry: a shorter L reads the same blob
+        desc = self._desc(B, Ln)
+        lib = L.lib()
+        nb = lib.ecgmm_transformer_infer_workspace(C.byref(desc))
+        if nb == 0:
+            L.check(1, "transformer infer workspace query")
+        ws = _Scratch.get("ecgmm_transformer_infer", nb, x.device)   # transient: nothing in it outlives the call
+        self.blob.record_stream(torch.cuda.current_stream(x.device))
+        logits = torch.empty(B, self.classes, device=x.device, dtype=torch.float32)
+        L.check(lib.ecgmm_transformer_infer(C.byref(desc), ptr(x), ptr(lengths), ptr(self.blob), self.blob.numel(), ptr(logits),
+                                            ptr(ws), ws.numel(), stream()), "transformer infer")
+        return logits
+
+    def workspace_bytes(self, B, Ln):
+        """Bytes of the inference workspace for ``B`` records of ``Ln`` samples (no GPU work)."""
+        return int(L.lib().ecgmm_transformer_infer_workspace(C.byref(self._desc(B, Ln))))
+
+
 def _find_encoder(model):
     if isinstance(model, (ResNet18, ResNet1D_SE)):
         return model
@@ -216,19 +328,24 @@ def _find_encoder(model):
 class Predictor:
     """Eval-mode forward of ``model`` through the inference plans.
 
-    ``model``: an ``ECGMultimodalModel`` (either variant), a ``ResNet18`` / ``ImageOnlyClassifier``, a ``ResNet1D_SE`` or
-    the spectrogram ``CRNN``, on a ROCm device.  Construction prepares the folded weights; :meth:`refresh` prepares them
+    ``model``: an ``ECGMultimodalModel`` (either variant), a ``ResNet18`` / ``ImageOnlyClassifier``, a ``ResNet1D_SE``,
+    the spectrogram ``CRNN`` or an ``ECGTransformer1D`` (either ``time_attention`` mode), on a ROCm device.  Construction prepares the folded weights; :meth:`refresh` prepares them
     again (see the module docstring: nothing can detect stale weights for you).  Calling the predictor never changes
     ``model.training``, a running statistic or a ``.grad``.  A ``CRNN`` predictor is called as the model is,
-    ``predictor(x, lengths=None)``; its snapshot covers the front end, the LSTM and the classifier.
+    ``predictor(x, lengths=None)``; its snapshot covers the front end, the LSTM and the classifier.  So is an
+    ``ECGTransformer1D`` predictor (``lengths`` only with ``time_attention``); its snapshot covers every parameter.  It
+    refuses ``d_model > 256`` and a ``dim_feedforward`` that is no multiple of 16 or exceeds 4096 with a ``ValueError``.
     """
 
     def __init__(self, model):
         self.model = model
         self.multimodal = isinstance(model, ECGMultimodalModel)
         self.crnn = isinstance(model, CRNN)
+        self.transformer = isinstance(model, ECGTransformer1D)
         if self.crnn:
             self.encoder = _CRNNPlan(model)
+        elif self.transformer:
+            self.encoder = _TransformerPlan(model)
         elif self.multimodal:
             self.image, self.signal = _EncoderPlan(model.image_encoder), _EncoderPlan(model.signal_encoder)
             self._snapshot_head()
@@ -236,7 +353,7 @@ class Predictor:
             enc = _find_encoder(model)
             if enc is None:
                 raise TypeError(f"Predictor: unsupported model {type(model).__name__} (ECGMultimodalModel, ResNet18, "
-                                "ImageOnlyClassifier, ResNet1D_SE or CRNN)")
+                                "ImageOnlyClassifier, ResNet1D_SE, CRNN or ECGTransformer1D)")
             self.encoder = _EncoderPlan(enc)
 
     def _snapshot_head(self):
@@ -255,11 +372,12 @@ class Predictor:
 
     @torch.no_grad()
     def __call__(self, *inputs, lengths=None):
-        if self.crnn:
+        if self.crnn or self.transformer:
             if len(inputs) == 2 and lengths is None:
                 inputs, lengths = inputs[:1], inputs[1]
             if len(inputs) != 1:
-                raise TypeError(f"Predictor(CRNN) takes (spectrogram, lengths=None), got {len(inputs)} inputs")
+                raise TypeError(f"Predictor({type(self.model).__name__}) takes ({'spectrogram' if self.crnn else 'signal'}, "
+                                f"lengths=None), got {len(inputs)} inputs")
             return self.encoder(inputs[0], lengths)
         if lengths is not None:
             raise TypeError(f"Predictor({type(self.model).__name__}) takes no lengths")
@@ -310,7 +428,9 @@ class Predictor:
 
         Batches are ``(*inputs, labels)`` or ``(*inputs, labels, index)`` with three inputs for the multimodal model and
         one otherwise (the dataset classes of this package); for a ``CRNN`` the one input is the spectrogram or the pair
-        ``(spectrogram, frames)`` a loader with lengths yields (``train_physionet2.DeviceSpectrogramLoader``).
+        ``(spectrogram, frames)`` a loader with lengths yields (``train_physionet2.DeviceSpectrogramLoader``); for an
+        ``ECGTransformer1D`` the signals ``[B, L]`` (given their channel axis here) or the pair ``(signals, lengths)`` of
+        ``train_physionet.DeviceSignalLoader``.
         -> ``(prob [n, classes], labels [n], index [n])`` CPU tensors; without an index column the index is the running
         position."""
         n_in = 3 if self.multimodal else 1
@@ -320,9 +440,12 @@ class Predictor:
             if len(batch) not in (n_in + 1, n_in + 2):
                 raise ValueError(f"predict_proba: a batch of {len(batch)} tensors; expected {n_in} inputs, labels[, index]")
             inputs = batch[:n_in]
-            if self.crnn and isinstance(inputs[0], (tuple, list)):   # ((spec, frames), labels)
+            if (self.crnn or self.transformer) and isinstance(inputs[0], (tuple, list)):   # ((input, lengths), labels)
                 inputs = tuple(inputs[0])
-            logits = self.logits(*(t.to(device) for t in inputs))
+            inputs = [t.to(device) for t in inputs]
+            if self.transformer and inputs[0].dim() == 2:   # the loaders yield [B, L]; the model takes [B, 1, L]
+                inputs[0] = inputs[0].unsqueeze(1)
+            logits = self.logits(*inputs)
             probs.append(torch.softmax(logits.float().cpu(), dim=1))
             labels.append(torch.as_tensor(batch[n_in]).cpu())
             b = probs[-1].shape[0]

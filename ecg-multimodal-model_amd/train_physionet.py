@@ -421,8 +421,10 @@ def main(config=Config, num_epochs=30, batch_size=8, quiet=False, use_predictor=
          rollout_samples=0, target_fs=None):
     """``model``: ``"resnet"`` (the reference's choice) or ``"transformer"`` (its commented alternative, :276); ``max_len``:
     the length every record is padded or cut to.
-    ``use_predictor``: run the validation and test passes through an ``ecgmm.inference.Predictor`` (BatchNorm-folded
-    inference plan), refreshed after every training epoch and after every checkpoint load.  Default off.
+    ``use_predictor``: run the validation and test passes through an ``ecgmm.inference.Predictor`` (the BatchNorm-folded
+    plan of the ResNet1D_SE; for ``model="transformer"`` the four-launches-per-layer plan of :class:`ECGTransformer1D`, with
+    either ``time_attention`` and with ``use_lengths``), refreshed after every training epoch and after every checkpoint
+    load.  Default off.
     ``time_attention`` or ``config.physionet_time_attention`` (off by default; ``model="transformer"`` only): the encoder
     attends along each record's positions instead of across the batch (:class:`ECGTransformer1D`).
     ``use_lengths`` or ``config.physionet_use_lengths`` (off by default; needs ``time_attention``): the loaders carry
@@ -455,8 +457,6 @@ def main(config=Config, num_epochs=30, batch_size=8, quiet=False, use_predictor=
     train_loader, val_loader, test_loader = get_signalonly_dataloaders(config, batch_size, label_map, augment, split, max_len,
                                                                        **({"use_lengths": True} if use_lengths else {}),
                                                                        **({} if target_fs is None else {"target_fs": target_fs}))
-    if use_predictor and model != "resnet":
-        raise ValueError("use_predictor=True needs model='resnet' (the inference plan is the ResNet1D_SE's)")
     model = build_model(model, num_classes, config, max_len, **({"time_attention": True} if time_attention else {})).to(device)
     criterion = FocalLoss(alpha=1.0, gamma=2.0)
     optimizer = FusedAdam(model.parameters(), lr=0.001)

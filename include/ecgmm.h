@@ -1054,6 +1054,67 @@ size_t ecgmm_embed1d_bwd_workspace(int B, int Cin, int L, int Dm);
 int ecgmm_embed1d_bwd(const float* x, const float* w, const float* dy, float* dw, float* db, float* dpos, float* dx, int B,
                       int Cin, int L, int Dm, int pos_len, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Forward-only tails of a post-norm TransformerEncoderLayer and the inference plan of ECGTransformer1D
+ * (csrc/transformer_infer.hip, csrc/plan_infer.hip; ecgmm.inference.Predictor).  Exact fp32 on v_mfma_f32_16x16x4_f32.
+ *
+ * ecgmm_linear_res_ln: out[r, :] = LayerNorm(res[r, :] + a[r, :] W^T + bias; gamma, beta, eps).  a [R, K], W [E, K] (torch's
+ *   layout), res and out [R, E], bias / gamma / beta [E]: out_proj + residual + norm1 of a layer as ONE launch; the pre-norm
+ *   sum is never stored.
+ * ecgmm_ffn_res_ln:    out[r, :] = LayerNorm(x[r, :] + relu(x[r, :] W1^T + b1) W2^T + b2; gamma, beta, eps).  x and out [R, E],
+ *   W1 [ff, E], b1 [ff], W2 [E, ff], b2 / gamma / beta [E]: the feed-forward block + residual + norm2 as ONE launch; the
+ *   hidden activation lives in registers, 16 units at a time, and never exists in memory.  No workspace.
+ * The variance is the biased one over the E values of a row (two passes over the registers: mean, then the centred sum of
+ * squares).  A wave owns whole rows; a row's bits depend on that row and the weights alone -- not on R, not on the row's place
+ * in a tile -- the summation order is fixed, there are no atomics, two identical calls give identical bits.
+ * Needs R >= 1; E a multiple of 16 with 16 <= E <= 256; K / ff a multiple of 16 with 16 <= K, ff <= 4096; eps >= 0; every
+ * operand non-null and 16-byte aligned; out must NOT alias res, a or x (equal pointers are refused: in place is not
+ * supported).  Anything else is ECGMM_ERR_SHAPE with the limit in the message, and nothing is written. */
+/* train_physionet.py:219-220, 236 in eval mode: out_proj, the residual add and norm1 of each encoder layer */
+int ecgmm_linear_res_ln(const float* a, const float* w, const float* bias, const float* res, const float* gamma,
+                        const float* beta, float* out, int64_t R, int K, int E, float eps, void* stream);
+/* train_physionet.py:219-220, 236 in eval mode: linear1, ReLU, linear2, the residual add and norm2 of each encoder layer */
+int ecgmm_ffn_res_ln(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* gamma,
+                     const float* beta, float* out, int64_t R, int E, int ff, float eps, void* stream);
+
+/* The whole eval forward of ECGTransformer1D (train_physionet.py:211-240) as an inference plan, in the shape of
+ * ecgmm_crnn_front_infer*.  E = d_model, ff = dim_feedforward, classes = num_classes; the classifier's hidden width is the
+ * model's 64.  batch_first = 0 is the reference's attention ACROSS THE BATCH (S = B, N = L), 1 attends along each record's
+ * positions (S = L, N = B).
+ * prepare: params[3 + 12 * layers + 4] fp32 device pointers -- conv.weight [E, input_dim, 3], conv.bias [E], pos_embedding
+ *   [L, E] (L of THIS descriptor = the rows of the embedding to keep, the model's seq_len), then per layer in_proj_weight
+ *   [3E, E], in_proj_bias, out_proj.weight [E, E], out_proj.bias, linear1.weight [ff, E], linear1.bias, linear2.weight [E, ff],
+ *   linear2.bias, norm1.weight, norm1.bias, norm2.weight, norm2.bias, then classifier.1.weight [64, E], .bias,
+ *   classifier.4.weight [classes, 64], .bias -- are copied into one blob (B is not looked at).  The positional table is
+ *   the blob's last entry, so a run at any L' <= L reads the same blob.
+ * infer: x [B, input_dim, L] fp32 -> logits [B, classes] fp32 on the given stream, reading the blob alone:
+ *   embed (ecgmm_embed1d_fwd), per layer 4 launches -- in_proj (ecgmm_linear_fwd), ecgmm_mha_forward(_varlen),
+ *   ecgmm_linear_res_ln, ecgmm_ffn_res_ln -- then the mean over the positions and Linear-ReLU-Linear.  Bit for bit that
+ *   sequence of per-op calls.  lengths (nullable, device int32 [B], only with batch_first = 1, clamped to [0, L] on the
+ *   device): positions at or behind a record's length are never keys and do not enter the mean, and the record's raw samples
+ *   there are replaced by zeros before the convolution (one more launch), so its logits depend on its own live samples
+ *   alone; a length 0 gives the classifier of a zero vector.
+ * workspace: rotating buffers that depend neither on layers nor on ff -- x, next x and the attention output [B L, E] each,
+ *   qkv [B L, 3E], lse [B L heads], and [B, E] + [B, 64] + [B] for the tail: at most
+ *   4 B L (6E + heads) + 4 B (E + 64 + classes) bytes + 256 per buffer.
+ * Needs B, L, layers, classes >= 1, 1 <= input_dim <= 12, E and ff as the two ops above, E / heads 16 or 32, eps >= 0,
+ * B <= 65535; else ECGMM_ERR_SHAPE (the size queries: 0) with the limit in the message; a short blob or workspace is
+ * ECGMM_ERR_WORKSPACE.  The size queries need no GPU. */
+typedef struct {
+  int B, L, input_dim, E, heads, ff, layers, classes, batch_first;
+  float eps;
+} ecgmm_transformer_infer_desc;
+/* train_physionet.py:211-240 */
+size_t ecgmm_transformer_infer_prepared_bytes(const ecgmm_transformer_infer_desc* d);
+/* train_physionet.py:211-240 (a snapshot of every parameter) */
+int ecgmm_transformer_infer_prepare(const ecgmm_transformer_infer_desc* d, const void* const* params, void* blob,
+                                    size_t blob_bytes, void* stream);
+/* train_physionet.py:233-240 */
+size_t ecgmm_transformer_infer_workspace(const ecgmm_transformer_infer_desc* d);
+/* train_physionet.py:233-240 under model.eval() and torch.no_grad() (:352-358) */
+int ecgmm_transformer_infer(const ecgmm_transformer_infer_desc* d, const float* x, const int32_t* lengths, const void* blob,
+                            size_t blob_bytes, float* logits, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
