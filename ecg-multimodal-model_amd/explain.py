@@ -234,20 +234,24 @@ def overlay(image, cam, alpha=0.5):
     return as_u8(heat), as_u8(mixed)
 
 
-def main(config=Config, model_path=None, out_dir="./gradcam", samples=4, output="fusion", quiet=False):
-    """writes gradcam_<i>.png + gradcam_<i>_overlay.png for the first ``samples`` test samples; -> list of file paths"""
+def main(config=Config, model_path=None, out_dir="./gradcam", samples=4, output="fusion", quiet=False, model_cls=None):
+    """writes gradcam_<i>.png + gradcam_<i>_overlay.png for the first ``samples`` test samples; -> list of file paths.
+    ``model_cls``: the model class (default: the paper_modal_balance ``ECGMultimodalModel``).  With the TabNet variant
+    (``ecgmm.multimodal.ECGMultimodalModel``) the step masks of the same samples' clinical rows are written too, as
+    ``clinical_masks.npz`` (``ClinicalTabNetEncoder.visualize_masks``), the last path of the list."""
     from PIL import Image
 
     from .dataset import get_dataloaders
     from .multimodal_paper_modal_balance import ECGMultimodalModel
+    from .tabnet import ClinicalTabNetEncoder
     device = torch.device(config.device)
     _train_loader, _val_loader, test_loader = get_dataloaders(config)
-    model = ECGMultimodalModel(config).to(device)
+    model = (model_cls or ECGMultimodalModel)(config).to(device)
     if model_path:
         model.load_state_dict(torch.load(model_path, map_location=device))
     model.eval()
     os.makedirs(out_dir, exist_ok=True)
-    written = []
+    written, clin_rows = [], []
     for *batch, _index in test_loader:
         images, ecg_signals, clinical, labels = (t.to(device) for t in batch)
         cam_img, _cam_sig = grad_cam(model, images, ecg_signals, clinical, output=output)
@@ -260,10 +264,16 @@ def main(config=Config, model_path=None, out_dir="./gradcam", samples=4, output=
                 path = os.path.join(out_dir, name)
                 Image.fromarray(arr).save(path)
                 written.append(path)
+            clin_rows.append(clinical[b])
             if not quiet:
                 print(f"sample {i}: label {int(labels[b])}, map mean {float(cam_img[b].mean()):.3f} -> {written[-1]}")
         if len(written) >= 2 * samples:
             break
+    if clin_rows and isinstance(model.clinical_encoder, ClinicalTabNetEncoder):
+        model.clinical_encoder.visualize_masks(torch.stack(clin_rows), None, out_dir, "clinical")
+        written.append(os.path.join(out_dir, "clinical_masks.npz"))
+        if not quiet:
+            print(f"clinical step masks of {len(clin_rows)} samples -> {written[-1]}")
     return written
 
 

@@ -54,6 +54,11 @@ class TransformerInferDesc(C.Structure):
     _fields_ = [(n, i32) for n in ("B", "L", "input_dim", "E", "heads", "ff", "layers", "classes", "batch_first")] + [("eps", f32)]
 
 
+class TabNetInferDesc(C.Structure):
+    _fields_ = [(n, i32) for n in ("input_dim", "n_d", "n_a", "n_steps", "n_shared", "n_independent", "out_dim")] + \
+               [("gamma", f32), ("epsilon", f32), ("bn_eps", f32)]
+
+
 P = C.POINTER
 # name -> (restype, argtypes).  Must list every function declared in include/ecgmm.h
 # (tests/test_abi.py parses the header and checks the two agree).
@@ -272,6 +277,9 @@ SIGNATURES = {
     "ecgmm_transformer_infer_prepare": (i32, [P(TransformerInferDesc), P(vp), vp, sz, vp]),
     "ecgmm_transformer_infer_workspace": (sz, [P(TransformerInferDesc)]),
     "ecgmm_transformer_infer": (i32, [P(TransformerInferDesc), vp, vp, vp, sz, vp, vp, sz, vp]),
+    "ecgmm_tabnet_infer_prepared_bytes": (sz, [P(TabNetInferDesc)]),
+    "ecgmm_tabnet_infer_prepare": (i32, [P(TabNetInferDesc), P(vp), vp, sz, vp]),
+    "ecgmm_tabnet_infer": (i32, [P(TabNetInferDesc), vp, i64, vp, sz, vp, vp, vp, vp, vp]),
 }
 
 # Entry points of the input-gradient / Grad-CAM feature.  A library selected with ECGMM_LIB for an A/B run may predate them:
@@ -334,7 +342,9 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  "ecgmm_crnn_front_infer_workspace", "ecgmm_crnn_front_infer",
                  # the transformer's fused layer tails and inference plan (ecgmm.inference.Predictor(ECGTransformer1D))
                  "ecgmm_linear_res_ln", "ecgmm_ffn_res_ln", "ecgmm_transformer_infer_prepared_bytes",
-                 "ecgmm_transformer_infer_prepare", "ecgmm_transformer_infer_workspace", "ecgmm_transformer_infer")
+                 "ecgmm_transformer_infer_prepare", "ecgmm_transformer_infer_workspace", "ecgmm_transformer_infer",
+                 # TabNet's fused eval forward and masks (ecgmm.inference._TabNetPlan, csrc/tabnet_infer.hip)
+                 "ecgmm_tabnet_infer_prepared_bytes", "ecgmm_tabnet_infer_prepare", "ecgmm_tabnet_infer")
 
 _lib = None
 

@@ -20,8 +20,15 @@ Grad-CAM and input gradients (ecgmm/explain.py) therefore keep using the model's
 gradients through raw pointers, so tensor version counters do not move and a ``Predictor`` cannot notice that the model
 was trained further: call :meth:`Predictor.refresh` after the weights changed (``load_state_dict``, an optimizer step).
 Until then it keeps returning the answer of the weights it was prepared from.  The snapshot covers both encoders and
-the multimodal head; the clinical branch (a few small dense layers, or TabNet) runs the model's own eval forward on the
-live parameters.
+the multimodal head; the clinical branch of the MLP variant (a few small dense layers) runs the model's own eval forward on
+the live parameters.
+
+**TabNet** (``ecgmm.tabnet.ClinicalTabNetEncoder``): ``Predictor(encoder)(x) -> z``, and inside
+``Predictor(model, clinical_plan=True)`` the TabNet variant's clinical branch: the whole eval forward is ONE launch of
+``ecgmm_tabnet_infer`` (csrc/tabnet_infer.hip) on a blob in which every BatchNorm is folded into the ``fc`` in front of it
+(a shared ``fc`` once per FeatTransformer, with that FeatTransformer's statistics), where the module's forward issues about
+110.  The blob is a snapshot like every other part of a predictor.  ``clinical_plan=False`` keeps the module's own forward;
+the MLP variant and a TabNet shape outside the fused path (``ecgmm.tabnet.FUSED_LIMITS``) do so silently.
 
 **The spectrogram CRNN** (``ecgmm.crnn.CRNN``, ``train_physionet2``): ``Predictor(model)(x, lengths=None)``.  The three
 ConvBlocks run as ``ecgmm_crnn_front_infer`` (csrc/plan_infer.hip: block 1 as one conv + ReLU + pool kernel, no
@@ -46,6 +53,7 @@ from .hip import lib as L
 from .hip.functional import _Scratch, _require_cuda, f32c, new_bytes, ptr, stream
 from .image_encoder import ResNet18
 from .multimodal_paper_modal_balance import ECGMultimodalModel, ResNet1D_SE
+from . import tabnet as T
 from .train_physionet import ECGTransformer1D
 
 __all__ = ["Predictor"]
@@ -316,6 +324,32 @@ class _TransformerPlan:
         return int(L.lib().ecgmm_transformer_infer_workspace(C.byref(self._desc(B, Ln))))
 
 
+class _TabNetPlan:
+    """``ClinicalTabNetEncoder`` through ``ecgmm_tabnet_infer`` (csrc/tabnet_infer.hip): one folded blob, one launch per
+    forward -- the answer is that of the parameters and running statistics the plan was prepared from."""
+
+    def __init__(self, module):
+        if not isinstance(module, T.ClinicalTabNetEncoder):
+            raise TypeError(f"no TabNet inference plan for {type(module).__name__}")
+        self.module = module
+        self.blob = None
+        self.refresh()
+
+    def refresh(self):
+        net = self.module.tabnet
+        self.desc, self.blob = T.fused_fold(net.encoder, net.final_mapping.weight)
+        return self
+
+    def __call__(self, x):
+        """``x [B, D]`` -> ``z [B, latent_dim]`` (the module's forward also returns M_loss; a predictor has no use for it)"""
+        return T.fused_run(self.desc, self.blob, x)[0]
+
+    def masks(self, x):
+        """``(M_explain [B, D], {step: M [B, D]})`` of the snapshot (``forward_masks`` of the module folds per call)"""
+        _, mexp, masks, _ = T.fused_run(self.desc, self.blob, x, explain=True)
+        return mexp, {step: masks[step] for step in range(self.desc.n_steps)}
+
+
 def _find_encoder(model):
     if isinstance(model, (ResNet18, ResNet1D_SE)):
         return model
@@ -329,7 +363,9 @@ class Predictor:
     """Eval-mode forward of ``model`` through the inference plans.
 
     ``model``: an ``ECGMultimodalModel`` (either variant), a ``ResNet18`` / ``ImageOnlyClassifier``, a ``ResNet1D_SE``,
-    the spectrogram ``CRNN`` or an ``ECGTransformer1D`` (either ``time_attention`` mode), on a ROCm device.  Construction prepares the folded weights; :meth:`refresh` prepares them
+    the spectrogram ``CRNN``, an ``ECGTransformer1D`` (either ``time_attention`` mode) or a ``ClinicalTabNetEncoder``
+    (``predictor(x) -> z``), on a ROCm device.  ``clinical_plan`` (multimodal TabNet variant only): the clinical branch as one
+    fused launch on a folded snapshot instead of the module's own forward.  Construction prepares the folded weights; :meth:`refresh` prepares them
     again (see the module docstring: nothing can detect stale weights for you).  Calling the predictor never changes
     ``model.training``, a running statistic or a ``.grad``.  A ``CRNN`` predictor is called as the model is,
     ``predictor(x, lengths=None)``; its snapshot covers the front end, the LSTM and the classifier.  So is an
@@ -337,23 +373,30 @@ class Predictor:
     refuses ``d_model > 256`` and a ``dim_feedforward`` that is no multiple of 16 or exceeds 4096 with a ``ValueError``.
     """
 
-    def __init__(self, model):
+    def __init__(self, model, clinical_plan=True):
         self.model = model
         self.multimodal = isinstance(model, ECGMultimodalModel)
         self.crnn = isinstance(model, CRNN)
         self.transformer = isinstance(model, ECGTransformer1D)
-        if self.crnn:
+        self.clinical = None
+        if isinstance(model, T.ClinicalTabNetEncoder):
+            self.encoder = _TabNetPlan(model)
+        elif self.crnn:
             self.encoder = _CRNNPlan(model)
         elif self.transformer:
             self.encoder = _TransformerPlan(model)
         elif self.multimodal:
             self.image, self.signal = _EncoderPlan(model.image_encoder), _EncoderPlan(model.signal_encoder)
+            clin = model.clinical_encoder
+            if clinical_plan and isinstance(clin, T.ClinicalTabNetEncoder) and \
+                    T.fused_refusal(clin.tabnet.encoder, clin.tabnet.final_mapping.weight.shape[0]) is None:
+                self.clinical = _TabNetPlan(clin)
             self._snapshot_head()
         else:
             enc = _find_encoder(model)
             if enc is None:
                 raise TypeError(f"Predictor: unsupported model {type(model).__name__} (ECGMultimodalModel, ResNet18, "
-                                "ImageOnlyClassifier, ResNet1D_SE, CRNN or ECGTransformer1D)")
+                                "ImageOnlyClassifier, ResNet1D_SE, CRNN, ECGTransformer1D or ClinicalTabNetEncoder)")
             self.encoder = _EncoderPlan(enc)
 
     def _snapshot_head(self):
@@ -365,6 +408,8 @@ class Predictor:
         if self.multimodal:
             self.image.refresh()
             self.signal.refresh()
+            if self.clinical is not None:
+                self.clinical.refresh()
             self._snapshot_head()
         else:
             self.encoder.refresh()
@@ -407,7 +452,7 @@ class Predictor:
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 signal_raw = self.signal(ecg_signal)
-                clinical_raw = model._clinical_forward(clinical)
+                clinical_raw = self._clinical_forward(clinical)
             image_raw = self.image(image)
             main.wait_stream(side)
             signal_raw.record_stream(main)
@@ -415,8 +460,11 @@ class Predictor:
         else:
             image_raw = self.image(image)
             signal_raw = self.signal(ecg_signal)
-            clinical_raw = model._clinical_forward(clinical)
+            clinical_raw = self._clinical_forward(clinical)
         return E.run_head(image_raw, signal_raw, clinical_raw, spec, self._head_params)
+
+    def _clinical_forward(self, clinical):
+        return self.clinical(clinical) if self.clinical is not None else self.model._clinical_forward(clinical)
 
     def logits(self, *inputs):
         """The class logits of a forward: ``fusion_logits`` of the multimodal 6-tuple, the output itself otherwise."""

@@ -32,5 +32,9 @@ class ECGMultimodalModel(_pmb.ECGMultimodalModel):
         z, _ = self.clinical_encoder(clinical)
         return z
 
+    def visualize_clinical_masks(self, clinical, feature_names=None, save_dir="./shap", base_filename="mask"):
+        """multimodal.py:247-249: the step masks of the clinical branch, as ``ClinicalTabNetEncoder.visualize_masks``"""
+        return self.clinical_encoder.visualize_masks(clinical, feature_names, save_dir, base_filename)
+
 
 MultimodalModel = ECGMultimodalModel

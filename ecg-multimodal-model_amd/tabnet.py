@@ -9,7 +9,9 @@ _bwd / _eval_bwd (one virtual batch = one row slice, no concatenation), and the 
 csrc/tabnet.hip: GLU gate, sparsemax, the mask / prior recurrence, column split (+ReLU), mask entropy.
 Every arithmetic step is a HIP kernel with a hand-written backward (torch.autograd.Function); there is no CPU path.
 """
+import ctypes as C
 import math
+import os
 
 import numpy as np
 import torch
@@ -360,6 +362,85 @@ class AttentiveTransformer(nn.Module):
         return _Sparsemax.apply(x)
 
 
+# ---- the fused eval forward (csrc/tabnet_infer.hip): one fold launch + one forward launch ---------------------------------
+FUSED_LIMITS = ("input_dim <= 64, n_d and n_a multiples of 16 with n_d + n_a <= 128, n_steps <= 8, "
+                "1 <= n_shared + n_independent <= 8, output width a multiple of 16 up to 128")
+
+
+def fused_refusal(enc, out_dim=16):
+    """None when the fused path takes a ``TabNetEncoder`` of this shape, else the reason (it names the limit)"""
+    layers = enc.n_shared + enc.n_independent
+    ok = (1 <= enc.input_dim <= 64 and enc.n_d >= 16 and enc.n_a >= 16 and enc.n_d % 16 == 0 and enc.n_a % 16 == 0
+          and enc.n_d + enc.n_a <= 128 and 1 <= enc.n_steps <= 8 and 1 <= layers <= 8
+          and 16 <= out_dim <= 128 and out_dim % 16 == 0)
+    if ok:
+        return None
+    return (f"TabNet: input_dim={enc.input_dim}, n_d={enc.n_d}, n_a={enc.n_a}, n_steps={enc.n_steps}, n_shared={enc.n_shared}, "
+            f"n_independent={enc.n_independent}, output width {out_dim} is outside the fused eval path ({FUSED_LIMITS})")
+
+
+def fused_fold(enc, final_weight=None):
+    """Fold every BatchNorm of ``enc`` (a ``TabNetEncoder``) into the fc in front of it, from the CURRENT parameters and
+    running statistics -> (desc, blob).  ``final_weight`` [out_dim, n_d]: the mapping of the summed step outputs (None: a
+    zero [16, n_d] matrix, for callers that want the masks alone)."""
+    params = [v for v in enc.state_dict(keep_vars=True).values() if v.is_floating_point()]
+    dev = params[0].device
+    if final_weight is None:
+        final_weight = torch.zeros(16, enc.n_d, device=dev)
+    params.append(final_weight)
+    reason = fused_refusal(enc, final_weight.shape[0])
+    if reason:
+        raise ValueError(reason)
+    want = 4 + 5 * (enc.n_steps + 1) * (enc.n_shared + enc.n_independent) + 5 * enc.n_steps + 1
+    if len(params) != want:
+        raise RuntimeError(f"TabNet: expected {want} float tensors in the state_dict, found {len(params)}")
+    for p in params:
+        _require_cuda(p, "TabNet fused forward: parameter")
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            raise RuntimeError("TabNet fused forward: parameters must be contiguous fp32")
+    eps = {float(m.eps) for m in enc.modules() if isinstance(m, hnn.BatchNorm1d)}
+    if len(eps) != 1:
+        raise RuntimeError("TabNet fused forward: the BatchNorms do not share one eps")
+    desc = L.TabNetInferDesc(enc.input_dim, enc.n_d, enc.n_a, enc.n_steps, enc.n_shared, enc.n_independent,
+                             final_weight.shape[0], float(enc.gamma), float(enc.epsilon), eps.pop())
+    lib = L.lib()
+    nb = lib.ecgmm_tabnet_infer_prepared_bytes(C.byref(desc))
+    if nb == 0:
+        L.check(1, "tabnet prepared-size query")
+    with torch.cuda.device(dev), torch.no_grad():
+        blob = HF.new_bytes(nb, dev)   # a NEW blob: a forward already enqueued with an old one keeps consistent weights
+        table = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
+        L.check(lib.ecgmm_tabnet_infer_prepare(C.byref(desc), table, ptr(blob), blob.numel(), stream()), "tabnet infer prepare")
+    return desc, blob
+
+
+def fused_run(desc, blob, x, explain=False, entropy=False):
+    """-> (out [B, out_dim], M_explain [B, D] | None, masks [n_steps, B, D] | None, row_entropy [B] | None)"""
+    _require_cuda(x, "TabNet fused forward")
+    if x.dim() != 2 or x.shape[1] != desc.input_dim:
+        raise ValueError(f"TabNet expects [B, {desc.input_dim}], got {tuple(x.shape)}")
+    x = f32c(x.detach())
+    B, dev = x.shape[0], x.device
+    new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
+    out = new(B, desc.out_dim)
+    mexp, masks = (new(B, desc.input_dim), new(desc.n_steps, B, desc.input_dim)) if explain else (None, None)
+    ent = new(B) if entropy else None
+    with torch.cuda.device(dev):
+        blob.record_stream(torch.cuda.current_stream(dev))
+        L.check(L.lib().ecgmm_tabnet_infer(C.byref(desc), ptr(x), B, ptr(blob), blob.numel(), ptr(out), ptr(mexp), ptr(masks),
+                                           ptr(ent), stream()), "tabnet infer")
+    return out, mexp, masks, ent
+
+
+def _forward_masks(enc, x):
+    if enc.training:
+        raise RuntimeError("forward_masks uses the running statistics of every BatchNorm: the module is in training mode -- "
+                           "call eval() first (forward_masks does not change the mode)")
+    desc, blob = fused_fold(enc)     # per call: never stale
+    _, mexp, masks, _ = fused_run(desc, blob, x, explain=True)
+    return mexp, {step: masks[step] for step in range(enc.n_steps)}
+
+
 class TabNetEncoder(nn.Module):
     def __init__(self, input_dim, output_dim, n_d=8, n_a=8, n_steps=3, gamma=1.3, n_independent=2, n_shared=2,
                  epsilon=1e-15, virtual_batch_size=128, momentum=0.02):
@@ -367,6 +448,7 @@ class TabNetEncoder(nn.Module):
         if input_dim > 64:
             raise ValueError("TabNetEncoder: the sparsemax kernel handles up to 64 features")
         self.input_dim, self.n_d, self.n_a, self.n_steps, self.gamma, self.epsilon = input_dim, n_d, n_a, n_steps, gamma, epsilon
+        self.n_shared, self.n_independent = n_shared, n_independent
         self.initial_bn = SmallBatchNorm1d(input_dim, momentum=0.01)
         self.group_attention_matrix = torch.eye(input_dim)   # plain attribute in the library (identity grouping only here)
         shared = None
@@ -399,6 +481,12 @@ class TabNetEncoder(nn.Module):
             steps_output.append(d)
         return steps_output, _Scale.apply(m_loss, 1.0 / self.n_steps)
 
+    def forward_masks(self, x):
+        """pytorch_tabnet's ``forward_masks``: ``(M_explain [B, D], {step: M [B, D]})`` of the eval forward, from ONE fused
+        launch on weights folded at this call.  Refuses training mode (RuntimeError) and shapes outside the fused path
+        (ValueError naming the limit)."""
+        return _forward_masks(self, x)
+
 
 class TabNetNoEmbeddings(nn.Module):
     def __init__(self, input_dim, output_dim, n_d=8, n_a=8, n_steps=3, gamma=1.3, n_independent=2, n_shared=2,
@@ -416,6 +504,10 @@ class TabNetNoEmbeddings(nn.Module):
             res = _AddScale.apply(res, d, 1.0)
         return self.final_mapping(res), m_loss.reshape(())
 
+    def forward_masks(self, x):
+        """``(M_explain [B, D], {step: M [B, D]})``, as ``TabNetEncoder.forward_masks``"""
+        return _forward_masks(self.encoder, x)
+
 
 class ClinicalTabNetEncoder(nn.Module):
     """multimodal.py:109-148: forward(x) -> (latent [B, latent_dim], M_loss)"""
@@ -428,6 +520,30 @@ class ClinicalTabNetEncoder(nn.Module):
 
     def forward(self, x):
         return self.tabnet(x)
+
+    def forward_masks(self, x):
+        """``(M_explain [B, D], {step: M [B, D]})``, as ``TabNetEncoder.forward_masks``"""
+        return self.tabnet.forward_masks(x)
+
+    def visualize_masks(self, X, feature_names=None, save_dir="./shap", base_filename="mask"):
+        """multimodal.py:170-240 without the plots: the step masks of ``X`` (numpy or tensor, [B, D]) are computed by
+        ``forward_masks`` and written to ``<save_dir>/<base_filename>_masks.npz`` as ``feature_names``, ``masks``
+        [n_steps, B, D], ``step_mean`` [n_steps, D] (what each of the reference's per-step heat maps shows), ``M_explain``
+        [B, D] and ``M_agg_mean`` [D] (the mean over the steps, then over the batch: its aggregate heat map).  Returns that
+        dict.  The module must be in eval mode; its mode is not changed."""
+        dev = next(self.parameters()).device
+        X = torch.as_tensor(X, dtype=torch.float32).to(dev)
+        m_explain, step_masks = self.forward_masks(X)
+        masks = torch.stack([step_masks[k] for k in sorted(step_masks)]).cpu().numpy()
+        if feature_names is None:
+            feature_names = [f"var_{i}" for i in range(X.shape[1])]
+        if len(feature_names) != X.shape[1]:
+            raise ValueError(f"visualize_masks: {len(feature_names)} feature names for {X.shape[1]} features")
+        result = dict(feature_names=np.asarray([str(n) for n in feature_names]), masks=masks, step_mean=masks.mean(axis=1),
+                      M_explain=m_explain.cpu().numpy(), M_agg_mean=masks.mean(axis=0).mean(axis=0))
+        os.makedirs(save_dir, exist_ok=True)
+        np.savez(os.path.join(save_dir, f"{base_filename}_masks.npz"), **result)
+        return result
 
     def load_pretrained_partial(self, weight_path):
         """everything but the output layer (multimodal.py:150-167)"""

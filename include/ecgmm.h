@@ -1115,6 +1115,50 @@ size_t ecgmm_transformer_infer_workspace(const ecgmm_transformer_infer_desc* d);
 int ecgmm_transformer_infer(const ecgmm_transformer_infer_desc* d, const float* x, const int32_t* lengths, const void* blob,
                             size_t blob_bytes, float* logits, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The eval forward of TabNetNoEmbeddings (ecgmm/tabnet.py; pytorch_tabnet as multimodal.py:113-123 instantiates it) as an
+ * inference plan (csrc/tabnet_infer.hip; ecgmm.inference.Predictor, TabNetEncoder.forward_masks).  Exact fp32 on
+ * v_mfma_f32_16x16x4_f32; ONE launch per prepare and ONE per forward, whatever the depth.
+ *
+ * prepare: params[4 + 5 (n_steps + 1) (n_shared + n_independent) + 5 n_steps + 1] fp32 device pointers, IN state_dict ORDER
+ *   with every num_batches_tracked left out: encoder.initial_bn {weight, bias, running_mean, running_var}; then for the
+ *   FeatTransformers initial_splitter, feat_transformers.0 .. n_steps-1, for their GLU layers shared.glu_layers.* then
+ *   specifics.glu_layers.*: {fc.weight [2 (n_d + n_a), K], bn.bn.weight, .bias, .running_mean, .running_var} (K = input_dim
+ *   for a FeatTransformer's first layer, n_d + n_a otherwise; a shared fc.weight appears once per FeatTransformer, as it does
+ *   in the state_dict, each time next to THAT FeatTransformer's BatchNorm); then for att_transformers.0 .. n_steps-1:
+ *   {fc.weight [input_dim, n_a], bn.bn.weight, .bias, .running_mean, .running_var}; then final_mapping.weight [out_dim, n_d].
+ *   Every BatchNorm is folded into the bias-free fc in front of it: s_j = gamma_j / sqrt(rv_j + bn_eps),
+ *   W'[j, k] = s_j W[j, k], b'_j = beta_j - rm_j s_j (one fused multiply-add); gamma_j = 0 gives a row of exact zeros.
+ *   initial_bn becomes a (scale, shift) pair and is NOT folded into the first layer: the masks multiply the normalised
+ *   input.  K and the attentive output width are zero-padded to multiples of 16; every byte of the blob is written.
+ *   Blob layout, in floats, every piece at a multiple of 64 (Dp = input_dim rounded up to 16, W = n_d + n_a, pad64 rounds up
+ *   to 64): scale[64] shift[64] | for each FeatTransformer, for each layer: W' [2W, K] row-major (K = Dp for the first layer,
+ *   W otherwise), b' [pad64(2W)] | for each step: attentive W' [Dp, n_a], b' [64] | final_mapping [out_dim, n_d].
+ * infer: x [B, input_dim] -> out [B, out_dim] = final_mapping(sum_step relu(d_step)).  Optional outputs, not written when null
+ *   (out has the same bits whichever are requested): m_explain [B, input_dim] = sum_step M_step * sum_j relu(d_step)_j
+ *   (pytorch_tabnet's forward_masks with the identity group matrix), masks [n_steps, B, input_dim] (each row on the simplex;
+ *   an entry outside the support is exactly 0.0), row_entropy [B] = sum_step sum_d M log(M + epsilon) (its mean over B,
+ *   divided by n_steps, is the module's M_loss).  The sparsemax is Michelot's fixed point on the row minus its maximum (no
+ *   sort).  A row's bits depend on that row and the blob alone -- not on B, not on its place in a tile; no atomics; two
+ *   identical calls give identical bits.
+ * Needs 1 <= input_dim <= 64; n_d and n_a multiples of 16 with n_d + n_a <= 128; 1 <= n_steps <= 8; n_shared,
+ * n_independent >= 0 with 1 <= n_shared + n_independent <= 8; out_dim a multiple of 16 with 16 <= out_dim <= 128 (a ragged
+ * out_dim is refused, not padded); 0 <= gamma <= 1e6; epsilon, bn_eps in [0, 1]; 1 <= B < 2^31 - 64; a 16-byte aligned blob.
+ * Anything else is ECGMM_ERR_SHAPE (the size query: 0) with the limit in the message and nothing is written; a short blob is
+ * ECGMM_ERR_WORKSPACE.  There is no workspace.  The size query needs no GPU. */
+typedef struct {
+  int input_dim, n_d, n_a, n_steps, n_shared, n_independent, out_dim;
+  float gamma, epsilon, bn_eps;
+} ecgmm_tabnet_infer_desc;
+/* multimodal.py:113-123 */
+size_t ecgmm_tabnet_infer_prepared_bytes(const ecgmm_tabnet_infer_desc* d);
+/* multimodal.py:113-123 in eval mode (a folded snapshot of every parameter and running statistic) */
+int ecgmm_tabnet_infer_prepare(const ecgmm_tabnet_infer_desc* d, const void* const* params, void* blob, size_t blob_bytes,
+                               void* stream);
+/* multimodal.py:141-148 under model.eval() and torch.no_grad(); the masks are what :170-240 plots */
+int ecgmm_tabnet_infer(const ecgmm_tabnet_infer_desc* d, const float* x, int64_t B, const void* blob, size_t blob_bytes,
+                       float* out, float* m_explain, float* masks, float* row_entropy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
