@@ -179,13 +179,15 @@ void layout_ws1d(const Net1D& r, void* base, Ws1D& w) {
   w.bytes = align_up(a.off, 256);
 }
 
-int check_tables(const void* const* params, int np, const void* const* buffers, int nb, const char* who) {
-  if (!params || !buffers) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: null parameter / buffer table", who);
-  for (int i = 0; i < np; ++i)
-    if (!params[i]) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: parameter %d is null", who, i);
-  for (int i = 0; i < nb; ++i)
-    if (!buffers[i]) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: buffer %d is null", who, i);
+int check_table(const void* const* table, int n, const char* what, const char* who) {
+  if (!table) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: null %s table", who, what);
+  for (int i = 0; i < n; ++i)
+    if (!table[i]) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: %s %d is null", who, what, i);
   return 0;
+}
+int check_tables(const void* const* params, int np, const void* const* buffers, int nb, const char* who) {
+  ECG_TRY(check_table(params, np, "parameter", who));
+  return check_table(buffers, nb, "buffer", who);
 }
 
 EcgFoldItem conv_item(int kind, const void* const* params, int p_w, const float* conv_bias, int p_bn,
@@ -512,10 +514,11 @@ namespace {
 
 constexpr int TFM_HIDDEN = 64;        // the classifier's hidden width (train_physionet.py:227)
 constexpr int TFM_LAYER_PARAMS = 12;
+constexpr int TFM_MAX_LAYERS = 64;
 
 int buildt_static(const ecgmm_transformer_infer_desc* d, const char* who) {
   if (!d) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: null descriptor", who);
-  if (d->layers < 1 || d->layers > 64) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: layers=%d (needs 1 <= layers <= 64)", who, d->layers);
+  if (d->layers < 1 || d->layers > TFM_MAX_LAYERS) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: layers=%d (needs 1 <= layers <= 64)", who, d->layers);
   if (d->classes < 1 || d->classes > 4096) ECG_FAIL(ECGMM_ERR_SHAPE, "%s: classes=%d (needs 1 <= classes <= 4096)", who, d->classes);
   if (d->input_dim < 1 || d->input_dim > 12)
     ECG_FAIL(ECGMM_ERR_SHAPE, "%s: input_dim=%d (needs 1 <= input_dim <= 12)", who, d->input_dim);
@@ -541,10 +544,11 @@ int buildt(const ecgmm_transformer_infer_desc* d, const char* who) {
 struct BlobT {
   struct Layer { float *in_w, *in_b, *out_w, *out_b, *w1, *b1, *w2, *b2, *g1, *be1, *g2, *be2; };
   float *conv_w, *conv_b, *cw1, *cb1, *cw2, *cb2, *pos;
+  Layer layer[TFM_MAX_LAYERS];   // filled for d.layers
   size_t bytes;
 };
 // entry i of the parameter table <-> (destination, floats), in the table's order; the positional table is the blob's LAST
-// entry, so every other offset is independent of L
+// entry, so every other offset is independent of L.  The ONE walk of the blob: sizes, copy items and every pointer.
 struct CopyT { float* dst; size_t n; };
 int layout_blobt(const ecgmm_transformer_infer_desc& d, void* base, BlobT& q, CopyT* items) {
   Arena a(base);
@@ -559,8 +563,13 @@ int layout_blobt(const ecgmm_transformer_infer_desc& d, void* base, BlobT& q, Co
   q.conv_b = take(E, 1);
   n = 3;
   for (int l = 0; l < d.layers; ++l) {
-    const size_t sizes[TFM_LAYER_PARAMS] = {3 * E * E, 3 * E, E * E, E, ff * E, ff, E * ff, E, E, E, E, E};
-    for (int j = 0; j < TFM_LAYER_PARAMS; ++j) take(sizes[j], n++);
+    BlobT::Layer& k = q.layer[l];
+    k.in_w = take(3 * E * E, n++); k.in_b = take(3 * E, n++);
+    k.out_w = take(E * E, n++);    k.out_b = take(E, n++);
+    k.w1 = take(ff * E, n++);      k.b1 = take(ff, n++);
+    k.w2 = take(E * ff, n++);      k.b2 = take(E, n++);
+    k.g1 = take(E, n++);           k.be1 = take(E, n++);
+    k.g2 = take(E, n++);           k.be2 = take(E, n++);
   }
   q.cw1 = take(TFM_HIDDEN * E, n++);
   q.cb1 = take(TFM_HIDDEN, n++);
@@ -569,23 +578,6 @@ int layout_blobt(const ecgmm_transformer_infer_desc& d, void* base, BlobT& q, Co
   q.pos = take((size_t)d.L * E, 2);
   q.bytes = align_up(a.off, 256);
   return n;
-}
-// the layers' tensors again, from the same walk (the Arena is deterministic): layer l of a blob at `base`
-BlobT::Layer blobt_layer(const ecgmm_transformer_infer_desc& d, void* base, int layer) {
-  Arena a(base);
-  const size_t E = d.E, ff = d.ff;
-  a.take<float>(E * d.input_dim * 3);
-  a.take<float>(E);
-  BlobT::Layer k = {};
-  for (int l = 0; l <= layer; ++l) {
-    k.in_w = a.take<float>(3 * E * E); k.in_b = a.take<float>(3 * E);
-    k.out_w = a.take<float>(E * E);    k.out_b = a.take<float>(E);
-    k.w1 = a.take<float>(ff * E);      k.b1 = a.take<float>(ff);
-    k.w2 = a.take<float>(E * ff);      k.b2 = a.take<float>(E);
-    k.g1 = a.take<float>(E);           k.be1 = a.take<float>(E);
-    k.g2 = a.take<float>(E);           k.be2 = a.take<float>(E);
-  }
-  return k;
 }
 
 // x / nxt / att: [R, E] each (att first holds the zero-padded copy of the raw input: input_dim <= 12 < E); qkv [R, 3E];
@@ -623,11 +615,9 @@ extern "C" int ecgmm_transformer_infer_prepare(const ecgmm_transformer_infer_des
                                                size_t blob_bytes, void* stream_) {
   ECG_TRY(buildt_static(d, "transformer infer prepare"));
   const int np = 3 + TFM_LAYER_PARAMS * d->layers + 4;
-  if (!params) ECG_FAIL(ECGMM_ERR_SHAPE, "transformer infer prepare: null parameter table");
-  for (int i = 0; i < np; ++i)
-    if (!params[i]) ECG_FAIL(ECGMM_ERR_SHAPE, "transformer infer prepare: parameter %d is null", i);
+  ECG_TRY(check_table(params, np, "parameter", "transformer infer prepare"));
   BlobT q;
-  CopyT items[3 + TFM_LAYER_PARAMS * 64 + 4];
+  CopyT items[3 + TFM_LAYER_PARAMS * TFM_MAX_LAYERS + 4];
   layout_blobt(*d, blob, q, items);
   ECG_NEED(blob, blob_bytes, q.bytes, "transformer infer prepare: blob");
   for (int i = 0; i < np; ++i) {
@@ -672,7 +662,7 @@ extern "C" int ecgmm_transformer_infer(const ecgmm_transformer_infer_desc* d, co
   m.N = d->batch_first ? B : L;
   m.heads = d->heads; m.head_dim = E / d->heads; m.batch_first = d->batch_first; m.p_drop = 0.f;
   for (int l = 0; l < d->layers; ++l) {
-    const BlobT::Layer k = blobt_layer(*d, const_cast<void*>(blob), l);
+    const BlobT::Layer& k = q.layer[l];
     ECG_TRY(ecg_linear_fwd(w.x, k.in_w, k.in_b, w.qkv, (int)R, E, 3 * E, 0, nullptr, s));
     if (lengths) ECG_TRY(ecgmm_mha_forward_varlen(&m, w.qkv, lengths, w.att, w.lse, 0, 0, stream_));
     else ECG_TRY(ecgmm_mha_forward(&m, w.qkv, w.att, w.lse, 0, 0, stream_));

@@ -9,7 +9,6 @@ _bwd / _eval_bwd (one virtual batch = one row slice, no concatenation), and the 
 csrc/tabnet.hip: GLU gate, sparsemax, the mask / prior recurrence, column split (+ReLU), mask entropy.
 Every arithmetic step is a HIP kernel with a hand-written backward (torch.autograd.Function); there is no CPU path.
 """
-import ctypes as C
 import math
 import os
 
@@ -21,6 +20,7 @@ from .hip import functional as HF
 from .hip import lib as L
 from .hip import nn as hnn
 from .hip.functional import _Scratch, _require_cuda, f32c, grad_sink, ptr, stream
+from .hip.prepared import PreparedPlan
 
 EW = dict(MUL=0, ADD_SCALE=1, PRIOR=2, RELU=3, RELU_BWD=4, SCALE=5, NEG_MUL=6, ADD=7, RSUB=8)
 
@@ -367,6 +367,11 @@ FUSED_LIMITS = ("input_dim <= 64, n_d and n_a multiples of 16 with n_d + n_a <= 
                 "1 <= n_shared + n_independent <= 8, output width a multiple of 16 up to 128")
 
 
+class FusedPlan(PreparedPlan):
+    """``ecgmm_tabnet_infer*``: one folded blob, one launch, no workspace (``fused_fold`` / ``fused_run`` below)"""
+    prefix, name, who, workspace = "ecgmm_tabnet", "tabnet", "Predictor(ClinicalTabNetEncoder)", False
+
+
 def fused_refusal(enc, out_dim=16):
     """None when the fused path takes a ``TabNetEncoder`` of this shape, else the reason (it names the limit)"""
     layers = enc.n_shared + enc.n_independent
@@ -394,24 +399,13 @@ def fused_fold(enc, final_weight=None):
     want = 4 + 5 * (enc.n_steps + 1) * (enc.n_shared + enc.n_independent) + 5 * enc.n_steps + 1
     if len(params) != want:
         raise RuntimeError(f"TabNet: expected {want} float tensors in the state_dict, found {len(params)}")
-    for p in params:
-        _require_cuda(p, "TabNet fused forward: parameter")
-        if p.dtype != torch.float32 or not p.is_contiguous():
-            raise RuntimeError("TabNet fused forward: parameters must be contiguous fp32")
+    FusedPlan.check_params(params, "TabNet fused forward: parameter", fp32="TabNet fused forward")
     eps = {float(m.eps) for m in enc.modules() if isinstance(m, hnn.BatchNorm1d)}
     if len(eps) != 1:
         raise RuntimeError("TabNet fused forward: the BatchNorms do not share one eps")
     desc = L.TabNetInferDesc(enc.input_dim, enc.n_d, enc.n_a, enc.n_steps, enc.n_shared, enc.n_independent,
                              final_weight.shape[0], float(enc.gamma), float(enc.epsilon), eps.pop())
-    lib = L.lib()
-    nb = lib.ecgmm_tabnet_infer_prepared_bytes(C.byref(desc))
-    if nb == 0:
-        L.check(1, "tabnet prepared-size query")
-    with torch.cuda.device(dev), torch.no_grad():
-        blob = HF.new_bytes(nb, dev)   # a NEW blob: a forward already enqueued with an old one keeps consistent weights
-        table = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
-        L.check(lib.ecgmm_tabnet_infer_prepare(C.byref(desc), table, ptr(blob), blob.numel(), stream()), "tabnet infer prepare")
-    return desc, blob
+    return desc, FusedPlan.prepare(desc, [params], dev)
 
 
 def fused_run(desc, blob, x, explain=False, entropy=False):
@@ -420,16 +414,9 @@ def fused_run(desc, blob, x, explain=False, entropy=False):
     if x.dim() != 2 or x.shape[1] != desc.input_dim:
         raise ValueError(f"TabNet expects [B, {desc.input_dim}], got {tuple(x.shape)}")
     x = f32c(x.detach())
-    B, dev = x.shape[0], x.device
-    new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
-    out = new(B, desc.out_dim)
-    mexp, masks = (new(B, desc.input_dim), new(desc.n_steps, B, desc.input_dim)) if explain else (None, None)
-    ent = new(B) if entropy else None
-    with torch.cuda.device(dev):
-        blob.record_stream(torch.cuda.current_stream(dev))
-        L.check(L.lib().ecgmm_tabnet_infer(C.byref(desc), ptr(x), B, ptr(blob), blob.numel(), ptr(out), ptr(mexp), ptr(masks),
-                                           ptr(ent), stream()), "tabnet infer")
-    return out, mexp, masks, ent
+    B, D = x.shape
+    return tuple(FusedPlan.run(desc, blob, (x, B), [(B, desc.out_dim), (B, D) if explain else None,
+                                                    (desc.n_steps, B, D) if explain else None, (B,) if entropy else None], x.device))
 
 
 def _forward_masks(enc, x):

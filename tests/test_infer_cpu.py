@@ -154,6 +154,54 @@ def test_predictor_refuses_cpu_model_and_unknown_models():
         Predictor(torch.nn.Linear(2, 2))
 
 
+def test_every_registered_plan_prepares_through_the_one_base_procedure(monkeypatch):
+    """Every plan class ``Predictor`` knows derives from ``PreparedPlan`` and gets its blob from THAT class's prepare step.
+    With the step recording its calls, the device requirement waived (so CPU parameters do) and the library itself out of
+    reach, constructing each kind of predictor still works: no plan has a size-query-and-allocate sequence of its own."""
+    from ecgmm import inference as INF
+    from ecgmm.config import Config
+    from ecgmm.crnn import CRNN
+    from ecgmm.hip.prepared import PreparedPlan
+    from ecgmm.image_encoder import ResNet18
+    from ecgmm.multimodal import ECGMultimodalModel as TabVariant
+    from ecgmm.multimodal_paper_modal_balance import ECGMultimodalModel, ResNet1D_SE
+    from ecgmm.tabnet import ClinicalTabNetEncoder
+    from ecgmm.train_physionet import ECGTransformer1D
+
+    cfg = type("Cfg", (Config,), {"compute_dtype": "fp32", "clinical_input_dim": 24})
+    models = {ClinicalTabNetEncoder: [ClinicalTabNetEncoder(2, 32)], CRNN: [CRNN(compute_dtype="fp32")],
+              ECGTransformer1D: [ECGTransformer1D(seq_len=16, d_model=64, nhead=4, num_layers=2, dim_feedforward=128)],
+              ECGMultimodalModel: [ECGMultimodalModel(cfg), TabVariant(cfg)],
+              ResNet18: [ResNet18(num_classes=4, compute_dtype="fp32")], ResNet1D_SE: [ResNet1D_SE(1, 4, compute_dtype="fp32")]}
+    assert {kind for kind, _ in INF.PLANS} == set(models), "a registered plan has no model in this test"
+    calls, handed_out = [], []
+
+    def prepare(cls, desc, tables, device):
+        calls.append((cls, [len(t) for t in tables]))
+        handed_out.append(torch.zeros(16, dtype=torch.uint8))
+        return handed_out[-1]
+
+    def no_library():
+        raise AssertionError("a plan reached the library outside PreparedPlan.prepare")
+
+    monkeypatch.setattr(PreparedPlan, "prepare", classmethod(prepare))
+    monkeypatch.setattr(PreparedPlan, "check_params", staticmethod(lambda tensors, what, fp32=None: None))
+    monkeypatch.setattr(L, "lib", no_library)
+    for kind, plan in INF.PLANS:
+        assert issubclass(plan, PreparedPlan), plan.__name__
+        assert "prepare" not in vars(plan) and "run" not in vars(plan), plan.__name__ + " overrides a base procedure"
+        for model in models[kind]:
+            del calls[:], handed_out[:]
+            predict = INF.Predictor(model.eval())
+            assert type(predict.encoder) is plan
+            parts = [p for p in (predict.image, predict.signal, predict.clinical) if p is not None] or [predict.encoder]
+            assert len(calls) == len(parts) and all(issubclass(c, PreparedPlan) for c, _ in calls)
+            assert [id(p.blob) for p in parts] == [id(b) for b in handed_out], "a blob that the base did not prepare"
+            predict.refresh()
+            assert len(calls) == 2 * len(parts)
+            assert [id(p.blob) for p in parts] == [id(b) for b in handed_out[len(parts):]], "refresh() kept an old blob"
+
+
 def test_train_evaluate_keeps_its_default_signature():
     import inspect
 

@@ -263,6 +263,6 @@ def test_predictor_takes_the_clinical_encoder_and_keeps_its_eval_mode_message():
     with pytest.raises(ValueError, match="n_d=8"):
         inference._TabNetPlan(ClinicalTabNetEncoder(2, 8).eval())
     assert inspect.signature(inference.Predictor.__init__).parameters["clinical_plan"].default in (True, False)
-    src = inspect.getsource(inference.Predictor.__call__)
+    src = inspect.getsource(inference._MultimodalPlan.__call__)
     assert "Predictor: the clinical branch runs the model's own forward, which is in training mode " in src
     assert "ClinicalTabNetEncoder" in inference.Predictor.__doc__ and "clinical_plan" in inference.Predictor.__doc__
