@@ -474,6 +474,10 @@ int ecgmm_crnn_gradcam(const float* seq, const float* dseq, const int32_t* steps
                        size_t ws_bytes, float* cam, int B, int Tp, int C, int Fp, int F, int T, void* stream) {
   return ecg_crnn_gradcam(seq, dseq, steps, frames, ws, ws_bytes, cam, B, Tp, C, Fp, F, T, S_(stream));
 }
+int ecgmm_gradcam(int dtype, const void* act, const float* dpooled, float* small, float* out, int N, int Hs, int Ws, int C,
+                  int H, int W, void* stream) {
+  return ecg_gradcam(dtype, act, dpooled, small, out, N, Hs, Ws, C, H, W, S_(stream));
+}
 size_t ecgmm_conv5_bwd_weight_workspace(int dtype, const ecgmm_conv_desc* c) {
   if (!c) { ecg_set_error("conv5_bwd_weight_workspace: null desc"); return 0; }
   return ecg_conv5_wgrad_workspace(dtype, geom_of(c));

@@ -155,7 +155,10 @@ int ecg_crnn_gradcam(const float* seq, const float* dseq, const int* steps, cons
 int ecg_gradcam(int dtype, const void* act, const float* dpooled, float* small, float* out, int N, int Hs, int Ws, int C,
                 int H, int W, hipStream_t stream) {
   if (!act || !dpooled || !small || !out) ECG_FAIL(ECGMM_ERR_SHAPE, "gradcam: null operand");
-  if (N < 1 || Hs < 1 || Ws < 1 || C < 1 || H < 1 || W < 1) ECG_FAIL(ECGMM_ERR_SHAPE, "gradcam: bad shape");
+  if (N < 1 || Hs < 1 || Ws < 1 || C < 1 || H < 1 || W < 1)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "gradcam: bad shape N=%d Hs=%d Ws=%d C=%d H=%d W=%d", N, Hs, Ws, C, H, W);
+  // (the kernels index the coarse map and one output plane with int)
+  if ((long)Hs * Ws > 0x7fffffffL || (long)H * W > 0x7fffffffL) ECG_FAIL(ECGMM_ERR_SHAPE, "gradcam: map too large");
   const int R = Hs * Ws;
   const long NR = (long)N * R;
   const float scale = 1.f / (float)R;

@@ -244,6 +244,7 @@ SIGNATURES = {
     "ecgmm_conv5_in1_bwd_data_tile": (None, [i32, P(i32), P(i32), P(i32)]),
     "ecgmm_crnn_gradcam_workspace": (sz, [i32, i32, i32, i32]),
     "ecgmm_crnn_gradcam": (i32, [vp, vp, vp, vp, vp, sz, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "ecgmm_gradcam": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "ecgmm_relu_maxpool2": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, vp]),
     "ecgmm_conv5_in1_relu_pool2": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, vp]),
     "ecgmm_fold_conv5_bn": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, vp]),
@@ -344,7 +345,9 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  "ecgmm_linear_res_ln", "ecgmm_ffn_res_ln", "ecgmm_transformer_infer_prepared_bytes",
                  "ecgmm_transformer_infer_prepare", "ecgmm_transformer_infer_workspace", "ecgmm_transformer_infer",
                  # TabNet's fused eval forward and masks (ecgmm.inference._TabNetPlan, csrc/tabnet_infer.hip)
-                 "ecgmm_tabnet_infer_prepared_bytes", "ecgmm_tabnet_infer_prepare", "ecgmm_tabnet_infer")
+                 "ecgmm_tabnet_infer_prepared_bytes", "ecgmm_tabnet_infer_prepare", "ecgmm_tabnet_infer",
+                 # the encoders' Grad-CAM map kernels on their own (csrc/gradcam.hip)
+                 "ecgmm_gradcam")
 
 _lib = None
 

@@ -875,6 +875,17 @@ size_t ecgmm_crnn_gradcam_workspace(int B, int Tp, int Fp, int C);
 int ecgmm_crnn_gradcam(const float* seq, const float* dseq, const int32_t* steps, const int32_t* frames, void* ws,
                        size_t ws_bytes, float* cam, int B, int Tp, int C, int Fp, int F, int T, void* stream);
 
+/* The map kernels behind ecgmm_resnet18_gradcam / ecgmm_resnet1d_gradcam on their own (csrc/gradcam.hip), for callers that
+ * hold the last activation and d logit / d pooled themselves, and for the tests:
+ *   s[n][r]  = relu((1 / (Hs*Ws)) * sum_c dpooled[n][c] * act[n][r][c]),  s[n] *= 1 / max_r s[n][r]  (the reciprocal form: the
+ *              maximum becomes 1 or 1 - 2^-24; all zero when the maximum is 0)
+ *   out [N][H][W] fp32 = bilinear upsample of s from (Hs, Ws) to (H, W), align_corners=False
+ * act [N][Hs*Ws][C] channels-last in `dtype` (ECGMM_BF16 / ECGMM_F32), dpooled [N][C] fp32, small [N][Hs*Ws] fp32 scratch that
+ * holds the normalised coarse map afterwards; every element of small and out is written.  Refused with a message: a null
+ * operand, an extent < 1, an unknown dtype, Hs*Ws or H*W beyond 2^31 - 1. */
+int ecgmm_gradcam(int dtype, const void* act, const float* dpooled, float* small, float* out, int N, int Hs, int Ws, int C,
+                  int H, int W, void* stream);
+
 /* The log-spectrogram in front of the CRNN (train_physionet2.py:30-34): np.log1p(np.abs(scipy.signal.stft(x, fs, window,
  * nperseg=64, noverlap = 64 - hop)[2])) with scipy's defaults (boundary='zeros', padded=True, one-sided, scaling='spectrum',
  * no detrend) for a whole [S][L] fp32 matrix in one launch.  Frame t covers samples [hop*t - 32, hop*t + 32) of the record,

@@ -1,7 +1,7 @@
 """Float64 checkers: the bf16 conv kernels (below), the BatchNorm / pooling passes, the fp32 dense tails, the LSTM
 recurrence, the TabNet clinical branch, the ops that run only inside the encoder launch plans, the fp32-operand conv
-kernels and the two elementwise passes of the inference plans (their own sections further down, each with its bounds
-derived in a header comment).
+kernels, the two elementwise passes of the inference plans and the Grad-CAM map kernels of the two ResNet encoders (their own
+sections further down, each with its bounds derived in a header comment).
 
 
 With the operands rounded to bf16, every product x * w is exact in float64 and so is any sum of a few million of them to
@@ -1992,4 +1992,215 @@ def check_gate_res_relu(out, y, gate, res, rows_per_sample, bf16, name="gate_res
     print(r)
     assert torch.isfinite(out.double()).all(), name + ": non-finite output"
     assert r.ok, str(r)
+    return r
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Grad-CAM of the two ResNet encoders (csrc/gradcam.hip: ecgmm_gradcam, the map kernels behind ecgmm_resnet18_gradcam and
+# ecgmm_resnet1d_gradcam).  act [N][R = Hs * Ws][C] in the compute dtype and dpooled [N][C] fp32 are taken as given (a bf16
+# act already rounded), and the float64 evaluation of
+#     s = relu((1 / R) sum_c dpooled[n][c] act[n][r][c]),   q = s / max_r s  (all zero where the maximum is 0),
+#     out = F.interpolate(q, (H, W), mode="bilinear", align_corners=False)
+# is the exact answer.  Three stages, nothing calibrated:
+#
+#   weighted sum   e1 = g_k(C + 2) A,  A = (1 / R) sum_c |dpooled| |act|: the dot-product bound of C summands in any order
+#                  (lanes stride the channels, then a wave butterfly); the + 2 are the multiplication by the fp32 value of
+#                  1 / R and that value's own rounding.  ReLU is 1-Lipschitz and adds nothing.  Where dpooled itself is only
+#                  known to within dd (the plan entry points: the fp32 classifier backward against its float64 value), the
+#                  kernel's sum is that of dpooled + delta, |delta| <= dd:  e1 += (1 + g_k(C + 2)) (1 / R) sum_c dd |act|.
+#   normalise      with m = max_r s and em = max_r e1 (a maximum moves by no more than its arguments),
+#                      |s~ / m~ - s / m| = |(s~ - s) m - s (m~ - m)| / (m m~) <= (e1 + q em) / (m - em) =: d      (em < m)
+#                  and the encoders' form, q~ = s~ * fl(1 / m~), rounds twice more:  e2 = d + g_k(2) (q + d).
+#                  m == 0: every sum is <= 0; a sample none of whose sums fp32 can lift above 0 (|sum| > e1 everywhere) must be
+#                  exactly 0.  A maximum inside its own error (m <= em) decides nothing.  No error of a map in [0, 1] may
+#                  exceed 1: the bound is capped there, which is also what "decides nothing" means.
+#   upsample       per axis the kernel forms src~ = (dst + 0.5) * fl(in / out) - 0.5 in fp32: dst + 0.5 is exact, the quotient,
+#                  the product and the difference round once each, so |src~ - src| <= g_k(3) (|src| + 1) =: dsrc (src before
+#                  the clamp at 0, which is 1-Lipschitz).  The weight lam = src~ - floor(src~) is exact.  Write f~ for the
+#                  bilinear interpolant of the kernel's coarse map q~ and f for that of q:
+#                      |out - f(src)| <= |f~(src) - f(src)| + |f~(src~) - f~(src)| + rounding of the lerp
+#                    * the first term is the interpolant of q~ - q at the exact coordinate: a convex combination of the four
+#                      neighbours' errors, at most the largest of them;
+#                    * f~ is continuous and piecewise linear in each coordinate, so the second is at most dsrc times the
+#                      largest slope |q~[i + 1] - q~[i]| between src and src~.  Being continuous it needs no special case
+#                      where fp32 and float64 choose a different i0 at an integer boundary: the two cells agree on their
+#                      common edge.  The slope is taken over the cell and its neighbours on either side (a 3 x 3 dilation of
+#                      the per-node largest adjacent difference), and from q with 2 max(e2) added for q~;
+#                    * the lerp c0 * fl(1 - lam) + c1 * lam rounds three times on its longest path, per axis: g_k(3) or
+#                      g_k(6) times the largest of the four values.
+#                  An axis with in == out has fl(in / out) = 1, src~ = dst exactly and lam = 0: c0 * 1 + c1 * 0 is c0, no
+#                  rounding and no coordinate term -- with both axes so, out is the coarse map bit for bit.
+#   Given the kernel's own stored coarse map (`small`), the upsample is checked on its own from it, as every consumer stage
+#   in this file is (e_in = 0), and the coarse map against stages 1 and 2.
+#
+# What the bound can and cannot resolve: at C = 512 the first stage alone is 514 u A / m of a map in [0, 1], some hundreds of
+# fp32 ulps where the channel sum cancels -- it is the standard bound, not tightened to the kernel's tree.  Lost channels, a
+# neighbour's weights or maximum, swapped extents, align_corners=True, a missing -0.5, a missing ReLU and a border clamped
+# one early are all orders of magnitude outside it (tests/test_gradcam_cpu.py); a few fp32 ulps on one element are resolved
+# only where the derivation leaves no room: a sample that must be exactly 0, and the upsample of a stored coarse map at
+# identity size.  Dropping the 1 / R scale cancels in the normalisation and is accepted, as it must be.
+# Measured on the MI355X: tests/test_gradcam_f64_gpu.py, module docstring.
+# ----------------------------------------------------------------------------------------------------------------------
+# (N, Hs, Ws, C, H, W) -> the sample given an all-negative dpooled (None: none)
+GRADCAM_CASES = {
+    (2, 7, 7, 512, 224, 224): None,
+    (1, 8, 79, 512, 250, 2500): None,
+    (2, 1, 313, 256, 1, 5000): None,
+    (3, 1, 1, 64, 5, 9): 1,
+    (2, 3, 5, 70, 3, 5): 0,
+    (2, 9, 11, 33, 4, 6): None,
+    (5, 2, 3, 8, 7, 7): 2,
+    (2, 17, 19, 16, 40, 40): None,
+    (5, 2, 2, 8, 512, 512): 4,
+}
+# a sample meant to be nonzero has its float64 maximum at least this many times above the weighted-sum bound
+GRADCAM_MARGIN = 100.0
+
+
+# the salt of the operands: chosen on the float64 reference alone (tests/test_gradcam_cpu.py asserts it) so that every live
+# sample of every case clears GRADCAM_MARGIN -- with R == 1 a sample has one sum, which half the salts make negative
+GRADCAM_SALT = 10
+
+
+def gradcam_inputs(case, bf16, salt=GRADCAM_SALT):
+    """act [N][R][C] >= 0 with about half its elements 0, as behind a ReLU (bf16-rounded for bf16), dpooled [N][C] of mixed
+    signs (the ReLU clips about half the positions); the case's negative sample gets -|dpooled| - 2^-10 (every weighted sum of it is <= 0)"""
+    from oracle import fill
+    N, Hs, Ws, C, H, W = case
+    act = _b(fill.hash_tensor((N, Hs * Ws, C), 7001 + salt).clamp_min(0), bf16)
+    dp = fill.hash_tensor((N, C), 7002 + salt, 0.5)
+    neg = GRADCAM_CASES.get(tuple(case))
+    if neg is not None:
+        dp[neg] = -dp[neg].abs() - 2.0 ** -10
+    return act, dp
+
+
+@dataclass
+class GradcamRef:
+    pre: torch.Tensor        # (1 / R) sum_c dpooled * act before the ReLU           [N][R] float64
+    A: torch.Tensor          # the same on absolute values
+    m: torch.Tensor          # per-sample maximum of relu(pre)                        [N]
+    small: torch.Tensor      # the normalised coarse map                              [N][Hs][Ws]
+    out: torch.Tensor        # upsampled                                              [N][H][W]
+    e_small: torch.Tensor    # allowed |error| of the coarse map (stages 1 and 2)     [N][Hs][Ws]
+    e_out: torch.Tensor      # allowed |error| of the map from the operands (all three stages)
+    em: torch.Tensor         # weighted-sum bound at its largest, per sample          [N]
+
+
+def upsample_ref(small, H, W):
+    """small [N][Hs][Ws] -> float64 [N][H][W], F.interpolate(bilinear, align_corners=False)"""
+    return F.interpolate(small.double()[:, None], size=(H, W), mode="bilinear", align_corners=False)[:, 0]
+
+
+def _axis(in_, out_, dev_):
+    """float64 source coordinate of every destination index (clamped at 0), its cell i0, i1 and the coordinate error"""
+    dst = torch.arange(out_, dtype=torch.float64, device=dev_)
+    raw = (dst + 0.5) * (float(in_) / float(out_)) - 0.5
+    src = raw.clamp_min(0)
+    i0 = src.floor().long().clamp_max(in_ - 1)
+    i1 = (i0 + 1).clamp_max(in_ - 1)
+    dsrc = torch.zeros_like(src) if in_ == out_ else g_k(3) * (raw.abs() + 1)
+    return i0, i1, dsrc
+
+
+def _dilate(v):
+    """largest value of the 3 x 3 neighbourhood, v [N][Hs][Ws]"""
+    return F.max_pool2d(v[:, None], 3, stride=1, padding=1)[:, 0]
+
+
+def upsample_bound(small, e_in, H, W):
+    """allowed |out - upsample_ref(small)| of the fp32 upsample of a coarse map known to within e_in (same shape as small,
+    or None: the map is the kernel's own stored input)"""
+    q = small.double()
+    N, Hs, Ws = q.shape
+    e = torch.zeros_like(q) if e_in is None else e_in.double()
+    h0, h1, dh = _axis(Hs, H, q.device)
+    w0, w1, dw = _axis(Ws, W, q.device)
+    cell = lambda t: torch.stack([t[:, h0][:, :, w0], t[:, h0][:, :, w1], t[:, h1][:, :, w0], t[:, h1][:, :, w1]]).amax(0)
+    e4, v4 = cell(e), cell(q.abs() + e)
+    K = 3 * (int(Hs != H) + int(Ws != W))
+    bound = e4 + g_k(K) * v4 if K else e4
+    emax2 = 2 * _dilate(e)
+    z = torch.zeros_like(q)
+    if Ws != W:
+        d = (q[:, :, 1:] - q[:, :, :-1]).abs()
+        node = torch.maximum(torch.cat([d, z[:, :, :1]], 2), torch.cat([z[:, :, :1], d], 2))
+        bound = bound + dw.view(1, 1, W) * (_dilate(node) + emax2)[:, h0][:, :, w0]
+    if Hs != H:
+        d = (q[:, 1:] - q[:, :-1]).abs()
+        node = torch.maximum(torch.cat([d, z[:, :1]], 1), torch.cat([z[:, :1], d], 1))
+        bound = bound + dh.view(1, H, 1) * (_dilate(node) + emax2)[:, h0][:, :, w0]
+    return bound.clamp_max(1.0)
+
+
+def gradcam_ref(act, dpooled, Hs, Ws, H, W, dpooled_err=None):
+    """float64 Grad-CAM of the operands as given and the allowed error of every element.  act [N][Hs * Ws][C] (any float dtype),
+    dpooled [N][C]; dpooled_err [N][C]: what the kernel's dpooled may differ by from the one given here"""
+    a, d = act.double(), dpooled.double()
+    N, R, C = a.shape
+    assert R == Hs * Ws and d.shape == (N, C)
+    pre = torch.einsum("nrc,nc->nr", a, d) / R
+    A = torch.einsum("nrc,nc->nr", a.abs(), d.abs()) / R
+    e1 = g_k(C + 2) * A
+    if dpooled_err is not None:
+        e1 = e1 + (1 + g_k(C + 2)) * torch.einsum("nrc,nc->nr", a.abs(), dpooled_err.double()) / R
+    s = pre.clamp_min(0)
+    m, em = s.amax(1), e1.amax(1)
+    live = (m > 0)[:, None]
+    q = torch.where(live, s / m.clamp_min(1e-300)[:, None], torch.zeros_like(s))
+    room = (m - em)[:, None]
+    dq = torch.where(room > 0, (e1 + q * em[:, None]) / room.clamp_min(1e-300), torch.full_like(q, float("inf")))
+    e2 = dq + g_k(2) * (q + dq)
+    # m == 0: exactly zero unless fp32 may lift some sum of the sample above 0
+    may_rise = ((e1 >= pre.abs()) & (e1 > 0)).any(1, keepdim=True)
+    e2 = torch.where(live, e2, torch.where(may_rise, torch.ones_like(e2), torch.zeros_like(e2))).clamp_max(1.0)
+    small, e_small = q.view(N, Hs, Ws), e2.view(N, Hs, Ws)
+    return GradcamRef(pre, A, m, small, upsample_ref(small, H, W), e_small, upsample_bound(small, e_small, H, W), em)
+
+
+def gradcam_ratio(out, ref, small=None, name="gradcam"):
+    """worst |err| / bound of a map against gradcam_ref.  small None: out against the three-stage bound.  small given (the
+    kernel's stored coarse map): small against stages 1 and 2, out against the float64 upsample of that stored map.
+    .parts: the two ratios (small, out)"""
+    N, H, W = ref.out.shape
+    out = out.reshape(N, H, W).double()
+    if small is None:
+        ratio = _ratio((out - ref.out).abs(), ref.e_out)
+        parts = dict(out=float(ratio.max()))
+    else:
+        sm = small.reshape(ref.small.shape).double()
+        r_small = _ratio((sm - ref.small).abs(), ref.e_small)
+        fin = torch.where(torch.isfinite(sm), sm, torch.zeros_like(sm))
+        ratio = _ratio((out - upsample_ref(fin, H, W)).abs(), upsample_bound(fin, None, H, W))
+        parts = dict(small=float(r_small.max()), out=float(ratio.max()))
+        if parts["small"] > parts["out"]:
+            flat = int(torch.argmax(r_small))
+            r = Report(name + " (coarse map)", parts["small"], _unravel(flat, r_small.shape))
+            r.parts = parts
+            return r
+    flat = int(torch.argmax(ratio))
+    r = Report(name, float(ratio.reshape(-1)[flat]), _unravel(flat, ratio.shape))
+    r.parts = parts
+    return r
+
+
+def gradcam_live(ref, expect_zero=()):
+    """the reference alone: every sample not in expect_zero has its maximum GRADCAM_MARGIN times above the weighted-sum bound
+    (never zeros against zeros), every sample in it is all zero with a bound of exactly 0.  -> smallest m / em seen"""
+    worst = float("inf")
+    for n in range(ref.m.shape[0]):
+        if n in expect_zero:
+            assert float(ref.m[n]) == 0 and float(ref.out[n].abs().max()) == 0 and float(ref.e_out[n].max()) == 0, n
+        else:
+            margin = float(ref.m[n] / ref.em[n].clamp_min(1e-300))
+            assert margin >= GRADCAM_MARGIN, "sample %d: maximum %.3g against a bound of %.3g" % (n, float(ref.m[n]), float(ref.em[n]))
+            worst = min(worst, margin)
+    return worst
+
+
+def check_gradcam(out, ref, small=None, name="gradcam"):
+    r = gradcam_ratio(out, ref, small, name)
+    print(r, r.parts)
+    assert torch.isfinite(out.double()).all(), name + ": non-finite map"
+    assert r.ok, str(r) + " " + str(r.parts)
     return r

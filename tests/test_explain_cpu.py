@@ -13,7 +13,7 @@ from ecgmm.image_encoder import ResNet18
 from ecgmm.multimodal_paper_modal_balance import ECGMultimodalModel
 
 NEW = ("ecgmm_stem_bwd_data", "ecgmm_resnet18_backward_dx", "ecgmm_resnet1d_backward_dx", "ecgmm_resnet18_gradcam",
-       "ecgmm_resnet1d_gradcam", "ecgmm_bn_eval_bwd", "ecgmm_bn_small_eval_bwd")
+       "ecgmm_resnet1d_gradcam", "ecgmm_bn_eval_bwd", "ecgmm_bn_small_eval_bwd", "ecgmm_gradcam")
 
 
 def test_new_entry_points_are_declared_bound_and_exported():
@@ -23,6 +23,16 @@ def test_new_entry_points_are_declared_bound_and_exported():
     for name in NEW:
         assert name + "(" in header and name in L.SIGNATURES and hasattr(h, name), name
     assert L.lib().ecgmm_version() == 100
+
+
+def test_gradcam_op_refusals_launch_nothing():
+    """ecgmm_gradcam checks its arguments before its first launch: every refusal answers without a GPU"""
+    lib = L.lib()
+    p = ctypes.c_void_p(256)             # never dereferenced: each call below is refused first
+    for args, msg in (((L.F32, None, p, p, p, 2, 7, 7, 512, 224, 224), b"null"), ((L.BF16, p, p, p, None, 2, 7, 7, 512, 224, 224), b"null"),
+                      ((L.F32, p, p, p, p, 2, 0, 7, 512, 224, 224), b"bad shape"), ((L.F32, p, p, p, p, 2, 7, 7, 512, 224, 0), b"bad shape"),
+                      ((L.F32, p, p, p, p, 1, 46341, 46341, 8, 4, 4), b"too large"), ((L.F32, p, p, p, p, 1, 2, 2, 8, 65536, 32768), b"too large")):
+        assert lib.ecgmm_gradcam(*args, None) != 0 and msg in lib.ecgmm_last_error(), args
 
 
 def test_explain_refuses_cpu_tensors():
