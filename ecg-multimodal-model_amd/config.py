@@ -62,6 +62,7 @@ class Config:
     num_workers = 0
     physionet2_max_len = None       # train_physionet2: truncate longer records before the spectrogram (None: keep all)
     physionet2_use_lengths = False  # train_physionet2: each record's own length to the BiLSTM and the mean over time
+    physionet2_lstm_dtype = "fp32"  # train_physionet2: the BiLSTM's recurrent products, "fp32" (exact) or "bf16" (W_hh on chip)
     physionet2_saliency_samples = 0  # train_physionet2: input gradients + Grad-CAM of the first k test spectrograms (npz)
     physionet_time_attention = False  # train_physionet, model="transformer": attend along the positions (batch_first=True)
     physionet_use_lengths = False     # train_physionet, with time attention: each record's own length to the encoder and the mean

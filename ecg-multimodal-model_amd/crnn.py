@@ -25,7 +25,9 @@ class ConvBlock(nn.Module):
 
 
 class CRNN(nn.Module):
-    def __init__(self, input_channels=1, num_classes=2, compute_dtype="fp32"):
+    def __init__(self, input_channels=1, num_classes=2, compute_dtype="fp32", lstm_dtype=None):
+        """``compute_dtype``: the three ConvBlocks.  ``lstm_dtype``: the BiLSTM's recurrent products, ``None`` = ``"fp32"``
+        whatever ``compute_dtype`` is (``"bf16"``: :class:`ecgmm.hip.nn.LSTM` with ``compute_dtype="bf16"``)."""
         super().__init__()
         if input_channels != 1:
             raise ValueError(f"CRNN: input_channels={input_channels} is not supported: the first convolution's kernel takes "
@@ -36,7 +38,8 @@ class CRNN(nn.Module):
         self.conv2 = ConvBlock(32, 64)
         self.conv3 = ConvBlock(64, 128)
         self.flatten = nn.Flatten(start_dim=2)
-        self.bilstm = HN.LSTM(512, 200, 3, batch_first=True, bidirectional=True)
+        self.lstm_dtype = "fp32" if lstm_dtype is None else str(lstm_dtype).lower()
+        self.bilstm = HN.LSTM(512, 200, 3, batch_first=True, bidirectional=True, compute_dtype=self.lstm_dtype)
         self.classifier = HN.Sequential(HN.Linear(400, 64), nn.ReLU(), nn.Dropout(0.3), HN.Linear(64, num_classes))
 
     def _front_tables(self):

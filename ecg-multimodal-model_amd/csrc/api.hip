@@ -421,29 +421,47 @@ int ecgmm_axpby(float a, const float* x, float b, float* y, int64_t n, void* str
   return ecg_axpby(a, x, b, y, (long)n, S_(stream));
 }
 
-size_t ecgmm_lstm_fwd_workspace(const ecgmm_lstm_desc* d) { return ecg_lstm_fwd_workspace(d); }
-size_t ecgmm_lstm_bwd_workspace(const ecgmm_lstm_desc* d) { return ecg_lstm_bwd_workspace(d); }
+size_t ecgmm_lstm_fwd_workspace(const ecgmm_lstm_desc* d) { return ecg_lstm_fwd_workspace(d, ECGMM_F32); }
+size_t ecgmm_lstm_bwd_workspace(const ecgmm_lstm_desc* d) { return ecg_lstm_bwd_workspace(d, ECGMM_F32); }
 int ecgmm_lstm_forward(const ecgmm_lstm_desc* d, const float* x, const float* const* params, const float* h0,
                        const float* c0, float* y, float* hn, float* cn, void* ws, size_t ws_bytes, void* stream) {
-  return ecg_lstm_forward(d, x, nullptr, params, h0, c0, y, hn, cn, ws, ws_bytes, S_(stream));
+  return ecg_lstm_forward(d, ECGMM_F32, x, nullptr, params, h0, c0, y, hn, cn, ws, ws_bytes, S_(stream));
 }
 int ecgmm_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const float* const* params, const float* h0,
                         const float* c0, const float* dy, const float* dhn, const float* dcn, const void* ws, float* dx,
                         float* const* grads, float* dh0, float* dc0, void* scratch, size_t scratch_bytes, void* stream) {
-  return ecg_lstm_backward(d, x, nullptr, params, h0, c0, dy, dhn, dcn, ws, dx, grads, dh0, dc0, scratch, scratch_bytes,
-                           S_(stream));
+  return ecg_lstm_backward(d, ECGMM_F32, x, nullptr, params, h0, c0, dy, dhn, dcn, ws, dx, grads, dh0, dc0, scratch,
+                           scratch_bytes, S_(stream));
 }
 int ecgmm_lstm_forward_varlen(const ecgmm_lstm_desc* d, const float* x, const int32_t* lengths, const float* const* params,
                               const float* h0, const float* c0, float* y, float* hn, float* cn, void* ws, size_t ws_bytes,
                               void* stream) {
-  return ecg_lstm_forward(d, x, lengths, params, h0, c0, y, hn, cn, ws, ws_bytes, S_(stream));
+  return ecg_lstm_forward(d, ECGMM_F32, x, lengths, params, h0, c0, y, hn, cn, ws, ws_bytes, S_(stream));
 }
 int ecgmm_lstm_backward_varlen(const ecgmm_lstm_desc* d, const float* x, const int32_t* lengths, const float* const* params,
                                const float* h0, const float* c0, const float* dy, const float* dhn, const float* dcn,
                                const void* ws, float* dx, float* const* grads, float* dh0, float* dc0, void* scratch,
                                size_t scratch_bytes, void* stream) {
-  return ecg_lstm_backward(d, x, lengths, params, h0, c0, dy, dhn, dcn, ws, dx, grads, dh0, dc0, scratch, scratch_bytes,
-                           S_(stream));
+  return ecg_lstm_backward(d, ECGMM_F32, x, lengths, params, h0, c0, dy, dhn, dcn, ws, dx, grads, dh0, dc0, scratch,
+                           scratch_bytes, S_(stream));
+}
+size_t ecgmm_lstm_fwd_workspace_dt(const ecgmm_lstm_desc* d, int dtype) { return ecg_lstm_fwd_workspace(d, dtype); }
+size_t ecgmm_lstm_bwd_workspace_dt(const ecgmm_lstm_desc* d, int dtype) { return ecg_lstm_bwd_workspace(d, dtype); }
+int ecgmm_lstm_forward_dt(const ecgmm_lstm_desc* d, int dtype, const float* x, const int32_t* lengths,
+                          const float* const* params, const float* h0, const float* c0, float* y, float* hn, float* cn,
+                          void* ws, size_t ws_bytes, void* stream) {
+  return ecg_lstm_forward(d, dtype, x, lengths, params, h0, c0, y, hn, cn, ws, ws_bytes, S_(stream));
+}
+int ecgmm_lstm_backward_dt(const ecgmm_lstm_desc* d, int dtype, const float* x, const int32_t* lengths,
+                           const float* const* params, const float* h0, const float* c0, const float* dy, const float* dhn,
+                           const float* dcn, const void* ws, float* dx, float* const* grads, float* dh0, float* dc0,
+                           void* scratch, size_t scratch_bytes, void* stream) {
+  return ecg_lstm_backward(d, dtype, x, lengths, params, h0, c0, dy, dhn, dcn, ws, dx, grads, dh0, dc0, scratch,
+                           scratch_bytes, S_(stream));
+}
+int ecgmm_lstm_ws_view(const ecgmm_lstm_desc* d, int dtype, const char* which, int layer, int direction, size_t* offset,
+                       size_t* bytes) {
+  return ecg_lstm_ws_view(d, dtype, which, layer, direction, offset, bytes);
 }
 int ecgmm_seq_mean_varlen_fwd(const float* x, const int32_t* lengths, float* out, int B, int T, int C, void* stream) {
   return ecg_seq_mean_varlen_fwd(x, lengths, out, B, T, C, S_(stream));

@@ -61,6 +61,7 @@ struct LstmFwdArgs {
   LstmFwdDir d[2];
   const int* lengths;   // [B] or null (VL kernels only)
   int B, T, H, ldo, batch_first, save;
+  const u32x4* w_pack[2];   // bf16 kernels: W_hh of each direction as bf16 B fragments (pack_whh_bf16_kernel)
 };
 
 struct LstmBwdDir {
@@ -80,6 +81,7 @@ struct LstmBwdArgs {
   LstmBwdDir d[2];
   const int* lengths;   // [B] or null (VL kernels only)
   int B, T, H, ldo, batch_first;
+  const u32x4* w_pack[2];   // bf16 kernels: W_hh^T of each direction as bf16 B fragments
 };
 
 __device__ __forceinline__ size_t seq_row(int b, int t, int B, int T, int batch_first) {
@@ -357,6 +359,373 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_seq_bwd_kernel(LstmBwdArgs 
   }
 }
 
+// ---- compute dtype bf16: the recurrent products on v_mfma_f32_16x16x32_bf16, W_hh held on chip ---------------------------------
+// Only the recurrent operands are rounded (f2bf, to nearest even): pre_t = P_t + b_hh + bf(h_{t-1}) bf(W_hh)^T in the forward,
+// dh_{t-1} = dy_{t-1} + bf(dgates_t) bf(W_hh) in the backward; products are exact and summed in fp32 in the accumulator, in the
+// order of the K steps.  Everything stored (y, h_{t-1}, c_t, gates, dgates, the states) is the unrounded fp32 value.
+// Same slices and ownership as the fp32 kernels: tile ht = wave + 8 ti of 16 hidden units belongs to one wave for all steps, so
+// c, the fp32 h, and the dh / dc carries are lane-local REGISTERS in the C/D layout (row 4 (lane >> 4) + r, unit lane & 15); LDS
+// holds only what every wave reads: bf16 h (double-buffered, one barrier per step) resp. the step's bf16 gate gradients (two
+// barriers per step).  K is padded with zeros to a multiple of 32: KS = ceil(Hp / 32) steps forward, 4 Hp / 32 backward.
+// One pack launch per call rounds the fp32 W_hh of every layer and direction to bf16 B fragments in operand order, into the
+// workspace (written by every call from the parameter itself: there is no copy that could go stale).  Before the time loop a
+// wave fetches its own tiles' fragments once, 16 bytes per lane and fragment: the first KR K-steps of each tile stay in
+// registers; the rest sits in LDS (REST = 1: no W_hh byte is fetched inside the time loop) or, where it does not fit, streams
+// from that copy every step (REST = 2).  (Converting from fp32 inside the set-up was tried: the compiler gathers the eight
+// scalar loads of every fragment before the first conversion, and the kernel spills hundreds of registers.)
+// Fragment of lane l for K-step ks: elements k = 32 ks + 8 (l >> 4) + 0..7 of A's row / B's column l & 15.
+
+// forward B operand: unit j of gate g, reduction indices k0 .. k0 + 7 of W_hh [4H][H]
+__device__ __forceinline__ u32x4 whh_frag_fwd(const float* w, int H, int g, int j, int k0) {
+  // every load is in bounds (clamped) and unconditional, then selected: no branch per element
+  const float* wrow = w + ((size_t)g * H + (j < H ? j : H - 1)) * H;
+  float f[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int k = k0 + u;
+    const float v = wrow[k < H ? k : H - 1];
+    f[u] = j < H && k < H ? v : 0.f;
+  }
+  return pack16<bf16_t>(f);
+}
+// backward B operand: output unit k, reduction indices n0 .. n0 + 7 of the padded gate columns (gate g at g Hp .. g Hp + H)
+__device__ __forceinline__ u32x4 whh_frag_bwd(const float* w, int H, int Hp, int k, int n0) {
+  const int g = n0 / Hp, j0 = n0 - g * Hp;   // n0 % 8 == 0 and Hp % 16 == 0: the eight columns are of one gate
+  const float* wcol = w + (size_t)(g < 4 ? g : 3) * H * H + (k < H ? k : H - 1);
+  float f[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int j = j0 + u;
+    const float v = wcol[(size_t)(j < H ? j : H - 1) * H];   // in bounds (clamped), unconditional, then selected
+    f[u] = g < 4 && k < H && j < H ? v : 0.f;
+  }
+  return pack16<bf16_t>(f);
+}
+__device__ __forceinline__ f32x4 mfma_bf16(const u32x4& a, const u32x4& b, const f32x4& c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
+}
+
+struct LstmPackArgs {
+  const float* w[2 * LSTM_MAX_LAYERS];
+  u32x4* dst[2 * LSTM_MAX_LAYERS];
+  int H, transposed;
+};
+// forward: dst[((ht KS + ks) 4 + g) 64 + lane]; transposed (backward): dst[(kt KSB + ks) 64 + lane].  blockIdx.y = matrix.
+__global__ __launch_bounds__(256) void pack_whh_bf16_kernel(LstmPackArgs a) {
+  const int H = a.H, Hp = (H + 15) & ~15, tiles = Hp >> 4;
+  const float* w = a.w[blockIdx.y];
+  u32x4* dst = a.dst[blockIdx.y];
+  const int KS = a.transposed ? Hp >> 3 : (Hp + 31) >> 5;
+  const int n = tiles * KS * (a.transposed ? 1 : 4) * 64;
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256) {
+    const int lane = e & 63, i16 = lane & 15, g4 = lane >> 4;
+    int q = e >> 6;
+    if (a.transposed) {
+      const int ks = q % KS, kt = q / KS;
+      dst[e] = whh_frag_bwd(w, H, Hp, kt * 16 + i16, ks * 32 + 8 * g4);
+    } else {
+      const int g = q & 3;
+      q >>= 2;
+      const int ks = q % KS, ht = q / KS;
+      dst[e] = whh_frag_fwd(w, H, g, ht * 16 + i16, ks * 32 + 8 * g4);
+    }
+  }
+}
+
+// KR K-steps in registers for a wave's first tile, KR1 <= KR for its others (two or three tiles at KR each leave the cell
+// update no registers: the compiler spills)
+template <int NT, int KR, int KR1, int REST, bool VL>
+__global__ __launch_bounds__(LSTM_THREADS) void lstm_seq_fwd_bf16_kernel(LstmFwdArgs a) {
+  extern __shared__ float lstm_lds[];
+  const LstmFwdDir& p = a.d[blockIdx.y];
+  const int H = a.H, Hp = (H + 15) & ~15, KS = (Hp + 31) >> 5, HB = KS * 32 + 8, B = a.B, T = a.T;
+  const int rest0 = KS > KR ? KS - KR : 0, rest1 = KS > KR1 ? KS - KR1 : 0;   // K-steps not in registers: tiles 0..7, others
+  bf16_t* hb = reinterpret_cast<bf16_t*>(lstm_lds);             // [2][16][HB]: bf(h), columns H .. 32 KS stay zero
+  int* len = reinterpret_cast<int*>(hb + 2 * LSTM_ROWS * HB);   // [16]
+  u32x4* wl = reinterpret_cast<u32x4*>(len + LSTM_ROWS);        // REST == 1: [tile][rest][4][64] B fragments
+  const u32x4* wg = a.w_pack[blockIdx.y];                       // all of bf(W_hh) as B fragments (pack_whh_bf16_kernel)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i16 = lane & 15, g4 = lane >> 4;
+  const int b0 = blockIdx.x * LSTM_ROWS;
+
+  for (int e = tid; e < LSTM_ROWS * HB; e += LSTM_THREADS) {
+    const int b = e / HB, j = e - b * HB;
+    const bool ok = j < H && b0 + b < B;
+    hb[e] = ok && p.h0 ? f2bf(p.h0[(size_t)(b0 + b) * H + j]) : (bf16_t)0;
+    hb[LSTM_ROWS * HB + e] = 0;
+  }
+  if (VL) load_slice_lengths(len, a.lengths, b0, B, T);
+  u32x4 wr[NT][KR][4];   // this wave's tiles, K-steps 0 .. KR-1, for all T steps
+  float hreg[NT][4], creg[NT][4];
+#pragma unroll
+  for (int ti = 0; ti < NT; ++ti) {
+    const int ht = wave + ti * LSTM_WAVES, j = ht * 16 + i16;
+#pragma unroll
+    for (int ks = 0; ks < KR; ++ks)
+#pragma unroll
+      for (int g = 0; g < 4; ++g)   // a fragment no MFMA uses (tile or K-step outside H) reads fragment 0: in bounds, unused
+        wr[ti][ks][g] = wg[ht * 16 < Hp && ks < KS ? ((ht * KS + ks) * 4 + g) * 64 + lane : lane];
+    if (REST == 1 && ht * 16 < Hp) {
+      const int kr = ti == 0 ? KR : KR1;
+      const int lo = ti == 0 ? ht * rest0 - kr : LSTM_WAVES * rest0 + (ht - LSTM_WAVES) * rest1 - kr;   // + ks: LDS K-step slot
+      for (int ks = kr; ks < KS; ++ks)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) wl[((lo + ks) * 4 + g) * 64 + lane] = wg[((ht * KS + ks) * 4 + g) * 64 + lane];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int b = b0 + g4 * 4 + r;
+      const bool ok = j < H && b < B;
+      hreg[ti][r] = ok && p.h0 ? p.h0[(size_t)b * H + j] : 0.f;
+      creg[ti][r] = ok && p.c0 ? p.c0[(size_t)b * H + j] : 0.f;
+    }
+  }
+  __syncthreads();
+  const int tmax = VL ? slice_tmax(len) : T;   // executed steps: uniform over the workgroup
+  if (VL) {   // steps tmax .. T-1 of the slice: y = 0 and a finite hprev
+    const int nb = B - b0 < LSTM_ROWS ? B - b0 : LSTM_ROWS;
+    for (int e = tid; e < (T - tmax) * nb * H; e += LSTM_THREADS) {
+      const int tt = tmax + e / (nb * H), q = e % (nb * H), b = b0 + q / H, j = q % H;
+      const size_t row = seq_row(b, tt, B, T, a.batch_first);
+      p.out[row * a.ldo + j] = 0.f;
+      if (a.save) p.hprev[row * H + j] = 0.f;
+    }
+  }
+
+  const int G4 = 4 * H;
+  for (int s = 0; s < tmax; ++s) {
+    const int t = p.reverse ? tmax - 1 - s : s;
+    const bf16_t* hc = hb + (s & 1) * LSTM_ROWS * HB;
+    bf16_t* hx = hb + ((s + 1) & 1) * LSTM_ROWS * HB;
+#pragma unroll
+    for (int ti = 0; ti < NT; ++ti) {
+      const int ht = wave + ti * LSTM_WAVES;
+      if (ht * 16 < Hp) {   // uniform over the wave; no barrier inside
+        int j = ht * 16 + i16;
+        asm volatile("" : "+v"(j));   // addresses are formed anew each step: hoisted out of the time loop, every tile's
+                                      // and row's pointers would take the registers the weights live in
+        const bool jok = j < H;
+        unsigned row[4];   // B T max(4H, In) < 2^31 (check_desc): every element offset below fits 32 bits
+        bool rok[4];
+        float xg[4][4];   // P_t + b_hh
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int b = b0 + g4 * 4 + r;
+          rok[r] = jok && b < B;
+          row[r] = (unsigned)seq_row(b < B ? b : B - 1, t, B, T, a.batch_first);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const float bh = jok ? p.b_hh[g * H + j] : 0.f;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) xg[g][r] = (rok[r] ? p.gates[row[r] * G4 + g * H + j] : 0.f) + bh;
+        }
+        f32x4 acc[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const bf16_t* ha = hc + i16 * HB + 8 * g4;
+        const int kr = ti == 0 ? KR : KR1;
+        const int lo = ti == 0 ? ht * rest0 - kr : LSTM_WAVES * rest0 + (ht - LSTM_WAVES) * rest1 - kr;
+#pragma unroll
+        for (int ks = 0; ks < (ti == 0 ? KR : KR1); ++ks)
+          if (ks < KS) {
+            const u32x4 av = *reinterpret_cast<const u32x4*>(ha + ks * 32);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) acc[g] = mfma_bf16(av, wr[ti][ks][g], acc[g]);
+          }
+        if (REST != 0)
+          for (int ks = kr; ks < KS; ++ks) {
+            const u32x4 av = *reinterpret_cast<const u32x4*>(ha + ks * 32);
+            const u32x4* wp = REST == 1 ? wl + ((lo + ks) * 4) * 64 + lane : wg + ((ht * KS + ks) * 4) * 64 + lane;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) acc[g] = mfma_bf16(av, wp[g * 64], acc[g]);
+          }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int bl = g4 * 4 + r;
+          const float ig = sigmoidf_(acc[0][r] + xg[0][r]);
+          const float fg = sigmoidf_(acc[1][r] + xg[1][r]);
+          const float gg = tanhf(acc[2][r] + xg[2][r]);
+          const float og = sigmoidf_(acc[3][r] + xg[3][r]);
+          const float hp = hreg[ti][r];
+          if (VL && t >= len[bl]) {   // the length from LDS each step: four fewer registers held across the loop   // dead row: hold h and c, y = 0; the held h is the finite hprev the dW_hh GEMM reads
+            hx[bl * HB + j] = f2bf(hp);
+            if (rok[r]) {
+              p.out[row[r] * a.ldo + j] = 0.f;
+              if (a.save) p.hprev[row[r] * H + j] = hp;
+            }
+            continue;
+          }
+          // spelled out, as in lstm_seq_bwd_kernel: the VL and the fixed instantiation must not differ in what they fuse
+          const float c = __builtin_fmaf(fg, creg[ti][r], ig * gg);
+          const float h = og * tanhf(c);
+          creg[ti][r] = jok ? c : 0.f;
+          hreg[ti][r] = jok ? h : 0.f;
+          hx[bl * HB + j] = jok ? f2bf(h) : (bf16_t)0;   // columns H .. Hp stay zero: reduction padding of the next step
+          if (rok[r]) {
+            p.out[row[r] * a.ldo + j] = h;
+            if (a.save) {
+              float* gp = p.gates + row[r] * G4 + j;
+              gp[0] = ig; gp[H] = fg; gp[2 * H] = gg; gp[3 * H] = og;
+              p.csave[row[r] * H + j] = c;
+              p.hprev[row[r] * H + j] = hp;
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int ti = 0; ti < NT; ++ti) {
+    const int j = (wave + ti * LSTM_WAVES) * 16 + i16;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int b = b0 + g4 * 4 + r;
+      if (j < H && b < B) {
+        if (p.hn) p.hn[(size_t)b * H + j] = hreg[ti][r];
+        if (p.cn) p.cn[(size_t)b * H + j] = creg[ti][r];
+      }
+    }
+  }
+}
+
+template <int NT, int KR, int REST, bool VL>
+__global__ __launch_bounds__(LSTM_THREADS) void lstm_seq_bwd_bf16_kernel(LstmBwdArgs a) {
+  extern __shared__ float lstm_lds[];
+  const LstmBwdDir& p = a.d[blockIdx.y];
+  const int H = a.H, Hp = (H + 15) & ~15, KS = Hp >> 3, GB = 4 * Hp + 8, B = a.B, T = a.T;   // 4 Hp = 32 KS exactly
+  const int rest = KS > KR ? KS - KR : 0;
+  bf16_t* dgs = reinterpret_cast<bf16_t*>(lstm_lds);          // [16][GB]: bf(gate gradients) of the step, gate g at g Hp
+  int* len = reinterpret_cast<int*>(dgs + LSTM_ROWS * GB);    // [16]
+  u32x4* wl = reinterpret_cast<u32x4*>(len + LSTM_ROWS);      // REST == 1: [tile][rest][64] B fragments
+  const u32x4* wg = a.w_pack[blockIdx.y];                     // all of bf(W_hh)^T as B fragments
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i16 = lane & 15, g4 = lane >> 4;
+  const int b0 = blockIdx.x * LSTM_ROWS;
+
+  for (int e = tid; e < LSTM_ROWS * GB; e += LSTM_THREADS) dgs[e] = 0;
+  if (VL) load_slice_lengths(len, a.lengths, b0, B, T);
+  u32x4 wr[NT][KR];   // this wave's tiles of dh, K-steps 0 .. KR-1, for all T steps
+  float dhreg[NT][4], dcreg[NT][4];
+#pragma unroll
+  for (int ti = 0; ti < NT; ++ti) {
+    const int kt = wave + ti * LSTM_WAVES, k = kt * 16 + i16;
+#pragma unroll
+    for (int ks = 0; ks < KR; ++ks) wr[ti][ks] = wg[kt * 16 < Hp && ks < KS ? (kt * KS + ks) * 64 + lane : lane];
+    if (REST == 1 && kt * 16 < Hp)
+      for (int ks = KR; ks < KS; ++ks) wl[(kt * rest + ks - KR) * 64 + lane] = wg[(kt * KS + ks) * 64 + lane];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int b = b0 + g4 * 4 + r;
+      const bool ok = k < H && b < B;
+      dhreg[ti][r] = ok && p.dhn ? p.dhn[(size_t)b * H + k] : 0.f;
+      dcreg[ti][r] = ok && p.dcn ? p.dcn[(size_t)b * H + k] : 0.f;
+    }
+  }
+  __syncthreads();
+  const int tmax = VL ? slice_tmax(len) : T;   // the steps the forward executed: uniform over the workgroup
+  int lr[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) lr[r] = VL ? len[g4 * 4 + r] : T;
+
+  const int G4 = 4 * H;
+  if (VL) {   // steps tmax .. T-1 of the slice: the GEMMs after this kernel read all B T rows of dgates
+    const int nb = B - b0 < LSTM_ROWS ? B - b0 : LSTM_ROWS;
+    for (int e = tid; e < (T - tmax) * nb * G4; e += LSTM_THREADS) {
+      const int tt = tmax + e / (nb * G4), q = e % (nb * G4), b = b0 + q / G4, n = q % G4;
+      p.dgates[seq_row(b, tt, B, T, a.batch_first) * G4 + n] = 0.f;
+    }
+  }
+  for (int s = 0; s < tmax; ++s) {
+    const int t = p.reverse ? s : tmax - 1 - s;       // the forward walk, backwards
+    const bool first = s == tmax - 1;                 // (fixed lengths) the forward's first step: c_{t-1} = c0
+    const int tp = p.reverse ? t + 1 : t - 1;
+#pragma unroll
+    for (int ti = 0; ti < NT; ++ti) {
+      const int ht = wave + ti * LSTM_WAVES;
+      if (ht * 16 < Hp) {
+        int j = ht * 16 + i16;
+        asm volatile("" : "+v"(j));   // as in the forward: no per-tile pointers kept across steps
+        const bool jok = j < H;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int bl = g4 * 4 + r, b = b0 + bl;
+          float di = 0.f, df = 0.f, dg = 0.f, dop = 0.f, dcp = 0.f;
+          const bool live = !VL || t < lr[r];   // a dead row runs the same arithmetic and drops it (see lstm_seq_bwd_kernel)
+          if (jok && b < B) {
+            // the lane-local cell block of lstm_seq_bwd_kernel, contraction pinned the same way
+#pragma clang fp contract(off)
+            const size_t row = seq_row(b, t, B, T, a.batch_first);
+            const float* gp = p.gates + row * G4 + j;
+            const float ig = gp[0], fg = gp[H], gg = gp[2 * H], og = gp[3 * H];
+            const float c = p.csave[row * H + j];
+            const bool rfirst = VL ? (!live || (p.reverse ? t == lr[r] - 1 : t == 0)) : first;
+            const float cp = rfirst ? (p.c0 ? p.c0[(size_t)b * H + j] : 0.f)
+                                    : p.csave[seq_row(b, tp, B, T, a.batch_first) * H + j];
+            const float dh = (p.dy ? p.dy[row * a.ldo + j] : 0.f) + dhreg[ti][r];
+            const float tc = tanhf(c);
+            const float dc = __builtin_fmaf(dh * og, __builtin_fmaf(-tc, tc, 1.f), dcreg[ti][r]);
+            dop = dh * tc * og * (1.f - og);
+            di = dc * gg * ig * (1.f - ig);
+            df = dc * cp * fg * (1.f - fg);
+            dg = dc * ig * (1.f - gg * gg);
+            dcp = dc * fg;
+            if (VL) {   // dead row: exact-zero gate gradients, the dc carry kept (dh: below); dy there is not used
+              di = live ? di : 0.f; df = live ? df : 0.f; dg = live ? dg : 0.f; dop = live ? dop : 0.f;
+              dcp = live ? dcp : dcreg[ti][r];
+            }
+            float* dq = p.dgates + row * G4 + j;
+            dq[0] = di; dq[H] = df; dq[2 * H] = dg; dq[3 * H] = dop;   // the unrounded gradients
+          }
+          dcreg[ti][r] = dcp;
+          bf16_t* ds = dgs + bl * GB + j;
+          ds[0] = f2bf(di); ds[Hp] = f2bf(df); ds[2 * Hp] = f2bf(dg); ds[3 * Hp] = f2bf(dop);
+        }
+      }
+    }
+    __syncthreads();
+    // dh_{t-1}[b][k] = sum_n bf(dgates[b][n]) bf(W_hh[n][k]): this wave's tiles of k, the same tiles it owns above
+#pragma unroll
+    for (int ti = 0; ti < NT; ++ti) {
+      const int kt = wave + ti * LSTM_WAVES;
+      if (kt * 16 < Hp) {
+        f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};   // even and odd K-steps
+        const bf16_t* da = dgs + i16 * GB + 8 * g4;
+#pragma unroll
+        for (int ks = 0; ks < KR; ++ks)
+          if (ks < KS) acc[ks & 1] = mfma_bf16(*reinterpret_cast<const u32x4*>(da + ks * 32), wr[ti][ks], acc[ks & 1]);
+        if (REST != 0) {
+          static_assert(KR % 2 == 0, "even and odd K-steps keep their accumulators");
+          const u32x4* wp = REST == 1 ? wl + (kt * rest - KR) * 64 + lane : wg + (kt * KS) * 64 + lane;
+          for (int ks = KR; ks < KS; ks += 2) {   // KS is even
+            acc[0] = mfma_bf16(*reinterpret_cast<const u32x4*>(da + ks * 32), wp[ks * 64], acc[0]);
+            acc[1] = mfma_bf16(*reinterpret_cast<const u32x4*>(da + ks * 32 + 32), wp[ks * 64 + 64], acc[1]);
+          }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (!VL || t < lr[r]) dhreg[ti][r] = acc[0][r] + acc[1][r];   // a dead row keeps its dh carry
+      }
+    }
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int ti = 0; ti < NT; ++ti) {
+    const int k = (wave + ti * LSTM_WAVES) * 16 + i16;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int b = b0 + g4 * 4 + r;
+      if (k < H && b < B) {
+        if (p.dh0) p.dh0[(size_t)b * H + k] = dhreg[ti][r];
+        if (p.dc0) p.dc0[(size_t)b * H + k] = dcreg[ti][r];
+      }
+    }
+  }
+}
+
 // out[b][c] = sum_{t < len_b} x[b][t][c] / len_b, t in order; one thread per (b, c), consecutive c in a wave
 __global__ __launch_bounds__(256) void seq_mean_varlen_fwd_kernel(const float* __restrict__ x, const int* __restrict__ lengths,
                                                                   float* __restrict__ out, int T, int C) {
@@ -412,9 +781,49 @@ struct FwdLayout {
   float* csave[LSTM_MAX_LAYERS][2];
   float* hprev[LSTM_MAX_LAYERS][2];
   float* out[LSTM_MAX_LAYERS];   // outputs of layers 0 .. L-2 (the last layer writes y)
+  u32x4* wpack[LSTM_MAX_LAYERS][2];   // bf16 only: W_hh as B fragments, behind everything else
+  size_t wpack_each;
   size_t bytes;
 };
-FwdLayout fwd_layout(const ecgmm_lstm_desc* d, void* ws) {
+
+// ---- bf16 instantiations per range of H ------------------------------------------------------------------------------------
+// NT tiles per wave, KR K-steps of each tile in registers, REST: where the other K-steps are (0 none, 1 LDS, 2 streamed copy).
+struct Bf16Cfg { int nt, kr, rest; size_t lds, pack_bytes; };
+Bf16Cfg bf16_fwd_cfg(int H) {
+  const int Hp = (H + 15) & ~15, tiles = Hp >> 4, KS = (Hp + 31) >> 5;
+  Bf16Cfg c;
+  int kr1;   // as the kernel's KR1
+  if (tiles <= 8) { c = {1, 4, 0, 0, 0}; kr1 = 4; }            // H <= 128: KS <= 4, all of W_hh in registers
+  else if (tiles <= 13) { c = {2, 5, 1, 0, 0}; kr1 = 4; }      // H <= 208: K-steps 5, 6 (tiles 8 ..: 4, 5, 6) in LDS, 124 KiB at 13
+  else if (tiles <= 16) { c = {2, 5, 2, 0, 0}; kr1 = 4; }      // H <= 256
+  else { c = {3, 3, 2, 0, 0}; kr1 = 2; }                       // H <= 384
+  const int rest0 = KS > c.kr ? KS - c.kr : 0, rest1 = KS > kr1 ? KS - kr1 : 0;
+  const int slots = tiles <= LSTM_WAVES ? tiles * rest0 : LSTM_WAVES * rest0 + (tiles - LSTM_WAVES) * rest1;
+  c.lds = (size_t)2 * LSTM_ROWS * (KS * 32 + 8) * sizeof(bf16_t) + LSTM_ROWS * sizeof(int) +
+          (c.rest == 1 ? (size_t)slots * 4 * 64 * sizeof(u32x4) : 0);
+  c.pack_bytes = (size_t)tiles * KS * 4 * 64 * sizeof(u32x4);
+  return c;
+}
+Bf16Cfg bf16_bwd_cfg(int H) {
+  const int Hp = (H + 15) & ~15, tiles = Hp >> 4, KS = Hp >> 3;
+  Bf16Cfg c;
+  if (tiles <= 8) c = {1, 16, 0, 0, 0};           // H <= 128: KS <= 16
+  else if (tiles <= 13) c = {2, 16, 1, 0, 0};     // H <= 208: K-steps 16 .. 25 in LDS (130 KiB at 13 tiles)
+  else if (tiles <= 16) c = {2, 16, 2, 0, 0};
+  else c = {3, 10, 2, 0, 0};
+  const int rest = KS > c.kr ? KS - c.kr : 0;
+  c.lds = (size_t)LSTM_ROWS * (4 * Hp + 8) * sizeof(bf16_t) + LSTM_ROWS * sizeof(int) +
+          (c.rest == 1 ? (size_t)tiles * rest * 64 * sizeof(u32x4) : 0);
+  c.pack_bytes = (size_t)tiles * KS * 64 * sizeof(u32x4);
+  return c;
+}
+int check_dtype(int dtype, const char* what) {
+  if (dtype != ECGMM_F32 && dtype != ECGMM_BF16)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "%s: compute dtype %d is neither ECGMM_F32 nor ECGMM_BF16", what, dtype);
+  return 0;
+}
+
+FwdLayout fwd_layout(const ecgmm_lstm_desc* d, void* ws, int dtype = ECGMM_F32) {
   FwdLayout f;
   memset(&f, 0, sizeof(f));
   Arena ar(ws);
@@ -439,6 +848,11 @@ FwdLayout fwd_layout(const ecgmm_lstm_desc* d, void* ws) {
       if (l < L - 1) f.out[l] = pp[l & 1];
     }
   }
+  if (dtype == ECGMM_BF16 && bf16_fwd_cfg(d->H).pack_bytes) {
+    f.wpack_each = bf16_fwd_cfg(d->H).pack_bytes;
+    for (int l = 0; l < L; ++l)
+      for (int k = 0; k < D; ++k) f.wpack[l][k] = static_cast<u32x4*>(ar.take_bytes(f.wpack_each));
+  }
   f.bytes = align_up(ar.off, 256);
   return f;
 }
@@ -448,9 +862,11 @@ struct BwdLayout {
   float* dyb[2];
   float* dxtmp;
   void* lin;
+  u32x4* wpack[LSTM_MAX_LAYERS][2];   // bf16 only: W_hh^T as B fragments, behind everything else
+  size_t wpack_each;
   size_t lin_bytes, bytes;
 };
-BwdLayout bwd_layout(const ecgmm_lstm_desc* d, void* scratch) {
+BwdLayout bwd_layout(const ecgmm_lstm_desc* d, void* scratch, int dtype = ECGMM_F32) {
   BwdLayout b;
   memset(&b, 0, sizeof(b));
   Arena ar(scratch);
@@ -466,6 +882,11 @@ BwdLayout bwd_layout(const ecgmm_lstm_desc* d, void* scratch) {
   if (ecg_linear_bwd_scratch(rows, H, 4 * H) > lin) lin = ecg_linear_bwd_scratch(rows, H, 4 * H);
   b.lin_bytes = lin;
   b.lin = ar.take_bytes(lin);
+  if (dtype == ECGMM_BF16 && bf16_bwd_cfg(H).pack_bytes) {
+    b.wpack_each = bf16_bwd_cfg(H).pack_bytes;
+    for (int l = 0; l < L; ++l)
+      for (int k = 0; k < D; ++k) b.wpack[l][k] = static_cast<u32x4*>(ar.take_bytes(b.wpack_each));
+  }
   b.bytes = align_up(ar.off, 256);
   return b;
 }
@@ -480,29 +901,96 @@ void set_lds_attrs() {
   lds_attr_done = true;
 }
 
+template <typename A> using SeqKernel = void (*)(A);
+template <typename A> void launch_seq(SeqKernel<A> kernel, dim3 grid, size_t lds, hipStream_t s, const A& a) {
+  // once per kernel would do; the call is a host-side table write and keeps the launchers free of state
+  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipLaunchKernelGGL(kernel, grid, dim3(LSTM_THREADS), lds, s, a);
+}
+template <bool VL> void launch_fwd_bf16(const Bf16Cfg& c, dim3 grid, hipStream_t s, const LstmFwdArgs& a) {
+  if (c.nt == 1) launch_seq<LstmFwdArgs>(lstm_seq_fwd_bf16_kernel<1, 4, 4, 0, VL>, grid, c.lds, s, a);
+  else if (c.nt == 2 && c.rest == 1) launch_seq<LstmFwdArgs>(lstm_seq_fwd_bf16_kernel<2, 5, 4, 1, VL>, grid, c.lds, s, a);
+  else if (c.nt == 2) launch_seq<LstmFwdArgs>(lstm_seq_fwd_bf16_kernel<2, 5, 4, 2, VL>, grid, c.lds, s, a);
+  else launch_seq<LstmFwdArgs>(lstm_seq_fwd_bf16_kernel<3, 3, 2, 2, VL>, grid, c.lds, s, a);
+}
+template <bool VL> void launch_bwd_bf16(const Bf16Cfg& c, dim3 grid, hipStream_t s, const LstmBwdArgs& a) {
+  if (c.nt == 1) launch_seq<LstmBwdArgs>(lstm_seq_bwd_bf16_kernel<1, 16, 0, VL>, grid, c.lds, s, a);
+  else if (c.nt == 2 && c.rest == 1) launch_seq<LstmBwdArgs>(lstm_seq_bwd_bf16_kernel<2, 16, 1, VL>, grid, c.lds, s, a);
+  else if (c.nt == 2) launch_seq<LstmBwdArgs>(lstm_seq_bwd_bf16_kernel<2, 16, 2, VL>, grid, c.lds, s, a);
+  else launch_seq<LstmBwdArgs>(lstm_seq_bwd_bf16_kernel<3, 10, 2, VL>, grid, c.lds, s, a);
+}
+// one launch per call: every layer's and direction's W_hh into its streamed bf16 copy
+int pack_whh(const ecgmm_lstm_desc* d, const float* const* params, u32x4* const (*dst)[2], int transposed, hipStream_t s) {
+  const int D = d->bidirectional ? 2 : 1, L = d->layers;
+  LstmPackArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.H = d->H; pa.transposed = transposed;
+  for (int l = 0; l < L; ++l)
+    for (int k = 0; k < D; ++k) {
+      pa.w[l * D + k] = params[(size_t)(l * D + k) * 4 + 1];
+      pa.dst[l * D + k] = dst[l][k];
+      if (!pa.w[l * D + k]) ECG_FAIL(ECGMM_ERR_SHAPE, "lstm: null W_hh (layer %d)", l);
+    }
+  hipLaunchKernelGGL(pack_whh_bf16_kernel, dim3(64, L * D), dim3(256), 0, s, pa);
+  ECG_CHECK_LAUNCH("pack_whh_bf16");
+  return 0;
+}
+
 }  // namespace
 
-size_t ecg_lstm_fwd_workspace(const ecgmm_lstm_desc* d) {
-  if (check_desc(d, "lstm_fwd_workspace") != 0) return 0;
-  return fwd_layout(d, nullptr).bytes;
+size_t ecg_lstm_fwd_workspace(const ecgmm_lstm_desc* d, int dtype) {
+  if (check_desc(d, "lstm_fwd_workspace") != 0 || check_dtype(dtype, "lstm_fwd_workspace") != 0) return 0;
+  return fwd_layout(d, nullptr, dtype).bytes;
 }
-size_t ecg_lstm_bwd_workspace(const ecgmm_lstm_desc* d) {
-  if (check_desc(d, "lstm_bwd_workspace") != 0) return 0;
-  return bwd_layout(d, nullptr).bytes;
+size_t ecg_lstm_bwd_workspace(const ecgmm_lstm_desc* d, int dtype) {
+  if (check_desc(d, "lstm_bwd_workspace") != 0 || check_dtype(dtype, "lstm_bwd_workspace") != 0) return 0;
+  return bwd_layout(d, nullptr, dtype).bytes;
 }
 
-int ecg_lstm_forward(const ecgmm_lstm_desc* d, const float* x, const int* lengths, const float* const* params,
+int ecg_lstm_ws_view(const ecgmm_lstm_desc* d, int dtype, const char* which, int layer, int direction, size_t* offset,
+                     size_t* bytes) {
+  ECG_TRY(check_desc(d, "lstm_ws_view"));
+  ECG_TRY(check_dtype(dtype, "lstm_ws_view"));
+  const int D = d->bidirectional ? 2 : 1;
+  if (!which || !offset || !bytes) ECG_FAIL(ECGMM_ERR_SHAPE, "lstm_ws_view: null argument");
+  if (layer < 0 || layer >= d->layers || direction < 0 || direction >= D)
+    ECG_FAIL(ECGMM_ERR_SHAPE, "lstm_ws_view: layer %d / direction %d outside %d x %d", layer, direction, d->layers, D);
+  const size_t BT = (size_t)d->B * d->T, H = d->H;
+  // the layouts over a base that is never dereferenced (over a null base the arena hands out null pointers)
+  unsigned char* const base = reinterpret_cast<unsigned char*>((uintptr_t)1 << 20);
+  const FwdLayout f = fwd_layout(d, base, dtype);
+  const BwdLayout w = bwd_layout(d, base, dtype);
+  const void* at = nullptr;
+  bool found = true;
+  if (!strcmp(which, "dgates")) { at = w.dgates[direction]; *bytes = BT * 4 * H * sizeof(float); }
+  else if (!d->save_for_backward) ECG_FAIL(ECGMM_ERR_SHAPE, "lstm_ws_view: %s is kept only with save_for_backward = 1", which);
+  else if (!strcmp(which, "gates")) { at = f.gates[layer][direction]; *bytes = BT * 4 * H * sizeof(float); }
+  else if (!strcmp(which, "c")) { at = f.csave[layer][direction]; *bytes = BT * H * sizeof(float); }
+  else if (!strcmp(which, "hprev")) { at = f.hprev[layer][direction]; *bytes = BT * H * sizeof(float); }
+  else if (!strcmp(which, "out")) {
+    if (layer == d->layers - 1) ECG_FAIL(ECGMM_ERR_SHAPE, "lstm_ws_view: the last layer's output is y, not in the workspace");
+    at = f.out[layer]; *bytes = BT * D * H * sizeof(float);   // both directions side by side
+  } else found = false;
+  if (!found) ECG_FAIL(ECGMM_ERR_SHAPE, "lstm_ws_view: unknown view '%s' (gates, c, hprev, out, dgates)", which);
+  *offset = (size_t)(static_cast<const unsigned char*>(at) - base);
+  return 0;
+}
+
+int ecg_lstm_forward(const ecgmm_lstm_desc* d, int dtype, const float* x, const int* lengths, const float* const* params,
                      const float* h0, const float* c0, float* y, float* hn, float* cn, void* ws, size_t ws_bytes,
                      hipStream_t s) {
   ECG_TRY(check_desc(d, "lstm_forward"));
+  ECG_TRY(check_dtype(dtype, "lstm_forward"));
   if (!x || !params || !y) ECG_FAIL(ECGMM_ERR_SHAPE, "lstm_forward: x, params and y must not be null");
-  const FwdLayout f = fwd_layout(d, ws);
+  const FwdLayout f = fwd_layout(d, ws, dtype);
   if (!ws || ws_bytes < f.bytes)
     ECG_FAIL(ECGMM_ERR_WORKSPACE, "lstm_forward: workspace %zu bytes, need %zu", ws_bytes, f.bytes);
   const int D = d->bidirectional ? 2 : 1, L = d->layers, H = d->H, B = d->B, T = d->T;
   const int rows = B * T;
   const size_t BH = (size_t)B * H;
   set_lds_attrs();
+  const Bf16Cfg bc = bf16_fwd_cfg(H);
+  if (dtype == ECGMM_BF16 && bc.pack_bytes) ECG_TRY(pack_whh(d, params, f.wpack, 0, s));
   for (int l = 0; l < L; ++l) {
     const float* in = l == 0 ? x : f.out[l - 1];
     const int In = l == 0 ? d->In : D * H;
@@ -525,9 +1013,16 @@ int ecg_lstm_forward(const ecgmm_lstm_desc* d, const float* x, const int* length
       q.hn = hn ? hn + (size_t)(l * D + k) * BH : nullptr;
       q.cn = cn ? cn + (size_t)(l * D + k) * BH : nullptr;
       q.reverse = k;
+      a.w_pack[k] = f.wpack[l][k];
       v4 = v4 && ((uintptr_t)pr[1] & 15) == 0;
     }
     const dim3 grid(ceil_div(B, LSTM_ROWS), D);
+    if (dtype == ECGMM_BF16) {
+      if (lengths) launch_fwd_bf16<true>(bc, grid, s, a);
+      else launch_fwd_bf16<false>(bc, grid, s, a);
+      ECG_CHECK_LAUNCH("lstm_seq_fwd_bf16");
+      continue;
+    }
     // 2 (4H x H) FLOPs per batch row and step; W_hh once per step and slice from L2 (not HBM: 0 algorithmic bytes beyond
     // the projections, the saved tensors and the output)
     if (lengths) {
@@ -540,15 +1035,16 @@ int ecg_lstm_forward(const ecgmm_lstm_desc* d, const float* x, const int* length
   return 0;
 }
 
-int ecg_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const int* lengths, const float* const* params,
+int ecg_lstm_backward(const ecgmm_lstm_desc* d, int dtype, const float* x, const int* lengths, const float* const* params,
                       const float* h0, const float* c0, const float* dy, const float* dhn, const float* dcn, const void* ws,
                       float* dx, float* const* grads, float* dh0, float* dc0, void* scratch, size_t scratch_bytes,
                       hipStream_t s) {
   ECG_TRY(check_desc(d, "lstm_backward"));
+  ECG_TRY(check_dtype(dtype, "lstm_backward"));
   if (!d->save_for_backward) ECG_FAIL(ECGMM_ERR_SHAPE, "lstm_backward: the forward ran with save_for_backward = 0");
   if (!x || !params || !ws) ECG_FAIL(ECGMM_ERR_SHAPE, "lstm_backward: x, params and the forward workspace must not be null");
-  const FwdLayout f = fwd_layout(d, const_cast<void*>(ws));   // read only
-  const BwdLayout w = bwd_layout(d, scratch);
+  const FwdLayout f = fwd_layout(d, const_cast<void*>(ws), dtype);   // read only
+  const BwdLayout w = bwd_layout(d, scratch, dtype);
   if (!scratch || scratch_bytes < w.bytes)
     ECG_FAIL(ECGMM_ERR_WORKSPACE, "lstm_backward: scratch %zu bytes, need %zu", scratch_bytes, w.bytes);
   const int D = d->bidirectional ? 2 : 1, L = d->layers, H = d->H, B = d->B, T = d->T;
@@ -556,6 +1052,8 @@ int ecg_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const int* lengt
   const size_t BH = (size_t)B * H;
   (void)h0;   // h_{t-1} of every step, h0 included, is in the forward workspace
   set_lds_attrs();
+  const Bf16Cfg bc = bf16_bwd_cfg(H);
+  if (dtype == ECGMM_BF16 && bc.pack_bytes) ECG_TRY(pack_whh(d, params, w.wpack, 1, s));
   for (int l = L - 1; l >= 0; --l) {
     const float* in = l == 0 ? x : f.out[l - 1];
     const int In = l == 0 ? d->In : D * H;
@@ -578,9 +1076,13 @@ int ecg_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const int* lengt
       q.dh0 = dh0 ? dh0 + (size_t)(l * D + k) * BH : nullptr;
       q.dc0 = dc0 ? dc0 + (size_t)(l * D + k) * BH : nullptr;
       q.reverse = k;
+      a.w_pack[k] = w.wpack[l][k];
     }
     const dim3 grid(ceil_div(B, LSTM_ROWS), D);
-    if (lengths) hipLaunchKernelGGL(lstm_seq_bwd_kernel<true>, grid, dim3(LSTM_THREADS), bwd_lds(H, true), s, a);
+    if (dtype == ECGMM_BF16) {
+      if (lengths) launch_bwd_bf16<true>(bc, grid, s, a);
+      else launch_bwd_bf16<false>(bc, grid, s, a);
+    } else if (lengths) hipLaunchKernelGGL(lstm_seq_bwd_kernel<true>, grid, dim3(LSTM_THREADS), bwd_lds(H, true), s, a);
     else hipLaunchKernelGGL(lstm_seq_bwd_kernel<false>, grid, dim3(LSTM_THREADS), bwd_lds(H), s, a);
     ECG_CHECK_LAUNCH("lstm_seq_bwd");
     float* dst = l > 0 ? w.dyb[l & 1] : dx;   // dx of layer l is the dy of layer l - 1

@@ -256,13 +256,16 @@ int ecg_linear_bwd(const float* dz, const float* x, const float* w, float* dx, f
                    int Out, void* scratch, size_t scratch_bytes, hipStream_t s);
 
 // lstm.hip: nn.LSTM plans (projection GEMMs through ecg_linear_*, the recurrence on lstm_seq_fwd / lstm_seq_bwd kernels)
-size_t ecg_lstm_fwd_workspace(const ecgmm_lstm_desc* d);
-size_t ecg_lstm_bwd_workspace(const ecgmm_lstm_desc* d);
+// dtype: ECGMM_F32 (the exact-fp32 recurrence) or ECGMM_BF16 (recurrent products on bf16 operands, W_hh held on chip)
+size_t ecg_lstm_fwd_workspace(const ecgmm_lstm_desc* d, int dtype);
+size_t ecg_lstm_bwd_workspace(const ecgmm_lstm_desc* d, int dtype);
+int ecg_lstm_ws_view(const ecgmm_lstm_desc* d, int dtype, const char* which, int layer, int direction, size_t* offset,
+                     size_t* bytes);
 // lengths: device int32 [B] or null (null: the fixed-length kernels, the code of before there were lengths)
-int ecg_lstm_forward(const ecgmm_lstm_desc* d, const float* x, const int* lengths, const float* const* params,
+int ecg_lstm_forward(const ecgmm_lstm_desc* d, int dtype, const float* x, const int* lengths, const float* const* params,
                      const float* h0, const float* c0, float* y, float* hn, float* cn, void* ws, size_t ws_bytes,
                      hipStream_t s);
-int ecg_lstm_backward(const ecgmm_lstm_desc* d, const float* x, const int* lengths, const float* const* params,
+int ecg_lstm_backward(const ecgmm_lstm_desc* d, int dtype, const float* x, const int* lengths, const float* const* params,
                       const float* h0, const float* c0, const float* dy, const float* dhn, const float* dcn, const void* ws,
                       float* dx, float* const* grads, float* dh0, float* dc0, void* scratch, size_t scratch_bytes,
                       hipStream_t s);

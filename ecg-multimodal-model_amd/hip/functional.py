@@ -468,15 +468,27 @@ def check_lengths(lengths, B, T):
     return t.to(torch.int32)
 
 
+def _lstm_dtype_code(name):
+    """``"fp32"`` / ``"bf16"`` -> the library's dtype code (``ValueError`` otherwise)"""
+    key = str(name).lower()
+    if key not in ("fp32", "bf16"):
+        raise ValueError(f"lstm: compute_dtype must be 'fp32' or 'bf16', got {name!r}")
+    return L.BF16 if key == "bf16" else L.F32
+
+
 class LSTMFn(torch.autograd.Function):
     """y, h_n, c_n = LSTM(x, h0, c0; params).  ``params`` in torch's ``_flat_weights`` order (per layer, per direction:
     w_ih, w_hh, b_ih, b_hh).  The forward keeps its workspace (activated gates, c_t, h_{t-1}) on ``ctx`` only when some
     input requires grad; the backward reads it and writes parameter gradients into their sinks.  ``cfg`` may carry a fifth
-    entry, the device ``int32 [B]`` lengths (or ``None``): the ``_varlen`` entry points, else the fixed ones."""
+    entry, the device ``int32 [B]`` lengths (or ``None``): the ``_varlen`` entry points, else the fixed ones; and a sixth,
+    the compute dtype code of the recurrence: ``ECGMM_BF16`` goes through the ``_dt`` entry points, fp32 through the ones
+    it always went through."""
 
     @staticmethod
     def forward(ctx, x, h0, c0, cfg, *params):
-        hidden, layers, bidirectional, batch_first, lengths = (tuple(cfg) + (None,))[:5]
+        hidden, layers, bidirectional, batch_first = tuple(cfg)[:4]
+        lengths = cfg[4] if len(cfg) > 4 else None
+        dt = cfg[5] if len(cfg) > 5 else L.F32
         _require_cuda(x, "lstm")
         for t in (h0, c0) + params:
             if t is not None:
@@ -500,7 +512,7 @@ class LSTMFn(torch.autograd.Function):
         save = any(ctx.needs_input_grad)
         desc = L.LSTMDesc(B, T, In, hidden, layers, int(bidirectional), int(batch_first), int(save))
         lib = L.lib()
-        nb = lib.ecgmm_lstm_fwd_workspace(C.byref(desc))
+        nb = lib.ecgmm_lstm_fwd_workspace_dt(C.byref(desc), dt) if dt != L.F32 else lib.ecgmm_lstm_fwd_workspace(C.byref(desc))
         if nb == 0:
             raise RuntimeError("ecgmm lstm: " + lib.ecgmm_last_error().decode(errors="replace"))
         ws = new_bytes(nb, x.device) if save else _Scratch.get("lstm_fwd", nb, x.device)
@@ -508,18 +520,22 @@ class LSTMFn(torch.autograd.Function):
         y = torch.empty(yshape, device=x.device, dtype=torch.float32)
         hn = torch.empty(layers * D, B, hidden, device=x.device, dtype=torch.float32)
         cn = torch.empty_like(hn)
-        if lengths is None:
-            L.check(lib.ecgmm_lstm_forward(C.byref(desc), ptr(x), _ptr_table(params), ptr(h0), ptr(c0), ptr(y), ptr(hn),
-                                           ptr(cn), ptr(ws), ws.numel(), stream()), "lstm_forward")
-        else:
+        if lengths is not None:
             if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,) or lengths.device != x.device:
                 raise RuntimeError(f"lstm: lengths must be int32 [{B}] on {x.device} (HF.check_lengths)")
             lengths = lengths.contiguous()
+        if dt != L.F32:
+            L.check(lib.ecgmm_lstm_forward_dt(C.byref(desc), dt, ptr(x), ptr(lengths), _ptr_table(params), ptr(h0), ptr(c0),
+                                              ptr(y), ptr(hn), ptr(cn), ptr(ws), ws.numel(), stream()), "lstm_forward_dt")
+        elif lengths is None:
+            L.check(lib.ecgmm_lstm_forward(C.byref(desc), ptr(x), _ptr_table(params), ptr(h0), ptr(c0), ptr(y), ptr(hn),
+                                           ptr(cn), ptr(ws), ws.numel(), stream()), "lstm_forward")
+        else:
             L.check(lib.ecgmm_lstm_forward_varlen(C.byref(desc), ptr(x), ptr(lengths), _ptr_table(params), ptr(h0),
                                                   ptr(c0), ptr(y), ptr(hn), ptr(cn), ptr(ws), ws.numel(), stream()),
                     "lstm_forward_varlen")
         if save:
-            ctx.desc, ctx.ws, ctx.params, ctx.lengths = desc, ws, params, lengths
+            ctx.desc, ctx.ws, ctx.params, ctx.lengths, ctx.dt = desc, ws, params, lengths, dt
             ctx.save_for_backward(x, h0, c0)
             ctx.set_materialize_grads(False)
         return y, hn, cn
@@ -536,9 +552,15 @@ class LSTMFn(torch.autograd.Function):
         # sinks only for the gradients this backward was asked for (torch.autograd.grad w.r.t. inputs leaves .grad alone)
         sinks = [grad_sink(p) if need[4 + i] and _grad_wanted(p) else None for i, p in enumerate(params)]
         lib = L.lib()
-        nb = lib.ecgmm_lstm_bwd_workspace(C.byref(desc))
+        dt = ctx.dt
+        nb = lib.ecgmm_lstm_bwd_workspace_dt(C.byref(desc), dt) if dt != L.F32 else lib.ecgmm_lstm_bwd_workspace(C.byref(desc))
         scratch = _Scratch.get("lstm_bwd", nb, x.device)
-        if ctx.lengths is None:
+        if dt != L.F32:
+            L.check(lib.ecgmm_lstm_backward_dt(C.byref(desc), dt, ptr(x), ptr(ctx.lengths), _ptr_table(params), ptr(h0),
+                                               ptr(c0), ptr(dy), ptr(dhn), ptr(dcn), ptr(ctx.ws), ptr(dx), _ptr_table(sinks),
+                                               ptr(dh0), ptr(dc0), ptr(scratch), scratch.numel(), stream()),
+                    "lstm_backward_dt")
+        elif ctx.lengths is None:
             L.check(lib.ecgmm_lstm_backward(C.byref(desc), ptr(x), _ptr_table(params), ptr(h0), ptr(c0), ptr(dy), ptr(dhn),
                                             ptr(dcn), ptr(ctx.ws), ptr(dx), _ptr_table(sinks), ptr(dh0), ptr(dc0),
                                             ptr(scratch), scratch.numel(), stream()), "lstm_backward")
@@ -550,8 +572,14 @@ class LSTMFn(torch.autograd.Function):
         return (dx, dh0, dc0, None) + (None,) * len(params)
 
 
-def lstm(x, hx, params, hidden_size, num_layers=1, bidirectional=False, batch_first=False, lengths=None):
+def lstm(x, hx, params, hidden_size, num_layers=1, bidirectional=False, batch_first=False, lengths=None,
+         compute_dtype="fp32"):
     """``torch.nn.LSTM`` forward (with bias, no dropout, no projection): returns ``(output, (h_n, c_n))``.
+
+    ``compute_dtype`` ``"fp32"`` (exact fp32 products, the default) or ``"bf16"``: the recurrent products ``h W_hh^T`` and
+    ``dgates W_hh`` take their operands rounded to bf16 (fp32 sums, ``W_hh`` held on chip for all steps); the input
+    projections, the gradient GEMMs, the parameters and everything stored stay fp32.  Anything else is a
+    ``ValueError``.
 
     ``lengths`` (one per batch row, see :func:`check_lengths`): ``x`` stays padded and the result is
     ``pad_packed_sequence(lstm(pack_padded_sequence(x, lengths, enforce_sorted=False), hx), total_length=T)``: the output is
@@ -560,6 +588,7 @@ def lstm(x, hx, params, hidden_size, num_layers=1, bidirectional=False, batch_fi
     runs as many serial steps as its longest row: rows ordered by length free their CUs early, but a layer still lasts as
     long as the longest slice, and no time was gained at B = 256."""
     h0, c0 = (None, None) if hx is None else hx
+    dt = _lstm_dtype_code(compute_dtype)
     cfg = (int(hidden_size), int(num_layers), bool(bidirectional), bool(batch_first))
     if lengths is not None:
         if not isinstance(x, torch.Tensor) or x.dim() != 3:
@@ -567,6 +596,8 @@ def lstm(x, hx, params, hidden_size, num_layers=1, bidirectional=False, batch_fi
         _require_cuda(x, "lstm")
         B, T = (x.shape[0], x.shape[1]) if batch_first else (x.shape[1], x.shape[0])
         cfg += (check_lengths(lengths, B, T).to(x.device),)
+    if dt != L.F32:
+        cfg = (cfg + (None,))[:5] + (dt,)
     y, hn, cn = LSTMFn.apply(x, h0, c0, cfg, *params)
     return y, (hn, cn)
 

@@ -224,6 +224,12 @@ SIGNATURES = {
     "ecgmm_lstm_forward_varlen": (i32, [P(LSTMDesc), vp, vp, P(vp), vp, vp, vp, vp, vp, vp, sz, vp]),
     "ecgmm_lstm_backward_varlen": (i32, [P(LSTMDesc), vp, vp, P(vp), vp, vp, vp, vp, vp, vp, vp, P(vp), vp, vp, vp, sz,
                                          vp]),
+    "ecgmm_lstm_fwd_workspace_dt": (sz, [P(LSTMDesc), i32]),
+    "ecgmm_lstm_bwd_workspace_dt": (sz, [P(LSTMDesc), i32]),
+    "ecgmm_lstm_forward_dt": (i32, [P(LSTMDesc), i32, vp, vp, P(vp), vp, vp, vp, vp, vp, vp, sz, vp]),
+    "ecgmm_lstm_backward_dt": (i32, [P(LSTMDesc), i32, vp, vp, P(vp), vp, vp, vp, vp, vp, vp, vp, P(vp), vp, vp, vp, sz,
+                                     vp]),
+    "ecgmm_lstm_ws_view": (i32, [P(LSTMDesc), i32, C.c_char_p, i32, i32, P(sz), P(sz)]),
     "ecgmm_seq_mean_varlen_fwd": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "ecgmm_seq_mean_varlen_bwd": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "ecgmm_conv5_in1_stats_rows": (i32, [i32, i32, i32]),
@@ -347,7 +353,10 @@ LATER_SYMBOLS = ("ecgmm_resnet18_backward_dx", "ecgmm_resnet18_gradcam", "ecgmm_
                  # TabNet's fused eval forward and masks (ecgmm.inference._TabNetPlan, csrc/tabnet_infer.hip)
                  "ecgmm_tabnet_infer_prepared_bytes", "ecgmm_tabnet_infer_prepare", "ecgmm_tabnet_infer",
                  # the encoders' Grad-CAM map kernels on their own (csrc/gradcam.hip)
-                 "ecgmm_gradcam")
+                 "ecgmm_gradcam",
+                 # the LSTM recurrence in a compute dtype (ecgmm.hip.nn.LSTM(compute_dtype=...), csrc/lstm.hip)
+                 "ecgmm_lstm_fwd_workspace_dt", "ecgmm_lstm_bwd_workspace_dt", "ecgmm_lstm_forward_dt",
+                 "ecgmm_lstm_backward_dt", "ecgmm_lstm_ws_view")
 
 _lib = None
 

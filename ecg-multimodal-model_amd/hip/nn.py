@@ -141,11 +141,15 @@ class Sequential(nn.Sequential):
 class LSTM(nn.Module):
     """``torch.nn.LSTM`` on the HIP recurrence kernels (train_physionet2.py:75-76): same parameter names, shapes,
     registration order, initialisation and state_dict keys, so checkpoints move in both directions.  Train and eval modes
-    compute the same function (there is no dropout)."""
+    compute the same function (there is no dropout).  ``compute_dtype`` (``"fp32"`` default, or ``"bf16"``: the recurrent
+    products on bf16 operands, see :func:`ecgmm.hip.functional.lstm`) is a property of the module, not of its parameters:
+    they stay fp32 and a checkpoint does not carry it."""
 
     def __init__(self, input_size, hidden_size, num_layers=1, bias=True, batch_first=False, dropout=0.0,
-                 bidirectional=False, proj_size=0):
+                 bidirectional=False, proj_size=0, compute_dtype="fp32"):
         super().__init__()
+        HF._lstm_dtype_code(compute_dtype)   # ValueError on anything but fp32 / bf16
+        self.compute_dtype = str(compute_dtype).lower()
         if dropout != 0:
             raise ValueError(f"LSTM: dropout={dropout} is not supported (only dropout=0)")
         if proj_size != 0:
@@ -183,7 +187,8 @@ class LSTM(nn.Module):
         if x.shape[2] != self.input_size:
             raise ValueError(f"LSTM: input has {x.shape[2]} features, expected input_size={self.input_size}")
         params = [getattr(self, n) for n in self._flat_names]
-        return HF.lstm(x, hx, params, self.hidden_size, self.num_layers, self.bidirectional, self.batch_first, lengths)
+        return HF.lstm(x, hx, params, self.hidden_size, self.num_layers, self.bidirectional, self.batch_first, lengths,
+                       getattr(self, "compute_dtype", "fp32"))   # a module pickled before there was one: fp32
 
     def extra_repr(self):
         return (f"{self.input_size}, {self.hidden_size}, num_layers={self.num_layers}, batch_first={self.batch_first}, "

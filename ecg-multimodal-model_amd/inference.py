@@ -147,7 +147,8 @@ class _CRNNPlan(PreparedPlan):
             lengths = HF.check_lengths(lengths, seq.shape[0], x.shape[3]).to(seq.device)
             lengths = torch.clamp(lengths // 8, 1, seq.shape[1]).to(torch.int32)
         # under no_grad nothing requires a gradient, so the LSTM keeps no saves (save = 0)
-        out, _ = HF.lstm(seq, None, self._lstm, rnn.hidden_size, rnn.num_layers, rnn.bidirectional, rnn.batch_first, lengths)
+        out, _ = HF.lstm(seq, None, self._lstm, rnn.hidden_size, rnn.num_layers, rnn.bidirectional, rnn.batch_first, lengths,
+                         getattr(rnn, "compute_dtype", "fp32"))   # the model's lstm_dtype
         w1, b1, w2, b2 = self._dense
         return HF.linear(HF.linear(HF.seq_mean(out, lengths), w1, b1, L.ACT_RELU), w2, b2)   # eval: no dropout
 

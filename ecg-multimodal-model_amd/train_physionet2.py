@@ -152,7 +152,7 @@ def evaluate(model, loader, predictor=None):
 
 
 def main(config=Config, num_epochs=None, batch_size=None, quiet=False, use_lengths=False, saliency_samples=0,
-         use_predictor=False):
+         use_predictor=False, lstm_dtype=None):
     """-> (history, {"best": metrics, "last": metrics}, checkpoint directory).  ``use_lengths`` or
     ``config.physionet2_use_lengths`` (both off by default): the CRNN gets every record's own length (module docstring).
     ``saliency_samples=k`` > 0 (or ``config.physionet2_saliency_samples``): after the test pass, with the weights it ended
@@ -161,7 +161,10 @@ def main(config=Config, num_epochs=None, batch_size=None, quiet=False, use_lengt
     ``use_predictor`` or ``config.physionet2_use_predictor`` (both off by default): the validation and test passes run
     through an ``ecgmm.inference.Predictor`` (BatchNorm-folded inference plan of the front end, no saves), refreshed after
     every training epoch and after every checkpoint load; the saliency dump keeps the model's own forward, which is what
-    a backward needs."""
+    a backward needs.
+    ``lstm_dtype`` (``None``: ``config.physionet2_lstm_dtype``, default ``"fp32"``): ``"bf16"`` runs the BiLSTM's recurrent
+    products on bf16 operands (``CRNN(lstm_dtype=...)``), in training, evaluation and the predictor alike."""
+    lstm_dtype = lstm_dtype or getattr(config, "physionet2_lstm_dtype", "fp32")
     use_lengths = bool(use_lengths or getattr(config, "physionet2_use_lengths", False))
     use_predictor = bool(use_predictor or getattr(config, "physionet2_use_predictor", False))
     saliency_samples = int(saliency_samples or getattr(config, "physionet2_saliency_samples", 0) or 0)
@@ -174,7 +177,7 @@ def main(config=Config, num_epochs=None, batch_size=None, quiet=False, use_lengt
     if not quiet:
         print(f"Using device: {device}")
     train_loader, val_loader, test_loader = get_spectrogram_dataloaders(config, batch_size, use_lengths=use_lengths)
-    model = CRNN(compute_dtype=getattr(config, "compute_dtype", "bf16")).to(device)
+    model = CRNN(compute_dtype=getattr(config, "compute_dtype", "bf16"), lstm_dtype=lstm_dtype).to(device)
     criterion = FocalLoss()
     optimizer = FusedAdam(model.parameters(), lr=config.lr)
     ckpt_dir = T.run_dir(config.checkpoint_dir)

@@ -740,6 +740,40 @@ int ecgmm_lstm_backward_varlen(const ecgmm_lstm_desc* d, const float* x, const i
                                const float* h0, const float* c0, const float* dy, const float* dhn, const float* dcn,
                                const void* ws, float* dx, float* const* grads, float* dh0, float* dc0, void* scratch,
                                size_t scratch_bytes, void* stream);
+/* The same four calls with a compute dtype for the RECURRENT products; lengths nullable (null: the fixed-length kernels).
+ * ECGMM_F32 runs exactly the code behind the entry points above: the same bits and the same workspace sizes.
+ * ECGMM_BF16 changes only the recurrent products, which run on v_mfma_f32_16x16x32_bf16 with W_hh held on chip (registers
+ * and LDS) for all T steps where it fits (H <= 208; above that part of it streams from a bf16 copy in the workspace):
+ *   forward   pre_t = P_t + b_hh + bf(h_{t-1}) bf(W_hh)^T, P_t = x_t W_ih^T + b_ih the exact-fp32 projection as above.
+ *             bf() is round-to-nearest-even to bf16; h0 is rounded as an operand the same way.  The products are exact, the
+ *             sums fp32 in the MFMA accumulator in the kernel's fixed order (K-steps of 32 ascending; K zero-padded).  The
+ *             gate functions, c_t, h_t, y, hn, cn are fp32 as above; y and the saved h_{t-1} are the UNROUNDED h; c is
+ *             never rounded.
+ *   backward  dh_{t-1} = dy_{t-1} + bf(dgates_t) bf(W_hh); the cell arithmetic is that of the fp32 kernel; the stored dgates
+ *             are the unrounded fp32 values, and dW_ih, dW_hh, dx, db are the exact-fp32 GEMMs / row sums over them, the
+ *             layer input and the saved h_{t-1}, as above (db_ih and db_hh bit-identical to each other).
+ *   lengths   the masked hold described above, unchanged: exact zeros in the padding, hn / cn after the row's last own
+ *             step, padded x finite.
+ * Two identical calls give identical bits.  The bf16 workspaces are larger than the fp32 ones by the packed bf(W_hh)
+ * (written by every call from the fp32 parameters; nothing is cached between calls).  A dtype other than the two, like H
+ * above 384, is ECGMM_ERR_SHAPE (the workspace queries return 0) with ecgmm_last_error() set. */
+size_t ecgmm_lstm_fwd_workspace_dt(const ecgmm_lstm_desc* d, int dtype);
+size_t ecgmm_lstm_bwd_workspace_dt(const ecgmm_lstm_desc* d, int dtype);
+/* train_physionet2.py:94-95: x, (h_n, c_n) = self.lstm(x), recurrence in `dtype` */
+int ecgmm_lstm_forward_dt(const ecgmm_lstm_desc* d, int dtype, const float* x, const int32_t* lengths,
+                          const float* const* params, const float* h0, const float* c0, float* y, float* hn, float* cn,
+                          void* ws, size_t ws_bytes, void* stream);
+/* train_physionet2.py:94-95: the nn.LSTM part of loss.backward(), recurrence in `dtype` (that of the forward) */
+int ecgmm_lstm_backward_dt(const ecgmm_lstm_desc* d, int dtype, const float* x, const int32_t* lengths,
+                           const float* const* params, const float* h0, const float* c0, const float* dy, const float* dhn,
+                           const float* dcn, const void* ws, float* dx, float* const* grads, float* dh0, float* dc0,
+                           void* scratch, size_t scratch_bytes, void* stream);
+/* Where a saved tensor lies (needs no GPU; for tests).  which = "gates" (activated gates [B T][4H]), "c" (c_t [B T][H]),
+ * "hprev" (h_{t-1} [B T][H]), "out" (output of layer < layers-1, [B T][D H], both directions): byte offset and size inside
+ * the forward workspace of a save_for_backward = 1 descriptor; "dgates" ([B T][4H] of `direction`): inside the backward
+ * scratch, holding the LAST layer processed (layer 0), so meaningful for single-layer calls.  Rows are ordered as x. */
+int ecgmm_lstm_ws_view(const ecgmm_lstm_desc* d, int dtype, const char* which, int layer, int direction, size_t* offset,
+                       size_t* bytes);
 /* train_physionet2.py:94-95: x.mean(dim=1) over each row's own steps: out[b,c] = sum_{t < len_b} x[b,t,c] / len_b, x [B,T,C]
  * fp32, lengths [B] device int32 clamped to [0, T]; len_b = 0 gives 0.  Any C >= 1; the sum runs t = 0, 1, ... in order. */
 int ecgmm_seq_mean_varlen_fwd(const float* x, const int32_t* lengths, float* out, int B, int T, int C, void* stream);

@@ -82,8 +82,21 @@ for name in ("bf16", "fp32"):
         with torch.no_grad():
             return net(x)
 
-    rec = measure({"a_eval": a, "b_predictor": lambda: predict(x), "c_refresh_each_call": lambda: predict.refresh()(x)})
+    # the lstm_dtype leg: the same weights with the BiLSTM's recurrence in bf16, in the same rounds
+    net_l = CRNN(compute_dtype=name, lstm_dtype="bf16").to(dev).eval()
+    net_l.load_state_dict(net.state_dict())
+    predict_l = Predictor(net_l)
+
+    def a_l():
+        with torch.no_grad():
+            return net_l(x)
+
+    rec = measure({"a_eval": a, "b_predictor": lambda: predict(x), "c_refresh_each_call": lambda: predict.refresh()(x),
+                   "a_eval_lstm_bf16": a_l, "b_predictor_lstm_bf16": lambda: predict_l(x)})
     rec["b_over_a"] = round(rec["b_predictor"]["ms"] / rec["a_eval"]["ms"], 4)
+    rec["b_lstm_bf16_over_b"] = round(rec["b_predictor_lstm_bf16"]["ms"] / rec["b_predictor"]["ms"], 4)
+    rec["lstm_bf16_logit_max_abs_diff"] = float((predict_l(x) - predict(x)).abs().max())
+    del predict_l, net_l
 
     # ---- per op, same call: block 1 fused against its two-launch chain
     params, buffers = net._front_tables()
